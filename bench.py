@@ -23,6 +23,12 @@ roofline_large: the same stage on 3x the walkers (380 MB of worldlines: beyond t
 roofline_k2 / roofline_mc: secondary figures -- K2 (slice energies of ThermEnergy) against the FP64 vector peak,
           and the device-resident sampler's bead-pair rate against K1's.
 
+A plain run sets up, warms up, times --steps steps of the headline stage and prints one JSON line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step computed
+(DIR/delta_action.npy: the Delta S of every item, float64; the inputs are seeded, so runs with the same arguments are
+comparable output for output).  Every other leg above -- roofline, roofline_large, roofline_k2 / roofline_mc, the mc
+sampler legs, cpu_baseline and the check against the oracle -- runs only with --full.
+
 N>1 (launched by torch.distributed.run): one process per GPU, walkers shard across ranks (weak
 scaling: 128 walkers per GPU), no data-path collective in the Delta-S leg; the `mc` leg ends its block with ONE
 all-reduce (RCCL) of the real block-estimator vector (energies and their squares, g(r), S(k), counters:
@@ -100,7 +106,11 @@ def cpu_baseline(cfg, VT, WF, Paths, sets, budget_s=12.0):
 
     # all host cores, one thread per core over disjoint item ranges (ctypes drops the GIL)
     import threading
-    nthr = max(1, min(os.cpu_count() or 1, 64))
+    try:                                       # the CPUs this process may use, not the whole machine's
+        ncpu = int(os.environ["OMP_NUM_THREADS"])
+    except (KeyError, ValueError):
+        ncpu = len(os.sched_getaffinity(0))
+    nthr = max(1, min(ncpu, 64))
     w, ip, ib, xnew, xold = sets[0]
     chunks = np.array_split(np.arange(len(w)), nthr)
     reps = max(1, int(4.0 * one * nthr / (len(w) * (cfg.Np - 1))))
@@ -184,7 +194,13 @@ def main():
     ap.add_argument("--no-mc", action="store_true", help="skip the device-resident sampler legs (profiling runs of K1 only)")
     ap.add_argument("--mc-steps", type=int, default=14, help="MC steps per timed leg of the device-resident sampler (>= 0.5 s at 128 walkers)")
     ap.add_argument("--mc-large-walkers", type=int, default=1024, help="walkers of the second sampler leg (0: skip)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary legs (roofline, roofline_large, mc, "
+                                                        "cpu_baseline, oracle check); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the Delta S computed by the last timed step to DIR/delta_action.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -256,6 +272,43 @@ def main():
     elapsed = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps
 
+    # what the timed path returned in its last step: the Delta S of every item of that stage
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = d_out[(args.steps - 1) % nsets].cpu().numpy().astype(np.float64)
+        np.save(os.path.join(args.dump_outputs, "delta_action.npy" if rank == 0 else "delta_action.rank%d.npy" % rank), last)
+
+    red_dev = dev if args.backend == "nccl" else torch.device("cpu")
+    if world > 1:
+        tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+
+    pair_evals_per_step = n_items * (cfg.Np - 1)
+    value = world * pair_evals_per_step * args.steps / elapsed
+    headline = {
+        "metric": "bead-pair action evals/sec (K1 Delta-S, N=256 Nb=161 4He, 128 walkers/GPU)",
+        "value": value, "unit": "bead-pair action evals/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "liquid 4He N=%d beads=%d (namelist Nb=%d), %d walkers/GPU x %d GPU(s) = %d walkers, one "
+                               "full-chain Delta-S stage per step (%d items x %d partners per GPU)"
+                               % (cfg.Np, cfg.M, cfg.Nb, W, world, W * world, n_items, cfg.Np - 1),
+                   "walkers_per_gpu": W, "global_walkers": W * world, "items_per_step": n_items,
+                   "items_per_step_global": n_items * world,
+                   "stages_per_sweep_equiv": None},
+        "kernel_only_evals_per_s": pair_evals_per_step / (kern_ms * 1e-3),
+    }
+    if not args.full:
+        ctx.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline))
+        return
+
     # per-launch durations (a pass of its own after the timed region: one event between every two launches)
     def per_launch(fn, n, stream):
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
@@ -267,14 +320,6 @@ def main():
         return [evs[i].elapsed_time(evs[i + 1]) for i in range(n)]
     k1_launches = launch_stats(per_launch(step, min(200, max(20, args.steps)), kstream))
 
-    red_dev = dev if args.backend == "nccl" else torch.device("cpu")
-    if world > 1:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
-
-    pair_evals_per_step = n_items * (cfg.Np - 1)
-    value = world * pair_evals_per_step * args.steps / elapsed
     alg_bytes = n_items * (cfg.dim * cfg.Np * 8 + 2 * cfg.dim * 8 + 8)      # 6 200 B/item
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
     # HBM traffic per launch from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in
@@ -659,18 +704,8 @@ def main():
                     mc["cpu_baseline"] = cpu_sweep_baseline(cfg.Np, cfg.Nb)
                 except Exception as e:                           # noqa: BLE001 -- the baseline is reported, never required
                     mc["cpu_baseline"] = {"error": repr(e)[:300]}
-        result = {
-            "metric": "bead-pair action evals/sec (K1 Delta-S, N=256 Nb=161 4He, 128 walkers/GPU)",
-            "value": value, "unit": "bead-pair action evals/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "liquid 4He N=%d beads=%d (namelist Nb=%d), %d walkers/GPU x %d GPU(s) = %d walkers, one "
-                                   "full-chain Delta-S stage per step (%d items x %d partners per GPU)"
-                                   % (cfg.Np, cfg.M, cfg.Nb, W, world, W * world, n_items, cfg.Np - 1),
-                       "walkers_per_gpu": W, "global_walkers": W * world, "items_per_step": n_items,
-                       "items_per_step_global": n_items * world,
-                       "stages_per_sweep_equiv": None},
+        result = dict(headline)
+        result.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          # measured live: kernel_ms (HIP events on the context's stream).  NOT measured in this run:
@@ -685,9 +720,8 @@ def main():
                          "streaming_read_same_bytes": stream_read},
             "roofline_large": large,
             "cpu_baseline": cpu,
-            "kernel_only_evals_per_s": pair_evals_per_step / (kern_ms * 1e-3),
             "mc": mc,
-        }
+        })
     ctx.close()
     if world > 1:
         dist.barrier()

@@ -15,7 +15,8 @@ HEADERS = ["pigs_device.h", "pigs_k1_device.h", "pigs_kernels.h", "pigs_comm.h",
 # build (no FMA); hipcc's default is fast contraction.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
          "-Wall", "-Wno-unused-function"]
-OBJDIR = os.environ.get("PIGS_OBJDIR", "/tmp/pigs_hip_obj")
+# objects stay inside the checkout (build/ is git-ignored): no directory shared between users or checkouts
+OBJDIR = os.environ.get("PIGS_OBJDIR", os.path.join(ROOT, "build", "hip_obj"))
 
 
 def hipcc():

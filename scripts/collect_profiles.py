@@ -24,7 +24,7 @@ def main():
     out = {"correction": "MI355X_MICROARCH.md (HBM): on gfx950 FETCH_SIZE counts 64 B per 128-B request of a coalesced "
                          "streaming read -> doubled; WRITE_SIZE exact.  Separate --pmc passes with --kernel-trace only. "
                          "Units: KB per launch as rocprofv3 reports them.",
-           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --steps 20 --warmup 2 --no-cpu"}
+           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu"}
     fe = per_launch(os.path.join(d, "fetch"), "FETCH_SIZE", "k_delta_action")
     wr = per_launch(os.path.join(d, "write"), "WRITE_SIZE", "k_delta_action")
     kern = sorted({k for _, k, _ in fe})
@@ -58,7 +58,7 @@ def main():
 
 def kernel_stats(d, dst):
     """Per (kernel, grid size) duration statistics from the kernel trace of
-    `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 10 --no-cpu` (the --stats table itself
+    `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 200 --warmup 10 --no-cpu` (the --stats table itself
     lumps the 128-walker and the 384-walker launches of K1 together)."""
     import collections
     acc = collections.defaultdict(list)

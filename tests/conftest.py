@@ -27,12 +27,15 @@ def oracle():
     return Oracle()
 
 
-@pytest.fixture(scope="session")
-def ref():
+@pytest.fixture
+def tape(request):
+    """The reference's answers for this test (tests/reftape.py): from oracle/_ref/libvpiref.so where it is built,
+    checked against the recorded ones in tests/golden/ref_tapes/; replayed from those everywhere else."""
     from oracle.pyoracle import Ref
-    if not Ref.available():
-        pytest.skip("oracle/_ref/libvpiref.so not built here (needs /root/reference)")
-    return Ref()
+    from reftape import RefTape
+    t = RefTape(request.node.nodeid, Ref() if Ref.available() else None)
+    yield t
+    t.finish()
 
 
 def system_from_golden(d, **over):

@@ -7,6 +7,11 @@ routines through oracle/ref_probe.f90 (full 64-bit values); nothing here comes f
 restatement.  The fixtures are data: inputs + expected outputs, no reference source text.
 
     python tests/golden/make_golden.py
+
+The reference's answers behind tests/test_oracle_vs_ref.py and tests/test_host_sampler.py (tests/golden/ref_tapes/)
+are recorded by those tests themselves (tests/reftape.py):
+
+    PIGS_RECORD_REF_TAPES=1 python -m pytest tests/test_oracle_vs_ref.py tests/test_host_sampler.py
 """
 import os
 import subprocess
@@ -200,6 +205,10 @@ RUNS = {
                            Nblock=6, Nstep=25, CWorm="0.5d0", Nobdm=4, Npw=1),
     "he4_worm_s1984": dict(dim=3, Np=16, Nb=8, seed=1984, sampling="bis", Lstag=8, Nlev=3, Nstag=3,
                            Nblock=6, Nstep=25, CWorm="0.5d0", Nobdm=4, Npw=1),
+    # the input test_host_driver.py::test_reference_program_itself_if_present gives the program (he4_worm_s1982's with
+    # another seed and 15 steps): its files only
+    "he4_worm_s4242": dict(dim=3, Np=16, Nb=8, seed=4242, sampling="bis", Lstag=8, Nlev=3, Nstag=3,
+                           Nblock=6, Nstep=15, CWorm="0.5d0", Nobdm=4, Npw=1, driver=False),
     # a busier worm (dt = 0.02, CWorm = 0.6): several opens, closes and dozens of accepted swaps; Npw = 2
     "he4_wormbusy_s7": dict(dim=3, Np=16, Nb=8, seed=7, dt="2.0d-2", sampling="bis", Lstag=8, Nlev=3, Nstag=3,
                             Nblock=6, Nstep=20, CWorm="0.6d0", Nobdm=4, Npw=2),

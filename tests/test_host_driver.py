@@ -154,18 +154,24 @@ def test_lockstep_walkers_reproduce_per_seed_reference_runs(exe, tmp_path):
 
 
 def test_reference_program_itself_if_present(exe, tmp_path):
-    """Where the reference build exists, run it fresh on a new input and compare again."""
+    """The reference program on an input no other test uses (seed 4242, 15 steps): its files are recorded in
+    tests/golden/vpi_runs/he4_worm_s4242; where the reference build exists it is also run afresh and must still
+    write them."""
     from oracle.pyoracle import REF_VPI
-    if not os.path.exists(REF_VPI):
-        pytest.skip("oracle/_ref/vpi not built here")
+    src = os.path.join(RUNS, "he4_worm_s4242")
     txt = open(os.path.join(RUNS, "he4_worm_s1982", "vpi.in")).read().replace("seed = 1982", "seed = 4242") \
         .replace("Nstep = 25", "Nstep = 15")
+    assert txt == open(os.path.join(src, "vpi.in")).read()
+    want = {f: open(os.path.join(src, f), "rb").read() for f in FILES}
     a, b = tmp_path / "ref", tmp_path / "mine"
     a.mkdir(); b.mkdir()
-    run_pigs_vpi(REF_VPI, txt, str(a))
+    if os.path.exists(REF_VPI):
+        run_pigs_vpi(REF_VPI, txt, str(a))
+        for f in FILES:
+            assert open(a / f, "rb").read() == want[f], f
     run_pigs_vpi(exe, txt, str(b))
     for f in FILES:
-        assert open(a / f, "rb").read() == open(b / f, "rb").read(), f
+        assert open(b / f, "rb").read() == want[f], f
 
 
 def test_resume_from_reference_checkpoint(exe, tmp_path):
