@@ -195,6 +195,9 @@ typedef struct pigs_sweep_params {
     int32_t swapping, Nobdm, Nbin, Npw;
     int32_t sampling, reserved;           /* diagonal movers: 0 = 'bis' (bisection), 1 = 'sta' (staging) */
 } pigs_sweep_params;
+/* Success means that pigs_sampler_step runs this input: PIGS_ERR_UNSUPPORTED when the sampler's LDS staging does not
+ * hold the worldline, or when a periodic 'bis' input with Nlev > 4 needs the stage-machine kernel and that kernel does
+ * not fit (odd Nmax, or table plus chain buffers beyond LDS).  A caller may then pick the host-driven sampler. */
 int pigs_sampler_init(pigs_ctx *ctx, const pigs_sweep_params *sp);
 /* seed walker's stream as the reference's sgrnd(seed) does */
 int pigs_sampler_seed(pigs_ctx *ctx, int32_t walker, int32_t seed);

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -49,29 +50,35 @@ int fail(int code, const char *fmt, ...)
                         __FILE__, __LINE__);                                             \
     } while (0)
 
+// Device memory owned by its holder (move-only): `alloc` for the fixed arrays, `reserve` for the grow-only scratch.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;
-    hipError_t reserve(size_t n)
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    ~DevBuf() { release(); }
+    // exactly n elements: a no-op at that size already, otherwise the old contents are dropped
+    hipError_t alloc(size_t n)
     {
-        if (n <= cap) return hipSuccess;
-        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
-        size_t want = n + n / 4 + 64;
-        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
+        if (p && n == cap) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e == hipSuccess) cap = n; else p = nullptr;
         return e;
     }
+    hipError_t reserve(size_t n) { return n <= cap ? hipSuccess : alloc(n + n / 4 + 64); }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-} // namespace
-
-// pinned, device-mapped host arrays of the staged (low-latency) entry points
+// pinned, device-mapped host arrays (move-only): the staged (low-latency) entry points, the estimators' result block
 struct PinBuf {
     void *h = nullptr, *d = nullptr;
     size_t bytes = 0;
-    hipError_t reserve(size_t want, size_t keep_bytes)
+    PinBuf() = default;
+    PinBuf(PinBuf &&o) noexcept : h(std::exchange(o.h, nullptr)), d(std::exchange(o.d, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    ~PinBuf() { if (h) (void)hipHostFree(h); }
+    hipError_t reserve(size_t want, size_t keep_bytes = 0)
     {
         if (want <= bytes) return hipSuccess;
         void *nh = nullptr, *nd = nullptr;
@@ -84,8 +91,48 @@ struct PinBuf {
         h = nh; d = nd; bytes = want;
         return hipSuccess;
     }
-    void release() { if (h) (void)hipHostFree(h); h = d = nullptr; bytes = 0; }
 };
+
+// a stream, event or communicator handle destroyed by its holder (move-only)
+template <typename H, auto Destroy>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    ~Handle() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    operator H() const { return h; }
+};
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event  = Handle<hipEvent_t, hipEventDestroy>;
+using Comm   = Handle<pigs_comm *, pigs_comm_destroy>;
+
+// One batch of the diagonal estimators (pigs_diagonal_estimators and its overlapped form) for n walkers, validated.
+// Slot lists: [0, nslot) the ThermEnergy slices 0..2Nb-1 (Q8) of every walker, [nslot, nslot + n) the walkers themselves
+// (K4, K7).  Result block (nres doubles): [LocalEnergy slice 0: 3n][LocalEnergy slice 2Nb: 3n][E n][Ec n][Ep n][gr][Sk].
+struct EstBatch {
+    int n = 0, Nbin = 0, Nk = 0;
+    double rbin = 0.0;
+    bool structure = false;
+    size_t ns = 0, nslot = 0, ng = 0, nk = 0, nres = 0;
+    std::vector<int32_t> w;                 // the walkers
+};
+
+// the device buffers a batch runs in: slot lists, ThermEnergy slices, result block
+struct EstBufs {
+    DevBuf<int32_t> slotw, slotb;
+    DevBuf<double>  slices, res;
+    hipError_t reserve(const EstBatch &b)
+    {
+        hipError_t e = slotw.reserve(b.nslot + b.n);
+        if (e == hipSuccess) e = slotb.reserve(b.nslot);
+        if (e == hipSuccess) e = slices.reserve(b.nslot * 3);
+        if (e == hipSuccess) e = res.reserve(b.nres);
+        return e;
+    }
+};
+
+} // namespace
 
 // several contexts of one process meeting in host memory (pigs_comm_init_all on duplicate devices: rehearsal only)
 struct HostGroup {
@@ -101,25 +148,26 @@ struct pigs_ctx {
     DevParams   P;
     int         device    = 0;
     int         n_walkers = 0;
-    hipStream_t stream    = nullptr;
-    double *d_paths = nullptr, *d_VT = nullptr, *d_WF = nullptr;
+    Stream      stream;
+    DevBuf<double> d_paths, d_VT, d_WF;
     std::shared_ptr<HostGroup> hgroup;   // rehearsal form of the estimator reduction (several contexts on one GPU)
     int hrank = 0;
-    double *d_VTimg = nullptr;           // [0, VT(0)] VT(0..Nmax+1) [0 0 0 0]: PipeTab image for the sampler (pigs_k1_device.h)
+    DevBuf<double> d_VTimg;              // [0, VT(0)] VT(0..Nmax+1) [0 0 0 0]: PipeTab image for the sampler (pigs_k1_device.h)
     size_t  path_doubles = 0;        // resident doubles per walker (padded SoA)
     size_t  raw_doubles  = 0;        // dim*Np*(2Nb+1): reference layout per walker
-    DevBuf<int32_t> d_walker, d_ip, d_ib, d_slotw, d_slotb;
-    DevBuf<double>  d_xnew, d_xold, d_out, d_parts, d_stage, d_slices, d_res;
-    pigs_comm  *comm = nullptr;
+    DevBuf<int32_t> d_walker, d_ip, d_ib;
+    DevBuf<double>  d_xnew, d_xold, d_out, d_parts, d_stage;
+    EstBufs     est;                         // estimators on the context's stream (also the scratch of K2/K3, K4, K7 alone)
+    Comm        comm;
     int         k1_variant = K1_AUTO;
     PinBuf      st_w, st_ip, st_ib, st_xn, st_xo, st_out;      // staged items
     PinBuf      cs_w, cs_ip, cs_ib, cs_x;                      // staged commits
     int64_t     st_cap = 0, cs_cap = 0;
     // device-resident sampler
-    uint32_t   *d_rng = nullptr;
-    unsigned long long *d_counters = nullptr;
-    double     *d_worm = nullptr, *d_nrho = nullptr, *d_dklog = nullptr;
-    int        *d_evlog = nullptr;
+    DevBuf<uint32_t> d_rng;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<double> d_worm, d_nrho, d_dklog;
+    DevBuf<int> d_evlog;
     size_t      nrho_doubles = 0;
     SweepParams sweep{};
     int         cm_freq = 1;
@@ -130,22 +178,19 @@ struct pigs_ctx {
     int         cm_split = -1;
     bool        cm_exclusive = false;       // the caller vouches that no other context's kernels run on this device meanwhile
     bool        cm_shared = false;          // several contexts of this process sample on this device at once: see g_cm_gate
-    unsigned long long *d_xch = nullptr;    // exchange buffer of the cooperating workgroups
-    int        *h_cm_err = nullptr;         // (pinned, device-visible) set by a workgroup whose partner never answered
+    DevBuf<unsigned long long> d_xch;       // exchange buffer of the cooperating workgroups
+    PinBuf      h_cm_err;                   // (one int) set by a workgroup whose partner never answered
     unsigned int cm_seq = 1;                // sequence tags of the exchange: advanced by every launch
-    bool        counted = false;            // in g_live_ctx
     bool        sampler_ready = false;
     // asynchronous estimators (pigs_diagonal_estimators_begin / _end): a snapshot of the worldlines and a second stream
-    hipStream_t stream2 = nullptr;
-    hipEvent_t  ev_snap = nullptr;
-    double     *d_shadow = nullptr;
-    DevBuf<int32_t> a_slotw, a_slotb;
-    DevBuf<double>  a_slices, a_res;
+    Stream      stream2;
+    Event       ev_snap;
+    DevBuf<double> d_shadow;
+    EstBufs     a_buf;
     PinBuf      a_host;                     // results land here (pinned: the copy is truly asynchronous)
     std::vector<int32_t> a_sw, a_sb;        // slot lists: must outlive the asynchronous upload
-    struct { bool on = false, launched = false; int n = 0, Nbin = 0, Nk = 0; double rbin = 0.0; bool structure = false;
-             size_t ng = 0, nk = 0, nres = 0; } a_pend;
-    hipEvent_t  ev_gate = nullptr;          // recorded behind the TranslateChain kernel of the next step (see launch_pending_estimators)
+    struct { bool on = false, launched = false; EstBatch b; } a_pend;
+    Event       ev_gate;                    // recorded behind the TranslateChain kernel of the next step (see launch_pending_estimators)
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -225,7 +270,7 @@ int pigs_ctx_create(const pigs_params *p, const double *VTable, const double *Lo
     if (device_id < 0 || device_id >= ndev) return fail(PIGS_ERR_ARG, "device_id=%d of %d", device_id, ndev);
     HIPCHK(hipSetDevice(device_id));
 
-    pigs_ctx *c = new (std::nothrow) pigs_ctx();
+    std::unique_ptr<pigs_ctx> c(new (std::nothrow) pigs_ctx());
     if (!c) return fail(PIGS_ERR_ARG, "out of host memory");
     c->hp = *p;
     c->device = device_id;
@@ -251,88 +296,55 @@ int pigs_ctx_create(const pigs_params *p, const double *VTable, const double *Lo
     c->path_doubles = slice_doubles(P.dim, P.NpPad) * P.M;
     c->raw_doubles  = (size_t)P.dim * P.Np * P.M;
 
-    int rc = PIGS_OK;
-    do {
-        {
-            // Contexts on one device alternate between the normal and the high stream priority: the runtime maps streams onto
-            // a few hardware queues PER PRIORITY (GPU_MAX_HW_QUEUES = 4 by default, shared with every other stream of the
-            // process), and two sampling shards whose streams land on one hardware queue run one after the other instead of
-            // side by side (round 3: bench.py's two-shard leg at 77 instead of 38.5 ms per MC step).  Different priorities
-            // are different queues for certain; with CUs to spare the priority itself decides nothing.
-            int least = 0, greatest = 0;
-            const int serial = g_ctx_serial[device_id & 63].fetch_add(1);
-            if ((serial & 1) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least) {
-                if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-            } else if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-        }
-        const size_t tb = (size_t)(p->Nmax + 2) * sizeof(double);
-        if (hipMalloc((void **)&c->d_VT, tb) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-        if (hipMalloc((void **)&c->d_WF, tb) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-        if (hipMalloc((void **)&c->d_paths, c->path_doubles * n_walkers * sizeof(double)) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-        if (hipMemcpy(c->d_VT, VTable, tb, hipMemcpyHostToDevice) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-        if ((LogWF && p->wf_table ? hipMemcpy(c->d_WF, LogWF, tb, hipMemcpyHostToDevice) : hipMemset(c->d_WF, 0, tb)) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-        {
-            std::vector<double> img((size_t)p->Nmax + 2 + 6, 0.0);
-            img[1] = VTable[0];
-            memcpy(&img[2], VTable, tb);
-            if (hipMalloc((void **)&c->d_VTimg, img.size() * sizeof(double)) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-            if (hipMemcpy(c->d_VTimg, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-        }
-        if (hipMemset(c->d_paths, 0, c->path_doubles * n_walkers * sizeof(double)) != hipSuccess) { rc = PIGS_ERR_HIP; break; }
-    } while (0);
-    if (rc != PIGS_OK) {
-        fail(rc, "context allocation failed: %s", hipGetErrorString(hipGetLastError()));
-        pigs_ctx_destroy(c);
-        return rc;
+    {
+        // Contexts on one device alternate between the normal and the high stream priority: the runtime maps streams onto
+        // a few hardware queues PER PRIORITY (GPU_MAX_HW_QUEUES = 4 by default, shared with every other stream of the
+        // process), and two sampling shards whose streams land on one hardware queue run one after the other instead of
+        // side by side (round 3: bench.py's two-shard leg at 77 instead of 38.5 ms per MC step).  Different priorities
+        // are different queues for certain; with CUs to spare the priority itself decides nothing.
+        int least = 0, greatest = 0;
+        const int serial = g_ctx_serial[device_id & 63].fetch_add(1);
+        if ((serial & 1) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
+            HIPCHK(hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, greatest));
+        else
+            HIPCHK(hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking));
     }
+    const size_t nt = (size_t)p->Nmax + 2, tb = nt * sizeof(double), np = c->path_doubles * n_walkers;
+    HIPCHK(c->d_VT.alloc(nt));
+    HIPCHK(c->d_WF.alloc(nt));
+    HIPCHK(c->d_paths.alloc(np));
+    HIPCHK(hipMemcpy(c->d_VT.p, VTable, tb, hipMemcpyHostToDevice));
+    HIPCHK(LogWF && p->wf_table ? hipMemcpy(c->d_WF.p, LogWF, tb, hipMemcpyHostToDevice) : hipMemset(c->d_WF.p, 0, tb));
+    std::vector<double> img(nt + 6, 0.0);
+    img[1] = VTable[0];
+    memcpy(&img[2], VTable, tb);
+    HIPCHK(c->d_VTimg.alloc(img.size()));
+    HIPCHK(hipMemcpy(c->d_VTimg.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(c->d_paths.p, 0, np * sizeof(double)));
     {
         hipDeviceProp_t pr;
         if (hipGetDeviceProperties(&pr, device_id) == hipSuccess && pr.multiProcessorCount > 0) c->n_cu = pr.multiProcessorCount;
     }
-    c->counted = true;
     g_live_ctx[device_id & 63].fetch_add(1);
-    *out = c;
+    *out = c.release();
     return PIGS_OK;
 }
 
 int pigs_ctx_destroy(pigs_ctx *c)
 {
     if (!c) return PIGS_OK;
-    if (c->counted) { g_live_ctx[c->device & 63].fetch_sub(1); c->counted = false; }
+    g_live_ctx[c->device & 63].fetch_sub(1);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->comm) { pigs_comm_destroy(c->comm); c->comm = nullptr; }
-    c->d_walker.release(); c->d_ip.release(); c->d_ib.release(); c->d_slotw.release(); c->d_slotb.release();
-    c->d_xnew.release(); c->d_xold.release(); c->d_out.release(); c->d_parts.release();
-    c->d_stage.release(); c->d_slices.release(); c->d_res.release();
-    c->st_w.release(); c->st_ip.release(); c->st_ib.release(); c->st_xn.release(); c->st_xo.release(); c->st_out.release();
-    c->cs_w.release(); c->cs_ip.release(); c->cs_ib.release(); c->cs_x.release();
-    if (c->d_rng) (void)hipFree(c->d_rng);
-    if (c->d_worm) (void)hipFree(c->d_worm);
-    if (c->d_nrho) (void)hipFree(c->d_nrho);
-    if (c->d_dklog) (void)hipFree(c->d_dklog);
-    if (c->d_evlog) (void)hipFree(c->d_evlog);
-    if (c->d_xch) (void)hipFree(c->d_xch);
-    if (c->h_cm_err) (void)hipHostFree(c->h_cm_err);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    if (c->d_paths) (void)hipFree(c->d_paths);
-    if (c->d_VT) (void)hipFree(c->d_VT);
-    if (c->d_VTimg) (void)hipFree(c->d_VTimg);
-    if (c->d_WF) (void)hipFree(c->d_WF);
-    if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
-    if (c->ev_snap) (void)hipEventDestroy(c->ev_snap);
-    if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
-    if (c->d_shadow) (void)hipFree(c->d_shadow);
-    c->a_host.release();
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+    delete c;                                   // every resource is released by the member that owns it
     return PIGS_OK;
 }
 
 // after a synchronisation: did a cooperating workgroup of the TranslateChain kernel give up waiting (pigs_cm.hip)?
 static int check_cm(pigs_ctx *c)
 {
-    if (c->h_cm_err && *(volatile int *)c->h_cm_err)
+    if (c->h_cm_err.h && *(volatile int *)c->h_cm_err.h)
         return fail(PIGS_ERR_HIP, "TranslateChain kernel: a cooperating workgroup timed out; the worldlines of this context are invalid");
     return PIGS_OK;
 }
@@ -359,7 +371,7 @@ int pigs_sync(pigs_ctx *c)
 int pigs_stream(pigs_ctx *c, void **s)
 {
     if (!c || !s) return fail(PIGS_ERR_ARG, "null pointer");
-    *s = (void *)c->stream;
+    *s = (void *)c->stream.h;
     return PIGS_OK;
 }
 
@@ -404,14 +416,13 @@ int pigs_selftest_fastmath(pigs_ctx *c, int32_t blocks, int32_t iters, uint64_t 
 {
     int rc = check_ctx(c); if (rc) return rc;
     if (!bad || blocks < 1 || iters < 1) return fail(PIGS_ERR_ARG, "bad arguments");
-    unsigned long long *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, 4 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), c->stream));
-    HIPCHK(launch_selftest_fastmath(c->P, 0x1234567ull, blocks, iters, d, c->stream));
+    DevBuf<unsigned long long> d;
+    HIPCHK(d.alloc(4));
+    HIPCHK(hipMemsetAsync(d.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(launch_selftest_fastmath(c->P, 0x1234567ull, blocks, iters, d.p, c->stream));
     unsigned long long h[4];
-    HIPCHK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h, d.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     SYNC_CHECKED(c);
-    HIPCHK(hipFree(d));
     for (int i = 0; i < 4; ++i) bad[i] = h[i];
     return PIGS_OK;
 }
@@ -424,12 +435,15 @@ int pigs_selftest_log(pigs_ctx *c, int64_t n, uint64_t seed, uint64_t *mismatche
     int rc = check_ctx(c); if (rc) return rc;
     if (!mismatches || n < 1) return fail(PIGS_ERR_ARG, "bad arguments");
     const size_t chunk = (size_t)1 << 24;
-    double *d[2] = {nullptr, nullptr}, *h[2] = {nullptr, nullptr};
+    DevBuf<double> d[2];
+    PinBuf hb[2];
+    double *h[2] = {nullptr, nullptr};
     uint64_t bad = 0; double firstx = 0.0; bool have = false;
     hipError_t e = hipSuccess;
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipMalloc((void **)&d[k], chunk * sizeof(double));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&h[k], chunk * sizeof(double), hipHostMallocDefault);
+        e = d[k].alloc(chunk);
+        if (e == hipSuccess) e = hb[k].reserve(chunk * sizeof(double));
+        h[k] = (double *)hb[k].h;
     }
     auto compare = [&](const double *res, uint64_t first, size_t m) {
         const unsigned nt = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
@@ -448,14 +462,13 @@ int pigs_selftest_log(pigs_ctx *c, int64_t n, uint64_t seed, uint64_t *mismatche
     uint64_t done = 0; int cur = 0; size_t prev_m = 0; uint64_t prev_first = 0;
     while (e == hipSuccess && done < (uint64_t)n) {
         const size_t m = (size_t)std::min<uint64_t>(chunk, (uint64_t)n - done);
-        e = launch_selftest_log(done, m, seed, d[cur], c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h[cur], d[cur], m * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        e = launch_selftest_log(done, m, seed, d[cur].p, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h[cur], d[cur].p, m * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (prev_m) compare(h[cur ^ 1], prev_first, prev_m);            // overlaps the chunk in flight
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         prev_m = m; prev_first = done; done += m; cur ^= 1;
     }
     if (e == hipSuccess && prev_m) compare(h[cur ^ 1], prev_first, prev_m);
-    for (int k = 0; k < 2; ++k) { if (d[k]) (void)hipFree(d[k]); if (h[k]) (void)hipHostFree(h[k]); }
     if (e != hipSuccess) return fail(PIGS_ERR_HIP, "pigs_selftest_log: %s", hipGetErrorString(e));
     *mismatches = bad;
     if (first_bad) *first_bad = firstx;
@@ -467,21 +480,18 @@ int pigs_selftest_stream_read(pigs_ctx *c, int32_t reps, double *bytes, double *
     int rc = check_ctx(c); if (rc) return rc;
     if (!bytes || !seconds || reps < 1) return fail(PIGS_ERR_ARG, "bad arguments");
     const size_t nd = c->path_doubles * (size_t)c->n_walkers;
-    double *sink = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevBuf<double> sink;
+    Event e0, e1;
     float ms = 0.f;
-    hipError_t e = hipMalloc((void **)&sink, sizeof(double));
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    for (int r = 0; r < 3 && e == hipSuccess; ++r) e = launch_stream_read(c->d_paths, nd, c->n_cu, sink, c->stream);
+    hipError_t e = sink.alloc(1);
+    if (e == hipSuccess) e = hipEventCreate(&e0.h);
+    if (e == hipSuccess) e = hipEventCreate(&e1.h);
+    for (int r = 0; r < 3 && e == hipSuccess; ++r) e = launch_stream_read(c->d_paths.p, nd, c->n_cu, sink.p, c->stream);
     if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
-    for (int r = 0; r < reps && e == hipSuccess; ++r) e = launch_stream_read(c->d_paths, nd, c->n_cu, sink, c->stream);
+    for (int r = 0; r < reps && e == hipSuccess; ++r) e = launch_stream_read(c->d_paths.p, nd, c->n_cu, sink.p, c->stream);
     if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);                    // nothing leaks on an error return
-    if (e1) (void)hipEventDestroy(e1);
-    if (sink) (void)hipFree(sink);
     if (e != hipSuccess) return fail(PIGS_ERR_HIP, "pigs_selftest_stream_read: %s", hipGetErrorString(e));
     *bytes = (double)(nd * sizeof(double));
     *seconds = 1e-3 * (double)ms / reps;
@@ -501,7 +511,7 @@ static int upload_range(pigs_ctx *c, int w0, int nw, const double *raw)
         HIPCHK(c->d_stage.reserve(c->raw_doubles * m));
         HIPCHK(hipMemcpyAsync(c->d_stage.p, raw + c->raw_doubles * a, c->raw_doubles * m * sizeof(double),
                               hipMemcpyHostToDevice, c->stream));
-        HIPCHK(launch_pack(c->P, c->d_paths, c->d_stage.p, w0 + a, m, c->stream));
+        HIPCHK(launch_pack(c->P, c->d_paths.p, c->d_stage.p, w0 + a, m, c->stream));
         SYNC_CHECKED(c);
     }
     return PIGS_OK;
@@ -516,7 +526,7 @@ static int download_range(pigs_ctx *c, int w0, int nw, double *raw)
     for (int a = 0; a < nw; a += chunk) {
         const int m = nw - a < chunk ? nw - a : chunk;
         HIPCHK(c->d_stage.reserve(c->raw_doubles * m));
-        HIPCHK(launch_unpack(c->P, c->d_paths, c->d_stage.p, w0 + a, m, c->stream));
+        HIPCHK(launch_unpack(c->P, c->d_paths.p, c->d_stage.p, w0 + a, m, c->stream));
         HIPCHK(hipMemcpyAsync(raw + c->raw_doubles * a, c->d_stage.p, c->raw_doubles * m * sizeof(double),
                               hipMemcpyDeviceToHost, c->stream));
         SYNC_CHECKED(c);
@@ -559,7 +569,7 @@ static int delta_action_host(pigs_ctx *c, int64_t n, const int32_t *walker, cons
     HIPCHK(hipMemcpyAsync(c->d_ib.p, ib, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_xnew.p, xnew, nd * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_xold.p, xold, nd * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_delta_action(c->P, c->k1_variant, c->d_paths, c->d_VT, c->d_VTimg, c->d_WF, (int)n, c->d_walker.p, c->d_ip.p,
+    HIPCHK(launch_delta_action(c->P, c->k1_variant, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, (int)n, c->d_walker.p, c->d_ip.p,
                                c->d_ib.p, c->d_xnew.p, c->d_xold.p, c->d_out.p,
                                parts ? c->d_parts.p : nullptr, s));
     if (DeltaS) HIPCHK(hipMemcpyAsync(DeltaS, c->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -591,7 +601,7 @@ int pigs_delta_action_batch_dev(pigs_ctx *c, int64_t n, const int32_t *d_walker,
     if (n == 0) return PIGS_OK;
     if (!d_walker || !d_ip || !d_ib || !d_xnew || !d_xold || !d_DeltaS) return fail(PIGS_ERR_ARG, "null device pointer");
     // indices are range-checked on the device (out-of-range items produce NaN, never a fault)
-    HIPCHK(launch_delta_action(c->P, c->k1_variant, c->d_paths, c->d_VT, c->d_VTimg, c->d_WF, (int)n, d_walker, d_ip, d_ib,
+    HIPCHK(launch_delta_action(c->P, c->k1_variant, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, (int)n, d_walker, d_ip, d_ib,
                                d_xnew, d_xold, d_DeltaS, nullptr, c->stream));
     return PIGS_OK;
 }
@@ -625,7 +635,7 @@ int pigs_delta_action_staged(pigs_ctx *c, int64_t n)
     if (n < 0 || n > c->st_cap) return fail(PIGS_ERR_ARG, "n_items=%lld exceeds the staged capacity %lld", (long long)n, (long long)c->st_cap);
     if (n == 0) return PIGS_OK;
     // indices are range-checked on the device (bad item -> NaN)
-    HIPCHK(launch_delta_action(c->P, c->k1_variant, c->d_paths, c->d_VT, c->d_VTimg, c->d_WF, (int)n,
+    HIPCHK(launch_delta_action(c->P, c->k1_variant, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, (int)n,
                                (const int32_t *)c->st_w.d, (const int32_t *)c->st_ip.d, (const int32_t *)c->st_ib.d,
                                (const double *)c->st_xn.d, (const double *)c->st_xo.d, (double *)c->st_out.d,
                                nullptr, c->stream));
@@ -656,11 +666,9 @@ int pigs_commit_staged(pigs_ctx *c, int64_t n)
     if (n < 0 || n > c->cs_cap) return fail(PIGS_ERR_ARG, "n=%lld exceeds the staged capacity %lld", (long long)n, (long long)c->cs_cap);
     if (n == 0) return PIGS_OK;
     const int32_t *w = (const int32_t *)c->cs_w.h, *ip = (const int32_t *)c->cs_ip.h, *ib = (const int32_t *)c->cs_ib.h;
-    for (int64_t i = 0; i < n; ++i)
-        if (w[i] < 0 || w[i] >= c->n_walkers || ip[i] < 1 || ip[i] > c->P.Np || ib[i] < 0 || ib[i] >= c->P.M)
-            return fail(PIGS_ERR_ARG, "commit %lld: walker=%d ip=%d ib=%d out of range", (long long)i, w[i], ip[i], ib[i]);
+    rc = check_items(c, n, w, ip, ib); if (rc) return rc;
     mark_superseded(n, (int32_t *)c->cs_w.h, ip, ib, c->P.M, c->P.Np);
-    HIPCHK(launch_commit_beads(c->P, c->d_paths, n, (const int32_t *)c->cs_w.d, (const int32_t *)c->cs_ip.d,
+    HIPCHK(launch_commit_beads(c->P, c->d_paths.p, n, (const int32_t *)c->cs_w.d, (const int32_t *)c->cs_ip.d,
                                (const int32_t *)c->cs_ib.d, (const double *)c->cs_x.d, c->stream));
     return PIGS_OK;
 }
@@ -683,7 +691,7 @@ int pigs_commit_beads(pigs_ctx *c, int64_t n, const int32_t *walker, const int32
     HIPCHK(hipMemcpyAsync(c->d_ip.p, ip, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_ib.p, ib, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->d_xnew.p, x, nd * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_commit_beads(c->P, c->d_paths, n, c->d_walker.p, c->d_ip.p, c->d_ib.p, c->d_xnew.p, s));
+    HIPCHK(launch_commit_beads(c->P, c->d_paths.p, n, c->d_walker.p, c->d_ip.p, c->d_ib.p, c->d_xnew.p, s));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }
@@ -694,7 +702,7 @@ int pigs_swap_tails(pigs_ctx *c, int32_t walker, int32_t iw, int32_t ik)
     if (walker < 0 || walker >= c->n_walkers || iw < 1 || iw > c->P.Np || ik < 1 || ik > c->P.Np)
         return fail(PIGS_ERR_ARG, "swap_tails(walker=%d, iw=%d, ik=%d) out of range", walker, iw, ik);
     if (iw == ik) return PIGS_OK;
-    HIPCHK(launch_swap_tails(c->P, c->d_paths, walker, iw, ik, c->stream));
+    HIPCHK(launch_swap_tails(c->P, c->d_paths.p, walker, iw, ik, c->stream));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }
@@ -745,6 +753,7 @@ int pigs_sampler_init(pigs_ctx *c, const pigs_sweep_params *sp)
     const bool worm = sp->CWorm > 0.0;
     if (worm && (sp->Nobdm < 0 || sp->Nbin < 1 || sp->Npw < 0 || !(sp->rbin > 0.0) || !(sp->density > 0.0)))
         return fail(PIGS_ERR_ARG, "worm parameters out of range");
+    c->sampler_ready = false;                 // until this call has gone through
     SweepParams &k = c->sweep;
     memset(&k, 0, sizeof k);
     k.Nlev = sta ? 1 : sp->Nlev; k.Nstag = sp->Nstag; k.Lstag = sp->Lstag; k.staging = sta;
@@ -755,47 +764,41 @@ int pigs_sampler_init(pigs_ctx *c, const pigs_sweep_params *sp)
     c->cm_freq = sp->CMFreq;
     // one workgroup per walker: the 8-wave form (periodic: table image in LDS) while every walker gets a CU of its own,
     // the 4-wave form (three workgroups per CU) beyond that (measured: scripts/sampler_bench.py)
-    {
-        int dev = 0, ncu = 256;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-            ncu = pr.multiProcessorCount;
-        c->n_cu = ncu;
-        c->sweep_threads = sweep_form(c->P, c->sweep, c->n_walkers > ncu ? 256 : 1024);
-    }
+    c->sweep_threads = sweep_form(c->P, c->sweep, c->n_walkers > c->n_cu ? 256 : 1024);
     if (sweep_lds_bytes(c->P, c->sweep, c->sweep_threads) > 160 * 1024) c->sweep_threads = sweep_form(c->P, c->sweep, 256);
     if (sweep_lds_bytes(c->P, c->sweep, c->sweep_threads) > 160 * 1024) return fail(PIGS_ERR_UNSUPPORTED, "worldline too long for the sampler's LDS staging");
+    // periodic 'bis' inputs beyond four levels need the stage-machine kernel (pigs_sampler_step): refused here, so that
+    // a caller can pick the host-driven sampler instead
+    if (!c->P.trap && !k.staging && k.Nlev > 4 && !diag_supported(c->P, k))
+        return fail(PIGS_ERR_UNSUPPORTED, "Nlev=%d needs the stage-machine kernel, which does not fit this worldline", k.Nlev);
     const size_t W = c->n_walkers;
-    if (!c->d_rng) HIPCHK(hipMalloc((void **)&c->d_rng, W * kRngWords * sizeof(uint32_t)));
-    if (!c->d_counters) HIPCHK(hipMalloc((void **)&c->d_counters, W * kCounters * sizeof(unsigned long long)));
-    if (!c->d_worm) HIPCHK(hipMalloc((void **)&c->d_worm, W * kWormDoubles * sizeof(double)));
     // a step logs at most one open / close event and one swap per OBDM iteration
     k.ev_ints = kEvInts > 4 + 2 * (1 + k.Nobdm) ? kEvInts : 4 + 2 * (1 + k.Nobdm);
-    if (c->d_evlog) { HIPCHK(hipFree(c->d_evlog)); c->d_evlog = nullptr; }
-    HIPCHK(hipMalloc((void **)&c->d_evlog, W * k.ev_ints * sizeof(int)));
-    if (c->d_nrho) { HIPCHK(hipFree(c->d_nrho)); c->d_nrho = nullptr; }
     c->nrho_doubles = W * (size_t)k.Nbin * (k.Npw + 1);
-    HIPCHK(hipMalloc((void **)&c->d_nrho, c->nrho_doubles * sizeof(double)));
-    if (c->d_dklog) { HIPCHK(hipFree(c->d_dklog)); c->d_dklog = nullptr; }
     // 0.5d0*real(dim)*log(2.d0*pi*real(Ls)*dt) of vpi_mod.f90:1873, tabulated with the host libm
     std::vector<double> dk(sp->Lstag + 2, 0.0);
     const double pi = std::acos(-1.0);
     for (int Ls = 1; Ls <= sp->Lstag + 1; ++Ls)
         dk[Ls] = 0.5 * (double)(float)c->P.dim * std::log(2.0 * pi * (double)(float)Ls * c->P.dt);
-    HIPCHK(hipMalloc((void **)&c->d_dklog, dk.size() * sizeof(double)));
+    HIPCHK(c->d_rng.alloc(W * kRngWords));
+    HIPCHK(c->d_counters.alloc(W * kCounters));
+    HIPCHK(c->d_worm.alloc(W * kWormDoubles));
+    HIPCHK(c->d_evlog.alloc(W * k.ev_ints));
+    HIPCHK(c->d_nrho.alloc(c->nrho_doubles));
+    HIPCHK(c->d_dklog.alloc(dk.size()));
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->d_dklog, dk.data(), dk.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(c->d_counters, 0, W * kCounters * sizeof(unsigned long long), s));
-    HIPCHK(hipMemsetAsync(c->d_worm, 0, W * kWormDoubles * sizeof(double), s));
-    HIPCHK(hipMemsetAsync(c->d_evlog, 0, W * k.ev_ints * sizeof(int), s));
-    HIPCHK(hipMemsetAsync(c->d_nrho, 0, c->nrho_doubles * sizeof(double), s));
+    HIPCHK(hipMemcpyAsync(c->d_dklog.p, dk.data(), dk.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_counters.p, 0, W * kCounters * sizeof(unsigned long long), s));
+    HIPCHK(hipMemsetAsync(c->d_worm.p, 0, W * kWormDoubles * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(c->d_evlog.p, 0, W * k.ev_ints * sizeof(int), s));
+    HIPCHK(hipMemsetAsync(c->d_nrho.p, 0, c->nrho_doubles * sizeof(double), s));
     std::vector<uint32_t> st(W * kRngWords);
     for (size_t w = 0; w < W; ++w) {
         uint32_t seedw[624];
         mt_seed_words(4357u, seedw);
         mt_block_to_device(624, seedw, &st[w * kRngWords]);
     }
-    HIPCHK(hipMemcpyAsync(c->d_rng, st.data(), st.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_rng.p, st.data(), st.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     SYNC_CHECKED(c);
     c->sampler_ready = true;
     return PIGS_OK;
@@ -808,7 +811,7 @@ int pigs_sampler_set_rng(pigs_ctx *c, int32_t walker, int32_t mti, const int32_t
     if (walker < 0 || walker >= c->n_walkers || !mt || mti < 0 || mti > 624) return fail(PIGS_ERR_ARG, "bad rng state");
     uint32_t st[kRngWords];
     mt_block_to_device(mti, (const uint32_t *)mt, st);
-    HIPCHK(hipMemcpyAsync(c->d_rng + (size_t)walker * kRngWords, st, sizeof st, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_rng.p + (size_t)walker * kRngWords, st, sizeof st, hipMemcpyHostToDevice, c->stream));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }
@@ -819,7 +822,7 @@ int pigs_sampler_get_rng(pigs_ctx *c, int32_t walker, int32_t *mti, int32_t mt[6
     if (!c->sampler_ready) return fail(PIGS_ERR_ARG, "pigs_sampler_init first");
     if (walker < 0 || walker >= c->n_walkers || !mt || !mti) return fail(PIGS_ERR_ARG, "bad rng request");
     uint32_t st[kRngWords];
-    HIPCHK(hipMemcpyAsync(st, c->d_rng + (size_t)walker * kRngWords, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(st, c->d_rng.p + (size_t)walker * kRngWords, sizeof st, hipMemcpyDeviceToHost, c->stream));
     SYNC_CHECKED(c);
     memcpy(mt, st + 624, 624 * sizeof(uint32_t));                    // block form: what mtsavef would hold
     *mti = (int32_t)st[1248];
@@ -866,30 +869,30 @@ int pigs_sampler_step(pigs_ctx *c, int32_t istep)
     }
     bool cm_done = false;
     if (H >= 1) {
-        if (!c->d_xch) {
-            const size_t nb = cm_exchange_words(c->P) * sizeof(unsigned long long);
-            HIPCHK(hipMalloc((void **)&c->d_xch, nb));
-            HIPCHK(hipMemsetAsync(c->d_xch, 0, nb, c->stream));
-            HIPCHK(hipHostMalloc((void **)&c->h_cm_err, sizeof(int), hipHostMallocMapped));
-            *c->h_cm_err = 0;
+        if (!c->d_xch.p) {
+            HIPCHK(c->d_xch.alloc(cm_exchange_words(c->P)));
+            HIPCHK(hipMemsetAsync(c->d_xch.p, 0, c->d_xch.cap * sizeof(unsigned long long), c->stream));
+        }
+        if (!c->h_cm_err.h) {
+            HIPCHK(c->h_cm_err.reserve(sizeof(int)));
+            *(int *)c->h_cm_err.h = 0;
         }
         sp.parts = 1;
-        HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths, c->d_VT, c->d_VTimg, c->d_WF, c->d_rng, c->d_counters,
-                            c->d_worm, c->d_evlog, c->d_nrho, c->d_dklog, c->stream));
-        int *d_err = nullptr;
-        HIPCHK(hipHostGetDevicePointer((void **)&d_err, c->h_cm_err, 0));
+        HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
+                            c->d_worm.p, c->d_evlog.p, c->d_nrho.p, c->d_dklog.p, c->stream));
+        int *d_err = (int *)c->h_cm_err.d;
         hipError_t e = hipSuccess;
         if (c->cm_shared && H > 1) {
             std::lock_guard<std::mutex> lk(g_cm_mutex[c->device & 63]);
             hipEvent_t &gate = g_cm_gate[c->device & 63];
             if (!gate) e = hipEventCreateWithFlags(&gate, hipEventDisableTiming);
             else       e = hipStreamWaitEvent(c->stream, gate, 0);           // the device's previous TranslateChain kernel, whoever launched it
-            if (e == hipSuccess) e = launch_cm(c->P, sp, H, c->cm_seq, c->d_paths, c->d_VTimg, c->d_WF, c->d_rng, c->d_counters,
-                                               c->d_worm, c->d_xch, d_err, c->stream);
+            if (e == hipSuccess) e = launch_cm(c->P, sp, H, c->cm_seq, c->d_paths.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
+                                               c->d_worm.p, c->d_xch.p, d_err, c->stream);
             if (e == hipSuccess) e = hipEventRecord(gate, c->stream);
         } else {
-            e = launch_cm(c->P, sp, H, c->cm_seq, c->d_paths, c->d_VTimg, c->d_WF, c->d_rng, c->d_counters,
-                          c->d_worm, c->d_xch, d_err, c->stream);
+            e = launch_cm(c->P, sp, H, c->cm_seq, c->d_paths.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
+                          c->d_worm.p, c->d_xch.p, d_err, c->stream);
         }
         HIPCHK(e);
         c->cm_seq += (unsigned int)c->P.Np + 1;
@@ -905,25 +908,24 @@ int pigs_sampler_step(pigs_ctx *c, int32_t istep)
     if (c->a_pend.on && !c->a_pend.launched) {                // a step without the TranslateChain kernel: beside the whole step
         rc = launch_pending_estimators(c, c->ev_snap); if (rc) return rc;
     }
+    // (pigs_sampler_init refused the inputs that need the stage machine where it does not fit)
     const bool need_split = !c->P.trap && !sp.staging && sp.Nlev > 4;
-    const bool split = (c->sweep_split || need_split) && diag_supported(c->P, sp);
-    if (need_split && !split) return fail(PIGS_ERR_UNSUPPORTED, "Nlev=%d needs the stage-machine kernel, which does not fit this worldline", sp.Nlev);
-    if (split) {
+    if ((c->sweep_split || need_split) && diag_supported(c->P, sp)) {
         if (!cm_done) {
             sp.parts = 1;
-            HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths, c->d_VT, c->d_VTimg, c->d_WF, c->d_rng, c->d_counters,
-                                c->d_worm, c->d_evlog, c->d_nrho, c->d_dklog, c->stream));
+            HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
+                                c->d_worm.p, c->d_evlog.p, c->d_nrho.p, c->d_dklog.p, c->stream));
         }
-        HIPCHK(launch_diag(c->P, sp, 512, c->d_paths, c->d_VTimg, c->d_WF, c->d_rng, c->d_counters, c->d_worm, c->stream));
+        HIPCHK(launch_diag(c->P, sp, 512, c->d_paths.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p, c->d_worm.p, c->stream));
         if (sp.worm) {
             sp.parts = 4;
-            HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths, c->d_VT, c->d_VTimg, c->d_WF, c->d_rng, c->d_counters,
-                                c->d_worm, c->d_evlog, c->d_nrho, c->d_dklog, c->stream));
+            HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
+                                c->d_worm.p, c->d_evlog.p, c->d_nrho.p, c->d_dklog.p, c->stream));
         }
     } else {
         sp.parts = cm_done ? 6 : 7;
-        HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths, c->d_VT, c->d_VTimg, c->d_WF, c->d_rng, c->d_counters,
-                            c->d_worm, c->d_evlog, c->d_nrho, c->d_dklog, c->stream));
+        HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
+                            c->d_worm.p, c->d_evlog.p, c->d_nrho.p, c->d_dklog.p, c->stream));
     }
     return PIGS_OK;
 }
@@ -932,7 +934,7 @@ int pigs_sampler_counters16(pigs_ctx *c, int64_t *cnt)
 {
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->sampler_ready || !cnt) return fail(PIGS_ERR_ARG, "pigs_sampler_init first / null output");
-    HIPCHK(hipMemcpyAsync(cnt, c->d_counters, (size_t)c->n_walkers * kCounters * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(cnt, c->d_counters.p, (size_t)c->n_walkers * kCounters * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }
@@ -952,7 +954,7 @@ int pigs_sampler_get_worm(pigs_ctx *c, int32_t *isopen, int32_t *iworm, double *
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->sampler_ready || !isopen || !iworm || !xend) return fail(PIGS_ERR_ARG, "pigs_sampler_init first / null output");
     std::vector<double> h((size_t)c->n_walkers * kWormDoubles);
-    HIPCHK(hipMemcpyAsync(h.data(), c->d_worm, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h.data(), c->d_worm.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     SYNC_CHECKED(c);
     const int d = c->P.dim;
     for (int w = 0; w < c->n_walkers; ++w) {
@@ -975,7 +977,7 @@ int pigs_sampler_set_worm(pigs_ctx *c, const int32_t *isopen, const int32_t *iwo
         h[(size_t)w * kWormDoubles + 1] = (double)iworm[w];
         for (int t = 0; t < 2 * d; ++t) h[(size_t)w * kWormDoubles + 2 + t] = xend[(size_t)w * 2 * d + t];
     }
-    HIPCHK(hipMemcpyAsync(c->d_worm, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_worm.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }
@@ -992,7 +994,7 @@ int pigs_sampler_events(pigs_ctx *c, int32_t *events)
 {
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->sampler_ready || !events) return fail(PIGS_ERR_ARG, "pigs_sampler_init first / null output");
-    HIPCHK(hipMemcpyAsync(events, c->d_evlog, (size_t)c->n_walkers * c->sweep.ev_ints * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(events, c->d_evlog.p, (size_t)c->n_walkers * c->sweep.ev_ints * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }
@@ -1001,7 +1003,7 @@ int pigs_sampler_nrho(pigs_ctx *c, double *nrho, const int32_t *reset)
 {
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->sampler_ready || !nrho) return fail(PIGS_ERR_ARG, "pigs_sampler_init first / null output");
-    HIPCHK(hipMemcpyAsync(nrho, c->d_nrho, c->nrho_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(nrho, c->d_nrho.p, c->nrho_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (reset) {
         // zero the histograms of the flagged walkers, one memset per run of consecutive walkers
         const size_t per = c->nrho_doubles / (size_t)c->n_walkers;
@@ -1009,7 +1011,7 @@ int pigs_sampler_nrho(pigs_ctx *c, double *nrho, const int32_t *reset)
             if (!reset[w]) { ++w; continue; }
             int e = w;
             while (e < c->n_walkers && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_nrho + (size_t)w * per, 0, (size_t)(e - w) * per * sizeof(double), c->stream));
+            HIPCHK(hipMemsetAsync(c->d_nrho.p + (size_t)w * per, 0, (size_t)(e - w) * per * sizeof(double), c->stream));
             w = e;
         }
     }
@@ -1023,7 +1025,7 @@ int pigs_slice_download(pigs_ctx *c, int32_t ib, double *R)
     if (!R || ib < 0 || ib >= c->P.M) return fail(PIGS_ERR_ARG, "bad slice request");
     const size_t n = (size_t)c->P.dim * c->P.Np * c->n_walkers;
     HIPCHK(c->d_stage.reserve(n));
-    HIPCHK(launch_slice_gather(c->P, c->d_paths, ib, c->d_stage.p, c->stream));
+    HIPCHK(launch_slice_gather(c->P, c->d_paths.p, ib, c->d_stage.p, c->stream));
     HIPCHK(hipMemcpyAsync(R, c->d_stage.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     SYNC_CHECKED(c);
     return PIGS_OK;
@@ -1036,17 +1038,88 @@ int pigs_potential_energy_slice(pigs_ctx *c, int32_t walker, int32_t ib, int32_t
     int rc = check_ctx(c); if (rc) return rc;
     if (!Pot) return fail(PIGS_ERR_ARG, "null Pot");
     if (walker < 0 || walker >= c->n_walkers || ib < 0 || ib >= c->P.M) return fail(PIGS_ERR_ARG, "walker=%d ib=%d out of range", walker, ib);
-    HIPCHK(c->d_slotw.reserve(1)); HIPCHK(c->d_slotb.reserve(1)); HIPCHK(c->d_slices.reserve(3));
+    HIPCHK(c->est.slotw.reserve(1)); HIPCHK(c->est.slotb.reserve(1)); HIPCHK(c->est.slices.reserve(3));
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->d_slotw.p, &walker, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_slotb.p, &ib, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_slice_energy(c->P, c->d_paths, c->d_VT, c->d_VTimg, 1, c->d_slotw.p, c->d_slotb.p, want_F2 ? 2 : 0, 0, c->d_slices.p, s));
+    HIPCHK(hipMemcpyAsync(c->est.slotw.p, &walker, sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->est.slotb.p, &ib, sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(launch_slice_energy(c->P, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, 1, c->est.slotw.p, c->est.slotb.p, want_F2 ? 2 : 0, 0, c->est.slices.p, s));
     double h[3];
-    HIPCHK(hipMemcpyAsync(h, c->d_slices.p, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h, c->est.slices.p, sizeof h, hipMemcpyDeviceToHost, s));
     SYNC_CHECKED(c);
     *Pot = h[0];
     if (F2) *F2 = want_F2 ? h[1] : 0.0;
     return PIGS_OK;
+}
+
+// the walkers of a request -- walkers[i], or 0..n-1 when the list is left out -- range-checked
+static int walker_list(const pigs_ctx *c, int n, const int32_t *walkers, std::vector<int32_t> &sw)
+{
+    sw.resize(n);
+    for (int i = 0; i < n; ++i) {
+        sw[i] = walkers ? walkers[i] : i;
+        if (sw[i] < 0 || sw[i] >= c->n_walkers) return fail(PIGS_ERR_ARG, "walker %d out of range", sw[i]);
+    }
+    return PIGS_OK;
+}
+
+// ---- the diagonal-estimator batch (EstBatch): shared by ThermEnergy and both forms of pigs_diagonal_estimators ------
+static int est_describe(const pigs_ctx *c, int n, const int32_t *walkers, bool structure, int Nbin, double rbin, int Nk,
+                        EstBatch &b)
+{
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    if (structure && (Nbin < 1 || Nk < 0 || !(rbin > 0.0))) return fail(PIGS_ERR_ARG, "bad structure request");
+    if (structure && c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "structural estimators are defined for PBC runs only (vpi.f90:466)");
+    const int rc = walker_list(c, n, walkers, b.w); if (rc) return rc;
+    b.n = n; b.Nbin = Nbin; b.rbin = rbin; b.Nk = Nk; b.structure = structure;
+    b.ns = 2 * (size_t)c->P.Nb;                       // ThermEnergy: slices 0..2Nb-1 (Q8)
+    b.nslot = (size_t)n * b.ns;
+    b.ng = structure ? (size_t)n * Nbin : 0;
+    b.nk = structure ? (size_t)n * Nk * c->P.dim : 0;
+    b.nres = (size_t)9 * n + b.ng + b.nk;
+    return PIGS_OK;
+}
+
+static void est_slots(const EstBatch &b, std::vector<int32_t> &sw, std::vector<int32_t> &sb)
+{
+    sw.resize(b.nslot + b.n); sb.resize(b.nslot);
+    for (int i = 0; i < b.n; ++i) {
+        for (size_t s = 0; s < b.ns; ++s) { sw[i * b.ns + s] = b.w[i]; sb[i * b.ns + s] = (int32_t)s; }
+        sw[b.nslot + i] = b.w[i];
+    }
+}
+
+// on stream s: the slot lists up into d, the five launches on the worldlines `paths` (ThermEnergy's slices on at most
+// cu_cap workgroups; 0: no cap), the result block down to `host`.  sw, sb and host must outlive the copies.
+static int est_launch(pigs_ctx *c, const EstBatch &b, const double *paths, EstBufs &d, const std::vector<int32_t> &sw,
+                      const std::vector<int32_t> &sb, double *host, hipStream_t s, int cu_cap)
+{
+    const size_t n = b.n;
+    HIPCHK(hipMemcpyAsync(d.slotw.p, sw.data(), sw.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.slotb.p, sb.data(), sb.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    double *r = d.res.p;
+    const int32_t *dw = d.slotw.p + b.nslot;
+    HIPCHK(launch_local_energy(c->P, paths, c->d_VT.p, c->d_WF.p, b.n, dw, 0, r, s));
+    HIPCHK(launch_local_energy(c->P, paths, c->d_VT.p, c->d_WF.p, b.n, dw, 2 * c->P.Nb, r + 3 * n, s));
+    HIPCHK(launch_slice_energy(c->P, paths, c->d_VT.p, c->d_VTimg.p, (int)b.nslot, d.slotw.p, d.slotb.p, 1, 1, d.slices.p, s, cu_cap));
+    HIPCHK(launch_therm_combine(c->P, b.n, d.slices.p, r + 6 * n, r + 7 * n, r + 8 * n, s));
+    if (b.structure)
+        HIPCHK(launch_structure(c->P, paths, b.n, dw, c->P.Nb, b.Nbin, b.rbin, b.Nk, r + 9 * n, r + 9 * n + b.ng, s));
+    HIPCHK(hipMemcpyAsync(host, r, b.nres * sizeof(double), hipMemcpyDeviceToHost, s));
+    return PIGS_OK;
+}
+
+// a result block on the host into en (9 per walker), gr and Sk
+static void est_unpack(const EstBatch &b, const double *h, double *en, double *gr, double *Sk)
+{
+    const size_t n = b.n;
+    for (size_t i = 0; i < n; ++i) {
+        for (int q = 0; q < 3; ++q) { en[9 * i + q] = h[3 * i + q]; en[9 * i + 3 + q] = h[3 * n + 3 * i + q]; }
+        en[9 * i + 6] = h[6 * n + i]; en[9 * i + 7] = h[7 * n + i]; en[9 * i + 8] = h[8 * n + i];
+    }
+    if (b.structure) {
+        memcpy(gr, h + 9 * n, b.ng * sizeof(double));
+        if (b.nk) memcpy(Sk, h + 9 * n + b.ng, b.nk * sizeof(double));
+    }
 }
 
 int pigs_therm_energy_batch(pigs_ctx *c, int32_t n, const int32_t *walkers, double *E, double *Ec, double *Ep)
@@ -1055,24 +1128,20 @@ int pigs_therm_energy_batch(pigs_ctx *c, int32_t n, const int32_t *walkers, doub
     if (n < 0 || (n > c->n_walkers && !walkers)) return fail(PIGS_ERR_ARG, "n=%d walkers", n);
     if (n == 0) return PIGS_OK;
     if (!E || !Ec || !Ep) return fail(PIGS_ERR_ARG, "null output");
-    const int ns = 2 * c->P.Nb;                       // slices 0..2Nb-1 (Q8)
-    std::vector<int32_t> sw((size_t)n * ns), sb((size_t)n * ns);
-    for (int i = 0; i < n; ++i) {
-        const int w = walkers ? walkers[i] : i;
-        if (w < 0 || w >= c->n_walkers) return fail(PIGS_ERR_ARG, "walker %d out of range", w);
-        for (int b = 0; b < ns; ++b) { sw[(size_t)i * ns + b] = w; sb[(size_t)i * ns + b] = b; }
-    }
-    const size_t nslot = (size_t)n * ns;
-    HIPCHK(c->d_slotw.reserve(nslot)); HIPCHK(c->d_slotb.reserve(nslot));
-    HIPCHK(c->d_slices.reserve(nslot * 3)); HIPCHK(c->d_res.reserve((size_t)n * 3));
+    EstBatch b;
+    std::vector<int32_t> sw, sb;
+    rc = est_describe(c, n, walkers, false, 0, 0.0, 0, b); if (rc) return rc;
+    est_slots(b, sw, sb);
+    HIPCHK(c->est.reserve(b));
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->d_slotw.p, sw.data(), nslot * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_slotb.p, sb.data(), nslot * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_slice_energy(c->P, c->d_paths, c->d_VT, c->d_VTimg, (int)nslot, c->d_slotw.p, c->d_slotb.p, 1, 1, c->d_slices.p, s));
-    HIPCHK(launch_therm_combine(c->P, n, c->d_slices.p, c->d_res.p, c->d_res.p + n, c->d_res.p + 2 * (size_t)n, s));
-    HIPCHK(hipMemcpyAsync(E, c->d_res.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(Ec, c->d_res.p + n, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(Ep, c->d_res.p + 2 * (size_t)n, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    double *r = c->est.res.p;
+    HIPCHK(hipMemcpyAsync(c->est.slotw.p, sw.data(), b.nslot * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->est.slotb.p, sb.data(), b.nslot * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(launch_slice_energy(c->P, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, (int)b.nslot, c->est.slotw.p, c->est.slotb.p, 1, 1, c->est.slices.p, s));
+    HIPCHK(launch_therm_combine(c->P, n, c->est.slices.p, r, r + n, r + 2 * (size_t)n, s));
+    HIPCHK(hipMemcpyAsync(E, r, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(Ec, r + n, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(Ep, r + 2 * (size_t)n, n * sizeof(double), hipMemcpyDeviceToHost, s));
     SYNC_CHECKED(c);   // sw/sb must outlive the async copies
     return PIGS_OK;
 }
@@ -1086,17 +1155,14 @@ int pigs_local_energy_batch(pigs_ctx *c, int32_t n, const int32_t *walkers, int3
     if (n == 0) return PIGS_OK;
     if (!E || !Kin || !Pot) return fail(PIGS_ERR_ARG, "null output");
     if (ib < 0 || ib >= c->P.M) return fail(PIGS_ERR_ARG, "ib=%d out of range", ib);
-    std::vector<int32_t> sw(n);
-    for (int i = 0; i < n; ++i) {
-        sw[i] = walkers ? walkers[i] : i;
-        if (sw[i] < 0 || sw[i] >= c->n_walkers) return fail(PIGS_ERR_ARG, "walker %d out of range", sw[i]);
-    }
-    HIPCHK(c->d_slotw.reserve(n)); HIPCHK(c->d_res.reserve((size_t)n * 3));
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    HIPCHK(c->est.slotw.reserve(n)); HIPCHK(c->est.res.reserve((size_t)n * 3));
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->d_slotw.p, sw.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_local_energy(c->P, c->d_paths, c->d_VT, c->d_WF, n, c->d_slotw.p, ib, c->d_res.p, s));
+    HIPCHK(hipMemcpyAsync(c->est.slotw.p, sw.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(launch_local_energy(c->P, c->d_paths.p, c->d_VT.p, c->d_WF.p, n, c->est.slotw.p, ib, c->est.res.p, s));
     std::vector<double> h((size_t)n * 3);
-    HIPCHK(hipMemcpyAsync(h.data(), c->d_res.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h.data(), c->est.res.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     SYNC_CHECKED(c);
     for (int i = 0; i < n; ++i) { E[i] = h[3 * i]; Kin[i] = h[3 * i + 1]; Pot[i] = h[3 * i + 2]; }
     return PIGS_OK;
@@ -1111,18 +1177,15 @@ int pigs_structure_batch(pigs_ctx *c, int32_t n, const int32_t *walkers, int32_t
     if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "structural estimators are defined for PBC runs only (vpi.f90:466)");
     if (n == 0) return PIGS_OK;
     if (!gr || !Sk) return fail(PIGS_ERR_ARG, "null output");
-    std::vector<int32_t> sw(n);
-    for (int i = 0; i < n; ++i) {
-        sw[i] = walkers ? walkers[i] : i;
-        if (sw[i] < 0 || sw[i] >= c->n_walkers) return fail(PIGS_ERR_ARG, "walker %d out of range", sw[i]);
-    }
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
     const size_t ng = (size_t)n * Nbin, ns = (size_t)n * Nk * c->P.dim;
-    HIPCHK(c->d_slotw.reserve(n)); HIPCHK(c->d_res.reserve(ng + ns));
+    HIPCHK(c->est.slotw.reserve(n)); HIPCHK(c->est.res.reserve(ng + ns));
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->d_slotw.p, sw.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(launch_structure(c->P, c->d_paths, n, c->d_slotw.p, ib, Nbin, rbin, Nk, c->d_res.p, c->d_res.p + ng, s));
-    HIPCHK(hipMemcpyAsync(gr, c->d_res.p, ng * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (ns) HIPCHK(hipMemcpyAsync(Sk, c->d_res.p + ng, ns * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(c->est.slotw.p, sw.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(launch_structure(c->P, c->d_paths.p, n, c->est.slotw.p, ib, Nbin, rbin, Nk, c->est.res.p, c->est.res.p + ng, s));
+    HIPCHK(hipMemcpyAsync(gr, c->est.res.p, ng * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (ns) HIPCHK(hipMemcpyAsync(Sk, c->est.res.p + ng, ns * sizeof(double), hipMemcpyDeviceToHost, s));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }
@@ -1139,46 +1202,16 @@ int pigs_diagonal_estimators(pigs_ctx *c, int32_t n, const int32_t *walkers, int
     int rc = check_ctx(c); if (rc) return rc;
     if (n < 0 || !en) return fail(PIGS_ERR_ARG, "n=%d / null output", n);
     if (n == 0) return PIGS_OK;
-    const bool structure = gr || Sk;
-    if (structure && (!gr || !Sk || Nbin < 1 || Nk < 0 || !(rbin > 0.0))) return fail(PIGS_ERR_ARG, "bad structure request");
-    if (structure && c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "structural estimators are defined for PBC runs only (vpi.f90:466)");
-    const int ns = 2 * c->P.Nb;                       // ThermEnergy: slices 0..2Nb-1 (Q8)
-    const size_t nslot = (size_t)n * ns;
-    // slot lists: [0, nslot) the ThermEnergy slices, [nslot, nslot + n) the walkers themselves (K4, K7)
-    std::vector<int32_t> sw(nslot + n), sb(nslot);
-    for (int i = 0; i < n; ++i) {
-        const int w = walkers ? walkers[i] : i;
-        if (w < 0 || w >= c->n_walkers) return fail(PIGS_ERR_ARG, "walker %d out of range", w);
-        for (int b = 0; b < ns; ++b) { sw[(size_t)i * ns + b] = w; sb[(size_t)i * ns + b] = b; }
-        sw[nslot + i] = w;
-    }
-    const size_t ng = structure ? (size_t)n * Nbin : 0, nk = structure ? (size_t)n * Nk * c->P.dim : 0;
-    // result block: [LocalEnergy slice 0: 3n][LocalEnergy slice 2Nb: 3n][E n][Ec n][Ep n][gr][Sk]
-    const size_t nres = (size_t)9 * n + ng + nk;
-    HIPCHK(c->d_slotw.reserve(nslot + n)); HIPCHK(c->d_slotb.reserve(nslot));
-    HIPCHK(c->d_slices.reserve(nslot * 3)); HIPCHK(c->d_res.reserve(nres));
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->d_slotw.p, sw.data(), sw.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_slotb.p, sb.data(), sb.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    double *r = c->d_res.p;
-    const int32_t *dw = c->d_slotw.p + nslot;
-    HIPCHK(launch_local_energy(c->P, c->d_paths, c->d_VT, c->d_WF, n, dw, 0, r, s));
-    HIPCHK(launch_local_energy(c->P, c->d_paths, c->d_VT, c->d_WF, n, dw, 2 * c->P.Nb, r + 3 * (size_t)n, s));
-    HIPCHK(launch_slice_energy(c->P, c->d_paths, c->d_VT, c->d_VTimg, (int)nslot, c->d_slotw.p, c->d_slotb.p, 1, 1, c->d_slices.p, s));
-    HIPCHK(launch_therm_combine(c->P, n, c->d_slices.p, r + 6 * (size_t)n, r + 7 * (size_t)n, r + 8 * (size_t)n, s));
-    if (structure)
-        HIPCHK(launch_structure(c->P, c->d_paths, n, dw, c->P.Nb, Nbin, rbin, Nk, r + 9 * (size_t)n, r + 9 * (size_t)n + ng, s));
-    std::vector<double> h(nres);
-    HIPCHK(hipMemcpyAsync(h.data(), r, nres * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (!gr != !Sk) return fail(PIGS_ERR_ARG, "bad structure request");
+    EstBatch b;
+    std::vector<int32_t> sw, sb;
+    rc = est_describe(c, n, walkers, gr != nullptr, Nbin, rbin, Nk, b); if (rc) return rc;
+    est_slots(b, sw, sb);
+    HIPCHK(c->est.reserve(b));
+    std::vector<double> h(b.nres);
+    rc = est_launch(c, b, c->d_paths.p, c->est, sw, sb, h.data(), c->stream, 0); if (rc) return rc;
     SYNC_CHECKED(c);
-    for (int i = 0; i < n; ++i) {
-        for (int q = 0; q < 3; ++q) { en[9 * i + q] = h[3 * i + q]; en[9 * i + 3 + q] = h[3 * (size_t)n + 3 * i + q]; }
-        en[9 * i + 6] = h[6 * (size_t)n + i]; en[9 * i + 7] = h[7 * (size_t)n + i]; en[9 * i + 8] = h[8 * (size_t)n + i];
-    }
-    if (structure) {
-        memcpy(gr, h.data() + 9 * (size_t)n, ng * sizeof(double));
-        if (nk) memcpy(Sk, h.data() + 9 * (size_t)n + ng, nk * sizeof(double));
-    }
+    est_unpack(b, h.data(), en, gr, Sk);
     return PIGS_OK;
 }
 
@@ -1194,68 +1227,37 @@ static int launch_pending_estimators(pigs_ctx *c, hipEvent_t gate)
 {
     if (!c->a_pend.on || c->a_pend.launched) return PIGS_OK;
     c->a_pend.launched = true;
-    const int n = c->a_pend.n;
-    if (n == 0) return PIGS_OK;
-    const int ns = 2 * c->P.Nb;
-    const size_t nslot = (size_t)n * ns, ng = c->a_pend.ng, nres = c->a_pend.nres;
-    hipStream_t s = c->stream2;
-    HIPCHK(hipStreamWaitEvent(s, gate, 0));
-    HIPCHK(hipMemcpyAsync(c->a_slotw.p, c->a_sw.data(), c->a_sw.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->a_slotb.p, c->a_sb.data(), c->a_sb.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    double *r = c->a_res.p;
-    const int32_t *dw = c->a_slotw.p + nslot;
+    if (c->a_pend.b.n == 0) return PIGS_OK;
+    HIPCHK(hipStreamWaitEvent(c->stream2, gate, 0));
     const int half = c->n_cu / 2 > 0 ? c->n_cu / 2 : 1;
-    HIPCHK(launch_local_energy(c->P, c->d_shadow, c->d_VT, c->d_WF, n, dw, 0, r, s));
-    HIPCHK(launch_local_energy(c->P, c->d_shadow, c->d_VT, c->d_WF, n, dw, 2 * c->P.Nb, r + 3 * (size_t)n, s));
-    HIPCHK(launch_slice_energy(c->P, c->d_shadow, c->d_VT, c->d_VTimg, (int)nslot, c->a_slotw.p, c->a_slotb.p, 1, 1, c->a_slices.p, s, half));
-    HIPCHK(launch_therm_combine(c->P, n, c->a_slices.p, r + 6 * (size_t)n, r + 7 * (size_t)n, r + 8 * (size_t)n, s));
-    if (c->a_pend.structure)
-        HIPCHK(launch_structure(c->P, c->d_shadow, n, dw, c->P.Nb, c->a_pend.Nbin, c->a_pend.rbin, c->a_pend.Nk, r + 9 * (size_t)n,
-                                r + 9 * (size_t)n + ng, s));
-    HIPCHK(hipMemcpyAsync(c->a_host.h, r, nres * sizeof(double), hipMemcpyDeviceToHost, s));
-    return PIGS_OK;
+    return est_launch(c, c->a_pend.b, c->d_shadow.p, c->a_buf, c->a_sw, c->a_sb, (double *)c->a_host.h, c->stream2, half);
 }
 
 int pigs_diagonal_estimators_begin(pigs_ctx *c, int32_t n, const int32_t *walkers, int32_t Nbin, double rbin, int32_t Nk,
                                    int32_t structure)
 {
     int rc = check_ctx(c); if (rc) return rc;
-    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     if (c->a_pend.on) return fail(PIGS_ERR_ARG, "an estimator batch is pending: pigs_diagonal_estimators_end first");
     rc = check_cm(c); if (rc) return rc;
-    const bool st = structure != 0;
-    if (st && (Nbin < 1 || Nk < 0 || !(rbin > 0.0))) return fail(PIGS_ERR_ARG, "bad structure request");
-    if (st && c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "structural estimators are defined for PBC runs only (vpi.f90:466)");
-    c->a_pend.n = n; c->a_pend.Nbin = Nbin; c->a_pend.Nk = Nk; c->a_pend.rbin = rbin; c->a_pend.structure = st;
+    EstBatch b;
+    rc = est_describe(c, n, walkers, structure != 0, Nbin, rbin, Nk, b); if (rc) return rc;
+    if (n > 0) {
+        const size_t nd = c->path_doubles * (size_t)c->n_walkers;
+        if (!c->stream2) HIPCHK(hipStreamCreateWithFlags(&c->stream2.h, hipStreamNonBlocking));
+        if (!c->ev_snap) HIPCHK(hipEventCreateWithFlags(&c->ev_snap.h, hipEventDisableTiming));
+        if (!c->ev_gate) HIPCHK(hipEventCreateWithFlags(&c->ev_gate.h, hipEventDisableTiming));
+        HIPCHK(c->d_shadow.alloc(nd));
+        HIPCHK(c->a_buf.reserve(b));
+        HIPCHK(c->a_host.reserve(b.nres * sizeof(double)));
+        est_slots(b, c->a_sw, c->a_sb);
+        // the snapshot is ordered on the context's stream: after everything queued so far, before whatever comes next.
+        // The kernels themselves are launched by the next pigs_sampler_step behind its TranslateChain kernel (which fills
+        // the chip: estimators started beside it would only take CUs away from it) or, failing that, by _end.
+        HIPCHK(hipMemcpyAsync(c->d_shadow.p, c->d_paths.p, nd * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->ev_snap, c->stream));
+    }
+    c->a_pend.b = std::move(b);
     c->a_pend.launched = false;
-    if (n == 0) { c->a_pend.on = true; c->a_pend.nres = 0; return PIGS_OK; }
-    const int ns = 2 * c->P.Nb;
-    const size_t nslot = (size_t)n * ns;
-    c->a_sw.resize(nslot + n); c->a_sb.resize(nslot);
-    for (int i = 0; i < n; ++i) {
-        const int w = walkers ? walkers[i] : i;
-        if (w < 0 || w >= c->n_walkers) return fail(PIGS_ERR_ARG, "walker %d out of range", w);
-        for (int b = 0; b < ns; ++b) { c->a_sw[(size_t)i * ns + b] = w; c->a_sb[(size_t)i * ns + b] = b; }
-        c->a_sw[nslot + i] = w;
-    }
-    const size_t ng = st ? (size_t)n * Nbin : 0, nk = st ? (size_t)n * Nk * c->P.dim : 0;
-    const size_t nres = (size_t)9 * n + ng + nk;
-    c->a_pend.ng = ng; c->a_pend.nk = nk; c->a_pend.nres = nres;
-    const size_t nd = c->path_doubles * (size_t)c->n_walkers;
-    if (!c->stream2) {
-        HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_snap, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_gate, hipEventDisableTiming));
-        HIPCHK(hipMalloc((void **)&c->d_shadow, nd * sizeof(double)));
-    }
-    HIPCHK(c->a_slotw.reserve(nslot + n)); HIPCHK(c->a_slotb.reserve(nslot));
-    HIPCHK(c->a_slices.reserve(nslot * 3)); HIPCHK(c->a_res.reserve(nres));
-    HIPCHK(c->a_host.reserve(nres * sizeof(double), 0));
-    // the snapshot is ordered on the context's stream: after everything queued so far, before whatever comes next.  The
-    // kernels themselves are launched by the next pigs_sampler_step behind its TranslateChain kernel (which fills the
-    // chip: estimators started beside it would only take CUs away from it) or, failing that, by _end.
-    HIPCHK(hipMemcpyAsync(c->d_shadow, c->d_paths, nd * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_snap, c->stream));
     c->a_pend.on = true;
     return PIGS_OK;
 }
@@ -1264,25 +1266,14 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
 {
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->a_pend.on) return fail(PIGS_ERR_ARG, "no estimator batch is pending: pigs_diagonal_estimators_begin first");
-    c->a_pend.on = false;
-    const int n = c->a_pend.n;
-    if (n == 0) return PIGS_OK;
-    if (!en || (c->a_pend.structure && (!gr || !Sk))) return fail(PIGS_ERR_ARG, "null output");
-    c->a_pend.on = true;                                  // (launch_pending_estimators looks at it)
+    const EstBatch &b = c->a_pend.b;
+    if (b.n > 0 && (!en || (b.structure && (!gr || !Sk)))) return fail(PIGS_ERR_ARG, "null output");   // (still pending)
     rc = launch_pending_estimators(c, c->ev_snap);        // no sampler step came in between: start them now
     c->a_pend.on = false;
-    if (rc) return rc;
+    if (rc || b.n == 0) return rc;
     HIPCHK(hipStreamSynchronize(c->stream2));
     rc = check_cm(c); if (rc) return rc;
-    const double *h = reinterpret_cast<const double *>(c->a_host.h);
-    for (int i = 0; i < n; ++i) {
-        for (int q = 0; q < 3; ++q) { en[9 * i + q] = h[3 * i + q]; en[9 * i + 3 + q] = h[3 * (size_t)n + 3 * i + q]; }
-        en[9 * i + 6] = h[6 * (size_t)n + i]; en[9 * i + 7] = h[7 * (size_t)n + i]; en[9 * i + 8] = h[8 * (size_t)n + i];
-    }
-    if (c->a_pend.structure) {
-        memcpy(gr, h + 9 * (size_t)n, c->a_pend.ng * sizeof(double));
-        if (c->a_pend.nk) memcpy(Sk, h + 9 * (size_t)n + c->a_pend.ng, c->a_pend.nk * sizeof(double));
-    }
+    est_unpack(b, (const double *)c->a_host.h, en, gr, Sk);
     return PIGS_OK;
 }
 
@@ -1298,8 +1289,8 @@ int pigs_comm_init_rank(pigs_ctx *c, int32_t nranks, int32_t rank, const char id
 {
     int rc = check_ctx(c); if (rc) return rc;
     if (nranks < 1 || rank < 0 || rank >= nranks || !id) return fail(PIGS_ERR_ARG, "bad rank %d/%d", rank, nranks);
-    if (c->comm) { pigs_comm_destroy(c->comm); c->comm = nullptr; }
-    const char *err = pigs_comm_create_rank(&c->comm, nranks, rank, id);
+    c->comm.reset();
+    const char *err = pigs_comm_create_rank(&c->comm.h, nranks, rank, id);
     return err ? fail(PIGS_ERR_COMM, "%s", err) : PIGS_OK;
 }
 
@@ -1315,7 +1306,7 @@ int pigs_comm_init_all(pigs_ctx **ctxs, int32_t nranks)
         for (int k = 0; k < i; ++k) distinct = distinct && devs[k] != devs[i];
     }
     for (int i = 0; i < nranks; ++i) {
-        if (ctxs[i]->comm) { pigs_comm_destroy(ctxs[i]->comm); ctxs[i]->comm = nullptr; }
+        ctxs[i]->comm.reset();
         ctxs[i]->hgroup.reset();
     }
     if (!distinct) {
@@ -1342,7 +1333,7 @@ int pigs_comm_init_all(pigs_ctx **ctxs, int32_t nranks)
     }
     const char *err = pigs_comm_create_all(comms.data(), nranks, devs.data());
     if (err) return fail(PIGS_ERR_COMM, "%s", err);
-    for (int i = 0; i < nranks; ++i) ctxs[i]->comm = comms[i];
+    for (int i = 0; i < nranks; ++i) ctxs[i]->comm.h = comms[i];
     return PIGS_OK;
 }
 
@@ -1373,12 +1364,12 @@ int pigs_estimators_allreduce(pigs_ctx *c, double *vec, int32_t n)
         return PIGS_OK;
     }
     if (!c->comm) return fail(PIGS_ERR_COMM, "no communicator: call pigs_comm_init_rank / pigs_comm_init_all first");
-    HIPCHK(c->d_res.reserve(n));
+    HIPCHK(c->est.res.reserve(n));
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(c->d_res.p, vec, n * sizeof(double), hipMemcpyHostToDevice, s));
-    const char *err = pigs_comm_allreduce_sum_f64(c->comm, c->d_res.p, n, s);
+    HIPCHK(hipMemcpyAsync(c->est.res.p, vec, n * sizeof(double), hipMemcpyHostToDevice, s));
+    const char *err = pigs_comm_allreduce_sum_f64(c->comm, c->est.res.p, n, s);
     if (err) return fail(PIGS_ERR_COMM, "%s", err);
-    HIPCHK(hipMemcpyAsync(vec, c->d_res.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(vec, c->est.res.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
     SYNC_CHECKED(c);
     return PIGS_OK;
 }

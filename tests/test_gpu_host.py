@@ -478,7 +478,7 @@ def test_samplers_agree_bit_for_bit_over_hundreds_of_steps(exe, tmp_path, sampli
 def test_sampler_choice_is_automatic_when_left_out(exe, tmp_path):
     """&gpu without device_sampler: the front end takes the device-resident sampler where it serves the input (and says so)
     -- same files as the reference run -- and the host-driven one where it does not (a trapped system with Nlev = 5: K6's
-    trap form stops at four levels)."""
+    trap form stops at four levels; a periodic one with Nlev = 5 and an odd Nmax: no stage-machine kernel)."""
     src = os.path.join(RUNS, "he4_worm_s1982")
     a = tmp_path / "auto"; a.mkdir()
     _run(exe, open(os.path.join(src, "vpi.in")).read(), str(a))
@@ -509,6 +509,34 @@ def test_sampler_choice_is_automatic_when_left_out(exe, tmp_path):
 """
     _run(exe, inp, str(b))
     assert "host-driven (the device-resident sampler does not serve" in open(b / "stdout.txt").read()
+    # a periodic 'bis' input with Nlev = 5 needs the stage-machine kernel, which an odd Nmax rules out: pigs_sampler_init
+    # says so, and the run is the host-driven one (it used to abort at the first MC step)
+    inp = """&system
+ dim = 2, Np = 6, density = 0.1d0, trap = F
+/
+&samp
+ resume = F, dt = 1.0d-2, Nb = 16, seed = 11, delta_cm = 0.2d0, CMFreq = 1, sampling = 'bis', Lstag = 4, Nlev = 5, Nstag = 2,
+ Nblock = 1, Nstep = 5, Nbin = 50, Nk = 10
+/
+&obdm
+ swapping = T, CWorm = 0.0d0, Nobdm = 0, Npw = 0
+/
+&wavefun
+ Nmax = 4001, wf_table = T, v_table = T
+/
+&jastrow
+ Rm = 1.10d0
+/
+"""
+    d = tmp_path / "odd_nmax"; d.mkdir()
+    _run(exe, inp, str(d))
+    assert "host-driven (the device-resident sampler does not serve" in open(d / "stdout.txt").read()
+    h = tmp_path / "odd_nmax_host"; h.mkdir()
+    _run(exe, inp + "&gpu\n device_sampler = F\n/\n", str(h))
+    files = sorted(f for f in os.listdir(h) if f not in ("stdout.txt", "vpi.in"))
+    assert files == sorted(f for f in os.listdir(d) if f not in ("stdout.txt", "vpi.in")) and "worldlines_final.bin" in files
+    for f in files:
+        assert open(d / f, "rb").read() == open(h / f, "rb").read(), f
 
 
 def test_gpu_device_sampler_with_the_references_default_nlev_1(exe, tmp_path):
