@@ -207,6 +207,11 @@ int pigs_sampler_set_rng(pigs_ctx *ctx, int32_t walker, int32_t mti, const int32
 int pigs_sampler_get_rng(pigs_ctx *ctx, int32_t walker, int32_t *mti, int32_t mt[624]);
 /* one MC step (istep is the 1-based step number: CM moves when mod(istep,CMFreq)==0); asynchronous */
 int pigs_sampler_step(pigs_ctx *ctx, int32_t istep);
+/* the form the sampler runs in (read only, changes nothing): out[0] threads per workgroup of the sweep kernel,
+ * out[1] H = workgroups per walker of the TranslateChain kernel in the last step with CM moves (0: TranslateChain ran
+ * inside the sweep kernel; -1: no such step yet), out[2] 1 if the last step ran the stage-machine kernel (pigs_diag.hip),
+ * out[3] 1 if the context samples next to other contexts on its device (tuning key "cm_shared") */
+int pigs_sampler_form(pigs_ctx *ctx, int32_t out[4]);
 /* accepted-move counters per walker since pigs_sampler_init: acc[4*w+{0,1,2,3}] = CM, head, tail, bisection */
 int pigs_sampler_counters(pigs_ctx *ctx, int64_t *acc);
 /* accepted/attempted counters per walker since pigs_sampler_init, 16 per walker:

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "pigs_set_tuning", "pigs_selftest_fastmath", "pigs_selftest_stream_read", "pigs_selftest_log",
     "pigs_stage_reserve", "pigs_delta_action_staged", "pigs_commit_reserve", "pigs_commit_staged",
     "pigs_sampler_init", "pigs_sampler_seed", "pigs_sampler_set_rng", "pigs_sampler_get_rng", "pigs_sampler_step",
-    "pigs_sampler_counters", "pigs_sampler_counters16", "pigs_sampler_get_worm", "pigs_sampler_set_worm",
+    "pigs_sampler_form", "pigs_sampler_counters", "pigs_sampler_counters16", "pigs_sampler_get_worm", "pigs_sampler_set_worm",
     "pigs_sampler_events", "pigs_sampler_event_ints", "pigs_sampler_nrho", "pigs_slice_download", "pigs_build_tables_kind", "pigs_structure_batch",
     "pigs_diagonal_estimators", "pigs_diagonal_estimators_begin", "pigs_diagonal_estimators_end",
 ]
@@ -108,6 +108,7 @@ def load_library(path=LIB_PATH):
     L.pigs_sampler_set_rng.argtypes = [vp, C.c_int32, C.c_int32, _ip]
     L.pigs_sampler_get_rng.argtypes = [vp, C.c_int32, _ip, _ip]
     L.pigs_sampler_step.argtypes = [vp, C.c_int32]
+    L.pigs_sampler_form.argtypes = [vp, _ip]
     L.pigs_sampler_counters.argtypes = [vp, C.POINTER(C.c_int64)]
     L.pigs_sampler_counters16.argtypes = [vp, C.POINTER(C.c_int64)]
     L.pigs_sampler_get_worm.argtypes = [vp, _ip, _ip, _dp]
@@ -351,6 +352,13 @@ class PigsContext:
 
     def sampler_step(self, istep):
         _chk(self.L, self.L.pigs_sampler_step(self.h, int(istep)), "pigs_sampler_step")
+
+    def sampler_form(self):
+        """The form the sampler runs in: dict(sweep_threads, cm_H (workgroups per walker of the last step's TranslateChain
+        kernel; 0: inside the sweep kernel, -1: no TranslateChain yet), stage_machine, cm_shared)."""
+        out = np.zeros(4, np.int32)
+        _chk(self.L, self.L.pigs_sampler_form(self.h, _i(out)), "pigs_sampler_form")
+        return dict(sweep_threads=int(out[0]), cm_H=int(out[1]), stage_machine=bool(out[2]), cm_shared=bool(out[3]))
 
     def sampler_counters(self):
         acc = np.zeros((self.n_walkers, 4), np.int64)

@@ -181,6 +181,8 @@ struct pigs_ctx {
     DevBuf<unsigned long long> d_xch;       // exchange buffer of the cooperating workgroups
     PinBuf      h_cm_err;                   // (one int) set by a workgroup whose partner never answered
     unsigned int cm_seq = 1;                // sequence tags of the exchange: advanced by every launch
+    int         form_cm = -1;               // H of the last step's TranslateChain (0: inside the sweep kernel): pigs_sampler_form
+    bool        form_diag = false;          // the last step ran the stage-machine kernel
     bool        sampler_ready = false;
     // asynchronous estimators (pigs_diagonal_estimators_begin / _end): a snapshot of the worldlines and a second stream
     Stream      stream2;
@@ -754,6 +756,8 @@ int pigs_sampler_init(pigs_ctx *c, const pigs_sweep_params *sp)
     if (worm && (sp->Nobdm < 0 || sp->Nbin < 1 || sp->Npw < 0 || !(sp->rbin > 0.0) || !(sp->density > 0.0)))
         return fail(PIGS_ERR_ARG, "worm parameters out of range");
     c->sampler_ready = false;                 // until this call has gone through
+    c->form_cm = -1;
+    c->form_diag = false;
     SweepParams &k = c->sweep;
     memset(&k, 0, sizeof k);
     k.Nlev = sta ? 1 : sp->Nlev; k.Nstag = sp->Nstag; k.Lstag = sp->Lstag; k.staging = sta;
@@ -867,6 +871,7 @@ int pigs_sampler_step(pigs_ctx *c, int32_t istep)
         // second live context, and the sharded front end on one GPU, failed here with "invalid argument")
         if (H >= 1 && !cm_fits(c->P, H)) H = 0;
     }
+    if (sp.do_cm) c->form_cm = H;
     bool cm_done = false;
     if (H >= 1) {
         if (!c->d_xch.p) {
@@ -910,7 +915,8 @@ int pigs_sampler_step(pigs_ctx *c, int32_t istep)
     }
     // (pigs_sampler_init refused the inputs that need the stage machine where it does not fit)
     const bool need_split = !c->P.trap && !sp.staging && sp.Nlev > 4;
-    if ((c->sweep_split || need_split) && diag_supported(c->P, sp)) {
+    c->form_diag = (c->sweep_split || need_split) && diag_supported(c->P, sp);
+    if (c->form_diag) {
         if (!cm_done) {
             sp.parts = 1;
             HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
@@ -927,6 +933,17 @@ int pigs_sampler_step(pigs_ctx *c, int32_t istep)
         HIPCHK(launch_sweep(c->P, sp, c->sweep_threads, c->d_paths.p, c->d_VT.p, c->d_VTimg.p, c->d_WF.p, c->d_rng.p, c->d_counters.p,
                             c->d_worm.p, c->d_evlog.p, c->d_nrho.p, c->d_dklog.p, c->stream));
     }
+    return PIGS_OK;
+}
+
+int pigs_sampler_form(pigs_ctx *c, int32_t out[4])
+{
+    if (!c || !out) return fail(PIGS_ERR_ARG, "null pointer");
+    if (!c->sampler_ready) return fail(PIGS_ERR_ARG, "pigs_sampler_init first");
+    out[0] = sweep_form(c->P, c->sweep, c->sweep_threads);   // what launch_sweep makes of the tuned value
+    out[1] = c->form_cm;
+    out[2] = c->form_diag ? 1 : 0;
+    out[3] = c->cm_shared ? 1 : 0;
     return PIGS_OK;
 }
 

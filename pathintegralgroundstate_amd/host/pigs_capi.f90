@@ -263,6 +263,14 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_sampler_counters
 
+     ! (pigs_sampler_form is looked up at run time: see sampler_form below)
+     function c_dlsym(handle,name) bind(C,name='dlsym') result(p)
+       import :: c_ptr, c_funptr, c_char
+       type(c_ptr), value :: handle
+       character(kind=c_char), intent(in) :: name(*)
+       type(c_funptr) :: p
+     end function c_dlsym
+
      function pigs_sampler_counters16(ctx,cnt) bind(C,name='pigs_sampler_counters16') result(rc)
        import :: c_int, c_int64_t, c_ptr
        type(c_ptr), value :: ctx
@@ -377,7 +385,32 @@ module pigs_capi
 
   end interface
 
+  abstract interface
+     function pigs_sampler_form_t(ctx,out) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int32_t) :: out(4)
+       integer(c_int) :: rc
+     end function pigs_sampler_form_t
+  end interface
+
 contains
+
+  ! pigs_sampler_form (the kernel form the device-resident sampler ran in) where the backend exports it: a report, not
+  ! a dependency -- found at run time in the process's libraries (dlsym with RTLD_DEFAULT = NULL), so the host still links
+  ! against backends without it.  .false. where it is not there.
+  logical function sampler_form(ctx,form)
+    type(c_ptr), intent(in)         :: ctx
+    integer(c_int32_t), intent(out) :: form(4)
+    type(c_funptr) :: f
+    procedure(pigs_sampler_form_t), pointer :: query
+    form = 0
+    f = c_dlsym(c_null_ptr,'pigs_sampler_form'//c_null_char)
+    sampler_form = c_associated(f)
+    if (.not. sampler_form) return
+    call c_f_procpointer(f,query)
+    call pigs_check(query(ctx,form),'pigs_sampler_form')
+  end function sampler_form
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

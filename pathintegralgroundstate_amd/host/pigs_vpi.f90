@@ -811,6 +811,15 @@ contains
     chk_all(:,:,:,w0+1:w0+NW) = chk
   end block
 
+  ! the form the device-resident sampler ran its last step in (pigs_sampler_form): tests check they ran the form they meant to
+  if (device_sampler .and. ish==1) then
+     block
+       integer(c_int32_t) :: form(4)
+       if (sampler_form(ctx,form)) print '(a,i5,a,i2,a,l2,a,l2)','  > sampler form: sweep threads',form(1),', TranslateChain workgroups per walker',form(2), &
+            & ', stage machine',form(3)/=0,', shared',form(4)/=0
+     end block
+  end if
+
   call sampler_free(s)
   end subroutine run_shard
 

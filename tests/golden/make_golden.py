@@ -8,6 +8,9 @@ restatement.  The fixtures are data: inputs + expected outputs, no reference sou
 
     python tests/golden/make_golden.py
 
+`python tests/golden/make_golden.py walkers [set ...]` writes only the many-seed sets (WALKER_SETS); they run the
+reference once per seed on a pool of processes sized by the affinity mask (at most 16).
+
 The reference's answers behind tests/test_oracle_vs_ref.py and tests/test_host_sampler.py (tests/golden/ref_tapes/)
 are recorded by those tests themselves (tests/reftape.py):
 
@@ -361,6 +364,99 @@ def make_runs(only=None):
     print("reference program runs written to", base)
 
 
+# ---------------------------------------------------------------------------------------------
+# Many seeds of one BASELINE-size input: vpi_runs/<set>/walkers.npz holds, row by row, the reference's answer for seed
+# seed0 + w -- the front end seeds walker w with seed + w, so row w is walker w of a front-end run with the input's seed,
+# and the first rows are the device sampler's walkers at the occupancies bench.py runs (tests/test_gpu_sampler_occupancy.py).
+# Per row only what pins a run: final generator position and a SHA-256 of its 624 words, the 16 counters, the final
+# worldline's SHA-256, every step's energies, the block averages; with the worm sector also the worm state, the event log
+# (padded with zeros to the longest, plus its length) and the OBDM histogram.  gr_total / sk_total are summed over the
+# first N_SUMMED rows: what the front end's walker-summed gr_vpi.out / sk_vpi.out hold at N_SUMMED walkers.
+WALKER_SETS = {
+    "c3_n256_walkers": dict(base="c3_n256_s1982", n_seeds=1024),
+    "c5_n256_dipolar_walkers": dict(base="c5_n256_dipolar_s1982", n_seeds=128),
+}
+N_SUMMED = 128
+
+_W = {}
+
+
+def _walker_init(kw, VT):
+    sys.path.insert(0, OUT)
+    _W.update(ref=Ref(), kw=kw, VT=VT)
+
+
+def _walker_run(seed):
+    import hashlib
+    kw = dict(_W["kw"], seed=seed)
+    _, res = drive_run(_W["ref"], kw, _W["VT"])
+    sha = lambda a: np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)   # noqa: E731
+
+    def blocks(rows):               # a block without a diagonal step has no row: padded to Nblock rows, block number 0
+        out = np.zeros((kw["Nblock"], 4))
+        out[:len(rows)] = rows
+        return out
+    out = dict(mti=np.int32(res["mti"]), mt_sha256=sha(np.asarray(res["mt"], np.uint32)), counters=res["counters"],
+               Path_sha256=sha(res["Path"]), steps=res["steps"], block_e=blocks(res["block_e"]),
+               block_t=blocks(res["block_t"]),
+               gr_total=res["gr_total"], sk_total=res["sk_total"], Path_shape=np.array(res["Path"].shape))
+    if _fnum(kw["CWorm"]) > 0:
+        out.update(isopen=np.int32(res["isopen"]), iworm=np.int32(res["iworm"]), xend=res["xend"], events=res["events"],
+                   nrho_total=res["nrho_total"])
+    return out
+
+
+def make_walker_sets(only=None):
+    import multiprocessing as mp
+    import shutil
+    import time
+    from pathintegralgroundstate_amd import SystemConfig, api
+    nproc = min(16, len(os.sched_getaffinity(0)))
+    for name, spec in WALKER_SETS.items():
+        if only and name not in only:
+            continue
+        kw = dict(RUNS[spec["base"]])
+        kw.pop("big", None)
+        potential = kw.pop("potential", "aziz2")
+        kw.pop("driver", None)
+        dst = os.path.join(OUT, "vpi_runs", name)
+        os.makedirs(dst, exist_ok=True)
+        shutil.copy(os.path.join(OUT, "vpi_runs", spec["base"], "vpi.in"), os.path.join(dst, "vpi.in"))
+        VT = None
+        if potential != "aziz2":
+            cfg = SystemConfig.from_namelists(open(os.path.join(dst, "vpi.in")).read())
+            VT, _ = api.build_tables(cfg, potential)
+        seeds = kw["seed"] + np.arange(spec["n_seeds"])
+        t0 = time.time()
+        # processes, not threads: the reference keeps its state in module globals
+        with mp.get_context("spawn").Pool(nproc, initializer=_walker_init, initargs=(kw, VT)) as pool:
+            rows = []
+            for i, r in enumerate(pool.imap(_walker_run, [int(s) for s in seeds], chunksize=1)):
+                rows.append(r)
+                if (i + 1) % 64 == 0:
+                    print(f"{name}: {i + 1}/{len(seeds)} seeds, {time.time() - t0:.0f} s", flush=True)
+        out = {k: np.stack([r[k] for r in rows]) for k in ("mti", "mt_sha256", "counters", "Path_sha256", "steps",
+                                                           "block_e", "block_t")}
+        out.update(seed=seeds.astype(np.int64), Path_shape=rows[0]["Path_shape"], potential=np.array(potential),
+                   n_summed=np.int32(N_SUMMED))
+        gr, sk = np.zeros_like(rows[0]["gr_total"]), np.zeros_like(rows[0]["sk_total"])
+        for r in rows[:N_SUMMED]:                                   # walker order, as the front end adds them
+            gr += r["gr_total"]
+            sk += r["sk_total"]
+        out.update(gr_total=gr, sk_total=sk)
+        if "events" in rows[0]:
+            nev = np.array([len(r["events"]) for r in rows], np.int32)
+            ev = np.zeros((len(rows), max(1, int(nev.max())), 3), np.int64)
+            for i, r in enumerate(rows):
+                ev[i, :nev[i]] = r["events"]
+            out.update(isopen=np.stack([r["isopen"] for r in rows]), iworm=np.stack([r["iworm"] for r in rows]),
+                       xend=np.stack([r["xend"] for r in rows]), events=ev, n_events=nev,
+                       nrho_total=np.stack([r["nrho_total"] for r in rows]))
+        np.savez_compressed(os.path.join(dst, "walkers.npz"), **out)
+        print(f"{name}: {len(seeds)} seeds on {nproc} processes in {time.time() - t0:.0f} s, "
+              f"{os.path.getsize(os.path.join(dst, 'walkers.npz'))} bytes", flush=True)
+
+
 def make_resume_fixture():
     """Reference run A (2 blocks) leaves checkpoint.dat + rand_state; reference run B resumes from them
     for 2 more blocks (quirk Q10: it reads the FIRST rand_state record, i.e. the state after block 1)."""
@@ -449,6 +545,8 @@ if __name__ == "__main__":
         main()
     if what in ("all", "runs"):
         make_runs(set(sys.argv[2:]) or None)
+    if what in ("all", "walkers"):
+        make_walker_sets(set(sys.argv[2:]) or None)
     if what in ("all", "resume"):
         make_resume_fixture()
     if what in ("all", "crystal"):

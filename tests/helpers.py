@@ -133,3 +133,38 @@ def block_energy_errors(rows, want):
 # host-driven one since round 1, the device-resident one since its Box-Muller log() became the host libm's bit for bit
 # (csrc/pigs_log_host.h, round 3; rounds 1-2 allowed 2e-9 here).
 MIXED_TOL = 1e-10
+
+
+# ---- many seeds of one input: tests/golden/vpi_runs/<set>/walkers.npz (tests/golden/make_golden.py, WALKER_SETS) ----
+def walker_row(W, w):
+    """Row w of a walkers.npz (the reference run of seed W["seed"][w]) as a driver.npz-like dict: the generator words as
+    their SHA-256 (mt_sha256) in place of mt, the padding of the block rows (block number 0: a block without a diagonal
+    step) and of the event log dropped."""
+    r = {k: W[k][w] for k in ("seed", "mti", "mt_sha256", "counters", "Path_sha256", "steps")}
+    for k in ("block_e", "block_t"):
+        r[k] = W[k][w][W[k][w][:, 0] > 0]
+    r["Path_shape"], r["potential"] = W["Path_shape"], W["potential"]
+    if "events" in W:
+        r.update(isopen=W["isopen"][w], iworm=W["iworm"][w], xend=W["xend"][w], events=W["events"][w, :W["n_events"][w]],
+                 nrho_total=W["nrho_total"][w])
+    else:
+        r["events"] = np.zeros((0, 3), np.int64)             # no worm sector: no events
+    return r
+
+
+def rng_sha256(words):
+    """SHA-256 of a generator's 624 words (as walkers.npz stores them)."""
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(words, np.uint32).tobytes()).digest(), np.uint8)
+
+
+def walker_summed_structure(cfg, gr_total, sk_total, n_walkers, ngr):
+    """g(r) and S(k) columns of the front end's walker-summed gr_vpi.out / sk_vpi.out (host/pigs_estimators.f90:
+    normalize_gr, normalize_sk, write_radial, write_sk) for a run of ONE block in which each of n_walkers walkers made ngr
+    diagonal steps, from the raw histograms summed over walkers and steps (gr_total (Nbin,), sk_total (Nk, dim))."""
+    from math import gamma, pi
+    dim = cfg.dim
+    r = (np.arange(1, cfg.Nbin + 1) - 0.5) * cfg.rbin
+    nid = cfg.density * pi ** (0.5 * dim) / gamma(0.5 * dim + 1.0) * ((r + 0.5 * cfg.rbin) ** dim - (r - 0.5 * cfg.rbin) ** dim)
+    norm = float(cfg.Np) * float(ngr)
+    return gr_total / (nid * norm) / n_walkers, sk_total / norm / n_walkers

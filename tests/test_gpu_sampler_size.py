@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from helpers import MIXED_TOL, check_worldline_vs_driver, fold_maxnorm
+from helpers import MIXED_TOL, check_worldline_vs_driver, fold_maxnorm, rng_sha256
 from pathintegralgroundstate_amd import SystemConfig
 
 pytestmark = pytest.mark.gpu
@@ -31,64 +31,90 @@ def _cfg(name):
     return SystemConfig.from_namelists(open(os.path.join(RUNS, name, "vpi.in")).read())
 
 
-def run_k6(gpu_lib, oracle, names, threads=None, split=0, cm=None):
+def run_k6(gpu_lib, oracle, names, threads=None, split=0, cm=None, rows=None, overlap=False):
     """The reference's block loop (vpi.f90:244-545) around pigs_sampler_step for the runs `names` (same input, one
     walker per seed).  Returns per walker: per-step rows [diag, E, Kin, Pot, Et, Kt], final worldline, counters16,
-    generator state, worm state, events, OBDM histogram."""
+    generator state, worm state, events, OBDM histogram; and the form the sampler ran in (pigs_sampler_form).
+    rows: per-walker reference answers (helpers.walker_row of a walkers.npz) in place of the runs' driver.npz -- walker w
+    then runs the input of names[0] with seed rows[w]["seed"].  overlap: the diagonal steps' estimators through
+    diagonal_estimators_begin / _end, queued behind the next step as the front end queues them (host/pigs_vpi.f90:
+    426-438, 600-610), g(r) and S(k) included and summed over walkers and steps (CWorm = 0 inputs)."""
     from oracle.pyoracle import System
     cfg = _cfg(names[0])
-    drv = [dict(np.load(os.path.join(RUNS, n, "driver.npz"))) for n in names]
+    if rows is None:
+        drv = [dict(np.load(os.path.join(RUNS, n, "driver.npz"))) for n in names]
+        seeds = [_cfg(n).seed for n in names]
+    else:
+        drv, seeds = rows, [int(r["seed"]) for r in rows]
+    assert not overlap or cfg.CWorm == 0
     pot = str(drv[0]["potential"])
     S = System(dim=cfg.dim, Np=cfg.Np, Nb=cfg.Nb, density=cfg.density, dt=cfg.dt, trap=cfg.trap, a_ho=cfg.a_ho,
                Lbox=cfg.Lbox, rcut=cfg.rcut)
     VT, WF = gpu_lib.build_tables(cfg, pot)
-    W = len(names)
-    ctx = gpu_lib.PigsContext(cfg, VT, WF, n_walkers=W)
-    ctx.sampler_init(CWorm=cfg.CWorm, swapping=cfg.swapping, Nobdm=cfg.Nobdm, Nbin=cfg.Nbin, Npw=cfg.Npw,
-                     sampling=cfg.sampling)
-    if threads:
-        ctx.set_tuning("sweep_threads", threads)
-    ctx.set_tuning("sweep_split", split)          # 1: the diagonal bisection moves in pigs_diag.hip's stage machine
-    if cm is not None:
-        ctx.set_tuning("cm_split", cm)            # TranslateChain by `cm` workgroups per walker (pigs_cm.hip); 0: inside the sweep kernel
-    Paths, xends = [], []
-    for w, n in enumerate(names):
-        P, g = oracle.init_path(S, _cfg(n).seed)
-        Paths.append(P)
-        xends.append(np.stack([P[cfg.Nb, cfg.Np - 1], P[cfg.Nb, cfg.Np - 1]]))
-        ctx.sampler_set_rng(w, g.mti, np.array(g.mt[:], np.uint32))
-    ctx.upload_all(np.stack(Paths))
-    ctx.sampler_set_worm(np.zeros(W, np.int32), np.zeros(W, np.int32), np.stack(xends))
-    steps = [[] for _ in range(W)]
-    events = [[] for _ in range(W)]
-    g = 0
-    for ib in range(cfg.Nblock):
-        for istep in range(1, cfg.Nstep + 1):
-            g += 1
-            ctx.sampler_step(istep)
-            if cfg.CWorm > 0:
-                ev = ctx.sampler_events()
-                isopen = ev[:, 1] != 0
-                for w in range(W):
-                    events[w] += [(g, int(ev[w, 2 + 2 * i]), int(ev[w, 3 + 2 * i])) for i in range(ev[w, 0])]
-            else:
-                isopen = np.zeros(W, bool)
-            closed = np.flatnonzero(~isopen)
-            rows = np.full((W, 6), np.nan)
-            rows[:, 0] = ~isopen
-            if len(closed):
-                E1, _, _ = ctx.local_energy_batch(0, closed)
-                E2, _, _ = ctx.local_energy_batch(2 * cfg.Nb, closed)
-                Et, Kt, Pt = ctx.therm_energy_batch(closed)
-                E = 0.5 * (E1 + E2)
-                rows[closed, 1:] = np.stack([E, E - Pt, Pt, Et, Kt], 1)
+    W = len(drv)
+    with gpu_lib.PigsContext(cfg, VT, WF, n_walkers=W) as ctx:
+        ctx.sampler_init(CWorm=cfg.CWorm, swapping=cfg.swapping, Nobdm=cfg.Nobdm, Nbin=cfg.Nbin, Npw=cfg.Npw,
+                         sampling=cfg.sampling)
+        if threads:
+            ctx.set_tuning("sweep_threads", threads)
+        ctx.set_tuning("sweep_split", split)          # 1: the diagonal bisection moves in pigs_diag.hip's stage machine
+        if cm is not None:
+            ctx.set_tuning("cm_split", cm)            # TranslateChain by `cm` workgroups per walker (pigs_cm.hip); 0: inside the sweep kernel
+        xends = []
+        for w, seed in enumerate(seeds):              # one walker at a time: 1 024 worldlines of 161 beads are 1 GB
+            P, g = oracle.init_path(S, seed)
+            ctx.upload(w, P)
+            xends.append(np.stack([P[cfg.Nb, cfg.Np - 1], P[cfg.Nb, cfg.Np - 1]]))
+            ctx.sampler_set_rng(w, g.mti, np.array(g.mt[:], np.uint32))
+        ctx.sampler_set_worm(np.zeros(W, np.int32), np.zeros(W, np.int32), np.stack(xends))
+        steps = [[] for _ in range(W)]
+        events = [[] for _ in range(W)]
+        gr_sum, sk_sum = np.zeros(cfg.Nbin), np.zeros((cfg.Nk, cfg.dim))
+
+        def collect():                                # the pending batch of diagonal_estimators_begin
+            nonlocal gr_sum, sk_sum
+            e = ctx.diagonal_estimators_end()
+            E = 0.5 * (e["E1"] + e["E2"])
+            rows_ = np.stack([np.ones(W), E, E - e["Vt"], e["Vt"], e["Et"], e["Kt"]], 1)
+            gr_sum = gr_sum + e["gr"].sum(0)
+            sk_sum = sk_sum + e["Sk"].sum(0)
             for w in range(W):
-                steps[w].append(rows[w])
-    out = dict(cfg=cfg, drv=drv, steps=[np.array(s) for s in steps], final=ctx.download_all(),
-               counters=ctx.sampler_counters16(), rng=[ctx.sampler_get_rng(w) for w in range(W)],
-               worm=ctx.sampler_get_worm() if cfg.CWorm > 0 else None, events=events,
-               nrho=ctx.sampler_nrho() if cfg.CWorm > 0 and cfg.Nobdm > 0 else None)
-    ctx.close()
+                steps[w].append(rows_[w])
+        g = 0
+        for ib in range(cfg.Nblock):
+            for istep in range(1, cfg.Nstep + 1):
+                g += 1
+                ctx.sampler_step(istep)
+                if overlap:
+                    if istep > 1:                     # the previous step's estimators, computed while this step ran
+                        collect()
+                    ctx.diagonal_estimators_begin(cfg.Nbin, cfg.rbin, cfg.Nk)
+                    continue
+                if cfg.CWorm > 0:
+                    ev = ctx.sampler_events()
+                    isopen = ev[:, 1] != 0
+                    for w in range(W):
+                        events[w] += [(g, int(ev[w, 2 + 2 * i]), int(ev[w, 3 + 2 * i])) for i in range(ev[w, 0])]
+                else:
+                    isopen = np.zeros(W, bool)
+                closed = np.flatnonzero(~isopen)
+                rows_ = np.full((W, 6), np.nan)
+                rows_[:, 0] = ~isopen
+                if len(closed):
+                    E1, _, _ = ctx.local_energy_batch(0, closed)
+                    E2, _, _ = ctx.local_energy_batch(2 * cfg.Nb, closed)
+                    Et, Kt, Pt = ctx.therm_energy_batch(closed)
+                    E = 0.5 * (E1 + E2)
+                    rows_[closed, 1:] = np.stack([E, E - Pt, Pt, Et, Kt], 1)
+                for w in range(W):
+                    steps[w].append(rows_[w])
+            if overlap:                               # the block's last step: collected before the block ends
+                collect()
+        out = dict(cfg=cfg, drv=drv, steps=[np.array(s) for s in steps], final=ctx.download_all(),
+                   counters=ctx.sampler_counters16(), rng=[ctx.sampler_get_rng(w) for w in range(W)],
+                   worm=ctx.sampler_get_worm() if cfg.CWorm > 0 else None, events=events,
+                   nrho=ctx.sampler_nrho() if cfg.CWorm > 0 and cfg.Nobdm > 0 else None, form=ctx.sampler_form(),
+                   gr_sum=gr_sum if overlap else None, sk_sum=sk_sum if overlap else None)
     return out
 
 
@@ -97,7 +123,10 @@ def check_against_driver(r, w):
     # random stream: same block, same index, same words
     pos, words = r["rng"][w]
     assert int(pos) == int(drv["mti"]), (pos, drv["mti"])
-    assert np.array_equal(np.asarray(words, np.uint32), drv["mt"].astype(np.uint32))
+    if "mt" in drv:
+        assert np.array_equal(np.asarray(words, np.uint32), drv["mt"].astype(np.uint32))
+    else:                                                   # a walkers.npz row keeps the words' SHA-256
+        assert np.array_equal(rng_sha256(words), drv["mt_sha256"])
     # decisions
     assert np.array_equal(np.asarray(r["counters"][w], np.int64), drv["counters"]), (r["counters"][w], drv["counters"])
     assert [tuple(e) for e in r["events"][w]] == [tuple(int(x) for x in e) for e in drv["events"]]
