@@ -261,6 +261,27 @@ __device__ __forceinline__ double min_image_rn(double (&x)[DIM], const DevParams
     return r2;
 }
 
+// r^2 alone, for the beads that never use the signed components (even and end beads: no force term).  Per component
+// m = min(|v|, L - |v|) -- one v_add_f64 (neg/abs modifiers) and one v_min_f64 (abs modifier) where min_image_rn takes
+// four -- and m*m equals, bit for bit, the square of the two compares of pbc_mod.f90:40-41 (one fold) for every input:
+//   |v| <= L/2: L - |v| >= |v|, so m = |v|;  L/2 < |v| <= 2L: L - |v| is exact (Sterbenz) and equals minus the folded
+//   value;  beyond 2L both round the same magnitude;  a tie at L/2 gives L/2 either way;  +-Inf gives -Inf (square
+//   +Inf);  NaN stays NaN.
+// min_image_rn differs from the two compares only for |v| within about an ulp of L/2 (it decides the fold on
+// RN(|v| RN(1/L))): there this form agrees with the reference and min_image_rn does not.
+template <int DIM>
+__device__ __forceinline__ double min_image_mag(const double (&x)[DIM], const DevParams &P)
+{
+    double r2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+        const double a = __builtin_fabs(x[k]);
+        const double m = __builtin_fmin(a, P.Lbox[k] - a);
+        r2 = r2 + m * m;                                          // the reference's rounding sequence
+    }
+    return r2;
+}
+
 struct FCell {
     int    i0;        // int(r/dr) = ix-1 of the reference
     double f, omf;    // position inside the cell, 1-f

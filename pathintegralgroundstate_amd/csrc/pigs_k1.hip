@@ -22,6 +22,8 @@
 //            depend on how many other items share its launch
 //   14 reference order (validation): exact-term arithmetic, per-partner terms parked in LDS and added by one lane
 //            per accumulator in the reference's jp order -- every bit of Delta S equals the reference's
+#include <atomic>
+
 #include "pigs_device.h"
 #include "pigs_k1_device.h"
 #include "pigs_kernels.h"
@@ -507,8 +509,8 @@ __device__ __forceinline__ void pipe2_pass(const DevParams &P, PipeTab VT, const
                                                                               // from hoisting all four passes' distance arithmetic above the class branch (spills)
         dn[k] = R.xn[k] - rj; dold[k] = R.xo[k] - rj;
     }
-    const double r2o = min_image_rn<DIM>(dold, P);
-    const double r2n = min_image_rn<DIM>(dn, P);
+    const double r2o = pipe_r2<DIM, CLS>(dold, P);
+    const double r2n = pipe_r2<DIM, CLS>(dn, P);
     pipe_pair<DIM, CLS, false>(P, VT, WF, floor_r2(r2n), valid && r2n <= P.rcut2, dn, A);
     pipe_pair<DIM, CLS, true>(P, VT, WF, floor_r2(r2o), valid && r2o <= P.rcut2, dold, A);
     __builtin_amdgcn_sched_barrier(0);
@@ -561,6 +563,19 @@ __device__ __forceinline__ void pipe2_item(const DevParams &P, PipeTab VT, const
     finish_item<DIM, CLS>(P, lane, R.b, A, red, out, parts);
 }
 
+// -DPIGS_EXPERIMENT_K1_CLOCK (experiment builds only): lane 0 of every pipe2 wave records, with an ordinary global
+// store at its end, four s_memrealtime stamps (100 MHz, one clock for the whole chip) and its item count into
+// k1_clock[(blockIdx * 16 + wave) * 5]: entry, its own first-item loads and table chunks landed (vmcnt 0), past the
+// workgroup barrier (the first table lookup follows within one pass's distance arithmetic), end.  The last launch's
+// record is read by pigs_k1_clock_read(); scripts/k1_head.py turns it into the head / tail split of profiles/r04_*.
+#ifdef PIGS_EXPERIMENT_K1_CLOCK
+constexpr int kK1ClockWaves = 16 * 1024;
+__device__ unsigned long long k1_clock[kK1ClockWaves * 5];
+#define K1STAMP(v) const unsigned long long v = __builtin_amdgcn_s_memrealtime()
+#else
+#define K1STAMP(v) do { } while (0)
+#endif
+
 template <int DIM>
 __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     DevParams P, const double *__restrict__ paths, const double *__restrict__ VTg,
@@ -581,6 +596,7 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     ItemMeta<DIM> cur;
     PipeState<DIM> st;
     const int nt = P.Nmax + 2;
+    K1STAMP(t_entry);
     pipe_table_dma_issue(smem, VTg, nt, wid, lane);              // L2 hits, issued ahead of the HBM requests below
     {
         const ItemRaw r0 = pipe2_request<DIM>((int)blockIdx.x + (k_cur < n_local ? k_cur : 0) * (int)gridDim.x,
@@ -593,9 +609,14 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     }
 
     const PipeTab VT = pipe_table_dma_finish(smem, VTg, nt);
+    K1STAMP(t_loaded);
     if (threadIdx.x == 0) next_local = 32;
     double *red = reinterpret_cast<double *>(smem + pipe_tab_bytes(nt) + (size_t)wid * kWaveLds);
     __syncthreads();                                            // the only workgroup barrier
+    K1STAMP(t_ready);
+#ifdef PIGS_EXPERIMENT_K1_CLOCK
+    int n_done = 0;
+#endif
 
     st.idle = (size_t)(P.Nmax + 2) >= sl ? VTg : paths;         // any readable region of at least one slice
     while (k_cur < n_local) {                                   // wave-uniform
@@ -627,7 +648,18 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
         k_cur = k_nx;
         k_nx = st.k_nn;
         st.raw_next = st.raw_nn;
+#ifdef PIGS_EXPERIMENT_K1_CLOCK
+        ++n_done;
+#endif
     }
+#ifdef PIGS_EXPERIMENT_K1_CLOCK
+    K1STAMP(t_end);
+    const int slot = (int)blockIdx.x * 16 + wid;
+    if (lane == 0 && slot < kK1ClockWaves) {
+        unsigned long long *c = k1_clock + (size_t)slot * 5;
+        c[0] = t_entry; c[1] = t_loaded; c[2] = t_ready; c[3] = t_end; c[4] = (unsigned long long)n_done;
+    }
+#endif
 }
 
 // bit-for-bit check of the short division / sqrt forms against the compiler's IEEE ones
@@ -690,11 +722,23 @@ static int k1_pipe_blocks()
     return n;
 }
 
-template <typename K>
-static hipError_t set_lds(K kern, size_t bytes)
+// raise a kernel's dynamic-LDS limit once per (kernel, device) -- and again only for a larger request -- instead of on
+// every launch: hipFuncSetAttribute is a host call on the enqueue path of every step
+template <auto Kern>
+static hipError_t set_lds(size_t bytes)
 {
     if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    constexpr int kMaxDev = 64;
+    static std::atomic<size_t> granted[kMaxDev];                // one table per kernel instantiation, zero-initialised
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = -1;
+    if (dev >= 0 && bytes <= granted[dev].load(std::memory_order_acquire)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess && dev >= 0) {
+        size_t g = granted[dev].load(std::memory_order_relaxed);
+        while (g < bytes && !granted[dev].compare_exchange_weak(g, bytes, std::memory_order_release)) {}
+    }
+    return e;
 }
 
 hipError_t launch_delta_action(const DevParams &P, int variant, const double *paths, const double *VT,
@@ -765,7 +809,7 @@ hipError_t launch_delta_action(const DevParams &P, int variant, const double *pa
         if (blocks > k1_pipe_blocks()) blocks = k1_pipe_blocks();
 #define CALLP(D)                                                                                        \
     do {                                                                                                \
-        e = set_lds(k_delta_action_pipe2<D>, lds);                                                      \
+        e = set_lds<k_delta_action_pipe2<D>>(lds);                                                      \
         if (e == hipSuccess)                                                                            \
             hipLaunchKernelGGL((k_delta_action_pipe2<D>), dim3(blocks), dim3(1024), lds, st, P, paths,  \
                                VT, WF, n_items, walker, ip, ib, xnew, xold, out, parts);                \
@@ -780,7 +824,7 @@ hipError_t launch_delta_action(const DevParams &P, int variant, const double *pa
         const int grid = n_items < (1 << 16) ? n_items : (1 << 16);
 #define CALL(D, T)                                                                                      \
     do {                                                                                                \
-        e = set_lds(k_delta_action_reforder<D, T>, lds);                                                \
+        e = set_lds<k_delta_action_reforder<D, T>>(lds);                                                \
         if (e == hipSuccess)                                                                            \
             hipLaunchKernelGGL((k_delta_action_reforder<D, T>), dim3(grid), dim3(64), lds, st, P, paths, VT, WF, \
                                n_items, walker, ip, ib, xnew, xold, out, parts);                        \
@@ -795,6 +839,17 @@ hipError_t launch_delta_action(const DevParams &P, int variant, const double *pa
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }
+
+#ifdef PIGS_EXPERIMENT_K1_CLOCK
+// the clock records of the last pipe2 launch (n_waves x 5 words, see k1_clock); synchronises the device
+extern "C" int pigs_k1_clock_read(unsigned long long *dst, int n_waves)
+{
+    if (!dst || n_waves <= 0 || n_waves > kK1ClockWaves) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(k1_clock), (size_t)n_waves * 5 * sizeof(unsigned long long), 0,
+                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+#endif
 
 hipError_t launch_selftest_fastmath(const DevParams &P, unsigned long long seed, int blocks, int iters,
                                     unsigned long long *d_bad, hipStream_t st)

@@ -429,6 +429,16 @@ __device__ __forceinline__ void pipe_pair(const DevParams &P, PipeTab VT, const 
 }
 
 
+// r^2 of one distance in the branch-free forms: odd beads need the folded components for their force terms
+// (min_image_rn mutates d); even and end beads only r^2 and r, so they take the two-instruction magnitude form.
+// Every caller of the pipe arithmetic (pipe2, the grid twin, the sampler's tasks) goes through here: same bits.
+template <int DIM, int CLS>
+__device__ __forceinline__ double pipe_r2(double (&d)[DIM], const DevParams &P)
+{
+    if constexpr (CLS == CLS_ODD) return min_image_rn<DIM>(d, P);
+    else                          return min_image_mag<DIM>(d, P);
+}
+
 // ---- branch-free item evaluation on a PipeTab (periodic systems, Np <= 256) --------------------------------
 // one pass of 64 partners: both distances as independent chains; rjm = this lane's partner coordinates
 template <int DIM, int CLS>
@@ -446,8 +456,8 @@ __device__ __forceinline__ void pipe_pass_at(const DevParams &P, PipeTab VT, con
         asm volatile("; class %1 pass" : "+v"(rj) : "n"(CLS));
         dn[k] = xn[k] - rj; dold[k] = xo[k] - rj;
     }
-    const double r2o = min_image_rn<DIM>(dold, P);
-    const double r2n = min_image_rn<DIM>(dn, P);
+    const double r2o = pipe_r2<DIM, CLS>(dold, P);
+    const double r2n = pipe_r2<DIM, CLS>(dn, P);
     pipe_pair<DIM, CLS, false>(P, VT, WF, floor_r2(r2n), valid && r2n <= P.rcut2, dn, A);
     pipe_pair<DIM, CLS, true>(P, VT, WF, floor_r2(r2o), valid && r2o <= P.rcut2, dold, A);
     __builtin_amdgcn_sched_barrier(0);                                // two chains in flight (VGPRs)
@@ -565,14 +575,14 @@ __device__ __forceinline__ void pipe_task_cls(const DevParams &P, PipeTab VT, co
                     double d[DIM];
 #pragma unroll
                     for (int k = 0; k < DIM; ++k) d[k] = xn[k] - rj[m][k];
-                    const double r2 = min_image_rn<DIM>(d, P);
+                    const double r2 = pipe_r2<DIM, CLS>(d, P);
                     pipe_pair<DIM, CLS, false>(P, VT, WF, floor_r2(r2), valid && r2 <= P.rcut2, d, A);
                 }
                 if (sides & 2) {
                     double d[DIM];
 #pragma unroll
                     for (int k = 0; k < DIM; ++k) d[k] = xo[k] - rj[m][k];
-                    const double r2 = min_image_rn<DIM>(d, P);
+                    const double r2 = pipe_r2<DIM, CLS>(d, P);
                     pipe_pair<DIM, CLS, true>(P, VT, WF, floor_r2(r2), valid && r2 <= P.rcut2, d, A);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -630,14 +640,14 @@ __device__ __forceinline__ void pipe_task_rolled_cls(const DevParams &P, PipeTab
             double d[DIM];
 #pragma unroll
             for (int k = 0; k < DIM; ++k) d[k] = xn[k] - rj[k];
-            const double r2 = min_image_rn<DIM>(d, P);
+            const double r2 = pipe_r2<DIM, CLS>(d, P);
             pipe_pair<DIM, CLS, false>(P, VT, WF, floor_r2(r2), valid && r2 <= P.rcut2, d, A);
         }
         if (sides & 2) {
             double d[DIM];
 #pragma unroll
             for (int k = 0; k < DIM; ++k) d[k] = xo[k] - rj[k];
-            const double r2 = min_image_rn<DIM>(d, P);
+            const double r2 = pipe_r2<DIM, CLS>(d, P);
             pipe_pair<DIM, CLS, true>(P, VT, WF, floor_r2(r2), valid && r2 <= P.rcut2, d, A);
         }
     }
