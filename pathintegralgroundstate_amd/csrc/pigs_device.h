@@ -330,12 +330,37 @@ __device__ __forceinline__ void wave_reduce_multi(double (&v)[N], int lane)
     for (; stride >= 1; stride >>= 1) v[0] += __shfl_xor(v[0], stride, kWave);
 }
 
+// ---- one butterfly step: s + (s of lane l ^ S), with no per-lane index arithmetic ----------
+// S < 32: ds_swizzle in bit-mask mode (and 0x1f, or 0, xor S) -- the LDS crossbar without an address VGPR.
+// S = 32: v_permlane32_swap of s with itself leaves the low half's values in lanes l and l+32 of one
+// register and the high half's in the other, so every lane adds x[l % 32] + x[l % 32 + 32]: for lanes
+// 0..31 the very operands, in the very order, of s + __shfl_xor(s, 32); for lanes 32..63 the same two
+// operands swapped (the same sum).  Same partners as the __shfl_xor butterfly, so the same bits.
+template <int S>
+__device__ __forceinline__ double add_xor_lane(double s)
+{
+    union { double d; int i[2]; } u, a, b;
+    u.d = s;
+    if constexpr (S < 32) {
+        a.i[0] = __builtin_amdgcn_ds_swizzle(u.i[0], (S << 10) | 0x1f);
+        a.i[1] = __builtin_amdgcn_ds_swizzle(u.i[1], (S << 10) | 0x1f);
+        return s + a.d;
+    } else {
+        static_assert(S == 32, "xor stride must be a power of two below 64");
+        const auto lo = __builtin_amdgcn_permlane32_swap(u.i[0], u.i[0], false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap(u.i[1], u.i[1], false, false);
+        a.i[0] = lo[0]; a.i[1] = hi[0];                      // x[l % 32]
+        b.i[0] = lo[1]; b.i[1] = hi[1];                      // x[l % 32 + 32]
+        return a.d + b.d;
+    }
+}
+
 // ---- N accumulators x 64 lanes summed through a per-wave LDS transpose ---------------------
 // scratch: N rows of kRedStride doubles (stride 65 keeps both the row writes and the strided
 // reads bank-conflict free).  Each lane first adds up N entries of value (lane % N), then the
-// 64/N partials per value are folded with log2(64/N) shuffles: ~3N+5*log2(64/N) instructions
-// instead of ~50 per value for a plain butterfly.  Afterwards every lane l holds the total of
-// value l % N.  DS instructions of one wave execute in issue order, so no barrier is needed
+// 64/N partials per value are folded with log2(64/N) xor steps (add_xor_lane): ~3N+3*log2(64/N)
+// instructions instead of ~50 per value for a plain butterfly.  Afterwards every lane l holds the
+// total of value l % N.  DS instructions of one wave execute in issue order, so no barrier is needed
 // between the writes and the reads (wave_barrier only pins the compiler's order).
 constexpr int kRedStride = 65;
 
@@ -352,8 +377,11 @@ __device__ __forceinline__ double wave_reduce_lds(const double (&v)[N], double *
 #pragma unroll
     for (int k = 1; k < N; ++k) s = s + row[k];
     __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int stride = N; stride < kWave; stride <<= 1) s = s + __shfl_xor(s, stride, kWave);
+    if constexpr (N <= 2) s = add_xor_lane<2>(s);          // strides N, 2N, ..., 32: the butterfly's order
+    if constexpr (N <= 4) s = add_xor_lane<4>(s);
+    s = add_xor_lane<8>(s);
+    s = add_xor_lane<16>(s);
+    s = add_xor_lane<32>(s);
     return s;
 }
 

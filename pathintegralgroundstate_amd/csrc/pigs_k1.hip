@@ -375,9 +375,12 @@ __device__ __forceinline__ size_t pipe_tab_bytes(int nt) { return ((size_t)(nt +
 
 // Staging the table image with the LDS-DMA form of the global load (global_load_lds_dwordx4: 16 bytes per lane
 // straight into LDS at M0 + lane*16, no VGPRs, no ds_write): issued as the very first instructions of the
-// kernel, ahead of the HBM requests of the first items; completion is a vmcnt matter, so ONE `s_waitcnt vmcnt(0)`
-// before the workgroup barrier covers it (the first item needs its own loads by then anyway).  A wave issues the
-// chunk [u*blockDim + wid*64, +64) only if it starts inside the table; lanes past the end are masked off.
+// kernel, ahead of the HBM requests of the first items; completion is a vmcnt matter, and vmcnt retires in order,
+// so the wait before the workgroup barrier leaves the first item's slice loads -- the last VMEM requests a wave
+// issues before it -- in flight: the barrier overlaps their latency.  A wave issues the chunk
+// [u*blockDim + wid*64, +64) only if it starts inside the table; lanes past the end are masked off.  The odd last
+// entry (if any) is loaded at entry too, ahead of the slice loads, so the same wait covers it (loaded after them, it
+// made wave 0 -- and with it the barrier -- wait for wave 0's slices).
 
 __device__ __forceinline__ void pipe_table_dma_issue(unsigned char *smem, const double *__restrict__ VTg, int nt, int wid, int lane)
 {
@@ -394,14 +397,16 @@ __device__ __forceinline__ void pipe_table_dma_issue(unsigned char *smem, const 
 #endif
 }
 
-// after this and a workgroup barrier the image is complete
-__device__ __forceinline__ PipeTab pipe_table_dma_finish(unsigned char *smem, const double *__restrict__ VTg, int nt)
+// after this and a workgroup barrier the image is complete.  IN_FLIGHT: the VMEM requests the wave issued after
+// the table chunks (its first item's slice loads) that may stay outstanding; `tail` = VTg[nt - 1] when nt is odd.
+template <int IN_FLIGHT>
+__device__ __forceinline__ PipeTab pipe_table_dma_finish(unsigned char *smem, int nt, double tail)
 {
     double *base = reinterpret_cast<double *>(smem);          // base[1] = leading copy, base[2..] = table
     double *tab  = base + 2;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(IN_FLIGHT) : "memory");
     if (threadIdx.x == 0) {
-        if (nt & 1) tab[nt - 1] = VTg[nt - 1];
+        if (nt & 1) tab[nt - 1] = tail;
         base[0] = 0.0; base[1] = tab[0];                          // wave 0 staged chunk 0 itself: tab[0] has landed
         tab[nt] = 0.0; tab[nt + 1] = 0.0; tab[nt + 2] = 0.0; tab[nt + 3] = 0.0;
     }
@@ -426,6 +431,7 @@ template <int DIM>
 struct ItemMeta {                                   // wave-uniform (SGPRs)
     int    p, b, ok;
     const double *S;
+    int    nb;                                      // bytes of a coordinate row (0 for a malformed record)
     double xn[DIM], xo[DIM];
 };
 
@@ -471,28 +477,45 @@ __device__ __forceinline__ void pipe2_decode(const DevParams &P, const double *_
         R.xo[k] = bcast_lane(r.x, DIM + k);
     }
     R.S = paths + (R.ok ? ((size_t)w * P.M + R.b) * sl : 0);
+    R.nb = R.ok ? P.NpPad * 8 : 0;
 }
 
-// only the slice address of a record (what the coordinate lookahead needs mid-item; the full decode waits
-// for the item's own turn so that two decoded records never compete for SGPRs)
-template <int DIM>
-__device__ __forceinline__ const double *pipe2_slice(const DevParams &P, const double *__restrict__ paths, const ItemRaw &r, size_t sl)
+// only the slice of a record (what the coordinate lookahead needs mid-item; the full decode waits for the item's
+// own turn so that two decoded records never compete for SGPRs).  has = false: no item, no loads (nb = 0).
+struct SliceRef {
+    const double *S;
+    int nb;
+};
+
+__device__ __forceinline__ SliceRef pipe2_slice(const DevParams &P, const double *__restrict__ paths, const ItemRaw &r,
+                                                size_t sl, bool has)
 {
     const int w = __builtin_amdgcn_readlane(r.i, 0);
     const int p = __builtin_amdgcn_readlane(r.i, 1) - 1;
     const int b = __builtin_amdgcn_readlane(r.i, 2);
-    const bool ok = (unsigned)w < (unsigned)P.nW && (unsigned)p < (unsigned)P.Np && (unsigned)b < (unsigned)P.M;
-    return paths + (ok ? ((size_t)w * P.M + b) * sl : 0);
+    const bool ok = has && (unsigned)w < (unsigned)P.nW && (unsigned)p < (unsigned)P.Np && (unsigned)b < (unsigned)P.M;
+    return SliceRef{paths + (ok ? ((size_t)w * P.M + b) * sl : 0), ok ? P.NpPad * 8 : 0};
 }
 
+// Partner coordinates of pass m through one buffer descriptor per coordinate row (base S + k NpPad, NpPad*8 bytes;
+// SALU work only): the lane's byte offset is lane*8 + m*512, one compare and select per pass.
+// The range check does the rest -- a lane past NpPad (passes beyond NpPad exist when Np < 256) gets 0.0 and reads
+// nothing, never the next row or the next slice, and so does the moved particle's own row, which is given an offset
+// past the end (vpi_mod.f90:2699: row p is never read).  Every lane gets finite data; the lanes that are not partners
+// are masked through the table's zero cell as before, and contribute exactly +0 whatever finite values they hold.
+// nbytes = 0 (no next item, malformed record) makes every load of the slice a no-op.
+constexpr unsigned kPipeRowOff = 0x40000000u;                         // an offset past any coordinate row
+
 template <int DIM>
-__device__ __forceinline__ void pipe2_load(const DevParams &P, const double *__restrict__ S, int p, int m, int lane,
-                                           double (&rj)[DIM])
+__device__ __forceinline__ void pipe2_load(const DevParams &P, const double *__restrict__ S, int nbytes, int p, int m,
+                                           int lane, double (&rj)[DIM])
 {
-    const int j  = m * kWave + lane;
-    const int jj = pipe_row(P, j, p);                                 // never the moved particle's own row
+    const unsigned off = (lane == p - m * kWave ? kPipeRowOff : (unsigned)lane * 8u) + (unsigned)(m * kWave * 8);
 #pragma unroll
-    for (int k = 0; k < DIM; ++k) rj[k] = S[(size_t)k * P.NpPad + jj];
+    for (int k = 0; k < DIM; ++k) {
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(S + (size_t)k * P.NpPad), 0, nbytes, 0x00020000);
+        rj[k] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0));
+    }
 }
 
 template <int DIM, int CLS, int M>
@@ -523,7 +546,6 @@ struct PipeState {
     ItemRaw raw_nn;           // record of the item after it (requested mid-item)
     int k_nn;                 // queue index of that item
     bool has_next;            // the wave has a next item
-    const double *idle;       // what the look-ahead reads when it has not
     double a0[DIM], a1[DIM];  // passes 0/1: of the current item on entry, of the next item on exit
 };
 
@@ -538,14 +560,14 @@ __device__ __forceinline__ void pipe2_item(const DevParams &P, PipeTab VT, const
 {
     Acc<DIM, CLS> A;
     double b0[DIM], b1[DIM];
-    pipe2_load<DIM>(P, R.S, R.p, 2, lane, b0);
+    pipe2_load<DIM>(P, R.S, R.nb, R.p, 2, lane, b0);
     pipe2_pass<DIM, CLS, 0>(P, VT, WF, R, st.a0, lane, A);
-    pipe2_load<DIM>(P, R.S, R.p, 3, lane, b1);
+    pipe2_load<DIM>(P, R.S, R.nb, R.p, 3, lane, b1);
     pipe2_pass<DIM, CLS, 1>(P, VT, WF, R, st.a1, lane, A);
     // the next item's record arrived an item ago; the one after it is drawn from the queue and requested now
-    // no next item: the look-ahead loads still run (a branch here costs 40 spilled VGPRs) but read `idle`, a
-    // region every CU keeps hot in L2 (the table in global memory): no HBM traffic for nothing
-    const double *Snext = st.has_next ? pipe2_slice<DIM>(P, paths, st.raw_next, sl) : st.idle;
+    // no next item: the look-ahead loads still run (a branch here costs 40 spilled VGPRs) on an empty descriptor:
+    // no memory traffic at all
+    const SliceRef Snext = pipe2_slice(P, paths, st.raw_next, sl, st.has_next);
     {
         int kn = 0;
         if (lane == 0) kn = atomicAdd(queue, 1);
@@ -556,18 +578,19 @@ __device__ __forceinline__ void pipe2_item(const DevParams &P, PipeTab VT, const
         st.raw_nn = pipe2_request<DIM>((int)blockIdx.x + kq * (int)gridDim.x, walker, ipv, ibv, xnew, xold, lane);
     }
     const int pnext = __builtin_amdgcn_readlane(st.raw_next.i, 1) - 1;    // (a wave without a next item re-reads a stale record: any row does)
-    pipe2_load<DIM>(P, Snext, pnext, 0, lane, st.a0);
+    pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 0, lane, st.a0);
     pipe2_pass<DIM, CLS, 2>(P, VT, WF, R, b0, lane, A);
-    pipe2_load<DIM>(P, Snext, pnext, 1, lane, st.a1);
+    pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 1, lane, st.a1);
     pipe2_pass<DIM, CLS, 3>(P, VT, WF, R, b1, lane, A);
     finish_item<DIM, CLS>(P, lane, R.b, A, red, out, parts);
 }
 
 // -DPIGS_EXPERIMENT_K1_CLOCK (experiment builds only): lane 0 of every pipe2 wave records, with an ordinary global
 // store at its end, four s_memrealtime stamps (100 MHz, one clock for the whole chip) and its item count into
-// k1_clock[(blockIdx * 16 + wave) * 5]: entry, its own first-item loads and table chunks landed (vmcnt 0), past the
-// workgroup barrier (the first table lookup follows within one pass's distance arithmetic), end.  The last launch's
-// record is read by pigs_k1_clock_read(); scripts/k1_head.py turns it into the head / tail split of profiles/r04_*.
+// k1_clock[(blockIdx * 16 + wave) * 5]: entry, its table chunks and first records landed (its first slice loads still
+// in flight), past the workgroup barrier (the first table lookup follows within one pass's distance arithmetic), end.
+// The last launch's record is read by pigs_k1_clock_read(); scripts/k1_head.py turns it into the head / tail split of
+// profiles/r04_* and r05_*.
 #ifdef PIGS_EXPERIMENT_K1_CLOCK
 constexpr int kK1ClockWaves = 16 * 1024;
 __device__ unsigned long long k1_clock[kK1ClockWaves * 5];
@@ -598,17 +621,18 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     const int nt = P.Nmax + 2;
     K1STAMP(t_entry);
     pipe_table_dma_issue(smem, VTg, nt, wid, lane);              // L2 hits, issued ahead of the HBM requests below
+    const double tail = VTg[nt - 1];                             // the odd last entry (used when nt is odd)
     {
         const ItemRaw r0 = pipe2_request<DIM>((int)blockIdx.x + (k_cur < n_local ? k_cur : 0) * (int)gridDim.x,
                                               walker, ipv, ibv, xnew, xold, lane);
         st.raw_next = pipe2_request<DIM>((int)blockIdx.x + (k_nx < n_local ? k_nx : (k_cur < n_local ? k_cur : 0)) * (int)gridDim.x,
                                          walker, ipv, ibv, xnew, xold, lane);
         pipe2_decode<DIM>(P, paths, r0, sl, cur);
-        pipe2_load<DIM>(P, cur.S, cur.p, 0, lane, st.a0);
-        pipe2_load<DIM>(P, cur.S, cur.p, 1, lane, st.a1);
+        pipe2_load<DIM>(P, cur.S, cur.nb, cur.p, 0, lane, st.a0);
+        pipe2_load<DIM>(P, cur.S, cur.nb, cur.p, 1, lane, st.a1);
     }
 
-    const PipeTab VT = pipe_table_dma_finish(smem, VTg, nt);
+    const PipeTab VT = pipe_table_dma_finish<2 * DIM>(smem, nt, tail);   // passes 0/1 stay in flight
     K1STAMP(t_loaded);
     if (threadIdx.x == 0) next_local = 32;
     double *red = reinterpret_cast<double *>(smem + pipe_tab_bytes(nt) + (size_t)wid * kWaveLds);
@@ -618,7 +642,6 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     int n_done = 0;
 #endif
 
-    st.idle = (size_t)(P.Nmax + 2) >= sl ? VTg : paths;         // any readable region of at least one slice
     while (k_cur < n_local) {                                   // wave-uniform
         st.has_next = k_nx < n_local;
         const int it = (int)blockIdx.x + k_cur * (int)gridDim.x;
@@ -627,7 +650,7 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
         if (!cur.ok) {
             // malformed item: NaN result; keep the pipeline moving without evaluating anything
             if (lane == 0) *o = __builtin_nan("");
-            const double *Snext = st.has_next ? pipe2_slice<DIM>(P, paths, st.raw_next, sl) : st.idle;
+            const SliceRef Snext = pipe2_slice(P, paths, st.raw_next, sl, st.has_next);
             int kn = 0;
             if (lane == 0) kn = atomicAdd(&next_local, 1);
             kn = __builtin_amdgcn_readfirstlane(kn);
@@ -635,8 +658,8 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
             st.raw_nn = pipe2_request<DIM>((int)blockIdx.x + (kn < n_local ? kn : k_cur) * (int)gridDim.x,
                                            walker, ipv, ibv, xnew, xold, lane);
             const int pnext = __builtin_amdgcn_readlane(st.raw_next.i, 1) - 1;
-            pipe2_load<DIM>(P, Snext, pnext, 0, lane, st.a0);
-            pipe2_load<DIM>(P, Snext, pnext, 1, lane, st.a1);
+            pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 0, lane, st.a0);
+            pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 1, lane, st.a1);
         } else {
             const bool odd  = (cur.b & 1) != 0;
             const bool endb = (cur.b == 0) || (cur.b == 2 * P.Nb);
