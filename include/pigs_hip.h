@@ -268,6 +268,33 @@ int pigs_diagonal_estimators_begin(pigs_ctx *ctx, int32_t n, const int32_t *walk
                                    int32_t structure);
 int pigs_diagonal_estimators_end(pigs_ctx *ctx, double *en, double *gr, double *Sk);
 
+/* ---- density profiles and pair distribution of a TRAPPED system (new: the reference allocates dens(Nbin,Nbin),
+ * vpi.f90:198, and leaves its DensityProfile call commented out, vpi.f90:471) ---------------------------------------
+ * Three histograms of the middle slice Path(:,:,Nb), 64-bit integer counts per walker, accumulated on the device:
+ *   planar  Nbin^min(dim,2) bins of width b = (2h)/Nbin over [-h, h) in the first min(dim,2) coordinates, flat index
+ *           j_1 + Nbin*j_2 (x fastest; for dim = 3 the column density over x_1, x_2).  t = (x_k + h)/b; the particle
+ *           counts if 0 <= t < Nbin for each of those coordinates, in bin (int)t
+ *   radial  Nbin bins of width br = h/Nbin over r = |x| in [0, h): u = r/br counts if u < Nbin, in bin (int)u
+ *   pair    Nbin bins of width br over the pair distance d (no minimum image): +2 per pair i < j with d/br < Nbin
+ *   samples +1 per accumulate.
+ * Decisions are taken in double before any conversion to an integer (NaN, +-Inf, huge values drop out).  b and br are
+ * computed once by pigs_density_init in double exactly as written above.  Normalisation is the caller's (per walker and
+ * block, with S = the block's samples: planar c/(S b^min(dim,2)), radial c/(S dV_j), pair c/(S Np dV_j), where
+ * dV_j = V_d((j+1)br) - V_d(j br) and V_d the volume of the d-ball).
+ *
+ * pigs_density_init allocates and zeroes the accumulators (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a
+ * periodic context, PIGS_ERR_ARG for Nbin < 1 or !(half_width > 0). */
+int pigs_density_init(pigs_ctx *ctx, int32_t Nbin, double half_width);
+/* Adds slice Nb of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no host synchronisation: it sees the worldline every call queued before it left (a pigs_diagonal_estimators_begin
+ * just before it snapshots the same one), never the next step's.  PIGS_ERR_ARG before pigs_density_init or for a
+ * walker out of range. */
+int pigs_density_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' accumulators, walker-major: planar (Nbin^min(dim,2) per walker), radial, pair (Nbin each), samples (1);
+ * then zeroes those of the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context. */
+int pigs_density_read(pigs_ctx *ctx, int64_t *planar, int64_t *radial, int64_t *pair, int64_t *samples,
+                      const int32_t *reset);
+
 /* ---- multi-GPU: block-estimator reduction (new) ------------------------ */
 /* RCCL communicator over `nranks` contexts.  Single-process form (one host thread per
  * GPU, the Fortran host: pigs_vpi's &gpu n_gpus = G): pigs_comm_init_all.  Multi-process form: rank 0 obtains an id

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "pigs_sampler_form", "pigs_sampler_counters", "pigs_sampler_counters16", "pigs_sampler_get_worm", "pigs_sampler_set_worm",
     "pigs_sampler_events", "pigs_sampler_event_ints", "pigs_sampler_nrho", "pigs_slice_download", "pigs_build_tables_kind", "pigs_structure_batch",
     "pigs_diagonal_estimators", "pigs_diagonal_estimators_begin", "pigs_diagonal_estimators_end",
+    "pigs_density_init", "pigs_density_accumulate", "pigs_density_read",
 ]
 
 
@@ -121,6 +122,10 @@ def load_library(path=LIB_PATH):
     L.pigs_diagonal_estimators.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp]
     L.pigs_diagonal_estimators_begin.argtypes = [vp, C.c_int32, _ip, C.c_int32, C.c_double, C.c_int32, C.c_int32]
     L.pigs_diagonal_estimators_end.argtypes = [vp, _dp, _dp, _dp]
+    _lp = C.POINTER(C.c_int64)
+    L.pigs_density_init.argtypes = [vp, C.c_int32, C.c_double]
+    L.pigs_density_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_density_read.argtypes = [vp, _lp, _lp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -404,6 +409,43 @@ class PigsContext:
         R = np.empty((self.n_walkers, self.cfg.Np, self.cfg.dim))
         _chk(self.L, self.L.pigs_slice_download(self.h, int(ib), _d(R)), "pigs_slice_download")
         return R
+
+    # ---- density profiles of a trapped system (pigs_density_*: slice Nb, 64-bit counts per walker)
+    def density_init(self, Nbin, half_width):
+        """Allocate and zero the accumulators: Nbin bins per axis over [-half_width, half_width) (planar) and over
+        [0, half_width) (radial, pair).  Calling it again resizes and zeroes them."""
+        _chk(self.L, self.L.pigs_density_init(self.h, int(Nbin), float(half_width)), "pigs_density_init")
+        self._dens_nbin = int(Nbin)
+
+    def density_accumulate(self, walkers=None):
+        """Queue one sample of slice Nb of `walkers` (None: all) on the context's stream; does not wait."""
+        if walkers is None:
+            _chk(self.L, self.L.pigs_density_accumulate(self.h, self.n_walkers, None), "pigs_density_accumulate")
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, self.L.pigs_density_accumulate(self.h, wl.size, _i(wl)), "pigs_density_accumulate")
+
+    def density_read(self, reset=None):
+        """dict of int64 arrays: planar [W, Nbin] (dim 1) or [W, Nbin, Nbin] (x fastest in the last axis), radial
+        [W, Nbin], pair [W, Nbin], samples [W].  reset: None, True (all walkers) or a per-walker mask of walkers whose
+        accumulators are zeroed after the copy."""
+        nb = getattr(self, "_dens_nbin", 0)
+        if not nb:
+            raise PigsError("density_read: density_init first")
+        W, dp = self.n_walkers, min(self.cfg.dim, 2)
+        out = {"planar": np.zeros((W,) + (nb,) * dp, np.int64), "radial": np.zeros((W, nb), np.int64),
+               "pair": np.zeros((W, nb), np.int64), "samples": np.zeros(W, np.int64)}
+        if reset is None or reset is False:
+            mask = None
+        else:
+            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
+            if keep.size != W:
+                raise ValueError("reset mask needs one entry per walker")
+            mask = _i(keep)
+        lp = C.POINTER(C.c_int64)
+        _chk(self.L, self.L.pigs_density_read(self.h, *(out[k].ctypes.data_as(lp) for k in ("planar", "radial", "pair", "samples")),
+                                              mask), "pigs_density_read")
+        return out
 
     # ---- K5
     def commit_beads(self, walker, ip, ib, x):

@@ -193,6 +193,11 @@ struct pigs_ctx {
     std::vector<int32_t> a_sw, a_sb;        // slot lists: must outlive the asynchronous upload
     struct { bool on = false, launched = false; EstBatch b; } a_pend;
     Event       ev_gate;                    // recorded behind the TranslateChain kernel of the next step (see launch_pending_estimators)
+    // density profiles of a trapped system (pigs_density_*): per-walker 64-bit counts, walker-major
+    DevBuf<unsigned long long> d_dplanar, d_dradial, d_dpair, d_dsamples;
+    int         dens_nbin = 0;              // 0: pigs_density_init not called yet
+    size_t      dens_nplanar = 0;           // planar bins per walker: Nbin^min(dim,2)
+    double      dens_h = 0.0, dens_b = 0.0, dens_br = 0.0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -1291,6 +1296,84 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     HIPCHK(hipStreamSynchronize(c->stream2));
     rc = check_cm(c); if (rc) return rc;
     est_unpack(b, (const double *)c->a_host.h, en, gr, Sk);
+    return PIGS_OK;
+}
+
+// ---- density profiles of a trapped system ------------------------------------------------------
+// Three per-walker histograms of slice Nb (pigs_density.hip) accumulated on the device and read per block.  The widths
+// are computed here, once, in double: b = (2h)/Nbin for the planar grid over [-h, h), br = h/Nbin for r and d in [0, h).
+int pigs_density_init(pigs_ctx *c, int32_t Nbin, double half_width)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "density profiles are defined for trapped systems only");
+    if (Nbin < 1 || !(half_width > 0.0)) return fail(PIGS_ERR_ARG, "pigs_density_init: Nbin=%d half_width=%g", Nbin, half_width);
+    const int dp = c->P.dim < 2 ? c->P.dim : 2;
+    size_t np = 1;
+    for (int k = 0; k < dp; ++k) np *= (size_t)Nbin;
+    const size_t W = (size_t)c->n_walkers;
+    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
+    c->dens_nbin = 0;
+    HIPCHK(c->d_dplanar.alloc(W * np));
+    HIPCHK(c->d_dradial.alloc(W * Nbin));
+    HIPCHK(c->d_dpair.alloc(W * Nbin));
+    HIPCHK(c->d_dsamples.alloc(W));
+    HIPCHK(hipMemsetAsync(c->d_dplanar.p, 0, W * np * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_dradial.p, 0, W * Nbin * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_dpair.p, 0, W * Nbin * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_dsamples.p, 0, W * sizeof(unsigned long long), c->stream));
+    SYNC_CHECKED(c);
+    c->dens_nbin = Nbin;
+    c->dens_nplanar = np;
+    c->dens_h = half_width;
+    c->dens_b = (2.0 * half_width) / Nbin;
+    c->dens_br = half_width / Nbin;
+    return PIGS_OK;
+}
+
+int pigs_density_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->dens_nbin) return fail(PIGS_ERR_ARG, "pigs_density_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // the list goes by value in the kernel arguments: queued on the context's stream, nothing to wait for
+    for (int i0 = 0; i0 < n; i0 += kDensListMax) {
+        const int m = std::min(kDensListMax, n - i0);
+        DensList L{};
+        for (int i = 0; i < m; ++i) L.w[i] = sw[i0 + i];
+        HIPCHK(launch_density(c->P, c->d_paths.p, m, L, c->dens_nbin, c->dens_h, c->dens_b, c->dens_br, c->d_dplanar.p,
+                              c->d_dradial.p, c->d_dpair.p, c->d_dsamples.p, c->stream));
+    }
+    return PIGS_OK;
+}
+
+int pigs_density_read(pigs_ctx *c, int64_t *planar, int64_t *radial, int64_t *pair, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->dens_nbin) return fail(PIGS_ERR_ARG, "pigs_density_init first");
+    if (!planar || !radial || !pair || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t W = (size_t)c->n_walkers, nb = (size_t)c->dens_nbin, np = c->dens_nplanar;
+    const size_t u = sizeof(unsigned long long);
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(planar, c->d_dplanar.p, W * np * u, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(radial, c->d_dradial.p, W * nb * u, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pair, c->d_dpair.p, W * nb * u, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(samples, c->d_dsamples.p, W * u, hipMemcpyDeviceToHost, s));
+    if (reset) {
+        // zero the accumulators of the flagged walkers, one memset per array and run of consecutive walkers
+        for (size_t w = 0; w < W;) {
+            if (!reset[w]) { ++w; continue; }
+            size_t e = w;
+            while (e < W && reset[e]) ++e;
+            HIPCHK(hipMemsetAsync(c->d_dplanar.p + w * np, 0, (e - w) * np * u, s));
+            HIPCHK(hipMemsetAsync(c->d_dradial.p + w * nb, 0, (e - w) * nb * u, s));
+            HIPCHK(hipMemsetAsync(c->d_dpair.p + w * nb, 0, (e - w) * nb * u, s));
+            HIPCHK(hipMemsetAsync(c->d_dsamples.p + w, 0, (e - w) * u, s));
+            w = e;
+        }
+    }
+    SYNC_CHECKED(c);
     return PIGS_OK;
 }
 

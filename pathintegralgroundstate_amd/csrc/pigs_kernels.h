@@ -48,6 +48,17 @@ hipError_t launch_local_energy(const DevParams &P, const double *paths, const do
 hipError_t launch_structure(const DevParams &P, const double *paths, int n_slots, const int32_t *slot_walker,
                             int ib, int Nbin, double rbin, int Nk, double *gr, double *Sk, hipStream_t st);
 
+// pigs_density.hip: planar / radial density and pair distribution of slice Nb of a trapped system, 64-bit counts
+// accumulated per walker (pigs_density_accumulate).  The walker list travels in the kernel arguments (no upload, no
+// host buffer to keep alive), at most kDensListMax walkers per launch.  The pair histogram is staged in LDS for
+// Nbin <= kDensLdsBins and added with global atomics beyond.
+constexpr int kDensListMax = 256;
+constexpr int kDensLdsBins = 8192;
+struct DensList { int32_t w[kDensListMax]; };
+hipError_t launch_density(const DevParams &P, const double *paths, int n, const DensList &list, int Nbin, double h,
+                          double b, double br, unsigned long long *planar, unsigned long long *radial,
+                          unsigned long long *pair, unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

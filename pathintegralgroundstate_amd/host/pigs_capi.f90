@@ -392,7 +392,37 @@ module pigs_capi
        integer(c_int32_t) :: out(4)
        integer(c_int) :: rc
      end function pigs_sampler_form_t
+
+     ! density profiles of a trapped system (include/pigs_hip.h, pigs_density_*): looked up at run time, see density_bind
+     function pigs_density_init_t(ctx,Nbin,half_width) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value        :: ctx
+       integer(c_int32_t), value :: Nbin
+       real(c_double), value     :: half_width
+       integer(c_int) :: rc
+     end function pigs_density_init_t
+
+     function pigs_density_accumulate_t(ctx,n,walkers) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int32_t), value      :: n
+       integer(c_int32_t), intent(in) :: walkers(*)
+       integer(c_int) :: rc
+     end function pigs_density_accumulate_t
+
+     function pigs_density_read_t(ctx,planar,radial,pair,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int64_t)             :: planar(*),radial(*),pair(*),samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its accumulators after the copy
+       integer(c_int) :: rc
+     end function pigs_density_read_t
   end interface
+
+  ! bound by density_bind (null until then)
+  procedure(pigs_density_init_t), pointer       :: dens_init => null()
+  procedure(pigs_density_accumulate_t), pointer :: dens_accumulate => null()
+  procedure(pigs_density_read_t), pointer       :: dens_read => null()
 
 contains
 
@@ -411,6 +441,21 @@ contains
     call c_f_procpointer(f,query)
     call pigs_check(query(ctx,form),'pigs_sampler_form')
   end function sampler_form
+
+  ! The density-profile entry points, found at run time in the process's libraries (dlsym with RTLD_DEFAULT = NULL) and
+  ! only when a run asks for them: the host links against backends without them (the CPU twin of tests/shim) and never
+  ! names them at link time.  .false. (pointers left null) where the backend does not export all three.
+  logical function density_bind()
+    type(c_funptr) :: f(3)
+    f(1) = c_dlsym(c_null_ptr,'pigs_density_init'//c_null_char)
+    f(2) = c_dlsym(c_null_ptr,'pigs_density_accumulate'//c_null_char)
+    f(3) = c_dlsym(c_null_ptr,'pigs_density_read'//c_null_char)
+    density_bind = c_associated(f(1)) .and. c_associated(f(2)) .and. c_associated(f(3))
+    if (.not. density_bind) return
+    call c_f_procpointer(f(1),dens_init)
+    call c_f_procpointer(f(2),dens_accumulate)
+    call c_f_procpointer(f(3),dens_read)
+  end function density_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -11,6 +11,7 @@ module pigs_estimators
   public :: est_params, pair_correlation, structure_factor, obdm_accumulate
   public :: normalize_gr, normalize_sk, normalize_nr, variance, perm_state, perm_sampling
   public :: write_radial, write_sk, write_nr
+  public :: normalize_density, write_density, write_profile
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -150,6 +151,79 @@ contains
        nrho(:,ibin) = nrho(:,ibin)/(p%CWorm*nid*zconf*real(Nobdm))
     end do
   end subroutine normalize_nr
+
+  ! ---- density profiles of a trapped system (counts of pigs_density_read: slice Nb, grid half-width h, Nbin bins per
+  ! axis) -> one walker's profiles of one block with S samples: planar c/(S b^min(dim,2)) over [-h,h) with b = (2h)/Nbin,
+  ! radial c/(S dV_j) and pair c/(S Np dV_j) over [0,h) with br = h/Nbin and dV_j = V_d(j br) - V_d((j-1) br).
+  ! With every particle inside the grid the planar and radial profiles integrate to Np, the pair distribution to Np-1.
+  subroutine normalize_density(dim,Np,Nbin,h,S,cpl,crad,cpair,dpl,drad,dpair)
+    integer, intent(in)    :: dim,Np,Nbin
+    real(8), intent(in)    :: h
+    integer(8), intent(in) :: S,cpl(:),crad(Nbin),cpair(Nbin)
+    real(8), intent(out)   :: dpl(:),drad(Nbin),dpair(Nbin)
+    real(8) :: b,br,kn,dv
+    integer :: j
+    b  = (2.d0*h)/Nbin
+    br = h/Nbin
+    kn = acos(-1.d0)**(0.5d0*dim)/gamma(0.5d0*dim+1.d0)
+    dpl = real(cpl,8)/(real(S,8)*b**min(dim,2))
+    do j=1,Nbin
+       dv       = kn*(real(j,8)*br)**dim-kn*(real(j-1,8)*br)**dim
+       drad(j)  = real(crad(j),8)/(real(S,8)*dv)
+       dpair(j) = real(cpair(j),8)/(real(S,8)*real(Np,8)*dv)
+    end do
+  end subroutine normalize_density
+
+  ! dens_vpi.out: x y mean err with x fastest and a blank line after each y row (dim >= 2), x mean err (dim = 1); bin
+  ! centres of the planar grid
+  subroutine write_density(fname,dim,Nbin,h,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: dim,Nbin,n
+    real(8), intent(in)    :: h
+    real(8), intent(inout) :: av(:),av2(:)
+    real(8) :: b,x,y
+    integer :: i,j1,j2,u
+    b = (2.d0*h)/Nbin
+    av  = av/real(n)
+    av2 = av2/real(n)
+    open (newunit=u,file=fname)
+    if (dim==1) then
+       do j1=1,Nbin
+          x = -h+(real(j1)-0.5d0)*b
+          write (u,'(20g20.10e3)') x,av(j1),variance(n,av(j1),av2(j1))
+       end do
+    else
+       do j2=1,Nbin
+          y = -h+(real(j2)-0.5d0)*b
+          do j1=1,Nbin
+             x = -h+(real(j1)-0.5d0)*b
+             i = j1+Nbin*(j2-1)
+             write (u,'(20g20.10e3)') x,y,av(i),variance(n,av(i),av2(i))
+          end do
+          write (u,'(a)') ''
+       end do
+    end if
+    close (u)
+  end subroutine write_density
+
+  ! rho_vpi.out / pr_vpi.out: r mean err at the bin centres of [0,h), br = h/Nbin
+  subroutine write_profile(fname,Nbin,h,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: Nbin,n
+    real(8), intent(in)    :: h
+    real(8), intent(inout) :: av(Nbin),av2(Nbin)
+    real(8) :: br,r
+    integer :: j,u
+    br = h/Nbin
+    open (newunit=u,file=fname)
+    do j=1,Nbin
+       r      = (real(j)-0.5d0)*br
+       av(j)  = av(j)/real(n)
+       av2(j) = av2(j)/real(n)
+       write (u,'(20g20.10e3)') r,av(j),variance(n,av(j),av2(j))
+    end do
+    close (u)
+  end subroutine write_profile
 
   ! the reference's "variance": standard error sqrt((<x^2>-<x>^2)/n)
   function variance(n,av,av2) result(v)

@@ -12,6 +12,8 @@
 ! meet ONCE per block in one all-reduce (RCCL over xGMI: pigs_comm_init_all / pigs_estimators_allreduce); thread 0
 ! writes the walker-summed files.  same_device = T puts every shard on `device`: a one-GPU rehearsal.)
 ! (potential: aziz2 | lj | dipolar -- the reference selects it by editing system_mod.f90)
+! (density_profile = T, trapped systems only: the planar and radial density and the pair distribution of the middle
+! slice, accumulated on the GPU -- dens_vpi.out, rho_vpi.out, pr_vpi.out; grid half-width rcut/2, Nbin bins per axis)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -42,7 +44,7 @@ program pigs_vpi
   real (kind=8)     :: a_ho(3)
   integer           :: dim,Np,Nb,seed,CMFreq,Lstag,Nlev,Nstag,Nblock,Nstep,Nbin,Nk
   integer           :: Nobdm,Npw,Nmax,n_walkers,device,ios,k1_variant,n_gpus
-  logical           :: device_sampler,checkpointing,same_device
+  logical           :: device_sampler,checkpointing,same_device,density_profile
   logical           :: sampler_auto
   integer(c_int)    :: rc_probe
   type(pigs_sweep_params) :: probe_par
@@ -54,7 +56,7 @@ program pigs_vpi
   namelist /wavefun/ Nmax,wf_table,v_table
   namelist /extpot/  a_ho
   namelist /jastrow/ Rm
-  namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device
+  namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device,density_profile
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -76,7 +78,7 @@ program pigs_vpi
   CMFreq = 1; Nstag = 1; Nblock = 1; Nstep = 1; Nbin = 100; Nk = 50; sampling = 'bis'
   delta_cm = 0.d0; density = 0.d0; a_ho = 1.d0; Rm = 1.d0
   n_walkers = 1; device = 0; device_sampler = .false.; potential = 'aziz2'; checkpointing = .true.; k1_variant = 0
-  n_gpus = 1; same_device = .false.
+  n_gpus = 1; same_device = .false.; density_profile = .false.
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -98,6 +100,19 @@ program pigs_vpi
   if (.not. v_table) then
      write (0,*) 'pigs_vpi: v_table = T is required (the reference Force() is a stub: system_mod.f90:186-209)'
      stop 2
+  end if
+  if (density_profile) then
+     ! the profiles of a trapped system (the reference's dead DensityProfile, vpi.f90:471); the entry points are resolved
+     ! at run time, only here, so that the front end still links against backends without them
+     if (.not. trap) then
+        write (0,'(a)') ' pigs_vpi: density_profile = T needs a trapped system (trap = T): periodic runs write g(r) instead'
+        stop 2
+     end if
+     if (.not. density_bind()) then
+        write (0,'(a)') ' pigs_vpi: density_profile = T: this backend does not export pigs_density_init / _accumulate /'// &
+             & ' _read (the density profiles run on libpigs_hip.so only)'
+        stop 2
+     end if
   end if
   NWtot = n_walkers
   G = max(1,min(n_gpus,NWtot))
@@ -200,6 +215,9 @@ program pigs_vpi
   else
      print '(a)',    '  > Sampler             : host-driven (lock-step batches through K1)'
   end if
+  if (density_profile) then
+     print '(a)',    '  > Density profiles    : on (slice Nb: dens_vpi.out, rho_vpi.out, pr_vpi.out)'
+  end if
 
   !=====================================================================
 
@@ -282,6 +300,13 @@ contains
 
   real(8), allocatable :: vec(:),AvGrAll(:),AvGr2All(:),AvSkAll(:,:),AvSk2All(:,:),AvNrAll(:,:),AvNr2All(:,:),tmp1(:),tmp2(:,:),tmp3(:,:)
   real(8) :: cnt_all(13)
+  ! density profiles (density_profile = T): the block's counts from the device, the normalised block profiles, their
+  ! per-walker sums and the walker-averaged sums; ndv doubles of the block vector (0 with the key off)
+  integer :: npl,ndv,ndensav,ndensall
+  integer(c_int64_t), allocatable :: dc_pl(:,:),dc_rad(:,:),dc_pair(:,:),dc_smp(:)
+  integer(c_int32_t), allocatable :: dc_reset(:)
+  real(8), allocatable :: dpl(:),drad(:),dpair(:),AvDpl(:,:),AvDpl2(:,:),AvDrad(:,:),AvDrad2(:,:),AvDpair(:,:),AvDpair2(:,:)
+  real(8), allocatable :: AvDplAll(:),AvDpl2All(:),AvDradAll(:),AvDrad2All(:),AvDpairAll(:),AvDpair2All(:),tmpd(:)
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -369,6 +394,19 @@ contains
      dev_acc0 = 0
   end if
 
+  npl = 0; ndv = 0; ndensav = 0
+  if (density_profile) then
+     npl = Nbin**min(dim,2)
+     ndv = npl+2*Nbin+1
+     allocate (dc_pl(npl,NW),dc_rad(Nbin,NW),dc_pair(Nbin,NW),dc_smp(NW),dc_reset(NW),dpl(npl),drad(Nbin),dpair(Nbin))
+     allocate (AvDpl(npl,NW),AvDpl2(npl,NW),AvDrad(Nbin,NW),AvDrad2(Nbin,NW),AvDpair(Nbin,NW),AvDpair2(Nbin,NW))
+     allocate (AvDplAll(npl),AvDpl2All(npl),AvDradAll(Nbin),AvDrad2All(Nbin),AvDpairAll(Nbin),AvDpair2All(Nbin),tmpd(ndv-1))
+     AvDpl = 0.d0; AvDpl2 = 0.d0; AvDrad = 0.d0; AvDrad2 = 0.d0; AvDpair = 0.d0; AvDpair2 = 0.d0
+     AvDplAll = 0.d0; AvDpl2All = 0.d0; AvDradAll = 0.d0; AvDrad2All = 0.d0; AvDpairAll = 0.d0; AvDpair2All = 0.d0
+     dc_reset = 1
+     call pigs_check(dens_init(ctx,int(Nbin,c_int32_t),rcut/2.d0),'pigs_density_init')
+  end if
+
   allocate (perm(NW))
   do w=1,NW
      allocate (perm(w)%members(Np),perm(w)%histogram(Np))
@@ -405,7 +443,7 @@ contains
   ! the vector that meets the other shards' once per block: number of walkers with a diagonal block, their summed block
   ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
   nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
-  allocate (vec(nvec),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
+  allocate (vec(nvec+ndv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
   allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
   AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
   ngrav = 0; nnrav = 0
@@ -612,6 +650,9 @@ contains
                    & en9,c_null_ptr,c_null_ptr),'pigs_diagonal_estimators')
               est_have = .true.
            end if
+           ! the same walkers' slice Nb into the density accumulators: queued on the context's stream behind the
+           ! snapshot of _begin (device-resident sampler) / the flushed commits (host-driven), before the next step
+           if (density_profile) call pigs_check(dens_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_density_accumulate')
         end if
 
      end do   ! istep
@@ -636,6 +677,7 @@ contains
            nrho = dev_nrho
         end if
      end if
+     if (density_profile) call pigs_check(dens_read(ctx,dc_pl,dc_rad,dc_pair,dc_smp,dc_reset),'pigs_density_read')
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -653,6 +695,16 @@ contains
               vec(21:20+Nbin) = vec(21:20+Nbin)+gr(:,w)
               vec(21+Nbin:20+Nbin+dim*Nk) = vec(21+Nbin:20+Nbin+dim*Nk)+reshape(Sk(:,:,w),[dim*Nk])
               vec(nvec-1) = vec(nvec-1)+1.d0
+           end if
+           if (density_profile) then
+              call normalize_density(dim,Np,Nbin,rcut/2.d0,int(dc_smp(w),8),dc_pl(:,w),dc_rad(:,w),dc_pair(:,w),dpl,drad,dpair)
+              AvDpl(:,w)   = AvDpl(:,w)+dpl;     AvDpl2(:,w)   = AvDpl2(:,w)+dpl*dpl
+              AvDrad(:,w)  = AvDrad(:,w)+drad;   AvDrad2(:,w)  = AvDrad2(:,w)+drad*drad
+              AvDpair(:,w) = AvDpair(:,w)+dpair; AvDpair2(:,w) = AvDpair2(:,w)+dpair*dpair
+              vec(nvec+1:nvec+npl) = vec(nvec+1:nvec+npl)+dpl
+              vec(nvec+npl+1:nvec+npl+Nbin) = vec(nvec+npl+1:nvec+npl+Nbin)+drad
+              vec(nvec+npl+Nbin+1:nvec+npl+2*Nbin) = vec(nvec+npl+Nbin+1:nvec+npl+2*Nbin)+dpair
+              vec(nvec+ndv) = vec(nvec+ndv)+1.d0
            end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -677,7 +729,7 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
      ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
      if (ish==1 .and. NWtot>1) then
@@ -696,6 +748,16 @@ contains
            nnrav = nnrav+1
            tmp3 = reshape(vec(21+Nbin+dim*Nk:20+Nbin+dim*Nk+(Npw+1)*Nbin),[Npw+1,Nbin])/nnrall
            AvNrAll = AvNrAll+tmp3; AvNr2All = AvNr2All+tmp3*tmp3
+        end if
+        if (density_profile) then            ! walker average of the block's density profiles
+           ndensall = nint(vec(nvec+ndv))
+           if (ndensall>0) then
+              ndensav = ndensav+1
+              tmpd = vec(nvec+1:nvec+ndv-1)/ndensall
+              AvDplAll   = AvDplAll+tmpd(1:npl);                 AvDpl2All   = AvDpl2All+tmpd(1:npl)**2
+              AvDradAll  = AvDradAll+tmpd(npl+1:npl+Nbin);       AvDrad2All  = AvDrad2All+tmpd(npl+1:npl+Nbin)**2
+              AvDpairAll = AvDpairAll+tmpd(npl+Nbin+1:npl+2*Nbin); AvDpair2All = AvDpair2All+tmpd(npl+Nbin+1:npl+2*Nbin)**2
+           end if
         end if
      end if
      ! ---- checkpoint (reference vpi.f90:541-545, vpi_mod.f90:263-309): text worldline, particle-major
@@ -782,6 +844,11 @@ contains
         call write_sk('sk_vpi'//trim(suffix)//'.out',ep,diag_bl(w),AvSk(:,:,w),AvSk2(:,:,w))
         call write_nr('nr_vpi'//trim(suffix)//'.out',ep,obdm_bl(w),AvNr(:,:,w),AvNr2(:,:,w))
      end if
+     if (density_profile) then
+        call write_density('dens_vpi'//trim(suffix)//'.out',dim,Nbin,rcut/2.d0,diag_bl(w),AvDpl(:,w),AvDpl2(:,w))
+        call write_profile('rho_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),AvDrad(:,w),AvDrad2(:,w))
+        call write_profile('pr_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),AvDpair(:,w),AvDpair2(:,w))
+     end if
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
@@ -789,6 +856,11 @@ contains
         call write_radial('gr_vpi.out',ep,ngrav,AvGrAll,AvGr2All)
         call write_sk('sk_vpi.out',ep,ngrav,AvSkAll,AvSk2All)
         call write_nr('nr_vpi.out',ep,nnrav,AvNrAll,AvNr2All)
+     end if
+     if (density_profile) then
+        call write_density('dens_vpi.out',dim,Nbin,rcut/2.d0,ndensav,AvDplAll,AvDpl2All)
+        call write_profile('rho_vpi.out',Nbin,rcut/2.d0,ndensav,AvDradAll,AvDrad2All)
+        call write_profile('pr_vpi.out',Nbin,rcut/2.d0,ndensav,AvDpairAll,AvDpair2All)
      end if
   end if
 
