@@ -11,6 +11,9 @@ restatement.  The fixtures are data: inputs + expected outputs, no reference sou
 `python tests/golden/make_golden.py walkers [set ...]` writes only the many-seed sets (WALKER_SETS); they run the
 reference once per seed on a pool of processes sized by the affinity mask (at most 16).
 
+`python tests/golden/make_golden.py runs [name ...]` writes the program runs (RUNS).  The runs beyond 256 particles (n257_*,
+n300_*, n520_*, trap3d_n260_*) take 2 to 20 s each on one core: program + driver, about a minute for all seven.
+
 The reference's answers behind tests/test_oracle_vs_ref.py and tests/test_host_sampler.py (tests/golden/ref_tapes/)
 are recorded by those tests themselves (tests/reftape.py):
 
@@ -275,6 +278,29 @@ RUNS = {
                                     Nblock=6, Nstep=10, CWorm="0.5d0", Nobdm=10, Npw=2, big=True),
     "c5_n256_dipolar_long_s1982": dict(dim=3, Np=256, Nb=160, seed=1982, sampling="bis", Lstag=32, Nlev=4, Nstag=5,
                                        Nblock=6, Nstep=10, CWorm="0.5d0", Nobdm=10, Npw=2, big=True, potential="dipolar"),
+    # ---- beyond 256 particles: more than four 64-partner passes per bead, i.e. a second (third) 256-partner trip in every
+    # kernel (tests/test_gpu_large_np.py, tests/test_large_np_fixtures.py).  Short chains, a few steps: seconds per run.
+    # Np = 300: five passes, the last one ragged; Nlev = 4 (one-launch sweep kernel) and Nlev = 5 (stage machine)
+    "n300_bis4_s1982": dict(dim=3, Np=300, Nb=16, seed=1982, sampling="bis", Lstag=8, Nlev=4, Nstag=2,
+                            Nblock=2, Nstep=3, CWorm="0.0d0", Nobdm=0, Npw=0, big=True),
+    "n300_bis4_s1983": dict(dim=3, Np=300, Nb=16, seed=1983, sampling="bis", Lstag=8, Nlev=4, Nstag=2,
+                            Nblock=2, Nstep=3, CWorm="0.0d0", Nobdm=0, Npw=0, big=True),
+    "n300_bis5_s1982": dict(dim=3, Np=300, Nb=24, seed=1982, sampling="bis", Lstag=8, Nlev=5, Nstag=2,
+                            Nblock=2, Nstep=3, CWorm="0.0d0", Nobdm=0, Npw=0, big=True),
+    # Np = 520: nine passes (third trip), Lstag = 20: the sweep kernel's task totals at their largest
+    "n520_lstag20_s1982": dict(dim=3, Np=520, Nb=20, seed=1982, sampling="bis", Lstag=20, Nlev=4, Nstag=2,
+                               Nblock=2, Nstep=2, CWorm="0.0d0", Nobdm=0, Npw=0, big=True),
+    # Np = 257: one particle in the fifth pass; staging movers
+    "n257_sta_s1982": dict(dim=3, Np=257, Nb=16, seed=1982, sampling="sta", Lstag=8, Nlev=3, Nstag=2,
+                           Nblock=2, Nstep=3, CWorm="0.0d0", Nobdm=0, Npw=0, big=True),
+    # worm sector at Np = 300 (the knobs of he4_wormbusy_*; seed 4 of the seeds 1-6 tried at CWorm = 1 and 3 is the one
+    # with opens, closes AND swaps accepted within 32 steps: 3 opens, 2 closes, 2 swaps, 16 diagonal steps)
+    "n300_worm_s4": dict(dim=3, Np=300, Nb=16, seed=4, dt="2.0d-2", sampling="bis", Lstag=8, Nlev=4, Nstag=2,
+                         Nblock=4, Nstep=8, CWorm="3.0d0", Nobdm=4, Npw=1, big=True),
+    # 3D trap, Np = 260: the sweep kernel's trap template (exact-term arithmetic) with a fifth pass
+    "trap3d_n260_s1982": dict(dim=3, Np=260, Nb=16, seed=1982, trap="T", a_ho="1.0d0 1.3d0 0.8d0", dt="1.0d-2",
+                              sampling="bis", Lstag=8, Nlev=3, Nstag=2, Nblock=2, Nstep=3, CWorm="0.0d0", Nobdm=0, Npw=0,
+                              big=True),
 }
 RUN_FILES = ["e_vpi.out", "et_vpi.out", "gr_vpi.out", "sk_vpi.out", "nr_vpi.out", "fort.99"]
 BIG_STRIDE = 8           # fixtures of the N=256 runs keep every 8th bead + SHA-256 + per-bead sums

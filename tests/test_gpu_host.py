@@ -427,7 +427,10 @@ def test_gpu_crystal_start_from_config_ini(exe, dev, tmp_path):
 
 @pytest.mark.parametrize("sampling,system,samp,cworm", [
     ("bis", "dim = 3, Np = 30, density = 0.3d0", "Nb = 16, Lstag = 6, Nlev = 3", "0.4d0"),
-    ("sta", "dim = 2, Np = 21, density = 0.1d0", "Nb = 12, Lstag = 6, Nlev = 2", "0.5d0")])
+    ("sta", "dim = 2, Np = 21, density = 0.1d0", "Nb = 12, Lstag = 6, Nlev = 2", "0.5d0"),
+    # beyond 256 particles (five 64-partner passes; no reference run of these inputs exists): diagonal sector only, and a busy worm
+    ("bis", "dim = 3, Np = 300, density = 0.3d0", "Nb = 16, Lstag = 8, Nlev = 4", "0.0d0"),
+    ("bis", "dim = 3, Np = 300, density = 0.3d0", "Nb = 16, Lstag = 8, Nlev = 4", "0.4d0")])
 def test_samplers_agree_bit_for_bit_over_hundreds_of_steps(exe, tmp_path, sampling, system, samp, cworm):
     """Soak (short form of scripts/k6_vs_host_soak.py, which runs 3 000 steps: identical): 300 MC steps x 4 walkers with a
     busy worm sector through the host-driven sampler and through the device-resident one.  Final worldlines bit-identical,

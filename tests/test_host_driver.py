@@ -61,12 +61,16 @@ def test_front_end_reproduces_reference_files(exe, name, tmp_path):
     assert np.all(np.abs(rows - wrows) <= 1e-13 * np.abs(wrows)), np.max(np.abs(rows - wrows) / np.abs(wrows))
 
 
-@pytest.mark.parametrize("name", ["c3_n256_s1982", "c5_n256_dipolar_s1982"])
+@pytest.mark.parametrize("name", ["c3_n256_s1982", "c5_n256_dipolar_s1982",
+                                  # beyond 256 particles (tests/test_large_np_fixtures.py)
+                                  "n300_bis4_s1982", "n300_bis4_s1983", "n300_bis5_s1982", "n520_lstag20_s1982",
+                                  "n257_sta_s1982", "n300_worm_s4", "trap3d_n260_s1982"])
 def test_front_end_at_baseline_sizes(exe, name, tmp_path):
     """BASELINE configs 3 and 5 (N=256, 161 / 321 beads; C5 with the dipolar table, worm sector and swaps) through
     the host-driven sampler: final worldline bit-identical to the reference's movers run in the program's
     schedule (SHA-256 of all N*M*3 coordinates), 64-bit block energies, and -- where the reference PROGRAM can run
-    the input (Aziz potential) -- its files byte for byte."""
+    the input (Aziz potential) -- its files byte for byte.  The same for the runs beyond 256 particles (periodic and
+    trapped, bisection and staging movers, worm sector)."""
     src = os.path.join(RUNS, name)
     drv = dict(np.load(os.path.join(src, "driver.npz")))
     pot = str(drv["potential"])
