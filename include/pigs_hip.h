@@ -295,6 +295,33 @@ int pigs_density_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
 int pigs_density_read(pigs_ctx *ctx, int64_t *planar, int64_t *radial, int64_t *pair, int64_t *samples,
                       const int32_t *reset);
 
+/* ---- imaginary-time density correlations F(q,tau) of a PERIODIC system (new: the reference has equal-time estimators
+ * only; PIGS keeps the whole path, and the worldlines are resident on the device) --------------------------------------
+ *   F(q, tau_l) = < rho_q(tau0 + tau_l) rho_-q(tau0) > / Np,    tau_l = l dt  (l links of the path)
+ * on the reference's S(k) grid (sample_mod.f90:435-476, vpi.f90:119): for axis k = 1..dim and iq = 1..Nk,
+ *   q = real(iq) * (2 pi / Lbox(k)),  C(s) = sum_i cos(q x_k(i,s)),  S(s) = sum_i sin(q x_k(i,s))
+ * with the phase q x formed as pigs_structure_batch forms it.  The slices used are the window Nb-window .. Nb+window
+ * (0 <= window <= Nb), the lags l = 0 .. Ntau (0 <= Ntau <= 2 window).  Per walker and accumulate call the device adds
+ *   acc[walker][l][iq][k] += sum over a = Nb-window .. Nb+window-l (ascending) of C(a) C(a+l) + S(a) S(a+l)
+ * and 1 to samples[walker].  n_pairs(l) = 2 window + 1 - l terms per call, so the estimator is
+ *   F(q_{k,iq}; tau_l) = acc / (samples * n_pairs(l) * Np)          (the caller's division; profiles.normalize_fqt)
+ * and its l = 0 value is S(q) averaged over the window; with window = 0, Ntau = 0 the increment is exactly the
+ * reference's StructureFactor term of slice Nb.  The sums are taken in fixed orders without floating-point atomics: the
+ * same worldline gives the same bits whatever the walker list.  The window must stay inside the part of the path where
+ * the projection has converged (PIGS expectation values are ground-state ones only that far from the ends): choosing it
+ * is the caller's business, the library does not judge it.
+ *
+ * pigs_fqt_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context,
+ * PIGS_ERR_ARG for Nk < 1, window < 0, window > Nb, Ntau < 0 or Ntau > 2 window. */
+int pigs_fqt_init(pigs_ctx *ctx, int32_t Nk, int32_t Ntau, int32_t window);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no host synchronisation: it sees the worldline every call queued before it left, never the next step's.  PIGS_ERR_ARG
+ * before pigs_fqt_init or for a walker out of range. */
+int pigs_fqt_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' raw sums F[n_walkers][Ntau+1][Nk][dim] (k fastest) and samples[n_walkers]; then zeroes those of the
+ * walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context. */
+int pigs_fqt_read(pigs_ctx *ctx, double *F, int64_t *samples, const int32_t *reset);
+
 /* ---- multi-GPU: block-estimator reduction (new) ------------------------ */
 /* RCCL communicator over `nranks` contexts.  Single-process form (one host thread per
  * GPU, the Fortran host: pigs_vpi's &gpu n_gpus = G): pigs_comm_init_all.  Multi-process form: rank 0 obtains an id

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "pigs_sampler_events", "pigs_sampler_event_ints", "pigs_sampler_nrho", "pigs_slice_download", "pigs_build_tables_kind", "pigs_structure_batch",
     "pigs_diagonal_estimators", "pigs_diagonal_estimators_begin", "pigs_diagonal_estimators_end",
     "pigs_density_init", "pigs_density_accumulate", "pigs_density_read",
+    "pigs_fqt_init", "pigs_fqt_accumulate", "pigs_fqt_read",
 ]
 
 
@@ -126,6 +127,9 @@ def load_library(path=LIB_PATH):
     L.pigs_density_init.argtypes = [vp, C.c_int32, C.c_double]
     L.pigs_density_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_density_read.argtypes = [vp, _lp, _lp, _lp, _lp, _ip]
+    L.pigs_fqt_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.pigs_fqt_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_fqt_read.argtypes = [vp, _dp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -445,6 +449,41 @@ class PigsContext:
         lp = C.POINTER(C.c_int64)
         _chk(self.L, self.L.pigs_density_read(self.h, *(out[k].ctypes.data_as(lp) for k in ("planar", "radial", "pair", "samples")),
                                               mask), "pigs_density_read")
+        return out
+
+    # ---- imaginary-time density correlations of a periodic system (pigs_fqt_*: raw sums per walker, lag, harmonic, axis)
+    def fqt_init(self, Nk, Ntau, window):
+        """Allocate and zero the sums of F(q, tau_l), l = 0..Ntau, over the slices Nb-window..Nb+window on the S(k) grid
+        of Nk harmonics per axis.  The window has to stay inside the part of the path where the projection has
+        converged; that is the caller's choice.  Calling it again resizes and zeroes."""
+        _chk(self.L, self.L.pigs_fqt_init(self.h, int(Nk), int(Ntau), int(window)), "pigs_fqt_init")
+        self._fqt_shape = (int(Ntau) + 1, int(Nk), self.cfg.dim)
+
+    def fqt_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        if walkers is None:
+            _chk(self.L, self.L.pigs_fqt_accumulate(self.h, self.n_walkers, None), "pigs_fqt_accumulate")
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, self.L.pigs_fqt_accumulate(self.h, wl.size, _i(wl)), "pigs_fqt_accumulate")
+
+    def fqt_read(self, reset=None):
+        """dict: F, the raw sums [W, Ntau+1, Nk, dim] (profiles.normalize_fqt divides them), and samples [W] (int64).
+        reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        shape = getattr(self, "_fqt_shape", None)
+        if shape is None:
+            raise PigsError("fqt_read: fqt_init first")
+        W = self.n_walkers
+        out = {"F": np.zeros((W,) + shape), "samples": np.zeros(W, np.int64)}
+        if reset is None or reset is False:
+            mask = None
+        else:
+            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
+            if keep.size != W:
+                raise ValueError("reset mask needs one entry per walker")
+            mask = _i(keep)
+        _chk(self.L, self.L.pigs_fqt_read(self.h, _d(out["F"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
+             "pigs_fqt_read")
         return out
 
     # ---- K5

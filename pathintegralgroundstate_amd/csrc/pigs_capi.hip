@@ -198,6 +198,14 @@ struct pigs_ctx {
     int         dens_nbin = 0;              // 0: pigs_density_init not called yet
     size_t      dens_nplanar = 0;           // planar bins per walker: Nbin^min(dim,2)
     double      dens_h = 0.0, dens_b = 0.0, dens_br = 0.0;
+    // imaginary-time density correlations of a periodic system (pigs_fqt_*): raw sums [walker][l][iq][k], the samples per
+    // walker, and the C/S scratch of one launch's window slices ([fqt_slots][2 window + 1][Nk dim][2])
+    DevBuf<double> d_fqt_acc, d_fqt_rho;
+    DevBuf<unsigned long long> d_fqt_samples;
+    int         fqt_nk = 0;                 // 0: pigs_fqt_init not called yet
+    int         fqt_ntau = 0, fqt_window = 0, fqt_slots = 0;
+    std::vector<int64_t> fqt_mark;          // per walker: the last launch (fqt_launch) that listed it
+    int64_t     fqt_launch = 0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -1370,6 +1378,85 @@ int pigs_density_read(pigs_ctx *c, int64_t *planar, int64_t *radial, int64_t *pa
             HIPCHK(hipMemsetAsync(c->d_dradial.p + w * nb, 0, (e - w) * nb * u, s));
             HIPCHK(hipMemsetAsync(c->d_dpair.p + w * nb, 0, (e - w) * nb * u, s));
             HIPCHK(hipMemsetAsync(c->d_dsamples.p + w, 0, (e - w) * u, s));
+            w = e;
+        }
+    }
+    SYNC_CHECKED(c);
+    return PIGS_OK;
+}
+
+// ---- imaginary-time density correlations F(q,tau) of a periodic system ---------------------------
+// Raw sums per walker, lag, harmonic and axis (pigs_fqt.hip), accumulated on the device and read per block.
+int pigs_fqt_init(pigs_ctx *c, int32_t Nk, int32_t Ntau, int32_t window)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "F(q,tau) is defined for periodic systems only (the q grid is the box's)");
+    if (Nk < 1 || window < 0 || window > c->P.Nb || Ntau < 0 || Ntau > 2 * window)
+        return fail(PIGS_ERR_ARG, "pigs_fqt_init: Nk=%d Ntau=%d window=%d (Nb=%d)", Nk, Ntau, window, c->P.Nb);
+    const size_t W = (size_t)c->n_walkers, per = (size_t)(Ntau + 1) * Nk * c->P.dim;
+    const int slots = std::min(c->n_walkers, kFqtListMax);
+    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
+    c->fqt_nk = 0;
+    HIPCHK(c->d_fqt_acc.alloc(W * per));
+    HIPCHK(c->d_fqt_samples.alloc(W));
+    HIPCHK(c->d_fqt_rho.alloc((size_t)slots * (2 * window + 1) * 2 * Nk * c->P.dim));
+    HIPCHK(hipMemsetAsync(c->d_fqt_acc.p, 0, W * per * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_fqt_samples.p, 0, W * sizeof(unsigned long long), c->stream));
+    SYNC_CHECKED(c);
+    c->fqt_nk = Nk;
+    c->fqt_ntau = Ntau;
+    c->fqt_window = window;
+    c->fqt_slots = slots;
+    return PIGS_OK;
+}
+
+int pigs_fqt_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->fqt_nk) return fail(PIGS_ERR_ARG, "pigs_fqt_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // The list goes by value in the kernel arguments: queued on the context's stream, nothing to wait for.  A launch
+    // ends where the scratch is full or a walker would appear in it a second time (one thread owns an accumulator
+    // element per launch); the stream orders the launches, so a walker listed twice is added twice.
+    // A list left out (0..n-1) holds no repeats and needs no marks.
+    if (walkers) c->fqt_mark.resize(c->n_walkers, 0);
+    for (int i0 = 0; i0 < n;) {
+        const int64_t launch = ++c->fqt_launch;
+        FqtList L{};
+        int m = 0;
+        while (i0 + m < n && m < c->fqt_slots && !(walkers && c->fqt_mark[sw[i0 + m]] == launch)) {
+            if (walkers) c->fqt_mark[sw[i0 + m]] = launch;
+            L.w[m] = sw[i0 + m];
+            ++m;
+        }
+        HIPCHK(launch_fqt(c->P, c->d_paths.p, m, L, c->fqt_window, c->fqt_ntau, c->fqt_nk, c->d_fqt_rho.p, c->d_fqt_acc.p,
+                          c->d_fqt_samples.p, c->stream));
+        i0 += m;
+    }
+    return PIGS_OK;
+}
+
+int pigs_fqt_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->fqt_nk) return fail(PIGS_ERR_ARG, "pigs_fqt_init first");
+    if (!F || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t W = (size_t)c->n_walkers, per = (size_t)(c->fqt_ntau + 1) * c->fqt_nk * c->P.dim;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(F, c->d_fqt_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(samples, c->d_fqt_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (reset) {
+        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
+        for (size_t w = 0; w < W;) {
+            if (!reset[w]) { ++w; continue; }
+            size_t e = w;
+            while (e < W && reset[e]) ++e;
+            HIPCHK(hipMemsetAsync(c->d_fqt_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
+            HIPCHK(hipMemsetAsync(c->d_fqt_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
             w = e;
         }
     }

@@ -59,6 +59,16 @@ hipError_t launch_density(const DevParams &P, const double *paths, int n, const 
                           double b, double br, unsigned long long *planar, unsigned long long *radial,
                           unsigned long long *pair, unsigned long long *samples, hipStream_t st);
 
+// pigs_fqt.hip: imaginary-time density correlations F(q,tau) of a periodic system (pigs_fqt_accumulate).  Stage 1 writes
+// C(s), S(s) of the window slices Nb-window .. Nb+window of the n listed walkers to rho ([slot][slice][(iq-1) dim + k][2]
+// doubles), stage 2 adds the ordered pair sums of the lags 0..Ntau to acc ([walker][l][(iq-1) dim + k]) and 1 to samples.
+// One thread owns an accumulator element per launch: the caller never lists a walker twice in ONE launch.  The list
+// travels in the kernel arguments, at most kFqtListMax walkers per launch.
+constexpr int kFqtListMax = 256;
+struct FqtList { int32_t w[kFqtListMax]; };
+hipError_t launch_fqt(const DevParams &P, const double *paths, int n, const FqtList &list, int window, int Ntau, int Nk,
+                      double *rho, double *acc, unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

@@ -417,12 +417,43 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its accumulators after the copy
        integer(c_int) :: rc
      end function pigs_density_read_t
+
+     ! imaginary-time density correlations of a periodic system (include/pigs_hip.h, pigs_fqt_*): looked up at run time,
+     ! see fqt_bind
+     function pigs_fqt_init_t(ctx,Nk,Ntau,window) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value        :: ctx
+       integer(c_int32_t), value :: Nk,Ntau,window
+       integer(c_int) :: rc
+     end function pigs_fqt_init_t
+
+     function pigs_fqt_accumulate_t(ctx,n,walkers) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int32_t), value      :: n
+       integer(c_int32_t), intent(in) :: walkers(*)
+       integer(c_int) :: rc
+     end function pigs_fqt_accumulate_t
+
+     function pigs_fqt_read_t(ctx,F,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: F(*)          ! raw sums (dim,Nk,0:Ntau,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_fqt_read_t
   end interface
 
   ! bound by density_bind (null until then)
   procedure(pigs_density_init_t), pointer       :: dens_init => null()
   procedure(pigs_density_accumulate_t), pointer :: dens_accumulate => null()
   procedure(pigs_density_read_t), pointer       :: dens_read => null()
+
+  ! bound by fqt_bind (null until then)
+  procedure(pigs_fqt_init_t), pointer       :: fqt_init => null()
+  procedure(pigs_fqt_accumulate_t), pointer :: fqt_accumulate => null()
+  procedure(pigs_fqt_read_t), pointer       :: fqt_read => null()
 
 contains
 
@@ -456,6 +487,19 @@ contains
     call c_f_procpointer(f(2),dens_accumulate)
     call c_f_procpointer(f(3),dens_read)
   end function density_bind
+
+  ! The F(q,tau) entry points, found like the density ones: at run time, only when a run asks for them.
+  logical function fqt_bind()
+    type(c_funptr) :: f(3)
+    f(1) = c_dlsym(c_null_ptr,'pigs_fqt_init'//c_null_char)
+    f(2) = c_dlsym(c_null_ptr,'pigs_fqt_accumulate'//c_null_char)
+    f(3) = c_dlsym(c_null_ptr,'pigs_fqt_read'//c_null_char)
+    fqt_bind = c_associated(f(1)) .and. c_associated(f(2)) .and. c_associated(f(3))
+    if (.not. fqt_bind) return
+    call c_f_procpointer(f(1),fqt_init)
+    call c_f_procpointer(f(2),fqt_accumulate)
+    call c_f_procpointer(f(3),fqt_read)
+  end function fqt_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -12,6 +12,7 @@ module pigs_estimators
   public :: normalize_gr, normalize_sk, normalize_nr, variance, perm_state, perm_sampling
   public :: write_radial, write_sk, write_nr
   public :: normalize_density, write_density, write_profile
+  public :: normalize_fqt, write_fqt
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -224,6 +225,44 @@ contains
     end do
     close (u)
   end subroutine write_profile
+
+  ! ---- imaginary-time density correlations (raw sums of pigs_fqt_read: window slices Nb-window..Nb+window, lags
+  ! 0..Ntau) -> one walker's F(q,tau_l) of one block with S samples: raw/(S n_pairs(l) Np), n_pairs(l) = 2 window + 1 - l
+  ! products per sample.  Lag 0 is S(k) averaged over the window (window = 0: normalize_sk's value).
+  subroutine normalize_fqt(p,Ntau,window,S,raw,F)
+    type(est_params), intent(in) :: p
+    integer, intent(in)    :: Ntau,window
+    integer(8), intent(in) :: S
+    real(8), intent(in)    :: raw(p%dim,p%Nk,0:Ntau)
+    real(8), intent(out)   :: F(p%dim,p%Nk,0:Ntau)
+    integer :: l
+    do l=0,Ntau
+       F(:,:,l) = raw(:,:,l)/(real(S,8)*real(2*window+1-l,8)*real(p%Np,8))
+    end do
+  end subroutine normalize_fqt
+
+  ! fqt_vpi.out: one table per lag laid out like sk_vpi.out (q, mean, err per axis), each preceded by a comment line
+  ! with l, tau_l = l dt and n_pairs(l), and followed by two blank lines (a gnuplot index)
+  subroutine write_fqt(fname,p,Ntau,window,dt,n,av,av2)
+    character(len=*), intent(in) :: fname
+    type(est_params), intent(in) :: p
+    integer, intent(in)    :: Ntau,window,n
+    real(8), intent(in)    :: dt
+    real(8), intent(inout) :: av(p%dim,p%Nk,0:Ntau),av2(p%dim,p%Nk,0:Ntau)
+    integer :: j,k,l,u
+    open (newunit=u,file=fname)
+    do l=0,Ntau
+       write (u,'(a,i6,a,g20.10e3,a,i6)') '# l =',l,'  tau =',real(l,8)*dt,'  n_pairs =',2*window+1-l
+       do j=1,p%Nk
+          av(:,j,l)  = av(:,j,l)/real(n)
+          av2(:,j,l) = av2(:,j,l)/real(n)
+          write (u,'(20g20.10e3)') (j*p%qbin(k),av(k,j,l),variance(n,av(k,j,l),av2(k,j,l)),k=1,p%dim)
+       end do
+       write (u,'(a)') ''
+       write (u,'(a)') ''
+    end do
+    close (u)
+  end subroutine write_fqt
 
   ! the reference's "variance": standard error sqrt((<x^2>-<x>^2)/n)
   function variance(n,av,av2) result(v)

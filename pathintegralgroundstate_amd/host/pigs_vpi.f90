@@ -14,6 +14,10 @@
 ! (potential: aziz2 | lj | dipolar -- the reference selects it by editing system_mod.f90)
 ! (density_profile = T, trapped systems only: the planar and radial density and the pair distribution of the middle
 ! slice, accumulated on the GPU -- dens_vpi.out, rho_vpi.out, pr_vpi.out; grid half-width rcut/2, Nbin bins per axis)
+! (fq_tau = T, periodic systems only: the imaginary-time density correlations F(q,tau_l) = <rho_q(tau0+tau_l) rho_-q(tau0)>/Np
+! on the S(k) grid for the lags l = 0..fq_ntau (tau_l = l dt) between the slices Nb-fq_window..Nb+fq_window, accumulated
+! on the GPU -- fqt_vpi.out; fq_window defaults to ceiling(fq_ntau/2) and must stay inside the part of the path where
+! the projection has converged: that is the user's choice, the program does not judge it)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -44,7 +48,8 @@ program pigs_vpi
   real (kind=8)     :: a_ho(3)
   integer           :: dim,Np,Nb,seed,CMFreq,Lstag,Nlev,Nstag,Nblock,Nstep,Nbin,Nk
   integer           :: Nobdm,Npw,Nmax,n_walkers,device,ios,k1_variant,n_gpus
-  logical           :: device_sampler,checkpointing,same_device,density_profile
+  logical           :: device_sampler,checkpointing,same_device,density_profile,fq_tau
+  integer           :: fq_ntau,fq_window
   logical           :: sampler_auto
   integer(c_int)    :: rc_probe
   type(pigs_sweep_params) :: probe_par
@@ -56,7 +61,8 @@ program pigs_vpi
   namelist /wavefun/ Nmax,wf_table,v_table
   namelist /extpot/  a_ho
   namelist /jastrow/ Rm
-  namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device,density_profile
+  namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device,density_profile, &
+       &             fq_tau,fq_ntau,fq_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -79,6 +85,7 @@ program pigs_vpi
   delta_cm = 0.d0; density = 0.d0; a_ho = 1.d0; Rm = 1.d0
   n_walkers = 1; device = 0; device_sampler = .false.; potential = 'aziz2'; checkpointing = .true.; k1_variant = 0
   n_gpus = 1; same_device = .false.; density_profile = .false.
+  fq_tau = .false.; fq_ntau = 0; fq_window = -1
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -111,6 +118,29 @@ program pigs_vpi
      if (.not. density_bind()) then
         write (0,'(a)') ' pigs_vpi: density_profile = T: this backend does not export pigs_density_init / _accumulate /'// &
              & ' _read (the density profiles run on libpigs_hip.so only)'
+        stop 2
+     end if
+  end if
+  if (fq_tau) then
+     ! imaginary-time density correlations of a periodic system; the entry points are resolved at run time like the
+     ! density profiles' ones
+     if (trap) then
+        write (0,'(a)') ' pigs_vpi: fq_tau = T needs a periodic system (trap = F): its q grid is that of the box'
+        stop 2
+     end if
+     if (fq_window<0) fq_window = (max(fq_ntau,0)+1)/2          ! ceiling(fq_ntau/2)
+     if (fq_ntau<0 .or. fq_ntau>2*fq_window) then
+        write (0,'(a,i0,a,i0,a)') ' pigs_vpi: fq_tau = T: fq_ntau = ',fq_ntau,' must lie in 0 .. 2*fq_window = ',2*fq_window, &
+             & ' (lags between the slices Nb-fq_window .. Nb+fq_window)'
+        stop 2
+     end if
+     if (fq_window>Nb) then
+        write (0,'(a,i0,a,i0)') ' pigs_vpi: fq_tau = T: fq_window = ',fq_window,' must not exceed Nb = ',Nb
+        stop 2
+     end if
+     if (.not. fqt_bind()) then
+        write (0,'(a)') ' pigs_vpi: fq_tau = T: this backend does not export pigs_fqt_init / _accumulate / _read'// &
+             & ' (F(q,tau) runs on libpigs_hip.so only)'
         stop 2
      end if
   end if
@@ -219,6 +249,10 @@ program pigs_vpi
      print '(a)',    '  > Density profiles    : on (slice Nb: dens_vpi.out, rho_vpi.out, pr_vpi.out)'
   end if
 
+  if (fq_tau) then
+     print '(a,i0,a,i0,a,i0,a)', '  > F(q,tau)            : on (lags 0..',fq_ntau,', slices Nb-',fq_window,'..Nb+',fq_window,': fqt_vpi.out)'
+  end if
+
   !=====================================================================
 
   !$omp parallel num_threads(G) default(shared)
@@ -307,6 +341,12 @@ contains
   integer(c_int32_t), allocatable :: dc_reset(:)
   real(8), allocatable :: dpl(:),drad(:),dpair(:),AvDpl(:,:),AvDpl2(:,:),AvDrad(:,:),AvDrad2(:,:),AvDpair(:,:),AvDpair2(:,:)
   real(8), allocatable :: AvDplAll(:),AvDpl2All(:),AvDradAll(:),AvDrad2All(:),AvDpairAll(:),AvDpair2All(:),tmpd(:)
+  ! F(q,tau) (fq_tau = T): the block's raw sums from the device, the normalised block values, their per-walker sums and
+  ! the walker-averaged sums; nfv doubles of the block vector behind the density ones (0 with the key off)
+  integer :: nfq,nfv,nfqav,nfqall
+  integer(c_int64_t), allocatable :: fq_smp(:)
+  integer(c_int32_t), allocatable :: fq_reset(:)
+  real(8), allocatable :: fq_raw(:,:,:,:),fqb(:,:,:),AvFq(:,:,:,:),AvFq2(:,:,:,:),AvFqAll(:,:,:),AvFq2All(:,:,:),tmpf(:,:,:)
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -407,6 +447,18 @@ contains
      call pigs_check(dens_init(ctx,int(Nbin,c_int32_t),rcut/2.d0),'pigs_density_init')
   end if
 
+  nfq = 0; nfv = 0; nfqav = 0
+  if (fq_tau) then
+     nfq = dim*Nk*(fq_ntau+1)
+     nfv = nfq+1
+     ! (third index: lag l + 1; 1-based, as every array here that goes through reshape)
+     allocate (fq_raw(dim,Nk,fq_ntau+1,NW),fq_smp(NW),fq_reset(NW),fqb(dim,Nk,fq_ntau+1),tmpf(dim,Nk,fq_ntau+1))
+     allocate (AvFq(dim,Nk,fq_ntau+1,NW),AvFq2(dim,Nk,fq_ntau+1,NW),AvFqAll(dim,Nk,fq_ntau+1),AvFq2All(dim,Nk,fq_ntau+1))
+     AvFq = 0.d0; AvFq2 = 0.d0; AvFqAll = 0.d0; AvFq2All = 0.d0
+     fq_reset = 1
+     call pigs_check(fqt_init(ctx,int(Nk,c_int32_t),int(fq_ntau,c_int32_t),int(fq_window,c_int32_t)),'pigs_fqt_init')
+  end if
+
   allocate (perm(NW))
   do w=1,NW
      allocate (perm(w)%members(Np),perm(w)%histogram(Np))
@@ -443,7 +495,7 @@ contains
   ! the vector that meets the other shards' once per block: number of walkers with a diagonal block, their summed block
   ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
   nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
-  allocate (vec(nvec+ndv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
+  allocate (vec(nvec+ndv+nfv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
   allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
   AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
   ngrav = 0; nnrav = 0
@@ -653,6 +705,8 @@ contains
            ! the same walkers' slice Nb into the density accumulators: queued on the context's stream behind the
            ! snapshot of _begin (device-resident sampler) / the flushed commits (host-driven), before the next step
            if (density_profile) call pigs_check(dens_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_density_accumulate')
+           ! and, at the same place, their window slices into the F(q,tau) sums
+           if (fq_tau) call pigs_check(fqt_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqt_accumulate')
         end if
 
      end do   ! istep
@@ -678,6 +732,7 @@ contains
         end if
      end if
      if (density_profile) call pigs_check(dens_read(ctx,dc_pl,dc_rad,dc_pair,dc_smp,dc_reset),'pigs_density_read')
+     if (fq_tau) call pigs_check(fqt_read(ctx,fq_raw,fq_smp,fq_reset),'pigs_fqt_read')
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -706,6 +761,12 @@ contains
               vec(nvec+npl+Nbin+1:nvec+npl+2*Nbin) = vec(nvec+npl+Nbin+1:nvec+npl+2*Nbin)+dpair
               vec(nvec+ndv) = vec(nvec+ndv)+1.d0
            end if
+           if (fq_tau) then
+              call normalize_fqt(ep,fq_ntau,fq_window,int(fq_smp(w),8),fq_raw(:,:,:,w),fqb)
+              AvFq(:,:,:,w) = AvFq(:,:,:,w)+fqb; AvFq2(:,:,:,w) = AvFq2(:,:,:,w)+fqb*fqb
+              vec(nvec+ndv+1:nvec+ndv+nfq) = vec(nvec+ndv+1:nvec+ndv+nfq)+reshape(fqb,[nfq])
+              vec(nvec+ndv+nfv) = vec(nvec+ndv+nfv)+1.d0
+           end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
            write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -729,7 +790,7 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
      ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
      if (ish==1 .and. NWtot>1) then
@@ -757,6 +818,14 @@ contains
               AvDplAll   = AvDplAll+tmpd(1:npl);                 AvDpl2All   = AvDpl2All+tmpd(1:npl)**2
               AvDradAll  = AvDradAll+tmpd(npl+1:npl+Nbin);       AvDrad2All  = AvDrad2All+tmpd(npl+1:npl+Nbin)**2
               AvDpairAll = AvDpairAll+tmpd(npl+Nbin+1:npl+2*Nbin); AvDpair2All = AvDpair2All+tmpd(npl+Nbin+1:npl+2*Nbin)**2
+           end if
+        end if
+        if (fq_tau) then                     ! walker average of the block's F(q,tau)
+           nfqall = nint(vec(nvec+ndv+nfv))
+           if (nfqall>0) then
+              nfqav = nfqav+1
+              tmpf = reshape(vec(nvec+ndv+1:nvec+ndv+nfq),[dim,Nk,fq_ntau+1])/nfqall
+              AvFqAll = AvFqAll+tmpf; AvFq2All = AvFq2All+tmpf*tmpf
            end if
         end if
      end if
@@ -849,6 +918,7 @@ contains
         call write_profile('rho_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),AvDrad(:,w),AvDrad2(:,w))
         call write_profile('pr_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),AvDpair(:,w),AvDpair2(:,w))
      end if
+     if (fq_tau) call write_fqt('fqt_vpi'//trim(suffix)//'.out',ep,fq_ntau,fq_window,dt,diag_bl(w),AvFq(:,:,:,w),AvFq2(:,:,:,w))
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
@@ -862,6 +932,7 @@ contains
         call write_profile('rho_vpi.out',Nbin,rcut/2.d0,ndensav,AvDradAll,AvDrad2All)
         call write_profile('pr_vpi.out',Nbin,rcut/2.d0,ndensav,AvDpairAll,AvDpair2All)
      end if
+     if (fq_tau) call write_fqt('fqt_vpi.out',ep,fq_ntau,fq_window,dt,nfqav,AvFqAll,AvFq2All)
   end if
 
   do w=1,NW

@@ -1,4 +1,7 @@
-"""Normalisation of the trapped-system profiles that PigsContext.density_read returns (pigs_density_*).
+"""Normalisation of the accumulators that PigsContext.density_read (trapped systems, pigs_density_*) and
+PigsContext.fqt_read (periodic systems, pigs_fqt_*) return.
+
+Trapped-system profiles:
 
 With S = the samples of a walker and V_d(r) = unit_ball(d) * r**d (the reference's ball volume,
 pigs_estimators.f90 unit_ball):
@@ -6,6 +9,11 @@ pigs_estimators.f90 unit_ball):
   radial  c_j / (S * (V_d((j+1)*br) - V_d(j*br)))            br = h/Nbin, grid [0, h)
   pair    c_j / (S * Np * (V_d((j+1)*br) - V_d(j*br)))
 With every particle inside the grid the planar and radial profiles integrate to Np and the pair distribution to Np-1.
+
+Imaginary-time density correlations (normalize_fqt): raw[l][iq][k] holds, per sample, the n_pairs(l) = 2*window + 1 - l
+products C(a)C(a+l) + S(a)S(a+l) of the window slices, so
+  F(q, tau_l) = raw / (S * n_pairs(l) * Np),   q = iq * (2*pi/Lbox[k]) for iq = 1..Nk,   tau_l = l*dt
+and F(q, 0) is S(q) averaged over the window.
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -50,3 +58,21 @@ def normalize_profiles(counts, dim, Np, Nbin, half_width):
     x = -half_width + (np.arange(Nbin) + 0.5) * b
     r = (np.arange(Nbin) + 0.5) * br
     return {"planar": planar, "radial": radial, "pair": pair, "x": x, "r": r}
+
+
+def normalize_fqt(raw, Np, window, dt, Lbox):
+    """raw: the dict of fqt_read (F [W, Ntau+1, Nk, dim] raw sums, samples [W]) or one walker's slice of it.
+    Returns (F, q, tau): F of the same shape as raw["F"], q [Nk, dim] (column k: iq * 2*pi/Lbox[k], iq = 1..Nk) and
+    tau [Ntau+1] = l*dt.  A walker without samples gives NaN."""
+    A = np.asarray(raw["F"], dtype=np.float64)
+    S = np.asarray(raw["samples"], dtype=np.float64)
+    nl, Nk, dim = A.shape[-3:]
+    l = np.arange(nl, dtype=np.float64)
+    n_pairs = 2.0 * window + 1.0 - l
+    if nl > 2 * window + 1:
+        raise ValueError("more lags than the window holds")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        F = A / (S.reshape(S.shape + (1, 1, 1)) * n_pairs[:, None, None] * float(Np))
+    L = np.asarray(Lbox, dtype=np.float64)[:dim]
+    q = np.arange(1, Nk + 1, dtype=np.float64)[:, None] * (2.0 * np.pi / L)[None, :]
+    return F, q, l * dt
