@@ -322,6 +322,41 @@ int pigs_fqt_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context. */
 int pigs_fqt_read(pigs_ctx *ctx, double *F, int64_t *samples, const int32_t *reset);
 
+/* ---- vector structure factor S(q) of a PERIODIC system on the full reciprocal grid (new: the reference's S(k) and
+ * pigs_fqt_* live on the axis grid q = iq 2 pi / L along the box axes only, which reaches neither the (1,1,1)-type
+ * Bragg vectors of a solid nor the |q| shells between the axis harmonics) ------------------------------------------------
+ * The vectors are the integer ones n = (n_1 .. n_dim) with |n_k| <= nmax of the half space: the first non-zero component
+ * is positive, so n = 0 is left out and q, -q are counted once.  For each
+ *   q_k = real(n_k) * (2 pi / Lbox(k)),     Nq = ((2 nmax + 1)^dim - 1) / 2  vectors.
+ * ENUMERATION ORDER: ascending lexicographic order of (n_1, .., n_dim), n_1 slowest.  With S = 2 nmax + 1 vector iqv
+ * (0-based) is the one whose rank sum_k (n_k + nmax) S^(dim-k) among ALL S^dim vectors is iqv + Nq + 1 (the half space
+ * is exactly what follows n = 0).  3D, nmax = 1: (0,0,1), (0,1,-1), (0,1,0), (0,1,1), (1,-1,-1), ..., (1,1,1).
+ * pigs_sqv_vectors hands the list out; no caller needs to restate it.  In 1D the grid is the axis grid n = 1..nmax.
+ * The slices used are the window Nb-window .. Nb+window (0 <= window <= Nb), as for F(q,tau).  Per walker and
+ * accumulate call the device adds
+ *   acc[walker][iqv] += sum over a = Nb-window .. Nb+window (ascending) of C(a)^2 + S(a)^2
+ *   C(a) = sum_i cos(q . x_i(a)),  S(a) = sum_i sin(q . x_i(a))
+ * and 1 to samples[walker], so the estimator is
+ *   S(q) = acc / (samples * (2 window + 1) * Np)                     (the caller's division; profiles.normalize_sqv)
+ * exp(i q.x) is formed as the product of per-axis phasors exp(i real(m) (2 pi/Lbox(k)) x_k), m = |n_k|, each from one
+ * sincos of the phase rounded as pigs_structure_batch rounds it.  The sums are taken in fixed orders without
+ * floating-point atomics: the same worldline gives the same bits whatever the walker list, the launch split or the
+ * context.  The window must stay inside the converged part of the path; the library does not judge it.
+ *
+ * pigs_sqv_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context,
+ * PIGS_ERR_ARG for nmax < 1, nmax > 16 in 3D, nmax > 64 in 1D or 2D, window < 0 or window > Nb. */
+int pigs_sqv_init(pigs_ctx *ctx, int32_t nmax, int32_t window);
+/* Nq, and the vectors n[Nq][dim] in the enumeration order above.  PIGS_ERR_ARG before pigs_sqv_init. */
+int pigs_sqv_count(pigs_ctx *ctx, int64_t *Nq);
+int pigs_sqv_vectors(pigs_ctx *ctx, int32_t *n);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * PIGS_ERR_ARG before pigs_sqv_init or for a walker out of range. */
+int pigs_sqv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' raw sums S[n_walkers][Nq] and samples[n_walkers]; then zeroes those of the walkers w with
+ * reset[w] != 0 (reset == NULL: none).  Synchronises the context. */
+int pigs_sqv_read(pigs_ctx *ctx, double *S, int64_t *samples, const int32_t *reset);
+
 /* ---- multi-GPU: block-estimator reduction (new) ------------------------ */
 /* RCCL communicator over `nranks` contexts.  Single-process form (one host thread per
  * GPU, the Fortran host: pigs_vpi's &gpu n_gpus = G): pigs_comm_init_all.  Multi-process form: rank 0 obtains an id

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "pigs_diagonal_estimators", "pigs_diagonal_estimators_begin", "pigs_diagonal_estimators_end",
     "pigs_density_init", "pigs_density_accumulate", "pigs_density_read",
     "pigs_fqt_init", "pigs_fqt_accumulate", "pigs_fqt_read",
+    "pigs_sqv_init", "pigs_sqv_count", "pigs_sqv_vectors", "pigs_sqv_accumulate", "pigs_sqv_read",
 ]
 
 
@@ -130,6 +131,11 @@ def load_library(path=LIB_PATH):
     L.pigs_fqt_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
     L.pigs_fqt_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_fqt_read.argtypes = [vp, _dp, _lp, _ip]
+    L.pigs_sqv_init.argtypes = [vp, C.c_int32, C.c_int32]
+    L.pigs_sqv_count.argtypes = [vp, _lp]
+    L.pigs_sqv_vectors.argtypes = [vp, _ip]
+    L.pigs_sqv_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_sqv_read.argtypes = [vp, _dp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -484,6 +490,51 @@ class PigsContext:
             mask = _i(keep)
         _chk(self.L, self.L.pigs_fqt_read(self.h, _d(out["F"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
              "pigs_fqt_read")
+        return out
+
+    # ---- vector structure factor on the full reciprocal grid (pigs_sqv_*: raw sums per walker and vector)
+    def sqv_init(self, nmax, window=0):
+        """Allocate and zero the sums of S(q) over the slices Nb-window..Nb+window for the integer vectors |n_k| <= nmax
+        of the half space (sqv_vectors lists them).  Calling it again resizes and zeroes."""
+        _chk(self.L, self.L.pigs_sqv_init(self.h, int(nmax), int(window)), "pigs_sqv_init")
+        nq = C.c_int64(0)
+        _chk(self.L, self.L.pigs_sqv_count(self.h, C.byref(nq)), "pigs_sqv_count")
+        self._sqv_nq = int(nq.value)
+
+    def sqv_vectors(self):
+        """The stored vectors n [Nq, dim] (int32) in the library's enumeration order."""
+        nq = getattr(self, "_sqv_nq", None)
+        if nq is None:
+            raise PigsError("sqv_vectors: sqv_init first")
+        n = np.zeros((nq, self.cfg.dim), np.int32)
+        _chk(self.L, self.L.pigs_sqv_vectors(self.h, _i(n)), "pigs_sqv_vectors")
+        return n
+
+    def sqv_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        if walkers is None:
+            _chk(self.L, self.L.pigs_sqv_accumulate(self.h, self.n_walkers, None), "pigs_sqv_accumulate")
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, self.L.pigs_sqv_accumulate(self.h, wl.size, _i(wl)), "pigs_sqv_accumulate")
+
+    def sqv_read(self, reset=None):
+        """dict: S, the raw sums [W, Nq] (profiles.normalize_sqv divides them), and samples [W] (int64).
+        reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        nq = getattr(self, "_sqv_nq", None)
+        if nq is None:
+            raise PigsError("sqv_read: sqv_init first")
+        W = self.n_walkers
+        out = {"S": np.zeros((W, nq)), "samples": np.zeros(W, np.int64)}
+        if reset is None or reset is False:
+            mask = None
+        else:
+            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
+            if keep.size != W:
+                raise ValueError("reset mask needs one entry per walker")
+            mask = _i(keep)
+        _chk(self.L, self.L.pigs_sqv_read(self.h, _d(out["S"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
+             "pigs_sqv_read")
         return out
 
     # ---- K5

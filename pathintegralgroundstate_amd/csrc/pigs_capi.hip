@@ -206,6 +206,15 @@ struct pigs_ctx {
     int         fqt_ntau = 0, fqt_window = 0, fqt_slots = 0;
     std::vector<int64_t> fqt_mark;          // per walker: the last launch (fqt_launch) that listed it
     int64_t     fqt_launch = 0;
+    // vector structure factor on the full reciprocal grid (pigs_sqv_*): raw sums [walker][iqv], the samples per walker,
+    // and the C^2 + S^2 scratch of one launch's window slices ([sqv_slots][2 window + 1][Nq])
+    DevBuf<double> d_sqv_acc, d_sqv_rho2;
+    DevBuf<unsigned long long> d_sqv_samples;
+    int         sqv_nmax = 0;               // 0: pigs_sqv_init not called yet
+    int         sqv_window = 0, sqv_slots = 0;
+    int64_t     sqv_nq = 0;
+    std::vector<int64_t> sqv_mark;          // per walker: the last launch (sqv_launch) that listed it
+    int64_t     sqv_launch = 0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -1457,6 +1466,115 @@ int pigs_fqt_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset
             while (e < W && reset[e]) ++e;
             HIPCHK(hipMemsetAsync(c->d_fqt_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
             HIPCHK(hipMemsetAsync(c->d_fqt_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
+            w = e;
+        }
+    }
+    SYNC_CHECKED(c);
+    return PIGS_OK;
+}
+
+// ---- vector structure factor S(q) on the full reciprocal grid of a periodic system ----------------
+// Raw sums per walker and vector (pigs_sqv.hip), accumulated on the device and read per block.
+constexpr size_t kSqvScratchMax = (size_t)256 << 20;      // bytes of slice scratch behind one launch
+
+int pigs_sqv_init(pigs_ctx *c, int32_t nmax, int32_t window)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the vector S(q) is defined for periodic systems only (the q grid is the box's)");
+    if (nmax < 1 || nmax > (c->P.dim == 3 ? 16 : 64) || window < 0 || window > c->P.Nb)
+        return fail(PIGS_ERR_ARG, "pigs_sqv_init: nmax=%d (1..%d in %dD) window=%d (0..Nb=%d)", nmax, c->P.dim == 3 ? 16 : 64,
+                    c->P.dim, window, c->P.Nb);
+    const SqvShape sh = sqv_shape(c->P.dim, nmax);
+    const size_t W = (size_t)c->n_walkers, per = (size_t)sh.Nq, slice = (size_t)(2 * window + 1) * per;
+    // as many walkers per launch as the list holds and the scratch cap allows, one at the least
+    const int slots = (int)std::max<size_t>(1, std::min<size_t>(std::min(c->n_walkers, kSqvListMax),
+                                                                kSqvScratchMax / (slice * sizeof(double))));
+    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
+    c->sqv_nmax = 0;
+    HIPCHK(c->d_sqv_acc.alloc(W * per));
+    HIPCHK(c->d_sqv_samples.alloc(W));
+    HIPCHK(c->d_sqv_rho2.alloc((size_t)slots * slice));
+    HIPCHK(hipMemsetAsync(c->d_sqv_acc.p, 0, W * per * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_sqv_samples.p, 0, W * sizeof(unsigned long long), c->stream));
+    SYNC_CHECKED(c);
+    c->sqv_nmax = nmax;
+    c->sqv_window = window;
+    c->sqv_slots = slots;
+    c->sqv_nq = sh.Nq;
+    return PIGS_OK;
+}
+
+int pigs_sqv_count(pigs_ctx *c, int64_t *Nq)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
+    if (!Nq) return fail(PIGS_ERR_ARG, "null output");
+    *Nq = c->sqv_nq;
+    return PIGS_OK;
+}
+
+int pigs_sqv_vectors(pigs_ctx *c, int32_t *n)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
+    if (!n) return fail(PIGS_ERR_ARG, "null output");
+    // vector iqv has rank iqv + Nq + 1 among all (2 nmax + 1)^dim vectors, n_1 slowest (include/pigs_hip.h)
+    const int dim = c->P.dim, nmax = c->sqv_nmax, S = 2 * nmax + 1;
+    for (int64_t iqv = 0; iqv < c->sqv_nq; ++iqv) {
+        int64_t r = iqv + c->sqv_nq + 1;
+        for (int k = dim - 1; k >= 0; --k) {
+            n[iqv * dim + k] = (int32_t)(r % S) - nmax;
+            r /= S;
+        }
+    }
+    return PIGS_OK;
+}
+
+int pigs_sqv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // As pigs_fqt_accumulate: the list goes by value in the kernel arguments, and a launch ends where the scratch is
+    // full or a walker would appear in it a second time; the stream orders the launches.
+    if (walkers) c->sqv_mark.resize(c->n_walkers, 0);
+    for (int i0 = 0; i0 < n;) {
+        const int64_t launch = ++c->sqv_launch;
+        SqvList L{};
+        int m = 0;
+        while (i0 + m < n && m < c->sqv_slots && !(walkers && c->sqv_mark[sw[i0 + m]] == launch)) {
+            if (walkers) c->sqv_mark[sw[i0 + m]] = launch;
+            L.w[m] = sw[i0 + m];
+            ++m;
+        }
+        HIPCHK(launch_sqv(c->P, c->d_paths.p, m, L, c->sqv_window, c->sqv_nmax, c->d_sqv_rho2.p, c->d_sqv_acc.p,
+                          c->d_sqv_samples.p, c->stream));
+        i0 += m;
+    }
+    return PIGS_OK;
+}
+
+int pigs_sqv_read(pigs_ctx *c, double *S, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
+    if (!S || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t W = (size_t)c->n_walkers, per = (size_t)c->sqv_nq;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(S, c->d_sqv_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(samples, c->d_sqv_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (reset) {
+        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
+        for (size_t w = 0; w < W;) {
+            if (!reset[w]) { ++w; continue; }
+            size_t e = w;
+            while (e < W && reset[e]) ++e;
+            HIPCHK(hipMemsetAsync(c->d_sqv_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
+            HIPCHK(hipMemsetAsync(c->d_sqv_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
             w = e;
         }
     }

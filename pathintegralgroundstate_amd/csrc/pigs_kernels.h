@@ -69,6 +69,22 @@ struct FqtList { int32_t w[kFqtListMax]; };
 hipError_t launch_fqt(const DevParams &P, const double *paths, int n, const FqtList &list, int window, int Ntau, int Nk,
                       double *rho, double *acc, unsigned long long *samples, hipStream_t st);
 
+// pigs_sqv.hip: the vector structure factor on the full reciprocal grid (pigs_sqv_accumulate).  Stage 1 writes
+// C^2 + S^2 of every stored vector for the window slices Nb-window .. Nb+window of the n listed walkers to rho2
+// ([slot][slice][iqv] doubles), stage 2 adds their sum over the slices (ascending) to acc ([walker][iqv]) and 1 to samples.
+// One thread owns an accumulator element per launch: the caller never lists a walker twice in ONE launch.  The list
+// travels in the kernel arguments, at most kSqvListMax walkers per launch.  sqv_shape gives the sizes that follow from
+// (dim, nmax) alone: Nq vectors, the prefixes and chunks of the work items, the particle tile and its LDS bytes.
+constexpr int kSqvListMax = 256;
+constexpr int kSqvChunk = 8;                     // values of |n_dim| per work item: 4 * 8 running sums in registers
+constexpr int kSqvThreadsMax = 512;
+constexpr size_t kSqvLdsBudget = 40 * 1024;      // phasor table of one particle tile: several workgroups share a CU
+struct SqvList { int32_t w[kSqvListMax]; };
+struct SqvShape { long long Nq; int nprefix, nchunk, tile, threads; size_t lds; };
+SqvShape sqv_shape(int dim, int nmax);
+hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const SqvList &list, int window, int nmax,
+                      double *rho2, double *acc, unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

@@ -443,6 +443,46 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_fqt_read_t
+
+     ! vector structure factor on the full reciprocal grid (include/pigs_hip.h, pigs_sqv_*): looked up at run time, see
+     ! sqv_bind
+     function pigs_sqv_init_t(ctx,nmax,window) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value        :: ctx
+       integer(c_int32_t), value :: nmax,window
+       integer(c_int) :: rc
+     end function pigs_sqv_init_t
+
+     function pigs_sqv_count_t(ctx,Nq) bind(C) result(rc)
+       import :: c_int, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t) :: Nq
+       integer(c_int) :: rc
+     end function pigs_sqv_count_t
+
+     function pigs_sqv_vectors_t(ctx,n) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int32_t) :: n(*)                      ! the stored vectors (dim,Nq)
+       integer(c_int) :: rc
+     end function pigs_sqv_vectors_t
+
+     function pigs_sqv_accumulate_t(ctx,n,walkers) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int32_t), value      :: n
+       integer(c_int32_t), intent(in) :: walkers(*)
+       integer(c_int) :: rc
+     end function pigs_sqv_accumulate_t
+
+     function pigs_sqv_read_t(ctx,S,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: S(*)          ! raw sums (Nq,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_sqv_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -454,6 +494,13 @@ module pigs_capi
   procedure(pigs_fqt_init_t), pointer       :: fqt_init => null()
   procedure(pigs_fqt_accumulate_t), pointer :: fqt_accumulate => null()
   procedure(pigs_fqt_read_t), pointer       :: fqt_read => null()
+
+  ! bound by sqv_bind (null until then)
+  procedure(pigs_sqv_init_t), pointer       :: sqv_init => null()
+  procedure(pigs_sqv_count_t), pointer      :: sqv_count => null()
+  procedure(pigs_sqv_vectors_t), pointer    :: sqv_vectors => null()
+  procedure(pigs_sqv_accumulate_t), pointer :: sqv_accumulate => null()
+  procedure(pigs_sqv_read_t), pointer       :: sqv_read => null()
 
 contains
 
@@ -500,6 +547,27 @@ contains
     call c_f_procpointer(f(2),fqt_accumulate)
     call c_f_procpointer(f(3),fqt_read)
   end function fqt_bind
+
+  ! The vector-S(q) entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function sqv_bind()
+    type(c_funptr) :: f(5)
+    integer :: i
+    f(1) = c_dlsym(c_null_ptr,'pigs_sqv_init'//c_null_char)
+    f(2) = c_dlsym(c_null_ptr,'pigs_sqv_count'//c_null_char)
+    f(3) = c_dlsym(c_null_ptr,'pigs_sqv_vectors'//c_null_char)
+    f(4) = c_dlsym(c_null_ptr,'pigs_sqv_accumulate'//c_null_char)
+    f(5) = c_dlsym(c_null_ptr,'pigs_sqv_read'//c_null_char)
+    sqv_bind = .true.
+    do i=1,5
+       sqv_bind = sqv_bind .and. c_associated(f(i))
+    end do
+    if (.not. sqv_bind) return
+    call c_f_procpointer(f(1),sqv_init)
+    call c_f_procpointer(f(2),sqv_count)
+    call c_f_procpointer(f(3),sqv_vectors)
+    call c_f_procpointer(f(4),sqv_accumulate)
+    call c_f_procpointer(f(5),sqv_read)
+  end function sqv_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

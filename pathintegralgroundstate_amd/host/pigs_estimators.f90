@@ -13,6 +13,7 @@ module pigs_estimators
   public :: write_radial, write_sk, write_nr
   public :: normalize_density, write_density, write_profile
   public :: normalize_fqt, write_fqt
+  public :: normalize_sqv, sqv_shells, sqv_shell_means, write_sqvec, write_sqshell
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -263,6 +264,134 @@ contains
     end do
     close (u)
   end subroutine write_fqt
+
+  ! ---- vector structure factor on the full reciprocal grid (raw sums of pigs_sqv_read: window slices
+  ! Nb-window..Nb+window) -> one walker's S(q) of one block with S samples: raw/(S (2 window + 1) Np)
+  subroutine normalize_sqv(Np,window,S,Nq,raw,Sq)
+    integer, intent(in)    :: Np,window,Nq
+    integer(8), intent(in) :: S
+    real(8), intent(in)    :: raw(Nq)
+    real(8), intent(out)   :: Sq(Nq)
+    Sq = raw/(real(S,8)*real(2*window+1,8)*real(Np,8))
+  end subroutine normalize_sqv
+
+  ! The |q| shells of the stored vectors nv(dim,Nq): shell(iqv) = 1..nsh in ascending |q|, qsh the modulus (root of the
+  ! shell's mean |q|^2) and mult the multiplicity counting +q and -q.  With all box lengths bitwise equal the shell key
+  ! is the integer sum of n_k^2; otherwise vectors whose |q|^2 agree to 1e-12 relative share a shell.
+  subroutine sqv_shells(p,Nq,nv,shell,nsh,qsh,mult)
+    type(est_params), intent(in) :: p
+    integer, intent(in)  :: Nq
+    integer(4), intent(in) :: nv(p%dim,Nq)
+    integer, intent(out) :: shell(Nq),nsh
+    real(8), allocatable, intent(out) :: qsh(:)
+    integer, allocatable, intent(out) :: mult(:)
+    real(8) :: key(Nq),q2(Nq),qs(Nq)
+    integer :: idx(Nq),tmp(Nq),cnt(Nq),i,k
+    logical :: cubic
+    cubic = .true.
+    do k=2,p%dim
+       cubic = cubic .and. p%Lbox(k)==p%Lbox(1)
+    end do
+    do i=1,Nq
+       q2(i) = 0.d0; key(i) = 0.d0
+       do k=1,p%dim
+          q2(i)  = q2(i)+(real(nv(k,i),8)*p%qbin(k))**2
+          key(i) = key(i)+real(nv(k,i),8)**2
+       end do
+       if (.not. cubic) key(i) = q2(i)
+       idx(i) = i
+    end do
+    call msort(1,Nq)
+    nsh = 0; cnt = 0; qs = 0.d0
+    do i=1,Nq
+       if (i==1) then
+          nsh = 1
+       else if (key(idx(i))-key(idx(i-1))>1.d-12*key(idx(i))) then
+          nsh = nsh+1
+       end if
+       shell(idx(i)) = nsh
+       cnt(nsh) = cnt(nsh)+1
+       qs(nsh)  = qs(nsh)+q2(idx(i))
+    end do
+    allocate (qsh(nsh),mult(nsh))
+    qsh  = sqrt(qs(1:nsh)/cnt(1:nsh))
+    mult = 2*cnt(1:nsh)
+  contains
+    ! stable merge sort of idx(lo:hi) by key
+    recursive subroutine msort(lo,hi)
+      integer, intent(in) :: lo,hi
+      integer :: mid,a,b,c
+      if (hi<=lo) return
+      mid = (lo+hi)/2
+      call msort(lo,mid); call msort(mid+1,hi)
+      a = lo; b = mid+1
+      do c=lo,hi
+         if (b>hi) then
+            tmp(c) = idx(a); a = a+1
+         else if (a>mid) then
+            tmp(c) = idx(b); b = b+1
+         else if (key(idx(b))<key(idx(a))) then
+            tmp(c) = idx(b); b = b+1
+         else
+            tmp(c) = idx(a); a = a+1
+         end if
+      end do
+      idx(lo:hi) = tmp(lo:hi)
+    end subroutine msort
+  end subroutine sqv_shells
+
+  ! mean of Sq over the stored vectors of every shell
+  subroutine sqv_shell_means(Nq,shell,nsh,mult,Sq,Ssh)
+    integer, intent(in)  :: Nq,nsh,shell(Nq),mult(nsh)
+    real(8), intent(in)  :: Sq(Nq)
+    real(8), intent(out) :: Ssh(nsh)
+    integer :: i
+    Ssh = 0.d0
+    do i=1,Nq
+       Ssh(shell(i)) = Ssh(shell(i))+Sq(i)
+    end do
+    Ssh = Ssh/(0.5d0*real(mult,8))
+  end subroutine sqv_shell_means
+
+  ! sqvec_vpi.out: one line per stored vector: n_1..n_dim, |q|, S(q), error over the n blocks
+  subroutine write_sqvec(fname,p,Nq,nv,n,av,av2)
+    character(len=*), intent(in) :: fname
+    type(est_params), intent(in) :: p
+    integer, intent(in)    :: Nq,n
+    integer(4), intent(in) :: nv(p%dim,Nq)
+    real(8), intent(inout) :: av(Nq),av2(Nq)
+    integer :: i,k,u
+    real(8) :: q2
+    character(len=24) :: fmt
+    write (fmt,'(a,i0,a)') '(',p%dim,'i6,3g20.10e3)'
+    open (newunit=u,file=fname)
+    do i=1,Nq
+       av(i)  = av(i)/real(n)
+       av2(i) = av2(i)/real(n)
+       q2 = 0.d0
+       do k=1,p%dim
+          q2 = q2+(real(nv(k,i),8)*p%qbin(k))**2
+       end do
+       write (u,fmt) (nv(k,i),k=1,p%dim),sqrt(q2),av(i),variance(n,av(i),av2(i))
+    end do
+    close (u)
+  end subroutine write_sqvec
+
+  ! sq_vpi.out: one line per |q| shell: |q|, S, error over the n blocks, multiplicity (+q and -q)
+  subroutine write_sqshell(fname,nsh,qsh,mult,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: nsh,mult(nsh),n
+    real(8), intent(in)    :: qsh(nsh)
+    real(8), intent(inout) :: av(nsh),av2(nsh)
+    integer :: i,u
+    open (newunit=u,file=fname)
+    do i=1,nsh
+       av(i)  = av(i)/real(n)
+       av2(i) = av2(i)/real(n)
+       write (u,'(3g20.10e3,i8)') qsh(i),av(i),variance(n,av(i),av2(i)),mult(i)
+    end do
+    close (u)
+  end subroutine write_sqshell
 
   ! the reference's "variance": standard error sqrt((<x^2>-<x>^2)/n)
   function variance(n,av,av2) result(v)

@@ -18,6 +18,9 @@
 ! on the S(k) grid for the lags l = 0..fq_ntau (tau_l = l dt) between the slices Nb-fq_window..Nb+fq_window, accumulated
 ! on the GPU -- fqt_vpi.out; fq_window defaults to ceiling(fq_ntau/2) and must stay inside the part of the path where
 ! the projection has converged: that is the user's choice, the program does not judge it)
+! (sq_vector = T, periodic systems only: the structure factor S(q) on the full reciprocal grid, all integer vectors
+! |n_k| <= sq_nmax (default 8) of the half space, averaged over the slices Nb-sq_window..Nb+sq_window (default 0),
+! accumulated on the GPU -- sqvec_vpi.out, one line per vector, and sq_vpi.out, one line per |q| shell)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -50,6 +53,8 @@ program pigs_vpi
   integer           :: Nobdm,Npw,Nmax,n_walkers,device,ios,k1_variant,n_gpus
   logical           :: device_sampler,checkpointing,same_device,density_profile,fq_tau
   integer           :: fq_ntau,fq_window
+  logical           :: sq_vector
+  integer           :: sq_nmax,sq_window
   logical           :: sampler_auto
   integer(c_int)    :: rc_probe
   type(pigs_sweep_params) :: probe_par
@@ -62,7 +67,7 @@ program pigs_vpi
   namelist /extpot/  a_ho
   namelist /jastrow/ Rm
   namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device,density_profile, &
-       &             fq_tau,fq_ntau,fq_window
+       &             fq_tau,fq_ntau,fq_window,sq_vector,sq_nmax,sq_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -86,6 +91,7 @@ program pigs_vpi
   n_walkers = 1; device = 0; device_sampler = .false.; potential = 'aziz2'; checkpointing = .true.; k1_variant = 0
   n_gpus = 1; same_device = .false.; density_profile = .false.
   fq_tau = .false.; fq_ntau = 0; fq_window = -1
+  sq_vector = .false.; sq_nmax = 8; sq_window = 0
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -141,6 +147,27 @@ program pigs_vpi
      if (.not. fqt_bind()) then
         write (0,'(a)') ' pigs_vpi: fq_tau = T: this backend does not export pigs_fqt_init / _accumulate / _read'// &
              & ' (F(q,tau) runs on libpigs_hip.so only)'
+        stop 2
+     end if
+  end if
+  if (sq_vector) then
+     ! structure factor on the full reciprocal grid of a periodic system; entry points resolved at run time as above
+     if (trap) then
+        write (0,'(a)') ' pigs_vpi: sq_vector = T needs a periodic system (trap = F): its q grid is that of the box'
+        stop 2
+     end if
+     if (sq_nmax<1 .or. sq_nmax>merge(16,64,dim==3)) then
+        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: sq_vector = T: sq_nmax = ',sq_nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
+             & ' (dim = ',dim,')'
+        stop 2
+     end if
+     if (sq_window<0 .or. sq_window>Nb) then
+        write (0,'(a,i0,a,i0)') ' pigs_vpi: sq_vector = T: sq_window = ',sq_window,' must lie in 0 .. Nb = ',Nb
+        stop 2
+     end if
+     if (.not. sqv_bind()) then
+        write (0,'(a)') ' pigs_vpi: sq_vector = T: this backend does not export pigs_sqv_init / _count / _vectors /'// &
+             & ' _accumulate / _read (the vector S(q) runs on libpigs_hip.so only)'
         stop 2
      end if
   end if
@@ -253,6 +280,11 @@ program pigs_vpi
      print '(a,i0,a,i0,a,i0,a)', '  > F(q,tau)            : on (lags 0..',fq_ntau,', slices Nb-',fq_window,'..Nb+',fq_window,': fqt_vpi.out)'
   end if
 
+  if (sq_vector) then
+     print '(a,i0,a,i0,a,i0,a)', '  > Vector S(q)         : on (|n_k| <= ',sq_nmax,', slices Nb-',sq_window,'..Nb+',sq_window, &
+          & ': sqvec_vpi.out, sq_vpi.out)'
+  end if
+
   !=====================================================================
 
   !$omp parallel num_threads(G) default(shared)
@@ -347,6 +379,16 @@ contains
   integer(c_int64_t), allocatable :: fq_smp(:)
   integer(c_int32_t), allocatable :: fq_reset(:)
   real(8), allocatable :: fq_raw(:,:,:,:),fqb(:,:,:),AvFq(:,:,:,:),AvFq2(:,:,:,:),AvFqAll(:,:,:),AvFq2All(:,:,:),tmpf(:,:,:)
+  ! vector S(q) (sq_vector = T): the stored vectors and their |q| shells, the block's raw sums from the device, the
+  ! normalised block values per vector and per shell, their per-walker sums and the walker-averaged sums; nsv doubles of
+  ! the block vector behind the F(q,tau) ones (0 with the key off)
+  integer :: nsq,nsv,nsqav,nsqall,nsh
+  integer(c_int64_t) :: sq_count
+  integer(c_int32_t), allocatable :: sq_n(:,:),sq_reset(:)
+  integer(c_int64_t), allocatable :: sq_smp(:)
+  integer, allocatable :: sq_shell(:),sq_mult(:)
+  real(8), allocatable :: sq_raw(:,:),sqb(:),shb(:),sq_q(:),AvSq(:,:),AvSq2(:,:),AvSh(:,:),AvSh2(:,:)
+  real(8), allocatable :: AvSqAll(:),AvSq2All(:),AvShAll(:),AvSh2All(:)
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -459,6 +501,20 @@ contains
      call pigs_check(fqt_init(ctx,int(Nk,c_int32_t),int(fq_ntau,c_int32_t),int(fq_window,c_int32_t)),'pigs_fqt_init')
   end if
 
+  nsq = 0; nsv = 0; nsqav = 0
+  if (sq_vector) then
+     call pigs_check(sqv_init(ctx,int(sq_nmax,c_int32_t),int(sq_window,c_int32_t)),'pigs_sqv_init')
+     call pigs_check(sqv_count(ctx,sq_count),'pigs_sqv_count')
+     nsq = int(sq_count)
+     nsv = nsq+1
+     allocate (sq_n(dim,nsq),sq_shell(nsq),sq_raw(nsq,NW),sq_smp(NW),sq_reset(NW),sqb(nsq))
+     call pigs_check(sqv_vectors(ctx,sq_n),'pigs_sqv_vectors')
+     call sqv_shells(ep,nsq,sq_n,sq_shell,nsh,sq_q,sq_mult)
+     allocate (shb(nsh),AvSq(nsq,NW),AvSq2(nsq,NW),AvSh(nsh,NW),AvSh2(nsh,NW),AvSqAll(nsq),AvSq2All(nsq),AvShAll(nsh),AvSh2All(nsh))
+     AvSq = 0.d0; AvSq2 = 0.d0; AvSh = 0.d0; AvSh2 = 0.d0; AvSqAll = 0.d0; AvSq2All = 0.d0; AvShAll = 0.d0; AvSh2All = 0.d0
+     sq_reset = 1
+  end if
+
   allocate (perm(NW))
   do w=1,NW
      allocate (perm(w)%members(Np),perm(w)%histogram(Np))
@@ -495,7 +551,7 @@ contains
   ! the vector that meets the other shards' once per block: number of walkers with a diagonal block, their summed block
   ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
   nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
-  allocate (vec(nvec+ndv+nfv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
+  allocate (vec(nvec+ndv+nfv+nsv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
   allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
   AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
   ngrav = 0; nnrav = 0
@@ -707,6 +763,8 @@ contains
            if (density_profile) call pigs_check(dens_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_density_accumulate')
            ! and, at the same place, their window slices into the F(q,tau) sums
            if (fq_tau) call pigs_check(fqt_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqt_accumulate')
+           ! and into the sums of the vector S(q)
+           if (sq_vector) call pigs_check(sqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sqv_accumulate')
         end if
 
      end do   ! istep
@@ -733,6 +791,7 @@ contains
      end if
      if (density_profile) call pigs_check(dens_read(ctx,dc_pl,dc_rad,dc_pair,dc_smp,dc_reset),'pigs_density_read')
      if (fq_tau) call pigs_check(fqt_read(ctx,fq_raw,fq_smp,fq_reset),'pigs_fqt_read')
+     if (sq_vector) call pigs_check(sqv_read(ctx,sq_raw,sq_smp,sq_reset),'pigs_sqv_read')
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -767,6 +826,14 @@ contains
               vec(nvec+ndv+1:nvec+ndv+nfq) = vec(nvec+ndv+1:nvec+ndv+nfq)+reshape(fqb,[nfq])
               vec(nvec+ndv+nfv) = vec(nvec+ndv+nfv)+1.d0
            end if
+           if (sq_vector) then
+              call normalize_sqv(Np,sq_window,int(sq_smp(w),8),nsq,sq_raw(:,w),sqb)
+              call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sqb,shb)
+              AvSq(:,w) = AvSq(:,w)+sqb; AvSq2(:,w) = AvSq2(:,w)+sqb*sqb
+              AvSh(:,w) = AvSh(:,w)+shb; AvSh2(:,w) = AvSh2(:,w)+shb*shb
+              vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq) = vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq)+sqb
+              vec(nvec+ndv+nfv+nsv) = vec(nvec+ndv+nfv+nsv)+1.d0
+           end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
            write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -790,7 +857,7 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv+nsv,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
      ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
      if (ish==1 .and. NWtot>1) then
@@ -826,6 +893,16 @@ contains
               nfqav = nfqav+1
               tmpf = reshape(vec(nvec+ndv+1:nvec+ndv+nfq),[dim,Nk,fq_ntau+1])/nfqall
               AvFqAll = AvFqAll+tmpf; AvFq2All = AvFq2All+tmpf*tmpf
+           end if
+        end if
+        if (sq_vector) then                  ! walker average of the block's vector S(q) and of its shell means
+           nsqall = nint(vec(nvec+ndv+nfv+nsv))
+           if (nsqall>0) then
+              nsqav = nsqav+1
+              sqb = vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq)/nsqall
+              call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sqb,shb)
+              AvSqAll = AvSqAll+sqb; AvSq2All = AvSq2All+sqb*sqb
+              AvShAll = AvShAll+shb; AvSh2All = AvSh2All+shb*shb
            end if
         end if
      end if
@@ -919,6 +996,10 @@ contains
         call write_profile('pr_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),AvDpair(:,w),AvDpair2(:,w))
      end if
      if (fq_tau) call write_fqt('fqt_vpi'//trim(suffix)//'.out',ep,fq_ntau,fq_window,dt,diag_bl(w),AvFq(:,:,:,w),AvFq2(:,:,:,w))
+     if (sq_vector) then
+        call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',ep,nsq,sq_n,diag_bl(w),AvSq(:,w),AvSq2(:,w))
+        call write_sqshell('sq_vpi'//trim(suffix)//'.out',nsh,sq_q,sq_mult,diag_bl(w),AvSh(:,w),AvSh2(:,w))
+     end if
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
@@ -933,6 +1014,10 @@ contains
         call write_profile('pr_vpi.out',Nbin,rcut/2.d0,ndensav,AvDpairAll,AvDpair2All)
      end if
      if (fq_tau) call write_fqt('fqt_vpi.out',ep,fq_ntau,fq_window,dt,nfqav,AvFqAll,AvFq2All)
+     if (sq_vector) then
+        call write_sqvec('sqvec_vpi.out',ep,nsq,sq_n,nsqav,AvSqAll,AvSq2All)
+        call write_sqshell('sq_vpi.out',nsh,sq_q,sq_mult,nsqav,AvShAll,AvSh2All)
+     end if
   end if
 
   do w=1,NW

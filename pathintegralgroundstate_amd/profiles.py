@@ -1,5 +1,5 @@
-"""Normalisation of the accumulators that PigsContext.density_read (trapped systems, pigs_density_*) and
-PigsContext.fqt_read (periodic systems, pigs_fqt_*) return.
+"""Normalisation of the accumulators that PigsContext.density_read (trapped systems, pigs_density_*),
+PigsContext.fqt_read and PigsContext.sqv_read (periodic systems, pigs_fqt_*, pigs_sqv_*) return.
 
 Trapped-system profiles:
 
@@ -14,6 +14,11 @@ Imaginary-time density correlations (normalize_fqt): raw[l][iq][k] holds, per sa
 products C(a)C(a+l) + S(a)S(a+l) of the window slices, so
   F(q, tau_l) = raw / (S * n_pairs(l) * Np),   q = iq * (2*pi/Lbox[k]) for iq = 1..Nk,   tau_l = l*dt
 and F(q, 0) is S(q) averaged over the window.
+
+Vector structure factor (normalize_sqv, shell_average): raw[iqv] holds, per sample, the 2*window + 1 values C^2 + S^2 of
+the window slices at the integer vector n[iqv] (q_k = n_k * 2*pi/Lbox[k]; half space, so q stands for -q too):
+  S(q) = raw / (S * (2*window + 1) * Np)
+and the vectors of equal |q| form a shell over which S(q) of an isotropic system is averaged.
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -76,3 +81,40 @@ def normalize_fqt(raw, Np, window, dt, Lbox):
     L = np.asarray(Lbox, dtype=np.float64)[:dim]
     q = np.arange(1, Nk + 1, dtype=np.float64)[:, None] * (2.0 * np.pi / L)[None, :]
     return F, q, l * dt
+
+
+def normalize_sqv(raw, samples, Np, window):
+    """raw: the sums of sqv_read ([W, Nq] or one walker's [Nq]), samples: [W] or a scalar.  Returns S(q) of the same
+    shape as raw: raw / (samples * (2*window + 1) * Np).  A walker without samples gives NaN."""
+    A = np.asarray(raw, dtype=np.float64)
+    S = np.asarray(samples, dtype=np.float64)
+    if S.ndim > 0:
+        S = S.reshape(S.shape + (1,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return A / (S * (2.0 * window + 1.0) * float(Np))
+
+
+def shell_average(n, Lbox, Sq):
+    """n: the stored vectors [Nq, dim] (sqv_vectors), Lbox: the box lengths, Sq: [..., Nq].
+    Returns (q, mean, mult): per shell, in ascending |q|, the modulus, the mean of Sq over the shell's stored vectors
+    (shape [..., n_shells]) and the multiplicity counting both +q and -q (twice the stored vectors of the shell).
+    With all box lengths bitwise equal the shell key is the integer sum of n_k^2; otherwise vectors whose |q|^2 agree
+    to 1e-12 relative share a shell."""
+    n = np.asarray(n, dtype=np.int64)
+    Sq = np.asarray(Sq, dtype=np.float64)
+    dim = n.shape[1]
+    L = np.asarray(Lbox, dtype=np.float64)[:dim]
+    qb = 2.0 * np.pi / L
+    q2 = ((n * qb[None, :]) ** 2).sum(axis=1)
+    if np.all(L == L[0]):
+        key = (n * n).sum(axis=1)
+        order = np.argsort(key, kind="stable")
+        start = np.flatnonzero(np.r_[True, np.diff(key[order]) != 0])
+    else:
+        order = np.argsort(q2, kind="stable")
+        s = q2[order]
+        start = np.flatnonzero(np.r_[True, np.diff(s) > 1e-12 * s[1:]])
+    cnt = np.diff(np.r_[start, n.shape[0]])
+    q = np.sqrt(np.add.reduceat(q2[order], start) / cnt)
+    mean = np.add.reduceat(Sq[..., order], start, axis=-1) / cnt
+    return q, mean, 2 * cnt
