@@ -357,6 +357,48 @@ int pigs_sqv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * reset[w] != 0 (reset == NULL: none).  Synchronises the context. */
 int pigs_sqv_read(pigs_ctx *ctx, double *S, int64_t *samples, const int32_t *reset);
 
+/* ---- pair distribution of a PERIODIC system on the vector grid, over a slice window (new: the only g(r) of a periodic
+ * system was pigs_structure_batch's radial histogram of one slice; this is the real-space partner of pigs_sqv_*) --------
+ * Two integer histograms per walker, accumulated on the device: g(r) on the Cartesian grid of the minimum-image cell and
+ * the radial one with the reference's PairCorrelation rule.
+ * For every listed walker, every slice a = Nb-window..Nb+window, and every pair i < j (0-based particle index):
+ * - Displacement.  Take d_k = x_k(i) - x_k(j).  Fold it once as pbc_mod.f90:40-41 does (min_image<DIM>: the two compares,
+ *   each against LboxHalf).  Let r2 be the sum of the squares, left to right, with no fused multiply-adds.
+ * - Vector histogram.
+ *   - The bin width is b_k = Lbox[k] / (double)Nbin.
+ *   - The bin coordinate is t_k = (d_k + LboxHalf[k]) / b_k.
+ *   - The pair counts +1 in the bin with flat index j_1 + Nbin*j_2 + Nbin^2*j_3 (x fastest, as `planar` of
+ *     pigs_density_*), where j_k = (int)t_k.
+ *   - It counts if and only if 0 <= t_k < Nbin holds in double for every k.  Otherwise it is dropped.
+ *   - The decision is taken before any conversion to an integer.  NaN, +-Inf, and a difference that one fold leaves
+ *     outside the cell are dropped without undefined behaviour.
+ *   - Only the ordered pair i < j is counted.  The partner -d is the host's business (profiles.normalize_grv
+ *     symmetrises by index reflection).
+ * - Radial histogram.  If r2 <= rcut2, take u = sqrt(r2)/rbin.  If u < Nr, the pair counts +1 in bin (int)u.  This is
+ *   pigs_structure_batch's rule, so 2*radial equals its `gr` summed over the window slices.
+ * - Samples.  samples[w] counts calls, not slices, as pigs_sqv_* does.
+ * Accumulators: 64-bit integers per walker; vec is [n_walkers][Nbin^dim], radial is [n_walkers][Nr], samples is
+ * [n_walkers].  The estimators are
+ *   g(r_vec) = (vec[j] + vec[reflected j]) / (samples (2 window + 1) Np density prod_k b_k)    (1 - 1/Np for an ideal gas)
+ *   g(r)     = 2 radial / (samples (2 window + 1) Np density shell volume)                      (the reference's NormAvGr)
+ * Counts are integer atomics (LDS u32, flushed before they could wrap, and global u64): the result depends on neither
+ * the walker list, the launch split nor the context.  The vector grid is privatised in LDS where it fits and the
+ * automatic choice takes it (tuning key "grv_form": -1 automatic, 0 global atomics, 1 LDS; a forced LDS form whose grid
+ * does not fit returns PIGS_ERR_ARG at the next accumulate).
+ *
+ * pigs_grv_init allocates and zeroes the counts (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context;
+ * PIGS_ERR_ARG for Nbin < 1, Nbin > 4096 in 1D, > 1024 in 2D, > 128 in 3D, Nr < 1, !(rbin > 0) or rbin not finite,
+ * window < 0 or window > Nb, or accumulators larger than 2 GiB in total. */
+int pigs_grv_init(pigs_ctx *ctx, int32_t Nbin, int32_t Nr, double rbin, int32_t window);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_grv_init or for a walker out of range. */
+int pigs_grv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' counts vec[n_walkers][Nbin^dim], radial[n_walkers][Nr] and samples[n_walkers]; then zeroes those of the
+ * walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_grv_init. */
+int pigs_grv_read(pigs_ctx *ctx, int64_t *vec, int64_t *radial, int64_t *samples, const int32_t *reset);
+
 /* ---- multi-GPU: block-estimator reduction (new) ------------------------ */
 /* RCCL communicator over `nranks` contexts.  Single-process form (one host thread per
  * GPU, the Fortran host: pigs_vpi's &gpu n_gpus = G): pigs_comm_init_all.  Multi-process form: rank 0 obtains an id

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "pigs_density_init", "pigs_density_accumulate", "pigs_density_read",
     "pigs_fqt_init", "pigs_fqt_accumulate", "pigs_fqt_read",
     "pigs_sqv_init", "pigs_sqv_count", "pigs_sqv_vectors", "pigs_sqv_accumulate", "pigs_sqv_read",
+    "pigs_grv_init", "pigs_grv_accumulate", "pigs_grv_read",
 ]
 
 
@@ -136,6 +137,9 @@ def load_library(path=LIB_PATH):
     L.pigs_sqv_vectors.argtypes = [vp, _ip]
     L.pigs_sqv_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_sqv_read.argtypes = [vp, _dp, _lp, _ip]
+    L.pigs_grv_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32]
+    L.pigs_grv_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_grv_read.argtypes = [vp, _lp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -535,6 +539,47 @@ class PigsContext:
             mask = _i(keep)
         _chk(self.L, self.L.pigs_sqv_read(self.h, _d(out["S"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
              "pigs_sqv_read")
+        return out
+
+    # ---- pair distribution on the vector grid over a slice window (pigs_grv_*: 64-bit counts per walker)
+    def grv_init(self, Nbin, window=0, Nr=None, rbin=None):
+        """Allocate and zero the counts of g(r) over the slices Nb-window..Nb+window: Nbin bins per axis over the
+        minimum-image cell, and Nr radial bins of width rbin (defaults: the context's Nbin and rcut / float32(Nbin), as
+        sampler_init computes it).  Calling it again resizes and zeroes."""
+        c = self.cfg
+        nr = c.Nbin if Nr is None else int(Nr)
+        rb = c.rcut / float(np.float32(nr)) if rbin is None else float(rbin)
+        _chk(self.L, self.L.pigs_grv_init(self.h, int(Nbin), nr, rb, int(window)), "pigs_grv_init")
+        self._grv_shape = (int(Nbin), nr)
+
+    def grv_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        if walkers is None:
+            _chk(self.L, self.L.pigs_grv_accumulate(self.h, self.n_walkers, None), "pigs_grv_accumulate")
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, self.L.pigs_grv_accumulate(self.h, wl.size, _i(wl)), "pigs_grv_accumulate")
+
+    def grv_read(self, reset=None):
+        """dict of int64 arrays: vec [W, Nbin, ..(dim times)] (x on the last axis), radial [W, Nr], samples [W]
+        (profiles.normalize_grv turns them into g).  reset: None, True (all walkers) or a per-walker mask of walkers
+        whose counts are zeroed after the copy."""
+        shp = getattr(self, "_grv_shape", None)
+        if shp is None:
+            raise PigsError("grv_read: grv_init first")
+        W = self.n_walkers
+        out = {"vec": np.zeros((W,) + (shp[0],) * self.cfg.dim, np.int64), "radial": np.zeros((W, shp[1]), np.int64),
+               "samples": np.zeros(W, np.int64)}
+        if reset is None or reset is False:
+            mask = None
+        else:
+            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
+            if keep.size != W:
+                raise ValueError("reset mask needs one entry per walker")
+            mask = _i(keep)
+        lp = C.POINTER(C.c_int64)
+        _chk(self.L, self.L.pigs_grv_read(self.h, *(out[k].ctypes.data_as(lp) for k in ("vec", "radial", "samples")), mask),
+             "pigs_grv_read")
         return out
 
     # ---- K5

@@ -215,6 +215,13 @@ struct pigs_ctx {
     int64_t     sqv_nq = 0;
     std::vector<int64_t> sqv_mark;          // per walker: the last launch (sqv_launch) that listed it
     int64_t     sqv_launch = 0;
+    // pair distribution on the vector grid over a slice window (pigs_grv_*): per-walker 64-bit counts, walker-major
+    DevBuf<unsigned long long> d_grv_vec, d_grv_radial, d_grv_samples;
+    int         grv_nbin = 0;               // 0: pigs_grv_init not called yet
+    int         grv_nr = 0, grv_window = 0;
+    int         grv_form = -1;              // tuning key "grv_form": -1 automatic, 0 global atomics, 1 grid privatised in LDS
+    size_t      grv_nvec = 0;               // vector bins per walker: Nbin^dim
+    double      grv_rbin = 0.0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -426,6 +433,11 @@ int pigs_set_tuning(pigs_ctx *c, const char *key, int32_t value)
     }
     if (!strcmp(key, "cm_exclusive")) {         // 1: other contexts of this process on the device are idle while this one samples
         c->cm_exclusive = value != 0;           // (bench.py's extra legs next to its main context): cooperating workgroups allowed
+        return PIGS_OK;
+    }
+    if (!strcmp(key, "grv_form")) {             // vector grid of pigs_grv_accumulate: -1 automatic, 0 global atomics, 1 privatised in LDS
+        if (value < -1 || value > 1) return fail(PIGS_ERR_ARG, "grv_form=%d", value);
+        c->grv_form = value;
         return PIGS_OK;
     }
     if (!strcmp(key, "sweep_threads")) {
@@ -1575,6 +1587,90 @@ int pigs_sqv_read(pigs_ctx *c, double *S, int64_t *samples, const int32_t *reset
             while (e < W && reset[e]) ++e;
             HIPCHK(hipMemsetAsync(c->d_sqv_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
             HIPCHK(hipMemsetAsync(c->d_sqv_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
+            w = e;
+        }
+    }
+    SYNC_CHECKED(c);
+    return PIGS_OK;
+}
+
+// ---- pair distribution of a periodic system on the vector grid, over a slice window ---------------
+// Integer counts per walker (pigs_grv.hip), accumulated on the device and read per block.
+int pigs_grv_init(pigs_ctx *c, int32_t Nbin, int32_t Nr, double rbin, int32_t window)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the vector g(r) is defined for periodic systems only (its grid is the box's)");
+    const int nbmax = c->P.dim == 3 ? 128 : c->P.dim == 2 ? 1024 : 4096;
+    if (Nbin < 1 || Nbin > nbmax || Nr < 1 || !(rbin > 0.0) || !std::isfinite(rbin) || window < 0 || window > c->P.Nb)
+        return fail(PIGS_ERR_ARG, "pigs_grv_init: Nbin=%d (1..%d in %dD) Nr=%d rbin=%g window=%d (0..Nb=%d)", Nbin, nbmax,
+                    c->P.dim, Nr, rbin, window, c->P.Nb);
+    size_t nv = 1;
+    for (int k = 0; k < c->P.dim; ++k) nv *= (size_t)Nbin;
+    const size_t W = (size_t)c->n_walkers, u = sizeof(unsigned long long);
+    const double bytes = (double)W * ((double)nv + (double)Nr + 1.0) * (double)u;
+    if (bytes > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_grv_init: %zu walkers x (%zu + %d + 1) counters pass 2 GiB", W, nv, Nr);
+    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
+    c->grv_nbin = 0;
+    HIPCHK(c->d_grv_vec.alloc(W * nv));
+    HIPCHK(c->d_grv_radial.alloc(W * Nr));
+    HIPCHK(c->d_grv_samples.alloc(W));
+    HIPCHK(hipMemsetAsync(c->d_grv_vec.p, 0, W * nv * u, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_grv_radial.p, 0, W * Nr * u, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_grv_samples.p, 0, W * u, c->stream));
+    SYNC_CHECKED(c);
+    c->grv_nbin = Nbin;
+    c->grv_nr = Nr;
+    c->grv_window = window;
+    c->grv_nvec = nv;
+    c->grv_rbin = rbin;
+    return PIGS_OK;
+}
+
+int pigs_grv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->grv_nbin) return fail(PIGS_ERR_ARG, "pigs_grv_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // the list goes by value in the kernel arguments: queued on the context's stream, nothing to wait for.  The counts
+    // are integer atomics, so a walker may appear twice in one launch.
+    for (int i0 = 0; i0 < n; i0 += kGrvListMax) {
+        const int m = std::min(kGrvListMax, n - i0);
+        const GrvShape sh = grv_shape(c->P.dim, c->P.Np, c->grv_nbin, c->grv_nr, c->grv_window, c->grv_form, m, c->n_cu);
+        if (sh.vec_lds && !sh.vec_fits)
+            return fail(PIGS_ERR_ARG, "pigs_grv_accumulate: grv_form = 1, but a grid of %zu bins does not fit the LDS", c->grv_nvec);
+        GrvList L{};
+        for (int i = 0; i < m; ++i) L.w[i] = sw[i0 + i];
+        HIPCHK(launch_grv(c->P, c->d_paths.p, m, L, sh, c->grv_window, c->grv_nbin, c->grv_nr, c->grv_rbin, c->d_grv_vec.p,
+                          c->d_grv_radial.p, c->d_grv_samples.p, c->stream));
+    }
+    return PIGS_OK;
+}
+
+int pigs_grv_read(pigs_ctx *c, int64_t *vec, int64_t *radial, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->grv_nbin) return fail(PIGS_ERR_ARG, "pigs_grv_init first");
+    if (!vec || !radial || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t W = (size_t)c->n_walkers, nv = c->grv_nvec, nr = (size_t)c->grv_nr;
+    const size_t u = sizeof(unsigned long long);
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(vec, c->d_grv_vec.p, W * nv * u, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(radial, c->d_grv_radial.p, W * nr * u, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(samples, c->d_grv_samples.p, W * u, hipMemcpyDeviceToHost, s));
+    if (reset) {
+        // zero the accumulators of the flagged walkers, one memset per array and run of consecutive walkers
+        for (size_t w = 0; w < W;) {
+            if (!reset[w]) { ++w; continue; }
+            size_t e = w;
+            while (e < W && reset[e]) ++e;
+            HIPCHK(hipMemsetAsync(c->d_grv_vec.p + w * nv, 0, (e - w) * nv * u, s));
+            HIPCHK(hipMemsetAsync(c->d_grv_radial.p + w * nr, 0, (e - w) * nr * u, s));
+            HIPCHK(hipMemsetAsync(c->d_grv_samples.p + w, 0, (e - w) * u, s));
             w = e;
         }
     }

@@ -85,6 +85,25 @@ SqvShape sqv_shape(int dim, int nmax);
 hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const SqvList &list, int window, int nmax,
                       double *rho2, double *acc, unsigned long long *samples, hipStream_t st);
 
+// pigs_grv.hip: the pair distribution of a periodic system on the vector grid and radially, over the window slices
+// Nb-window .. Nb+window (pigs_grv_accumulate): 64-bit counts per walker, vec [walker][Nbin^dim] (x fastest) and radial
+// [walker][Nr].  The list travels in the kernel arguments, at most kGrvListMax walkers per launch; a walker may be listed
+// twice in one launch (integer atomics).  grv_shape decides the form: the vector grid privatised in LDS (form 1, or
+// automatic up to kGrvAutoLdsBins bins where it fits kGrvLdsBudget next to the staging tiles and the radial histogram) with
+// nchunk runs of slices per walker, or global atomics with one workgroup per (walker, slice); vec_lds && !vec_fits is
+// a forced LDS form that does not fit, which the caller refuses.
+constexpr int kGrvListMax = 256;
+constexpr int kGrvTile = 256;                    // particles of a slice staged per tile
+constexpr int kGrvThreadsMax = 1024;
+constexpr size_t kGrvLdsBudget = 160 * 1024;     // LDS of one CU on gfx950
+constexpr long long kGrvAutoLdsBins = 1ll << 15; // automatic form: LDS up to 32^3 bins (measured)
+struct GrvList { int32_t w[kGrvListMax]; };
+struct GrvShape { int vec_lds, vec_fits, rad_lds, nchunk, threads, flush_every; size_t lds; };
+GrvShape grv_shape(int dim, int Np, int Nbin, int Nr, int window, int form, int n_list, int n_cu);
+hipError_t launch_grv(const DevParams &P, const double *paths, int n, const GrvList &list, const GrvShape &s, int window,
+                      int Nbin, int Nr, double rbin, unsigned long long *vec, unsigned long long *radial,
+                      unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

@@ -483,6 +483,35 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_sqv_read_t
+
+     ! pair distribution on the vector grid over a slice window (include/pigs_hip.h, pigs_grv_*): looked up at run time,
+     ! see grv_bind
+     function pigs_grv_init_t(ctx,Nbin,Nr,rbin,window) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value        :: ctx
+       integer(c_int32_t), value :: Nbin,Nr
+       real(c_double), value     :: rbin
+       integer(c_int32_t), value :: window
+       integer(c_int) :: rc
+     end function pigs_grv_init_t
+
+     function pigs_grv_accumulate_t(ctx,n,walkers) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int32_t), value      :: n
+       integer(c_int32_t), intent(in) :: walkers(*)
+       integer(c_int) :: rc
+     end function pigs_grv_accumulate_t
+
+     function pigs_grv_read_t(ctx,vec,radial,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int64_t)             :: vec(*)        ! counts (Nbin**dim,n_walkers), x fastest
+       integer(c_int64_t)             :: radial(*)     ! counts (Nr,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its counts after the copy
+       integer(c_int) :: rc
+     end function pigs_grv_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -501,6 +530,11 @@ module pigs_capi
   procedure(pigs_sqv_vectors_t), pointer    :: sqv_vectors => null()
   procedure(pigs_sqv_accumulate_t), pointer :: sqv_accumulate => null()
   procedure(pigs_sqv_read_t), pointer       :: sqv_read => null()
+
+  ! bound by grv_bind (null until then)
+  procedure(pigs_grv_init_t), pointer       :: grv_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: grv_accumulate => null()
+  procedure(pigs_grv_read_t), pointer       :: grv_read => null()
 
 contains
 
@@ -568,6 +602,23 @@ contains
     call c_f_procpointer(f(4),sqv_accumulate)
     call c_f_procpointer(f(5),sqv_read)
   end function sqv_bind
+
+  ! The vector-g(r) entry points, found like the vector-S(q) ones: at run time, only when a run asks for them.
+  logical function grv_bind()
+    type(c_funptr) :: f(3)
+    integer :: i
+    f(1) = c_dlsym(c_null_ptr,'pigs_grv_init'//c_null_char)
+    f(2) = c_dlsym(c_null_ptr,'pigs_grv_accumulate'//c_null_char)
+    f(3) = c_dlsym(c_null_ptr,'pigs_grv_read'//c_null_char)
+    grv_bind = .true.
+    do i=1,3
+       grv_bind = grv_bind .and. c_associated(f(i))
+    end do
+    if (.not. grv_bind) return
+    call c_f_procpointer(f(1),grv_init)
+    call c_f_procpointer(f(2),grv_accumulate)
+    call c_f_procpointer(f(3),grv_read)
+  end function grv_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -14,6 +14,7 @@ module pigs_estimators
   public :: normalize_density, write_density, write_profile
   public :: normalize_fqt, write_fqt
   public :: normalize_sqv, sqv_shells, sqv_shell_means, write_sqvec, write_sqshell
+  public :: normalize_grv, write_grvec
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -392,6 +393,54 @@ contains
     end do
     close (u)
   end subroutine write_sqshell
+
+  ! ---- pair distribution on the vector grid over a slice window (counts of pigs_grv_read: window slices
+  ! Nb-window..Nb+window, Ng bins per axis over the minimum-image cell, nv = Ng**dim, x fastest; radial counts on the run's
+  ! own Nbin/rbin grid) -> one walker's block values with S samples.  The device counts the ordered pair i < j only: the
+  ! partner -d is the reflected bin nv+1-j, and g = (c(j) + c(nv+1-j))/(S (2 window + 1) Np density prod_k b_k), which is
+  ! 1 - 1/Np for an ideal gas.  The radial part is the reference's g(r): 2 per pair through normalize_gr with
+  ! S (2 window + 1) slices, so at window 0 it is gr_vpi.out's.
+  subroutine normalize_grv(p,density,window,S,Ng,nv,cvec,crad,gvec,grw)
+    type(est_params), intent(in) :: p
+    real(8), intent(in)    :: density
+    integer, intent(in)    :: window,Ng,nv
+    integer(8), intent(in) :: S,cvec(nv),crad(p%Nbin)
+    real(8), intent(out)   :: gvec(nv),grw(p%Nbin)
+    real(8) :: cell
+    integer :: j,k
+    cell = 1.d0
+    do k=1,p%dim
+       cell = cell*(p%Lbox(k)/real(Ng,8))
+    end do
+    do j=1,nv
+       gvec(j) = real(cvec(j)+cvec(nv+1-j),8)/(real(S,8)*real(2*window+1,8)*real(p%Np,8)*density*cell)
+    end do
+    grw = 2.d0*real(crad,8)
+    call normalize_gr(p,density,int(S)*(2*window+1),grw)
+  end subroutine normalize_grv
+
+  ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
+  subroutine write_grvec(fname,p,Ng,nv,n,av,av2)
+    character(len=*), intent(in) :: fname
+    type(est_params), intent(in) :: p
+    integer, intent(in)    :: Ng,nv,n
+    real(8), intent(inout) :: av(nv),av2(nv)
+    integer :: j,k,u,rest
+    real(8) :: r(3),b
+    open (newunit=u,file=fname)
+    do j=1,nv
+       av(j)  = av(j)/real(n)
+       av2(j) = av2(j)/real(n)
+       rest = j-1
+       do k=1,p%dim
+          b    = p%Lbox(k)/real(Ng,8)
+          r(k) = -0.5d0*p%Lbox(k)+(real(mod(rest,Ng),8)+0.5d0)*b
+          rest = rest/Ng
+       end do
+       write (u,'(20g20.10e3)') (r(k),k=1,p%dim),av(j),variance(n,av(j),av2(j))
+    end do
+    close (u)
+  end subroutine write_grvec
 
   ! the reference's "variance": standard error sqrt((<x^2>-<x>^2)/n)
   function variance(n,av,av2) result(v)

@@ -21,6 +21,10 @@
 ! (sq_vector = T, periodic systems only: the structure factor S(q) on the full reciprocal grid, all integer vectors
 ! |n_k| <= sq_nmax (default 8) of the half space, averaged over the slices Nb-sq_window..Nb+sq_window (default 0),
 ! accumulated on the GPU -- sqvec_vpi.out, one line per vector, and sq_vpi.out, one line per |q| shell)
+! (gr_vector = T, periodic systems only: the pair distribution g(r) on the Cartesian grid of the minimum-image cell,
+! gr_nbin bins per axis (default 32), and radially on the run's own Nbin/rbin grid, both averaged over the slices
+! Nb-gr_window..Nb+gr_window (default 0), accumulated on the GPU -- grvec_vpi.out, one line per bin, and grw_vpi.out in
+! gr_vpi.out's format)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -55,6 +59,8 @@ program pigs_vpi
   integer           :: fq_ntau,fq_window
   logical           :: sq_vector
   integer           :: sq_nmax,sq_window
+  logical           :: gr_vector
+  integer           :: gr_nbin,gr_window
   logical           :: sampler_auto
   integer(c_int)    :: rc_probe
   type(pigs_sweep_params) :: probe_par
@@ -67,7 +73,8 @@ program pigs_vpi
   namelist /extpot/  a_ho
   namelist /jastrow/ Rm
   namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device,density_profile, &
-       &             fq_tau,fq_ntau,fq_window,sq_vector,sq_nmax,sq_window
+       &             fq_tau,fq_ntau,fq_window,sq_vector,sq_nmax,sq_window, &
+       &             gr_vector,gr_nbin,gr_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -92,6 +99,7 @@ program pigs_vpi
   n_gpus = 1; same_device = .false.; density_profile = .false.
   fq_tau = .false.; fq_ntau = 0; fq_window = -1
   sq_vector = .false.; sq_nmax = 8; sq_window = 0
+  gr_vector = .false.; gr_nbin = 32; gr_window = 0
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -168,6 +176,27 @@ program pigs_vpi
      if (.not. sqv_bind()) then
         write (0,'(a)') ' pigs_vpi: sq_vector = T: this backend does not export pigs_sqv_init / _count / _vectors /'// &
              & ' _accumulate / _read (the vector S(q) runs on libpigs_hip.so only)'
+        stop 2
+     end if
+  end if
+  if (gr_vector) then
+     ! pair distribution on the vector grid of a periodic system; entry points resolved at run time as above
+     if (trap) then
+        write (0,'(a)') ' pigs_vpi: gr_vector = T needs a periodic system (trap = F): its grid is the minimum-image cell of the box'
+        stop 2
+     end if
+     if (gr_nbin<1 .or. gr_nbin>merge(128,merge(1024,4096,dim==2),dim==3)) then
+        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: gr_vector = T: gr_nbin = ',gr_nbin,' must lie in 1 .. ', &
+             & merge(128,merge(1024,4096,dim==2),dim==3),' (dim = ',dim,')'
+        stop 2
+     end if
+     if (gr_window<0 .or. gr_window>Nb) then
+        write (0,'(a,i0,a,i0)') ' pigs_vpi: gr_vector = T: gr_window = ',gr_window,' must lie in 0 .. Nb = ',Nb
+        stop 2
+     end if
+     if (.not. grv_bind()) then
+        write (0,'(a)') ' pigs_vpi: gr_vector = T: this backend does not export pigs_grv_init / _accumulate / _read'// &
+             & ' (the vector g(r) runs on libpigs_hip.so only)'
         stop 2
      end if
   end if
@@ -285,6 +314,11 @@ program pigs_vpi
           & ': sqvec_vpi.out, sq_vpi.out)'
   end if
 
+  if (gr_vector) then
+     print '(a,i0,a,i0,a,i0,a)', '  > Vector g(r)         : on (',gr_nbin,' bins per axis, slices Nb-',gr_window,'..Nb+',gr_window, &
+          & ': grvec_vpi.out, grw_vpi.out)'
+  end if
+
   !=====================================================================
 
   !$omp parallel num_threads(G) default(shared)
@@ -389,6 +423,13 @@ contains
   integer, allocatable :: sq_shell(:),sq_mult(:)
   real(8), allocatable :: sq_raw(:,:),sqb(:),shb(:),sq_q(:),AvSq(:,:),AvSq2(:,:),AvSh(:,:),AvSh2(:,:)
   real(8), allocatable :: AvSqAll(:),AvSq2All(:),AvShAll(:),AvSh2All(:)
+  ! vector g(r) (gr_vector = T): the block's counts from the device, the normalised block values on the vector grid and
+  ! radially, their per-walker sums and the walker-averaged sums; ngv doubles of the block vector behind the vector-S(q)
+  ! ones (0 with the key off)
+  integer :: ngb,ngv,ngvav,ngvall
+  integer(c_int64_t), allocatable :: gv_vec(:,:),gv_rad(:,:),gv_smp(:)
+  integer(c_int32_t), allocatable :: gv_reset(:)
+  real(8), allocatable :: gvb(:),gwb(:),AvGv(:,:),AvGv2(:,:),AvGw(:,:),AvGw2(:,:),AvGvAll(:),AvGv2All(:),AvGwAll(:),AvGw2All(:)
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -515,6 +556,18 @@ contains
      sq_reset = 1
   end if
 
+  ngb = 0; ngv = 0; ngvav = 0
+  if (gr_vector) then
+     call pigs_check(grv_init(ctx,int(gr_nbin,c_int32_t),int(Nbin,c_int32_t),real(rbin,c_double),int(gr_window,c_int32_t)), &
+          & 'pigs_grv_init')
+     ngb = gr_nbin**dim
+     ngv = ngb+Nbin+1
+     allocate (gv_vec(ngb,NW),gv_rad(Nbin,NW),gv_smp(NW),gv_reset(NW),gvb(ngb),gwb(Nbin))
+     allocate (AvGv(ngb,NW),AvGv2(ngb,NW),AvGw(Nbin,NW),AvGw2(Nbin,NW),AvGvAll(ngb),AvGv2All(ngb),AvGwAll(Nbin),AvGw2All(Nbin))
+     AvGv = 0.d0; AvGv2 = 0.d0; AvGw = 0.d0; AvGw2 = 0.d0; AvGvAll = 0.d0; AvGv2All = 0.d0; AvGwAll = 0.d0; AvGw2All = 0.d0
+     gv_reset = 1
+  end if
+
   allocate (perm(NW))
   do w=1,NW
      allocate (perm(w)%members(Np),perm(w)%histogram(Np))
@@ -551,7 +604,7 @@ contains
   ! the vector that meets the other shards' once per block: number of walkers with a diagonal block, their summed block
   ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
   nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
-  allocate (vec(nvec+ndv+nfv+nsv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
+  allocate (vec(nvec+ndv+nfv+nsv+ngv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
   allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
   AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
   ngrav = 0; nnrav = 0
@@ -765,6 +818,8 @@ contains
            if (fq_tau) call pigs_check(fqt_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqt_accumulate')
            ! and into the sums of the vector S(q)
            if (sq_vector) call pigs_check(sqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sqv_accumulate')
+           ! and into the counts of the vector g(r)
+           if (gr_vector) call pigs_check(grv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_grv_accumulate')
         end if
 
      end do   ! istep
@@ -792,6 +847,7 @@ contains
      if (density_profile) call pigs_check(dens_read(ctx,dc_pl,dc_rad,dc_pair,dc_smp,dc_reset),'pigs_density_read')
      if (fq_tau) call pigs_check(fqt_read(ctx,fq_raw,fq_smp,fq_reset),'pigs_fqt_read')
      if (sq_vector) call pigs_check(sqv_read(ctx,sq_raw,sq_smp,sq_reset),'pigs_sqv_read')
+     if (gr_vector) call pigs_check(grv_read(ctx,gv_vec,gv_rad,gv_smp,gv_reset),'pigs_grv_read')
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -834,6 +890,14 @@ contains
               vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq) = vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq)+sqb
               vec(nvec+ndv+nfv+nsv) = vec(nvec+ndv+nfv+nsv)+1.d0
            end if
+           if (gr_vector) then
+              call normalize_grv(ep,density,gr_window,int(gv_smp(w),8),gr_nbin,ngb,gv_vec(:,w),gv_rad(:,w),gvb,gwb)
+              AvGv(:,w) = AvGv(:,w)+gvb; AvGv2(:,w) = AvGv2(:,w)+gvb*gvb
+              AvGw(:,w) = AvGw(:,w)+gwb; AvGw2(:,w) = AvGw2(:,w)+gwb*gwb
+              vec(nvec+ndv+nfv+nsv+1:nvec+ndv+nfv+nsv+ngb) = vec(nvec+ndv+nfv+nsv+1:nvec+ndv+nfv+nsv+ngb)+gvb
+              vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin) = vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin)+gwb
+              vec(nvec+ndv+nfv+nsv+ngv) = vec(nvec+ndv+nfv+nsv+ngv)+1.d0
+           end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
            write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -857,7 +921,7 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv+nsv,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv+nsv+ngv,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
      ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
      if (ish==1 .and. NWtot>1) then
@@ -903,6 +967,16 @@ contains
               call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sqb,shb)
               AvSqAll = AvSqAll+sqb; AvSq2All = AvSq2All+sqb*sqb
               AvShAll = AvShAll+shb; AvSh2All = AvSh2All+shb*shb
+           end if
+        end if
+        if (gr_vector) then                  ! walker average of the block's vector and windowed radial g(r)
+           ngvall = nint(vec(nvec+ndv+nfv+nsv+ngv))
+           if (ngvall>0) then
+              ngvav = ngvav+1
+              gvb = vec(nvec+ndv+nfv+nsv+1:nvec+ndv+nfv+nsv+ngb)/ngvall
+              gwb = vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin)/ngvall
+              AvGvAll = AvGvAll+gvb; AvGv2All = AvGv2All+gvb*gvb
+              AvGwAll = AvGwAll+gwb; AvGw2All = AvGw2All+gwb*gwb
            end if
         end if
      end if
@@ -1000,6 +1074,10 @@ contains
         call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',ep,nsq,sq_n,diag_bl(w),AvSq(:,w),AvSq2(:,w))
         call write_sqshell('sq_vpi'//trim(suffix)//'.out',nsh,sq_q,sq_mult,diag_bl(w),AvSh(:,w),AvSh2(:,w))
      end if
+     if (gr_vector) then
+        call write_grvec('grvec_vpi'//trim(suffix)//'.out',ep,gr_nbin,ngb,diag_bl(w),AvGv(:,w),AvGv2(:,w))
+        call write_radial('grw_vpi'//trim(suffix)//'.out',ep,diag_bl(w),AvGw(:,w),AvGw2(:,w))
+     end if
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
@@ -1017,6 +1095,10 @@ contains
      if (sq_vector) then
         call write_sqvec('sqvec_vpi.out',ep,nsq,sq_n,nsqav,AvSqAll,AvSq2All)
         call write_sqshell('sq_vpi.out',nsh,sq_q,sq_mult,nsqav,AvShAll,AvSh2All)
+     end if
+     if (gr_vector) then
+        call write_grvec('grvec_vpi.out',ep,gr_nbin,ngb,ngvav,AvGvAll,AvGv2All)
+        call write_radial('grw_vpi.out',ep,ngvav,AvGwAll,AvGw2All)
      end if
   end if
 

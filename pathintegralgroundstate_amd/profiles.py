@@ -1,5 +1,6 @@
 """Normalisation of the accumulators that PigsContext.density_read (trapped systems, pigs_density_*),
-PigsContext.fqt_read and PigsContext.sqv_read (periodic systems, pigs_fqt_*, pigs_sqv_*) return.
+PigsContext.fqt_read, PigsContext.sqv_read and PigsContext.grv_read (periodic systems, pigs_fqt_*, pigs_sqv_*,
+pigs_grv_*) return.
 
 Trapped-system profiles:
 
@@ -19,6 +20,14 @@ Vector structure factor (normalize_sqv, shell_average): raw[iqv] holds, per samp
 the window slices at the integer vector n[iqv] (q_k = n_k * 2*pi/Lbox[k]; half space, so q stands for -q too):
   S(q) = raw / (S * (2*window + 1) * Np)
 and the vectors of equal |q| form a shell over which S(q) of an isotropic system is averaged.
+
+Pair distribution on the vector grid (normalize_grv): vec[j] counts, per sample, the pairs i < j of the 2*window + 1
+window slices whose folded displacement x(i) - x(j) falls into bin j of the minimum-image cell (width b_k = Lbox[k]/Nbin);
+the partner -d is added by index reflection, and
+  g(r_vec) = (vec[j] + vec[Nbin-1-j on every axis]) / (S * (2*window + 1) * Np * density * prod_k b_k)
+which is 1 - 1/Np for an ideal gas.  radial[j] counts the same pairs by distance (bin width rbin, inside the cutoff):
+  g(r_j) = 2 * radial[j] / (S * (2*window + 1) * Np * density * kn * ((r_j + rbin/2)^dim - (r_j - rbin/2)^dim))
+with kn the volume of the unit ball: the reference's normalisation (sample_mod.f90, Normalize / NormAvGr).
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -118,3 +127,26 @@ def shell_average(n, Lbox, Sq):
     q = np.sqrt(np.add.reduceat(q2[order], start) / cnt)
     mean = np.add.reduceat(Sq[..., order], start, axis=-1) / cnt
     return q, mean, 2 * cnt
+
+
+def normalize_grv(counts, Np, window, density, Lbox, rbin, dim):
+    """counts: the dict of grv_read (vec [W, Nbin, ..dim times], radial [W, Nr], samples [W]) or one walker's slice of
+    it.  Returns a dict: g_vec (same shape as vec), the bin centres x (a list of dim arrays, x[k] along axis k of the
+    box; array axis -1-k), g_r (same shape as radial) and its bin centres r.  A walker without samples gives NaN."""
+    vec = np.asarray(counts["vec"], dtype=np.float64)
+    rad = np.asarray(counts["radial"], dtype=np.float64)
+    S = np.asarray(counts["samples"], dtype=np.float64)
+    Nbin, Nr = vec.shape[-1], rad.shape[-1]
+    L = np.asarray(Lbox, dtype=np.float64)[:dim]
+    b = L / float(Nbin)
+    axes = tuple(range(vec.ndim - dim, vec.ndim))
+    sym = vec + np.flip(vec, axis=axes)                              # c[j] + c[Nbin-1-j] on every axis
+    ns = 2.0 * window + 1.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g_vec = sym / (S.reshape(S.shape + (1,) * dim) * ns * float(Np) * density * float(np.prod(b)))
+        # the reference's g(r): centres (j - 1/2) rbin, ideal-gas count of the shell, 2 per pair
+        r = (np.arange(1, Nr + 1, dtype=np.float64) - 0.5) * rbin
+        nid = density * unit_ball(dim) * ((r + 0.5 * rbin) ** dim - (r - 0.5 * rbin) ** dim)
+        g_r = 2.0 * rad / (nid * (S.reshape(S.shape + (1,)) * ns * float(Np)))
+    x = [-0.5 * L[k] + (np.arange(Nbin) + 0.5) * b[k] for k in range(dim)]
+    return {"g_vec": g_vec, "x": x, "g_r": g_r, "r": r}
