@@ -357,6 +357,43 @@ int pigs_sqv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * reset[w] != 0 (reset == NULL: none).  Synchronises the context. */
 int pigs_sqv_read(pigs_ctx *ctx, double *S, int64_t *samples, const int32_t *reset);
 
+/* ---- imaginary-time density correlations F(q,tau) of a PERIODIC system on the full reciprocal grid (new: pigs_fqt_* has
+ * the lags on the axis grid only, pigs_sqv_* the full grid at equal times only; the analytic continuation to S(q,omega)
+ * wants both: every |q| shell, and 6-48 symmetry-related vectors per shell to average over) ---------------------------
+ * The vectors are exactly those of pigs_sqv_*, in its enumeration order (half space, |n_k| <= nmax, ascending
+ * lexicographic, n_1 slowest, Nq = ((2 nmax + 1)^dim - 1)/2); pigs_fqv_vectors hands the same list out.  The slices and
+ * lags are those of pigs_fqt_*: the window Nb-window .. Nb+window (0 <= window <= Nb), the lags l = 0 .. Ntau
+ * (0 <= Ntau <= 2 window).  Per listed walker and accumulate call the device adds
+ *   acc[walker][l][iqv] += sum over a = Nb-window .. Nb+window-l (ascending) of C(a) C(a+l) + S(a) S(a+l)
+ *   C(a) + i S(a) = sum_i exp(i q . x_i(a))
+ * and 1 to samples[walker].  C and S are formed exactly as pigs_sqv_* forms them (per-axis phasors from one sincos of
+ * the phase rounded as pigs_structure_batch rounds it, prefix product, fused multiply-adds over the particles in
+ * ascending order: one piece of device code serves both).  The two products and their sum are not fused; the sum over a
+ * runs left to right from 0.0 and is then added to the accumulator.  So lag 0 is bit-identical to what
+ * pigs_sqv_accumulate adds for the same nmax, window and worldline.  The estimator is
+ *   F(q; tau_l) = acc / (samples * (2 window + 1 - l) * Np)          (the caller's division; profiles.normalize_fqv)
+ * No floating-point atomics, every sum in one fixed order: the same worldline gives the same bits whatever the walker
+ * list, the launch split or the context.  The window must stay inside the converged part of the path; the library does
+ * not judge it.
+ *
+ * pigs_fqv_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context;
+ * PIGS_ERR_ARG for nmax < 1, nmax > 16 in 3D, nmax > 64 in 1D or 2D, window < 0, window > Nb, Ntau < 0, Ntau > 2 window,
+ * accumulators larger than 2 GiB in total, or a window of more than 4096 slices (one vector's slices must fit the
+ * 64 KiB of LDS the lag kernel stages them in). */
+int pigs_fqv_init(pigs_ctx *ctx, int32_t nmax, int32_t Ntau, int32_t window);
+/* Nq, and the vectors n[Nq][dim] in the enumeration order of pigs_sqv_vectors.  PIGS_ERR_ARG before pigs_fqv_init. */
+int pigs_fqv_count(pigs_ctx *ctx, int64_t *Nq);
+int pigs_fqv_vectors(pigs_ctx *ctx, int32_t *n);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch (fewer where the (C, S) scratch of a launch,
+ * 16 (2 window + 1) Nq bytes per walker, would pass 256 MiB) and more in further launches.  PIGS_ERR_ARG before
+ * pigs_fqv_init or for a walker out of range. */
+int pigs_fqv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' raw sums F[n_walkers][Ntau+1][Nq] (iqv fastest) and samples[n_walkers]; then zeroes those of the walkers
+ * w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_fqv_init. */
+int pigs_fqv_read(pigs_ctx *ctx, double *F, int64_t *samples, const int32_t *reset);
+
 /* ---- pair distribution of a PERIODIC system on the vector grid, over a slice window (new: the only g(r) of a periodic
  * system was pigs_structure_batch's radial histogram of one slice; this is the real-space partner of pigs_sqv_*) --------
  * Two integer histograms per walker, accumulated on the device: g(r) on the Cartesian grid of the minimum-image cell and

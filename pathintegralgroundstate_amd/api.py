@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "pigs_density_init", "pigs_density_accumulate", "pigs_density_read",
     "pigs_fqt_init", "pigs_fqt_accumulate", "pigs_fqt_read",
     "pigs_sqv_init", "pigs_sqv_count", "pigs_sqv_vectors", "pigs_sqv_accumulate", "pigs_sqv_read",
+    "pigs_fqv_init", "pigs_fqv_count", "pigs_fqv_vectors", "pigs_fqv_accumulate", "pigs_fqv_read",
     "pigs_grv_init", "pigs_grv_accumulate", "pigs_grv_read",
 ]
 
@@ -137,6 +138,11 @@ def load_library(path=LIB_PATH):
     L.pigs_sqv_vectors.argtypes = [vp, _ip]
     L.pigs_sqv_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_sqv_read.argtypes = [vp, _dp, _lp, _ip]
+    L.pigs_fqv_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.pigs_fqv_count.argtypes = [vp, _lp]
+    L.pigs_fqv_vectors.argtypes = [vp, _ip]
+    L.pigs_fqv_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_fqv_read.argtypes = [vp, _dp, _lp, _ip]
     L.pigs_grv_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.pigs_grv_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_grv_read.argtypes = [vp, _lp, _lp, _lp, _ip]
@@ -539,6 +545,52 @@ class PigsContext:
             mask = _i(keep)
         _chk(self.L, self.L.pigs_sqv_read(self.h, _d(out["S"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
              "pigs_sqv_read")
+        return out
+
+    # ---- F(q,tau) on the full reciprocal grid (pigs_fqv_*: raw sums per walker, lag and vector)
+    def fqv_init(self, nmax, Ntau=0, window=0):
+        """Allocate and zero the sums of F(q, tau_l), l = 0..Ntau, over the slices Nb-window..Nb+window for the vectors
+        of sqv_init(nmax) (fqv_vectors lists them).  Lag 0 is sqv's S(q), bit for bit.  Calling it again resizes and
+        zeroes."""
+        _chk(self.L, self.L.pigs_fqv_init(self.h, int(nmax), int(Ntau), int(window)), "pigs_fqv_init")
+        nq = C.c_int64(0)
+        _chk(self.L, self.L.pigs_fqv_count(self.h, C.byref(nq)), "pigs_fqv_count")
+        self._fqv_shape = (int(Ntau) + 1, int(nq.value))
+
+    def fqv_vectors(self):
+        """The stored vectors n [Nq, dim] (int32): those of sqv_vectors, in the same order."""
+        shape = getattr(self, "_fqv_shape", None)
+        if shape is None:
+            raise PigsError("fqv_vectors: fqv_init first")
+        n = np.zeros((shape[1], self.cfg.dim), np.int32)
+        _chk(self.L, self.L.pigs_fqv_vectors(self.h, _i(n)), "pigs_fqv_vectors")
+        return n
+
+    def fqv_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        if walkers is None:
+            _chk(self.L, self.L.pigs_fqv_accumulate(self.h, self.n_walkers, None), "pigs_fqv_accumulate")
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, self.L.pigs_fqv_accumulate(self.h, wl.size, _i(wl)), "pigs_fqv_accumulate")
+
+    def fqv_read(self, reset=None):
+        """dict: F, the raw sums [W, Ntau+1, Nq] (profiles.normalize_fqv divides them), and samples [W] (int64).
+        reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        shape = getattr(self, "_fqv_shape", None)
+        if shape is None:
+            raise PigsError("fqv_read: fqv_init first")
+        W = self.n_walkers
+        out = {"F": np.zeros((W,) + shape), "samples": np.zeros(W, np.int64)}
+        if reset is None or reset is False:
+            mask = None
+        else:
+            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
+            if keep.size != W:
+                raise ValueError("reset mask needs one entry per walker")
+            mask = _i(keep)
+        _chk(self.L, self.L.pigs_fqv_read(self.h, _d(out["F"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
+             "pigs_fqv_read")
         return out
 
     # ---- pair distribution on the vector grid over a slice window (pigs_grv_*: 64-bit counts per walker)

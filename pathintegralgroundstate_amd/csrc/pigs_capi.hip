@@ -215,6 +215,15 @@ struct pigs_ctx {
     int64_t     sqv_nq = 0;
     std::vector<int64_t> sqv_mark;          // per walker: the last launch (sqv_launch) that listed it
     int64_t     sqv_launch = 0;
+    // F(q,tau) on the vectors of pigs_sqv_* (pigs_fqv_*): raw sums [walker][l][iqv], the samples per walker, and the
+    // (C, S) scratch of one launch's window slices ([fqv_slots][2 window + 1][Nq][2])
+    DevBuf<double> d_fqv_acc, d_fqv_rho;
+    DevBuf<unsigned long long> d_fqv_samples;
+    int         fqv_nmax = 0;               // 0: pigs_fqv_init not called yet
+    int         fqv_ntau = 0, fqv_window = 0, fqv_slots = 0;
+    int64_t     fqv_nq = 0;
+    std::vector<int64_t> fqv_mark;          // per walker: the last launch (fqv_launch) that listed it
+    int64_t     fqv_launch = 0;
     // pair distribution on the vector grid over a slice window (pigs_grv_*): per-walker 64-bit counts, walker-major
     DevBuf<unsigned long long> d_grv_vec, d_grv_radial, d_grv_samples;
     int         grv_nbin = 0;               // 0: pigs_grv_init not called yet
@@ -1489,6 +1498,20 @@ int pigs_fqt_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset
 // Raw sums per walker and vector (pigs_sqv.hip), accumulated on the device and read per block.
 constexpr size_t kSqvScratchMax = (size_t)256 << 20;      // bytes of slice scratch behind one launch
 
+// vector iqv has rank iqv + Nq + 1 among all (2 nmax + 1)^dim vectors, n_1 slowest (include/pigs_hip.h): the one
+// enumeration of pigs_sqv_vectors and pigs_fqv_vectors
+static void sqv_enumerate(int dim, int nmax, int64_t Nq, int32_t *n)
+{
+    const int S = 2 * nmax + 1;
+    for (int64_t iqv = 0; iqv < Nq; ++iqv) {
+        int64_t r = iqv + Nq + 1;
+        for (int k = dim - 1; k >= 0; --k) {
+            n[iqv * dim + k] = (int32_t)(r % S) - nmax;
+            r /= S;
+        }
+    }
+}
+
 int pigs_sqv_init(pigs_ctx *c, int32_t nmax, int32_t window)
 {
     int rc = check_ctx(c); if (rc) return rc;
@@ -1531,15 +1554,7 @@ int pigs_sqv_vectors(pigs_ctx *c, int32_t *n)
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
     if (!n) return fail(PIGS_ERR_ARG, "null output");
-    // vector iqv has rank iqv + Nq + 1 among all (2 nmax + 1)^dim vectors, n_1 slowest (include/pigs_hip.h)
-    const int dim = c->P.dim, nmax = c->sqv_nmax, S = 2 * nmax + 1;
-    for (int64_t iqv = 0; iqv < c->sqv_nq; ++iqv) {
-        int64_t r = iqv + c->sqv_nq + 1;
-        for (int k = dim - 1; k >= 0; --k) {
-            n[iqv * dim + k] = (int32_t)(r % S) - nmax;
-            r /= S;
-        }
-    }
+    sqv_enumerate(c->P.dim, c->sqv_nmax, c->sqv_nq, n);
     return PIGS_OK;
 }
 
@@ -1587,6 +1602,112 @@ int pigs_sqv_read(pigs_ctx *c, double *S, int64_t *samples, const int32_t *reset
             while (e < W && reset[e]) ++e;
             HIPCHK(hipMemsetAsync(c->d_sqv_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
             HIPCHK(hipMemsetAsync(c->d_sqv_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
+            w = e;
+        }
+    }
+    SYNC_CHECKED(c);
+    return PIGS_OK;
+}
+
+// ---- F(q,tau) on the full reciprocal grid of a periodic system -----------------------------------
+// Raw sums per walker, lag and vector (pigs_fqv.hip): the vectors of pigs_sqv_*, the window and lags of pigs_fqt_*.
+int pigs_fqv_init(pigs_ctx *c, int32_t nmax, int32_t Ntau, int32_t window)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the vector F(q,tau) is defined for periodic systems only (the q grid is the box's)");
+    if (nmax < 1 || nmax > (c->P.dim == 3 ? 16 : 64) || window < 0 || window > c->P.Nb || Ntau < 0 || Ntau > 2 * window)
+        return fail(PIGS_ERR_ARG, "pigs_fqv_init: nmax=%d (1..%d in %dD) Ntau=%d (0..2 window) window=%d (0..Nb=%d)", nmax,
+                    c->P.dim == 3 ? 16 : 64, c->P.dim, Ntau, window, c->P.Nb);
+    if (!fqv_width(2 * window + 1))
+        return fail(PIGS_ERR_ARG, "pigs_fqv_init: %d window slices of one vector pass the %zu bytes of LDS staging", 2 * window + 1,
+                    kFqvLdsBudget);
+    const SqvShape sh = sqv_shape(c->P.dim, nmax);
+    const size_t W = (size_t)c->n_walkers, per = (size_t)(Ntau + 1) * (size_t)sh.Nq;
+    const size_t slice = (size_t)(2 * window + 1) * 2 * (size_t)sh.Nq;
+    if ((double)W * ((double)per + 1.0) * 8.0 > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_fqv_init: %zu walkers x (%d x %lld + 1) sums pass 2 GiB", W, Ntau + 1, (long long)sh.Nq);
+    // as many walkers per launch as the list holds and the scratch cap (that of pigs_sqv_*) allows, one at the least
+    const int slots = (int)std::max<size_t>(1, std::min<size_t>(std::min(c->n_walkers, kFqvListMax),
+                                                                kSqvScratchMax / (slice * sizeof(double))));
+    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
+    c->fqv_nmax = 0;
+    HIPCHK(c->d_fqv_acc.alloc(W * per));
+    HIPCHK(c->d_fqv_samples.alloc(W));
+    HIPCHK(c->d_fqv_rho.alloc((size_t)slots * slice));
+    HIPCHK(hipMemsetAsync(c->d_fqv_acc.p, 0, W * per * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_fqv_samples.p, 0, W * sizeof(unsigned long long), c->stream));
+    SYNC_CHECKED(c);
+    c->fqv_nmax = nmax;
+    c->fqv_ntau = Ntau;
+    c->fqv_window = window;
+    c->fqv_slots = slots;
+    c->fqv_nq = sh.Nq;
+    return PIGS_OK;
+}
+
+int pigs_fqv_count(pigs_ctx *c, int64_t *Nq)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->fqv_nmax) return fail(PIGS_ERR_ARG, "pigs_fqv_init first");
+    if (!Nq) return fail(PIGS_ERR_ARG, "null output");
+    *Nq = c->fqv_nq;
+    return PIGS_OK;
+}
+
+int pigs_fqv_vectors(pigs_ctx *c, int32_t *n)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->fqv_nmax) return fail(PIGS_ERR_ARG, "pigs_fqv_init first");
+    if (!n) return fail(PIGS_ERR_ARG, "null output");
+    sqv_enumerate(c->P.dim, c->fqv_nmax, c->fqv_nq, n);
+    return PIGS_OK;
+}
+
+int pigs_fqv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->fqv_nmax) return fail(PIGS_ERR_ARG, "pigs_fqv_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // As pigs_fqt_accumulate: the list goes by value in the kernel arguments, and a launch ends where the scratch is
+    // full or a walker would appear in it a second time; the stream orders the launches.
+    if (walkers) c->fqv_mark.resize(c->n_walkers, 0);
+    for (int i0 = 0; i0 < n;) {
+        const int64_t launch = ++c->fqv_launch;
+        FqvList L{};
+        int m = 0;
+        while (i0 + m < n && m < c->fqv_slots && !(walkers && c->fqv_mark[sw[i0 + m]] == launch)) {
+            if (walkers) c->fqv_mark[sw[i0 + m]] = launch;
+            L.w[m] = sw[i0 + m];
+            ++m;
+        }
+        HIPCHK(launch_fqv(c->P, c->d_paths.p, m, L, c->fqv_window, c->fqv_ntau, c->fqv_nmax, c->d_fqv_rho.p, c->d_fqv_acc.p,
+                          c->d_fqv_samples.p, c->stream));
+        i0 += m;
+    }
+    return PIGS_OK;
+}
+
+int pigs_fqv_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->fqv_nmax) return fail(PIGS_ERR_ARG, "pigs_fqv_init first");
+    if (!F || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t W = (size_t)c->n_walkers, per = (size_t)(c->fqv_ntau + 1) * (size_t)c->fqv_nq;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(F, c->d_fqv_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(samples, c->d_fqv_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (reset) {
+        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
+        for (size_t w = 0; w < W;) {
+            if (!reset[w]) { ++w; continue; }
+            size_t e = w;
+            while (e < W && reset[e]) ++e;
+            HIPCHK(hipMemsetAsync(c->d_fqv_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
+            HIPCHK(hipMemsetAsync(c->d_fqv_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
             w = e;
         }
     }

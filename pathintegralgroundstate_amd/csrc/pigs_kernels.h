@@ -85,6 +85,21 @@ SqvShape sqv_shape(int dim, int nmax);
 hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const SqvList &list, int window, int nmax,
                       double *rho2, double *acc, unsigned long long *samples, hipStream_t st);
 
+// pigs_fqv.hip: F(q,tau) on the vectors of pigs_sqv_* (pigs_fqv_accumulate).  Stage 1 writes (C, S) of every stored vector
+// for the window slices of the n listed walkers to rho ([slot][slice][iqv][2] doubles) with the device code of k_sqv_rho2,
+// stage 2 stages tiles of fqv_width(ns) vectors x ns slices in LDS and adds the ordered pair sums of the lags 0..Ntau to
+// acc ([walker][l][iqv]) and 1 to samples.  One thread owns an accumulator element per launch: the caller never lists a
+// walker twice in ONE launch.  fqv_width is the largest power of two <= kFqvWidthMax whose tile fits kFqvLdsBudget
+// (0: not even one vector's ns slices fit, which pigs_fqv_init refuses).
+constexpr int kFqvListMax = 256;
+constexpr int kFqvThreads = 256;
+constexpr int kFqvWidthMax = 64;                 // one wave of lanes over consecutive vectors
+constexpr size_t kFqvLdsBudget = 64 * 1024;      // 16 bytes per (slice, vector): 64 wide up to 64 slices, 16 wide at 161
+struct FqvList { int32_t w[kFqvListMax]; };
+int fqv_width(int ns);
+hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const FqvList &list, int window, int Ntau, int nmax,
+                      double *rho, double *acc, unsigned long long *samples, hipStream_t st);
+
 // pigs_grv.hip: the pair distribution of a periodic system on the vector grid and radially, over the window slices
 // Nb-window .. Nb+window (pigs_grv_accumulate): 64-bit counts per walker, vec [walker][Nbin^dim] (x fastest) and radial
 // [walker][Nr].  The list travels in the kernel arguments, at most kGrvListMax walkers per launch; a walker may be listed

@@ -12,7 +12,8 @@
 //   exp(i q.x) = e_1[n_1] e_2[n_2] e_3[n_3],     e_k[m] = exp(i real(m) qbin_k x_k),  e_k[-m] = conj(e_k[m]),
 // with dim*nmax phasors per particle, each from one direct sincos of the phase rounded as k_structure rounds it.
 //
-// Two launches on the context's stream:
+// Two launches on the context's stream (the body of the first is sqv_rho_slice in pigs_sqv_device.h, which k_fqv_rho of
+// pigs_fqv.hip runs too, keeping C and S instead of their squares):
 //   k_sqv_rho2     one workgroup per (listed walker, window slice).  The phasors of a tile of particles are staged in
 //                  LDS.  A work item is one prefix (n_1..n_{dim-1}) of the half space (lexicographically >= 0) and one
 //                  chunk of kSqvChunk values m = |n_dim|; a thread walks the particles in ascending order, forms the
@@ -29,22 +30,13 @@
 
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_sqv_device.h"
 
 namespace pigs {
 
 namespace {
 
-struct __align__(16) c2 { double x, y; };
-
-// e^(i n phase) from the table row of one particle and axis (entry m = |n|; entry 0 is 1)
-__device__ __forceinline__ c2 phasor(const c2 *row, int n)
-{
-    c2 e = row[n < 0 ? -n : n];
-    if (n < 0) e.y = -e.y;
-    return e;
-}
-
-// tab: [k][particle of the tile][m = 0..ms-1], ms = kSqvChunk * nchunk + 1
+// tab: [k][particle of the tile][m = 0..ms-1], ms = kSqvChunk * nchunk + 1 (sqv_rho_slice, pigs_sqv_device.h)
 template <int DIM>
 __global__ __launch_bounds__(kSqvThreadsMax) void k_sqv_rho2(
     DevParams P, const double *__restrict__ paths, SqvList list, int window, int nmax, int tile, int nprefix, int nchunk,
@@ -54,80 +46,8 @@ __global__ __launch_bounds__(kSqvThreadsMax) void k_sqv_rho2(
     const int ns = 2 * window + 1;
     const int slot = blockIdx.x / ns, j = blockIdx.x - slot * ns;
     const int w = list.w[slot];
-    const int Np = P.Np, NpPad = P.NpPad;
-    const int S = 2 * nmax + 1, ms = kSqvChunk * nchunk + 1;
-    const double *X = paths + ((size_t)w * P.M + (P.Nb - window + j)) * slice_doubles(DIM, NpPad);
-    double *out = rho2 + ((size_t)slot * ns + j) * (size_t)Nq;
-    const int nitems = nprefix * nchunk;
-    long long Sp = 1;                                                 // S^(dim-1): the prefixes of the whole cube
-    for (int k = 1; k < DIM; ++k) Sp *= S;
-
-    for (int item0 = 0; item0 < nitems; item0 += blockDim.x) {
-        const int item = item0 + threadIdx.x;
-        const bool live = item < nitems;
-        const int chunk = live ? item / nprefix : 0, p = live ? item - chunk * nprefix : 0;
-        const long long rp = p + (Sp - 1) / 2;                        // rank of the prefix in its cube; p = 0 is the zero prefix
-        int n1 = 0, n2 = 0;
-        if (DIM == 2) n1 = (int)rp - nmax;
-        if (DIM == 3) { n1 = (int)(rp / S) - nmax; n2 = (int)(rp - (rp / S) * S) - nmax; }
-        const int m0 = kSqvChunk * chunk + 1;
-        double a0r = 0.0, a0i = 0.0;                                  // m = 0 (chunk 0 keeps it)
-        double p1[kSqvChunk], p2[kSqvChunk], p3[kSqvChunk], p4[kSqvChunk];
-#pragma unroll
-        for (int m = 0; m < kSqvChunk; ++m) p1[m] = p2[m] = p3[m] = p4[m] = 0.0;
-
-        for (int i0 = 0; i0 < Np; i0 += tile) {
-            const int nt = min(tile, Np - i0);
-            __syncthreads();                                          // the previous tile has been consumed
-            for (int t = threadIdx.x; t < DIM * nt * ms; t += blockDim.x) {
-                const int k = t / (nt * ms), r = t - k * (nt * ms), il = r / ms, m = r - il * ms;
-                const double qbin = 2.0 * pi / P.Lbox[k];             // vpi.f90:119
-                const double qr = (double)(float)m * qbin * X[(size_t)k * NpPad + i0 + il];
-                c2 e;
-                sincos(qr, &e.y, &e.x);
-                tab[((size_t)k * tile + il) * ms + m] = e;
-            }
-            __syncthreads();
-            if (live) {
-                for (int il = 0; il < nt; ++il) {
-                    double ar = 1.0, ai = 0.0;
-                    if (DIM >= 2) {
-                        const c2 e = phasor(tab + (size_t)il * ms, n1);
-                        ar = e.x; ai = e.y;
-                    }
-                    if (DIM == 3) {
-                        const c2 e = phasor(tab + ((size_t)tile + il) * ms, n2);
-                        const double br = ar * e.x - ai * e.y, bi = ar * e.y + ai * e.x;
-                        ar = br; ai = bi;
-                    }
-                    a0r = a0r + ar; a0i = a0i + ai;
-                    const c2 *last = tab + ((size_t)(DIM - 1) * tile + il) * ms + m0;
-#pragma unroll
-                    for (int m = 0; m < kSqvChunk; ++m) {
-                        const c2 e = last[m];
-                        p1[m] = __builtin_fma(ar, e.x, p1[m]);
-                        p2[m] = __builtin_fma(ai, e.y, p2[m]);
-                        p3[m] = __builtin_fma(ar, e.y, p3[m]);
-                        p4[m] = __builtin_fma(ai, e.x, p4[m]);
-                    }
-                }
-            }
-        }
-        if (live) {
-            // index of (prefix, n_dim = 0); the stored vectors are those with index >= 0
-            const long long base = rp * S + nmax - Nq - 1;
-            if (chunk == 0 && base >= 0) out[base] = a0r * a0r + a0i * a0i;
-#pragma unroll
-            for (int m = 0; m < kSqvChunk; ++m) {
-                const int mm = m0 + m;
-                if (mm > nmax) continue;
-                const double cp = p1[m] - p2[m], sp = p3[m] + p4[m];      // a e[m]
-                const double cm = p1[m] + p2[m], sm = p4[m] - p3[m];      // a conj(e[m])
-                out[base + mm] = cp * cp + sp * sp;
-                if (base - mm >= 0) out[base - mm] = cm * cm + sm * sm;
-            }
-        }
-    }
+    const double *X = paths + ((size_t)w * P.M + (P.Nb - window + j)) * slice_doubles(DIM, P.NpPad);
+    sqv_rho_slice<DIM, false>(P, X, tab, nmax, tile, nprefix, nchunk, Nq, pi, rho2 + ((size_t)slot * ns + j) * (size_t)Nq);
 }
 
 // rho2: [slot][window slice][iqv]; acc: [walker][iqv]

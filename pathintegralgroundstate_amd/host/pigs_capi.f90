@@ -512,6 +512,24 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its counts after the copy
        integer(c_int) :: rc
      end function pigs_grv_read_t
+
+     ! F(q,tau) on the full reciprocal grid (include/pigs_hip.h, pigs_fqv_*): looked up at run time, see fqv_bind; _count,
+     ! _vectors and _accumulate have the signatures of the pigs_sqv_* ones
+     function pigs_fqv_init_t(ctx,nmax,Ntau,window) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value        :: ctx
+       integer(c_int32_t), value :: nmax,Ntau,window
+       integer(c_int) :: rc
+     end function pigs_fqv_init_t
+
+     function pigs_fqv_read_t(ctx,F,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: F(*)          ! raw sums (Nq,0:Ntau,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_fqv_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -535,6 +553,13 @@ module pigs_capi
   procedure(pigs_grv_init_t), pointer       :: grv_init => null()
   procedure(pigs_grv_accumulate_t), pointer :: grv_accumulate => null()
   procedure(pigs_grv_read_t), pointer       :: grv_read => null()
+
+  ! bound by fqv_bind (null until then)
+  procedure(pigs_fqv_init_t), pointer       :: fqv_init => null()
+  procedure(pigs_sqv_count_t), pointer      :: fqv_count => null()
+  procedure(pigs_sqv_vectors_t), pointer    :: fqv_vectors => null()
+  procedure(pigs_sqv_accumulate_t), pointer :: fqv_accumulate => null()
+  procedure(pigs_fqv_read_t), pointer       :: fqv_read => null()
 
 contains
 
@@ -619,6 +644,27 @@ contains
     call c_f_procpointer(f(2),grv_accumulate)
     call c_f_procpointer(f(3),grv_read)
   end function grv_bind
+
+  ! The vector-F(q,tau) entry points, found like the vector-S(q) ones: at run time, only when a run asks for them.
+  logical function fqv_bind()
+    type(c_funptr) :: f(5)
+    integer :: i
+    f(1) = c_dlsym(c_null_ptr,'pigs_fqv_init'//c_null_char)
+    f(2) = c_dlsym(c_null_ptr,'pigs_fqv_count'//c_null_char)
+    f(3) = c_dlsym(c_null_ptr,'pigs_fqv_vectors'//c_null_char)
+    f(4) = c_dlsym(c_null_ptr,'pigs_fqv_accumulate'//c_null_char)
+    f(5) = c_dlsym(c_null_ptr,'pigs_fqv_read'//c_null_char)
+    fqv_bind = .true.
+    do i=1,5
+       fqv_bind = fqv_bind .and. c_associated(f(i))
+    end do
+    if (.not. fqv_bind) return
+    call c_f_procpointer(f(1),fqv_init)
+    call c_f_procpointer(f(2),fqv_count)
+    call c_f_procpointer(f(3),fqv_vectors)
+    call c_f_procpointer(f(4),fqv_accumulate)
+    call c_f_procpointer(f(5),fqv_read)
+  end function fqv_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -14,6 +14,7 @@ module pigs_estimators
   public :: normalize_density, write_density, write_profile
   public :: normalize_fqt, write_fqt
   public :: normalize_sqv, sqv_shells, sqv_shell_means, write_sqvec, write_sqshell
+  public :: normalize_fqv, write_fqvec, write_fqshell
   public :: normalize_grv, write_grvec
 
   type est_params
@@ -393,6 +394,67 @@ contains
     end do
     close (u)
   end subroutine write_sqshell
+
+  ! ---- F(q,tau) on the full reciprocal grid (raw sums of pigs_fqv_read: the vectors of the vector S(q), window slices
+  ! Nb-window..Nb+window, lags 0..Ntau) -> one walker's F(q,tau_l) of one block with S samples:
+  ! raw/(S n_pairs(l) Np), n_pairs(l) = 2 window + 1 - l.  Lag 0 is normalize_sqv's value.
+  subroutine normalize_fqv(Np,Ntau,window,S,Nq,raw,F)
+    integer, intent(in)    :: Np,Ntau,window,Nq
+    integer(8), intent(in) :: S
+    real(8), intent(in)    :: raw(Nq,0:Ntau)
+    real(8), intent(out)   :: F(Nq,0:Ntau)
+    integer :: l
+    do l=0,Ntau
+       F(:,l) = raw(:,l)/(real(S,8)*real(2*window+1-l,8)*real(Np,8))
+    end do
+  end subroutine normalize_fqv
+
+  ! fqvec_vpi.out: one line per (lag, stored vector), lags slowest: l, tau_l = l dt, n_1..n_dim, |q|, F, error over the
+  ! n blocks
+  subroutine write_fqvec(fname,p,Ntau,dt,Nq,nv,n,av,av2)
+    character(len=*), intent(in) :: fname
+    type(est_params), intent(in) :: p
+    integer, intent(in)    :: Ntau,Nq,n
+    real(8), intent(in)    :: dt
+    integer(4), intent(in) :: nv(p%dim,Nq)
+    real(8), intent(inout) :: av(Nq,0:Ntau),av2(Nq,0:Ntau)
+    integer :: i,k,l,u
+    real(8) :: q2
+    character(len=32) :: fmt
+    write (fmt,'(a,i0,a)') '(i6,g20.10e3,',p%dim,'i6,3g20.10e3)'
+    open (newunit=u,file=fname)
+    do l=0,Ntau
+       do i=1,Nq
+          av(i,l)  = av(i,l)/real(n)
+          av2(i,l) = av2(i,l)/real(n)
+          q2 = 0.d0
+          do k=1,p%dim
+             q2 = q2+(real(nv(k,i),8)*p%qbin(k))**2
+          end do
+          write (u,fmt) l,real(l,8)*dt,(nv(k,i),k=1,p%dim),sqrt(q2),av(i,l),variance(n,av(i,l),av2(i,l))
+       end do
+    end do
+    close (u)
+  end subroutine write_fqvec
+
+  ! fqsh_vpi.out: one line per (lag, |q| shell), lags slowest: l, tau_l, |q|, F, error over the n blocks, multiplicity
+  ! (+q and -q); the shells are sq_vpi.out's
+  subroutine write_fqshell(fname,Ntau,dt,nsh,qsh,mult,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: Ntau,nsh,mult(nsh),n
+    real(8), intent(in)    :: dt,qsh(nsh)
+    real(8), intent(inout) :: av(nsh,0:Ntau),av2(nsh,0:Ntau)
+    integer :: i,l,u
+    open (newunit=u,file=fname)
+    do l=0,Ntau
+       do i=1,nsh
+          av(i,l)  = av(i,l)/real(n)
+          av2(i,l) = av2(i,l)/real(n)
+          write (u,'(i6,4g20.10e3,i8)') l,real(l,8)*dt,qsh(i),av(i,l),variance(n,av(i,l),av2(i,l)),mult(i)
+       end do
+    end do
+    close (u)
+  end subroutine write_fqshell
 
   ! ---- pair distribution on the vector grid over a slice window (counts of pigs_grv_read: window slices
   ! Nb-window..Nb+window, Ng bins per axis over the minimum-image cell, nv = Ng**dim, x fastest; radial counts on the run's

@@ -25,6 +25,10 @@
 ! gr_nbin bins per axis (default 32), and radially on the run's own Nbin/rbin grid, both averaged over the slices
 ! Nb-gr_window..Nb+gr_window (default 0), accumulated on the GPU -- grvec_vpi.out, one line per bin, and grw_vpi.out in
 ! gr_vpi.out's format)
+! (fq_vector = T, periodic systems only: F(q,tau_l) on the full reciprocal grid, the vectors of sq_vector with |n_k| <=
+! fqv_nmax (default 8), for the lags l = 0..fqv_ntau (default 0) between the slices Nb-fqv_window..Nb+fqv_window (default
+! ceiling(fqv_ntau/2)), accumulated on the GPU -- fqvec_vpi.out, one line per (lag, vector), and fqsh_vpi.out, one line
+! per (lag, |q| shell))
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -61,6 +65,8 @@ program pigs_vpi
   integer           :: sq_nmax,sq_window
   logical           :: gr_vector
   integer           :: gr_nbin,gr_window
+  logical           :: fq_vector
+  integer           :: fqv_nmax,fqv_ntau,fqv_window
   logical           :: sampler_auto
   integer(c_int)    :: rc_probe
   type(pigs_sweep_params) :: probe_par
@@ -74,7 +80,8 @@ program pigs_vpi
   namelist /jastrow/ Rm
   namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device,density_profile, &
        &             fq_tau,fq_ntau,fq_window,sq_vector,sq_nmax,sq_window, &
-       &             gr_vector,gr_nbin,gr_window
+       &             gr_vector,gr_nbin,gr_window, &
+       &             fq_vector,fqv_nmax,fqv_ntau,fqv_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -100,6 +107,7 @@ program pigs_vpi
   fq_tau = .false.; fq_ntau = 0; fq_window = -1
   sq_vector = .false.; sq_nmax = 8; sq_window = 0
   gr_vector = .false.; gr_nbin = 32; gr_window = 0
+  fq_vector = .false.; fqv_nmax = 8; fqv_ntau = 0; fqv_window = -1
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -197,6 +205,33 @@ program pigs_vpi
      if (.not. grv_bind()) then
         write (0,'(a)') ' pigs_vpi: gr_vector = T: this backend does not export pigs_grv_init / _accumulate / _read'// &
              & ' (the vector g(r) runs on libpigs_hip.so only)'
+        stop 2
+     end if
+  end if
+  if (fq_vector) then
+     ! F(q,tau) on the full reciprocal grid of a periodic system; entry points resolved at run time as above
+     if (trap) then
+        write (0,'(a)') ' pigs_vpi: fq_vector = T needs a periodic system (trap = F): its q grid is that of the box'
+        stop 2
+     end if
+     if (fqv_nmax<1 .or. fqv_nmax>merge(16,64,dim==3)) then
+        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: fq_vector = T: fqv_nmax = ',fqv_nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
+             & ' (dim = ',dim,')'
+        stop 2
+     end if
+     if (fqv_window<0) fqv_window = (max(fqv_ntau,0)+1)/2       ! ceiling(fqv_ntau/2)
+     if (fqv_ntau<0 .or. fqv_ntau>2*fqv_window) then
+        write (0,'(a,i0,a,i0,a)') ' pigs_vpi: fq_vector = T: fqv_ntau = ',fqv_ntau,' must lie in 0 .. 2*fqv_window = ',2*fqv_window, &
+             & ' (lags between the slices Nb-fqv_window .. Nb+fqv_window)'
+        stop 2
+     end if
+     if (fqv_window>Nb) then
+        write (0,'(a,i0,a,i0)') ' pigs_vpi: fq_vector = T: fqv_window = ',fqv_window,' must not exceed Nb = ',Nb
+        stop 2
+     end if
+     if (.not. fqv_bind()) then
+        write (0,'(a)') ' pigs_vpi: fq_vector = T: this backend does not export pigs_fqv_init / _count / _vectors /'// &
+             & ' _accumulate / _read (the vector F(q,tau) runs on libpigs_hip.so only)'
         stop 2
      end if
   end if
@@ -319,6 +354,11 @@ program pigs_vpi
           & ': grvec_vpi.out, grw_vpi.out)'
   end if
 
+  if (fq_vector) then
+     print '(a,i0,a,i0,a,i0,a,i0,a)', '  > Vector F(q,tau)   : on (|n_k| <= ',fqv_nmax,', lags 0..',fqv_ntau,', slices Nb-',fqv_window, &
+          & '..Nb+',fqv_window,': fqvec_vpi.out, fqsh_vpi.out)'
+  end if
+
   !=====================================================================
 
   !$omp parallel num_threads(G) default(shared)
@@ -430,6 +470,16 @@ contains
   integer(c_int64_t), allocatable :: gv_vec(:,:),gv_rad(:,:),gv_smp(:)
   integer(c_int32_t), allocatable :: gv_reset(:)
   real(8), allocatable :: gvb(:),gwb(:),AvGv(:,:),AvGv2(:,:),AvGw(:,:),AvGw2(:,:),AvGvAll(:),AvGv2All(:),AvGwAll(:),AvGw2All(:)
+  ! vector F(q,tau) (fq_vector = T): the stored vectors and their |q| shells (those of the vector S(q)), the block's raw
+  ! sums from the device, the normalised block values per (vector, lag) and per (shell, lag), their per-walker sums and
+  ! the walker-averaged sums; nqv doubles of the block vector behind the vector-g(r) ones (0 with the key off)
+  integer :: nfx,nqv,nfxav,nfxall,nfsh,lag
+  integer(c_int64_t) :: fx_count
+  integer(c_int32_t), allocatable :: fx_n(:,:),fx_reset(:)
+  integer(c_int64_t), allocatable :: fx_smp(:)
+  integer, allocatable :: fx_shell(:),fx_mult(:)
+  real(8), allocatable :: fx_raw(:,:,:),fxb(:,:),fxs(:,:),fx_q(:),AvFx(:,:,:),AvFx2(:,:,:),AvFs(:,:,:),AvFs2(:,:,:)
+  real(8), allocatable :: AvFxAll(:,:),AvFx2All(:,:),AvFsAll(:,:),AvFs2All(:,:)
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -568,6 +618,22 @@ contains
      gv_reset = 1
   end if
 
+  nfx = 0; nqv = 0; nfxav = 0
+  if (fq_vector) then
+     call pigs_check(fqv_init(ctx,int(fqv_nmax,c_int32_t),int(fqv_ntau,c_int32_t),int(fqv_window,c_int32_t)),'pigs_fqv_init')
+     call pigs_check(fqv_count(ctx,fx_count),'pigs_fqv_count')
+     nfx = int(fx_count)
+     nqv = nfx*(fqv_ntau+1)+1
+     ! (second index: lag l + 1; 1-based, as every array here that goes through reshape)
+     allocate (fx_n(dim,nfx),fx_shell(nfx),fx_raw(nfx,fqv_ntau+1,NW),fx_smp(NW),fx_reset(NW),fxb(nfx,fqv_ntau+1))
+     call pigs_check(fqv_vectors(ctx,fx_n),'pigs_fqv_vectors')
+     call sqv_shells(ep,nfx,fx_n,fx_shell,nfsh,fx_q,fx_mult)
+     allocate (fxs(nfsh,fqv_ntau+1),AvFx(nfx,fqv_ntau+1,NW),AvFx2(nfx,fqv_ntau+1,NW),AvFs(nfsh,fqv_ntau+1,NW),AvFs2(nfsh,fqv_ntau+1,NW))
+     allocate (AvFxAll(nfx,fqv_ntau+1),AvFx2All(nfx,fqv_ntau+1),AvFsAll(nfsh,fqv_ntau+1),AvFs2All(nfsh,fqv_ntau+1))
+     AvFx = 0.d0; AvFx2 = 0.d0; AvFs = 0.d0; AvFs2 = 0.d0; AvFxAll = 0.d0; AvFx2All = 0.d0; AvFsAll = 0.d0; AvFs2All = 0.d0
+     fx_reset = 1
+  end if
+
   allocate (perm(NW))
   do w=1,NW
      allocate (perm(w)%members(Np),perm(w)%histogram(Np))
@@ -604,7 +670,7 @@ contains
   ! the vector that meets the other shards' once per block: number of walkers with a diagonal block, their summed block
   ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
   nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
-  allocate (vec(nvec+ndv+nfv+nsv+ngv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
+  allocate (vec(nvec+ndv+nfv+nsv+ngv+nqv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
   allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
   AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
   ngrav = 0; nnrav = 0
@@ -820,6 +886,8 @@ contains
            if (sq_vector) call pigs_check(sqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sqv_accumulate')
            ! and into the counts of the vector g(r)
            if (gr_vector) call pigs_check(grv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_grv_accumulate')
+           ! and into the sums of the vector F(q,tau)
+           if (fq_vector) call pigs_check(fqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqv_accumulate')
         end if
 
      end do   ! istep
@@ -848,6 +916,7 @@ contains
      if (fq_tau) call pigs_check(fqt_read(ctx,fq_raw,fq_smp,fq_reset),'pigs_fqt_read')
      if (sq_vector) call pigs_check(sqv_read(ctx,sq_raw,sq_smp,sq_reset),'pigs_sqv_read')
      if (gr_vector) call pigs_check(grv_read(ctx,gv_vec,gv_rad,gv_smp,gv_reset),'pigs_grv_read')
+     if (fq_vector) call pigs_check(fqv_read(ctx,fx_raw,fx_smp,fx_reset),'pigs_fqv_read')
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -898,6 +967,17 @@ contains
               vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin) = vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin)+gwb
               vec(nvec+ndv+nfv+nsv+ngv) = vec(nvec+ndv+nfv+nsv+ngv)+1.d0
            end if
+           if (fq_vector) then
+              call normalize_fqv(Np,fqv_ntau,fqv_window,int(fx_smp(w),8),nfx,fx_raw(:,:,w),fxb)
+              do lag=1,fqv_ntau+1
+                 call sqv_shell_means(nfx,fx_shell,nfsh,fx_mult,fxb(:,lag),fxs(:,lag))
+              end do
+              AvFx(:,:,w) = AvFx(:,:,w)+fxb; AvFx2(:,:,w) = AvFx2(:,:,w)+fxb*fxb
+              AvFs(:,:,w) = AvFs(:,:,w)+fxs; AvFs2(:,:,w) = AvFs2(:,:,w)+fxs*fxs
+              vec(nvec+ndv+nfv+nsv+ngv+1:nvec+ndv+nfv+nsv+ngv+nqv-1) = vec(nvec+ndv+nfv+nsv+ngv+1:nvec+ndv+nfv+nsv+ngv+nqv-1) &
+                   & +reshape(fxb,[nqv-1])
+              vec(nvec+ndv+nfv+nsv+ngv+nqv) = vec(nvec+ndv+nfv+nsv+ngv+nqv)+1.d0
+           end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
            write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -921,7 +1001,7 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv+nsv+ngv,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv+nsv+ngv+nqv,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
      ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
      if (ish==1 .and. NWtot>1) then
@@ -977,6 +1057,18 @@ contains
               gwb = vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin)/ngvall
               AvGvAll = AvGvAll+gvb; AvGv2All = AvGv2All+gvb*gvb
               AvGwAll = AvGwAll+gwb; AvGw2All = AvGw2All+gwb*gwb
+           end if
+        end if
+        if (fq_vector) then                  ! walker average of the block's vector F(q,tau) and of its shell means
+           nfxall = nint(vec(nvec+ndv+nfv+nsv+ngv+nqv))
+           if (nfxall>0) then
+              nfxav = nfxav+1
+              fxb = reshape(vec(nvec+ndv+nfv+nsv+ngv+1:nvec+ndv+nfv+nsv+ngv+nqv-1),[nfx,fqv_ntau+1])/nfxall
+              do lag=1,fqv_ntau+1
+                 call sqv_shell_means(nfx,fx_shell,nfsh,fx_mult,fxb(:,lag),fxs(:,lag))
+              end do
+              AvFxAll = AvFxAll+fxb; AvFx2All = AvFx2All+fxb*fxb
+              AvFsAll = AvFsAll+fxs; AvFs2All = AvFs2All+fxs*fxs
            end if
         end if
      end if
@@ -1078,6 +1170,10 @@ contains
         call write_grvec('grvec_vpi'//trim(suffix)//'.out',ep,gr_nbin,ngb,diag_bl(w),AvGv(:,w),AvGv2(:,w))
         call write_radial('grw_vpi'//trim(suffix)//'.out',ep,diag_bl(w),AvGw(:,w),AvGw2(:,w))
      end if
+     if (fq_vector) then
+        call write_fqvec('fqvec_vpi'//trim(suffix)//'.out',ep,fqv_ntau,dt,nfx,fx_n,diag_bl(w),AvFx(:,:,w),AvFx2(:,:,w))
+        call write_fqshell('fqsh_vpi'//trim(suffix)//'.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,diag_bl(w),AvFs(:,:,w),AvFs2(:,:,w))
+     end if
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
@@ -1099,6 +1195,10 @@ contains
      if (gr_vector) then
         call write_grvec('grvec_vpi.out',ep,gr_nbin,ngb,ngvav,AvGvAll,AvGv2All)
         call write_radial('grw_vpi.out',ep,ngvav,AvGwAll,AvGw2All)
+     end if
+     if (fq_vector) then
+        call write_fqvec('fqvec_vpi.out',ep,fqv_ntau,dt,nfx,fx_n,nfxav,AvFxAll,AvFx2All)
+        call write_fqshell('fqsh_vpi.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,nfxav,AvFsAll,AvFs2All)
      end if
   end if
 

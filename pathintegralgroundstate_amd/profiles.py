@@ -1,6 +1,6 @@
 """Normalisation of the accumulators that PigsContext.density_read (trapped systems, pigs_density_*),
-PigsContext.fqt_read, PigsContext.sqv_read and PigsContext.grv_read (periodic systems, pigs_fqt_*, pigs_sqv_*,
-pigs_grv_*) return.
+PigsContext.fqt_read, PigsContext.sqv_read, PigsContext.fqv_read and PigsContext.grv_read (periodic systems, pigs_fqt_*,
+pigs_sqv_*, pigs_fqv_*, pigs_grv_*) return.
 
 Trapped-system profiles:
 
@@ -20,6 +20,11 @@ Vector structure factor (normalize_sqv, shell_average): raw[iqv] holds, per samp
 the window slices at the integer vector n[iqv] (q_k = n_k * 2*pi/Lbox[k]; half space, so q stands for -q too):
   S(q) = raw / (S * (2*window + 1) * Np)
 and the vectors of equal |q| form a shell over which S(q) of an isotropic system is averaged.
+
+F(q,tau) on the vector grid (normalize_fqv, shell_average): raw[l][iqv] holds, per sample, the n_pairs(l) products
+C(a)C(a+l) + S(a)S(a+l) of the window slices at the vector n[iqv] of the S(q) grid above:
+  F(q, tau_l) = raw / (S * n_pairs(l) * Np)
+Its l = 0 row is normalize_sqv's S(q); shell_average(n, Lbox, F) gives the table per lag and |q| shell.
 
 Pair distribution on the vector grid (normalize_grv): vec[j] counts, per sample, the pairs i < j of the 2*window + 1
 window slices whose folded displacement x(i) - x(j) falls into bin j of the minimum-image cell (width b_k = Lbox[k]/Nbin);
@@ -101,6 +106,22 @@ def normalize_sqv(raw, samples, Np, window):
         S = S.reshape(S.shape + (1,))
     with np.errstate(divide="ignore", invalid="ignore"):
         return A / (S * (2.0 * window + 1.0) * float(Np))
+
+
+def normalize_fqv(raw, samples, Np, window):
+    """raw: the sums of fqv_read ([W, Ntau+1, Nq] or one walker's [Ntau+1, Nq]), samples: [W] or a scalar.  Returns
+    F(q, tau_l) of the same shape as raw: raw / (samples * n_pairs(l) * Np), n_pairs(l) = 2*window + 1 - l.  A walker
+    without samples gives NaN."""
+    A = np.asarray(raw, dtype=np.float64)
+    S = np.asarray(samples, dtype=np.float64)
+    nl = A.shape[-2]
+    if nl > 2 * window + 1:
+        raise ValueError("more lags than the window holds")
+    if S.ndim > 0:
+        S = S.reshape(S.shape + (1, 1))
+    n_pairs = 2.0 * window + 1.0 - np.arange(nl, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return A / (S * n_pairs[:, None] * float(Np))
 
 
 def shell_average(n, Lbox, Sq):
