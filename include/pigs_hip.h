@@ -436,6 +436,40 @@ int pigs_grv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_grv_init. */
 int pigs_grv_read(pigs_ctx *ctx, int64_t *vec, int64_t *radial, int64_t *samples, const int32_t *reset);
 
+/* ---- imaginary-time profiles of the potential energy, the virial and the link lengths (new: pigs_fqt_*, pigs_sqv_*,
+ * pigs_fqv_*, pigs_grv_* and the density profiles all take a slice window "inside the converged part of the path"; this
+ * is the quantity that shows where that part is) ----------------------------------------------------------------------
+ * Periodic and trapped contexts.  Per listed walker w and EVERY slice b = 0..2Nb an accumulate call adds four sums,
+ *   Q[w][b][0]  Vpair = sum_{i<j} v(r_ij)          v  = Interpolate opt 0 on VTable, the reference's indexing
+ *   Q[w][b][1]  Vext  = sum_i sum_k TrapPot(0, a_ho(k), x_k(i))       (trap; exactly 0.0 in a periodic system)
+ *   Q[w][b][2]  W     = sum_{i<j} r_ij v'(r_ij)    v' = Interpolate opt 1 on VTable, the derivative of the force terms
+ *   Q[w][b][3]  D2    = sum_i |x_i(b) - x_i(b+1)|^2                   (exactly 0.0 for b = 2Nb)
+ * and 1 to samples[w].  Pairs as PotentialEnergy takes them (sample_mod.f90:13-150): periodic -- the difference folded
+ * once, counted if and only if r^2 <= rcut2, every term v and r v' with the reference's own rounding (only the order
+ * of the sum differs); trap -- plain distance, no cutoff, the plain arithmetic, table indices clamped to the table.  D2 of a
+ * periodic system folds the link once and counts a particle only if the folded |link|^2 <= rcut2 (quirk Q8, as
+ * ThermEnergy's spring term); in the trap it is the plain distance.  The estimators are the caller's divisions
+ * (profiles.normalize_tau): per particle Vpair/(samples Np), Vext/(samples Np), W/(samples Np), and the kinetic
+ * estimator of link b, dim/(2 dt) - D2[b]/(2 dt^2 Np samples); tau_b = (b - Nb) dt.  The pressure of a periodic system
+ * follows from the virial, P = density/dim (2 K/N - W/N); pairs beyond rcut are not in W and no tail correction is made.
+ * V(tau_b) falls from the trial function's value at b = 0, 2Nb to a plateau: the plateau is the usable window.
+ * The library still does not judge it.
+ * The sums are taken in fixed orders without floating-point atomics (per-lane sums in ascending particle order, the wave,
+ * the waves in wave order, then acc += value): the same worldline gives the same bits whatever the walker list, its
+ * order, the launch split or the number of walkers of the context (there is one kernel form and no tuning key).  A
+ * non-finite term (a coincident pair) stays in its own element (w, b, quantity).
+ *
+ * pigs_tau_init allocates and zeroes the sums (again: zeroes). */
+int pigs_tau_init(pigs_ctx *ctx);
+/* Adds every slice of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_tau_init, for n < 0 or for a walker out of range. */
+int pigs_tau_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' raw sums Q[n_walkers][2Nb+1][4] and samples[n_walkers]; then zeroes those of the walkers w with
+ * reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_tau_init. */
+int pigs_tau_read(pigs_ctx *ctx, double *Q, int64_t *samples, const int32_t *reset);
+
 /* ---- multi-GPU: block-estimator reduction (new) ------------------------ */
 /* RCCL communicator over `nranks` contexts.  Single-process form (one host thread per
  * GPU, the Fortran host: pigs_vpi's &gpu n_gpus = G): pigs_comm_init_all.  Multi-process form: rank 0 obtains an id

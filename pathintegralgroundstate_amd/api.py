@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "pigs_sqv_init", "pigs_sqv_count", "pigs_sqv_vectors", "pigs_sqv_accumulate", "pigs_sqv_read",
     "pigs_fqv_init", "pigs_fqv_count", "pigs_fqv_vectors", "pigs_fqv_accumulate", "pigs_fqv_read",
     "pigs_grv_init", "pigs_grv_accumulate", "pigs_grv_read",
+    "pigs_tau_init", "pigs_tau_accumulate", "pigs_tau_read",
 ]
 
 
@@ -133,6 +134,9 @@ def load_library(path=LIB_PATH):
     L.pigs_fqt_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
     L.pigs_fqt_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_fqt_read.argtypes = [vp, _dp, _lp, _ip]
+    L.pigs_tau_init.argtypes = [vp]
+    L.pigs_tau_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_tau_read.argtypes = [vp, _dp, _lp, _ip]
     L.pigs_sqv_init.argtypes = [vp, C.c_int32, C.c_int32]
     L.pigs_sqv_count.argtypes = [vp, _lp]
     L.pigs_sqv_vectors.argtypes = [vp, _ip]
@@ -500,6 +504,36 @@ class PigsContext:
             mask = _i(keep)
         _chk(self.L, self.L.pigs_fqt_read(self.h, _d(out["F"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
              "pigs_fqt_read")
+        return out
+
+    # ---- imaginary-time profiles (pigs_tau_*: raw sums Vpair, Vext, W, D2 per walker and slice)
+    def tau_init(self):
+        """Allocate and zero the sums of the imaginary-time profiles (every slice b = 0..2Nb: pair and external potential
+        energy, virial, squared link length).  Calling it again zeroes."""
+        _chk(self.L, self.L.pigs_tau_init(self.h), "pigs_tau_init")
+
+    def tau_accumulate(self, walkers=None):
+        """Queue one sample of every slice of `walkers` (None: all) on the context's stream; does not wait."""
+        if walkers is None:
+            _chk(self.L, self.L.pigs_tau_accumulate(self.h, self.n_walkers, None), "pigs_tau_accumulate")
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, self.L.pigs_tau_accumulate(self.h, wl.size, _i(wl)), "pigs_tau_accumulate")
+
+    def tau_read(self, reset=None):
+        """dict: Q, the raw sums [W, 2Nb+1, 4] (Vpair, Vext, W, D2; profiles.normalize_tau divides them), and samples [W]
+        (int64).  reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        W = self.n_walkers
+        out = {"Q": np.zeros((W, self.cfg.M, 4)), "samples": np.zeros(W, np.int64)}
+        if reset is None or reset is False:
+            mask = None
+        else:
+            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
+            if keep.size != W:
+                raise ValueError("reset mask needs one entry per walker")
+            mask = _i(keep)
+        _chk(self.L, self.L.pigs_tau_read(self.h, _d(out["Q"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
+             "pigs_tau_read")
         return out
 
     # ---- vector structure factor on the full reciprocal grid (pigs_sqv_*: raw sums per walker and vector)

@@ -231,6 +231,12 @@ struct pigs_ctx {
     int         grv_form = -1;              // tuning key "grv_form": -1 automatic, 0 global atomics, 1 grid privatised in LDS
     size_t      grv_nvec = 0;               // vector bins per walker: Nbin^dim
     double      grv_rbin = 0.0;
+    // imaginary-time profiles (pigs_tau_*): raw sums [walker][2Nb+1][4] and the samples per walker
+    DevBuf<double> d_tau_acc;
+    DevBuf<unsigned long long> d_tau_samples;
+    bool        tau_ready = false;          // pigs_tau_init called
+    std::vector<int64_t> tau_mark;          // per walker: the last launch (tau_launch) that listed it
+    int64_t     tau_launch = 0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -1487,6 +1493,75 @@ int pigs_fqt_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset
             while (e < W && reset[e]) ++e;
             HIPCHK(hipMemsetAsync(c->d_fqt_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
             HIPCHK(hipMemsetAsync(c->d_fqt_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
+            w = e;
+        }
+    }
+    SYNC_CHECKED(c);
+    return PIGS_OK;
+}
+
+// ---- imaginary-time profiles: V(tau), the virial and the link lengths of every slice --------------
+// Raw sums per walker, slice and quantity (pigs_tau.hip), accumulated on the device and read per block.
+int pigs_tau_init(pigs_ctx *c)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    const size_t W = (size_t)c->n_walkers, per = (size_t)c->P.M * 4;
+    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
+    c->tau_ready = false;
+    HIPCHK(c->d_tau_acc.alloc(W * per));
+    HIPCHK(c->d_tau_samples.alloc(W));
+    HIPCHK(hipMemsetAsync(c->d_tau_acc.p, 0, W * per * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_tau_samples.p, 0, W * sizeof(unsigned long long), c->stream));
+    SYNC_CHECKED(c);
+    c->tau_ready = true;
+    return PIGS_OK;
+}
+
+int pigs_tau_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->tau_ready) return fail(PIGS_ERR_ARG, "pigs_tau_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // As pigs_fqt_accumulate: the list goes by value in the kernel arguments, and a launch ends where it is full or a
+    // walker would appear in it a second time (one workgroup owns an accumulator element per launch); the stream orders
+    // the launches, so a walker listed twice is added twice.  A list left out (0..n-1) holds no repeats.
+    if (walkers) c->tau_mark.resize(c->n_walkers, 0);
+    for (int i0 = 0; i0 < n;) {
+        const int64_t launch = ++c->tau_launch;
+        TauList L{};
+        int m = 0;
+        while (i0 + m < n && m < kTauListMax && !(walkers && c->tau_mark[sw[i0 + m]] == launch)) {
+            if (walkers) c->tau_mark[sw[i0 + m]] = launch;
+            L.w[m] = sw[i0 + m];
+            ++m;
+        }
+        HIPCHK(launch_tau(c->P, c->d_paths.p, c->d_VT.p, m, L, c->d_tau_acc.p, c->d_tau_samples.p, c->stream));
+        i0 += m;
+    }
+    return PIGS_OK;
+}
+
+int pigs_tau_read(pigs_ctx *c, double *Q, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->tau_ready) return fail(PIGS_ERR_ARG, "pigs_tau_init first");
+    if (!Q || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t W = (size_t)c->n_walkers, per = (size_t)c->P.M * 4;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(Q, c->d_tau_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(samples, c->d_tau_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (reset) {
+        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
+        for (size_t w = 0; w < W;) {
+            if (!reset[w]) { ++w; continue; }
+            size_t e = w;
+            while (e < W && reset[e]) ++e;
+            HIPCHK(hipMemsetAsync(c->d_tau_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
+            HIPCHK(hipMemsetAsync(c->d_tau_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
             w = e;
         }
     }

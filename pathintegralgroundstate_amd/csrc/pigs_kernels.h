@@ -119,6 +119,15 @@ hipError_t launch_grv(const DevParams &P, const double *paths, int n, const GrvL
                       int Nbin, int Nr, double rbin, unsigned long long *vec, unsigned long long *radial,
                       unsigned long long *samples, hipStream_t st);
 
+// pigs_tau.hip: imaginary-time profiles (pigs_tau_accumulate): per listed walker and slice b = 0..2Nb the sums Vpair, Vext,
+// W = sum r v'(r) and D2 = sum_i |x_i(b) - x_i(b+1)|^2 are added to acc ([walker][2Nb+1][4]) and 1 to samples.  One
+// workgroup owns an accumulator element per launch: the caller never
+// lists a walker twice in ONE launch.  The list travels in the kernel arguments, at most kTauListMax walkers per launch.
+constexpr int kTauListMax = 256;
+struct TauList { int32_t w[kTauListMax]; };
+hipError_t launch_tau(const DevParams &P, const double *paths, const double *VT, int n, const TauList &list, double *acc,
+                      unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

@@ -530,6 +530,23 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_fqv_read_t
+
+     ! imaginary-time profiles (include/pigs_hip.h, pigs_tau_*): looked up at run time, see tau_bind; _accumulate has the
+     ! signature of pigs_fqt_accumulate
+     function pigs_tau_init_t(ctx) bind(C) result(rc)
+       import :: c_int, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int) :: rc
+     end function pigs_tau_init_t
+
+     function pigs_tau_read_t(ctx,Q,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: Q(*)          ! raw sums (4,0:2Nb,n_walkers): Vpair, Vext, W, D2
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_tau_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -560,6 +577,11 @@ module pigs_capi
   procedure(pigs_sqv_vectors_t), pointer    :: fqv_vectors => null()
   procedure(pigs_sqv_accumulate_t), pointer :: fqv_accumulate => null()
   procedure(pigs_fqv_read_t), pointer       :: fqv_read => null()
+
+  ! bound by tau_bind (null until then)
+  procedure(pigs_tau_init_t), pointer       :: tau_init => null()
+  procedure(pigs_fqt_accumulate_t), pointer :: tau_accumulate => null()
+  procedure(pigs_tau_read_t), pointer       :: tau_read => null()
 
 contains
 
@@ -665,6 +687,19 @@ contains
     call c_f_procpointer(f(4),fqv_accumulate)
     call c_f_procpointer(f(5),fqv_read)
   end function fqv_bind
+
+  ! The imaginary-time-profile entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function tau_bind()
+    type(c_funptr) :: f(3)
+    f(1) = c_dlsym(c_null_ptr,'pigs_tau_init'//c_null_char)
+    f(2) = c_dlsym(c_null_ptr,'pigs_tau_accumulate'//c_null_char)
+    f(3) = c_dlsym(c_null_ptr,'pigs_tau_read'//c_null_char)
+    tau_bind = c_associated(f(1)) .and. c_associated(f(2)) .and. c_associated(f(3))
+    if (.not. tau_bind) return
+    call c_f_procpointer(f(1),tau_init)
+    call c_f_procpointer(f(2),tau_accumulate)
+    call c_f_procpointer(f(3),tau_read)
+  end function tau_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -16,6 +16,7 @@ module pigs_estimators
   public :: normalize_sqv, sqv_shells, sqv_shell_means, write_sqvec, write_sqshell
   public :: normalize_fqv, write_fqvec, write_fqshell
   public :: normalize_grv, write_grvec
+  public :: normalize_tau, write_tau
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -266,6 +267,41 @@ contains
     end do
     close (u)
   end subroutine write_fqt
+
+  ! ---- imaginary-time profiles (raw sums of pigs_tau_read: Vpair, Vext, W = sum r v'(r), D2 = sum_i |x_i(b)-x_i(b+1)|^2 of
+  ! every slice b = 0..2Nb) -> one walker's profiles of one block with S samples, per particle: T(1:3,b) = raw(1:3,b)/(S Np)
+  ! and the kinetic estimator of the link b -> b+1, T(4,b) = dim/(2 dt) - D2(b)/(2 dt^2 Np S) (b = 2Nb has no link: 0)
+  subroutine normalize_tau(dim,Np,Nb,dt,S,raw,T)
+    integer, intent(in)    :: dim,Np,Nb
+    real(8), intent(in)    :: dt
+    integer(8), intent(in) :: S
+    real(8), intent(in)    :: raw(4,0:2*Nb)
+    real(8), intent(out)   :: T(4,0:2*Nb)
+    integer :: b
+    do b=0,2*Nb
+       T(1:3,b) = raw(1:3,b)/(real(S,8)*real(Np,8))
+       T(4,b)   = real(dim,8)/(2.d0*dt)-raw(4,b)/(2.d0*dt*dt*real(Np,8)*real(S,8))
+    end do
+    T(4,2*Nb) = 0.d0
+  end subroutine normalize_tau
+
+  ! tau_vpi.out: one row per slice: b, tau_b = (b-Nb) dt, then mean and error of Vpair/Np, Vext/Np, W/Np and of the link's
+  ! kinetic estimator (left out in the last row: slice 2Nb starts no link)
+  subroutine write_tau(fname,Nb,dt,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: Nb,n
+    real(8), intent(in)    :: dt
+    real(8), intent(inout) :: av(4,0:2*Nb),av2(4,0:2*Nb)
+    integer :: b,k,u,nc
+    open (newunit=u,file=fname)
+    do b=0,2*Nb
+       av(:,b)  = av(:,b)/real(n)
+       av2(:,b) = av2(:,b)/real(n)
+       nc = merge(3,4,b==2*Nb)
+       write (u,'(20g20.10e3)') real(b,8),real(b-Nb,8)*dt,(av(k,b),variance(n,av(k,b),av2(k,b)),k=1,nc)
+    end do
+    close (u)
+  end subroutine write_tau
 
   ! ---- vector structure factor on the full reciprocal grid (raw sums of pigs_sqv_read: window slices
   ! Nb-window..Nb+window) -> one walker's S(q) of one block with S samples: raw/(S (2 window + 1) Np)

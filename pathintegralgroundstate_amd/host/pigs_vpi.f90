@@ -29,6 +29,11 @@
 ! fqv_nmax (default 8), for the lags l = 0..fqv_ntau (default 0) between the slices Nb-fqv_window..Nb+fqv_window (default
 ! ceiling(fqv_ntau/2)), accumulated on the GPU -- fqvec_vpi.out, one line per (lag, vector), and fqsh_vpi.out, one line
 ! per (lag, |q| shell))
+! (tau_profile = T, periodic and trapped systems: the imaginary-time profiles of every slice b = 0..2Nb -- pair and external
+! potential energy, the virial W = sum r v'(r) and the kinetic estimator of every link, per particle, accumulated on the
+! GPU -- tau_vpi.out; the plateau of V(tau) around slice Nb is the converged part of the path, in which the windows above
+! must stay.  Periodic runs also write press_vpi.out, the virial pressure per block with W averaged over the slices
+! Nb-tau_window..Nb+tau_window (default 0); W stops at rcut and no tail correction is made)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -67,6 +72,8 @@ program pigs_vpi
   integer           :: gr_nbin,gr_window
   logical           :: fq_vector
   integer           :: fqv_nmax,fqv_ntau,fqv_window
+  logical           :: tau_profile
+  integer           :: tau_window
   logical           :: sampler_auto
   integer(c_int)    :: rc_probe
   type(pigs_sweep_params) :: probe_par
@@ -81,7 +88,8 @@ program pigs_vpi
   namelist /gpu/     n_walkers,device,device_sampler,potential,checkpointing,k1_variant,n_gpus,same_device,density_profile, &
        &             fq_tau,fq_ntau,fq_window,sq_vector,sq_nmax,sq_window, &
        &             gr_vector,gr_nbin,gr_window, &
-       &             fq_vector,fqv_nmax,fqv_ntau,fqv_window
+       &             fq_vector,fqv_nmax,fqv_ntau,fqv_window, &
+       &             tau_profile,tau_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -108,6 +116,7 @@ program pigs_vpi
   sq_vector = .false.; sq_nmax = 8; sq_window = 0
   gr_vector = .false.; gr_nbin = 32; gr_window = 0
   fq_vector = .false.; fqv_nmax = 8; fqv_ntau = 0; fqv_window = -1
+  tau_profile = .false.; tau_window = 0
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -235,6 +244,18 @@ program pigs_vpi
         stop 2
      end if
   end if
+  if (tau_profile) then
+     ! imaginary-time profiles of a periodic or trapped system; entry points resolved at run time as above
+     if (tau_window<0 .or. tau_window>Nb) then
+        write (0,'(a,i0,a,i0)') ' pigs_vpi: tau_profile = T: tau_window = ',tau_window,' must lie in 0 .. Nb = ',Nb
+        stop 2
+     end if
+     if (.not. tau_bind()) then
+        write (0,'(a)') ' pigs_vpi: tau_profile = T: this backend does not export pigs_tau_init / _accumulate / _read'// &
+             & ' (the imaginary-time profiles run on libpigs_hip.so only)'
+        stop 2
+     end if
+  end if
   NWtot = n_walkers
   G = max(1,min(n_gpus,NWtot))
   pi = acos(-1.d0)
@@ -342,6 +363,15 @@ program pigs_vpi
 
   if (fq_tau) then
      print '(a,i0,a,i0,a,i0,a)', '  > F(q,tau)            : on (lags 0..',fq_ntau,', slices Nb-',fq_window,'..Nb+',fq_window,': fqt_vpi.out)'
+  end if
+
+  if (tau_profile) then
+     if (trap) then
+        print '(a)', '  > V(tau) profiles     : on (slices 0..2Nb: tau_vpi.out)'
+     else
+        print '(a,i0,a,i0,a)', '  > V(tau) profiles     : on (slices 0..2Nb: tau_vpi.out; pressure over slices Nb-',tau_window,'..Nb+',tau_window, &
+             & ': press_vpi.out)'
+     end if
   end if
 
   if (sq_vector) then
@@ -480,6 +510,15 @@ contains
   integer, allocatable :: fx_shell(:),fx_mult(:)
   real(8), allocatable :: fx_raw(:,:,:),fxb(:,:),fxs(:,:),fx_q(:),AvFx(:,:,:),AvFx2(:,:,:),AvFs(:,:,:),AvFs2(:,:,:)
   real(8), allocatable :: AvFxAll(:,:),AvFx2All(:,:),AvFsAll(:,:),AvFs2All(:,:)
+  ! imaginary-time profiles (tau_profile = T): the block's raw sums from the device (Vpair, Vext, W, D2 per slice), the
+  ! normalised block profiles, their per-walker sums and the walker-averaged sums; ntv doubles of the block vector behind
+  ! the vector-F(q,tau) ones (0 with the key off), starting behind offset otq; the units of press_vpi*.out
+  integer :: ntq,ntv,ntauav,ntauall,otq,upav
+  integer(c_int64_t), allocatable :: tq_smp(:)
+  integer(c_int32_t), allocatable :: tq_reset(:)
+  integer, allocatable :: up(:)
+  real(8), allocatable :: tq_raw(:,:,:),tqb(:,:),AvTq(:,:,:),AvTq2(:,:,:),AvTqAll(:,:),AvTq2All(:,:),tmpt(:,:)
+  real(8) :: wwin
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -634,6 +673,18 @@ contains
      fx_reset = 1
   end if
 
+  ntq = 0; ntv = 0; ntauav = 0
+  if (tau_profile) then
+     ntq = 4*(2*Nb+1)
+     ntv = ntq+1
+     ! (second index: slice b + 1; 1-based, as every array here that goes through reshape)
+     allocate (tq_raw(4,2*Nb+1,NW),tq_smp(NW),tq_reset(NW),tqb(4,2*Nb+1),tmpt(4,2*Nb+1))
+     allocate (AvTq(4,2*Nb+1,NW),AvTq2(4,2*Nb+1,NW),AvTqAll(4,2*Nb+1),AvTq2All(4,2*Nb+1))
+     AvTq = 0.d0; AvTq2 = 0.d0; AvTqAll = 0.d0; AvTq2All = 0.d0
+     tq_reset = 1
+     call pigs_check(tau_init(ctx),'pigs_tau_init')
+  end if
+
   allocate (perm(NW))
   do w=1,NW
      allocate (perm(w)%members(Np),perm(w)%histogram(Np))
@@ -666,11 +717,26 @@ contains
      open (newunit=ueav,file='e_vpi.out')
      open (newunit=utav,file='et_vpi.out')
   end if
+  if (tau_profile .and. .not. trap) then
+     ! the virial pressure per block (periodic runs): per walker, and the walker average where there are several
+     allocate (up(NW))
+     do w=1,NW
+        suffix = ''
+        if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w0+w-1
+        open (newunit=up(w),file='press_vpi'//trim(suffix)//'.out')
+        call press_header(up(w))
+     end do
+     if (NWtot>1 .and. ish==1) then
+        open (newunit=upav,file='press_vpi.out')
+        call press_header(upav)
+     end if
+  end if
 
   ! the vector that meets the other shards' once per block: number of walkers with a diagonal block, their summed block
   ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
   nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
-  allocate (vec(nvec+ndv+nfv+nsv+ngv+nqv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
+  otq = nvec+ndv+nfv+nsv+ngv+nqv
+  allocate (vec(otq+ntv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
   allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
   AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
   ngrav = 0; nnrav = 0
@@ -888,6 +954,8 @@ contains
            if (gr_vector) call pigs_check(grv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_grv_accumulate')
            ! and into the sums of the vector F(q,tau)
            if (fq_vector) call pigs_check(fqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqv_accumulate')
+           ! and every slice into the imaginary-time profiles
+           if (tau_profile) call pigs_check(tau_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_tau_accumulate')
         end if
 
      end do   ! istep
@@ -917,6 +985,7 @@ contains
      if (sq_vector) call pigs_check(sqv_read(ctx,sq_raw,sq_smp,sq_reset),'pigs_sqv_read')
      if (gr_vector) call pigs_check(grv_read(ctx,gv_vec,gv_rad,gv_smp,gv_reset),'pigs_grv_read')
      if (fq_vector) call pigs_check(fqv_read(ctx,fx_raw,fx_smp,fx_reset),'pigs_fqv_read')
+     if (tau_profile) call pigs_check(tau_read(ctx,tq_raw,tq_smp,tq_reset),'pigs_tau_read')
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -978,6 +1047,19 @@ contains
                    & +reshape(fxb,[nqv-1])
               vec(nvec+ndv+nfv+nsv+ngv+nqv) = vec(nvec+ndv+nfv+nsv+ngv+nqv)+1.d0
            end if
+           if (tau_profile) then
+              call normalize_tau(dim,Np,Nb,dt,int(tq_smp(w),8),tq_raw(:,:,w),tqb)
+              AvTq(:,:,w) = AvTq(:,:,w)+tqb; AvTq2(:,:,w) = AvTq2(:,:,w)+tqb*tqb
+              do ib=1,2*Nb+1
+                 vec(otq+4*ib-3:otq+4*ib) = vec(otq+4*ib-3:otq+4*ib)+tqb(:,ib)
+              end do
+              vec(otq+ntv) = vec(otq+ntv)+1.d0
+              if (.not. trap) then
+                 ! W/Np over the window, the block's Kin/N of e_vpi.out, P = density/dim (2 Kin/N - W/N)
+                 wwin = sum(tqb(3,Nb+1-tau_window:Nb+1+tau_window))/real(2*tau_window+1,8)
+                 write (up(w),'(20g20.10e3)') real(iblock),wwin,BE(2,w)/Np,density/real(dim,8)*(2.d0*(BE(2,w)/Np)-wwin)
+              end if
+           end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
            write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -1001,7 +1083,7 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec+ndv+nfv+nsv+ngv+nqv,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(otq+ntv,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
      ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
      if (ish==1 .and. NWtot>1) then
@@ -1069,6 +1151,20 @@ contains
               end do
               AvFxAll = AvFxAll+fxb; AvFx2All = AvFx2All+fxb*fxb
               AvFsAll = AvFsAll+fxs; AvFs2All = AvFs2All+fxs*fxs
+           end if
+        end if
+     end if
+     if (ish==1 .and. NWtot>1 .and. tau_profile) then      ! walker average of the block's imaginary-time profiles
+        ntauall = nint(vec(otq+ntv))
+        if (ntauall>0) then
+           ntauav = ntauav+1
+           do ib=1,2*Nb+1
+              tmpt(:,ib) = vec(otq+4*ib-3:otq+4*ib)/ntauall
+           end do
+           AvTqAll = AvTqAll+tmpt; AvTq2All = AvTq2All+tmpt*tmpt
+           if (.not. trap .and. ndall>0) then
+              wwin = sum(tmpt(3,Nb+1-tau_window:Nb+1+tau_window))/real(2*tau_window+1,8)
+              write (upav,'(20g20.10e3)') real(iblock),wwin,mE(2)/ndall,density/real(dim,8)*(2.d0*(mE(2)/ndall)-wwin)
            end if
         end if
      end if
@@ -1174,6 +1270,10 @@ contains
         call write_fqvec('fqvec_vpi'//trim(suffix)//'.out',ep,fqv_ntau,dt,nfx,fx_n,diag_bl(w),AvFx(:,:,w),AvFx2(:,:,w))
         call write_fqshell('fqsh_vpi'//trim(suffix)//'.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,diag_bl(w),AvFs(:,:,w),AvFs2(:,:,w))
      end if
+     if (tau_profile) then
+        call write_tau('tau_vpi'//trim(suffix)//'.out',Nb,dt,diag_bl(w),AvTq(:,:,w),AvTq2(:,:,w))
+        if (.not. trap) close (up(w))
+     end if
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
@@ -1199,6 +1299,10 @@ contains
      if (fq_vector) then
         call write_fqvec('fqvec_vpi.out',ep,fqv_ntau,dt,nfx,fx_n,nfxav,AvFxAll,AvFx2All)
         call write_fqshell('fqsh_vpi.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,nfxav,AvFsAll,AvFs2All)
+     end if
+     if (tau_profile) then
+        call write_tau('tau_vpi.out',Nb,dt,ntauav,AvTqAll,AvTq2All)
+        if (.not. trap) close (upav)
      end if
   end if
 
@@ -1232,5 +1336,13 @@ contains
 
   call sampler_free(s)
   end subroutine run_shard
+
+  ! first line of press_vpi*.out
+  subroutine press_header(u)
+    integer, intent(in) :: u
+    write (u,'(a,i0,a,i0,a)') '# block, W/Np = <sum r dv/dr>/Np over the slices Nb-',tau_window,'..Nb+',tau_window, &
+         & ' (W stops at rcut: pairs beyond it are not counted, no tail correction), Kin/Np as e_vpi.out, '// &
+         & 'P = density/dim (2 Kin/Np - W/Np)'
+  end subroutine press_header
 
 end program pigs_vpi

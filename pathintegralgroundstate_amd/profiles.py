@@ -1,6 +1,6 @@
 """Normalisation of the accumulators that PigsContext.density_read (trapped systems, pigs_density_*),
 PigsContext.fqt_read, PigsContext.sqv_read, PigsContext.fqv_read and PigsContext.grv_read (periodic systems, pigs_fqt_*,
-pigs_sqv_*, pigs_fqv_*, pigs_grv_*) return.
+pigs_sqv_*, pigs_fqv_*, pigs_grv_*) and PigsContext.tau_read (both, pigs_tau_*) return.
 
 Trapped-system profiles:
 
@@ -33,6 +33,12 @@ the partner -d is added by index reflection, and
 which is 1 - 1/Np for an ideal gas.  radial[j] counts the same pairs by distance (bin width rbin, inside the cutoff):
   g(r_j) = 2 * radial[j] / (S * (2*window + 1) * Np * density * kn * ((r_j + rbin/2)^dim - (r_j - rbin/2)^dim))
 with kn the volume of the unit ball: the reference's normalisation (sample_mod.f90, Normalize / NormAvGr).
+
+Imaginary-time profiles (normalize_tau, pressure_virial): raw[b] holds, per sample, Vpair, Vext, W = sum r v'(r) and
+D2 = sum_i |x_i(b) - x_i(b+1)|^2 of slice b = 0..2Nb, so per particle
+  vpair, vext, w = raw[..., 0..2] / (S * Np),   klink[b] = dim/(2*dt) - D2[b] / (2*dt**2 * Np * S)  for the 2Nb links,
+at tau_b = (b - Nb)*dt; the plateau of vpair + vext around tau = 0 is the converged part of the path.  The pressure of a
+periodic system is P = density/dim * (2*K/N - W/N).
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -171,3 +177,28 @@ def normalize_grv(counts, Np, window, density, Lbox, rbin, dim):
         g_r = 2.0 * rad / (nid * (S.reshape(S.shape + (1,)) * ns * float(Np)))
     x = [-0.5 * L[k] + (np.arange(Nbin) + 0.5) * b[k] for k in range(dim)]
     return {"g_vec": g_vec, "x": x, "g_r": g_r, "r": r}
+
+
+def normalize_tau(raw, Np, dim, dt):
+    """raw: the dict of tau_read (Q [W, 2Nb+1, 4] raw sums, samples [W]) or one walker's slice of it.
+    Returns a dict: vpair, vext, w (per particle, [.., 2Nb+1]), klink ([.., 2Nb]: the kinetic estimator of the link
+    between slices b and b+1, dim/(2*dt) - D2/(2*dt**2 * Np * samples)) and tau [2Nb+1] = (b - Nb)*dt.  A walker without
+    samples gives NaN."""
+    Q = np.asarray(raw["Q"], dtype=np.float64)
+    S = np.asarray(raw["samples"], dtype=np.float64)
+    M = Q.shape[-2]
+    if Q.shape[-1] != 4 or M < 3 or M % 2 == 0:
+        raise ValueError("Q must be [.., 2Nb+1, 4]")
+    Nb = (M - 1) // 2
+    Sb = S.reshape(S.shape + (1,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per = Q[..., :3] / (Sb[..., None] * float(Np))
+        klink = dim / (2.0 * dt) - Q[..., :M - 1, 3] / (2.0 * dt * dt * float(Np) * Sb)
+    tau = (np.arange(M, dtype=np.float64) - Nb) * dt
+    return {"vpair": per[..., 0], "vext": per[..., 1], "w": per[..., 2], "klink": klink, "tau": tau}
+
+
+def pressure_virial(kin_per_particle, w_per_particle, density, dim):
+    """Virial pressure P = density/dim * (2*K/N - W/N) of a periodic system, with W/N = <sum_{i<j} r v'(r)>/N as
+    normalize_tau's `w` gives it.  Pairs beyond rcut are not in W and no tail correction is made."""
+    return density / dim * (2.0 * np.asarray(kin_per_particle, np.float64) - np.asarray(w_per_particle, np.float64))
