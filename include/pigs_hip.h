@@ -394,6 +394,58 @@ int pigs_fqv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_fqv_init. */
 int pigs_fqv_read(pigs_ctx *ctx, double *F, int64_t *samples, const int32_t *reset);
 
+/* ---- self (incoherent) part of F(q,tau) and the imaginary-time displacement of a PERIODIC system (new: pigs_fqt_* and
+ * pigs_fqv_* give the coherent <rho_q(tau) rho_-q(0)>; this follows ONE particle along its worldline, which needs particle
+ * labels that are continuous in imaginary time: the resident paths have them, pigs_swap_tails keeps them) ---------------
+ * The vectors, the window and the lags are exactly those of pigs_fqv_*: the half-space integer vectors |n_k| <= nmax in
+ * the enumeration order of pigs_sqv_vectors (pigs_fqs_vectors hands the same list out), the slices Nb-window .. Nb+window
+ * (0 <= window <= Nb), the lags l = 0 .. Ntau (0 <= Ntau <= 2 window).  Per listed walker w and accumulate call the device
+ * adds, with n_pairs(l) = 2 window + 1 - l slice pairs (a, a+l), a = Nb-window .. Nb+window-l,
+ *   F[w][l][iqv] += sum over the particles i and the pairs a of c_i(a) c_i(a+l) + s_i(a) s_i(a+l)
+ *   c_i(a) + i s_i(a) = exp(i q . x_i(a))
+ *   D[w][l][0]   += sum over i and a of r2
+ *   D[w][l][1]   += sum over i and a of r2 * r2
+ * and 1 to samples[w].
+ * - Phasors.  exp(i q.x) is the product of per-axis phasors exp(i real(m) (2 pi/Lbox(k)) x_k), m = |n_k| (conjugated for
+ *   n_k < 0), each from one sincos of the phase (double)(float)m * (2 pi/Lbox[k]) * x_k as pigs_sqv_* rounds it; the axes
+ *   are multiplied in its order, (e_1 e_2) e_3, each complex product as (ar br - ai bi, ar bi + ai br), nothing fused.  A
+ *   reciprocal vector of the box does not notice a wrap of x, so F needs no unfolded path.
+ * - Displacement.  d_k = x_k(i, a+l) - x_k(i, a), folded ONCE as pbc_mod.f90:40-41 does (the two compares, each against
+ *   LboxHalf); r2 is the sum of the squares, left to right, nothing fused.  Lag 0 adds exactly 0.0.  THIS IS THE
+ *   DISPLACEMENT ONLY WHILE |d_k| STAYS BELOW Lbox[k]/2, which holds for the imaginary-time spans in use (a particle
+ *   diffuses ~ sqrt(2 lambda tau) << L/2 there); the library does not judge it.
+ * - Summation order of F.  One running sum per element (w, l, iqv) and call starts at 0.0 and takes the terms
+ *   t = c c' + s s' (two products and their sum, not fused) as sum = sum + t with the particles i ascending and, per
+ *   particle, a ascending; the call's sum is then added to the accumulator.
+ * - Summation order of D.  With B = min(256, Np rounded up to a multiple of 64) lanes, lane j takes the particles j,
+ *   j + B, .. in ascending order and, per particle, a ascending: s1 = s1 + r2, s2 = s2 + r2 * r2.  The 64 lanes of a wave
+ *   are added by a butterfly (partner lane ^ 32, 16, .., 1), the waves in wave order from 0.0, then acc += value.
+ * No floating-point atomics: the same worldline gives the same bits whatever the walker list, its order, the launch
+ * split or the number of walkers of the context.  The estimators are the caller's divisions
+ *   F_s(q; tau_l)      = F / (samples * n_pairs(l) * Np)                          (profiles.normalize_fqs)
+ *   <dr^2>(tau_l)      = D[..][0] / (samples * n_pairs(l) * Np)                   (profiles.normalize_msd)
+ *   alpha_2(tau_l)     = dim <dr^4> / ((dim + 2) <dr^2>^2) - 1,  <dr^4> from D[..][1]   (the non-Gaussian parameter)
+ * F_s(q; 0) = 1 and <dr^2>(0) = 0.  The window must stay inside the converged part of the path; the library does not
+ * judge it.
+ *
+ * pigs_fqs_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context;
+ * PIGS_ERR_ARG for nmax < 1, nmax > 16 in 3D, nmax > 64 in 1D or 2D, window < 0, window > Nb, Ntau < 0, Ntau > 2 window,
+ * accumulators larger than 2 GiB in total, more than 3072 lags, or a window whose phasors do not fit the kernel's 64 KiB
+ * of LDS: 16 (2 window + 1) (dim (nmax + 1) + 1) bytes at the least. */
+int pigs_fqs_init(pigs_ctx *ctx, int32_t nmax, int32_t Ntau, int32_t window);
+/* Nq, and the vectors n[Nq][dim] in the enumeration order of pigs_sqv_vectors.  PIGS_ERR_ARG before pigs_fqs_init. */
+int pigs_fqs_count(pigs_ctx *ctx, int64_t *Nq);
+int pigs_fqs_vectors(pigs_ctx *ctx, int32_t *n);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches; there is no
+ * scratch.  PIGS_ERR_ARG before pigs_fqs_init, for n < 0 or for a walker out of range. */
+int pigs_fqs_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' raw sums F[n_walkers][Ntau+1][Nq] (iqv fastest), D[n_walkers][Ntau+1][2] and samples[n_walkers]; then
+ * zeroes those of the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before
+ * pigs_fqs_init. */
+int pigs_fqs_read(pigs_ctx *ctx, double *F, double *D, int64_t *samples, const int32_t *reset);
+
 /* ---- pair distribution of a PERIODIC system on the vector grid, over a slice window (new: the only g(r) of a periodic
  * system was pigs_structure_batch's radial histogram of one slice; this is the real-space partner of pigs_sqv_*) --------
  * Two integer histograms per walker, accumulated on the device: g(r) on the Cartesian grid of the minimum-image cell and

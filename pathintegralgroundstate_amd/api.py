@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "pigs_fqt_init", "pigs_fqt_accumulate", "pigs_fqt_read",
     "pigs_sqv_init", "pigs_sqv_count", "pigs_sqv_vectors", "pigs_sqv_accumulate", "pigs_sqv_read",
     "pigs_fqv_init", "pigs_fqv_count", "pigs_fqv_vectors", "pigs_fqv_accumulate", "pigs_fqv_read",
+    "pigs_fqs_init", "pigs_fqs_count", "pigs_fqs_vectors", "pigs_fqs_accumulate", "pigs_fqs_read",
     "pigs_grv_init", "pigs_grv_accumulate", "pigs_grv_read",
     "pigs_tau_init", "pigs_tau_accumulate", "pigs_tau_read",
 ]
@@ -147,6 +148,11 @@ def load_library(path=LIB_PATH):
     L.pigs_fqv_vectors.argtypes = [vp, _ip]
     L.pigs_fqv_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_fqv_read.argtypes = [vp, _dp, _lp, _ip]
+    L.pigs_fqs_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.pigs_fqs_count.argtypes = [vp, _lp]
+    L.pigs_fqs_vectors.argtypes = [vp, _ip]
+    L.pigs_fqs_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_fqs_read.argtypes = [vp, _dp, _dp, _lp, _ip]
     L.pigs_grv_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.pigs_grv_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_grv_read.argtypes = [vp, _lp, _lp, _lp, _ip]
@@ -625,6 +631,53 @@ class PigsContext:
             mask = _i(keep)
         _chk(self.L, self.L.pigs_fqv_read(self.h, _d(out["F"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
              "pigs_fqv_read")
+        return out
+
+    # ---- self part of F(q,tau) and the imaginary-time displacement (pigs_fqs_*: raw sums per walker, lag and vector)
+    def fqs_init(self, nmax, Ntau=0, window=0):
+        """Allocate and zero the sums of the self part F_s(q, tau_l) and of the displacement |x_i(tau_l) - x_i(0)|^2,
+        l = 0..Ntau, over the slices Nb-window..Nb+window for the vectors of sqv_init(nmax) (fqs_vectors lists them).
+        Calling it again resizes and zeroes."""
+        _chk(self.L, self.L.pigs_fqs_init(self.h, int(nmax), int(Ntau), int(window)), "pigs_fqs_init")
+        nq = C.c_int64(0)
+        _chk(self.L, self.L.pigs_fqs_count(self.h, C.byref(nq)), "pigs_fqs_count")
+        self._fqs_shape = (int(Ntau) + 1, int(nq.value))
+
+    def fqs_vectors(self):
+        """The stored vectors n [Nq, dim] (int32): those of sqv_vectors, in the same order."""
+        shape = getattr(self, "_fqs_shape", None)
+        if shape is None:
+            raise PigsError("fqs_vectors: fqs_init first")
+        n = np.zeros((shape[1], self.cfg.dim), np.int32)
+        _chk(self.L, self.L.pigs_fqs_vectors(self.h, _i(n)), "pigs_fqs_vectors")
+        return n
+
+    def fqs_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        if walkers is None:
+            _chk(self.L, self.L.pigs_fqs_accumulate(self.h, self.n_walkers, None), "pigs_fqs_accumulate")
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, self.L.pigs_fqs_accumulate(self.h, wl.size, _i(wl)), "pigs_fqs_accumulate")
+
+    def fqs_read(self, reset=None):
+        """dict: F, the raw sums [W, Ntau+1, Nq] (profiles.normalize_fqs divides them), D, the raw sums of r^2 and r^4
+        [W, Ntau+1, 2] (profiles.normalize_msd), and samples [W] (int64).
+        reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        shape = getattr(self, "_fqs_shape", None)
+        if shape is None:
+            raise PigsError("fqs_read: fqs_init first")
+        W = self.n_walkers
+        out = {"F": np.zeros((W,) + shape), "D": np.zeros((W, shape[0], 2)), "samples": np.zeros(W, np.int64)}
+        if reset is None or reset is False:
+            mask = None
+        else:
+            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
+            if keep.size != W:
+                raise ValueError("reset mask needs one entry per walker")
+            mask = _i(keep)
+        _chk(self.L, self.L.pigs_fqs_read(self.h, _d(out["F"]), _d(out["D"]),
+                                          out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask), "pigs_fqs_read")
         return out
 
     # ---- pair distribution on the vector grid over a slice window (pigs_grv_*: 64-bit counts per walker)

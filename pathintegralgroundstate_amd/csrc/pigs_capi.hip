@@ -224,6 +224,15 @@ struct pigs_ctx {
     int64_t     fqv_nq = 0;
     std::vector<int64_t> fqv_mark;          // per walker: the last launch (fqv_launch) that listed it
     int64_t     fqv_launch = 0;
+    // self part of F(q,tau) and the imaginary-time displacement (pigs_fqs_*): raw sums F [walker][l][iqv] and
+    // D [walker][l][2], the samples per walker; no scratch (pigs_fqs.hip keeps the phasors in LDS)
+    DevBuf<double> d_fqs_acc, d_fqs_dsp;
+    DevBuf<unsigned long long> d_fqs_samples;
+    int         fqs_nmax = 0;               // 0: pigs_fqs_init not called yet
+    int         fqs_ntau = 0, fqs_window = 0;
+    int64_t     fqs_nq = 0;
+    std::vector<int64_t> fqs_mark;          // per walker: the last launch (fqs_launch) that listed it
+    int64_t     fqs_launch = 0;
     // pair distribution on the vector grid over a slice window (pigs_grv_*): per-walker 64-bit counts, walker-major
     DevBuf<unsigned long long> d_grv_vec, d_grv_radial, d_grv_samples;
     int         grv_nbin = 0;               // 0: pigs_grv_init not called yet
@@ -1783,6 +1792,110 @@ int pigs_fqv_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset
             while (e < W && reset[e]) ++e;
             HIPCHK(hipMemsetAsync(c->d_fqv_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
             HIPCHK(hipMemsetAsync(c->d_fqv_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
+            w = e;
+        }
+    }
+    SYNC_CHECKED(c);
+    return PIGS_OK;
+}
+
+// ---- self part of F(q,tau) and the imaginary-time displacement of a periodic system ---------------
+// Raw sums per walker, lag and vector, and per walker and lag (pigs_fqs.hip): the vectors, window and lags of pigs_fqv_*.
+int pigs_fqs_init(pigs_ctx *c, int32_t nmax, int32_t Ntau, int32_t window)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the self part of F(q,tau) is defined for periodic systems only (the q grid is the box's)");
+    if (nmax < 1 || nmax > (c->P.dim == 3 ? 16 : 64) || window < 0 || window > c->P.Nb || Ntau < 0 || Ntau > 2 * window)
+        return fail(PIGS_ERR_ARG, "pigs_fqs_init: nmax=%d (1..%d in %dD) Ntau=%d (0..2 window) window=%d (0..Nb=%d)", nmax,
+                    c->P.dim == 3 ? 16 : 64, c->P.dim, Ntau, window, c->P.Nb);
+    if (!fqs_shape(c->P.dim, nmax, window, Ntau).width)
+        return fail(PIGS_ERR_ARG, "pigs_fqs_init: the phasors of %d window slices (nmax=%d, %dD) pass the %zu bytes of LDS, or %d lags"
+                    " the %d a workgroup takes", 2 * window + 1, nmax, c->P.dim, kFqsLdsBudget, Ntau + 1, kFqsThreads * kFqsLags);
+    const SqvShape sh = sqv_shape(c->P.dim, nmax);
+    const size_t W = (size_t)c->n_walkers, per = (size_t)(Ntau + 1) * (size_t)sh.Nq, perd = (size_t)(Ntau + 1) * 2;
+    if ((double)W * ((double)per + (double)perd + 1.0) * 8.0 > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_fqs_init: %zu walkers x (%d x (%lld + 2) + 1) sums pass 2 GiB", W, Ntau + 1, (long long)sh.Nq);
+    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
+    c->fqs_nmax = 0;
+    HIPCHK(c->d_fqs_acc.alloc(W * per));
+    HIPCHK(c->d_fqs_dsp.alloc(W * perd));
+    HIPCHK(c->d_fqs_samples.alloc(W));
+    HIPCHK(hipMemsetAsync(c->d_fqs_acc.p, 0, W * per * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_fqs_dsp.p, 0, W * perd * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_fqs_samples.p, 0, W * sizeof(unsigned long long), c->stream));
+    SYNC_CHECKED(c);
+    c->fqs_nmax = nmax;
+    c->fqs_ntau = Ntau;
+    c->fqs_window = window;
+    c->fqs_nq = sh.Nq;
+    return PIGS_OK;
+}
+
+int pigs_fqs_count(pigs_ctx *c, int64_t *Nq)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->fqs_nmax) return fail(PIGS_ERR_ARG, "pigs_fqs_init first");
+    if (!Nq) return fail(PIGS_ERR_ARG, "null output");
+    *Nq = c->fqs_nq;
+    return PIGS_OK;
+}
+
+int pigs_fqs_vectors(pigs_ctx *c, int32_t *n)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->fqs_nmax) return fail(PIGS_ERR_ARG, "pigs_fqs_init first");
+    if (!n) return fail(PIGS_ERR_ARG, "null output");
+    sqv_enumerate(c->P.dim, c->fqs_nmax, c->fqs_nq, n);
+    return PIGS_OK;
+}
+
+int pigs_fqs_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->fqs_nmax) return fail(PIGS_ERR_ARG, "pigs_fqs_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // As pigs_fqv_accumulate: the list goes by value in the kernel arguments, and a launch ends where the list is full
+    // or a walker would appear in it a second time; the stream orders the launches.
+    if (walkers) c->fqs_mark.resize(c->n_walkers, 0);
+    for (int i0 = 0; i0 < n;) {
+        const int64_t launch = ++c->fqs_launch;
+        FqsList L{};
+        int m = 0;
+        while (i0 + m < n && m < kFqsListMax && !(walkers && c->fqs_mark[sw[i0 + m]] == launch)) {
+            if (walkers) c->fqs_mark[sw[i0 + m]] = launch;
+            L.w[m] = sw[i0 + m];
+            ++m;
+        }
+        HIPCHK(launch_fqs(c->P, c->d_paths.p, m, L, c->fqs_window, c->fqs_ntau, c->fqs_nmax, c->d_fqs_acc.p, c->d_fqs_dsp.p,
+                          c->d_fqs_samples.p, c->stream));
+        i0 += m;
+    }
+    return PIGS_OK;
+}
+
+int pigs_fqs_read(pigs_ctx *c, double *F, double *D, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->fqs_nmax) return fail(PIGS_ERR_ARG, "pigs_fqs_init first");
+    if (!F || !D || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t W = (size_t)c->n_walkers, per = (size_t)(c->fqs_ntau + 1) * (size_t)c->fqs_nq, perd = (size_t)(c->fqs_ntau + 1) * 2;
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(F, c->d_fqs_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(D, c->d_fqs_dsp.p, W * perd * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(samples, c->d_fqs_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (reset) {
+        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
+        for (size_t w = 0; w < W;) {
+            if (!reset[w]) { ++w; continue; }
+            size_t e = w;
+            while (e < W && reset[e]) ++e;
+            HIPCHK(hipMemsetAsync(c->d_fqs_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
+            HIPCHK(hipMemsetAsync(c->d_fqs_dsp.p + w * perd, 0, (e - w) * perd * sizeof(double), s));
+            HIPCHK(hipMemsetAsync(c->d_fqs_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
             w = e;
         }
     }

@@ -100,6 +100,24 @@ int fqv_width(int ns);
 hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const FqvList &list, int window, int Ntau, int nmax,
                       double *rho, double *acc, unsigned long long *samples, hipStream_t st);
 
+// pigs_fqs.hip: the self part of F(q,tau) on the vectors of pigs_sqv_* and the imaginary-time displacement
+// (pigs_fqs_accumulate).  k_fqs_msd adds the sums of r2 and r2^2 of the lags 0..Ntau to dsp ([walker][l][2]); k_fqs loops
+// over the particles with their phasors in LDS (the per-axis table of all window slices, then a tile of fqs_shape().width
+// vectors x ns slices) and the lag sums in registers, at most kFqsLags lags per thread, and adds them to acc
+// ([walker][l][iqv]) and 1 to samples.  One thread owns an accumulator element per launch: the caller never lists a
+// walker twice in ONE launch.  fqs_shape gives the largest power of two <= kFqsWidthMax whose table and tile fit
+// kFqsLdsBudget and whose kFqsThreads / width lag groups cover Ntau + 1 lags (width 0: none, which pigs_fqs_init refuses).
+constexpr int kFqsListMax = 256;
+constexpr int kFqsThreads = 256;
+constexpr int kFqsWidthMax = 64;                 // one wave of lanes over consecutive vectors
+constexpr int kFqsLags = 12;                     // lag sums a thread keeps in registers across the particle loop
+constexpr size_t kFqsLdsBudget = 64 * 1024;      // 16 bytes per (slice, axis, m) and per (slice, vector)
+struct FqsList { int32_t w[kFqsListMax]; };
+struct FqsShape { int width; size_t lds; };
+FqsShape fqs_shape(int dim, int nmax, int window, int Ntau);
+hipError_t launch_fqs(const DevParams &P, const double *paths, int n, const FqsList &list, int window, int Ntau, int nmax,
+                      double *acc, double *dsp, unsigned long long *samples, hipStream_t st);
+
 // pigs_grv.hip: the pair distribution of a periodic system on the vector grid and radially, over the window slices
 // Nb-window .. Nb+window (pigs_grv_accumulate): 64-bit counts per walker, vec [walker][Nbin^dim] (x fastest) and radial
 // [walker][Nr].  The list travels in the kernel arguments, at most kGrvListMax walkers per launch; a walker may be listed

@@ -531,6 +531,18 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_fqv_read_t
 
+     ! self part of F(q,tau) and imaginary-time displacement (include/pigs_hip.h, pigs_fqs_*): looked up at run time, see
+     ! fqs_bind; _init has the signature of pigs_fqv_init, _count, _vectors and _accumulate those of the pigs_sqv_* ones
+     function pigs_fqs_read_t(ctx,F,D,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: F(*)          ! raw sums (Nq,0:Ntau,n_walkers)
+       real(c_double)                 :: D(*)          ! raw sums of r^2 and r^4 (2,0:Ntau,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_fqs_read_t
+
      ! imaginary-time profiles (include/pigs_hip.h, pigs_tau_*): looked up at run time, see tau_bind; _accumulate has the
      ! signature of pigs_fqt_accumulate
      function pigs_tau_init_t(ctx) bind(C) result(rc)
@@ -577,6 +589,13 @@ module pigs_capi
   procedure(pigs_sqv_vectors_t), pointer    :: fqv_vectors => null()
   procedure(pigs_sqv_accumulate_t), pointer :: fqv_accumulate => null()
   procedure(pigs_fqv_read_t), pointer       :: fqv_read => null()
+
+  ! bound by fqs_bind (null until then)
+  procedure(pigs_fqv_init_t), pointer       :: fqs_init => null()
+  procedure(pigs_sqv_count_t), pointer      :: fqs_count => null()
+  procedure(pigs_sqv_vectors_t), pointer    :: fqs_vectors => null()
+  procedure(pigs_sqv_accumulate_t), pointer :: fqs_accumulate => null()
+  procedure(pigs_fqs_read_t), pointer       :: fqs_read => null()
 
   ! bound by tau_bind (null until then)
   procedure(pigs_tau_init_t), pointer       :: tau_init => null()
@@ -687,6 +706,28 @@ contains
     call c_f_procpointer(f(4),fqv_accumulate)
     call c_f_procpointer(f(5),fqv_read)
   end function fqv_bind
+
+  ! The entry points of the self part of F(q,tau), found like the vector-F(q,tau) ones: at run time, only when a run asks
+  ! for them.
+  logical function fqs_bind()
+    type(c_funptr) :: f(5)
+    integer :: i
+    f(1) = c_dlsym(c_null_ptr,'pigs_fqs_init'//c_null_char)
+    f(2) = c_dlsym(c_null_ptr,'pigs_fqs_count'//c_null_char)
+    f(3) = c_dlsym(c_null_ptr,'pigs_fqs_vectors'//c_null_char)
+    f(4) = c_dlsym(c_null_ptr,'pigs_fqs_accumulate'//c_null_char)
+    f(5) = c_dlsym(c_null_ptr,'pigs_fqs_read'//c_null_char)
+    fqs_bind = .true.
+    do i=1,5
+       fqs_bind = fqs_bind .and. c_associated(f(i))
+    end do
+    if (.not. fqs_bind) return
+    call c_f_procpointer(f(1),fqs_init)
+    call c_f_procpointer(f(2),fqs_count)
+    call c_f_procpointer(f(3),fqs_vectors)
+    call c_f_procpointer(f(4),fqs_accumulate)
+    call c_f_procpointer(f(5),fqs_read)
+  end function fqs_bind
 
   ! The imaginary-time-profile entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
   logical function tau_bind()

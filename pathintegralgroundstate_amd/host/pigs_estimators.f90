@@ -15,6 +15,7 @@ module pigs_estimators
   public :: normalize_fqt, write_fqt
   public :: normalize_sqv, sqv_shells, sqv_shell_means, write_sqvec, write_sqshell
   public :: normalize_fqv, write_fqvec, write_fqshell
+  public :: normalize_msd, write_msd
   public :: normalize_grv, write_grvec
   public :: normalize_tau, write_tau
 
@@ -491,6 +492,40 @@ contains
     end do
     close (u)
   end subroutine write_fqshell
+
+  ! ---- imaginary-time displacement (raw sums D of pigs_fqs_read: r^2 and r^4 of the once-folded x_i(a+l) - x_i(a) over
+  ! the pairs of the window slices and the particles) -> one walker's block values with S samples: m(1,l) = <dr^2>(tau_l),
+  ! m(2,l) = <dr^4>(tau_l), each raw/(S n_pairs(l) Np).  The self part F_s of the same call goes through normalize_fqv.
+  subroutine normalize_msd(Np,Ntau,window,S,raw,m)
+    integer, intent(in)    :: Np,Ntau,window
+    integer(8), intent(in) :: S
+    real(8), intent(in)    :: raw(2,0:Ntau)
+    real(8), intent(out)   :: m(2,0:Ntau)
+    integer :: l
+    do l=0,Ntau
+       m(:,l) = raw(:,l)/(real(S,8)*real(2*window+1-l,8)*real(Np,8))
+    end do
+  end subroutine normalize_msd
+
+  ! msd_vpi.out: one line per lag: l, tau_l = l dt, <dr^2>, its error over the n blocks, and the non-Gaussian parameter
+  ! alpha_2 = dim <dr^4> / ((dim + 2) <dr^2>^2) - 1 of the averaged moments (0 where <dr^2> is 0: lag 0)
+  subroutine write_msd(fname,dim,Ntau,dt,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: dim,Ntau,n
+    real(8), intent(in)    :: dt
+    real(8), intent(inout) :: av(2,0:Ntau),av2(2,0:Ntau)
+    integer :: l,u
+    real(8) :: a2
+    open (newunit=u,file=fname)
+    do l=0,Ntau
+       av(:,l)  = av(:,l)/real(n)
+       av2(:,l) = av2(:,l)/real(n)
+       a2 = 0.d0
+       if (av(1,l)>0.d0) a2 = real(dim,8)*av(2,l)/(real(dim+2,8)*av(1,l)*av(1,l))-1.d0
+       write (u,'(i6,4g20.10e3)') l,real(l,8)*dt,av(1,l),variance(n,av(1,l),av2(1,l)),a2
+    end do
+    close (u)
+  end subroutine write_msd
 
   ! ---- pair distribution on the vector grid over a slice window (counts of pigs_grv_read: window slices
   ! Nb-window..Nb+window, Ng bins per axis over the minimum-image cell, nv = Ng**dim, x fastest; radial counts on the run's

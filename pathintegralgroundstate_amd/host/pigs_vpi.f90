@@ -29,6 +29,12 @@
 ! fqv_nmax (default 8), for the lags l = 0..fqv_ntau (default 0) between the slices Nb-fqv_window..Nb+fqv_window (default
 ! ceiling(fqv_ntau/2)), accumulated on the GPU -- fqvec_vpi.out, one line per (lag, vector), and fqsh_vpi.out, one line
 ! per (lag, |q| shell))
+! (fq_self = T, periodic systems only: the self (incoherent) part F_s(q,tau_l) on the vectors |n_k| <= fqs_nmax (default 8)
+! and the imaginary-time mean-square displacement <|x_i(tau_l) - x_i(0)|^2>, for the lags l = 0..fqs_ntau (default 0)
+! between the slices Nb-fqs_window..Nb+fqs_window (default ceiling(fqs_ntau/2)), accumulated on the GPU for the
+! diagonal-sector walkers of a step -- fqself_vpi.out, one line per (lag, vector), fqssh_vpi.out, one line per (lag, |q|
+! shell), and msd_vpi.out, one line per lag: l, tau_l, <dr^2>, error, alpha_2; the displacement is folded once, so it is
+! the true one while it stays below half the box)
 ! (tau_profile = T, periodic and trapped systems: the imaginary-time profiles of every slice b = 0..2Nb -- pair and external
 ! potential energy, the virial W = sum r v'(r) and the kinetic estimator of every link, per particle, accumulated on the
 ! GPU -- tau_vpi.out; the plateau of V(tau) around slice Nb is the converged part of the path, in which the windows above
@@ -72,6 +78,8 @@ program pigs_vpi
   integer           :: gr_nbin,gr_window
   logical           :: fq_vector
   integer           :: fqv_nmax,fqv_ntau,fqv_window
+  logical           :: fq_self
+  integer           :: fqs_nmax,fqs_ntau,fqs_window
   logical           :: tau_profile
   integer           :: tau_window
   logical           :: sampler_auto
@@ -89,7 +97,8 @@ program pigs_vpi
        &             fq_tau,fq_ntau,fq_window,sq_vector,sq_nmax,sq_window, &
        &             gr_vector,gr_nbin,gr_window, &
        &             fq_vector,fqv_nmax,fqv_ntau,fqv_window, &
-       &             tau_profile,tau_window
+       &             tau_profile,tau_window, &
+       &             fq_self,fqs_nmax,fqs_ntau,fqs_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -117,6 +126,7 @@ program pigs_vpi
   gr_vector = .false.; gr_nbin = 32; gr_window = 0
   fq_vector = .false.; fqv_nmax = 8; fqv_ntau = 0; fqv_window = -1
   tau_profile = .false.; tau_window = 0
+  fq_self = .false.; fqs_nmax = 8; fqs_ntau = 0; fqs_window = -1
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -241,6 +251,33 @@ program pigs_vpi
      if (.not. fqv_bind()) then
         write (0,'(a)') ' pigs_vpi: fq_vector = T: this backend does not export pigs_fqv_init / _count / _vectors /'// &
              & ' _accumulate / _read (the vector F(q,tau) runs on libpigs_hip.so only)'
+        stop 2
+     end if
+  end if
+  if (fq_self) then
+     ! self part of F(q,tau) and imaginary-time displacement of a periodic system; entry points resolved at run time as above
+     if (trap) then
+        write (0,'(a)') ' pigs_vpi: fq_self = T needs a periodic system (trap = F): its q grid is that of the box'
+        stop 2
+     end if
+     if (fqs_nmax<1 .or. fqs_nmax>merge(16,64,dim==3)) then
+        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: fq_self = T: fqs_nmax = ',fqs_nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
+             & ' (dim = ',dim,')'
+        stop 2
+     end if
+     if (fqs_window<0) fqs_window = (max(fqs_ntau,0)+1)/2       ! ceiling(fqs_ntau/2)
+     if (fqs_ntau<0 .or. fqs_ntau>2*fqs_window) then
+        write (0,'(a,i0,a,i0,a)') ' pigs_vpi: fq_self = T: fqs_ntau = ',fqs_ntau,' must lie in 0 .. 2*fqs_window = ',2*fqs_window, &
+             & ' (lags between the slices Nb-fqs_window .. Nb+fqs_window)'
+        stop 2
+     end if
+     if (fqs_window>Nb) then
+        write (0,'(a,i0,a,i0)') ' pigs_vpi: fq_self = T: fqs_window = ',fqs_window,' must not exceed Nb = ',Nb
+        stop 2
+     end if
+     if (.not. fqs_bind()) then
+        write (0,'(a)') ' pigs_vpi: fq_self = T: this backend does not export pigs_fqs_init / _count / _vectors /'// &
+             & ' _accumulate / _read (the self part of F(q,tau) runs on libpigs_hip.so only)'
         stop 2
      end if
   end if
@@ -389,6 +426,11 @@ program pigs_vpi
           & '..Nb+',fqv_window,': fqvec_vpi.out, fqsh_vpi.out)'
   end if
 
+  if (fq_self) then
+     print '(a,i0,a,i0,a,i0,a,i0,a)', '  > Self F_s(q,tau)     : on (|n_k| <= ',fqs_nmax,', lags 0..',fqs_ntau,', slices Nb-',fqs_window, &
+          & '..Nb+',fqs_window,': fqself_vpi.out, fqssh_vpi.out, msd_vpi.out)'
+  end if
+
   !=====================================================================
 
   !$omp parallel num_threads(G) default(shared)
@@ -514,6 +556,18 @@ contains
   ! normalised block profiles, their per-walker sums and the walker-averaged sums; ntv doubles of the block vector behind
   ! the vector-F(q,tau) ones (0 with the key off), starting behind offset otq; the units of press_vpi*.out
   integer :: ntq,ntv,ntauav,ntauall,otq,upav
+  ! self part of F(q,tau) and displacement (fq_self = T): the stored vectors and their |q| shells, the block's raw sums
+  ! from the device, the normalised block values per (vector, lag), per (shell, lag) and the two moments per lag, their
+  ! per-walker sums and the walker-averaged sums; nzv doubles of the block vector behind the imaginary-time-profile ones
+  ! (0 with the key off), starting behind offset oqs: F_s [nzx,ntau+1], the moments [2,ntau+1], one count
+  integer :: nzx,nzf,nzv,nzav,nzall,nzsh,oqs
+  integer(c_int64_t) :: zs_count
+  integer(c_int32_t), allocatable :: zs_n(:,:),zs_reset(:)
+  integer(c_int64_t), allocatable :: zs_smp(:)
+  integer, allocatable :: zs_shell(:),zs_mult(:)
+  real(8), allocatable :: zs_raw(:,:,:),zs_draw(:,:,:),zsb(:,:),zss(:,:),zsm(:,:),zs_q(:)
+  real(8), allocatable :: AvZx(:,:,:),AvZx2(:,:,:),AvZs(:,:,:),AvZs2(:,:,:),AvZm(:,:,:),AvZm2(:,:,:)
+  real(8), allocatable :: AvZxAll(:,:),AvZx2All(:,:),AvZsAll(:,:),AvZs2All(:,:),AvZmAll(:,:),AvZm2All(:,:)
   integer(c_int64_t), allocatable :: tq_smp(:)
   integer(c_int32_t), allocatable :: tq_reset(:)
   integer, allocatable :: up(:)
@@ -685,6 +739,26 @@ contains
      call pigs_check(tau_init(ctx),'pigs_tau_init')
   end if
 
+  nzx = 0; nzf = 0; nzv = 0; nzav = 0
+  if (fq_self) then
+     call pigs_check(fqs_init(ctx,int(fqs_nmax,c_int32_t),int(fqs_ntau,c_int32_t),int(fqs_window,c_int32_t)),'pigs_fqs_init')
+     call pigs_check(fqs_count(ctx,zs_count),'pigs_fqs_count')
+     nzx = int(zs_count)
+     nzf = nzx*(fqs_ntau+1)
+     nzv = nzf+2*(fqs_ntau+1)+1
+     ! (second index: lag l + 1; 1-based, as every array here that goes through reshape)
+     allocate (zs_n(dim,nzx),zs_shell(nzx),zs_raw(nzx,fqs_ntau+1,NW),zs_draw(2,fqs_ntau+1,NW),zs_smp(NW),zs_reset(NW))
+     allocate (zsb(nzx,fqs_ntau+1),zsm(2,fqs_ntau+1))
+     call pigs_check(fqs_vectors(ctx,zs_n),'pigs_fqs_vectors')
+     call sqv_shells(ep,nzx,zs_n,zs_shell,nzsh,zs_q,zs_mult)
+     allocate (zss(nzsh,fqs_ntau+1),AvZx(nzx,fqs_ntau+1,NW),AvZx2(nzx,fqs_ntau+1,NW),AvZs(nzsh,fqs_ntau+1,NW),AvZs2(nzsh,fqs_ntau+1,NW))
+     allocate (AvZm(2,fqs_ntau+1,NW),AvZm2(2,fqs_ntau+1,NW),AvZmAll(2,fqs_ntau+1),AvZm2All(2,fqs_ntau+1))
+     allocate (AvZxAll(nzx,fqs_ntau+1),AvZx2All(nzx,fqs_ntau+1),AvZsAll(nzsh,fqs_ntau+1),AvZs2All(nzsh,fqs_ntau+1))
+     AvZx = 0.d0; AvZx2 = 0.d0; AvZs = 0.d0; AvZs2 = 0.d0; AvZxAll = 0.d0; AvZx2All = 0.d0; AvZsAll = 0.d0; AvZs2All = 0.d0
+     AvZm = 0.d0; AvZm2 = 0.d0; AvZmAll = 0.d0; AvZm2All = 0.d0
+     zs_reset = 1
+  end if
+
   allocate (perm(NW))
   do w=1,NW
      allocate (perm(w)%members(Np),perm(w)%histogram(Np))
@@ -736,7 +810,8 @@ contains
   ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
   nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
   otq = nvec+ndv+nfv+nsv+ngv+nqv
-  allocate (vec(otq+ntv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
+  oqs = otq+ntv
+  allocate (vec(oqs+nzv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
   allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
   AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
   ngrav = 0; nnrav = 0
@@ -956,6 +1031,9 @@ contains
            if (fq_vector) call pigs_check(fqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqv_accumulate')
            ! and every slice into the imaginary-time profiles
            if (tau_profile) call pigs_check(tau_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_tau_accumulate')
+           ! and the window slices into the sums of the self part of F(q,tau) and of the displacement: diagonal-sector
+           ! walkers only (an open worm cuts the worldline at Nb)
+           if (fq_self) call pigs_check(fqs_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqs_accumulate')
         end if
 
      end do   ! istep
@@ -986,6 +1064,7 @@ contains
      if (gr_vector) call pigs_check(grv_read(ctx,gv_vec,gv_rad,gv_smp,gv_reset),'pigs_grv_read')
      if (fq_vector) call pigs_check(fqv_read(ctx,fx_raw,fx_smp,fx_reset),'pigs_fqv_read')
      if (tau_profile) call pigs_check(tau_read(ctx,tq_raw,tq_smp,tq_reset),'pigs_tau_read')
+     if (fq_self) call pigs_check(fqs_read(ctx,zs_raw,zs_draw,zs_smp,zs_reset),'pigs_fqs_read')
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -1060,6 +1139,19 @@ contains
                  write (up(w),'(20g20.10e3)') real(iblock),wwin,BE(2,w)/Np,density/real(dim,8)*(2.d0*(BE(2,w)/Np)-wwin)
               end if
            end if
+           if (fq_self) then
+              call normalize_fqv(Np,fqs_ntau,fqs_window,int(zs_smp(w),8),nzx,zs_raw(:,:,w),zsb)
+              call normalize_msd(Np,fqs_ntau,fqs_window,int(zs_smp(w),8),zs_draw(:,:,w),zsm)
+              do lag=1,fqs_ntau+1
+                 call sqv_shell_means(nzx,zs_shell,nzsh,zs_mult,zsb(:,lag),zss(:,lag))
+              end do
+              AvZx(:,:,w) = AvZx(:,:,w)+zsb; AvZx2(:,:,w) = AvZx2(:,:,w)+zsb*zsb
+              AvZs(:,:,w) = AvZs(:,:,w)+zss; AvZs2(:,:,w) = AvZs2(:,:,w)+zss*zss
+              AvZm(:,:,w) = AvZm(:,:,w)+zsm; AvZm2(:,:,w) = AvZm2(:,:,w)+zsm*zsm
+              vec(oqs+1:oqs+nzf) = vec(oqs+1:oqs+nzf)+reshape(zsb,[nzf])
+              vec(oqs+nzf+1:oqs+nzv-1) = vec(oqs+nzf+1:oqs+nzv-1)+reshape(zsm,[2*(fqs_ntau+1)])
+              vec(oqs+nzv) = vec(oqs+nzv)+1.d0
+           end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
            write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -1083,7 +1175,7 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(otq+ntv,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(oqs+nzv,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
      ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
      if (ish==1 .and. NWtot>1) then
@@ -1152,6 +1244,20 @@ contains
               AvFxAll = AvFxAll+fxb; AvFx2All = AvFx2All+fxb*fxb
               AvFsAll = AvFsAll+fxs; AvFs2All = AvFs2All+fxs*fxs
            end if
+        end if
+     end if
+     if (ish==1 .and. NWtot>1 .and. fq_self) then          ! walker average of the block's self part and displacement
+        nzall = nint(vec(oqs+nzv))
+        if (nzall>0) then
+           nzav = nzav+1
+           zsb = reshape(vec(oqs+1:oqs+nzf),[nzx,fqs_ntau+1])/nzall
+           zsm = reshape(vec(oqs+nzf+1:oqs+nzv-1),[2,fqs_ntau+1])/nzall
+           do lag=1,fqs_ntau+1
+              call sqv_shell_means(nzx,zs_shell,nzsh,zs_mult,zsb(:,lag),zss(:,lag))
+           end do
+           AvZxAll = AvZxAll+zsb; AvZx2All = AvZx2All+zsb*zsb
+           AvZsAll = AvZsAll+zss; AvZs2All = AvZs2All+zss*zss
+           AvZmAll = AvZmAll+zsm; AvZm2All = AvZm2All+zsm*zsm
         end if
      end if
      if (ish==1 .and. NWtot>1 .and. tau_profile) then      ! walker average of the block's imaginary-time profiles
@@ -1270,6 +1376,11 @@ contains
         call write_fqvec('fqvec_vpi'//trim(suffix)//'.out',ep,fqv_ntau,dt,nfx,fx_n,diag_bl(w),AvFx(:,:,w),AvFx2(:,:,w))
         call write_fqshell('fqsh_vpi'//trim(suffix)//'.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,diag_bl(w),AvFs(:,:,w),AvFs2(:,:,w))
      end if
+     if (fq_self) then
+        call write_fqvec('fqself_vpi'//trim(suffix)//'.out',ep,fqs_ntau,dt,nzx,zs_n,diag_bl(w),AvZx(:,:,w),AvZx2(:,:,w))
+        call write_fqshell('fqssh_vpi'//trim(suffix)//'.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,diag_bl(w),AvZs(:,:,w),AvZs2(:,:,w))
+        call write_msd('msd_vpi'//trim(suffix)//'.out',dim,fqs_ntau,dt,diag_bl(w),AvZm(:,:,w),AvZm2(:,:,w))
+     end if
      if (tau_profile) then
         call write_tau('tau_vpi'//trim(suffix)//'.out',Nb,dt,diag_bl(w),AvTq(:,:,w),AvTq2(:,:,w))
         if (.not. trap) close (up(w))
@@ -1299,6 +1410,11 @@ contains
      if (fq_vector) then
         call write_fqvec('fqvec_vpi.out',ep,fqv_ntau,dt,nfx,fx_n,nfxav,AvFxAll,AvFx2All)
         call write_fqshell('fqsh_vpi.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,nfxav,AvFsAll,AvFs2All)
+     end if
+     if (fq_self) then
+        call write_fqvec('fqself_vpi.out',ep,fqs_ntau,dt,nzx,zs_n,nzav,AvZxAll,AvZx2All)
+        call write_fqshell('fqssh_vpi.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,nzav,AvZsAll,AvZs2All)
+        call write_msd('msd_vpi.out',dim,fqs_ntau,dt,nzav,AvZmAll,AvZm2All)
      end if
      if (tau_profile) then
         call write_tau('tau_vpi.out',Nb,dt,ntauav,AvTqAll,AvTq2All)

@@ -1,6 +1,6 @@
 """Normalisation of the accumulators that PigsContext.density_read (trapped systems, pigs_density_*),
-PigsContext.fqt_read, PigsContext.sqv_read, PigsContext.fqv_read and PigsContext.grv_read (periodic systems, pigs_fqt_*,
-pigs_sqv_*, pigs_fqv_*, pigs_grv_*) and PigsContext.tau_read (both, pigs_tau_*) return.
+PigsContext.fqt_read, PigsContext.sqv_read, PigsContext.fqv_read, PigsContext.fqs_read and PigsContext.grv_read (periodic
+systems, pigs_fqt_*, pigs_sqv_*, pigs_fqv_*, pigs_fqs_*, pigs_grv_*) and PigsContext.tau_read (both, pigs_tau_*) return.
 
 Trapped-system profiles:
 
@@ -25,6 +25,13 @@ F(q,tau) on the vector grid (normalize_fqv, shell_average): raw[l][iqv] holds, p
 C(a)C(a+l) + S(a)S(a+l) of the window slices at the vector n[iqv] of the S(q) grid above:
   F(q, tau_l) = raw / (S * n_pairs(l) * Np)
 Its l = 0 row is normalize_sqv's S(q); shell_average(n, Lbox, F) gives the table per lag and |q| shell.
+
+Self part of F(q,tau) and imaginary-time displacement (normalize_fqs, normalize_msd): F[l][iqv] holds, per sample, the
+n_pairs(l) * Np single-particle products cos(q.(x_i(a+l) - x_i(a))), D[l] the sums of r^2 and r^4 of the once-folded
+displacement x_i(a+l) - x_i(a) over the same pairs and particles:
+  F_s(q, tau_l) = F / (S * n_pairs(l) * Np),   <dr^2>(tau_l) = D[l][0] / (S * n_pairs(l) * Np),
+  alpha_2(tau_l) = dim * <dr^4> / ((dim + 2) * <dr^2>^2) - 1      (0 for a Gaussian displacement in dim dimensions)
+F_s(q, 0) = 1 and <dr^2>(0) = 0; the distinct part is normalize_fqv - normalize_fqs.
 
 Pair distribution on the vector grid (normalize_grv): vec[j] counts, per sample, the pairs i < j of the 2*window + 1
 window slices whose folded displacement x(i) - x(j) falls into bin j of the minimum-image cell (width b_k = Lbox[k]/Nbin);
@@ -128,6 +135,36 @@ def normalize_fqv(raw, samples, Np, window):
     n_pairs = 2.0 * window + 1.0 - np.arange(nl, dtype=np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
         return A / (S * n_pairs[:, None] * float(Np))
+
+
+def normalize_fqs(raw, samples, Np, window):
+    """raw: the sums F of fqs_read ([W, Ntau+1, Nq] or one walker's [Ntau+1, Nq]), samples: [W] or a scalar.  Returns
+    F_s(q, tau_l) of the same shape: raw / (samples * n_pairs(l) * Np), the normalisation of normalize_fqv.  A walker
+    without samples gives NaN."""
+    return normalize_fqv(raw, samples, Np, window)
+
+
+def normalize_msd(raw, samples, Np, window, dim):
+    """raw: the sums D of fqs_read ([W, Ntau+1, 2] or one walker's [Ntau+1, 2]), samples: [W] or a scalar.  Returns
+    (msd, alpha2), each [.., Ntau+1]: msd = <|x_i(tau_l) - x_i(0)|^2> = D[..., 0] / (samples * n_pairs(l) * Np) and the
+    non-Gaussian parameter alpha2 = dim * <dr^4> / ((dim + 2) * msd^2) - 1, NaN where msd is 0 (lag 0).  A walker
+    without samples gives NaN."""
+    A = np.asarray(raw, dtype=np.float64)
+    S = np.asarray(samples, dtype=np.float64)
+    nl = A.shape[-2]
+    if A.shape[-1] != 2:
+        raise ValueError("D must be [.., Ntau+1, 2]")
+    if nl > 2 * window + 1:
+        raise ValueError("more lags than the window holds")
+    if S.ndim > 0:
+        S = S.reshape(S.shape + (1,))
+    n_pairs = 2.0 * window + 1.0 - np.arange(nl, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        norm = S * n_pairs * float(Np)
+        msd = A[..., 0] / norm
+        r4 = A[..., 1] / norm
+        alpha2 = dim * r4 / ((dim + 2.0) * msd * msd) - 1.0
+    return msd, alpha2
 
 
 def shell_average(n, Lbox, Sq):
