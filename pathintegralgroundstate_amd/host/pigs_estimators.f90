@@ -379,6 +379,24 @@ contains
     end subroutine msort
   end subroutine sqv_shells
 
+  ! C-callable handle on sqv_shells (no state): Lbox(dim) as the front end holds it, qbin = 2 pi / Lbox as it sets it
+  ! (pigs_vpi.f90); qsh and mult hold the first nsh of Nq entries.  For tests of the host logic.
+  subroutine est_sqv_shells(dim,Lbox,Nq,nv,shell,nsh,qsh,mult) bind(C,name='est_sqv_shells')
+    use iso_c_binding
+    integer(c_int), value :: dim,Nq
+    real(c_double), intent(in) :: Lbox(dim)
+    integer(c_int32_t), intent(in) :: nv(dim,Nq)
+    integer(c_int), intent(out) :: shell(Nq),nsh,mult(Nq)
+    real(c_double), intent(out) :: qsh(Nq)
+    type(est_params) :: p
+    real(8), allocatable :: q(:)
+    integer, allocatable :: m(:)
+    p%dim = dim; p%pi = acos(-1.d0)
+    p%Lbox = 1.d0; p%Lbox(1:dim) = Lbox; p%LboxHalf = 0.5d0*p%Lbox; p%qbin = 2.d0*p%pi/p%Lbox
+    call sqv_shells(p,Nq,nv,shell,nsh,q,m)
+    qsh(1:nsh) = q; mult(1:nsh) = m
+  end subroutine est_sqv_shells
+
   ! mean of Sq over the stored vectors of every shell
   subroutine sqv_shell_means(Nq,shell,nsh,mult,Sq,Ssh)
     integer, intent(in)  :: Nq,nsh,shell(Nq),mult(nsh)

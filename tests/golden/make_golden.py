@@ -301,6 +301,26 @@ RUNS = {
     "trap3d_n260_s1982": dict(dim=3, Np=260, Nb=16, seed=1982, trap="T", a_ho="1.0d0 1.3d0 0.8d0", dt="1.0d-2",
                               sampling="bis", Lstag=8, Nlev=3, Nstag=2, Nblock=2, Nstep=3, CWorm="0.0d0", Nobdm=0, Npw=0,
                               big=True),
+    # ---- boxes with unequal sides (the reference reads them from config_ini.in when crystal = T, vpi.f90:99-122; vpi.in
+    # cannot express them, so these exist in driver form only, with Lbox, density = Np / prod(Lbox) and rcut = min Lbox / 2
+    # stored beside the driver arrays).  Side ratios that are no permutation of one another; in [7.3, 4.1, 5.9] the
+    # shortest side, which sets rcut, is axis 1; [3.2, 4.8, 6.4] = 1.6 (2, 3, 4) is commensurate with a lattice.  `must`:
+    # counters that make_runs asserts to be positive.  Worm runs: of the seeds 1-12 tried, 7, 8 and 11 have an accepted
+    # open, close AND swap within 40 steps (seed 7: 2 opens, 1 close, 5 swaps; seed 8: 3, 2, 7).
+    "ortho_bis_s1982": dict(dim=3, Np=37, Nb=8, seed=1982, sampling="bis", Lstag=4, Nlev=3, Nstag=2, Nblock=2, Nstep=6,
+                            CWorm="0.0d0", Nobdm=0, Npw=0, Lbox=[7.3, 4.1, 5.9], must=("acc_cm", "acc_bd", "acc_head", "acc_tail")),
+    "ortho_bis_s1983": dict(dim=3, Np=37, Nb=8, seed=1983, sampling="bis", Lstag=4, Nlev=3, Nstag=2, Nblock=2, Nstep=6,
+                            CWorm="0.0d0", Nobdm=0, Npw=0, Lbox=[7.3, 4.1, 5.9], must=("acc_cm", "acc_bd", "acc_head", "acc_tail")),
+    "ortho_worm_s7": dict(dim=3, Np=24, Nb=8, seed=7, dt="2.0d-2", sampling="bis", Lstag=8, Nlev=3, Nstag=2, Nblock=4,
+                          Nstep=10, CWorm="3.0d0", Nobdm=4, Npw=1, Lbox=[3.2, 4.8, 6.4],
+                          must=("acc_cm", "acc_bd", "acc_open", "acc_close", "acc_swap")),
+    "ortho_worm_s8": dict(dim=3, Np=24, Nb=8, seed=8, dt="2.0d-2", sampling="bis", Lstag=8, Nlev=3, Nstag=2, Nblock=4,
+                          Nstep=10, CWorm="3.0d0", Nobdm=4, Npw=1, Lbox=[3.2, 4.8, 6.4],
+                          must=("acc_cm", "acc_bd", "acc_open", "acc_close", "acc_swap")),
+    "ortho2d_sta_s1982": dict(dim=2, Np=24, Nb=8, seed=1982, sampling="sta", Lstag=4, Nlev=2, Nstag=2, Nblock=2, Nstep=8,
+                              CWorm="0.0d0", Nobdm=0, Npw=0, Lbox=[5.0, 8.0], must=("acc_cm", "acc_bd", "acc_head", "acc_tail")),
+    "ortho2d_sta_s1983": dict(dim=2, Np=24, Nb=8, seed=1983, sampling="sta", Lstag=4, Nlev=2, Nstag=2, Nblock=2, Nstep=8,
+                              CWorm="0.0d0", Nobdm=0, Npw=0, Lbox=[5.0, 8.0], must=("acc_cm", "acc_bd", "acc_head", "acc_tail")),
 }
 RUN_FILES = ["e_vpi.out", "et_vpi.out", "gr_vpi.out", "sk_vpi.out", "nr_vpi.out", "fort.99"]
 BIG_STRIDE = 8           # fixtures of the N=256 runs keep every 8th bead + SHA-256 + per-bead sums
@@ -316,11 +336,14 @@ def drive_run(ref, kw, VT=None):
     trap = kw.get("trap", "F") == "T"
     a_ho = [float(t.replace("d", "e")) for t in str(kw.get("a_ho", "1.0d0")).split()]
     density = _fnum(kw.get("density", "0.365d0"))
+    Lbox = kw.get("Lbox")
+    if Lbox is not None:
+        density = kw["Np"] / float(np.prod(Lbox[:kw["dim"]]))
     if trap:
         from pathintegralgroundstate_amd import SystemConfig
         density = SystemConfig(dim=kw["dim"], Np=kw["Np"], Nb=kw["Nb"], trap=True, a_ho=a_ho).density   # vpi.f90:82-93
     S = System(dim=kw["dim"], Np=kw["Np"], Nb=kw["Nb"], density=density,
-               dt=_fnum(kw.get("dt", "5.0d-3")), trap=trap, a_ho=a_ho if trap else None,
+               dt=_fnum(kw.get("dt", "5.0d-3")), trap=trap, a_ho=a_ho if trap else None, Lbox=Lbox,
                CWorm=_fnum(kw["CWorm"]), Npw=kw["Npw"], Nbin=100, wf_table=kw.get("wf_table", "T") == "T")
     VTr, WF = ref.tables(S)
     if VT is None:
@@ -344,11 +367,15 @@ def make_runs(only=None):
         big = kw.pop("big", False)
         potential = kw.pop("potential", "aziz2")
         with_driver = kw.pop("driver", True)
+        must = kw.pop("must", ())
+        Lbox = kw.pop("Lbox", None)
+        if Lbox is not None:                                  # the density the box implies, in the namelist too
+            kw["density"] = repr(kw["Np"] / float(np.prod(Lbox[:kw["dim"]]))) + "d0"
         dst = os.path.join(base, name)
         os.makedirs(dst, exist_ok=True)
         P = None
         with tempfile.TemporaryDirectory() as td:
-            if potential == "aziz2":
+            if potential == "aziz2" and Lbox is None:
                 P = run_vpi(td, **kw)
                 for f in RUN_FILES:
                     if os.path.exists(os.path.join(td, f)):
@@ -371,7 +398,9 @@ def make_runs(only=None):
             # table builder (pigs_tables.cpp) -- input data for both sides of the comparison
             cfg = SystemConfig.from_namelists(open(os.path.join(dst, "vpi.in")).read())
             VT, _ = api.build_tables(cfg, potential)
-        S, res = drive_run(ref, kw, VT)
+        S, res = drive_run(ref, dict(kw, Lbox=Lbox), VT)
+        for k in must:                                        # the run contains what it is for
+            assert res["counters"][rd.COUNTER_NAMES.index(k)] > 0, (name, k, res["counters"])
         if P is not None:
             rd.validate_against_program(res, P, np.loadtxt(os.path.join(dst, "e_vpi.out")).reshape(-1, 4)
                                         if os.path.getsize(os.path.join(dst, "e_vpi.out")) else np.zeros((0, 4)),
@@ -384,6 +413,8 @@ def make_runs(only=None):
         elif os.path.exists(os.path.join(dst, "final_worldline.npz")):
             os.remove(os.path.join(dst, "final_worldline.npz"))
         c["potential"] = np.array(potential)
+        if Lbox is not None:
+            c.update(Lbox=S.Lbox[:S.dim].copy(), density=np.float64(S.density), rcut=np.float64(S.rcut))
         np.savez_compressed(os.path.join(dst, "driver.npz"), **c)
         print(name, "counters", dict(zip(rd.COUNTER_NAMES, res["counters"].tolist())), "events", len(res["events"]),
               flush=True)
@@ -522,21 +553,23 @@ def make_resume_fixture():
     print("resume fixture written to", dst)
 
 
-def make_crystal_fixture():
+def make_crystal_fixture(name="he4_crystal", cells=(3, 3, 3)):
     """crystal = T (reference vpi.f90:99-107, vpi_mod.f90:218-230): particle number, box and density come from
     config_ini.in, whose remaining lines are the start configuration (every bead of a particle on its lattice site).
-    A 3x3x3 simple-cubic lattice with a seeded jitter at density 0.45; worm sector on.  Reference PROGRAM files +
-    its final worldline; config_ini.in is part of the fixture (it is input data)."""
+    A simple-cubic lattice of `cells` cells (3x3x3: he4_crystal; 2x3x4, a box with sides a (2, 3, 4): he4_crystal_ortho)
+    with a seeded jitter at density 0.45; worm sector on.  Reference PROGRAM files + its final worldline; config_ini.in
+    is part of the fixture (it is input data)."""
     import shutil
-    dst = os.path.join(OUT, "vpi_runs", "he4_crystal")
+    dst = os.path.join(OUT, "vpi_runs", name)
     os.makedirs(dst, exist_ok=True)
-    n, dens = 3, 0.45
-    Np = n ** 3
-    L = (Np / dens) ** (1.0 / 3.0)
+    dens = 0.45
+    n = np.array(cells)
+    Np = int(n.prod())
+    L = np.full(3, (Np / dens) ** (1.0 / 3.0)) if len(set(cells)) == 1 else dens ** (-1.0 / 3.0) * n   # sides a * cells
     rng = np.random.default_rng(27)
-    sites = (np.stack(np.meshgrid(*[np.arange(n)] * 3, indexing="ij"), -1).reshape(-1, 3) + 0.5) * (L / n) - L / 2
+    sites = (np.stack(np.meshgrid(*[np.arange(c) for c in cells], indexing="ij"), -1).reshape(-1, 3) + 0.5) * (L / n) - L / 2
     sites = sites + rng.normal(0, 0.03, sites.shape)
-    cfg = "%d\n%s\n%.17g\n" % (Np, " ".join("%.17g" % L for _ in range(3)), dens)
+    cfg = "%d\n%s\n%.17g\n" % (Np, " ".join("%.17g" % x for x in L), dens)
     cfg += "".join(" ".join("%.17g" % x for x in r) + "\n" for r in sites)
     # the namelist's Np and density are deliberately different: config_ini.in wins (vpi.f90:103-105)
     kw = dict(dim=3, Np=8, Nb=8, seed=1982, sampling="bis", Lstag=8, Nlev=3, Nstag=3, Nblock=4, Nstep=15,
@@ -577,3 +610,4 @@ if __name__ == "__main__":
         make_resume_fixture()
     if what in ("all", "crystal"):
         make_crystal_fixture()
+        make_crystal_fixture("he4_crystal_ortho", (2, 3, 4))

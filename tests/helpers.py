@@ -83,6 +83,20 @@ def driver_blocks(drv):
     return be[:, 0].astype(int), np.concatenate([be[:, 1:4], bt[:, 1:4]], axis=1)
 
 
+def run_config(src):
+    """SystemConfig of the run in the directory `src`: its vpi.in, and -- where driver.npz carries a box that vpi.in
+    cannot express (sides that differ: Lbox, density = Np / prod(Lbox), rcut = min Lbox / 2) -- that box."""
+    import os
+    from pathintegralgroundstate_amd import SystemConfig
+    over = {}
+    drv = os.path.join(src, "driver.npz")
+    if os.path.exists(drv):
+        with np.load(drv) as d:
+            if "Lbox" in d.files:
+                over = dict(Lbox=[float(x) for x in d["Lbox"]], density=float(d["density"]), rcut=float(d["rcut"]))
+    return SystemConfig.from_namelists(open(os.path.join(src, "vpi.in")).read(), **over)
+
+
 def sha256_of(a):
     import hashlib
     return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a, float).tobytes()).digest(), np.uint8)

@@ -407,12 +407,8 @@ def test_gpu_front_end_config5_long_worm_trajectories(exe, name, dev, nblocks, t
             assert open(tmp_path / "perm_vpi.out").read().split() == open(os.path.join(src, "fort.99")).read().split()
 
 
-@pytest.mark.parametrize("dev", ["F", "T"])
-def test_gpu_crystal_start_from_config_ini(exe, dev, tmp_path):
-    """crystal = T on the MI355X, both samplers: Np / box / density and the start configuration from config_ini.in
-    (reference vpi.f90:99-107, vpi_mod.f90:218-230) -- worldline bit-identical to the reference program's, block
-    energies as printed, OBDM file and permutation histogram identical."""
-    src = os.path.join(RUNS, "he4_crystal")
+def crystal_start(exe, dev, name, tmp_path):
+    src = os.path.join(RUNS, name)
     _run(exe, open(os.path.join(src, "vpi.in")).read() + f"&gpu\n n_walkers = 1, device = 0, device_sampler = {dev}\n/\n",
          str(tmp_path), extra_files=[os.path.join(src, "config_ini.in")])
     want = np.load(os.path.join(src, "final_worldline.npz"))["Path"]
@@ -423,6 +419,14 @@ def test_gpu_crystal_start_from_config_ini(exe, dev, tmp_path):
     assert _close(tmp_path / "gr_vpi.out", os.path.join(src, "gr_vpi.out"), rel=1e-9)
     assert open(os.path.join(src, "nr_vpi.out"), "rb").read() == open(tmp_path / "nr_vpi.out", "rb").read()
     assert open(tmp_path / "perm_vpi.out").read().split() == open(os.path.join(src, "fort.99")).read().split()
+
+
+@pytest.mark.parametrize("dev", ["F", "T"])
+def test_gpu_crystal_start_from_config_ini(exe, dev, tmp_path):
+    """crystal = T on the MI355X, both samplers: Np / box / density and the start configuration from config_ini.in
+    (reference vpi.f90:99-107, vpi_mod.f90:218-230) -- worldline bit-identical to the reference program's, block
+    energies as printed, OBDM file and permutation histogram identical."""
+    crystal_start(exe, dev, "he4_crystal", tmp_path)
 
 
 @pytest.mark.parametrize("sampling,system,samp,cworm", [

@@ -20,15 +20,14 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from helpers import MIXED_TOL, check_worldline_vs_driver, fold_maxnorm, rng_sha256
-from pathintegralgroundstate_amd import SystemConfig
+from helpers import MIXED_TOL, check_worldline_vs_driver, fold_maxnorm, rng_sha256, run_config
 
 pytestmark = pytest.mark.gpu
 RUNS = os.path.join(GOLDEN, "vpi_runs")
 
 
 def _cfg(name):
-    return SystemConfig.from_namelists(open(os.path.join(RUNS, name, "vpi.in")).read())
+    return run_config(os.path.join(RUNS, name))
 
 
 def run_k6(gpu_lib, oracle, names, threads=None, split=0, cm=None, rows=None, overlap=False):

@@ -107,25 +107,40 @@ def test_host_driven_sampler_lstag_beyond_nb(exe, name, W, tmp_path):
         assert open(os.path.join(src, f), "rb").read() == open(mine, "rb").read(), f
 
 
-@pytest.mark.parametrize("W", [1, 2])
-def test_crystal_start_from_config_ini(exe, W, tmp_path):
-    """crystal = T (vpi.f90:99-107, vpi_mod.f90:218-230): Np, box and density come from config_ini.in -- the
-    namelist's Np = 8 and density = 0.2 are overridden by the file's 27 particles at 0.45 -- and every bead starts on
-    the particle's lattice site; no random number is spent on the start.  Reference program files byte for byte, final
-    worldline bit-identical; with two walkers each one reads the same lattice (walker 0 = the reference run)."""
-    src = os.path.join(RUNS, "he4_crystal")
+def crystal_start(exe, name, W, shape, tmp_path):
+    """A crystal = T fixture through the front end: reference program files byte for byte, final worldline
+    bit-identical; with two walkers walker 0 is the reference run."""
+    src = os.path.join(RUNS, name)
     txt = open(os.path.join(src, "vpi.in")).read()
-    assert "crystal = T" in txt and "Np = 8" in txt
+    assert "crystal = T" in txt and "Np = 8" in txt and "density = 0.2d0" in txt
     run_pigs_vpi(exe, txt + f"&gpu\n n_walkers = {W}, device = 0\n/\n", str(tmp_path),
                  extra_files=[os.path.join(src, "config_ini.in")])
     want = np.load(os.path.join(src, "final_worldline.npz"))["Path"]
-    assert want.shape == (17, 27, 3)
+    assert want.shape == shape
     assert same_bits(final_worldline(str(tmp_path), want.shape, W)[0], want)
     for f in FILES:
         mine = tmp_path / (f if W == 1 else f.replace(".out", ".w0000.out"))
         assert open(os.path.join(src, f), "rb").read() == open(mine, "rb").read(), f
     mine = tmp_path / ("perm_vpi.out" if W == 1 else "perm_vpi.w0000.out")
     assert open(mine).read().split() == open(os.path.join(src, "fort.99")).read().split()
+
+
+@pytest.mark.parametrize("W", [1, 2])
+def test_crystal_start_from_config_ini(exe, W, tmp_path):
+    """crystal = T (vpi.f90:99-107, vpi_mod.f90:218-230): Np, box and density come from config_ini.in -- the
+    namelist's Np = 8 and density = 0.2 are overridden by the file's 27 particles at 0.45 -- and every bead starts on
+    the particle's lattice site; no random number is spent on the start.  Reference program files byte for byte, final
+    worldline bit-identical; with two walkers each one reads the same lattice (walker 0 = the reference run)."""
+    crystal_start(exe, "he4_crystal", W, (17, 27, 3), tmp_path)
+
+
+@pytest.mark.parametrize("W", [1, 2])
+def test_crystal_start_unequal_sides_from_config_ini(exe, W, tmp_path):
+    """The same with a box whose sides differ: a 2x3x4 lattice of 24 particles in a (2, 3, 4), one length per axis from
+    config_ini.in (vpi.f90:99-107), LboxHalf, qbin per axis and rcut = min L_k / 2 from axis 0 (vpi.f90:117-122)."""
+    L = [float(x) for x in open(os.path.join(RUNS, "he4_crystal_ortho", "config_ini.in")).read().split("\n")[1].split()]
+    assert len(set(L)) == 3 and np.allclose(np.array(L) / L[0], [1.0, 1.5, 2.0], rtol=1e-15)
+    crystal_start(exe, "he4_crystal_ortho", W, (17, 24, 3), tmp_path)
 
 
 def test_worm_sector_with_lstag_beyond_nb_is_refused(exe, tmp_path):

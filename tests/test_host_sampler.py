@@ -71,7 +71,10 @@ def _same_path(tape, P, *got):
 
 @pytest.mark.parametrize("kw", [dict(dim=3, Np=16, Nb=20, density=0.365),
                                 dict(dim=2, Np=9, Nb=12, density=0.25),
-                                dict(dim=3, Np=6, Nb=10, trap=True, a_ho=[1.0, 1.2, 0.9])])
+                                dict(dim=3, Np=6, Nb=10, trap=True, a_ho=[1.0, 1.2, 0.9]),
+                                # unequal sides: the movers' folds and TranslateChain per axis (rcut from axis 1 / axis 0)
+                                dict(dim=3, Np=16, Nb=12, Lbox=[7.3, 4.1, 5.9], density=16 / (7.3 * 4.1 * 5.9)),
+                                dict(dim=2, Np=9, Nb=12, Lbox=[5.0, 8.0], density=9 / 40.0)])
 def test_diagonal_movers_bit_exact(libs, oracle, tape, kw):
     S = System(**kw)
     ref = tape.ref
@@ -104,7 +107,19 @@ def test_diagonal_movers_bit_exact(libs, oracle, tape, kw):
 
 
 def test_worm_movers_bit_exact(libs, oracle, tape):
-    S = System(dim=3, Np=12, Nb=16, density=0.365, CWorm=0.8)
+    _worm_movers(libs, oracle, tape, System(dim=3, Np=12, Nb=16, density=0.365, CWorm=0.8))
+
+
+def test_worm_movers_bit_exact_unequal_sides(libs, oracle, tape):
+    """The worm sector in the box 1.6 (2, 3, 4) at the same density: the folds of open, close, swap and the half-chain
+    movers per axis.  dt = 0.02 and CWorm = 3 (the knobs of the busy worm runs): at the cubic test's the reference accepts no
+    swap here."""
+    S = System(dim=3, Np=12, Nb=16, Lbox=[1.6 * 2, 1.6 * 3, 1.6 * 4], density=12 / (24 * 1.6 ** 3), CWorm=3.0, dt=2e-2)
+    assert len(set(S.Lbox.tolist())) == 3
+    _worm_movers(libs, oracle, tape, S)
+
+
+def _worm_movers(libs, oracle, tape, S):
     ref = tape.ref
     VT, WF, P, xend, delta, rng_state = _setup(tape, oracle, S, 5, sweeps=6)
     hs = HostSampler(S, VT, WF, W=1, backend=libs[0], hostlib=libs[1])

@@ -21,6 +21,10 @@ def _wrap(x, L):
     dict(dim=1, Np=5, Nb=3, density=0.4),
     dict(dim=3, Np=9, Nb=4, trap=True, a_ho=[0.9, 1.1, 1.4]),
     dict(dim=1, Np=2, Nb=10, trap=True, a_ho=[1.0]),
+    # boxes with unequal sides (crystal = T, vpi.f90:99-122): the shortest side, which sets rcut, is not axis 0
+    dict(dim=3, Np=37, Nb=5, Lbox=[7.3, 4.1, 5.9], density=37 / (7.3 * 4.1 * 5.9)),
+    dict(dim=3, Np=24, Nb=4, Lbox=[2 * 1.6, 3 * 1.6, 4 * 1.6], density=24 / (24 * 1.6 ** 3)),
+    dict(dim=2, Np=12, Nb=4, Lbox=[5.0, 8.0], density=12 / 40.0),
 ])
 def test_hot_path_vs_reference(oracle, tape, kw):
     S = System(**kw)
@@ -55,8 +59,7 @@ def test_hot_path_vs_reference(oracle, tape, kw):
     assert same_bits(tape.scalars(lambda: ref.therm_energy(VT, P)), oracle.therm_energy(S, VT, P))
 
 
-def test_structural_estimators_vs_reference(oracle, tape):
-    S = System(dim=3, Np=64, Nb=4, Npw=2)
+def _structural_estimators(oracle, tape, S):
     ref = tape.ref
     if ref:
         ref.set_system(S)
@@ -66,8 +69,19 @@ def test_structural_estimators_vs_reference(oracle, tape):
     assert tape.digest(lambda: ref.structure_factor(50, P[S.Nb])) == digest(oracle.structure_factor(S, 50, P[S.Nb]))
     rng = np.random.default_rng(5)
     for _ in range(50):
-        xe = rng.uniform(-S.Lbox[0] / 2, S.Lbox[0] / 2, (2, 3))
+        xe = rng.uniform(-S.Lbox / 2, S.Lbox / 2, (2, 3))
         assert tape.digest(lambda: ref.obdm(xe)) == digest(oracle.obdm(S, xe))
+
+
+def test_structural_estimators_vs_reference(oracle, tape):
+    _structural_estimators(oracle, tape, System(dim=3, Np=64, Nb=4, Npw=2))
+
+
+def test_structural_estimators_vs_reference_unequal_sides(oracle, tape):
+    """g(r), S(k) (qbin per axis) and the OBDM in the box [7.3, 4.1, 5.9]: rbin and the cutoff come from axis 1."""
+    S = System(dim=3, Np=37, Nb=4, Npw=2, Lbox=[7.3, 4.1, 5.9], density=37 / (7.3 * 4.1 * 5.9))
+    assert S.rcut == 2.05
+    _structural_estimators(oracle, tape, S)
 
 
 def test_box_and_primitives_vs_reference(oracle, tape):
@@ -78,19 +92,29 @@ def test_box_and_primitives_vs_reference(oracle, tape):
         S = System(dim=dim, Np=Np, Nb=2, density=rho)
         assert S.Lbox[0] == L
     S = System(dim=3, Np=64, Nb=40)
-    if ref:
-        ref.set_system(S)
-    rng = np.random.default_rng(3)
-    for _ in range(500):
-        x = rng.uniform(-1.5 * S.Lbox[0], 1.5 * S.Lbox[0], 3)
-        a = tape.scalars(lambda: np.append(*ref.minimum_image(x)))
-        b, r2b = oracle.minimum_image(S, x)
-        assert same_bits(a[:3], b) and a[3] == r2b
+    _minimum_image(oracle, tape, S)
     for opt in (0, 1):
         for ib in (0, 1, 2, 40, 79, 80):
             for pot, f2 in ((1.7, -3.3), (-2e5, 9e9)):
                 assert tape.scalars(lambda: ref.green_function(opt, ib, 5e-3, pot, f2))[0] == \
                     oracle.green_function(opt, ib, S.Nb, 5e-3, pot, f2)
+
+
+def _minimum_image(oracle, tape, S):
+    ref = tape.ref
+    if ref:
+        ref.set_system(S)
+    rng = np.random.default_rng(3)
+    for _ in range(500):
+        x = rng.uniform(-1.5 * S.Lbox, 1.5 * S.Lbox, 3)
+        a = tape.scalars(lambda: np.append(*ref.minimum_image(x)))
+        b, r2b = oracle.minimum_image(S, x)
+        assert same_bits(a[:3], b) and a[3] == r2b
+
+
+def test_minimum_image_vs_reference_unequal_sides(oracle, tape):
+    """The single fold per axis with inputs from +-1.5 L_k of the box [7.3, 4.1, 5.9]: a fold by another axis' length shows."""
+    _minimum_image(oracle, tape, System(dim=3, Np=37, Nb=4, Lbox=[7.3, 4.1, 5.9], density=37 / (7.3 * 4.1 * 5.9)))
 
 
 def test_rng_vs_reference(oracle, tape):
