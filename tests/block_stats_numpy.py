@@ -1,0 +1,171 @@
+"""Numpy restatement of what the front end does with the accumulate kernels' raw sums: the per-block normalisations and
+the block statistics of the estimator files, written from the documents (README.md) and the files' own
+headers, not from the Fortran, and without pathintegralgroundstate_amd.profiles.
+
+Normalisations (one walker, one block with S samples, i.e. S diagonal steps in the block):
+  S(q)                 raw / (S (2 window + 1) Np)
+  F(q,tau_l), F_s, dr^2, dr^4     raw / (S n_pairs(l) Np), n_pairs(l) = 2 window + 1 - l
+  g on the vector grid (c(j) + c(reflected j)) / (S (2 window + 1) Np density prod_k b_k), b_k = L_k / Ng
+  radial g(r)          2 c(j) / (S (2 window + 1) Np density (V_d(j rbin) - V_d((j-1) rbin)))
+  V(tau) profiles      Vpair, Vext, W: raw / (S Np); link kinetic energy dim/(2 dt) - D2 / (2 dt^2 Np S)
+  trap profiles        planar c / (S b^min(dim,2)), radial c / (S dV_j), pair c / (S Np dV_j); b = 2h/Nbin, br = h/Nbin
+  pressure             density / dim (2 Kin/Np - W/Np), W/Np the mean over the slices Nb-window..Nb+window
+  |q| shells           the mean of the block values over the stored vectors of equal |q|
+
+Statistics: a block counts for a walker only if the walker had a diagonal step in it.  A file's mean is the mean of the
+counted block values; its error the "variance" of the reference's files, sqrt((<b^2> - <b>^2) / n) over the n counted
+blocks.  The walker-averaged files take, per block, the mean over the walkers that counted it, and then the same two
+moments over the blocks that at least one walker counted."""
+import math
+
+import numpy as np
+
+
+# ---- statistics -------------------------------------------------------------------------------------------------------
+def moments(b, counted):
+    """b [Nblock, ...] block values, counted [Nblock] bool.  Returns (mean, err, n) over the counted blocks; n = 0 gives
+    NaN."""
+    b = np.asarray(b, np.float64)
+    counted = np.asarray(counted, bool)
+    n = int(counted.sum())
+    s1 = np.zeros(b.shape[1:])
+    s2 = np.zeros(b.shape[1:])
+    for k in np.flatnonzero(counted):
+        s1 = s1 + b[k]
+        s2 = s2 + b[k] * b[k]
+    with np.errstate(all="ignore"):
+        mean = s1 / n if n else np.full(b.shape[1:], np.nan)
+        var = (s2 / n - mean * mean) / n if n else np.full(b.shape[1:], np.nan)
+        # (a difference of two moments: a few ulp of mean^2 below zero stands for zero)
+        err = np.sqrt(np.maximum(var, 0.0))
+    return mean, err, n
+
+
+def walker_stats(b, counted, w):
+    """Walker w of b [W, Nblock, ...], counted [W, Nblock]."""
+    return moments(np.asarray(b)[w], np.asarray(counted)[w])
+
+
+def walker_average(b, counted):
+    """Per block, the mean of b [W, Nblock, ...] over the walkers that counted the block.  Returns (values [Nblock, ...],
+    counted [Nblock]); a block that nobody counted holds zeros and is not counted."""
+    b = np.asarray(b, np.float64)
+    counted = np.asarray(counted, bool)
+    W, nb = counted.shape
+    out = np.zeros(b.shape[1:])
+    for k in range(nb):
+        ws = np.flatnonzero(counted[:, k])
+        for w in ws:
+            out[k] = out[k] + b[w, k]
+        if ws.size:
+            out[k] = out[k] / ws.size
+    return out, counted.any(axis=0)
+
+
+def average_stats(b, counted):
+    """The walker-averaged file: moments over the blocks of walker_average."""
+    return moments(*walker_average(b, counted))
+
+
+def mean_bound(bound, counted, w=None):
+    """The same means applied to a per-block error bound (all its terms are non-negative): walker w, or the walker
+    average with w = None."""
+    if w is None:
+        return moments(*walker_average(bound, counted))[0]
+    return walker_stats(bound, counted, w)[0]
+
+
+# ---- normalisations ---------------------------------------------------------------------------------------------------
+def _s(S, extra):
+    S = np.asarray(S, np.float64)
+    return S.reshape(S.shape + (1,) * extra)
+
+
+def norm_window(raw, S, Np, window):
+    """raw [..., Nq], S [...]: the vector S(q)."""
+    raw = np.asarray(raw, np.float64)
+    with np.errstate(all="ignore"):
+        return raw / (_s(S, 1) * (2 * window + 1) * Np)
+
+
+def norm_lags(raw, S, Np, window, lag_axis):
+    """raw [..., Ntau+1 (at lag_axis, counted from the end, negative), ...], S [...]: every estimator over pairs of window
+    slices l apart."""
+    raw = np.asarray(raw, np.float64)
+    nl = raw.shape[lag_axis]
+    pairs = (2 * window + 1 - np.arange(nl)).astype(np.float64).reshape((nl,) + (1,) * (-lag_axis - 1))
+    with np.errstate(all="ignore"):
+        return raw / (_s(S, raw.ndim - np.ndim(S)) * pairs * Np)
+
+
+def ball(dim):
+    return math.pi ** (0.5 * dim) / math.gamma(0.5 * dim + 1.0)
+
+
+def norm_grv(vec, rad, S, Np, window, density, Lbox, rbin, dim):
+    """vec [..., Ng (dim axes)], rad [..., Nr], S [...].  Returns (g_vec, g_r)."""
+    vec = np.asarray(vec, np.float64)
+    rad = np.asarray(rad, np.float64)
+    Ng, Nr = vec.shape[-1], rad.shape[-1]
+    cell = 1.0
+    for k in range(dim):
+        cell = cell * (float(Lbox[k]) / Ng)
+    refl = vec
+    for ax in range(1, dim + 1):
+        refl = np.flip(refl, axis=-ax)
+    j = np.arange(1, Nr + 1, dtype=np.float64)
+    shell = ball(dim) * ((j * rbin) ** dim - ((j - 1.0) * rbin) ** dim)
+    with np.errstate(all="ignore"):
+        g_vec = (vec + refl) / (_s(S, dim) * (2 * window + 1) * Np * density * cell)
+        g_r = 2.0 * rad / (_s(S, 1) * (2 * window + 1) * Np * density * shell)
+    return g_vec, g_r
+
+
+def norm_tau(Q, S, Np, dim, dt):
+    """Q [..., 2Nb+1, 4], S [...].  Returns T [..., 2Nb+1, 4]: Vpair/Np, Vext/Np, W/Np and the link's kinetic estimator
+    (0 for slice 2Nb, which starts no link)."""
+    Q = np.asarray(Q, np.float64)
+    T = np.zeros(Q.shape)
+    with np.errstate(all="ignore"):
+        T[..., :3] = Q[..., :3] / (_s(S, 2) * Np)
+        T[..., 3] = dim / (2.0 * dt) - Q[..., 3] / (2.0 * dt * dt * Np * _s(S, 1))
+    T[..., -1, 3] = 0.0
+    return T
+
+
+def norm_density(planar, radial, pair, S, dim, Np, Nbin, h):
+    """planar [..., Nbin^min(dim,2)] (any layout of the trailing axes), radial, pair [..., Nbin], S [...]."""
+    planar = np.asarray(planar, np.float64)
+    b, br = 2.0 * h / Nbin, h / Nbin
+    j = np.arange(1, Nbin + 1, dtype=np.float64)
+    dv = ball(dim) * (j * br) ** dim - ball(dim) * ((j - 1.0) * br) ** dim
+    with np.errstate(all="ignore"):
+        return (planar / (_s(S, planar.ndim - np.ndim(S)) * b ** min(dim, 2)),
+                np.asarray(radial, np.float64) / (_s(S, 1) * dv),
+                np.asarray(pair, np.float64) / (_s(S, 1) * Np * dv))
+
+
+def pressure(kin, w, density, dim):
+    return density / dim * (2.0 * kin - w)
+
+
+def shells(n, Lbox):
+    """The |q| shells of the stored vectors n [Nq, dim] in a box of equal sides: (index of every vector's shell, |q| per
+    shell ascending, multiplicity per shell counting +q and -q)."""
+    n = np.asarray(n, np.int64)
+    L = [float(x) for x in Lbox[:n.shape[1]]]
+    assert all(x == L[0] for x in L), "shells by the integer n^2: equal sides only"
+    key = (n * n).sum(axis=1)
+    keys = np.unique(key)
+    idx = np.searchsorted(keys, key)
+    q = (2.0 * math.pi / L[0]) * np.sqrt(keys.astype(np.float64))
+    return idx, q, 2 * np.bincount(idx, minlength=keys.size)
+
+
+def shell_means(idx, nsh, x):
+    """x [..., Nq] -> [..., nsh]: the mean over the stored vectors of every shell."""
+    x = np.asarray(x, np.float64)
+    out = np.zeros(x.shape[:-1] + (nsh,))
+    for i, s in enumerate(idx):
+        out[..., s] = out[..., s] + x[..., i]
+    return out / np.bincount(idx, minlength=nsh)
