@@ -22,6 +22,7 @@ LIB_PATH = os.path.join(HERE, "libpigs_hip.so")
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 
 # every symbol include/pigs_hip.h declares
 ABI_SYMBOLS = [
@@ -187,6 +188,10 @@ def _d(a):
 
 def _i(a):
     return a.ctypes.data_as(_ip)
+
+
+def _l(a):
+    return a.ctypes.data_as(_lp)
 
 
 def device_count():
@@ -440,6 +445,25 @@ class PigsContext:
         _chk(self.L, self.L.pigs_slice_download(self.h, int(ib), _d(R)), "pigs_slice_download")
         return R
 
+    # ---- what the per-walker accumulator families below share
+    def _accumulate(self, name, walkers):
+        """pigs_<family>_accumulate `name` for `walkers` (None: all, the list left out)."""
+        if walkers is None:
+            _chk(self.L, getattr(self.L, name)(self.h, self.n_walkers, None), name)
+        else:
+            wl = _i32(walkers).ravel()
+            _chk(self.L, getattr(self.L, name)(self.h, wl.size, _i(wl)), name)
+
+    def _reset_mask(self, reset):
+        """The `reset` of a *_read -- None, True (all walkers) or a per-walker mask -- as the library takes it: a
+        pointer, which keeps its array alive, or None."""
+        if reset is None or reset is False:
+            return None
+        keep = np.ones(self.n_walkers, np.int32) if reset is True else _i32(reset)
+        if keep.size != self.n_walkers:
+            raise ValueError("reset mask needs one entry per walker")
+        return _i(keep)
+
     # ---- density profiles of a trapped system (pigs_density_*: slice Nb, 64-bit counts per walker)
     def density_init(self, Nbin, half_width):
         """Allocate and zero the accumulators: Nbin bins per axis over [-half_width, half_width) (planar) and over
@@ -449,11 +473,7 @@ class PigsContext:
 
     def density_accumulate(self, walkers=None):
         """Queue one sample of slice Nb of `walkers` (None: all) on the context's stream; does not wait."""
-        if walkers is None:
-            _chk(self.L, self.L.pigs_density_accumulate(self.h, self.n_walkers, None), "pigs_density_accumulate")
-        else:
-            wl = _i32(walkers).ravel()
-            _chk(self.L, self.L.pigs_density_accumulate(self.h, wl.size, _i(wl)), "pigs_density_accumulate")
+        self._accumulate("pigs_density_accumulate", walkers)
 
     def density_read(self, reset=None):
         """dict of int64 arrays: planar [W, Nbin] (dim 1) or [W, Nbin, Nbin] (x fastest in the last axis), radial
@@ -465,16 +485,9 @@ class PigsContext:
         W, dp = self.n_walkers, min(self.cfg.dim, 2)
         out = {"planar": np.zeros((W,) + (nb,) * dp, np.int64), "radial": np.zeros((W, nb), np.int64),
                "pair": np.zeros((W, nb), np.int64), "samples": np.zeros(W, np.int64)}
-        if reset is None or reset is False:
-            mask = None
-        else:
-            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
-            if keep.size != W:
-                raise ValueError("reset mask needs one entry per walker")
-            mask = _i(keep)
-        lp = C.POINTER(C.c_int64)
-        _chk(self.L, self.L.pigs_density_read(self.h, *(out[k].ctypes.data_as(lp) for k in ("planar", "radial", "pair", "samples")),
-                                              mask), "pigs_density_read")
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_density_read(self.h, *(_l(out[k]) for k in ("planar", "radial", "pair", "samples")), mask),
+             "pigs_density_read")
         return out
 
     # ---- imaginary-time density correlations of a periodic system (pigs_fqt_*: raw sums per walker, lag, harmonic, axis)
@@ -487,11 +500,7 @@ class PigsContext:
 
     def fqt_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
-        if walkers is None:
-            _chk(self.L, self.L.pigs_fqt_accumulate(self.h, self.n_walkers, None), "pigs_fqt_accumulate")
-        else:
-            wl = _i32(walkers).ravel()
-            _chk(self.L, self.L.pigs_fqt_accumulate(self.h, wl.size, _i(wl)), "pigs_fqt_accumulate")
+        self._accumulate("pigs_fqt_accumulate", walkers)
 
     def fqt_read(self, reset=None):
         """dict: F, the raw sums [W, Ntau+1, Nk, dim] (profiles.normalize_fqt divides them), and samples [W] (int64).
@@ -501,15 +510,8 @@ class PigsContext:
             raise PigsError("fqt_read: fqt_init first")
         W = self.n_walkers
         out = {"F": np.zeros((W,) + shape), "samples": np.zeros(W, np.int64)}
-        if reset is None or reset is False:
-            mask = None
-        else:
-            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
-            if keep.size != W:
-                raise ValueError("reset mask needs one entry per walker")
-            mask = _i(keep)
-        _chk(self.L, self.L.pigs_fqt_read(self.h, _d(out["F"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
-             "pigs_fqt_read")
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_fqt_read(self.h, _d(out["F"]), _l(out["samples"]), mask), "pigs_fqt_read")
         return out
 
     # ---- imaginary-time profiles (pigs_tau_*: raw sums Vpair, Vext, W, D2 per walker and slice)
@@ -520,26 +522,15 @@ class PigsContext:
 
     def tau_accumulate(self, walkers=None):
         """Queue one sample of every slice of `walkers` (None: all) on the context's stream; does not wait."""
-        if walkers is None:
-            _chk(self.L, self.L.pigs_tau_accumulate(self.h, self.n_walkers, None), "pigs_tau_accumulate")
-        else:
-            wl = _i32(walkers).ravel()
-            _chk(self.L, self.L.pigs_tau_accumulate(self.h, wl.size, _i(wl)), "pigs_tau_accumulate")
+        self._accumulate("pigs_tau_accumulate", walkers)
 
     def tau_read(self, reset=None):
         """dict: Q, the raw sums [W, 2Nb+1, 4] (Vpair, Vext, W, D2; profiles.normalize_tau divides them), and samples [W]
         (int64).  reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
         W = self.n_walkers
         out = {"Q": np.zeros((W, self.cfg.M, 4)), "samples": np.zeros(W, np.int64)}
-        if reset is None or reset is False:
-            mask = None
-        else:
-            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
-            if keep.size != W:
-                raise ValueError("reset mask needs one entry per walker")
-            mask = _i(keep)
-        _chk(self.L, self.L.pigs_tau_read(self.h, _d(out["Q"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
-             "pigs_tau_read")
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_tau_read(self.h, _d(out["Q"]), _l(out["samples"]), mask), "pigs_tau_read")
         return out
 
     # ---- vector structure factor on the full reciprocal grid (pigs_sqv_*: raw sums per walker and vector)
@@ -562,11 +553,7 @@ class PigsContext:
 
     def sqv_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
-        if walkers is None:
-            _chk(self.L, self.L.pigs_sqv_accumulate(self.h, self.n_walkers, None), "pigs_sqv_accumulate")
-        else:
-            wl = _i32(walkers).ravel()
-            _chk(self.L, self.L.pigs_sqv_accumulate(self.h, wl.size, _i(wl)), "pigs_sqv_accumulate")
+        self._accumulate("pigs_sqv_accumulate", walkers)
 
     def sqv_read(self, reset=None):
         """dict: S, the raw sums [W, Nq] (profiles.normalize_sqv divides them), and samples [W] (int64).
@@ -576,15 +563,8 @@ class PigsContext:
             raise PigsError("sqv_read: sqv_init first")
         W = self.n_walkers
         out = {"S": np.zeros((W, nq)), "samples": np.zeros(W, np.int64)}
-        if reset is None or reset is False:
-            mask = None
-        else:
-            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
-            if keep.size != W:
-                raise ValueError("reset mask needs one entry per walker")
-            mask = _i(keep)
-        _chk(self.L, self.L.pigs_sqv_read(self.h, _d(out["S"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
-             "pigs_sqv_read")
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_sqv_read(self.h, _d(out["S"]), _l(out["samples"]), mask), "pigs_sqv_read")
         return out
 
     # ---- F(q,tau) on the full reciprocal grid (pigs_fqv_*: raw sums per walker, lag and vector)
@@ -608,11 +588,7 @@ class PigsContext:
 
     def fqv_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
-        if walkers is None:
-            _chk(self.L, self.L.pigs_fqv_accumulate(self.h, self.n_walkers, None), "pigs_fqv_accumulate")
-        else:
-            wl = _i32(walkers).ravel()
-            _chk(self.L, self.L.pigs_fqv_accumulate(self.h, wl.size, _i(wl)), "pigs_fqv_accumulate")
+        self._accumulate("pigs_fqv_accumulate", walkers)
 
     def fqv_read(self, reset=None):
         """dict: F, the raw sums [W, Ntau+1, Nq] (profiles.normalize_fqv divides them), and samples [W] (int64).
@@ -622,15 +598,8 @@ class PigsContext:
             raise PigsError("fqv_read: fqv_init first")
         W = self.n_walkers
         out = {"F": np.zeros((W,) + shape), "samples": np.zeros(W, np.int64)}
-        if reset is None or reset is False:
-            mask = None
-        else:
-            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
-            if keep.size != W:
-                raise ValueError("reset mask needs one entry per walker")
-            mask = _i(keep)
-        _chk(self.L, self.L.pigs_fqv_read(self.h, _d(out["F"]), out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask),
-             "pigs_fqv_read")
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_fqv_read(self.h, _d(out["F"]), _l(out["samples"]), mask), "pigs_fqv_read")
         return out
 
     # ---- self part of F(q,tau) and the imaginary-time displacement (pigs_fqs_*: raw sums per walker, lag and vector)
@@ -654,11 +623,7 @@ class PigsContext:
 
     def fqs_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
-        if walkers is None:
-            _chk(self.L, self.L.pigs_fqs_accumulate(self.h, self.n_walkers, None), "pigs_fqs_accumulate")
-        else:
-            wl = _i32(walkers).ravel()
-            _chk(self.L, self.L.pigs_fqs_accumulate(self.h, wl.size, _i(wl)), "pigs_fqs_accumulate")
+        self._accumulate("pigs_fqs_accumulate", walkers)
 
     def fqs_read(self, reset=None):
         """dict: F, the raw sums [W, Ntau+1, Nq] (profiles.normalize_fqs divides them), D, the raw sums of r^2 and r^4
@@ -669,15 +634,8 @@ class PigsContext:
             raise PigsError("fqs_read: fqs_init first")
         W = self.n_walkers
         out = {"F": np.zeros((W,) + shape), "D": np.zeros((W, shape[0], 2)), "samples": np.zeros(W, np.int64)}
-        if reset is None or reset is False:
-            mask = None
-        else:
-            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
-            if keep.size != W:
-                raise ValueError("reset mask needs one entry per walker")
-            mask = _i(keep)
-        _chk(self.L, self.L.pigs_fqs_read(self.h, _d(out["F"]), _d(out["D"]),
-                                          out["samples"].ctypes.data_as(C.POINTER(C.c_int64)), mask), "pigs_fqs_read")
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_fqs_read(self.h, _d(out["F"]), _d(out["D"]), _l(out["samples"]), mask), "pigs_fqs_read")
         return out
 
     # ---- pair distribution on the vector grid over a slice window (pigs_grv_*: 64-bit counts per walker)
@@ -693,11 +651,7 @@ class PigsContext:
 
     def grv_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
-        if walkers is None:
-            _chk(self.L, self.L.pigs_grv_accumulate(self.h, self.n_walkers, None), "pigs_grv_accumulate")
-        else:
-            wl = _i32(walkers).ravel()
-            _chk(self.L, self.L.pigs_grv_accumulate(self.h, wl.size, _i(wl)), "pigs_grv_accumulate")
+        self._accumulate("pigs_grv_accumulate", walkers)
 
     def grv_read(self, reset=None):
         """dict of int64 arrays: vec [W, Nbin, ..(dim times)] (x on the last axis), radial [W, Nr], samples [W]
@@ -709,16 +663,8 @@ class PigsContext:
         W = self.n_walkers
         out = {"vec": np.zeros((W,) + (shp[0],) * self.cfg.dim, np.int64), "radial": np.zeros((W, shp[1]), np.int64),
                "samples": np.zeros(W, np.int64)}
-        if reset is None or reset is False:
-            mask = None
-        else:
-            keep = np.ones(W, np.int32) if reset is True else _i32(reset)
-            if keep.size != W:
-                raise ValueError("reset mask needs one entry per walker")
-            mask = _i(keep)
-        lp = C.POINTER(C.c_int64)
-        _chk(self.L, self.L.pigs_grv_read(self.h, *(out[k].ctypes.data_as(lp) for k in ("vec", "radial", "samples")), mask),
-             "pigs_grv_read")
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_grv_read(self.h, *(_l(out[k]) for k in ("vec", "radial", "samples")), mask), "pigs_grv_read")
         return out
 
     # ---- K5

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <utility>
 #include <condition_variable>
@@ -193,6 +194,8 @@ struct pigs_ctx {
     std::vector<int32_t> a_sw, a_sb;        // slot lists: must outlive the asynchronous upload
     struct { bool on = false, launched = false; EstBatch b; } a_pend;
     Event       ev_gate;                    // recorded behind the TranslateChain kernel of the next step (see launch_pending_estimators)
+    // the launches of the seven accumulator families below (each_launch): which walkers the current one holds
+    WalkerMarks list_marks;
     // density profiles of a trapped system (pigs_density_*): per-walker 64-bit counts, walker-major
     DevBuf<unsigned long long> d_dplanar, d_dradial, d_dpair, d_dsamples;
     int         dens_nbin = 0;              // 0: pigs_density_init not called yet
@@ -204,8 +207,6 @@ struct pigs_ctx {
     DevBuf<unsigned long long> d_fqt_samples;
     int         fqt_nk = 0;                 // 0: pigs_fqt_init not called yet
     int         fqt_ntau = 0, fqt_window = 0, fqt_slots = 0;
-    std::vector<int64_t> fqt_mark;          // per walker: the last launch (fqt_launch) that listed it
-    int64_t     fqt_launch = 0;
     // vector structure factor on the full reciprocal grid (pigs_sqv_*): raw sums [walker][iqv], the samples per walker,
     // and the C^2 + S^2 scratch of one launch's window slices ([sqv_slots][2 window + 1][Nq])
     DevBuf<double> d_sqv_acc, d_sqv_rho2;
@@ -213,8 +214,6 @@ struct pigs_ctx {
     int         sqv_nmax = 0;               // 0: pigs_sqv_init not called yet
     int         sqv_window = 0, sqv_slots = 0;
     int64_t     sqv_nq = 0;
-    std::vector<int64_t> sqv_mark;          // per walker: the last launch (sqv_launch) that listed it
-    int64_t     sqv_launch = 0;
     // F(q,tau) on the vectors of pigs_sqv_* (pigs_fqv_*): raw sums [walker][l][iqv], the samples per walker, and the
     // (C, S) scratch of one launch's window slices ([fqv_slots][2 window + 1][Nq][2])
     DevBuf<double> d_fqv_acc, d_fqv_rho;
@@ -222,8 +221,6 @@ struct pigs_ctx {
     int         fqv_nmax = 0;               // 0: pigs_fqv_init not called yet
     int         fqv_ntau = 0, fqv_window = 0, fqv_slots = 0;
     int64_t     fqv_nq = 0;
-    std::vector<int64_t> fqv_mark;          // per walker: the last launch (fqv_launch) that listed it
-    int64_t     fqv_launch = 0;
     // self part of F(q,tau) and the imaginary-time displacement (pigs_fqs_*): raw sums F [walker][l][iqv] and
     // D [walker][l][2], the samples per walker; no scratch (pigs_fqs.hip keeps the phasors in LDS)
     DevBuf<double> d_fqs_acc, d_fqs_dsp;
@@ -231,8 +228,6 @@ struct pigs_ctx {
     int         fqs_nmax = 0;               // 0: pigs_fqs_init not called yet
     int         fqs_ntau = 0, fqs_window = 0;
     int64_t     fqs_nq = 0;
-    std::vector<int64_t> fqs_mark;          // per walker: the last launch (fqs_launch) that listed it
-    int64_t     fqs_launch = 0;
     // pair distribution on the vector grid over a slice window (pigs_grv_*): per-walker 64-bit counts, walker-major
     DevBuf<unsigned long long> d_grv_vec, d_grv_radial, d_grv_samples;
     int         grv_nbin = 0;               // 0: pigs_grv_init not called yet
@@ -244,8 +239,6 @@ struct pigs_ctx {
     DevBuf<double> d_tau_acc;
     DevBuf<unsigned long long> d_tau_samples;
     bool        tau_ready = false;          // pigs_tau_init called
-    std::vector<int64_t> tau_mark;          // per walker: the last launch (tau_launch) that listed it
-    int64_t     tau_launch = 0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -1352,6 +1345,93 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     return PIGS_OK;
 }
 
+// ---- what the seven per-walker accumulator families below share ----------------------------------
+extern "C++" {      // templates
+
+// *_init, once the request is accepted: no accumulate may be in flight on the buffers being replaced, and until the new
+// ones stand the family counts as uninitialised (`ready` is the field its entry points test)
+template <typename Flag>
+static int init_begin(pigs_ctx *c, Flag &ready)
+{
+    HIPCHK(hipStreamSynchronize(c->stream));
+    ready = Flag();
+    return PIGS_OK;
+}
+
+// exactly n elements, and their zeroing queued on the context's stream
+template <typename T>
+static hipError_t alloc_zeroed(pigs_ctx *c, DevBuf<T> &b, size_t n)
+{
+    const hipError_t e = b.alloc(n);
+    return e == hipSuccess ? hipMemsetAsync(b.p, 0, n * sizeof(T), c->stream) : e;
+}
+
+// *_accumulate: `launch(m, list)` for every launch that take_walkers (pigs_walker_split.h has the rule) cuts out of the
+// checked list sw, at most `cap` walkers each; `walkers` is the caller's list (null: left out), `what` names the launcher
+template <typename Launch>
+static int each_launch(pigs_ctx *c, const std::vector<int32_t> &sw, const int32_t *walkers, bool unique, int cap,
+                       const char *what, Launch launch)
+{
+    if (unique && walkers) c->list_marks.last.resize(c->n_walkers, 0);
+    for (int i0 = 0; i0 < (int)sw.size();) {
+        WalkerList L{};
+        const int m = take_walkers(sw, walkers != nullptr, i0, cap, unique, c->list_marks, L);
+        const hipError_t e = launch(m, L);
+        if (e != hipSuccess) return fail(PIGS_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+        i0 += m;
+    }
+    return PIGS_OK;
+}
+
+} // extern "C++"
+
+// *_read: one accumulator array of 8-byte elements, `per` of them per walker, walker-major, and where its copy goes
+struct AccArray { void *dev; size_t per; void *host; };
+
+// copy every array to the host, then zero the flagged walkers (one memset per array and run of consecutive walkers), wait
+static int read_and_reset(pigs_ctx *c, std::initializer_list<AccArray> arrays, const int32_t *reset)
+{
+    const size_t W = (size_t)c->n_walkers, u = 8;
+    hipStream_t s = c->stream;
+    for (const AccArray &a : arrays) HIPCHK(hipMemcpyAsync(a.host, a.dev, W * a.per * u, hipMemcpyDeviceToHost, s));
+    for (size_t w = 0; reset && w < W;) {
+        if (!reset[w]) { ++w; continue; }
+        size_t e = w;
+        while (e < W && reset[e]) ++e;
+        for (const AccArray &a : arrays) HIPCHK(hipMemsetAsync((char *)a.dev + w * a.per * u, 0, (e - w) * a.per * u, s));
+        w = e;
+    }
+    SYNC_CHECKED(c);
+    return PIGS_OK;
+}
+
+// pigs_{sqv,fqv,fqs}_count and _vectors: the family's nmax (0: not initialised) and Nq
+static int grid_count(pigs_ctx *c, const char *family, int nmax, int64_t nq, int64_t *Nq)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!nmax) return fail(PIGS_ERR_ARG, "pigs_%s_init first", family);
+    if (!Nq) return fail(PIGS_ERR_ARG, "null output");
+    *Nq = nq;
+    return PIGS_OK;
+}
+
+// vector iqv has rank iqv + Nq + 1 among all (2 nmax + 1)^dim vectors, n_1 slowest (include/pigs_hip.h)
+static int grid_vectors(pigs_ctx *c, const char *family, int nmax, int64_t nq, int32_t *n)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!nmax) return fail(PIGS_ERR_ARG, "pigs_%s_init first", family);
+    if (!n) return fail(PIGS_ERR_ARG, "null output");
+    const int dim = c->P.dim, S = 2 * nmax + 1;
+    for (int64_t iqv = 0; iqv < nq; ++iqv) {
+        int64_t r = iqv + nq + 1;
+        for (int k = dim - 1; k >= 0; --k) {
+            n[iqv * dim + k] = (int32_t)(r % S) - nmax;
+            r /= S;
+        }
+    }
+    return PIGS_OK;
+}
+
 // ---- density profiles of a trapped system ------------------------------------------------------
 // Three per-walker histograms of slice Nb (pigs_density.hip) accumulated on the device and read per block.  The widths
 // are computed here, once, in double: b = (2h)/Nbin for the planar grid over [-h, h), br = h/Nbin for r and d in [0, h).
@@ -1364,16 +1444,11 @@ int pigs_density_init(pigs_ctx *c, int32_t Nbin, double half_width)
     size_t np = 1;
     for (int k = 0; k < dp; ++k) np *= (size_t)Nbin;
     const size_t W = (size_t)c->n_walkers;
-    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
-    c->dens_nbin = 0;
-    HIPCHK(c->d_dplanar.alloc(W * np));
-    HIPCHK(c->d_dradial.alloc(W * Nbin));
-    HIPCHK(c->d_dpair.alloc(W * Nbin));
-    HIPCHK(c->d_dsamples.alloc(W));
-    HIPCHK(hipMemsetAsync(c->d_dplanar.p, 0, W * np * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_dradial.p, 0, W * Nbin * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_dpair.p, 0, W * Nbin * sizeof(unsigned long long), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_dsamples.p, 0, W * sizeof(unsigned long long), c->stream));
+    rc = init_begin(c, c->dens_nbin); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_dplanar, W * np));
+    HIPCHK(alloc_zeroed(c, c->d_dradial, W * Nbin));
+    HIPCHK(alloc_zeroed(c, c->d_dpair, W * Nbin));
+    HIPCHK(alloc_zeroed(c, c->d_dsamples, W));
     SYNC_CHECKED(c);
     c->dens_nbin = Nbin;
     c->dens_nplanar = np;
@@ -1390,15 +1465,11 @@ int pigs_density_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
     if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     std::vector<int32_t> sw;
     rc = walker_list(c, n, walkers, sw); if (rc) return rc;
-    // the list goes by value in the kernel arguments: queued on the context's stream, nothing to wait for
-    for (int i0 = 0; i0 < n; i0 += kDensListMax) {
-        const int m = std::min(kDensListMax, n - i0);
-        DensList L{};
-        for (int i = 0; i < m; ++i) L.w[i] = sw[i0 + i];
-        HIPCHK(launch_density(c->P, c->d_paths.p, m, L, c->dens_nbin, c->dens_h, c->dens_b, c->dens_br, c->d_dplanar.p,
-                              c->d_dradial.p, c->d_dpair.p, c->d_dsamples.p, c->stream));
-    }
-    return PIGS_OK;
+    // integer atomics: a walker may appear twice in one launch
+    return each_launch(c, sw, walkers, false, kWalkerListMax, "launch_density", [&](int m, const WalkerList &L) {
+        return launch_density(c->P, c->d_paths.p, m, L, c->dens_nbin, c->dens_h, c->dens_b, c->dens_br, c->d_dplanar.p,
+                              c->d_dradial.p, c->d_dpair.p, c->d_dsamples.p, c->stream);
+    });
 }
 
 int pigs_density_read(pigs_ctx *c, int64_t *planar, int64_t *radial, int64_t *pair, int64_t *samples, const int32_t *reset)
@@ -1406,28 +1477,9 @@ int pigs_density_read(pigs_ctx *c, int64_t *planar, int64_t *radial, int64_t *pa
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->dens_nbin) return fail(PIGS_ERR_ARG, "pigs_density_init first");
     if (!planar || !radial || !pair || !samples) return fail(PIGS_ERR_ARG, "null output");
-    const size_t W = (size_t)c->n_walkers, nb = (size_t)c->dens_nbin, np = c->dens_nplanar;
-    const size_t u = sizeof(unsigned long long);
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(planar, c->d_dplanar.p, W * np * u, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(radial, c->d_dradial.p, W * nb * u, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(pair, c->d_dpair.p, W * nb * u, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(samples, c->d_dsamples.p, W * u, hipMemcpyDeviceToHost, s));
-    if (reset) {
-        // zero the accumulators of the flagged walkers, one memset per array and run of consecutive walkers
-        for (size_t w = 0; w < W;) {
-            if (!reset[w]) { ++w; continue; }
-            size_t e = w;
-            while (e < W && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_dplanar.p + w * np, 0, (e - w) * np * u, s));
-            HIPCHK(hipMemsetAsync(c->d_dradial.p + w * nb, 0, (e - w) * nb * u, s));
-            HIPCHK(hipMemsetAsync(c->d_dpair.p + w * nb, 0, (e - w) * nb * u, s));
-            HIPCHK(hipMemsetAsync(c->d_dsamples.p + w, 0, (e - w) * u, s));
-            w = e;
-        }
-    }
-    SYNC_CHECKED(c);
-    return PIGS_OK;
+    const size_t nb = (size_t)c->dens_nbin;
+    return read_and_reset(c, {{c->d_dplanar.p, c->dens_nplanar, planar}, {c->d_dradial.p, nb, radial}, {c->d_dpair.p, nb, pair},
+                              {c->d_dsamples.p, 1, samples}}, reset);
 }
 
 // ---- imaginary-time density correlations F(q,tau) of a periodic system ---------------------------
@@ -1440,14 +1492,11 @@ int pigs_fqt_init(pigs_ctx *c, int32_t Nk, int32_t Ntau, int32_t window)
     if (Nk < 1 || window < 0 || window > c->P.Nb || Ntau < 0 || Ntau > 2 * window)
         return fail(PIGS_ERR_ARG, "pigs_fqt_init: Nk=%d Ntau=%d window=%d (Nb=%d)", Nk, Ntau, window, c->P.Nb);
     const size_t W = (size_t)c->n_walkers, per = (size_t)(Ntau + 1) * Nk * c->P.dim;
-    const int slots = std::min(c->n_walkers, kFqtListMax);
-    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
-    c->fqt_nk = 0;
-    HIPCHK(c->d_fqt_acc.alloc(W * per));
-    HIPCHK(c->d_fqt_samples.alloc(W));
+    const int slots = std::min(c->n_walkers, kWalkerListMax);
+    rc = init_begin(c, c->fqt_nk); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_fqt_acc, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_fqt_samples, W));
     HIPCHK(c->d_fqt_rho.alloc((size_t)slots * (2 * window + 1) * 2 * Nk * c->P.dim));
-    HIPCHK(hipMemsetAsync(c->d_fqt_acc.p, 0, W * per * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_fqt_samples.p, 0, W * sizeof(unsigned long long), c->stream));
     SYNC_CHECKED(c);
     c->fqt_nk = Nk;
     c->fqt_ntau = Ntau;
@@ -1464,25 +1513,11 @@ int pigs_fqt_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
     if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     std::vector<int32_t> sw;
     rc = walker_list(c, n, walkers, sw); if (rc) return rc;
-    // The list goes by value in the kernel arguments: queued on the context's stream, nothing to wait for.  A launch
-    // ends where the scratch is full or a walker would appear in it a second time (one thread owns an accumulator
-    // element per launch); the stream orders the launches, so a walker listed twice is added twice.
-    // A list left out (0..n-1) holds no repeats and needs no marks.
-    if (walkers) c->fqt_mark.resize(c->n_walkers, 0);
-    for (int i0 = 0; i0 < n;) {
-        const int64_t launch = ++c->fqt_launch;
-        FqtList L{};
-        int m = 0;
-        while (i0 + m < n && m < c->fqt_slots && !(walkers && c->fqt_mark[sw[i0 + m]] == launch)) {
-            if (walkers) c->fqt_mark[sw[i0 + m]] = launch;
-            L.w[m] = sw[i0 + m];
-            ++m;
-        }
-        HIPCHK(launch_fqt(c->P, c->d_paths.p, m, L, c->fqt_window, c->fqt_ntau, c->fqt_nk, c->d_fqt_rho.p, c->d_fqt_acc.p,
-                          c->d_fqt_samples.p, c->stream));
-        i0 += m;
-    }
-    return PIGS_OK;
+    // one thread owns an accumulator element per launch, and the scratch holds fqt_slots walkers
+    return each_launch(c, sw, walkers, true, c->fqt_slots, "launch_fqt", [&](int m, const WalkerList &L) {
+        return launch_fqt(c->P, c->d_paths.p, m, L, c->fqt_window, c->fqt_ntau, c->fqt_nk, c->d_fqt_rho.p, c->d_fqt_acc.p,
+                          c->d_fqt_samples.p, c->stream);
+    });
 }
 
 int pigs_fqt_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset)
@@ -1490,23 +1525,8 @@ int pigs_fqt_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->fqt_nk) return fail(PIGS_ERR_ARG, "pigs_fqt_init first");
     if (!F || !samples) return fail(PIGS_ERR_ARG, "null output");
-    const size_t W = (size_t)c->n_walkers, per = (size_t)(c->fqt_ntau + 1) * c->fqt_nk * c->P.dim;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(F, c->d_fqt_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(samples, c->d_fqt_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (reset) {
-        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
-        for (size_t w = 0; w < W;) {
-            if (!reset[w]) { ++w; continue; }
-            size_t e = w;
-            while (e < W && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_fqt_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
-            HIPCHK(hipMemsetAsync(c->d_fqt_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
-            w = e;
-        }
-    }
-    SYNC_CHECKED(c);
-    return PIGS_OK;
+    const size_t per = (size_t)(c->fqt_ntau + 1) * c->fqt_nk * c->P.dim;
+    return read_and_reset(c, {{c->d_fqt_acc.p, per, F}, {c->d_fqt_samples.p, 1, samples}}, reset);
 }
 
 // ---- imaginary-time profiles: V(tau), the virial and the link lengths of every slice --------------
@@ -1516,12 +1536,9 @@ int pigs_tau_init(pigs_ctx *c)
     int rc = check_ctx(c); if (rc) return rc;
     rc = check_cm(c); if (rc) return rc;
     const size_t W = (size_t)c->n_walkers, per = (size_t)c->P.M * 4;
-    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
-    c->tau_ready = false;
-    HIPCHK(c->d_tau_acc.alloc(W * per));
-    HIPCHK(c->d_tau_samples.alloc(W));
-    HIPCHK(hipMemsetAsync(c->d_tau_acc.p, 0, W * per * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_tau_samples.p, 0, W * sizeof(unsigned long long), c->stream));
+    rc = init_begin(c, c->tau_ready); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_tau_acc, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_tau_samples, W));
     SYNC_CHECKED(c);
     c->tau_ready = true;
     return PIGS_OK;
@@ -1535,23 +1552,10 @@ int pigs_tau_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
     if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     std::vector<int32_t> sw;
     rc = walker_list(c, n, walkers, sw); if (rc) return rc;
-    // As pigs_fqt_accumulate: the list goes by value in the kernel arguments, and a launch ends where it is full or a
-    // walker would appear in it a second time (one workgroup owns an accumulator element per launch); the stream orders
-    // the launches, so a walker listed twice is added twice.  A list left out (0..n-1) holds no repeats.
-    if (walkers) c->tau_mark.resize(c->n_walkers, 0);
-    for (int i0 = 0; i0 < n;) {
-        const int64_t launch = ++c->tau_launch;
-        TauList L{};
-        int m = 0;
-        while (i0 + m < n && m < kTauListMax && !(walkers && c->tau_mark[sw[i0 + m]] == launch)) {
-            if (walkers) c->tau_mark[sw[i0 + m]] = launch;
-            L.w[m] = sw[i0 + m];
-            ++m;
-        }
-        HIPCHK(launch_tau(c->P, c->d_paths.p, c->d_VT.p, m, L, c->d_tau_acc.p, c->d_tau_samples.p, c->stream));
-        i0 += m;
-    }
-    return PIGS_OK;
+    // one workgroup owns an accumulator element per launch
+    return each_launch(c, sw, walkers, true, kWalkerListMax, "launch_tau", [&](int m, const WalkerList &L) {
+        return launch_tau(c->P, c->d_paths.p, c->d_VT.p, m, L, c->d_tau_acc.p, c->d_tau_samples.p, c->stream);
+    });
 }
 
 int pigs_tau_read(pigs_ctx *c, double *Q, int64_t *samples, const int32_t *reset)
@@ -1559,42 +1563,12 @@ int pigs_tau_read(pigs_ctx *c, double *Q, int64_t *samples, const int32_t *reset
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->tau_ready) return fail(PIGS_ERR_ARG, "pigs_tau_init first");
     if (!Q || !samples) return fail(PIGS_ERR_ARG, "null output");
-    const size_t W = (size_t)c->n_walkers, per = (size_t)c->P.M * 4;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(Q, c->d_tau_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(samples, c->d_tau_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (reset) {
-        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
-        for (size_t w = 0; w < W;) {
-            if (!reset[w]) { ++w; continue; }
-            size_t e = w;
-            while (e < W && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_tau_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
-            HIPCHK(hipMemsetAsync(c->d_tau_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
-            w = e;
-        }
-    }
-    SYNC_CHECKED(c);
-    return PIGS_OK;
+    return read_and_reset(c, {{c->d_tau_acc.p, (size_t)c->P.M * 4, Q}, {c->d_tau_samples.p, 1, samples}}, reset);
 }
 
 // ---- vector structure factor S(q) on the full reciprocal grid of a periodic system ----------------
 // Raw sums per walker and vector (pigs_sqv.hip), accumulated on the device and read per block.
 constexpr size_t kSqvScratchMax = (size_t)256 << 20;      // bytes of slice scratch behind one launch
-
-// vector iqv has rank iqv + Nq + 1 among all (2 nmax + 1)^dim vectors, n_1 slowest (include/pigs_hip.h): the one
-// enumeration of pigs_sqv_vectors and pigs_fqv_vectors
-static void sqv_enumerate(int dim, int nmax, int64_t Nq, int32_t *n)
-{
-    const int S = 2 * nmax + 1;
-    for (int64_t iqv = 0; iqv < Nq; ++iqv) {
-        int64_t r = iqv + Nq + 1;
-        for (int k = dim - 1; k >= 0; --k) {
-            n[iqv * dim + k] = (int32_t)(r % S) - nmax;
-            r /= S;
-        }
-    }
-}
 
 int pigs_sqv_init(pigs_ctx *c, int32_t nmax, int32_t window)
 {
@@ -1607,15 +1581,12 @@ int pigs_sqv_init(pigs_ctx *c, int32_t nmax, int32_t window)
     const SqvShape sh = sqv_shape(c->P.dim, nmax);
     const size_t W = (size_t)c->n_walkers, per = (size_t)sh.Nq, slice = (size_t)(2 * window + 1) * per;
     // as many walkers per launch as the list holds and the scratch cap allows, one at the least
-    const int slots = (int)std::max<size_t>(1, std::min<size_t>(std::min(c->n_walkers, kSqvListMax),
+    const int slots = (int)std::max<size_t>(1, std::min<size_t>(std::min(c->n_walkers, kWalkerListMax),
                                                                 kSqvScratchMax / (slice * sizeof(double))));
-    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
-    c->sqv_nmax = 0;
-    HIPCHK(c->d_sqv_acc.alloc(W * per));
-    HIPCHK(c->d_sqv_samples.alloc(W));
+    rc = init_begin(c, c->sqv_nmax); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_sqv_acc, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_sqv_samples, W));
     HIPCHK(c->d_sqv_rho2.alloc((size_t)slots * slice));
-    HIPCHK(hipMemsetAsync(c->d_sqv_acc.p, 0, W * per * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_sqv_samples.p, 0, W * sizeof(unsigned long long), c->stream));
     SYNC_CHECKED(c);
     c->sqv_nmax = nmax;
     c->sqv_window = window;
@@ -1626,20 +1597,12 @@ int pigs_sqv_init(pigs_ctx *c, int32_t nmax, int32_t window)
 
 int pigs_sqv_count(pigs_ctx *c, int64_t *Nq)
 {
-    int rc = check_ctx(c); if (rc) return rc;
-    if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
-    if (!Nq) return fail(PIGS_ERR_ARG, "null output");
-    *Nq = c->sqv_nq;
-    return PIGS_OK;
+    return c ? grid_count(c, "sqv", c->sqv_nmax, c->sqv_nq, Nq) : fail(PIGS_ERR_ARG, "null context");
 }
 
 int pigs_sqv_vectors(pigs_ctx *c, int32_t *n)
 {
-    int rc = check_ctx(c); if (rc) return rc;
-    if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
-    if (!n) return fail(PIGS_ERR_ARG, "null output");
-    sqv_enumerate(c->P.dim, c->sqv_nmax, c->sqv_nq, n);
-    return PIGS_OK;
+    return c ? grid_vectors(c, "sqv", c->sqv_nmax, c->sqv_nq, n) : fail(PIGS_ERR_ARG, "null context");
 }
 
 int pigs_sqv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
@@ -1650,23 +1613,11 @@ int pigs_sqv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
     if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     std::vector<int32_t> sw;
     rc = walker_list(c, n, walkers, sw); if (rc) return rc;
-    // As pigs_fqt_accumulate: the list goes by value in the kernel arguments, and a launch ends where the scratch is
-    // full or a walker would appear in it a second time; the stream orders the launches.
-    if (walkers) c->sqv_mark.resize(c->n_walkers, 0);
-    for (int i0 = 0; i0 < n;) {
-        const int64_t launch = ++c->sqv_launch;
-        SqvList L{};
-        int m = 0;
-        while (i0 + m < n && m < c->sqv_slots && !(walkers && c->sqv_mark[sw[i0 + m]] == launch)) {
-            if (walkers) c->sqv_mark[sw[i0 + m]] = launch;
-            L.w[m] = sw[i0 + m];
-            ++m;
-        }
-        HIPCHK(launch_sqv(c->P, c->d_paths.p, m, L, c->sqv_window, c->sqv_nmax, c->d_sqv_rho2.p, c->d_sqv_acc.p,
-                          c->d_sqv_samples.p, c->stream));
-        i0 += m;
-    }
-    return PIGS_OK;
+    // one thread owns an accumulator element per launch, and the scratch holds sqv_slots walkers
+    return each_launch(c, sw, walkers, true, c->sqv_slots, "launch_sqv", [&](int m, const WalkerList &L) {
+        return launch_sqv(c->P, c->d_paths.p, m, L, c->sqv_window, c->sqv_nmax, c->d_sqv_rho2.p, c->d_sqv_acc.p,
+                          c->d_sqv_samples.p, c->stream);
+    });
 }
 
 int pigs_sqv_read(pigs_ctx *c, double *S, int64_t *samples, const int32_t *reset)
@@ -1674,23 +1625,7 @@ int pigs_sqv_read(pigs_ctx *c, double *S, int64_t *samples, const int32_t *reset
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->sqv_nmax) return fail(PIGS_ERR_ARG, "pigs_sqv_init first");
     if (!S || !samples) return fail(PIGS_ERR_ARG, "null output");
-    const size_t W = (size_t)c->n_walkers, per = (size_t)c->sqv_nq;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(S, c->d_sqv_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(samples, c->d_sqv_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (reset) {
-        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
-        for (size_t w = 0; w < W;) {
-            if (!reset[w]) { ++w; continue; }
-            size_t e = w;
-            while (e < W && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_sqv_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
-            HIPCHK(hipMemsetAsync(c->d_sqv_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
-            w = e;
-        }
-    }
-    SYNC_CHECKED(c);
-    return PIGS_OK;
+    return read_and_reset(c, {{c->d_sqv_acc.p, (size_t)c->sqv_nq, S}, {c->d_sqv_samples.p, 1, samples}}, reset);
 }
 
 // ---- F(q,tau) on the full reciprocal grid of a periodic system -----------------------------------
@@ -1712,15 +1647,12 @@ int pigs_fqv_init(pigs_ctx *c, int32_t nmax, int32_t Ntau, int32_t window)
     if ((double)W * ((double)per + 1.0) * 8.0 > 2147483648.0)
         return fail(PIGS_ERR_ARG, "pigs_fqv_init: %zu walkers x (%d x %lld + 1) sums pass 2 GiB", W, Ntau + 1, (long long)sh.Nq);
     // as many walkers per launch as the list holds and the scratch cap (that of pigs_sqv_*) allows, one at the least
-    const int slots = (int)std::max<size_t>(1, std::min<size_t>(std::min(c->n_walkers, kFqvListMax),
+    const int slots = (int)std::max<size_t>(1, std::min<size_t>(std::min(c->n_walkers, kWalkerListMax),
                                                                 kSqvScratchMax / (slice * sizeof(double))));
-    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
-    c->fqv_nmax = 0;
-    HIPCHK(c->d_fqv_acc.alloc(W * per));
-    HIPCHK(c->d_fqv_samples.alloc(W));
+    rc = init_begin(c, c->fqv_nmax); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_fqv_acc, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_fqv_samples, W));
     HIPCHK(c->d_fqv_rho.alloc((size_t)slots * slice));
-    HIPCHK(hipMemsetAsync(c->d_fqv_acc.p, 0, W * per * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_fqv_samples.p, 0, W * sizeof(unsigned long long), c->stream));
     SYNC_CHECKED(c);
     c->fqv_nmax = nmax;
     c->fqv_ntau = Ntau;
@@ -1732,20 +1664,12 @@ int pigs_fqv_init(pigs_ctx *c, int32_t nmax, int32_t Ntau, int32_t window)
 
 int pigs_fqv_count(pigs_ctx *c, int64_t *Nq)
 {
-    int rc = check_ctx(c); if (rc) return rc;
-    if (!c->fqv_nmax) return fail(PIGS_ERR_ARG, "pigs_fqv_init first");
-    if (!Nq) return fail(PIGS_ERR_ARG, "null output");
-    *Nq = c->fqv_nq;
-    return PIGS_OK;
+    return c ? grid_count(c, "fqv", c->fqv_nmax, c->fqv_nq, Nq) : fail(PIGS_ERR_ARG, "null context");
 }
 
 int pigs_fqv_vectors(pigs_ctx *c, int32_t *n)
 {
-    int rc = check_ctx(c); if (rc) return rc;
-    if (!c->fqv_nmax) return fail(PIGS_ERR_ARG, "pigs_fqv_init first");
-    if (!n) return fail(PIGS_ERR_ARG, "null output");
-    sqv_enumerate(c->P.dim, c->fqv_nmax, c->fqv_nq, n);
-    return PIGS_OK;
+    return c ? grid_vectors(c, "fqv", c->fqv_nmax, c->fqv_nq, n) : fail(PIGS_ERR_ARG, "null context");
 }
 
 int pigs_fqv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
@@ -1756,23 +1680,11 @@ int pigs_fqv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
     if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     std::vector<int32_t> sw;
     rc = walker_list(c, n, walkers, sw); if (rc) return rc;
-    // As pigs_fqt_accumulate: the list goes by value in the kernel arguments, and a launch ends where the scratch is
-    // full or a walker would appear in it a second time; the stream orders the launches.
-    if (walkers) c->fqv_mark.resize(c->n_walkers, 0);
-    for (int i0 = 0; i0 < n;) {
-        const int64_t launch = ++c->fqv_launch;
-        FqvList L{};
-        int m = 0;
-        while (i0 + m < n && m < c->fqv_slots && !(walkers && c->fqv_mark[sw[i0 + m]] == launch)) {
-            if (walkers) c->fqv_mark[sw[i0 + m]] = launch;
-            L.w[m] = sw[i0 + m];
-            ++m;
-        }
-        HIPCHK(launch_fqv(c->P, c->d_paths.p, m, L, c->fqv_window, c->fqv_ntau, c->fqv_nmax, c->d_fqv_rho.p, c->d_fqv_acc.p,
-                          c->d_fqv_samples.p, c->stream));
-        i0 += m;
-    }
-    return PIGS_OK;
+    // one thread owns an accumulator element per launch, and the scratch holds fqv_slots walkers
+    return each_launch(c, sw, walkers, true, c->fqv_slots, "launch_fqv", [&](int m, const WalkerList &L) {
+        return launch_fqv(c->P, c->d_paths.p, m, L, c->fqv_window, c->fqv_ntau, c->fqv_nmax, c->d_fqv_rho.p, c->d_fqv_acc.p,
+                          c->d_fqv_samples.p, c->stream);
+    });
 }
 
 int pigs_fqv_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset)
@@ -1780,23 +1692,8 @@ int pigs_fqv_read(pigs_ctx *c, double *F, int64_t *samples, const int32_t *reset
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->fqv_nmax) return fail(PIGS_ERR_ARG, "pigs_fqv_init first");
     if (!F || !samples) return fail(PIGS_ERR_ARG, "null output");
-    const size_t W = (size_t)c->n_walkers, per = (size_t)(c->fqv_ntau + 1) * (size_t)c->fqv_nq;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(F, c->d_fqv_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(samples, c->d_fqv_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (reset) {
-        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
-        for (size_t w = 0; w < W;) {
-            if (!reset[w]) { ++w; continue; }
-            size_t e = w;
-            while (e < W && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_fqv_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
-            HIPCHK(hipMemsetAsync(c->d_fqv_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
-            w = e;
-        }
-    }
-    SYNC_CHECKED(c);
-    return PIGS_OK;
+    const size_t per = (size_t)(c->fqv_ntau + 1) * (size_t)c->fqv_nq;
+    return read_and_reset(c, {{c->d_fqv_acc.p, per, F}, {c->d_fqv_samples.p, 1, samples}}, reset);
 }
 
 // ---- self part of F(q,tau) and the imaginary-time displacement of a periodic system ---------------
@@ -1816,14 +1713,10 @@ int pigs_fqs_init(pigs_ctx *c, int32_t nmax, int32_t Ntau, int32_t window)
     const size_t W = (size_t)c->n_walkers, per = (size_t)(Ntau + 1) * (size_t)sh.Nq, perd = (size_t)(Ntau + 1) * 2;
     if ((double)W * ((double)per + (double)perd + 1.0) * 8.0 > 2147483648.0)
         return fail(PIGS_ERR_ARG, "pigs_fqs_init: %zu walkers x (%d x (%lld + 2) + 1) sums pass 2 GiB", W, Ntau + 1, (long long)sh.Nq);
-    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
-    c->fqs_nmax = 0;
-    HIPCHK(c->d_fqs_acc.alloc(W * per));
-    HIPCHK(c->d_fqs_dsp.alloc(W * perd));
-    HIPCHK(c->d_fqs_samples.alloc(W));
-    HIPCHK(hipMemsetAsync(c->d_fqs_acc.p, 0, W * per * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_fqs_dsp.p, 0, W * perd * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_fqs_samples.p, 0, W * sizeof(unsigned long long), c->stream));
+    rc = init_begin(c, c->fqs_nmax); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_fqs_acc, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_fqs_dsp, W * perd));
+    HIPCHK(alloc_zeroed(c, c->d_fqs_samples, W));
     SYNC_CHECKED(c);
     c->fqs_nmax = nmax;
     c->fqs_ntau = Ntau;
@@ -1834,20 +1727,12 @@ int pigs_fqs_init(pigs_ctx *c, int32_t nmax, int32_t Ntau, int32_t window)
 
 int pigs_fqs_count(pigs_ctx *c, int64_t *Nq)
 {
-    int rc = check_ctx(c); if (rc) return rc;
-    if (!c->fqs_nmax) return fail(PIGS_ERR_ARG, "pigs_fqs_init first");
-    if (!Nq) return fail(PIGS_ERR_ARG, "null output");
-    *Nq = c->fqs_nq;
-    return PIGS_OK;
+    return c ? grid_count(c, "fqs", c->fqs_nmax, c->fqs_nq, Nq) : fail(PIGS_ERR_ARG, "null context");
 }
 
 int pigs_fqs_vectors(pigs_ctx *c, int32_t *n)
 {
-    int rc = check_ctx(c); if (rc) return rc;
-    if (!c->fqs_nmax) return fail(PIGS_ERR_ARG, "pigs_fqs_init first");
-    if (!n) return fail(PIGS_ERR_ARG, "null output");
-    sqv_enumerate(c->P.dim, c->fqs_nmax, c->fqs_nq, n);
-    return PIGS_OK;
+    return c ? grid_vectors(c, "fqs", c->fqs_nmax, c->fqs_nq, n) : fail(PIGS_ERR_ARG, "null context");
 }
 
 int pigs_fqs_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
@@ -1858,23 +1743,11 @@ int pigs_fqs_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
     if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     std::vector<int32_t> sw;
     rc = walker_list(c, n, walkers, sw); if (rc) return rc;
-    // As pigs_fqv_accumulate: the list goes by value in the kernel arguments, and a launch ends where the list is full
-    // or a walker would appear in it a second time; the stream orders the launches.
-    if (walkers) c->fqs_mark.resize(c->n_walkers, 0);
-    for (int i0 = 0; i0 < n;) {
-        const int64_t launch = ++c->fqs_launch;
-        FqsList L{};
-        int m = 0;
-        while (i0 + m < n && m < kFqsListMax && !(walkers && c->fqs_mark[sw[i0 + m]] == launch)) {
-            if (walkers) c->fqs_mark[sw[i0 + m]] = launch;
-            L.w[m] = sw[i0 + m];
-            ++m;
-        }
-        HIPCHK(launch_fqs(c->P, c->d_paths.p, m, L, c->fqs_window, c->fqs_ntau, c->fqs_nmax, c->d_fqs_acc.p, c->d_fqs_dsp.p,
-                          c->d_fqs_samples.p, c->stream));
-        i0 += m;
-    }
-    return PIGS_OK;
+    // one thread owns an accumulator element per launch
+    return each_launch(c, sw, walkers, true, kWalkerListMax, "launch_fqs", [&](int m, const WalkerList &L) {
+        return launch_fqs(c->P, c->d_paths.p, m, L, c->fqs_window, c->fqs_ntau, c->fqs_nmax, c->d_fqs_acc.p, c->d_fqs_dsp.p,
+                          c->d_fqs_samples.p, c->stream);
+    });
 }
 
 int pigs_fqs_read(pigs_ctx *c, double *F, double *D, int64_t *samples, const int32_t *reset)
@@ -1882,25 +1755,8 @@ int pigs_fqs_read(pigs_ctx *c, double *F, double *D, int64_t *samples, const int
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->fqs_nmax) return fail(PIGS_ERR_ARG, "pigs_fqs_init first");
     if (!F || !D || !samples) return fail(PIGS_ERR_ARG, "null output");
-    const size_t W = (size_t)c->n_walkers, per = (size_t)(c->fqs_ntau + 1) * (size_t)c->fqs_nq, perd = (size_t)(c->fqs_ntau + 1) * 2;
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(F, c->d_fqs_acc.p, W * per * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(D, c->d_fqs_dsp.p, W * perd * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(samples, c->d_fqs_samples.p, W * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (reset) {
-        // zero the sums of the flagged walkers, one memset per array and run of consecutive walkers
-        for (size_t w = 0; w < W;) {
-            if (!reset[w]) { ++w; continue; }
-            size_t e = w;
-            while (e < W && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_fqs_acc.p + w * per, 0, (e - w) * per * sizeof(double), s));
-            HIPCHK(hipMemsetAsync(c->d_fqs_dsp.p + w * perd, 0, (e - w) * perd * sizeof(double), s));
-            HIPCHK(hipMemsetAsync(c->d_fqs_samples.p + w, 0, (e - w) * sizeof(unsigned long long), s));
-            w = e;
-        }
-    }
-    SYNC_CHECKED(c);
-    return PIGS_OK;
+    const size_t per = (size_t)(c->fqs_ntau + 1) * (size_t)c->fqs_nq, perd = (size_t)(c->fqs_ntau + 1) * 2;
+    return read_and_reset(c, {{c->d_fqs_acc.p, per, F}, {c->d_fqs_dsp.p, perd, D}, {c->d_fqs_samples.p, 1, samples}}, reset);
 }
 
 // ---- pair distribution of a periodic system on the vector grid, over a slice window ---------------
@@ -1916,18 +1772,14 @@ int pigs_grv_init(pigs_ctx *c, int32_t Nbin, int32_t Nr, double rbin, int32_t wi
                     c->P.dim, Nr, rbin, window, c->P.Nb);
     size_t nv = 1;
     for (int k = 0; k < c->P.dim; ++k) nv *= (size_t)Nbin;
-    const size_t W = (size_t)c->n_walkers, u = sizeof(unsigned long long);
-    const double bytes = (double)W * ((double)nv + (double)Nr + 1.0) * (double)u;
+    const size_t W = (size_t)c->n_walkers;
+    const double bytes = (double)W * ((double)nv + (double)Nr + 1.0) * 8.0;
     if (bytes > 2147483648.0)
         return fail(PIGS_ERR_ARG, "pigs_grv_init: %zu walkers x (%zu + %d + 1) counters pass 2 GiB", W, nv, Nr);
-    HIPCHK(hipStreamSynchronize(c->stream));           // no accumulate in flight on the buffers being replaced
-    c->grv_nbin = 0;
-    HIPCHK(c->d_grv_vec.alloc(W * nv));
-    HIPCHK(c->d_grv_radial.alloc(W * Nr));
-    HIPCHK(c->d_grv_samples.alloc(W));
-    HIPCHK(hipMemsetAsync(c->d_grv_vec.p, 0, W * nv * u, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_grv_radial.p, 0, W * Nr * u, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_grv_samples.p, 0, W * u, c->stream));
+    rc = init_begin(c, c->grv_nbin); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_grv_vec, W * nv));
+    HIPCHK(alloc_zeroed(c, c->d_grv_radial, W * Nr));
+    HIPCHK(alloc_zeroed(c, c->d_grv_samples, W));
     SYNC_CHECKED(c);
     c->grv_nbin = Nbin;
     c->grv_nr = Nr;
@@ -1945,19 +1797,18 @@ int pigs_grv_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
     if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
     std::vector<int32_t> sw;
     rc = walker_list(c, n, walkers, sw); if (rc) return rc;
-    // the list goes by value in the kernel arguments: queued on the context's stream, nothing to wait for.  The counts
-    // are integer atomics, so a walker may appear twice in one launch.
-    for (int i0 = 0; i0 < n; i0 += kGrvListMax) {
-        const int m = std::min(kGrvListMax, n - i0);
+    // integer atomics: a walker may appear twice in one launch.  The form follows from the launch's size; a forced LDS
+    // form that does not fit is refused at that launch, the launches before it stay queued.
+    bool fits = true;
+    rc = each_launch(c, sw, walkers, false, kWalkerListMax, "launch_grv", [&](int m, const WalkerList &L) {
         const GrvShape sh = grv_shape(c->P.dim, c->P.Np, c->grv_nbin, c->grv_nr, c->grv_window, c->grv_form, m, c->n_cu);
-        if (sh.vec_lds && !sh.vec_fits)
-            return fail(PIGS_ERR_ARG, "pigs_grv_accumulate: grv_form = 1, but a grid of %zu bins does not fit the LDS", c->grv_nvec);
-        GrvList L{};
-        for (int i = 0; i < m; ++i) L.w[i] = sw[i0 + i];
-        HIPCHK(launch_grv(c->P, c->d_paths.p, m, L, sh, c->grv_window, c->grv_nbin, c->grv_nr, c->grv_rbin, c->d_grv_vec.p,
-                          c->d_grv_radial.p, c->d_grv_samples.p, c->stream));
-    }
-    return PIGS_OK;
+        fits = !(sh.vec_lds && !sh.vec_fits);
+        if (!fits) return hipErrorInvalidValue;
+        return launch_grv(c->P, c->d_paths.p, m, L, sh, c->grv_window, c->grv_nbin, c->grv_nr, c->grv_rbin, c->d_grv_vec.p,
+                          c->d_grv_radial.p, c->d_grv_samples.p, c->stream);
+    });
+    if (!fits) return fail(PIGS_ERR_ARG, "pigs_grv_accumulate: grv_form = 1, but a grid of %zu bins does not fit the LDS", c->grv_nvec);
+    return rc;
 }
 
 int pigs_grv_read(pigs_ctx *c, int64_t *vec, int64_t *radial, int64_t *samples, const int32_t *reset)
@@ -1965,26 +1816,8 @@ int pigs_grv_read(pigs_ctx *c, int64_t *vec, int64_t *radial, int64_t *samples, 
     int rc = check_ctx(c); if (rc) return rc;
     if (!c->grv_nbin) return fail(PIGS_ERR_ARG, "pigs_grv_init first");
     if (!vec || !radial || !samples) return fail(PIGS_ERR_ARG, "null output");
-    const size_t W = (size_t)c->n_walkers, nv = c->grv_nvec, nr = (size_t)c->grv_nr;
-    const size_t u = sizeof(unsigned long long);
-    hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(vec, c->d_grv_vec.p, W * nv * u, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(radial, c->d_grv_radial.p, W * nr * u, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(samples, c->d_grv_samples.p, W * u, hipMemcpyDeviceToHost, s));
-    if (reset) {
-        // zero the accumulators of the flagged walkers, one memset per array and run of consecutive walkers
-        for (size_t w = 0; w < W;) {
-            if (!reset[w]) { ++w; continue; }
-            size_t e = w;
-            while (e < W && reset[e]) ++e;
-            HIPCHK(hipMemsetAsync(c->d_grv_vec.p + w * nv, 0, (e - w) * nv * u, s));
-            HIPCHK(hipMemsetAsync(c->d_grv_radial.p + w * nr, 0, (e - w) * nr * u, s));
-            HIPCHK(hipMemsetAsync(c->d_grv_samples.p + w, 0, (e - w) * u, s));
-            w = e;
-        }
-    }
-    SYNC_CHECKED(c);
-    return PIGS_OK;
+    return read_and_reset(c, {{c->d_grv_vec.p, c->grv_nvec, vec}, {c->d_grv_radial.p, (size_t)c->grv_nr, radial},
+                              {c->d_grv_samples.p, 1, samples}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

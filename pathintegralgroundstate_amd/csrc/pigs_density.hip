@@ -32,7 +32,7 @@ constexpr int kDensTile = 1024;       // particles of the slice staged in LDS at
 // pair counts, flushed as 2 x count) when lds_hist, in global memory otherwise.
 template <int DIM>
 __global__ __launch_bounds__(kDensThreads) void k_density(
-    DevParams P, const double *__restrict__ paths, DensList list, int tile, int Nbin, double h, double b, double br,
+    DevParams P, const double *__restrict__ paths, WalkerList list, int tile, int Nbin, double h, double b, double br,
     int lds_hist, unsigned long long *__restrict__ planar, unsigned long long *__restrict__ radial,
     unsigned long long *__restrict__ pair, unsigned long long *__restrict__ samples)
 {
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kDensThreads) void k_density(
 
 } // namespace
 
-hipError_t launch_density(const DevParams &P, const double *paths, int n, const DensList &list, int Nbin, double h,
+hipError_t launch_density(const DevParams &P, const double *paths, int n, const WalkerList &list, int Nbin, double h,
                           double b, double br, unsigned long long *planar, unsigned long long *radial,
                           unsigned long long *pair, unsigned long long *samples, hipStream_t st)
 {

@@ -40,7 +40,7 @@ namespace {
 // acc: [walker][l][iqv]; tab: [a][k][m = 0..nmax]; st: [a][vector of the tile], width a power of two <= kFqsThreads
 template <int DIM>
 __global__ __launch_bounds__(kFqsThreads) void k_fqs(
-    DevParams P, const double *__restrict__ paths, FqsList list, int window, int Ntau, int nmax, int width, int ntiles,
+    DevParams P, const double *__restrict__ paths, WalkerList list, int window, int Ntau, int nmax, int width, int ntiles,
     long long Nq, double pi, double *__restrict__ acc, unsigned long long *__restrict__ samples)
 {
     extern __shared__ c2 lds[];
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kFqsThreads) void k_fqs(
 // dsp: [walker][l][2]
 template <int DIM>
 __global__ __launch_bounds__(256) void k_fqs_msd(
-    DevParams P, const double *__restrict__ paths, FqsList list, int window, int Ntau, double *__restrict__ dsp)
+    DevParams P, const double *__restrict__ paths, WalkerList list, int window, int Ntau, double *__restrict__ dsp)
 {
     __shared__ double red[2 * 4];
     const int ns = 2 * window + 1;
@@ -187,11 +187,11 @@ FqsShape fqs_shape(int dim, int nmax, int window, int Ntau)
     return s;
 }
 
-hipError_t launch_fqs(const DevParams &P, const double *paths, int n, const FqsList &list, int window, int Ntau, int nmax,
+hipError_t launch_fqs(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Ntau, int nmax,
                       double *acc, double *dsp, unsigned long long *samples, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    if (n > kFqsListMax) return hipErrorInvalidValue;
+    if (n > kWalkerListMax) return hipErrorInvalidValue;
     const SqvShape q = sqv_shape(P.dim, nmax);
     const FqsShape s = fqs_shape(P.dim, nmax, window, Ntau);
     if (!s.width) return hipErrorInvalidValue;

@@ -34,7 +34,7 @@ constexpr int kFqtChunkVals = 8 * kFqtGroupsPerChunk;
 // value j = 2 m + cs of group g: harmonic iq = 4 (g % ng) + m + 1 of axis k = g / ng; cs = 0 cosine, 1 sine
 template <int DIM>
 __global__ __launch_bounds__(256) void k_fqt_rho(
-    DevParams P, const double *__restrict__ paths, FqtList list, int window, int Nk, double pi, double *__restrict__ rho)
+    DevParams P, const double *__restrict__ paths, WalkerList list, int window, int Nk, double pi, double *__restrict__ rho)
 {
     __shared__ double red[4 * 8 * kRedStride];         // wave_reduce_lds scratch, one block per wave
     __shared__ double part[4 * kFqtChunkVals];         // wave totals of one chunk of values
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void k_fqt_rho(
 
 // rho: [slot][window slice][(iq-1) dim + k][cos, sin]; acc: [walker][l][(iq-1) dim + k]
 __global__ __launch_bounds__(256) void k_fqt_correlate(
-    FqtList list, int n, int window, int Ntau, int T, const double *__restrict__ rho, double *__restrict__ acc,
+    WalkerList list, int n, int window, int Ntau, int T, const double *__restrict__ rho, double *__restrict__ acc,
     unsigned long long *__restrict__ samples)
 {
     const size_t per = (size_t)(Ntau + 1) * T;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_fqt_correlate(
 
 } // namespace
 
-hipError_t launch_fqt(const DevParams &P, const double *paths, int n, const FqtList &list, int window, int Ntau, int Nk,
+hipError_t launch_fqt(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Ntau, int Nk,
                       double *rho, double *acc, unsigned long long *samples, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;

@@ -32,7 +32,7 @@ namespace {
 
 template <int DIM>
 __global__ __launch_bounds__(kSqvThreadsMax) void k_fqv_rho(
-    DevParams P, const double *__restrict__ paths, FqvList list, int window, int nmax, int tile, int nprefix, int nchunk,
+    DevParams P, const double *__restrict__ paths, WalkerList list, int window, int nmax, int tile, int nprefix, int nchunk,
     long long Nq, double pi, double *__restrict__ rho)
 {
     extern __shared__ c2 tab[];
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kSqvThreadsMax) void k_fqv_rho(
 
 // rho: [slot][window slice][iqv] of c2; acc: [walker][l][iqv]; st: [slice][vector of the tile], width a power of two
 __global__ __launch_bounds__(kFqvThreads) void k_fqv_correlate(
-    FqvList list, int ns, int Ntau, int width, int ntiles, long long Nq, const double *__restrict__ rho,
+    WalkerList list, int ns, int Ntau, int width, int ntiles, long long Nq, const double *__restrict__ rho,
     double *__restrict__ acc, unsigned long long *__restrict__ samples)
 {
     extern __shared__ c2 st[];
@@ -84,7 +84,7 @@ int fqv_width(int ns)
     return (size_t)ns * width * sizeof(c2) > kFqvLdsBudget ? 0 : width;
 }
 
-hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const FqvList &list, int window, int Ntau, int nmax,
+hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Ntau, int nmax,
                       double *rho, double *acc, unsigned long long *samples, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;

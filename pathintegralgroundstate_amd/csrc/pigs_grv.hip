@@ -55,7 +55,7 @@ __device__ __forceinline__ void grv_flush(unsigned int *hist, unsigned int n, un
 
 template <int DIM, bool VEC_LDS, bool RAD_LDS>
 __global__ __launch_bounds__(kGrvThreadsMax) void k_grv(
-    DevParams P, const double *__restrict__ paths, GrvList list, GrvArgs A, unsigned long long *__restrict__ vec,
+    DevParams P, const double *__restrict__ paths, WalkerList list, GrvArgs A, unsigned long long *__restrict__ vec,
     unsigned long long *__restrict__ radial, unsigned long long *__restrict__ samples)
 {
     extern __shared__ double lds[];
@@ -210,7 +210,7 @@ GrvShape grv_shape(int dim, int Np, int Nbin, int Nr, int window, int form, int 
     return s;
 }
 
-hipError_t launch_grv(const DevParams &P, const double *paths, int n, const GrvList &list, const GrvShape &s, int window,
+hipError_t launch_grv(const DevParams &P, const double *paths, int n, const WalkerList &list, const GrvShape &s, int window,
                       int Nbin, int Nr, double rbin, unsigned long long *vec, unsigned long long *radial,
                       unsigned long long *samples, hipStream_t st)
 {

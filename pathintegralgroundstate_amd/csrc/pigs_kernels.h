@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "pigs_device.h"
+#include "pigs_walker_split.h"
 
 namespace pigs {
 
@@ -49,40 +50,33 @@ hipError_t launch_structure(const DevParams &P, const double *paths, int n_slots
                             int ib, int Nbin, double rbin, int Nk, double *gr, double *Sk, hipStream_t st);
 
 // pigs_density.hip: planar / radial density and pair distribution of slice Nb of a trapped system, 64-bit counts
-// accumulated per walker (pigs_density_accumulate).  The walker list travels in the kernel arguments (no upload, no
-// host buffer to keep alive), at most kDensListMax walkers per launch.  The pair histogram is staged in LDS for
-// Nbin <= kDensLdsBins and added with global atomics beyond.
-constexpr int kDensListMax = 256;
+// accumulated per walker (pigs_density_accumulate).  The walker list travels in the kernel arguments (WalkerList,
+// pigs_walker_split.h: at most kWalkerListMax walkers per launch), here and in the six families below.  The pair
+// histogram is staged in LDS for Nbin <= kDensLdsBins and added with global atomics beyond.
 constexpr int kDensLdsBins = 8192;
-struct DensList { int32_t w[kDensListMax]; };
-hipError_t launch_density(const DevParams &P, const double *paths, int n, const DensList &list, int Nbin, double h,
+hipError_t launch_density(const DevParams &P, const double *paths, int n, const WalkerList &list, int Nbin, double h,
                           double b, double br, unsigned long long *planar, unsigned long long *radial,
                           unsigned long long *pair, unsigned long long *samples, hipStream_t st);
 
 // pigs_fqt.hip: imaginary-time density correlations F(q,tau) of a periodic system (pigs_fqt_accumulate).  Stage 1 writes
 // C(s), S(s) of the window slices Nb-window .. Nb+window of the n listed walkers to rho ([slot][slice][(iq-1) dim + k][2]
 // doubles), stage 2 adds the ordered pair sums of the lags 0..Ntau to acc ([walker][l][(iq-1) dim + k]) and 1 to samples.
-// One thread owns an accumulator element per launch: the caller never lists a walker twice in ONE launch.  The list
-// travels in the kernel arguments, at most kFqtListMax walkers per launch.
-constexpr int kFqtListMax = 256;
-struct FqtList { int32_t w[kFqtListMax]; };
-hipError_t launch_fqt(const DevParams &P, const double *paths, int n, const FqtList &list, int window, int Ntau, int Nk,
+// One thread owns an accumulator element per launch: the caller never lists a walker twice in ONE launch.
+hipError_t launch_fqt(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Ntau, int Nk,
                       double *rho, double *acc, unsigned long long *samples, hipStream_t st);
 
 // pigs_sqv.hip: the vector structure factor on the full reciprocal grid (pigs_sqv_accumulate).  Stage 1 writes
 // C^2 + S^2 of every stored vector for the window slices Nb-window .. Nb+window of the n listed walkers to rho2
 // ([slot][slice][iqv] doubles), stage 2 adds their sum over the slices (ascending) to acc ([walker][iqv]) and 1 to samples.
-// One thread owns an accumulator element per launch: the caller never lists a walker twice in ONE launch.  The list
-// travels in the kernel arguments, at most kSqvListMax walkers per launch.  sqv_shape gives the sizes that follow from
-// (dim, nmax) alone: Nq vectors, the prefixes and chunks of the work items, the particle tile and its LDS bytes.
-constexpr int kSqvListMax = 256;
+// One thread owns an accumulator element per launch: the caller never lists a walker twice in ONE launch.  sqv_shape
+// gives the sizes that follow from (dim, nmax) alone: Nq vectors, the prefixes and chunks of the work items, the
+// particle tile and its LDS bytes.
 constexpr int kSqvChunk = 8;                     // values of |n_dim| per work item: 4 * 8 running sums in registers
 constexpr int kSqvThreadsMax = 512;
 constexpr size_t kSqvLdsBudget = 40 * 1024;      // phasor table of one particle tile: several workgroups share a CU
-struct SqvList { int32_t w[kSqvListMax]; };
 struct SqvShape { long long Nq; int nprefix, nchunk, tile, threads; size_t lds; };
 SqvShape sqv_shape(int dim, int nmax);
-hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const SqvList &list, int window, int nmax,
+hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int nmax,
                       double *rho2, double *acc, unsigned long long *samples, hipStream_t st);
 
 // pigs_fqv.hip: F(q,tau) on the vectors of pigs_sqv_* (pigs_fqv_accumulate).  Stage 1 writes (C, S) of every stored vector
@@ -91,13 +85,11 @@ hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const SqvL
 // acc ([walker][l][iqv]) and 1 to samples.  One thread owns an accumulator element per launch: the caller never lists a
 // walker twice in ONE launch.  fqv_width is the largest power of two <= kFqvWidthMax whose tile fits kFqvLdsBudget
 // (0: not even one vector's ns slices fit, which pigs_fqv_init refuses).
-constexpr int kFqvListMax = 256;
 constexpr int kFqvThreads = 256;
 constexpr int kFqvWidthMax = 64;                 // one wave of lanes over consecutive vectors
 constexpr size_t kFqvLdsBudget = 64 * 1024;      // 16 bytes per (slice, vector): 64 wide up to 64 slices, 16 wide at 161
-struct FqvList { int32_t w[kFqvListMax]; };
 int fqv_width(int ns);
-hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const FqvList &list, int window, int Ntau, int nmax,
+hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Ntau, int nmax,
                       double *rho, double *acc, unsigned long long *samples, hipStream_t st);
 
 // pigs_fqs.hip: the self part of F(q,tau) on the vectors of pigs_sqv_* and the imaginary-time displacement
@@ -107,43 +99,35 @@ hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const FqvL
 // ([walker][l][iqv]) and 1 to samples.  One thread owns an accumulator element per launch: the caller never lists a
 // walker twice in ONE launch.  fqs_shape gives the largest power of two <= kFqsWidthMax whose table and tile fit
 // kFqsLdsBudget and whose kFqsThreads / width lag groups cover Ntau + 1 lags (width 0: none, which pigs_fqs_init refuses).
-constexpr int kFqsListMax = 256;
 constexpr int kFqsThreads = 256;
 constexpr int kFqsWidthMax = 64;                 // one wave of lanes over consecutive vectors
 constexpr int kFqsLags = 12;                     // lag sums a thread keeps in registers across the particle loop
 constexpr size_t kFqsLdsBudget = 64 * 1024;      // 16 bytes per (slice, axis, m) and per (slice, vector)
-struct FqsList { int32_t w[kFqsListMax]; };
 struct FqsShape { int width; size_t lds; };
 FqsShape fqs_shape(int dim, int nmax, int window, int Ntau);
-hipError_t launch_fqs(const DevParams &P, const double *paths, int n, const FqsList &list, int window, int Ntau, int nmax,
+hipError_t launch_fqs(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Ntau, int nmax,
                       double *acc, double *dsp, unsigned long long *samples, hipStream_t st);
 
 // pigs_grv.hip: the pair distribution of a periodic system on the vector grid and radially, over the window slices
 // Nb-window .. Nb+window (pigs_grv_accumulate): 64-bit counts per walker, vec [walker][Nbin^dim] (x fastest) and radial
-// [walker][Nr].  The list travels in the kernel arguments, at most kGrvListMax walkers per launch; a walker may be listed
-// twice in one launch (integer atomics).  grv_shape decides the form: the vector grid privatised in LDS (form 1, or
+// [walker][Nr].  A walker may be listed twice in one launch (integer atomics).  grv_shape decides the form: the vector grid privatised in LDS (form 1, or
 // automatic up to kGrvAutoLdsBins bins where it fits kGrvLdsBudget next to the staging tiles and the radial histogram) with
 // nchunk runs of slices per walker, or global atomics with one workgroup per (walker, slice); vec_lds && !vec_fits is
 // a forced LDS form that does not fit, which the caller refuses.
-constexpr int kGrvListMax = 256;
 constexpr int kGrvTile = 256;                    // particles of a slice staged per tile
 constexpr int kGrvThreadsMax = 1024;
 constexpr size_t kGrvLdsBudget = 160 * 1024;     // LDS of one CU on gfx950
 constexpr long long kGrvAutoLdsBins = 1ll << 15; // automatic form: LDS up to 32^3 bins (measured)
-struct GrvList { int32_t w[kGrvListMax]; };
 struct GrvShape { int vec_lds, vec_fits, rad_lds, nchunk, threads, flush_every; size_t lds; };
 GrvShape grv_shape(int dim, int Np, int Nbin, int Nr, int window, int form, int n_list, int n_cu);
-hipError_t launch_grv(const DevParams &P, const double *paths, int n, const GrvList &list, const GrvShape &s, int window,
+hipError_t launch_grv(const DevParams &P, const double *paths, int n, const WalkerList &list, const GrvShape &s, int window,
                       int Nbin, int Nr, double rbin, unsigned long long *vec, unsigned long long *radial,
                       unsigned long long *samples, hipStream_t st);
 
 // pigs_tau.hip: imaginary-time profiles (pigs_tau_accumulate): per listed walker and slice b = 0..2Nb the sums Vpair, Vext,
 // W = sum r v'(r) and D2 = sum_i |x_i(b) - x_i(b+1)|^2 are added to acc ([walker][2Nb+1][4]) and 1 to samples.  One
-// workgroup owns an accumulator element per launch: the caller never
-// lists a walker twice in ONE launch.  The list travels in the kernel arguments, at most kTauListMax walkers per launch.
-constexpr int kTauListMax = 256;
-struct TauList { int32_t w[kTauListMax]; };
-hipError_t launch_tau(const DevParams &P, const double *paths, const double *VT, int n, const TauList &list, double *acc,
+// workgroup owns an accumulator element per launch: the caller never lists a walker twice in ONE launch.
+hipError_t launch_tau(const DevParams &P, const double *paths, const double *VT, int n, const WalkerList &list, double *acc,
                       unsigned long long *samples, hipStream_t st);
 
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,

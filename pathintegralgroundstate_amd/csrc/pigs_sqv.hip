@@ -39,7 +39,7 @@ namespace {
 // tab: [k][particle of the tile][m = 0..ms-1], ms = kSqvChunk * nchunk + 1 (sqv_rho_slice, pigs_sqv_device.h)
 template <int DIM>
 __global__ __launch_bounds__(kSqvThreadsMax) void k_sqv_rho2(
-    DevParams P, const double *__restrict__ paths, SqvList list, int window, int nmax, int tile, int nprefix, int nchunk,
+    DevParams P, const double *__restrict__ paths, WalkerList list, int window, int nmax, int tile, int nprefix, int nchunk,
     long long Nq, double pi, double *__restrict__ rho2)
 {
     extern __shared__ c2 tab[];
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kSqvThreadsMax) void k_sqv_rho2(
 
 // rho2: [slot][window slice][iqv]; acc: [walker][iqv]
 __global__ __launch_bounds__(256) void k_sqv_combine(
-    SqvList list, int n, int ns, long long Nq, const double *__restrict__ rho2, double *__restrict__ acc,
+    WalkerList list, int n, int ns, long long Nq, const double *__restrict__ rho2, double *__restrict__ acc,
     unsigned long long *__restrict__ samples)
 {
     const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,7 +86,7 @@ SqvShape sqv_shape(int dim, int nmax)
     return s;
 }
 
-hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const SqvList &list, int window, int nmax,
+hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int nmax,
                       double *rho2, double *acc, unsigned long long *samples, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;

@@ -93,7 +93,7 @@ __device__ __forceinline__ void tau_particle(const DevParams &P, const double *s
 // acc: [walker][2Nb+1][4]
 template <int DIM, bool TRAP>
 __global__ __launch_bounds__(256) void k_tau(
-    DevParams P, const double *__restrict__ paths, const double *__restrict__ VT, TauList list, double *__restrict__ acc,
+    DevParams P, const double *__restrict__ paths, const double *__restrict__ VT, WalkerList list, double *__restrict__ acc,
     unsigned long long *__restrict__ samples)
 {
     extern __shared__ double lds[];
@@ -127,11 +127,11 @@ __global__ __launch_bounds__(256) void k_tau(
 
 } // namespace
 
-hipError_t launch_tau(const DevParams &P, const double *paths, const double *VT, int n, const TauList &list, double *acc,
+hipError_t launch_tau(const DevParams &P, const double *paths, const double *VT, int n, const WalkerList &list, double *acc,
                       unsigned long long *samples, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    if (n > kTauListMax) return hipErrorInvalidValue;
+    if (n > kWalkerListMax) return hipErrorInvalidValue;
     const int n_slots = n * P.M;
     const int bs = std::min(256, ((P.Np + 63) / 64) * 64);
     const size_t lds = ((size_t)P.dim * P.NpPad + 4 * (bs / 64)) * sizeof(double);

@@ -172,3 +172,64 @@ def test_log_host_matches_this_machines_libm(tmp_path):
     out = subprocess.run([exe, "200"], capture_output=True, text=True, timeout=600)
     tested, bad, first = out.stdout.split()
     assert out.returncode == 0 and int(bad) == 0 and int(tested) >= 200000000, out.stdout
+
+
+def _split_rule(sw, listed, cap, unique):
+    """The launch split of the accumulator families, restated: (start, walkers) of every launch."""
+    out, i0 = [], 0
+    while i0 < len(sw):
+        seen, m = set(), 0
+        while i0 + m < len(sw) and m < cap and not (unique and listed and sw[i0 + m] in seen):
+            seen.add(sw[i0 + m])
+            m += 1
+        out.append((i0, sw[i0:i0 + m]))
+        i0 += m
+    return out
+
+
+def test_walker_split_matches_the_stated_rule(tmp_path):
+    """csrc/pigs_walker_split.h (where every pigs_*_accumulate ends one launch and begins the next) compiled for the CPU
+    against _split_rule: the same (start, count) sequence and the same list entries for random and built requests --
+    lists left out, caps 1, 2, 3 and 256, lengths 0..700, repeats adjacent, separated and exactly at a cap boundary,
+    with and without `unique`, all on ONE set of marks.  Once as built, once under -fsanitize=address,undefined."""
+    import subprocess
+    W = 700
+    rng = np.random.default_rng(20261019)
+    cases = []
+    for cap in (1, 2, 3, 256):
+        for unique in (0, 1):
+            for n in (0, 1, cap - 1, cap, cap + 1, 2 * cap, 2 * cap + 1, 700):
+                cases.append((cap, unique, 0, list(range(max(n, 0)))))              # the list left out
+            base = list(range(10, 10 + 2 * cap + 2))
+            for i, j in ((1, 0), (cap - 1, 0), (cap, 0), (cap, cap - 1), (cap + 1, cap), (cap + 1, 1), (2 * cap, cap),
+                         (2 * cap, cap - 1), (2 * cap + 1, cap + 1)):
+                sw = list(base)                                                     # walker sw[j] again at position i
+                sw[i] = sw[j]
+                cases.append((cap, unique, 1, sw))
+            cases.append((cap, unique, 1, [5] * (cap + 3)))
+            cases.append((cap, unique, 1, [5, 6] * (cap + 1)))
+    for _ in range(3000):
+        cap = int(rng.choice([1, 2, 3, 256]))
+        n = int(rng.integers(0, 701))
+        if rng.random() < 0.15:
+            cases.append((cap, int(rng.integers(0, 2)), 0, list(range(n))))
+        else:
+            sw = rng.integers(0, int(rng.choice([1, 2, 3, 5, 40, 300, W])), n)
+            if n and rng.random() < 0.5:                                            # runs of one walker
+                sw = np.repeat(sw, rng.integers(1, 4, n))[:n]
+            cases.append((cap, int(rng.integers(0, 2)), 1, [int(w) for w in sw]))
+    text = "".join("%d %d %d %d %s\n" % (cap, u, l, len(sw), " ".join(map(str, sw))) for cap, u, l, sw in cases)
+    want = [_split_rule(sw, bool(l), cap, bool(u)) for cap, u, l, sw in cases]
+    assert any(len(b) < cap and a + len(b) < len(sw) for (cap, u, l, sw), ws in zip(cases, want) for a, b in ws)
+    src = os.path.join(ROOT, "tests", "shim", "walker_split_check.cpp")
+    inc = "-I" + os.path.join(ROOT, "pathintegralgroundstate_amd", "csrc")
+    for name, flags in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = str(tmp_path / ("walker_split_" + name))
+        subprocess.check_call(["g++", "-std=c++17", "-Wall"] + flags + [inc, src, "-o", exe])
+        out = subprocess.run([exe, str(W)], input=text, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, (name, out.returncode, out.stderr[-2000:])
+        lines = out.stdout.split("\n")[:-1]
+        assert len(lines) == len(cases)
+        for (cap, u, l, sw), ws, line in zip(cases, want, lines):
+            got = [[int(x) for x in part.split()] for part in line.split(";") if part.strip()]
+            assert [(g[0], g[2:]) for g in got] == ws and all(g[1] == len(g) - 2 for g in got), (name, cap, u, l, sw)
