@@ -620,15 +620,25 @@ contains
     call pigs_check(query(ctx,form),'pigs_sampler_form')
   end function sampler_form
 
-  ! The density-profile entry points, found at run time in the process's libraries (dlsym with RTLD_DEFAULT = NULL) and
-  ! only when a run asks for them: the host links against backends without them (the CPU twin of tests/shim) and never
-  ! names them at link time.  .false. (pointers left null) where the backend does not export all three.
+  ! The entry points pre_names(1), pre_names(2), ... looked up in the process's libraries (dlsym with RTLD_DEFAULT = NULL):
+  ! .true. where every one is there.
+  logical function resolve_all(pre,names,f)
+    character(len=*), intent(in) :: pre,names(:)
+    type(c_funptr), intent(out)  :: f(size(names))
+    integer :: i
+    resolve_all = .true.
+    do i=1,size(names)
+       f(i) = c_dlsym(c_null_ptr,pre//'_'//trim(names(i))//c_null_char)
+       resolve_all = resolve_all .and. c_associated(f(i))
+    end do
+  end function resolve_all
+
+  ! The density-profile entry points, found at run time and only when a run asks for them: the host links against
+  ! backends without them (the CPU twin of tests/shim) and never names them at link time.  .false. (pointers left null)
+  ! where the backend does not export all three.
   logical function density_bind()
     type(c_funptr) :: f(3)
-    f(1) = c_dlsym(c_null_ptr,'pigs_density_init'//c_null_char)
-    f(2) = c_dlsym(c_null_ptr,'pigs_density_accumulate'//c_null_char)
-    f(3) = c_dlsym(c_null_ptr,'pigs_density_read'//c_null_char)
-    density_bind = c_associated(f(1)) .and. c_associated(f(2)) .and. c_associated(f(3))
+    density_bind = resolve_all('pigs_density',[character(len=10) :: 'init','accumulate','read'],f)
     if (.not. density_bind) return
     call c_f_procpointer(f(1),dens_init)
     call c_f_procpointer(f(2),dens_accumulate)
@@ -638,10 +648,7 @@ contains
   ! The F(q,tau) entry points, found like the density ones: at run time, only when a run asks for them.
   logical function fqt_bind()
     type(c_funptr) :: f(3)
-    f(1) = c_dlsym(c_null_ptr,'pigs_fqt_init'//c_null_char)
-    f(2) = c_dlsym(c_null_ptr,'pigs_fqt_accumulate'//c_null_char)
-    f(3) = c_dlsym(c_null_ptr,'pigs_fqt_read'//c_null_char)
-    fqt_bind = c_associated(f(1)) .and. c_associated(f(2)) .and. c_associated(f(3))
+    fqt_bind = resolve_all('pigs_fqt',[character(len=10) :: 'init','accumulate','read'],f)
     if (.not. fqt_bind) return
     call c_f_procpointer(f(1),fqt_init)
     call c_f_procpointer(f(2),fqt_accumulate)
@@ -651,16 +658,7 @@ contains
   ! The vector-S(q) entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
   logical function sqv_bind()
     type(c_funptr) :: f(5)
-    integer :: i
-    f(1) = c_dlsym(c_null_ptr,'pigs_sqv_init'//c_null_char)
-    f(2) = c_dlsym(c_null_ptr,'pigs_sqv_count'//c_null_char)
-    f(3) = c_dlsym(c_null_ptr,'pigs_sqv_vectors'//c_null_char)
-    f(4) = c_dlsym(c_null_ptr,'pigs_sqv_accumulate'//c_null_char)
-    f(5) = c_dlsym(c_null_ptr,'pigs_sqv_read'//c_null_char)
-    sqv_bind = .true.
-    do i=1,5
-       sqv_bind = sqv_bind .and. c_associated(f(i))
-    end do
+    sqv_bind = resolve_all('pigs_sqv',[character(len=10) :: 'init','count','vectors','accumulate','read'],f)
     if (.not. sqv_bind) return
     call c_f_procpointer(f(1),sqv_init)
     call c_f_procpointer(f(2),sqv_count)
@@ -672,14 +670,7 @@ contains
   ! The vector-g(r) entry points, found like the vector-S(q) ones: at run time, only when a run asks for them.
   logical function grv_bind()
     type(c_funptr) :: f(3)
-    integer :: i
-    f(1) = c_dlsym(c_null_ptr,'pigs_grv_init'//c_null_char)
-    f(2) = c_dlsym(c_null_ptr,'pigs_grv_accumulate'//c_null_char)
-    f(3) = c_dlsym(c_null_ptr,'pigs_grv_read'//c_null_char)
-    grv_bind = .true.
-    do i=1,3
-       grv_bind = grv_bind .and. c_associated(f(i))
-    end do
+    grv_bind = resolve_all('pigs_grv',[character(len=10) :: 'init','accumulate','read'],f)
     if (.not. grv_bind) return
     call c_f_procpointer(f(1),grv_init)
     call c_f_procpointer(f(2),grv_accumulate)
@@ -689,16 +680,7 @@ contains
   ! The vector-F(q,tau) entry points, found like the vector-S(q) ones: at run time, only when a run asks for them.
   logical function fqv_bind()
     type(c_funptr) :: f(5)
-    integer :: i
-    f(1) = c_dlsym(c_null_ptr,'pigs_fqv_init'//c_null_char)
-    f(2) = c_dlsym(c_null_ptr,'pigs_fqv_count'//c_null_char)
-    f(3) = c_dlsym(c_null_ptr,'pigs_fqv_vectors'//c_null_char)
-    f(4) = c_dlsym(c_null_ptr,'pigs_fqv_accumulate'//c_null_char)
-    f(5) = c_dlsym(c_null_ptr,'pigs_fqv_read'//c_null_char)
-    fqv_bind = .true.
-    do i=1,5
-       fqv_bind = fqv_bind .and. c_associated(f(i))
-    end do
+    fqv_bind = resolve_all('pigs_fqv',[character(len=10) :: 'init','count','vectors','accumulate','read'],f)
     if (.not. fqv_bind) return
     call c_f_procpointer(f(1),fqv_init)
     call c_f_procpointer(f(2),fqv_count)
@@ -711,16 +693,7 @@ contains
   ! for them.
   logical function fqs_bind()
     type(c_funptr) :: f(5)
-    integer :: i
-    f(1) = c_dlsym(c_null_ptr,'pigs_fqs_init'//c_null_char)
-    f(2) = c_dlsym(c_null_ptr,'pigs_fqs_count'//c_null_char)
-    f(3) = c_dlsym(c_null_ptr,'pigs_fqs_vectors'//c_null_char)
-    f(4) = c_dlsym(c_null_ptr,'pigs_fqs_accumulate'//c_null_char)
-    f(5) = c_dlsym(c_null_ptr,'pigs_fqs_read'//c_null_char)
-    fqs_bind = .true.
-    do i=1,5
-       fqs_bind = fqs_bind .and. c_associated(f(i))
-    end do
+    fqs_bind = resolve_all('pigs_fqs',[character(len=10) :: 'init','count','vectors','accumulate','read'],f)
     if (.not. fqs_bind) return
     call c_f_procpointer(f(1),fqs_init)
     call c_f_procpointer(f(2),fqs_count)
@@ -732,10 +705,7 @@ contains
   ! The imaginary-time-profile entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
   logical function tau_bind()
     type(c_funptr) :: f(3)
-    f(1) = c_dlsym(c_null_ptr,'pigs_tau_init'//c_null_char)
-    f(2) = c_dlsym(c_null_ptr,'pigs_tau_accumulate'//c_null_char)
-    f(3) = c_dlsym(c_null_ptr,'pigs_tau_read'//c_null_char)
-    tau_bind = c_associated(f(1)) .and. c_associated(f(2)) .and. c_associated(f(3))
+    tau_bind = resolve_all('pigs_tau',[character(len=10) :: 'init','accumulate','read'],f)
     if (.not. tau_bind) return
     call c_f_procpointer(f(1),tau_init)
     call c_f_procpointer(f(2),tau_accumulate)

@@ -59,6 +59,7 @@ program pigs_vpi
   use pigs_rng
   use pigs_sampler
   use pigs_estimators
+  use pigs_block_stats
   use omp_lib
 
   implicit none
@@ -233,21 +234,7 @@ program pigs_vpi
         write (0,'(a)') ' pigs_vpi: fq_vector = T needs a periodic system (trap = F): its q grid is that of the box'
         stop 2
      end if
-     if (fqv_nmax<1 .or. fqv_nmax>merge(16,64,dim==3)) then
-        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: fq_vector = T: fqv_nmax = ',fqv_nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
-             & ' (dim = ',dim,')'
-        stop 2
-     end if
-     if (fqv_window<0) fqv_window = (max(fqv_ntau,0)+1)/2       ! ceiling(fqv_ntau/2)
-     if (fqv_ntau<0 .or. fqv_ntau>2*fqv_window) then
-        write (0,'(a,i0,a,i0,a)') ' pigs_vpi: fq_vector = T: fqv_ntau = ',fqv_ntau,' must lie in 0 .. 2*fqv_window = ',2*fqv_window, &
-             & ' (lags between the slices Nb-fqv_window .. Nb+fqv_window)'
-        stop 2
-     end if
-     if (fqv_window>Nb) then
-        write (0,'(a,i0,a,i0)') ' pigs_vpi: fq_vector = T: fqv_window = ',fqv_window,' must not exceed Nb = ',Nb
-        stop 2
-     end if
+     call check_vectors_and_lags('fq_vector','fqv',fqv_nmax,fqv_ntau,fqv_window)
      if (.not. fqv_bind()) then
         write (0,'(a)') ' pigs_vpi: fq_vector = T: this backend does not export pigs_fqv_init / _count / _vectors /'// &
              & ' _accumulate / _read (the vector F(q,tau) runs on libpigs_hip.so only)'
@@ -260,21 +247,7 @@ program pigs_vpi
         write (0,'(a)') ' pigs_vpi: fq_self = T needs a periodic system (trap = F): its q grid is that of the box'
         stop 2
      end if
-     if (fqs_nmax<1 .or. fqs_nmax>merge(16,64,dim==3)) then
-        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: fq_self = T: fqs_nmax = ',fqs_nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
-             & ' (dim = ',dim,')'
-        stop 2
-     end if
-     if (fqs_window<0) fqs_window = (max(fqs_ntau,0)+1)/2       ! ceiling(fqs_ntau/2)
-     if (fqs_ntau<0 .or. fqs_ntau>2*fqs_window) then
-        write (0,'(a,i0,a,i0,a)') ' pigs_vpi: fq_self = T: fqs_ntau = ',fqs_ntau,' must lie in 0 .. 2*fqs_window = ',2*fqs_window, &
-             & ' (lags between the slices Nb-fqs_window .. Nb+fqs_window)'
-        stop 2
-     end if
-     if (fqs_window>Nb) then
-        write (0,'(a,i0,a,i0)') ' pigs_vpi: fq_self = T: fqs_window = ',fqs_window,' must not exceed Nb = ',Nb
-        stop 2
-     end if
+     call check_vectors_and_lags('fq_self','fqs',fqs_nmax,fqs_ntau,fqs_window)
      if (.not. fqs_bind()) then
         write (0,'(a)') ' pigs_vpi: fq_self = T: this backend does not export pigs_fqs_init / _count / _vectors /'// &
              & ' _accumulate / _read (the self part of F(q,tau) runs on libpigs_hip.so only)'
@@ -478,7 +451,7 @@ contains
   type(c_ptr)        :: ctx
   type(perm_state), allocatable :: perm(:)
 
-  integer :: w,k,ip,ib,istep,iblock,istag,iobdm,j,nd,i,nvec,ndall,ngrall,nnrall,ngrav,nnrav
+  integer :: w,k,ip,ib,istep,iblock,istag,iobdm,j,nd,i,nvec,ndall,nall
   integer, allocatable :: ipv(:),iupd(:),partner(:),diag_list(:)
   logical, allocatable :: act(:),isopen0(:),swp(:)
   integer(c_int32_t), allocatable :: wl(:)
@@ -492,8 +465,7 @@ contains
   real(8), allocatable :: try_cm(:),try_stag(:),try_cm_half(:),try_stag_half(:)
   integer, allocatable :: idiag(:),idiag_aux(:),idiag_block(:),obdm_bl(:),diag_bl(:),ngr(:)
   real(8), allocatable :: BE(:,:),BE2(:,:),BT(:,:),BT2(:,:),AE(:,:),AE2(:,:),AT(:,:),AT2(:,:)
-  real(8), allocatable :: gr(:,:),AvGr(:,:),AvGr2(:,:),Sk(:,:,:),AvSk(:,:,:),AvSk2(:,:,:)
-  real(8), allocatable :: nrho(:,:,:),AvNr(:,:,:),AvNr2(:,:,:)
+  real(8), allocatable :: gr(:,:),Sk(:,:,:),nrho(:,:,:)
   real(8) :: t0,t1,mE(3),mT(3)
   integer, allocatable :: ue(:),ut(:),uh(:)
   integer :: ueav,utav,ucfg
@@ -510,69 +482,74 @@ contains
   real(8), allocatable :: dev_nrho(:,:,:)
   character(len=32) :: suffix
 
-  real(8), allocatable :: vec(:),AvGrAll(:),AvGr2All(:),AvSkAll(:,:),AvSk2All(:,:),AvNrAll(:,:),AvNr2All(:,:),tmp1(:),tmp2(:,:),tmp3(:,:)
+  ! the vector that meets the other shards' once per block (nvec doubles), and the block statistics of every estimator
+  ! file: one series per file, one count per family (pigs_block_stats).  g(r) and S(k) share the count of the walkers with
+  ! a diagonal block, n(r) has the one of the walkers whose OBDM block is full.
+  real(8), allocatable :: vec(:)
   real(8) :: cnt_all(13)
-  ! density profiles (density_profile = T): the block's counts from the device, the normalised block profiles, their
-  ! per-walker sums and the walker-averaged sums; ndv doubles of the block vector (0 with the key off)
-  integer :: npl,ndv,ndensav,ndensall
+  type(block_series) :: sGr,sSk,sNr
+  type(block_count)  :: cGr,cNr
+  ! density profiles (density_profile = T): the block's counts from the device and the normalised block profiles
+  integer :: npl
   integer(c_int64_t), allocatable :: dc_pl(:,:),dc_rad(:,:),dc_pair(:,:),dc_smp(:)
   integer(c_int32_t), allocatable :: dc_reset(:)
-  real(8), allocatable :: dpl(:),drad(:),dpair(:),AvDpl(:,:),AvDpl2(:,:),AvDrad(:,:),AvDrad2(:,:),AvDpair(:,:),AvDpair2(:,:)
-  real(8), allocatable :: AvDplAll(:),AvDpl2All(:),AvDradAll(:),AvDrad2All(:),AvDpairAll(:),AvDpair2All(:),tmpd(:)
-  ! F(q,tau) (fq_tau = T): the block's raw sums from the device, the normalised block values, their per-walker sums and
-  ! the walker-averaged sums; nfv doubles of the block vector behind the density ones (0 with the key off)
-  integer :: nfq,nfv,nfqav,nfqall
+  real(8), allocatable :: dpl(:),drad(:),dpair(:)
+  type(block_series) :: sDpl,sDrad,sDpair
+  type(block_count)  :: cDens
+  ! F(q,tau) (fq_tau = T): the block's raw sums from the device and the normalised block values
   integer(c_int64_t), allocatable :: fq_smp(:)
   integer(c_int32_t), allocatable :: fq_reset(:)
-  real(8), allocatable :: fq_raw(:,:,:,:),fqb(:,:,:),AvFq(:,:,:,:),AvFq2(:,:,:,:),AvFqAll(:,:,:),AvFq2All(:,:,:),tmpf(:,:,:)
+  real(8), allocatable :: fq_raw(:,:,:,:),fqb(:,:,:)
+  type(block_series) :: sFq
+  type(block_count)  :: cFq
   ! vector S(q) (sq_vector = T): the stored vectors and their |q| shells, the block's raw sums from the device, the
-  ! normalised block values per vector and per shell, their per-walker sums and the walker-averaged sums; nsv doubles of
-  ! the block vector behind the F(q,tau) ones (0 with the key off)
-  integer :: nsq,nsv,nsqav,nsqall,nsh
+  ! normalised block values per vector and per shell
+  integer :: nsq,nsh
   integer(c_int64_t) :: sq_count
   integer(c_int32_t), allocatable :: sq_n(:,:),sq_reset(:)
   integer(c_int64_t), allocatable :: sq_smp(:)
   integer, allocatable :: sq_shell(:),sq_mult(:)
-  real(8), allocatable :: sq_raw(:,:),sqb(:),shb(:),sq_q(:),AvSq(:,:),AvSq2(:,:),AvSh(:,:),AvSh2(:,:)
-  real(8), allocatable :: AvSqAll(:),AvSq2All(:),AvShAll(:),AvSh2All(:)
+  real(8), allocatable :: sq_raw(:,:),sqb(:),shb(:),sq_q(:)
+  type(block_series) :: sSq,sSh
+  type(block_count)  :: cSq
   ! vector g(r) (gr_vector = T): the block's counts from the device, the normalised block values on the vector grid and
-  ! radially, their per-walker sums and the walker-averaged sums; ngv doubles of the block vector behind the vector-S(q)
-  ! ones (0 with the key off)
-  integer :: ngb,ngv,ngvav,ngvall
+  ! radially
+  integer :: ngb
   integer(c_int64_t), allocatable :: gv_vec(:,:),gv_rad(:,:),gv_smp(:)
   integer(c_int32_t), allocatable :: gv_reset(:)
-  real(8), allocatable :: gvb(:),gwb(:),AvGv(:,:),AvGv2(:,:),AvGw(:,:),AvGw2(:,:),AvGvAll(:),AvGv2All(:),AvGwAll(:),AvGw2All(:)
+  real(8), allocatable :: gvb(:),gwb(:)
+  type(block_series) :: sGv,sGw
+  type(block_count)  :: cGv
   ! vector F(q,tau) (fq_vector = T): the stored vectors and their |q| shells (those of the vector S(q)), the block's raw
-  ! sums from the device, the normalised block values per (vector, lag) and per (shell, lag), their per-walker sums and
-  ! the walker-averaged sums; nqv doubles of the block vector behind the vector-g(r) ones (0 with the key off)
-  integer :: nfx,nqv,nfxav,nfxall,nfsh,lag
+  ! sums from the device, the normalised block values per (vector, lag) and per (shell, lag)
+  integer :: nfx,nfsh
   integer(c_int64_t) :: fx_count
   integer(c_int32_t), allocatable :: fx_n(:,:),fx_reset(:)
   integer(c_int64_t), allocatable :: fx_smp(:)
   integer, allocatable :: fx_shell(:),fx_mult(:)
-  real(8), allocatable :: fx_raw(:,:,:),fxb(:,:),fxs(:,:),fx_q(:),AvFx(:,:,:),AvFx2(:,:,:),AvFs(:,:,:),AvFs2(:,:,:)
-  real(8), allocatable :: AvFxAll(:,:),AvFx2All(:,:),AvFsAll(:,:),AvFs2All(:,:)
+  real(8), allocatable :: fx_raw(:,:,:),fxb(:,:),fxs(:,:),fx_q(:)
+  type(block_series) :: sFx,sFs
+  type(block_count)  :: cFx
   ! imaginary-time profiles (tau_profile = T): the block's raw sums from the device (Vpair, Vext, W, D2 per slice), the
-  ! normalised block profiles, their per-walker sums and the walker-averaged sums; ntv doubles of the block vector behind
-  ! the vector-F(q,tau) ones (0 with the key off), starting behind offset otq; the units of press_vpi*.out
-  integer :: ntq,ntv,ntauav,ntauall,otq,upav
+  ! normalised block profiles; the units of press_vpi*.out
+  integer :: upav
+  integer(c_int64_t), allocatable :: tq_smp(:)
+  integer(c_int32_t), allocatable :: tq_reset(:)
+  integer, allocatable :: up(:)
+  real(8), allocatable :: tq_raw(:,:,:),tqb(:,:)
+  type(block_series) :: sTq
+  type(block_count)  :: cTq
+  real(8) :: wwin
   ! self part of F(q,tau) and displacement (fq_self = T): the stored vectors and their |q| shells, the block's raw sums
-  ! from the device, the normalised block values per (vector, lag), per (shell, lag) and the two moments per lag, their
-  ! per-walker sums and the walker-averaged sums; nzv doubles of the block vector behind the imaginary-time-profile ones
-  ! (0 with the key off), starting behind offset oqs: F_s [nzx,ntau+1], the moments [2,ntau+1], one count
-  integer :: nzx,nzf,nzv,nzav,nzall,nzsh,oqs
+  ! from the device, the normalised block values per (vector, lag), per (shell, lag) and the two moments per lag
+  integer :: nzx,nzsh
   integer(c_int64_t) :: zs_count
   integer(c_int32_t), allocatable :: zs_n(:,:),zs_reset(:)
   integer(c_int64_t), allocatable :: zs_smp(:)
   integer, allocatable :: zs_shell(:),zs_mult(:)
   real(8), allocatable :: zs_raw(:,:,:),zs_draw(:,:,:),zsb(:,:),zss(:,:),zsm(:,:),zs_q(:)
-  real(8), allocatable :: AvZx(:,:,:),AvZx2(:,:,:),AvZs(:,:,:),AvZs2(:,:,:),AvZm(:,:,:),AvZm2(:,:,:)
-  real(8), allocatable :: AvZxAll(:,:),AvZx2All(:,:),AvZsAll(:,:),AvZs2All(:,:),AvZmAll(:,:),AvZm2All(:,:)
-  integer(c_int64_t), allocatable :: tq_smp(:)
-  integer(c_int32_t), allocatable :: tq_reset(:)
-  integer, allocatable :: up(:)
-  real(8), allocatable :: tq_raw(:,:,:),tqb(:,:),AvTq(:,:,:),AvTq2(:,:,:),AvTqAll(:,:),AvTq2All(:,:),tmpt(:,:)
-  real(8) :: wwin
+  type(block_series) :: sZx,sZm,sZs
+  type(block_count)  :: cZs
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -590,8 +567,7 @@ contains
   ! from config_ini.in, or uniform random positions; every bead of a particle starts at the same
   ! point; walker w seeds its stream with seed+w-1
   do w=1,NW
-     suffix = ''
-     if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w0+w-1
+     suffix = walker_suffix(w0+w-1)
      if (resume) then
         open (newunit=ucfg,file='checkpoint'//trim(suffix)//'.dat',status='old')
         read (ucfg,*) lflag                      ! trap: the reference's init takes it from the file (vpi_mod.f90:166);
@@ -660,104 +636,102 @@ contains
      dev_acc0 = 0
   end if
 
-  npl = 0; ndv = 0; ndensav = 0
+  ! the first 20 doubles of the block vector: number of walkers with a diagonal block, their summed block energies, the
+  ! block's counters; behind them the summed normalised g(r), S(k), n(r) and how many walkers contributed, then what the
+  ! estimator keys add
+  nvec = 20
+  call series_create(sGr,Nbin,NW,nvec)
+  call series_create(sSk,dim*Nk,NW,nvec)
+  call series_create(sNr,(Npw+1)*Nbin,NW,nvec)
+  call count_create(cGr,nvec)
+  call count_create(cNr,nvec)
+
   if (density_profile) then
      npl = Nbin**min(dim,2)
-     ndv = npl+2*Nbin+1
      allocate (dc_pl(npl,NW),dc_rad(Nbin,NW),dc_pair(Nbin,NW),dc_smp(NW),dc_reset(NW),dpl(npl),drad(Nbin),dpair(Nbin))
-     allocate (AvDpl(npl,NW),AvDpl2(npl,NW),AvDrad(Nbin,NW),AvDrad2(Nbin,NW),AvDpair(Nbin,NW),AvDpair2(Nbin,NW))
-     allocate (AvDplAll(npl),AvDpl2All(npl),AvDradAll(Nbin),AvDrad2All(Nbin),AvDpairAll(Nbin),AvDpair2All(Nbin),tmpd(ndv-1))
-     AvDpl = 0.d0; AvDpl2 = 0.d0; AvDrad = 0.d0; AvDrad2 = 0.d0; AvDpair = 0.d0; AvDpair2 = 0.d0
-     AvDplAll = 0.d0; AvDpl2All = 0.d0; AvDradAll = 0.d0; AvDrad2All = 0.d0; AvDpairAll = 0.d0; AvDpair2All = 0.d0
+     call series_create(sDpl,npl,NW,nvec)
+     call series_create(sDrad,Nbin,NW,nvec)
+     call series_create(sDpair,Nbin,NW,nvec)
+     call count_create(cDens,nvec)
      dc_reset = 1
      call pigs_check(dens_init(ctx,int(Nbin,c_int32_t),rcut/2.d0),'pigs_density_init')
   end if
 
-  nfq = 0; nfv = 0; nfqav = 0
   if (fq_tau) then
-     nfq = dim*Nk*(fq_ntau+1)
-     nfv = nfq+1
-     ! (third index: lag l + 1; 1-based, as every array here that goes through reshape)
-     allocate (fq_raw(dim,Nk,fq_ntau+1,NW),fq_smp(NW),fq_reset(NW),fqb(dim,Nk,fq_ntau+1),tmpf(dim,Nk,fq_ntau+1))
-     allocate (AvFq(dim,Nk,fq_ntau+1,NW),AvFq2(dim,Nk,fq_ntau+1,NW),AvFqAll(dim,Nk,fq_ntau+1),AvFq2All(dim,Nk,fq_ntau+1))
-     AvFq = 0.d0; AvFq2 = 0.d0; AvFqAll = 0.d0; AvFq2All = 0.d0
+     ! (third index: lag l + 1)
+     allocate (fq_raw(dim,Nk,fq_ntau+1,NW),fq_smp(NW),fq_reset(NW),fqb(dim,Nk,fq_ntau+1))
+     call series_create(sFq,dim*Nk*(fq_ntau+1),NW,nvec)
+     call count_create(cFq,nvec)
      fq_reset = 1
      call pigs_check(fqt_init(ctx,int(Nk,c_int32_t),int(fq_ntau,c_int32_t),int(fq_window,c_int32_t)),'pigs_fqt_init')
   end if
 
-  nsq = 0; nsv = 0; nsqav = 0
   if (sq_vector) then
      call pigs_check(sqv_init(ctx,int(sq_nmax,c_int32_t),int(sq_window,c_int32_t)),'pigs_sqv_init')
      call pigs_check(sqv_count(ctx,sq_count),'pigs_sqv_count')
      nsq = int(sq_count)
-     nsv = nsq+1
      allocate (sq_n(dim,nsq),sq_shell(nsq),sq_raw(nsq,NW),sq_smp(NW),sq_reset(NW),sqb(nsq))
      call pigs_check(sqv_vectors(ctx,sq_n),'pigs_sqv_vectors')
      call sqv_shells(ep,nsq,sq_n,sq_shell,nsh,sq_q,sq_mult)
-     allocate (shb(nsh),AvSq(nsq,NW),AvSq2(nsq,NW),AvSh(nsh,NW),AvSh2(nsh,NW),AvSqAll(nsq),AvSq2All(nsq),AvShAll(nsh),AvSh2All(nsh))
-     AvSq = 0.d0; AvSq2 = 0.d0; AvSh = 0.d0; AvSh2 = 0.d0; AvSqAll = 0.d0; AvSq2All = 0.d0; AvShAll = 0.d0; AvSh2All = 0.d0
+     allocate (shb(nsh))
+     call series_create(sSq,nsq,NW,nvec)
+     call series_create(sSh,nsh,NW)
+     call count_create(cSq,nvec)
      sq_reset = 1
   end if
 
-  ngb = 0; ngv = 0; ngvav = 0
   if (gr_vector) then
      call pigs_check(grv_init(ctx,int(gr_nbin,c_int32_t),int(Nbin,c_int32_t),real(rbin,c_double),int(gr_window,c_int32_t)), &
           & 'pigs_grv_init')
      ngb = gr_nbin**dim
-     ngv = ngb+Nbin+1
      allocate (gv_vec(ngb,NW),gv_rad(Nbin,NW),gv_smp(NW),gv_reset(NW),gvb(ngb),gwb(Nbin))
-     allocate (AvGv(ngb,NW),AvGv2(ngb,NW),AvGw(Nbin,NW),AvGw2(Nbin,NW),AvGvAll(ngb),AvGv2All(ngb),AvGwAll(Nbin),AvGw2All(Nbin))
-     AvGv = 0.d0; AvGv2 = 0.d0; AvGw = 0.d0; AvGw2 = 0.d0; AvGvAll = 0.d0; AvGv2All = 0.d0; AvGwAll = 0.d0; AvGw2All = 0.d0
+     call series_create(sGv,ngb,NW,nvec)
+     call series_create(sGw,Nbin,NW,nvec)
+     call count_create(cGv,nvec)
      gv_reset = 1
   end if
 
-  nfx = 0; nqv = 0; nfxav = 0
   if (fq_vector) then
      call pigs_check(fqv_init(ctx,int(fqv_nmax,c_int32_t),int(fqv_ntau,c_int32_t),int(fqv_window,c_int32_t)),'pigs_fqv_init')
      call pigs_check(fqv_count(ctx,fx_count),'pigs_fqv_count')
      nfx = int(fx_count)
-     nqv = nfx*(fqv_ntau+1)+1
-     ! (second index: lag l + 1; 1-based, as every array here that goes through reshape)
+     ! (second index: lag l + 1)
      allocate (fx_n(dim,nfx),fx_shell(nfx),fx_raw(nfx,fqv_ntau+1,NW),fx_smp(NW),fx_reset(NW),fxb(nfx,fqv_ntau+1))
      call pigs_check(fqv_vectors(ctx,fx_n),'pigs_fqv_vectors')
      call sqv_shells(ep,nfx,fx_n,fx_shell,nfsh,fx_q,fx_mult)
-     allocate (fxs(nfsh,fqv_ntau+1),AvFx(nfx,fqv_ntau+1,NW),AvFx2(nfx,fqv_ntau+1,NW),AvFs(nfsh,fqv_ntau+1,NW),AvFs2(nfsh,fqv_ntau+1,NW))
-     allocate (AvFxAll(nfx,fqv_ntau+1),AvFx2All(nfx,fqv_ntau+1),AvFsAll(nfsh,fqv_ntau+1),AvFs2All(nfsh,fqv_ntau+1))
-     AvFx = 0.d0; AvFx2 = 0.d0; AvFs = 0.d0; AvFs2 = 0.d0; AvFxAll = 0.d0; AvFx2All = 0.d0; AvFsAll = 0.d0; AvFs2All = 0.d0
+     allocate (fxs(nfsh,fqv_ntau+1))
+     call series_create(sFx,nfx*(fqv_ntau+1),NW,nvec)
+     call series_create(sFs,nfsh*(fqv_ntau+1),NW)
+     call count_create(cFx,nvec)
      fx_reset = 1
   end if
 
-  ntq = 0; ntv = 0; ntauav = 0
   if (tau_profile) then
-     ntq = 4*(2*Nb+1)
-     ntv = ntq+1
-     ! (second index: slice b + 1; 1-based, as every array here that goes through reshape)
-     allocate (tq_raw(4,2*Nb+1,NW),tq_smp(NW),tq_reset(NW),tqb(4,2*Nb+1),tmpt(4,2*Nb+1))
-     allocate (AvTq(4,2*Nb+1,NW),AvTq2(4,2*Nb+1,NW),AvTqAll(4,2*Nb+1),AvTq2All(4,2*Nb+1))
-     AvTq = 0.d0; AvTq2 = 0.d0; AvTqAll = 0.d0; AvTq2All = 0.d0
+     ! (second index: slice b + 1)
+     allocate (tq_raw(4,2*Nb+1,NW),tq_smp(NW),tq_reset(NW),tqb(4,2*Nb+1))
+     call series_create(sTq,4*(2*Nb+1),NW,nvec)
+     call count_create(cTq,nvec)
      tq_reset = 1
      call pigs_check(tau_init(ctx),'pigs_tau_init')
   end if
 
-  nzx = 0; nzf = 0; nzv = 0; nzav = 0
   if (fq_self) then
      call pigs_check(fqs_init(ctx,int(fqs_nmax,c_int32_t),int(fqs_ntau,c_int32_t),int(fqs_window,c_int32_t)),'pigs_fqs_init')
      call pigs_check(fqs_count(ctx,zs_count),'pigs_fqs_count')
      nzx = int(zs_count)
-     nzf = nzx*(fqs_ntau+1)
-     nzv = nzf+2*(fqs_ntau+1)+1
-     ! (second index: lag l + 1; 1-based, as every array here that goes through reshape)
+     ! (second index: lag l + 1)
      allocate (zs_n(dim,nzx),zs_shell(nzx),zs_raw(nzx,fqs_ntau+1,NW),zs_draw(2,fqs_ntau+1,NW),zs_smp(NW),zs_reset(NW))
      allocate (zsb(nzx,fqs_ntau+1),zsm(2,fqs_ntau+1))
      call pigs_check(fqs_vectors(ctx,zs_n),'pigs_fqs_vectors')
      call sqv_shells(ep,nzx,zs_n,zs_shell,nzsh,zs_q,zs_mult)
-     allocate (zss(nzsh,fqs_ntau+1),AvZx(nzx,fqs_ntau+1,NW),AvZx2(nzx,fqs_ntau+1,NW),AvZs(nzsh,fqs_ntau+1,NW),AvZs2(nzsh,fqs_ntau+1,NW))
-     allocate (AvZm(2,fqs_ntau+1,NW),AvZm2(2,fqs_ntau+1,NW),AvZmAll(2,fqs_ntau+1),AvZm2All(2,fqs_ntau+1))
-     allocate (AvZxAll(nzx,fqs_ntau+1),AvZx2All(nzx,fqs_ntau+1),AvZsAll(nzsh,fqs_ntau+1),AvZs2All(nzsh,fqs_ntau+1))
-     AvZx = 0.d0; AvZx2 = 0.d0; AvZs = 0.d0; AvZs2 = 0.d0; AvZxAll = 0.d0; AvZx2All = 0.d0; AvZsAll = 0.d0; AvZs2All = 0.d0
-     AvZm = 0.d0; AvZm2 = 0.d0; AvZmAll = 0.d0; AvZm2All = 0.d0
+     allocate (zss(nzsh,fqs_ntau+1))
+     call series_create(sZx,nzx*(fqs_ntau+1),NW,nvec)
+     call series_create(sZm,2*(fqs_ntau+1),NW,nvec)
+     call series_create(sZs,nzsh*(fqs_ntau+1),NW)
+     call count_create(cZs,nvec)
      zs_reset = 1
   end if
+  allocate (vec(nvec))
 
   allocate (perm(NW))
   do w=1,NW
@@ -773,16 +747,14 @@ contains
   allocate (try_open(NW),try_close(NW),try_swap(NW),try_cm(NW),try_stag(NW),try_cm_half(NW),try_stag_half(NW))
   allocate (idiag(NW),idiag_aux(NW),idiag_block(NW),obdm_bl(NW),diag_bl(NW),ngr(NW))
   allocate (BE(3,NW),BE2(3,NW),BT(3,NW),BT2(3,NW),AE(3,NW),AE2(3,NW),AT(3,NW),AT2(3,NW))
-  allocate (gr(Nbin,NW),AvGr(Nbin,NW),AvGr2(Nbin,NW),Sk(dim,Nk,NW),AvSk(dim,Nk,NW),AvSk2(dim,Nk,NW))
-  allocate (nrho(0:Npw,Nbin,NW),AvNr(0:Npw,Nbin,NW),AvNr2(0:Npw,Nbin,NW))
+  allocate (gr(Nbin,NW),Sk(dim,Nk,NW),nrho(0:Npw,Nbin,NW))
   AE = 0.d0; AE2 = 0.d0; AT = 0.d0; AT2 = 0.d0
-  AvGr = 0.d0; AvGr2 = 0.d0; AvSk = 0.d0; AvSk2 = 0.d0; AvNr = 0.d0; AvNr2 = 0.d0; nrho = 0.d0
+  nrho = 0.d0
   idiag = 0; idiag_aux = 0; obdm_bl = 0; diag_bl = 0
 
   allocate (ue(NW),ut(NW),uh(NW))
   do w=1,NW
-     suffix = ''
-     if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w0+w-1
+     suffix = walker_suffix(w0+w-1)
      open (newunit=ue(w),file='e_vpi'//trim(suffix)//'.out')
      open (newunit=ut(w),file='et_vpi'//trim(suffix)//'.out')
      open (newunit=uh(w),file='e_vpi'//trim(suffix)//'.hex')
@@ -795,8 +767,7 @@ contains
      ! the virial pressure per block (periodic runs): per walker, and the walker average where there are several
      allocate (up(NW))
      do w=1,NW
-        suffix = ''
-        if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w0+w-1
+        suffix = walker_suffix(w0+w-1)
         open (newunit=up(w),file='press_vpi'//trim(suffix)//'.out')
         call press_header(up(w))
      end do
@@ -805,16 +776,6 @@ contains
         call press_header(upav)
      end if
   end if
-
-  ! the vector that meets the other shards' once per block: number of walkers with a diagonal block, their summed block
-  ! energies, the block's counters, the summed normalised g(r), S(k), n(r) and how many walkers contributed to each
-  nvec = 7+13+Nbin+dim*Nk+(Npw+1)*Nbin+2
-  otq = nvec+ndv+nfv+nsv+ngv+nqv
-  oqs = otq+ntv
-  allocate (vec(oqs+nzv),AvGrAll(Nbin),AvGr2All(Nbin),AvSkAll(dim,Nk),AvSk2All(dim,Nk),AvNrAll(0:Npw,Nbin),AvNr2All(0:Npw,Nbin))
-  allocate (tmp1(Nbin),tmp2(dim,Nk),tmp3(0:Npw,Nbin))
-  AvGrAll = 0.d0; AvGr2All = 0.d0; AvSkAll = 0.d0; AvSk2All = 0.d0; AvNrAll = 0.d0; AvNr2All = 0.d0
-  ngrav = 0; nnrav = 0
 
   do iblock=1,Nblock
 
@@ -1077,80 +1038,60 @@ contains
            if (.not. trap) then
               call normalize_gr(ep,density,ngr(w),gr(:,w))
               call normalize_sk(ep,ngr(w),Sk(:,:,w))
-              AvGr(:,w) = AvGr(:,w)+gr(:,w); AvGr2(:,w) = AvGr2(:,w)+gr(:,w)*gr(:,w)
-              AvSk(:,:,w) = AvSk(:,:,w)+Sk(:,:,w); AvSk2(:,:,w) = AvSk2(:,:,w)+Sk(:,:,w)*Sk(:,:,w)
-              vec(21:20+Nbin) = vec(21:20+Nbin)+gr(:,w)
-              vec(21+Nbin:20+Nbin+dim*Nk) = vec(21+Nbin:20+Nbin+dim*Nk)+reshape(Sk(:,:,w),[dim*Nk])
-              vec(nvec-1) = vec(nvec-1)+1.d0
+              call series_add(sGr,w,gr(:,w),vec)
+              call series_add(sSk,w,Sk(:,:,w),vec)
+              call count_add(cGr,vec)
            end if
            if (density_profile) then
               call normalize_density(dim,Np,Nbin,rcut/2.d0,int(dc_smp(w),8),dc_pl(:,w),dc_rad(:,w),dc_pair(:,w),dpl,drad,dpair)
-              AvDpl(:,w)   = AvDpl(:,w)+dpl;     AvDpl2(:,w)   = AvDpl2(:,w)+dpl*dpl
-              AvDrad(:,w)  = AvDrad(:,w)+drad;   AvDrad2(:,w)  = AvDrad2(:,w)+drad*drad
-              AvDpair(:,w) = AvDpair(:,w)+dpair; AvDpair2(:,w) = AvDpair2(:,w)+dpair*dpair
-              vec(nvec+1:nvec+npl) = vec(nvec+1:nvec+npl)+dpl
-              vec(nvec+npl+1:nvec+npl+Nbin) = vec(nvec+npl+1:nvec+npl+Nbin)+drad
-              vec(nvec+npl+Nbin+1:nvec+npl+2*Nbin) = vec(nvec+npl+Nbin+1:nvec+npl+2*Nbin)+dpair
-              vec(nvec+ndv) = vec(nvec+ndv)+1.d0
+              call series_add(sDpl,w,dpl,vec)
+              call series_add(sDrad,w,drad,vec)
+              call series_add(sDpair,w,dpair,vec)
+              call count_add(cDens,vec)
            end if
            if (fq_tau) then
               call normalize_fqt(ep,fq_ntau,fq_window,int(fq_smp(w),8),fq_raw(:,:,:,w),fqb)
-              AvFq(:,:,:,w) = AvFq(:,:,:,w)+fqb; AvFq2(:,:,:,w) = AvFq2(:,:,:,w)+fqb*fqb
-              vec(nvec+ndv+1:nvec+ndv+nfq) = vec(nvec+ndv+1:nvec+ndv+nfq)+reshape(fqb,[nfq])
-              vec(nvec+ndv+nfv) = vec(nvec+ndv+nfv)+1.d0
+              call series_add(sFq,w,fqb,vec)
+              call count_add(cFq,vec)
            end if
            if (sq_vector) then
               call normalize_sqv(Np,sq_window,int(sq_smp(w),8),nsq,sq_raw(:,w),sqb)
               call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sqb,shb)
-              AvSq(:,w) = AvSq(:,w)+sqb; AvSq2(:,w) = AvSq2(:,w)+sqb*sqb
-              AvSh(:,w) = AvSh(:,w)+shb; AvSh2(:,w) = AvSh2(:,w)+shb*shb
-              vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq) = vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq)+sqb
-              vec(nvec+ndv+nfv+nsv) = vec(nvec+ndv+nfv+nsv)+1.d0
+              call series_add(sSq,w,sqb,vec)
+              call series_add(sSh,w,shb,vec)
+              call count_add(cSq,vec)
            end if
            if (gr_vector) then
               call normalize_grv(ep,density,gr_window,int(gv_smp(w),8),gr_nbin,ngb,gv_vec(:,w),gv_rad(:,w),gvb,gwb)
-              AvGv(:,w) = AvGv(:,w)+gvb; AvGv2(:,w) = AvGv2(:,w)+gvb*gvb
-              AvGw(:,w) = AvGw(:,w)+gwb; AvGw2(:,w) = AvGw2(:,w)+gwb*gwb
-              vec(nvec+ndv+nfv+nsv+1:nvec+ndv+nfv+nsv+ngb) = vec(nvec+ndv+nfv+nsv+1:nvec+ndv+nfv+nsv+ngb)+gvb
-              vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin) = vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin)+gwb
-              vec(nvec+ndv+nfv+nsv+ngv) = vec(nvec+ndv+nfv+nsv+ngv)+1.d0
+              call series_add(sGv,w,gvb,vec)
+              call series_add(sGw,w,gwb,vec)
+              call count_add(cGv,vec)
            end if
            if (fq_vector) then
               call normalize_fqv(Np,fqv_ntau,fqv_window,int(fx_smp(w),8),nfx,fx_raw(:,:,w),fxb)
-              do lag=1,fqv_ntau+1
-                 call sqv_shell_means(nfx,fx_shell,nfsh,fx_mult,fxb(:,lag),fxs(:,lag))
-              end do
-              AvFx(:,:,w) = AvFx(:,:,w)+fxb; AvFx2(:,:,w) = AvFx2(:,:,w)+fxb*fxb
-              AvFs(:,:,w) = AvFs(:,:,w)+fxs; AvFs2(:,:,w) = AvFs2(:,:,w)+fxs*fxs
-              vec(nvec+ndv+nfv+nsv+ngv+1:nvec+ndv+nfv+nsv+ngv+nqv-1) = vec(nvec+ndv+nfv+nsv+ngv+1:nvec+ndv+nfv+nsv+ngv+nqv-1) &
-                   & +reshape(fxb,[nqv-1])
-              vec(nvec+ndv+nfv+nsv+ngv+nqv) = vec(nvec+ndv+nfv+nsv+ngv+nqv)+1.d0
+              call shell_means_lags(nfx,fx_shell,nfsh,fx_mult,fqv_ntau,fxb,fxs)
+              call series_add(sFx,w,fxb,vec)
+              call series_add(sFs,w,fxs,vec)
+              call count_add(cFx,vec)
            end if
            if (tau_profile) then
               call normalize_tau(dim,Np,Nb,dt,int(tq_smp(w),8),tq_raw(:,:,w),tqb)
-              AvTq(:,:,w) = AvTq(:,:,w)+tqb; AvTq2(:,:,w) = AvTq2(:,:,w)+tqb*tqb
-              do ib=1,2*Nb+1
-                 vec(otq+4*ib-3:otq+4*ib) = vec(otq+4*ib-3:otq+4*ib)+tqb(:,ib)
-              end do
-              vec(otq+ntv) = vec(otq+ntv)+1.d0
+              call series_add(sTq,w,tqb,vec)
+              call count_add(cTq,vec)
               if (.not. trap) then
                  ! W/Np over the window, the block's Kin/N of e_vpi.out, P = density/dim (2 Kin/N - W/N)
-                 wwin = sum(tqb(3,Nb+1-tau_window:Nb+1+tau_window))/real(2*tau_window+1,8)
+                 wwin = virial_window(tqb)
                  write (up(w),'(20g20.10e3)') real(iblock),wwin,BE(2,w)/Np,density/real(dim,8)*(2.d0*(BE(2,w)/Np)-wwin)
               end if
            end if
            if (fq_self) then
               call normalize_fqv(Np,fqs_ntau,fqs_window,int(zs_smp(w),8),nzx,zs_raw(:,:,w),zsb)
               call normalize_msd(Np,fqs_ntau,fqs_window,int(zs_smp(w),8),zs_draw(:,:,w),zsm)
-              do lag=1,fqs_ntau+1
-                 call sqv_shell_means(nzx,zs_shell,nzsh,zs_mult,zsb(:,lag),zss(:,lag))
-              end do
-              AvZx(:,:,w) = AvZx(:,:,w)+zsb; AvZx2(:,:,w) = AvZx2(:,:,w)+zsb*zsb
-              AvZs(:,:,w) = AvZs(:,:,w)+zss; AvZs2(:,:,w) = AvZs2(:,:,w)+zss*zss
-              AvZm(:,:,w) = AvZm(:,:,w)+zsm; AvZm2(:,:,w) = AvZm2(:,:,w)+zsm*zsm
-              vec(oqs+1:oqs+nzf) = vec(oqs+1:oqs+nzf)+reshape(zsb,[nzf])
-              vec(oqs+nzf+1:oqs+nzv-1) = vec(oqs+nzf+1:oqs+nzv-1)+reshape(zsm,[2*(fqs_ntau+1)])
-              vec(oqs+nzv) = vec(oqs+nzv)+1.d0
+              call shell_means_lags(nzx,zs_shell,nzsh,zs_mult,fqs_ntau,zsb,zss)
+              call series_add(sZx,w,zsb,vec)
+              call series_add(sZm,w,zsm,vec)
+              call series_add(sZs,w,zss,vec)
+              call count_add(cZs,vec)
            end if
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -1161,10 +1102,8 @@ contains
            obdm_bl(w) = obdm_bl(w)+1
            if (.not. trap) then
               call normalize_nr(ep,density,real(idiag_aux(w),8),Nobdm,nrho(:,:,w))
-              AvNr(:,:,w) = AvNr(:,:,w)+nrho(:,:,w); AvNr2(:,:,w) = AvNr2(:,:,w)+nrho(:,:,w)*nrho(:,:,w)
-              vec(21+Nbin+dim*Nk:20+Nbin+dim*Nk+(Npw+1)*Nbin) = vec(21+Nbin+dim*Nk:20+Nbin+dim*Nk+(Npw+1)*Nbin) &
-                   & +reshape(nrho(:,:,w),[(Npw+1)*Nbin])
-              vec(nvec) = vec(nvec)+1.d0
+              call series_add(sNr,w,nrho(:,:,w),vec)
+              call count_add(cNr,vec)
            end if
            idiag_aux(w) = 0
            nrho(:,:,w)  = 0.d0
@@ -1175,102 +1114,73 @@ contains
      vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
           & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
           & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(oqs+nzv,c_int32_t)),'pigs_estimators_allreduce')
+     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec,c_int32_t)),'pigs_estimators_allreduce')
      ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
-     ngrall = nint(vec(nvec-1)); nnrall = nint(vec(nvec))
+     ! ---- the walker average of every block value, over the walkers of all shards that counted the block
      if (ish==1 .and. NWtot>1) then
         if (ndall>0) then
            write (ueav,'(5g20.10e3)') real(iblock),mE/ndall
            write (utav,'(5g20.10e3)') real(iblock),mT/ndall
         end if
-        if (ngrall>0) then                   ! walker average of the block's normalised g(r), S(k)
-           ngrav = ngrav+1
-           tmp1 = vec(21:20+Nbin)/ngrall
-           tmp2 = reshape(vec(21+Nbin:20+Nbin+dim*Nk),[dim,Nk])/ngrall
-           AvGrAll = AvGrAll+tmp1; AvGr2All = AvGr2All+tmp1*tmp1
-           AvSkAll = AvSkAll+tmp2; AvSk2All = AvSk2All+tmp2*tmp2
+        nall = count_reduced(cGr,vec)
+        if (nall>0) then
+           call series_average(sGr,vec,nall)
+           call series_average(sSk,vec,nall)
         end if
-        if (nnrall>0) then
-           nnrav = nnrav+1
-           tmp3 = reshape(vec(21+Nbin+dim*Nk:20+Nbin+dim*Nk+(Npw+1)*Nbin),[Npw+1,Nbin])/nnrall
-           AvNrAll = AvNrAll+tmp3; AvNr2All = AvNr2All+tmp3*tmp3
-        end if
-        if (density_profile) then            ! walker average of the block's density profiles
-           ndensall = nint(vec(nvec+ndv))
-           if (ndensall>0) then
-              ndensav = ndensav+1
-              tmpd = vec(nvec+1:nvec+ndv-1)/ndensall
-              AvDplAll   = AvDplAll+tmpd(1:npl);                 AvDpl2All   = AvDpl2All+tmpd(1:npl)**2
-              AvDradAll  = AvDradAll+tmpd(npl+1:npl+Nbin);       AvDrad2All  = AvDrad2All+tmpd(npl+1:npl+Nbin)**2
-              AvDpairAll = AvDpairAll+tmpd(npl+Nbin+1:npl+2*Nbin); AvDpair2All = AvDpair2All+tmpd(npl+Nbin+1:npl+2*Nbin)**2
+        nall = count_reduced(cNr,vec)
+        if (nall>0) call series_average(sNr,vec,nall)
+        if (density_profile) then
+           nall = count_reduced(cDens,vec)
+           if (nall>0) then
+              call series_average(sDpl,vec,nall)
+              call series_average(sDrad,vec,nall)
+              call series_average(sDpair,vec,nall)
            end if
         end if
-        if (fq_tau) then                     ! walker average of the block's F(q,tau)
-           nfqall = nint(vec(nvec+ndv+nfv))
-           if (nfqall>0) then
-              nfqav = nfqav+1
-              tmpf = reshape(vec(nvec+ndv+1:nvec+ndv+nfq),[dim,Nk,fq_ntau+1])/nfqall
-              AvFqAll = AvFqAll+tmpf; AvFq2All = AvFq2All+tmpf*tmpf
+        if (fq_tau) then
+           nall = count_reduced(cFq,vec)
+           if (nall>0) call series_average(sFq,vec,nall)
+        end if
+        if (sq_vector) then                  ! the shell means are those of the averaged vectors
+           nall = count_reduced(cSq,vec)
+           if (nall>0) then
+              call series_average(sSq,vec,nall)
+              call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sSq%mean,shb)
+              call series_add_mean(sSh,shb)
            end if
         end if
-        if (sq_vector) then                  ! walker average of the block's vector S(q) and of its shell means
-           nsqall = nint(vec(nvec+ndv+nfv+nsv))
-           if (nsqall>0) then
-              nsqav = nsqav+1
-              sqb = vec(nvec+ndv+nfv+1:nvec+ndv+nfv+nsq)/nsqall
-              call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sqb,shb)
-              AvSqAll = AvSqAll+sqb; AvSq2All = AvSq2All+sqb*sqb
-              AvShAll = AvShAll+shb; AvSh2All = AvSh2All+shb*shb
+        if (gr_vector) then
+           nall = count_reduced(cGv,vec)
+           if (nall>0) then
+              call series_average(sGv,vec,nall)
+              call series_average(sGw,vec,nall)
            end if
         end if
-        if (gr_vector) then                  ! walker average of the block's vector and windowed radial g(r)
-           ngvall = nint(vec(nvec+ndv+nfv+nsv+ngv))
-           if (ngvall>0) then
-              ngvav = ngvav+1
-              gvb = vec(nvec+ndv+nfv+nsv+1:nvec+ndv+nfv+nsv+ngb)/ngvall
-              gwb = vec(nvec+ndv+nfv+nsv+ngb+1:nvec+ndv+nfv+nsv+ngb+Nbin)/ngvall
-              AvGvAll = AvGvAll+gvb; AvGv2All = AvGv2All+gvb*gvb
-              AvGwAll = AvGwAll+gwb; AvGw2All = AvGw2All+gwb*gwb
+        if (fq_vector) then
+           nall = count_reduced(cFx,vec)
+           if (nall>0) then
+              call series_average(sFx,vec,nall)
+              call shell_means_lags(nfx,fx_shell,nfsh,fx_mult,fqv_ntau,sFx%mean,fxs)
+              call series_add_mean(sFs,fxs)
            end if
         end if
-        if (fq_vector) then                  ! walker average of the block's vector F(q,tau) and of its shell means
-           nfxall = nint(vec(nvec+ndv+nfv+nsv+ngv+nqv))
-           if (nfxall>0) then
-              nfxav = nfxav+1
-              fxb = reshape(vec(nvec+ndv+nfv+nsv+ngv+1:nvec+ndv+nfv+nsv+ngv+nqv-1),[nfx,fqv_ntau+1])/nfxall
-              do lag=1,fqv_ntau+1
-                 call sqv_shell_means(nfx,fx_shell,nfsh,fx_mult,fxb(:,lag),fxs(:,lag))
-              end do
-              AvFxAll = AvFxAll+fxb; AvFx2All = AvFx2All+fxb*fxb
-              AvFsAll = AvFsAll+fxs; AvFs2All = AvFs2All+fxs*fxs
+        if (tau_profile) then
+           nall = count_reduced(cTq,vec)
+           if (nall>0) then
+              call series_average(sTq,vec,nall)
+              if (.not. trap .and. ndall>0) then
+                 wwin = virial_window(sTq%mean)
+                 write (upav,'(20g20.10e3)') real(iblock),wwin,mE(2)/ndall,density/real(dim,8)*(2.d0*(mE(2)/ndall)-wwin)
+              end if
            end if
         end if
-     end if
-     if (ish==1 .and. NWtot>1 .and. fq_self) then          ! walker average of the block's self part and displacement
-        nzall = nint(vec(oqs+nzv))
-        if (nzall>0) then
-           nzav = nzav+1
-           zsb = reshape(vec(oqs+1:oqs+nzf),[nzx,fqs_ntau+1])/nzall
-           zsm = reshape(vec(oqs+nzf+1:oqs+nzv-1),[2,fqs_ntau+1])/nzall
-           do lag=1,fqs_ntau+1
-              call sqv_shell_means(nzx,zs_shell,nzsh,zs_mult,zsb(:,lag),zss(:,lag))
-           end do
-           AvZxAll = AvZxAll+zsb; AvZx2All = AvZx2All+zsb*zsb
-           AvZsAll = AvZsAll+zss; AvZs2All = AvZs2All+zss*zss
-           AvZmAll = AvZmAll+zsm; AvZm2All = AvZm2All+zsm*zsm
-        end if
-     end if
-     if (ish==1 .and. NWtot>1 .and. tau_profile) then      ! walker average of the block's imaginary-time profiles
-        ntauall = nint(vec(otq+ntv))
-        if (ntauall>0) then
-           ntauav = ntauav+1
-           do ib=1,2*Nb+1
-              tmpt(:,ib) = vec(otq+4*ib-3:otq+4*ib)/ntauall
-           end do
-           AvTqAll = AvTqAll+tmpt; AvTq2All = AvTq2All+tmpt*tmpt
-           if (.not. trap .and. ndall>0) then
-              wwin = sum(tmpt(3,Nb+1-tau_window:Nb+1+tau_window))/real(2*tau_window+1,8)
-              write (upav,'(20g20.10e3)') real(iblock),wwin,mE(2)/ndall,density/real(dim,8)*(2.d0*(mE(2)/ndall)-wwin)
+        if (fq_self) then
+           nall = count_reduced(cZs,vec)
+           if (nall>0) then
+              call series_average(sZx,vec,nall)
+              call series_average(sZm,vec,nall)
+              call shell_means_lags(nzx,zs_shell,nzsh,zs_mult,fqs_ntau,sZx%mean,zss)
+              call series_add_mean(sZs,zss)
            end if
         end if
      end if
@@ -1286,8 +1196,7 @@ contains
            s%isopen = dev_open/=0; s%iworm = dev_iworm
         end if
         do w=1,NW
-           suffix = ''
-           if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w0+w-1
+           suffix = walker_suffix(w0+w-1)
            open (newunit=ucfg,file='checkpoint'//trim(suffix)//'.dat')
            if (trap) then
               write (ucfg,*) ".True."
@@ -1341,8 +1250,7 @@ contains
   !=====================================================================
   ! final averages and files (reference vpi.f90:590-642)
   do w=1,NW
-     suffix = ''
-     if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w0+w-1
+     suffix = walker_suffix(w0+w-1)
      close (ue(w)); close (ut(w)); close (uh(w))
      if (swapping) then
         open (newunit=k,file='perm_vpi'//trim(suffix)//'.out')
@@ -1354,70 +1262,70 @@ contains
      if (.not. trap) then
         ! written unconditionally, like the reference (a run without a single diagonal / OBDM block
         ! yields NaN columns there too)
-        call write_radial('gr_vpi'//trim(suffix)//'.out',ep,diag_bl(w),AvGr(:,w),AvGr2(:,w))
-        call write_sk('sk_vpi'//trim(suffix)//'.out',ep,diag_bl(w),AvSk(:,:,w),AvSk2(:,:,w))
-        call write_nr('nr_vpi'//trim(suffix)//'.out',ep,obdm_bl(w),AvNr(:,:,w),AvNr2(:,:,w))
+        call write_radial('gr_vpi'//trim(suffix)//'.out',ep,diag_bl(w),sGr%sum(:,w),sGr%sq(:,w))
+        call write_sk('sk_vpi'//trim(suffix)//'.out',ep,diag_bl(w),sSk%sum(:,w),sSk%sq(:,w))
+        call write_nr('nr_vpi'//trim(suffix)//'.out',ep,obdm_bl(w),sNr%sum(:,w),sNr%sq(:,w))
      end if
      if (density_profile) then
-        call write_density('dens_vpi'//trim(suffix)//'.out',dim,Nbin,rcut/2.d0,diag_bl(w),AvDpl(:,w),AvDpl2(:,w))
-        call write_profile('rho_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),AvDrad(:,w),AvDrad2(:,w))
-        call write_profile('pr_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),AvDpair(:,w),AvDpair2(:,w))
+        call write_density('dens_vpi'//trim(suffix)//'.out',dim,Nbin,rcut/2.d0,diag_bl(w),sDpl%sum(:,w),sDpl%sq(:,w))
+        call write_profile('rho_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),sDrad%sum(:,w),sDrad%sq(:,w))
+        call write_profile('pr_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),sDpair%sum(:,w),sDpair%sq(:,w))
      end if
-     if (fq_tau) call write_fqt('fqt_vpi'//trim(suffix)//'.out',ep,fq_ntau,fq_window,dt,diag_bl(w),AvFq(:,:,:,w),AvFq2(:,:,:,w))
+     if (fq_tau) call write_fqt('fqt_vpi'//trim(suffix)//'.out',ep,fq_ntau,fq_window,dt,diag_bl(w),sFq%sum(:,w),sFq%sq(:,w))
      if (sq_vector) then
-        call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',ep,nsq,sq_n,diag_bl(w),AvSq(:,w),AvSq2(:,w))
-        call write_sqshell('sq_vpi'//trim(suffix)//'.out',nsh,sq_q,sq_mult,diag_bl(w),AvSh(:,w),AvSh2(:,w))
+        call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',ep,nsq,sq_n,diag_bl(w),sSq%sum(:,w),sSq%sq(:,w))
+        call write_sqshell('sq_vpi'//trim(suffix)//'.out',nsh,sq_q,sq_mult,diag_bl(w),sSh%sum(:,w),sSh%sq(:,w))
      end if
      if (gr_vector) then
-        call write_grvec('grvec_vpi'//trim(suffix)//'.out',ep,gr_nbin,ngb,diag_bl(w),AvGv(:,w),AvGv2(:,w))
-        call write_radial('grw_vpi'//trim(suffix)//'.out',ep,diag_bl(w),AvGw(:,w),AvGw2(:,w))
+        call write_grvec('grvec_vpi'//trim(suffix)//'.out',ep,gr_nbin,ngb,diag_bl(w),sGv%sum(:,w),sGv%sq(:,w))
+        call write_radial('grw_vpi'//trim(suffix)//'.out',ep,diag_bl(w),sGw%sum(:,w),sGw%sq(:,w))
      end if
      if (fq_vector) then
-        call write_fqvec('fqvec_vpi'//trim(suffix)//'.out',ep,fqv_ntau,dt,nfx,fx_n,diag_bl(w),AvFx(:,:,w),AvFx2(:,:,w))
-        call write_fqshell('fqsh_vpi'//trim(suffix)//'.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,diag_bl(w),AvFs(:,:,w),AvFs2(:,:,w))
+        call write_fqvec('fqvec_vpi'//trim(suffix)//'.out',ep,fqv_ntau,dt,nfx,fx_n,diag_bl(w),sFx%sum(:,w),sFx%sq(:,w))
+        call write_fqshell('fqsh_vpi'//trim(suffix)//'.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,diag_bl(w),sFs%sum(:,w),sFs%sq(:,w))
      end if
      if (fq_self) then
-        call write_fqvec('fqself_vpi'//trim(suffix)//'.out',ep,fqs_ntau,dt,nzx,zs_n,diag_bl(w),AvZx(:,:,w),AvZx2(:,:,w))
-        call write_fqshell('fqssh_vpi'//trim(suffix)//'.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,diag_bl(w),AvZs(:,:,w),AvZs2(:,:,w))
-        call write_msd('msd_vpi'//trim(suffix)//'.out',dim,fqs_ntau,dt,diag_bl(w),AvZm(:,:,w),AvZm2(:,:,w))
+        call write_fqvec('fqself_vpi'//trim(suffix)//'.out',ep,fqs_ntau,dt,nzx,zs_n,diag_bl(w),sZx%sum(:,w),sZx%sq(:,w))
+        call write_fqshell('fqssh_vpi'//trim(suffix)//'.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,diag_bl(w),sZs%sum(:,w),sZs%sq(:,w))
+        call write_msd('msd_vpi'//trim(suffix)//'.out',dim,fqs_ntau,dt,diag_bl(w),sZm%sum(:,w),sZm%sq(:,w))
      end if
      if (tau_profile) then
-        call write_tau('tau_vpi'//trim(suffix)//'.out',Nb,dt,diag_bl(w),AvTq(:,:,w),AvTq2(:,:,w))
+        call write_tau('tau_vpi'//trim(suffix)//'.out',Nb,dt,diag_bl(w),sTq%sum(:,w),sTq%sq(:,w))
         if (.not. trap) close (up(w))
      end if
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
      if (.not. trap) then                    ! walker-averaged histograms from the reduced block vectors
-        call write_radial('gr_vpi.out',ep,ngrav,AvGrAll,AvGr2All)
-        call write_sk('sk_vpi.out',ep,ngrav,AvSkAll,AvSk2All)
-        call write_nr('nr_vpi.out',ep,nnrav,AvNrAll,AvNr2All)
+        call write_radial('gr_vpi.out',ep,cGr%nav,sGr%asum,sGr%asq)
+        call write_sk('sk_vpi.out',ep,cGr%nav,sSk%asum,sSk%asq)
+        call write_nr('nr_vpi.out',ep,cNr%nav,sNr%asum,sNr%asq)
      end if
      if (density_profile) then
-        call write_density('dens_vpi.out',dim,Nbin,rcut/2.d0,ndensav,AvDplAll,AvDpl2All)
-        call write_profile('rho_vpi.out',Nbin,rcut/2.d0,ndensav,AvDradAll,AvDrad2All)
-        call write_profile('pr_vpi.out',Nbin,rcut/2.d0,ndensav,AvDpairAll,AvDpair2All)
+        call write_density('dens_vpi.out',dim,Nbin,rcut/2.d0,cDens%nav,sDpl%asum,sDpl%asq)
+        call write_profile('rho_vpi.out',Nbin,rcut/2.d0,cDens%nav,sDrad%asum,sDrad%asq)
+        call write_profile('pr_vpi.out',Nbin,rcut/2.d0,cDens%nav,sDpair%asum,sDpair%asq)
      end if
-     if (fq_tau) call write_fqt('fqt_vpi.out',ep,fq_ntau,fq_window,dt,nfqav,AvFqAll,AvFq2All)
+     if (fq_tau) call write_fqt('fqt_vpi.out',ep,fq_ntau,fq_window,dt,cFq%nav,sFq%asum,sFq%asq)
      if (sq_vector) then
-        call write_sqvec('sqvec_vpi.out',ep,nsq,sq_n,nsqav,AvSqAll,AvSq2All)
-        call write_sqshell('sq_vpi.out',nsh,sq_q,sq_mult,nsqav,AvShAll,AvSh2All)
+        call write_sqvec('sqvec_vpi.out',ep,nsq,sq_n,cSq%nav,sSq%asum,sSq%asq)
+        call write_sqshell('sq_vpi.out',nsh,sq_q,sq_mult,cSq%nav,sSh%asum,sSh%asq)
      end if
      if (gr_vector) then
-        call write_grvec('grvec_vpi.out',ep,gr_nbin,ngb,ngvav,AvGvAll,AvGv2All)
-        call write_radial('grw_vpi.out',ep,ngvav,AvGwAll,AvGw2All)
+        call write_grvec('grvec_vpi.out',ep,gr_nbin,ngb,cGv%nav,sGv%asum,sGv%asq)
+        call write_radial('grw_vpi.out',ep,cGv%nav,sGw%asum,sGw%asq)
      end if
      if (fq_vector) then
-        call write_fqvec('fqvec_vpi.out',ep,fqv_ntau,dt,nfx,fx_n,nfxav,AvFxAll,AvFx2All)
-        call write_fqshell('fqsh_vpi.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,nfxav,AvFsAll,AvFs2All)
+        call write_fqvec('fqvec_vpi.out',ep,fqv_ntau,dt,nfx,fx_n,cFx%nav,sFx%asum,sFx%asq)
+        call write_fqshell('fqsh_vpi.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,cFx%nav,sFs%asum,sFs%asq)
      end if
      if (fq_self) then
-        call write_fqvec('fqself_vpi.out',ep,fqs_ntau,dt,nzx,zs_n,nzav,AvZxAll,AvZx2All)
-        call write_fqshell('fqssh_vpi.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,nzav,AvZsAll,AvZs2All)
-        call write_msd('msd_vpi.out',dim,fqs_ntau,dt,nzav,AvZmAll,AvZm2All)
+        call write_fqvec('fqself_vpi.out',ep,fqs_ntau,dt,nzx,zs_n,cZs%nav,sZx%asum,sZx%asq)
+        call write_fqshell('fqssh_vpi.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,cZs%nav,sZs%asum,sZs%asq)
+        call write_msd('msd_vpi.out',dim,fqs_ntau,dt,cZs%nav,sZm%asum,sZm%asq)
      end if
      if (tau_profile) then
-        call write_tau('tau_vpi.out',Nb,dt,ntauav,AvTqAll,AvTq2All)
+        call write_tau('tau_vpi.out',Nb,dt,cTq%nav,sTq%asum,sTq%asq)
         if (.not. trap) close (upav)
      end if
   end if
@@ -1452,6 +1360,55 @@ contains
 
   call sampler_free(s)
   end subroutine run_shard
+
+  ! the keys of fq_vector and fq_self (pre = fqv, fqs): pre_nmax within what the device stores, the lags 0..pre_ntau
+  ! within the window Nb-pre_window..Nb+pre_window (left out: the smallest window that holds them), the window on the path
+  subroutine check_vectors_and_lags(key,pre,nmax,ntau,window)
+    character(len=*), intent(in) :: key,pre
+    integer, intent(in)    :: nmax,ntau
+    integer, intent(inout) :: window
+    if (nmax<1 .or. nmax>merge(16,64,dim==3)) then
+       write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: '//key//' = T: '//pre//'_nmax = ',nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
+            & ' (dim = ',dim,')'
+       stop 2
+    end if
+    if (window<0) window = (max(ntau,0)+1)/2                   ! ceiling(ntau/2)
+    if (ntau<0 .or. ntau>2*window) then
+       write (0,'(a,i0,a,i0,a)') ' pigs_vpi: '//key//' = T: '//pre//'_ntau = ',ntau,' must lie in 0 .. 2*'//pre//'_window = ',2*window, &
+            & ' (lags between the slices Nb-'//pre//'_window .. Nb+'//pre//'_window)'
+       stop 2
+    end if
+    if (window>Nb) then
+       write (0,'(a,i0,a,i0)') ' pigs_vpi: '//key//' = T: '//pre//'_window = ',window,' must not exceed Nb = ',Nb
+       stop 2
+    end if
+  end subroutine check_vectors_and_lags
+
+  ! what the files of walker w (global, 0-based) carry behind their name: .wNNNN, nothing in a run of one walker
+  function walker_suffix(w) result(suffix)
+    integer, intent(in) :: w
+    character(len=32)   :: suffix
+    suffix = ''
+    if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w
+  end function walker_suffix
+
+  ! the |q|-shell means of every lag of F(Nq,0:Ntau)
+  subroutine shell_means_lags(Nq,shell,nsh,mult,Ntau,F,Fsh)
+    integer, intent(in)  :: Nq,nsh,shell(Nq),mult(nsh),Ntau
+    real(8), intent(in)  :: F(Nq,0:Ntau)
+    real(8), intent(out) :: Fsh(nsh,0:Ntau)
+    integer :: l
+    do l=0,Ntau
+       call sqv_shell_means(Nq,shell,nsh,mult,F(:,l),Fsh(:,l))
+    end do
+  end subroutine shell_means_lags
+
+  ! W/Np of the profiles T averaged over the slices Nb-tau_window..Nb+tau_window
+  function virial_window(T) result(wwin)
+    real(8), intent(in) :: T(4,2*Nb+1)
+    real(8) :: wwin
+    wwin = sum(T(3,Nb+1-tau_window:Nb+1+tau_window))/real(2*tau_window+1,8)
+  end function virial_window
 
   ! first line of press_vpi*.out
   subroutine press_header(u)
