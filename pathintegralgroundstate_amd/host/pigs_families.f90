@@ -1,0 +1,1176 @@
+!-----------------------------------------------------------------------
+! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
+!
+! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
+! tau_profile, fq_self.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
+! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
+! end walks through:
+!     check          the key's values (refused before the backend is asked), the window default, *_bind()
+!     banner         its line of the run's banner
+!     setup          *_init, its grids, allocation, its claims on the block vector, the reset mask, press_vpi*.out
+!     queue          *_accumulate for the diagonal walkers of a step
+!     read           *_read at the end of a block
+!     block          walker w counted the block: normalize_*, series_add per file, count_add
+!     average        on the shard that writes the walker averages, after the all-reduce: count_reduced, series_average
+!     write_walker   the files of walker w
+!     write_average  the walker-averaged files
+! A family_set holds one slot per family, in the order of their claims on the block vector and of every device call;
+! only the slots of the keys that are on are allocated, and the set has one procedure per phase that walks them.
+!
+! A new family is a new extension of `family` here, a slot (and a line of set_create) in family_set, and its keys in
+! family_keys and in the program's namelist.
+!-----------------------------------------------------------------------
+module pigs_families
+
+  use iso_c_binding
+  use pigs_capi
+  use pigs_estimators
+  use pigs_block_stats
+
+  implicit none
+  private
+  public :: family_keys,family_run,family_info,family_set
+
+  ! the values of the estimator keys of &gpu (the namelist itself and its defaults belong to the program)
+  type family_keys
+     logical :: density_profile = .false.
+     logical :: fq_tau = .false.
+     integer :: fq_ntau = 0, fq_window = -1
+     logical :: sq_vector = .false.
+     integer :: sq_nmax = 8, sq_window = 0
+     logical :: gr_vector = .false.
+     integer :: gr_nbin = 32, gr_window = 0
+     logical :: fq_vector = .false.
+     integer :: fqv_nmax = 8, fqv_ntau = 0, fqv_window = -1
+     logical :: tau_profile = .false.
+     integer :: tau_window = 0
+     logical :: fq_self = .false.
+     integer :: fqs_nmax = 8, fqs_ntau = 0, fqs_window = -1
+  end type family_keys
+
+  ! what the families need to know of the run and of the shard
+  type family_run
+     integer :: Nb = 0
+     real(8) :: dt = 0.d0, density = 0.d0, rcut = 0.d0
+     logical :: averages = .false.                  ! this shard writes the walker-averaged files (several walkers, shard 1)
+     character(len=32), allocatable :: suffix(:)    ! [NW] what the files of the shard's walkers carry behind their name
+  end type family_run
+
+  ! what only the caller knows of a block and the pressure of tau_profile needs
+  type family_info
+     integer :: iblock = 0
+     real(8) :: kin    = 0.d0     ! block: the walker's Kin/Np of e_vpi.out; average: that of the walkers that counted the block
+     integer :: ndall  = 0        ! average: how many walkers of all shards these are
+  end type family_info
+
+  type, abstract :: family
+     type(family_run) :: run
+     type(est_params) :: ep
+     integer(c_int64_t), allocatable :: smp(:)      ! [NW] the block's samples per walker, from the device
+     integer(c_int32_t), allocatable :: reset(:)    ! [NW] 1: the device zeroes the walker's sums after the copy
+     type(block_count) :: cnt
+   contains
+     procedure(check_i),         deferred :: check
+     procedure(banner_i),        deferred :: banner
+     procedure(setup_i),         deferred :: setup
+     procedure(queue_i),         deferred :: queue
+     procedure(read_i),          deferred :: read
+     procedure(block_i),         deferred :: block
+     procedure(average_i),       deferred :: average
+     procedure(write_walker_i),  deferred :: write_walker
+     procedure(write_average_i), deferred :: write_average
+  end type family
+
+  abstract interface
+     subroutine check_i(f,keys,dim,Nb,trap)
+       import :: family,family_keys
+       class(family), intent(inout)     :: f
+       type(family_keys), intent(inout) :: keys
+       integer, intent(in) :: dim,Nb
+       logical, intent(in) :: trap
+     end subroutine check_i
+     subroutine banner_i(f,keys,trap)
+       import :: family,family_keys
+       class(family), intent(in)     :: f
+       type(family_keys), intent(in) :: keys
+       logical, intent(in) :: trap
+     end subroutine banner_i
+     subroutine setup_i(f,keys,run,ctx,ep,NW,nvec)
+       import :: family,family_keys,family_run,est_params,c_ptr
+       class(family), intent(inout)  :: f
+       type(family_keys), intent(in) :: keys
+       type(family_run), intent(in)  :: run
+       type(c_ptr), intent(in)       :: ctx
+       type(est_params), intent(in)  :: ep
+       integer, intent(in)    :: NW
+       integer, intent(inout) :: nvec
+     end subroutine setup_i
+     subroutine queue_i(f,ctx,nd,wl)
+       import :: family,c_ptr,c_int32_t
+       class(family), intent(inout) :: f
+       type(c_ptr), intent(in)      :: ctx
+       integer, intent(in)          :: nd
+       integer(c_int32_t), intent(in) :: wl(:)
+     end subroutine queue_i
+     subroutine read_i(f,ctx)
+       import :: family,c_ptr
+       class(family), intent(inout) :: f
+       type(c_ptr), intent(in)      :: ctx
+     end subroutine read_i
+     subroutine block_i(f,w,info,vec)
+       import :: family,family_info
+       class(family), intent(inout)  :: f
+       integer, intent(in)           :: w
+       type(family_info), intent(in) :: info
+       real(8), intent(inout)        :: vec(:)
+     end subroutine block_i
+     subroutine average_i(f,info,vec)
+       import :: family,family_info
+       class(family), intent(inout)  :: f
+       type(family_info), intent(in) :: info
+       real(8), intent(in)           :: vec(:)
+     end subroutine average_i
+     subroutine write_walker_i(f,suffix,w,nblocks)
+       import :: family
+       class(family), intent(inout) :: f
+       character(len=*), intent(in) :: suffix
+       integer, intent(in)          :: w,nblocks
+     end subroutine write_walker_i
+     subroutine write_average_i(f)
+       import :: family
+       class(family), intent(inout) :: f
+     end subroutine write_average_i
+  end interface
+
+  ! the stored vectors of a reciprocal grid and their |q| shells (sq_vector, fq_vector, fq_self)
+  type qgrid
+     integer :: nq = 0, nsh = 0
+     integer(c_int32_t), allocatable :: n(:,:)      ! [dim,nq]
+     integer, allocatable :: shell(:),mult(:)       ! [nq] the shell of a vector, [nsh] the vectors of a shell
+     real(8), allocatable :: q(:)                   ! [nsh] |q|
+  end type qgrid
+
+  ! density profiles: the block's counts from the device and the normalised block profiles
+  type, extends(family) :: density_family
+     integer :: npl = 0
+     integer(c_int64_t), allocatable :: pl(:,:),rad(:,:),pair(:,:)
+     real(8), allocatable :: bpl(:),brad(:),bpair(:)
+     type(block_series) :: sPl,sRad,sPair
+   contains
+     procedure :: check => density_check
+     procedure :: banner => density_banner
+     procedure :: setup => density_setup
+     procedure :: queue => density_queue
+     procedure :: read => density_read
+     procedure :: block => density_block
+     procedure :: average => density_average
+     procedure :: write_walker => density_write_walker
+     procedure :: write_average => density_write_average
+  end type density_family
+
+  ! F(q,tau) on the S(k) grid: the block's raw sums from the device and the normalised block values
+  type, extends(family) :: fqt_family
+     integer :: ntau = 0, window = 0
+     real(8), allocatable :: raw(:,:,:,:),b(:,:,:)  ! (third index: lag l + 1)
+     type(block_series) :: s
+   contains
+     procedure :: check => fqt_check
+     procedure :: banner => fqt_banner
+     procedure :: setup => fqt_setup
+     procedure :: queue => fqt_queue
+     procedure :: read => fqt_read_block
+     procedure :: block => fqt_block
+     procedure :: average => fqt_average
+     procedure :: write_walker => fqt_write_walker
+     procedure :: write_average => fqt_write_average
+  end type fqt_family
+
+  ! vector S(q): the block's raw sums from the device, the normalised block values per vector and per shell
+  type, extends(family) :: sqv_family
+     integer :: window = 0
+     type(qgrid) :: g
+     real(8), allocatable :: raw(:,:),b(:),sh(:)
+     type(block_series) :: sVec,sSh
+   contains
+     procedure :: check => sqv_check
+     procedure :: banner => sqv_banner
+     procedure :: setup => sqv_setup
+     procedure :: queue => sqv_queue
+     procedure :: read => sqv_read_block
+     procedure :: block => sqv_block
+     procedure :: average => sqv_average
+     procedure :: write_walker => sqv_write_walker
+     procedure :: write_average => sqv_write_average
+  end type sqv_family
+
+  ! vector g(r): the block's counts from the device, the normalised block values on the vector grid and radially
+  type, extends(family) :: grv_family
+     integer :: nbin = 0, window = 0, ngb = 0
+     integer(c_int64_t), allocatable :: vec(:,:),rad(:,:)
+     real(8), allocatable :: bvec(:),brad(:)
+     type(block_series) :: sVec,sRad
+   contains
+     procedure :: check => grv_check
+     procedure :: banner => grv_banner
+     procedure :: setup => grv_setup
+     procedure :: queue => grv_queue
+     procedure :: read => grv_read_block
+     procedure :: block => grv_block
+     procedure :: average => grv_average
+     procedure :: write_walker => grv_write_walker
+     procedure :: write_average => grv_write_average
+  end type grv_family
+
+  ! a function of (vector, lag) on the full reciprocal grid: fq_vector, and with self = T fq_self, which has the two
+  ! moments of the displacement per lag beside it.  The block's raw sums from the device, the normalised block values per
+  ! (vector, lag), per (shell, lag) and of the moments.  What tells the two keys apart is set by fqv_family / fqs_family.
+  type, extends(family) :: lagged_family
+     logical :: self = .false.
+     character(len=9)  :: key = ''
+     character(len=3)  :: pre = ''                  ! of the key's values (pre_nmax ..) and of the device's entry points
+     character(len=25) :: what = ''                 ! in the message of a backend without it
+     character(len=25) :: label = ''                ! of the banner line
+     character(len=48) :: files = ''                ! at its end
+     character(len=6)  :: fvec = '', fsh = ''       ! file names before _vpi
+     procedure(pigs_sqv_accumulate_t), pointer, nopass :: accumulate => null()
+     integer :: ntau = 0, window = 0
+     type(qgrid) :: g
+     real(8), allocatable :: raw(:,:,:),draw(:,:,:),b(:,:),sh(:,:),bm(:,:)     ! (second index: lag l + 1)
+     type(block_series) :: sVec,sSh,sMsd
+   contains
+     procedure :: check => lagged_check
+     procedure :: banner => lagged_banner
+     procedure :: setup => lagged_setup
+     procedure :: queue => lagged_queue
+     procedure :: read => lagged_read_block
+     procedure :: block => lagged_block
+     procedure :: average => lagged_average
+     procedure :: write_walker => lagged_write_walker
+     procedure :: write_average => lagged_write_average
+  end type lagged_family
+
+  ! imaginary-time profiles: the block's raw sums from the device (Vpair, Vext, W, D2 per slice), the normalised block
+  ! profiles; the units of press_vpi*.out (periodic runs)
+  type, extends(family) :: tau_family
+     integer :: window = 0
+     real(8), allocatable :: raw(:,:,:),b(:,:)      ! (second index: slice b + 1)
+     type(block_series) :: s
+     integer, allocatable :: up(:)
+     integer :: upav = -1
+   contains
+     procedure :: check => tau_check
+     procedure :: banner => tau_banner
+     procedure :: setup => tau_setup
+     procedure :: queue => tau_queue
+     procedure :: read => tau_read_block
+     procedure :: block => tau_block
+     procedure :: average => tau_average
+     procedure :: write_walker => tau_write_walker
+     procedure :: write_average => tau_write_average
+  end type tau_family
+
+  integer, parameter :: NFAM = 7
+  ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7]
+
+  type family_slot
+     class(family), allocatable :: f
+  end type family_slot
+
+  ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self
+  type family_set
+     type(family_slot) :: slot(NFAM)
+   contains
+     procedure :: create => set_create
+     procedure :: check => set_check
+     procedure :: banner => set_banner
+     procedure :: setup => set_setup
+     procedure :: queue => set_queue
+     procedure :: read => set_read
+     procedure :: block => set_block
+     procedure :: average => set_average
+     procedure :: write_walker => set_write_walker
+     procedure :: write_average => set_write_average
+  end type family_set
+
+contains
+
+  !---------------------------------------------------------------------
+  ! the set: one procedure per phase
+
+  ! the slots of the keys that are on
+  subroutine set_create(fs,keys)
+    class(family_set), intent(inout) :: fs
+    type(family_keys), intent(in)    :: keys
+    if (keys%density_profile) allocate (density_family :: fs%slot(1)%f)
+    if (keys%fq_tau)          allocate (fqt_family :: fs%slot(2)%f)
+    if (keys%sq_vector)       allocate (sqv_family :: fs%slot(3)%f)
+    if (keys%gr_vector)       allocate (grv_family :: fs%slot(4)%f)
+    if (keys%fq_vector)       allocate (fs%slot(5)%f,source=fqv_family())
+    if (keys%tau_profile)     allocate (tau_family :: fs%slot(6)%f)
+    if (keys%fq_self)         allocate (fs%slot(7)%f,source=fqs_family())
+  end subroutine set_create
+
+  ! refuses what the keys cannot have (exit status 2) and fills in the windows that were left out
+  subroutine set_check(fs,keys,dim,Nb,trap)
+    class(family_set), intent(inout) :: fs
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(CHECK_ORDER(i))%f)) call fs%slot(CHECK_ORDER(i))%f%check(keys,dim,Nb,trap)
+    end do
+  end subroutine set_check
+
+  subroutine set_banner(fs,keys,trap)
+    class(family_set), intent(in) :: fs
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(BANNER_ORDER(i))%f)) call fs%slot(BANNER_ORDER(i))%f%banner(keys,trap)
+    end do
+  end subroutine set_banner
+
+  ! nvec: the layout counter of the block vector, which every family moves past its claims
+  subroutine set_setup(fs,keys,run,ctx,ep,NW,nvec)
+    class(family_set), intent(inout) :: fs
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%setup(keys,run,ctx,ep,NW,nvec)
+    end do
+  end subroutine set_setup
+
+  ! the slices of the diagonal walkers wl(1:nd) (0-based) of a step into every family's accumulators: queued on the
+  ! context's stream behind the snapshot of the overlapped estimators (device-resident sampler) / the flushed commits
+  ! (host-driven), before the next step.  Diagonal-sector walkers only: an open worm cuts the worldline at Nb.
+  subroutine set_queue(fs,ctx,nd,wl)
+    class(family_set), intent(inout) :: fs
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%queue(ctx,nd,wl)
+    end do
+  end subroutine set_queue
+
+  subroutine set_read(fs,ctx)
+    class(family_set), intent(inout) :: fs
+    type(c_ptr), intent(in) :: ctx
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%read(ctx)
+    end do
+  end subroutine set_read
+
+  subroutine set_block(fs,w,info,vec)
+    class(family_set), intent(inout) :: fs
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%block(w,info,vec)
+    end do
+  end subroutine set_block
+
+  subroutine set_average(fs,info,vec)
+    class(family_set), intent(inout) :: fs
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%average(info,vec)
+    end do
+  end subroutine set_average
+
+  ! the files of walker w (local index), which counted nblocks blocks
+  subroutine set_write_walker(fs,suffix,w,nblocks)
+    class(family_set), intent(inout) :: fs
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%write_walker(suffix,w,nblocks)
+    end do
+  end subroutine set_write_walker
+
+  ! the walker-averaged files, from the reduced block vectors: every family over the blocks that one of its walkers counted
+  subroutine set_write_average(fs)
+    class(family_set), intent(inout) :: fs
+    integer :: i
+    do i=1,NFAM
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%write_average()
+    end do
+  end subroutine set_write_average
+
+  !---------------------------------------------------------------------
+  ! shared by the families
+
+  ! what every setup starts with; every walker's sums are zeroed after every read
+  subroutine family_begin(f,run,ep,NW)
+    class(family), intent(inout) :: f
+    type(family_run), intent(in) :: run
+    type(est_params), intent(in) :: ep
+    integer, intent(in) :: NW
+    f%run = run
+    f%ep  = ep
+    allocate (f%smp(NW),f%reset(NW))
+    f%reset = 1
+  end subroutine family_begin
+
+  subroutine needs_periodic(key,why)
+    character(len=*), intent(in) :: key,why
+    write (0,'(a)') ' pigs_vpi: '//key//' = T needs a periodic system (trap = F): '//why
+    stop 2
+  end subroutine needs_periodic
+
+  ! the entry points are resolved at run time, only for the keys that are on, so that the front end still links against
+  ! backends without them
+  subroutine no_backend(key,entries,what_runs)
+    character(len=*), intent(in) :: key,entries,what_runs
+    write (0,'(a)') ' pigs_vpi: '//key//' = T: this backend does not export '//entries//' ('//what_runs// &
+         & ' on libpigs_hip.so only)'
+    stop 2
+  end subroutine no_backend
+
+  ! a window of slices Nb-window..Nb+window on the path
+  subroutine check_window(key,pre,window,Nb)
+    character(len=*), intent(in) :: key,pre
+    integer, intent(in) :: window,Nb
+    if (window<0 .or. window>Nb) then
+       write (0,'(a,i0,a,i0)') ' pigs_vpi: '//key//' = T: '//pre//'_window = ',window,' must lie in 0 .. Nb = ',Nb
+       stop 2
+    end if
+  end subroutine check_window
+
+  ! pre_nmax within what the device stores
+  subroutine check_vectors(key,pre,nmax,dim)
+    character(len=*), intent(in) :: key,pre
+    integer, intent(in) :: nmax,dim
+    if (nmax<1 .or. nmax>merge(16,64,dim==3)) then
+       write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: '//key//' = T: '//pre//'_nmax = ',nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
+            & ' (dim = ',dim,')'
+       stop 2
+    end if
+  end subroutine check_vectors
+
+  ! the lags 0..pre_ntau within the window Nb-pre_window..Nb+pre_window (left out: the smallest window that holds them),
+  ! the window on the path
+  subroutine check_lags(key,pre,ntau,window,Nb)
+    character(len=*), intent(in) :: key,pre
+    integer, intent(in)    :: ntau,Nb
+    integer, intent(inout) :: window
+    if (window<0) window = (max(ntau,0)+1)/2                   ! ceiling(ntau/2)
+    if (ntau<0 .or. ntau>2*window) then
+       write (0,'(a,i0,a,i0,a)') ' pigs_vpi: '//key//' = T: '//pre//'_ntau = ',ntau,' must lie in 0 .. 2*'//pre//'_window = ',2*window, &
+            & ' (lags between the slices Nb-'//pre//'_window .. Nb+'//pre//'_window)'
+       stop 2
+    end if
+    if (window>Nb) then
+       write (0,'(a,i0,a,i0)') ' pigs_vpi: '//key//' = T: '//pre//'_window = ',window,' must not exceed Nb = ',Nb
+       stop 2
+    end if
+  end subroutine check_lags
+
+  ! the keys of fq_vector and fq_self (pre = fqv, fqs)
+  subroutine check_vectors_and_lags(key,pre,dim,Nb,nmax,ntau,window)
+    character(len=*), intent(in) :: key,pre
+    integer, intent(in)    :: dim,Nb,nmax,ntau
+    integer, intent(inout) :: window
+    call check_vectors(key,pre,nmax,dim)
+    call check_lags(key,pre,ntau,window,Nb)
+  end subroutine check_vectors_and_lags
+
+  ! the vectors the device stored at its *_init and their |q| shells; entries: the family's pigs_<entries>_count / _vectors
+  subroutine qgrid_fill(g,ctx,ep,count,vectors,entries)
+    type(qgrid), intent(out)     :: g
+    type(c_ptr), intent(in)      :: ctx
+    type(est_params), intent(in) :: ep
+    procedure(pigs_sqv_count_t), pointer, intent(in)   :: count
+    procedure(pigs_sqv_vectors_t), pointer, intent(in) :: vectors
+    character(len=*), intent(in) :: entries
+    integer(c_int64_t) :: nq
+    call pigs_check(count(ctx,nq),entries//'_count')
+    g%nq = int(nq)
+    allocate (g%n(ep%dim,g%nq),g%shell(g%nq))
+    call pigs_check(vectors(ctx,g%n),entries//'_vectors')
+    call sqv_shells(ep,g%nq,g%n,g%shell,g%nsh,g%q,g%mult)
+  end subroutine qgrid_fill
+
+  ! the |q|-shell means of every lag of F(Nq,0:Ntau)
+  subroutine shell_means_lags(Nq,shell,nsh,mult,Ntau,F,Fsh)
+    integer, intent(in)  :: Nq,nsh,shell(Nq),mult(nsh),Ntau
+    real(8), intent(in)  :: F(Nq,0:Ntau)
+    real(8), intent(out) :: Fsh(nsh,0:Ntau)
+    integer :: l
+    do l=0,Ntau
+       call sqv_shell_means(Nq,shell,nsh,mult,F(:,l),Fsh(:,l))
+    end do
+  end subroutine shell_means_lags
+
+  ! W/Np of the profiles T averaged over the slices Nb-window..Nb+window
+  function virial_window(Nb,window,T) result(wwin)
+    integer, intent(in) :: Nb,window
+    real(8), intent(in) :: T(4,2*Nb+1)
+    real(8) :: wwin
+    wwin = sum(T(3,Nb+1-window:Nb+1+window))/real(2*window+1,8)
+  end function virial_window
+
+  ! first line of press_vpi*.out
+  subroutine press_header(u,window)
+    integer, intent(in) :: u,window
+    write (u,'(a,i0,a,i0,a)') '# block, W/Np = <sum r dv/dr>/Np over the slices Nb-',window,'..Nb+',window, &
+         & ' (W stops at rcut: pairs beyond it are not counted, no tail correction), Kin/Np as e_vpi.out, '// &
+         & 'P = density/dim (2 Kin/Np - W/Np)'
+  end subroutine press_header
+
+  !---------------------------------------------------------------------
+  ! density_profile: the profiles of a trapped system (the reference's dead DensityProfile, vpi.f90:471), slice Nb --
+  ! dens_vpi.out, rho_vpi.out, pr_vpi.out; grid half-width rcut/2
+
+  subroutine density_check(f,keys,dim,Nb,trap)
+    class(density_family), intent(inout) :: f
+    type(family_keys), intent(inout)     :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (.not. trap) then
+       write (0,'(a)') ' pigs_vpi: density_profile = T needs a trapped system (trap = T): periodic runs write g(r) instead'
+       stop 2
+    end if
+    if (.not. density_bind()) call no_backend('density_profile','pigs_density_init / _accumulate / _read','the density profiles run')
+  end subroutine density_check
+
+  subroutine density_banner(f,keys,trap)
+    class(density_family), intent(in) :: f
+    type(family_keys), intent(in)     :: keys
+    logical, intent(in) :: trap
+    print '(a)',    '  > Density profiles    : on (slice Nb: dens_vpi.out, rho_vpi.out, pr_vpi.out)'
+  end subroutine density_banner
+
+  subroutine density_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(density_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%npl = ep%Nbin**min(ep%dim,2)
+    allocate (f%pl(f%npl,NW),f%rad(ep%Nbin,NW),f%pair(ep%Nbin,NW),f%bpl(f%npl),f%brad(ep%Nbin),f%bpair(ep%Nbin))
+    call series_create(f%sPl,f%npl,NW,nvec)
+    call series_create(f%sRad,ep%Nbin,NW,nvec)
+    call series_create(f%sPair,ep%Nbin,NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(dens_init(ctx,int(ep%Nbin,c_int32_t),run%rcut/2.d0),'pigs_density_init')
+  end subroutine density_setup
+
+  subroutine density_queue(f,ctx,nd,wl)
+    class(density_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(dens_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_density_accumulate')
+  end subroutine density_queue
+
+  subroutine density_read(f,ctx)
+    class(density_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(dens_read(ctx,f%pl,f%rad,f%pair,f%smp,f%reset),'pigs_density_read')
+  end subroutine density_read
+
+  subroutine density_block(f,w,info,vec)
+    class(density_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_density(f%ep%dim,f%ep%Np,f%ep%Nbin,f%run%rcut/2.d0,int(f%smp(w),8),f%pl(:,w),f%rad(:,w),f%pair(:,w), &
+         & f%bpl,f%brad,f%bpair)
+    call series_add(f%sPl,w,f%bpl,vec)
+    call series_add(f%sRad,w,f%brad,vec)
+    call series_add(f%sPair,w,f%bpair,vec)
+    call count_add(f%cnt,vec)
+  end subroutine density_block
+
+  subroutine density_average(f,info,vec)
+    class(density_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sPl,vec,nall)
+       call series_average(f%sRad,vec,nall)
+       call series_average(f%sPair,vec,nall)
+    end if
+  end subroutine density_average
+
+  subroutine density_write_walker(f,suffix,w,nblocks)
+    class(density_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_density('dens_vpi'//trim(suffix)//'.out',f%ep%dim,f%ep%Nbin,f%run%rcut/2.d0,nblocks,f%sPl%sum(:,w),f%sPl%sq(:,w))
+    call write_profile('rho_vpi'//trim(suffix)//'.out',f%ep%Nbin,f%run%rcut/2.d0,nblocks,f%sRad%sum(:,w),f%sRad%sq(:,w))
+    call write_profile('pr_vpi'//trim(suffix)//'.out',f%ep%Nbin,f%run%rcut/2.d0,nblocks,f%sPair%sum(:,w),f%sPair%sq(:,w))
+  end subroutine density_write_walker
+
+  subroutine density_write_average(f)
+    class(density_family), intent(inout) :: f
+    call write_density('dens_vpi.out',f%ep%dim,f%ep%Nbin,f%run%rcut/2.d0,f%cnt%nav,f%sPl%asum,f%sPl%asq)
+    call write_profile('rho_vpi.out',f%ep%Nbin,f%run%rcut/2.d0,f%cnt%nav,f%sRad%asum,f%sRad%asq)
+    call write_profile('pr_vpi.out',f%ep%Nbin,f%run%rcut/2.d0,f%cnt%nav,f%sPair%asum,f%sPair%asq)
+  end subroutine density_write_average
+
+  !---------------------------------------------------------------------
+  ! fq_tau: imaginary-time density correlations of a periodic system on the S(k) grid, lags 0..fq_ntau between the slices
+  ! Nb-fq_window..Nb+fq_window -- fqt_vpi.out
+
+  subroutine fqt_check(f,keys,dim,Nb,trap)
+    class(fqt_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('fq_tau','its q grid is that of the box')
+    call check_lags('fq_tau','fq',keys%fq_ntau,keys%fq_window,Nb)
+    if (.not. fqt_bind()) call no_backend('fq_tau','pigs_fqt_init / _accumulate / _read','F(q,tau) runs')
+  end subroutine fqt_check
+
+  subroutine fqt_banner(f,keys,trap)
+    class(fqt_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,i0,a,i0,a,i0,a)', '  > F(q,tau)            : on (lags 0..',keys%fq_ntau,', slices Nb-',keys%fq_window,'..Nb+',keys%fq_window, &
+         & ': fqt_vpi.out)'
+  end subroutine fqt_banner
+
+  subroutine fqt_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(fqt_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%ntau = keys%fq_ntau; f%window = keys%fq_window
+    allocate (f%raw(ep%dim,ep%Nk,f%ntau+1,NW),f%b(ep%dim,ep%Nk,f%ntau+1))
+    call series_create(f%s,ep%dim*ep%Nk*(f%ntau+1),NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(fqt_init(ctx,int(ep%Nk,c_int32_t),int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_fqt_init')
+  end subroutine fqt_setup
+
+  subroutine fqt_queue(f,ctx,nd,wl)
+    class(fqt_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(fqt_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqt_accumulate')
+  end subroutine fqt_queue
+
+  subroutine fqt_read_block(f,ctx)
+    class(fqt_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(fqt_read(ctx,f%raw,f%smp,f%reset),'pigs_fqt_read')
+  end subroutine fqt_read_block
+
+  subroutine fqt_block(f,w,info,vec)
+    class(fqt_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_fqt(f%ep,f%ntau,f%window,int(f%smp(w),8),f%raw(:,:,:,w),f%b)
+    call series_add(f%s,w,f%b,vec)
+    call count_add(f%cnt,vec)
+  end subroutine fqt_block
+
+  subroutine fqt_average(f,info,vec)
+    class(fqt_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) call series_average(f%s,vec,nall)
+  end subroutine fqt_average
+
+  subroutine fqt_write_walker(f,suffix,w,nblocks)
+    class(fqt_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_fqt('fqt_vpi'//trim(suffix)//'.out',f%ep,f%ntau,f%window,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+  end subroutine fqt_write_walker
+
+  subroutine fqt_write_average(f)
+    class(fqt_family), intent(inout) :: f
+    call write_fqt('fqt_vpi.out',f%ep,f%ntau,f%window,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
+  end subroutine fqt_write_average
+
+  !---------------------------------------------------------------------
+  ! sq_vector: the structure factor on the full reciprocal grid of a periodic system, averaged over the slices
+  ! Nb-sq_window..Nb+sq_window -- sqvec_vpi.out, one line per vector, and sq_vpi.out, one line per |q| shell
+
+  subroutine sqv_check(f,keys,dim,Nb,trap)
+    class(sqv_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('sq_vector','its q grid is that of the box')
+    call check_vectors('sq_vector','sq',keys%sq_nmax,dim)
+    call check_window('sq_vector','sq',keys%sq_window,Nb)
+    if (.not. sqv_bind()) call no_backend('sq_vector','pigs_sqv_init / _count / _vectors / _accumulate / _read', &
+         & 'the vector S(q) runs')
+  end subroutine sqv_check
+
+  subroutine sqv_banner(f,keys,trap)
+    class(sqv_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,i0,a,i0,a,i0,a)', '  > Vector S(q)         : on (|n_k| <= ',keys%sq_nmax,', slices Nb-',keys%sq_window,'..Nb+',keys%sq_window, &
+         & ': sqvec_vpi.out, sq_vpi.out)'
+  end subroutine sqv_banner
+
+  subroutine sqv_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(sqv_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%window = keys%sq_window
+    call pigs_check(sqv_init(ctx,int(keys%sq_nmax,c_int32_t),int(f%window,c_int32_t)),'pigs_sqv_init')
+    call qgrid_fill(f%g,ctx,ep,sqv_count,sqv_vectors,'pigs_sqv')
+    allocate (f%raw(f%g%nq,NW),f%b(f%g%nq),f%sh(f%g%nsh))
+    call series_create(f%sVec,f%g%nq,NW,nvec)
+    call series_create(f%sSh,f%g%nsh,NW)
+    call count_create(f%cnt,nvec)
+  end subroutine sqv_setup
+
+  subroutine sqv_queue(f,ctx,nd,wl)
+    class(sqv_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(sqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sqv_accumulate')
+  end subroutine sqv_queue
+
+  subroutine sqv_read_block(f,ctx)
+    class(sqv_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(sqv_read(ctx,f%raw,f%smp,f%reset),'pigs_sqv_read')
+  end subroutine sqv_read_block
+
+  subroutine sqv_block(f,w,info,vec)
+    class(sqv_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_sqv(f%ep%Np,f%window,int(f%smp(w),8),f%g%nq,f%raw(:,w),f%b)
+    call sqv_shell_means(f%g%nq,f%g%shell,f%g%nsh,f%g%mult,f%b,f%sh)
+    call series_add(f%sVec,w,f%b,vec)
+    call series_add(f%sSh,w,f%sh,vec)
+    call count_add(f%cnt,vec)
+  end subroutine sqv_block
+
+  ! (the shell means are those of the averaged vectors)
+  subroutine sqv_average(f,info,vec)
+    class(sqv_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sVec,vec,nall)
+       call sqv_shell_means(f%g%nq,f%g%shell,f%g%nsh,f%g%mult,f%sVec%mean,f%sh)
+       call series_add_mean(f%sSh,f%sh)
+    end if
+  end subroutine sqv_average
+
+  subroutine sqv_write_walker(f,suffix,w,nblocks)
+    class(sqv_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',f%ep,f%g%nq,f%g%n,nblocks,f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_sqshell('sq_vpi'//trim(suffix)//'.out',f%g%nsh,f%g%q,f%g%mult,nblocks,f%sSh%sum(:,w),f%sSh%sq(:,w))
+  end subroutine sqv_write_walker
+
+  subroutine sqv_write_average(f)
+    class(sqv_family), intent(inout) :: f
+    call write_sqvec('sqvec_vpi.out',f%ep,f%g%nq,f%g%n,f%cnt%nav,f%sVec%asum,f%sVec%asq)
+    call write_sqshell('sq_vpi.out',f%g%nsh,f%g%q,f%g%mult,f%cnt%nav,f%sSh%asum,f%sSh%asq)
+  end subroutine sqv_write_average
+
+  !---------------------------------------------------------------------
+  ! gr_vector: the pair distribution on the Cartesian grid of the minimum-image cell of a periodic system, gr_nbin bins
+  ! per axis, and radially on the run's own Nbin/rbin grid, over the slices Nb-gr_window..Nb+gr_window -- grvec_vpi.out,
+  ! one line per bin, and grw_vpi.out in gr_vpi.out's format
+
+  subroutine grv_check(f,keys,dim,Nb,trap)
+    class(grv_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('gr_vector','its grid is the minimum-image cell of the box')
+    if (keys%gr_nbin<1 .or. keys%gr_nbin>merge(128,merge(1024,4096,dim==2),dim==3)) then
+       write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: gr_vector = T: gr_nbin = ',keys%gr_nbin,' must lie in 1 .. ', &
+            & merge(128,merge(1024,4096,dim==2),dim==3),' (dim = ',dim,')'
+       stop 2
+    end if
+    call check_window('gr_vector','gr',keys%gr_window,Nb)
+    if (.not. grv_bind()) call no_backend('gr_vector','pigs_grv_init / _accumulate / _read','the vector g(r) runs')
+  end subroutine grv_check
+
+  subroutine grv_banner(f,keys,trap)
+    class(grv_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,i0,a,i0,a,i0,a)', '  > Vector g(r)         : on (',keys%gr_nbin,' bins per axis, slices Nb-',keys%gr_window,'..Nb+',keys%gr_window, &
+         & ': grvec_vpi.out, grw_vpi.out)'
+  end subroutine grv_banner
+
+  subroutine grv_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(grv_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%nbin = keys%gr_nbin; f%window = keys%gr_window
+    call pigs_check(grv_init(ctx,int(f%nbin,c_int32_t),int(ep%Nbin,c_int32_t),real(ep%rbin,c_double),int(f%window,c_int32_t)), &
+         & 'pigs_grv_init')
+    f%ngb = f%nbin**ep%dim
+    allocate (f%vec(f%ngb,NW),f%rad(ep%Nbin,NW),f%bvec(f%ngb),f%brad(ep%Nbin))
+    call series_create(f%sVec,f%ngb,NW,nvec)
+    call series_create(f%sRad,ep%Nbin,NW,nvec)
+    call count_create(f%cnt,nvec)
+  end subroutine grv_setup
+
+  subroutine grv_queue(f,ctx,nd,wl)
+    class(grv_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(grv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_grv_accumulate')
+  end subroutine grv_queue
+
+  subroutine grv_read_block(f,ctx)
+    class(grv_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(grv_read(ctx,f%vec,f%rad,f%smp,f%reset),'pigs_grv_read')
+  end subroutine grv_read_block
+
+  subroutine grv_block(f,w,info,vec)
+    class(grv_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_grv(f%ep,f%run%density,f%window,int(f%smp(w),8),f%nbin,f%ngb,f%vec(:,w),f%rad(:,w),f%bvec,f%brad)
+    call series_add(f%sVec,w,f%bvec,vec)
+    call series_add(f%sRad,w,f%brad,vec)
+    call count_add(f%cnt,vec)
+  end subroutine grv_block
+
+  subroutine grv_average(f,info,vec)
+    class(grv_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sVec,vec,nall)
+       call series_average(f%sRad,vec,nall)
+    end if
+  end subroutine grv_average
+
+  subroutine grv_write_walker(f,suffix,w,nblocks)
+    class(grv_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_grvec('grvec_vpi'//trim(suffix)//'.out',f%ep,f%nbin,f%ngb,nblocks,f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_radial('grw_vpi'//trim(suffix)//'.out',f%ep,nblocks,f%sRad%sum(:,w),f%sRad%sq(:,w))
+  end subroutine grv_write_walker
+
+  subroutine grv_write_average(f)
+    class(grv_family), intent(inout) :: f
+    call write_grvec('grvec_vpi.out',f%ep,f%nbin,f%ngb,f%cnt%nav,f%sVec%asum,f%sVec%asq)
+    call write_radial('grw_vpi.out',f%ep,f%cnt%nav,f%sRad%asum,f%sRad%asq)
+  end subroutine grv_write_average
+
+  !---------------------------------------------------------------------
+  ! fq_vector: F(q,tau_l) on the full reciprocal grid of a periodic system, the vectors of sq_vector with |n_k| <=
+  ! fqv_nmax, lags 0..fqv_ntau between the slices Nb-fqv_window..Nb+fqv_window -- fqvec_vpi.out, one line per (lag,
+  ! vector), and fqsh_vpi.out, one line per (lag, |q| shell).
+  ! fq_self: the self (incoherent) part F_s(q,tau_l) in the same form -- fqself_vpi.out, fqssh_vpi.out -- and the
+  ! imaginary-time mean-square displacement with its fourth moment -- msd_vpi.out, one line per lag.
+
+  function fqv_family() result(f)
+    type(lagged_family) :: f
+    f%self = .false.; f%key = 'fq_vector'; f%pre = 'fqv'; f%what = 'the vector F(q,tau)'
+    f%label = '  > Vector F(q,tau)   :'; f%files = 'fqvec_vpi.out, fqsh_vpi.out'; f%fvec = 'fqvec'; f%fsh = 'fqsh'
+  end function fqv_family
+
+  function fqs_family() result(f)
+    type(lagged_family) :: f
+    f%self = .true.; f%key = 'fq_self'; f%pre = 'fqs'; f%what = 'the self part of F(q,tau)'
+    f%label = '  > Self F_s(q,tau)     :'; f%files = 'fqself_vpi.out, fqssh_vpi.out, msd_vpi.out'; f%fvec = 'fqself'; f%fsh = 'fqssh'
+  end function fqs_family
+
+  subroutine lagged_check(f,keys,dim,Nb,trap)
+    class(lagged_family), intent(inout) :: f
+    type(family_keys), intent(inout)    :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    logical :: bound
+    if (trap) call needs_periodic(trim(f%key),'its q grid is that of the box')
+    if (f%self) then
+       call check_vectors_and_lags(trim(f%key),f%pre,dim,Nb,keys%fqs_nmax,keys%fqs_ntau,keys%fqs_window)
+       bound = fqs_bind()
+    else
+       call check_vectors_and_lags(trim(f%key),f%pre,dim,Nb,keys%fqv_nmax,keys%fqv_ntau,keys%fqv_window)
+       bound = fqv_bind()
+    end if
+    if (.not. bound) call no_backend(trim(f%key),'pigs_'//f%pre//'_init / _count / _vectors / _accumulate / _read', &
+         & trim(f%what)//' runs')
+  end subroutine lagged_check
+
+  ! the key's values: fqs_* with self, fqv_* without
+  subroutine lagged_keys(f,keys,nmax,ntau,window)
+    class(lagged_family), intent(in) :: f
+    type(family_keys), intent(in)    :: keys
+    integer, intent(out) :: nmax,ntau,window
+    if (f%self) then
+       nmax = keys%fqs_nmax; ntau = keys%fqs_ntau; window = keys%fqs_window
+    else
+       nmax = keys%fqv_nmax; ntau = keys%fqv_ntau; window = keys%fqv_window
+    end if
+  end subroutine lagged_keys
+
+  subroutine lagged_banner(f,keys,trap)
+    class(lagged_family), intent(in) :: f
+    type(family_keys), intent(in)    :: keys
+    logical, intent(in) :: trap
+    integer :: nmax,ntau,window
+    call lagged_keys(f,keys,nmax,ntau,window)
+    print '(a,i0,a,i0,a,i0,a,i0,a)', trim(f%label)//' on (|n_k| <= ',nmax,', lags 0..',ntau,', slices Nb-',window, &
+         & '..Nb+',window,': '//trim(f%files)//')'
+  end subroutine lagged_banner
+
+  subroutine lagged_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(lagged_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: nmax
+    call family_begin(f,run,ep,NW)
+    call lagged_keys(f,keys,nmax,f%ntau,f%window)
+    if (f%self) then
+       call pigs_check(fqs_init(ctx,int(nmax,c_int32_t),int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_fqs_init')
+       call qgrid_fill(f%g,ctx,ep,fqs_count,fqs_vectors,'pigs_fqs')
+       f%accumulate => fqs_accumulate
+       allocate (f%draw(2,f%ntau+1,NW),f%bm(2,f%ntau+1))
+    else
+       call pigs_check(fqv_init(ctx,int(nmax,c_int32_t),int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_fqv_init')
+       call qgrid_fill(f%g,ctx,ep,fqv_count,fqv_vectors,'pigs_fqv')
+       f%accumulate => fqv_accumulate
+    end if
+    allocate (f%raw(f%g%nq,f%ntau+1,NW),f%b(f%g%nq,f%ntau+1),f%sh(f%g%nsh,f%ntau+1))
+    call series_create(f%sVec,f%g%nq*(f%ntau+1),NW,nvec)
+    if (f%self) call series_create(f%sMsd,2*(f%ntau+1),NW,nvec)
+    call series_create(f%sSh,f%g%nsh*(f%ntau+1),NW)
+    call count_create(f%cnt,nvec)
+  end subroutine lagged_setup
+
+  subroutine lagged_queue(f,ctx,nd,wl)
+    class(lagged_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(f%accumulate(ctx,int(nd,c_int32_t),wl),'pigs_'//f%pre//'_accumulate')
+  end subroutine lagged_queue
+
+  subroutine lagged_read_block(f,ctx)
+    class(lagged_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    if (f%self) then
+       call pigs_check(fqs_read(ctx,f%raw,f%draw,f%smp,f%reset),'pigs_fqs_read')
+    else
+       call pigs_check(fqv_read(ctx,f%raw,f%smp,f%reset),'pigs_fqv_read')
+    end if
+  end subroutine lagged_read_block
+
+  subroutine lagged_block(f,w,info,vec)
+    class(lagged_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_fqv(f%ep%Np,f%ntau,f%window,int(f%smp(w),8),f%g%nq,f%raw(:,:,w),f%b)
+    if (f%self) call normalize_msd(f%ep%Np,f%ntau,f%window,int(f%smp(w),8),f%draw(:,:,w),f%bm)
+    call shell_means_lags(f%g%nq,f%g%shell,f%g%nsh,f%g%mult,f%ntau,f%b,f%sh)
+    call series_add(f%sVec,w,f%b,vec)
+    if (f%self) call series_add(f%sMsd,w,f%bm,vec)
+    call series_add(f%sSh,w,f%sh,vec)
+    call count_add(f%cnt,vec)
+  end subroutine lagged_block
+
+  ! (the shell means are those of the averaged vectors)
+  subroutine lagged_average(f,info,vec)
+    class(lagged_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sVec,vec,nall)
+       if (f%self) call series_average(f%sMsd,vec,nall)
+       call shell_means_lags(f%g%nq,f%g%shell,f%g%nsh,f%g%mult,f%ntau,f%sVec%mean,f%sh)
+       call series_add_mean(f%sSh,f%sh)
+    end if
+  end subroutine lagged_average
+
+  subroutine lagged_write_walker(f,suffix,w,nblocks)
+    class(lagged_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_fqvec(trim(f%fvec)//'_vpi'//trim(suffix)//'.out',f%ep,f%ntau,f%run%dt,f%g%nq,f%g%n,nblocks,f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_fqshell(trim(f%fsh)//'_vpi'//trim(suffix)//'.out',f%ntau,f%run%dt,f%g%nsh,f%g%q,f%g%mult,nblocks,f%sSh%sum(:,w),f%sSh%sq(:,w))
+    if (f%self) call write_msd('msd_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,nblocks,f%sMsd%sum(:,w),f%sMsd%sq(:,w))
+  end subroutine lagged_write_walker
+
+  subroutine lagged_write_average(f)
+    class(lagged_family), intent(inout) :: f
+    call write_fqvec(trim(f%fvec)//'_vpi.out',f%ep,f%ntau,f%run%dt,f%g%nq,f%g%n,f%cnt%nav,f%sVec%asum,f%sVec%asq)
+    call write_fqshell(trim(f%fsh)//'_vpi.out',f%ntau,f%run%dt,f%g%nsh,f%g%q,f%g%mult,f%cnt%nav,f%sSh%asum,f%sSh%asq)
+    if (f%self) call write_msd('msd_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%sMsd%asum,f%sMsd%asq)
+  end subroutine lagged_write_average
+
+  !---------------------------------------------------------------------
+  ! tau_profile: the imaginary-time profiles of every slice b = 0..2Nb of a periodic or trapped system -- tau_vpi.out.
+  ! Periodic runs also write press_vpi*.out, the virial pressure per block with W averaged over the slices
+  ! Nb-tau_window..Nb+tau_window: per walker, and the walker average where there are several.
+
+  subroutine tau_check(f,keys,dim,Nb,trap)
+    class(tau_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    call check_window('tau_profile','tau',keys%tau_window,Nb)
+    if (.not. tau_bind()) call no_backend('tau_profile','pigs_tau_init / _accumulate / _read','the imaginary-time profiles run')
+  end subroutine tau_check
+
+  subroutine tau_banner(f,keys,trap)
+    class(tau_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    if (trap) then
+       print '(a)', '  > V(tau) profiles     : on (slices 0..2Nb: tau_vpi.out)'
+    else
+       print '(a,i0,a,i0,a)', '  > V(tau) profiles     : on (slices 0..2Nb: tau_vpi.out; pressure over slices Nb-',keys%tau_window,'..Nb+',keys%tau_window, &
+            & ': press_vpi.out)'
+    end if
+  end subroutine tau_banner
+
+  subroutine tau_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(tau_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: w
+    call family_begin(f,run,ep,NW)
+    f%window = keys%tau_window
+    allocate (f%raw(4,2*run%Nb+1,NW),f%b(4,2*run%Nb+1))
+    call series_create(f%s,4*(2*run%Nb+1),NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(tau_init(ctx),'pigs_tau_init')
+    if (.not. ep%trap) then
+       allocate (f%up(NW))
+       do w=1,NW
+          open (newunit=f%up(w),file='press_vpi'//trim(run%suffix(w))//'.out')
+          call press_header(f%up(w),f%window)
+       end do
+       if (run%averages) then
+          open (newunit=f%upav,file='press_vpi.out')
+          call press_header(f%upav,f%window)
+       end if
+    end if
+  end subroutine tau_setup
+
+  subroutine tau_queue(f,ctx,nd,wl)
+    class(tau_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(tau_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_tau_accumulate')
+  end subroutine tau_queue
+
+  subroutine tau_read_block(f,ctx)
+    class(tau_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(tau_read(ctx,f%raw,f%smp,f%reset),'pigs_tau_read')
+  end subroutine tau_read_block
+
+  subroutine tau_block(f,w,info,vec)
+    class(tau_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    real(8) :: wwin
+    call normalize_tau(f%ep%dim,f%ep%Np,f%run%Nb,f%run%dt,int(f%smp(w),8),f%raw(:,:,w),f%b)
+    call series_add(f%s,w,f%b,vec)
+    call count_add(f%cnt,vec)
+    if (.not. f%ep%trap) then
+       ! W/Np over the window, the block's Kin/N of e_vpi.out, P = density/dim (2 Kin/N - W/N)
+       wwin = virial_window(f%run%Nb,f%window,f%b)
+       write (f%up(w),'(20g20.10e3)') real(info%iblock),wwin,info%kin,f%run%density/real(f%ep%dim,8)*(2.d0*(info%kin)-wwin)
+    end if
+  end subroutine tau_block
+
+  subroutine tau_average(f,info,vec)
+    class(tau_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    real(8) :: wwin
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%s,vec,nall)
+       if (.not. f%ep%trap .and. info%ndall>0) then
+          wwin = virial_window(f%run%Nb,f%window,f%s%mean)
+          write (f%upav,'(20g20.10e3)') real(info%iblock),wwin,info%kin,f%run%density/real(f%ep%dim,8)*(2.d0*(info%kin)-wwin)
+       end if
+    end if
+  end subroutine tau_average
+
+  subroutine tau_write_walker(f,suffix,w,nblocks)
+    class(tau_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_tau('tau_vpi'//trim(suffix)//'.out',f%run%Nb,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+    if (.not. f%ep%trap) close (f%up(w))
+  end subroutine tau_write_walker
+
+  subroutine tau_write_average(f)
+    class(tau_family), intent(inout) :: f
+    call write_tau('tau_vpi.out',f%run%Nb,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
+    if (.not. f%ep%trap) close (f%upav)
+  end subroutine tau_write_average
+
+end module pigs_families

@@ -60,6 +60,7 @@ program pigs_vpi
   use pigs_sampler
   use pigs_estimators
   use pigs_block_stats
+  use pigs_families
   use omp_lib
 
   implicit none
@@ -83,6 +84,8 @@ program pigs_vpi
   integer           :: fqs_nmax,fqs_ntau,fqs_window
   logical           :: tau_profile
   integer           :: tau_window
+  type(family_keys) :: fk                ! the estimator keys, as the families take them
+  type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
   logical           :: sampler_auto
   integer(c_int)    :: rc_probe
   type(pigs_sweep_params) :: probe_par
@@ -150,122 +153,13 @@ program pigs_vpi
      write (0,*) 'pigs_vpi: v_table = T is required (the reference Force() is a stub: system_mod.f90:186-209)'
      stop 2
   end if
-  if (density_profile) then
-     ! the profiles of a trapped system (the reference's dead DensityProfile, vpi.f90:471); the entry points are resolved
-     ! at run time, only here, so that the front end still links against backends without them
-     if (.not. trap) then
-        write (0,'(a)') ' pigs_vpi: density_profile = T needs a trapped system (trap = T): periodic runs write g(r) instead'
-        stop 2
-     end if
-     if (.not. density_bind()) then
-        write (0,'(a)') ' pigs_vpi: density_profile = T: this backend does not export pigs_density_init / _accumulate /'// &
-             & ' _read (the density profiles run on libpigs_hip.so only)'
-        stop 2
-     end if
-  end if
-  if (fq_tau) then
-     ! imaginary-time density correlations of a periodic system; the entry points are resolved at run time like the
-     ! density profiles' ones
-     if (trap) then
-        write (0,'(a)') ' pigs_vpi: fq_tau = T needs a periodic system (trap = F): its q grid is that of the box'
-        stop 2
-     end if
-     if (fq_window<0) fq_window = (max(fq_ntau,0)+1)/2          ! ceiling(fq_ntau/2)
-     if (fq_ntau<0 .or. fq_ntau>2*fq_window) then
-        write (0,'(a,i0,a,i0,a)') ' pigs_vpi: fq_tau = T: fq_ntau = ',fq_ntau,' must lie in 0 .. 2*fq_window = ',2*fq_window, &
-             & ' (lags between the slices Nb-fq_window .. Nb+fq_window)'
-        stop 2
-     end if
-     if (fq_window>Nb) then
-        write (0,'(a,i0,a,i0)') ' pigs_vpi: fq_tau = T: fq_window = ',fq_window,' must not exceed Nb = ',Nb
-        stop 2
-     end if
-     if (.not. fqt_bind()) then
-        write (0,'(a)') ' pigs_vpi: fq_tau = T: this backend does not export pigs_fqt_init / _accumulate / _read'// &
-             & ' (F(q,tau) runs on libpigs_hip.so only)'
-        stop 2
-     end if
-  end if
-  if (sq_vector) then
-     ! structure factor on the full reciprocal grid of a periodic system; entry points resolved at run time as above
-     if (trap) then
-        write (0,'(a)') ' pigs_vpi: sq_vector = T needs a periodic system (trap = F): its q grid is that of the box'
-        stop 2
-     end if
-     if (sq_nmax<1 .or. sq_nmax>merge(16,64,dim==3)) then
-        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: sq_vector = T: sq_nmax = ',sq_nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
-             & ' (dim = ',dim,')'
-        stop 2
-     end if
-     if (sq_window<0 .or. sq_window>Nb) then
-        write (0,'(a,i0,a,i0)') ' pigs_vpi: sq_vector = T: sq_window = ',sq_window,' must lie in 0 .. Nb = ',Nb
-        stop 2
-     end if
-     if (.not. sqv_bind()) then
-        write (0,'(a)') ' pigs_vpi: sq_vector = T: this backend does not export pigs_sqv_init / _count / _vectors /'// &
-             & ' _accumulate / _read (the vector S(q) runs on libpigs_hip.so only)'
-        stop 2
-     end if
-  end if
-  if (gr_vector) then
-     ! pair distribution on the vector grid of a periodic system; entry points resolved at run time as above
-     if (trap) then
-        write (0,'(a)') ' pigs_vpi: gr_vector = T needs a periodic system (trap = F): its grid is the minimum-image cell of the box'
-        stop 2
-     end if
-     if (gr_nbin<1 .or. gr_nbin>merge(128,merge(1024,4096,dim==2),dim==3)) then
-        write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: gr_vector = T: gr_nbin = ',gr_nbin,' must lie in 1 .. ', &
-             & merge(128,merge(1024,4096,dim==2),dim==3),' (dim = ',dim,')'
-        stop 2
-     end if
-     if (gr_window<0 .or. gr_window>Nb) then
-        write (0,'(a,i0,a,i0)') ' pigs_vpi: gr_vector = T: gr_window = ',gr_window,' must lie in 0 .. Nb = ',Nb
-        stop 2
-     end if
-     if (.not. grv_bind()) then
-        write (0,'(a)') ' pigs_vpi: gr_vector = T: this backend does not export pigs_grv_init / _accumulate / _read'// &
-             & ' (the vector g(r) runs on libpigs_hip.so only)'
-        stop 2
-     end if
-  end if
-  if (fq_vector) then
-     ! F(q,tau) on the full reciprocal grid of a periodic system; entry points resolved at run time as above
-     if (trap) then
-        write (0,'(a)') ' pigs_vpi: fq_vector = T needs a periodic system (trap = F): its q grid is that of the box'
-        stop 2
-     end if
-     call check_vectors_and_lags('fq_vector','fqv',fqv_nmax,fqv_ntau,fqv_window)
-     if (.not. fqv_bind()) then
-        write (0,'(a)') ' pigs_vpi: fq_vector = T: this backend does not export pigs_fqv_init / _count / _vectors /'// &
-             & ' _accumulate / _read (the vector F(q,tau) runs on libpigs_hip.so only)'
-        stop 2
-     end if
-  end if
-  if (fq_self) then
-     ! self part of F(q,tau) and imaginary-time displacement of a periodic system; entry points resolved at run time as above
-     if (trap) then
-        write (0,'(a)') ' pigs_vpi: fq_self = T needs a periodic system (trap = F): its q grid is that of the box'
-        stop 2
-     end if
-     call check_vectors_and_lags('fq_self','fqs',fqs_nmax,fqs_ntau,fqs_window)
-     if (.not. fqs_bind()) then
-        write (0,'(a)') ' pigs_vpi: fq_self = T: this backend does not export pigs_fqs_init / _count / _vectors /'// &
-             & ' _accumulate / _read (the self part of F(q,tau) runs on libpigs_hip.so only)'
-        stop 2
-     end if
-  end if
-  if (tau_profile) then
-     ! imaginary-time profiles of a periodic or trapped system; entry points resolved at run time as above
-     if (tau_window<0 .or. tau_window>Nb) then
-        write (0,'(a,i0,a,i0)') ' pigs_vpi: tau_profile = T: tau_window = ',tau_window,' must lie in 0 .. Nb = ',Nb
-        stop 2
-     end if
-     if (.not. tau_bind()) then
-        write (0,'(a)') ' pigs_vpi: tau_profile = T: this backend does not export pigs_tau_init / _accumulate / _read'// &
-             & ' (the imaginary-time profiles run on libpigs_hip.so only)'
-        stop 2
-     end if
-  end if
+  ! the estimator keys: refused values end the run before the backend is asked for the key's entry points
+  fk = family_keys(density_profile=density_profile,fq_tau=fq_tau,fq_ntau=fq_ntau,fq_window=fq_window, &
+       & sq_vector=sq_vector,sq_nmax=sq_nmax,sq_window=sq_window,gr_vector=gr_vector,gr_nbin=gr_nbin,gr_window=gr_window, &
+       & fq_vector=fq_vector,fqv_nmax=fqv_nmax,fqv_ntau=fqv_ntau,fqv_window=fqv_window,tau_profile=tau_profile, &
+       & tau_window=tau_window,fq_self=fq_self,fqs_nmax=fqs_nmax,fqs_ntau=fqs_ntau,fqs_window=fqs_window)
+  call keyed%create(fk)
+  call keyed%check(fk,dim,Nb,trap)
   NWtot = n_walkers
   G = max(1,min(n_gpus,NWtot))
   pi = acos(-1.d0)
@@ -367,42 +261,7 @@ program pigs_vpi
   else
      print '(a)',    '  > Sampler             : host-driven (lock-step batches through K1)'
   end if
-  if (density_profile) then
-     print '(a)',    '  > Density profiles    : on (slice Nb: dens_vpi.out, rho_vpi.out, pr_vpi.out)'
-  end if
-
-  if (fq_tau) then
-     print '(a,i0,a,i0,a,i0,a)', '  > F(q,tau)            : on (lags 0..',fq_ntau,', slices Nb-',fq_window,'..Nb+',fq_window,': fqt_vpi.out)'
-  end if
-
-  if (tau_profile) then
-     if (trap) then
-        print '(a)', '  > V(tau) profiles     : on (slices 0..2Nb: tau_vpi.out)'
-     else
-        print '(a,i0,a,i0,a)', '  > V(tau) profiles     : on (slices 0..2Nb: tau_vpi.out; pressure over slices Nb-',tau_window,'..Nb+',tau_window, &
-             & ': press_vpi.out)'
-     end if
-  end if
-
-  if (sq_vector) then
-     print '(a,i0,a,i0,a,i0,a)', '  > Vector S(q)         : on (|n_k| <= ',sq_nmax,', slices Nb-',sq_window,'..Nb+',sq_window, &
-          & ': sqvec_vpi.out, sq_vpi.out)'
-  end if
-
-  if (gr_vector) then
-     print '(a,i0,a,i0,a,i0,a)', '  > Vector g(r)         : on (',gr_nbin,' bins per axis, slices Nb-',gr_window,'..Nb+',gr_window, &
-          & ': grvec_vpi.out, grw_vpi.out)'
-  end if
-
-  if (fq_vector) then
-     print '(a,i0,a,i0,a,i0,a,i0,a)', '  > Vector F(q,tau)   : on (|n_k| <= ',fqv_nmax,', lags 0..',fqv_ntau,', slices Nb-',fqv_window, &
-          & '..Nb+',fqv_window,': fqvec_vpi.out, fqsh_vpi.out)'
-  end if
-
-  if (fq_self) then
-     print '(a,i0,a,i0,a,i0,a,i0,a)', '  > Self F_s(q,tau)     : on (|n_k| <= ',fqs_nmax,', lags 0..',fqs_ntau,', slices Nb-',fqs_window, &
-          & '..Nb+',fqs_window,': fqself_vpi.out, fqssh_vpi.out, msd_vpi.out)'
-  end if
+  call keyed%banner(fk,trap)
 
   !=====================================================================
 
@@ -436,6 +295,106 @@ contains
     p%reserved = 0
   end subroutine fill_sweep_params
 
+  ! initial configuration of the shard's walkers w0+1.. (reference vpi_mod.f90:149-259): resume from checkpoint files, a
+  ! lattice from config_ini.in, or uniform random positions; every bead of a particle starts at the same point; walker w
+  ! seeds its stream with seed+w-1
+  subroutine initial_configuration(s,w0)
+    type(sampler_t), intent(inout) :: s
+    integer, intent(in) :: w0
+    integer :: w,k,ip,ib,j,ucfg
+    logical :: lflag
+    character(len=32) :: suffix
+    do w=1,s%W
+       suffix = walker_suffix(w0+w-1)
+       if (resume) then
+          open (newunit=ucfg,file='checkpoint'//trim(suffix)//'.dat',status='old')
+          read (ucfg,*) lflag                      ! trap: the reference's init takes it from the file (vpi_mod.f90:166);
+          if (lflag .neqv. trap) then              ! here the tables and the box were already built from the namelist value,
+             write (0,*) 'pigs_vpi: checkpoint',trim(suffix),'.dat was written with trap = ',lflag, &   ! so a mismatch is an error
+                  & ' but the namelist says trap = ',trap
+             stop 2
+          end if
+          read (ucfg,*) lflag
+          s%isopen(w) = lflag
+          read (ucfg,*) s%iworm(w)
+          do ip=1,Np
+             do ib=0,2*Nb
+                read (ucfg,*) (s%Path(k,ip,ib,w),k=1,dim)
+             end do
+          end do
+          read (ucfg,*)
+          read (ucfg,*)
+          do j=1,2
+             read (ucfg,*) (s%xend(k,j,w),k=1,dim)
+          end do
+          close (ucfg)
+          call mt_load(s%rng(w),'rand_state'//trim(suffix))
+          cycle
+       end if
+       call mt_seed(s%rng(w),seed+w0+w-1)
+       if (crystal .and. .not. trap) then
+          open (newunit=ucfg,file='config_ini.in',status='old')
+          read (ucfg,*)
+          read (ucfg,*)
+          read (ucfg,*)
+          do ip=1,Np
+             read (ucfg,*) (s%Path(k,ip,0,w),k=1,dim)
+          end do
+          close (ucfg)
+       else
+          do ip=1,Np
+             do k=1,dim
+                if (trap) then
+                   s%Path(k,ip,0,w) = 2.d0*a_ho(k)*(mt_real(s%rng(w))-0.5d0)
+                else
+                   s%Path(k,ip,0,w) = Lbox(k)*(mt_real(s%rng(w))-0.5d0)
+                end if
+             end do
+          end do
+       end if
+       do ib=1,2*Nb
+          s%Path(:,:,ib,w) = s%Path(:,:,0,w)
+       end do
+       s%xend(:,1,w) = s%Path(:,Np,Nb,w)
+       s%xend(:,2,w) = s%xend(:,1,w)
+    end do
+  end subroutine initial_configuration
+
+  ! checkpoint of the shard's walkers (reference vpi.f90:541-545, vpi_mod.f90:263-309): text worldline, particle-major
+  subroutine write_checkpoints(s,w0)
+    type(sampler_t), intent(in) :: s
+    integer, intent(in) :: w0
+    integer :: w,k,ip,ib,j,ucfg
+    character(len=32) :: suffix
+    do w=1,s%W
+       suffix = walker_suffix(w0+w-1)
+       open (newunit=ucfg,file='checkpoint'//trim(suffix)//'.dat')
+       if (trap) then
+          write (ucfg,*) ".True."
+       else
+          write (ucfg,*) ".False."
+       end if
+       if (s%isopen(w)) then
+          write (ucfg,*) ".True."
+       else
+          write (ucfg,*) ".False."
+       end if
+       write (ucfg,*) s%iworm(w)
+       do ip=1,Np
+          do ib=0,2*Nb
+             write (ucfg,*) (s%Path(k,ip,ib,w),k=1,dim)
+          end do
+       end do
+       write (ucfg,*)
+       write (ucfg,*)
+       do j=1,2
+          write (ucfg,*) (s%xend(k,j,w),k=1,dim)
+       end do
+       close (ucfg)
+       call mt_save(s%rng(w),'rand_state'//trim(suffix))
+    end do
+  end subroutine write_checkpoints
+
   !---------------------------------------------------------------------
   ! one shard: the walkers lo(ish)..hi(ish) on context ctxs(ish), the reference's block / step structure
   ! (vpi.f90:244-588) for all of them in lock-step.  Everything below is private to the calling thread.
@@ -450,8 +409,7 @@ contains
   type(est_params)   :: ep
   type(c_ptr)        :: ctx
   type(perm_state), allocatable :: perm(:)
-
-  integer :: w,k,ip,ib,istep,iblock,istag,iobdm,j,nd,i,nvec,ndall,nall
+  integer :: w,k,ip,istep,iblock,istag,iobdm,j,nd,i,nvec,ndall,nall
   integer, allocatable :: ipv(:),iupd(:),partner(:),diag_list(:)
   logical, allocatable :: act(:),isopen0(:),swp(:)
   integer(c_int32_t), allocatable :: wl(:)
@@ -468,8 +426,7 @@ contains
   real(8), allocatable :: gr(:,:),Sk(:,:,:),nrho(:,:,:)
   real(8) :: t0,t1,mE(3),mT(3)
   integer, allocatable :: ue(:),ut(:),uh(:)
-  integer :: ueav,utav,ucfg
-  logical :: lflag
+  integer :: ueav,utav
   integer(8) :: c0,c1,crate
   type(pigs_sweep_params) :: swp_par
   real(8), allocatable, target :: gr_inc(:,:),sk_inc(:,:,:)
@@ -489,67 +446,11 @@ contains
   real(8) :: cnt_all(13)
   type(block_series) :: sGr,sSk,sNr
   type(block_count)  :: cGr,cNr
-  ! density profiles (density_profile = T): the block's counts from the device and the normalised block profiles
-  integer :: npl
-  integer(c_int64_t), allocatable :: dc_pl(:,:),dc_rad(:,:),dc_pair(:,:),dc_smp(:)
-  integer(c_int32_t), allocatable :: dc_reset(:)
-  real(8), allocatable :: dpl(:),drad(:),dpair(:)
-  type(block_series) :: sDpl,sDrad,sDpair
-  type(block_count)  :: cDens
-  ! F(q,tau) (fq_tau = T): the block's raw sums from the device and the normalised block values
-  integer(c_int64_t), allocatable :: fq_smp(:)
-  integer(c_int32_t), allocatable :: fq_reset(:)
-  real(8), allocatable :: fq_raw(:,:,:,:),fqb(:,:,:)
-  type(block_series) :: sFq
-  type(block_count)  :: cFq
-  ! vector S(q) (sq_vector = T): the stored vectors and their |q| shells, the block's raw sums from the device, the
-  ! normalised block values per vector and per shell
-  integer :: nsq,nsh
-  integer(c_int64_t) :: sq_count
-  integer(c_int32_t), allocatable :: sq_n(:,:),sq_reset(:)
-  integer(c_int64_t), allocatable :: sq_smp(:)
-  integer, allocatable :: sq_shell(:),sq_mult(:)
-  real(8), allocatable :: sq_raw(:,:),sqb(:),shb(:),sq_q(:)
-  type(block_series) :: sSq,sSh
-  type(block_count)  :: cSq
-  ! vector g(r) (gr_vector = T): the block's counts from the device, the normalised block values on the vector grid and
-  ! radially
-  integer :: ngb
-  integer(c_int64_t), allocatable :: gv_vec(:,:),gv_rad(:,:),gv_smp(:)
-  integer(c_int32_t), allocatable :: gv_reset(:)
-  real(8), allocatable :: gvb(:),gwb(:)
-  type(block_series) :: sGv,sGw
-  type(block_count)  :: cGv
-  ! vector F(q,tau) (fq_vector = T): the stored vectors and their |q| shells (those of the vector S(q)), the block's raw
-  ! sums from the device, the normalised block values per (vector, lag) and per (shell, lag)
-  integer :: nfx,nfsh
-  integer(c_int64_t) :: fx_count
-  integer(c_int32_t), allocatable :: fx_n(:,:),fx_reset(:)
-  integer(c_int64_t), allocatable :: fx_smp(:)
-  integer, allocatable :: fx_shell(:),fx_mult(:)
-  real(8), allocatable :: fx_raw(:,:,:),fxb(:,:),fxs(:,:),fx_q(:)
-  type(block_series) :: sFx,sFs
-  type(block_count)  :: cFx
-  ! imaginary-time profiles (tau_profile = T): the block's raw sums from the device (Vpair, Vext, W, D2 per slice), the
-  ! normalised block profiles; the units of press_vpi*.out
-  integer :: upav
-  integer(c_int64_t), allocatable :: tq_smp(:)
-  integer(c_int32_t), allocatable :: tq_reset(:)
-  integer, allocatable :: up(:)
-  real(8), allocatable :: tq_raw(:,:,:),tqb(:,:)
-  type(block_series) :: sTq
-  type(block_count)  :: cTq
-  real(8) :: wwin
-  ! self part of F(q,tau) and displacement (fq_self = T): the stored vectors and their |q| shells, the block's raw sums
-  ! from the device, the normalised block values per (vector, lag), per (shell, lag) and the two moments per lag
-  integer :: nzx,nzsh
-  integer(c_int64_t) :: zs_count
-  integer(c_int32_t), allocatable :: zs_n(:,:),zs_reset(:)
-  integer(c_int64_t), allocatable :: zs_smp(:)
-  integer, allocatable :: zs_shell(:),zs_mult(:)
-  real(8), allocatable :: zs_raw(:,:,:),zs_draw(:,:,:),zsb(:,:),zss(:,:),zsm(:,:),zs_q(:)
-  type(block_series) :: sZx,sZm,sZs
-  type(block_count)  :: cZs
+  ! the accumulator families of the estimator keys (pigs_families): the shard's own set, what it is told of the run, and
+  ! of every block
+  type(family_set)  :: fams
+  type(family_run)  :: frun
+  type(family_info) :: info
 
   call get_environment_variable('PIGS_VPI_TRACE',envbuf)
   trace = envbuf(1:1)=='1'
@@ -563,63 +464,7 @@ contains
   ep%rcut2 = rcut2; ep%rbin = rbin; ep%pi = pi; ep%CWorm = CWorm
   ep%Lbox = Lbox; ep%LboxHalf = 0.5d0*Lbox; ep%qbin = 2.d0*pi/Lbox
 
-  ! initial configuration (reference vpi_mod.f90:149-259): resume from checkpoint files, a lattice
-  ! from config_ini.in, or uniform random positions; every bead of a particle starts at the same
-  ! point; walker w seeds its stream with seed+w-1
-  do w=1,NW
-     suffix = walker_suffix(w0+w-1)
-     if (resume) then
-        open (newunit=ucfg,file='checkpoint'//trim(suffix)//'.dat',status='old')
-        read (ucfg,*) lflag                      ! trap: the reference's init takes it from the file (vpi_mod.f90:166);
-        if (lflag .neqv. trap) then              ! here the tables and the box were already built from the namelist value,
-           write (0,*) 'pigs_vpi: checkpoint',trim(suffix),'.dat was written with trap = ',lflag, &   ! so a mismatch is an error
-                & ' but the namelist says trap = ',trap
-           stop 2
-        end if
-        read (ucfg,*) lflag
-        s%isopen(w) = lflag
-        read (ucfg,*) s%iworm(w)
-        do ip=1,Np
-           do ib=0,2*Nb
-              read (ucfg,*) (s%Path(k,ip,ib,w),k=1,dim)
-           end do
-        end do
-        read (ucfg,*)
-        read (ucfg,*)
-        do j=1,2
-           read (ucfg,*) (s%xend(k,j,w),k=1,dim)
-        end do
-        close (ucfg)
-        call mt_load(s%rng(w),'rand_state'//trim(suffix))
-        cycle
-     end if
-     call mt_seed(s%rng(w),seed+w0+w-1)
-     if (crystal .and. .not. trap) then
-        open (newunit=ucfg,file='config_ini.in',status='old')
-        read (ucfg,*)
-        read (ucfg,*)
-        read (ucfg,*)
-        do ip=1,Np
-           read (ucfg,*) (s%Path(k,ip,0,w),k=1,dim)
-        end do
-        close (ucfg)
-     else
-        do ip=1,Np
-           do k=1,dim
-              if (trap) then
-                 s%Path(k,ip,0,w) = 2.d0*a_ho(k)*(mt_real(s%rng(w))-0.5d0)
-              else
-                 s%Path(k,ip,0,w) = Lbox(k)*(mt_real(s%rng(w))-0.5d0)
-              end if
-           end do
-        end do
-     end if
-     do ib=1,2*Nb
-        s%Path(:,:,ib,w) = s%Path(:,:,0,w)
-     end do
-     s%xend(:,1,w) = s%Path(:,Np,Nb,w)
-     s%xend(:,2,w) = s%xend(:,1,w)
-  end do
+  call initial_configuration(s,w0)
   call sampler_upload(s)
   if (device_sampler) then
      call fill_sweep_params(swp_par)
@@ -646,91 +491,14 @@ contains
   call count_create(cGr,nvec)
   call count_create(cNr,nvec)
 
-  if (density_profile) then
-     npl = Nbin**min(dim,2)
-     allocate (dc_pl(npl,NW),dc_rad(Nbin,NW),dc_pair(Nbin,NW),dc_smp(NW),dc_reset(NW),dpl(npl),drad(Nbin),dpair(Nbin))
-     call series_create(sDpl,npl,NW,nvec)
-     call series_create(sDrad,Nbin,NW,nvec)
-     call series_create(sDpair,Nbin,NW,nvec)
-     call count_create(cDens,nvec)
-     dc_reset = 1
-     call pigs_check(dens_init(ctx,int(Nbin,c_int32_t),rcut/2.d0),'pigs_density_init')
-  end if
-
-  if (fq_tau) then
-     ! (third index: lag l + 1)
-     allocate (fq_raw(dim,Nk,fq_ntau+1,NW),fq_smp(NW),fq_reset(NW),fqb(dim,Nk,fq_ntau+1))
-     call series_create(sFq,dim*Nk*(fq_ntau+1),NW,nvec)
-     call count_create(cFq,nvec)
-     fq_reset = 1
-     call pigs_check(fqt_init(ctx,int(Nk,c_int32_t),int(fq_ntau,c_int32_t),int(fq_window,c_int32_t)),'pigs_fqt_init')
-  end if
-
-  if (sq_vector) then
-     call pigs_check(sqv_init(ctx,int(sq_nmax,c_int32_t),int(sq_window,c_int32_t)),'pigs_sqv_init')
-     call pigs_check(sqv_count(ctx,sq_count),'pigs_sqv_count')
-     nsq = int(sq_count)
-     allocate (sq_n(dim,nsq),sq_shell(nsq),sq_raw(nsq,NW),sq_smp(NW),sq_reset(NW),sqb(nsq))
-     call pigs_check(sqv_vectors(ctx,sq_n),'pigs_sqv_vectors')
-     call sqv_shells(ep,nsq,sq_n,sq_shell,nsh,sq_q,sq_mult)
-     allocate (shb(nsh))
-     call series_create(sSq,nsq,NW,nvec)
-     call series_create(sSh,nsh,NW)
-     call count_create(cSq,nvec)
-     sq_reset = 1
-  end if
-
-  if (gr_vector) then
-     call pigs_check(grv_init(ctx,int(gr_nbin,c_int32_t),int(Nbin,c_int32_t),real(rbin,c_double),int(gr_window,c_int32_t)), &
-          & 'pigs_grv_init')
-     ngb = gr_nbin**dim
-     allocate (gv_vec(ngb,NW),gv_rad(Nbin,NW),gv_smp(NW),gv_reset(NW),gvb(ngb),gwb(Nbin))
-     call series_create(sGv,ngb,NW,nvec)
-     call series_create(sGw,Nbin,NW,nvec)
-     call count_create(cGv,nvec)
-     gv_reset = 1
-  end if
-
-  if (fq_vector) then
-     call pigs_check(fqv_init(ctx,int(fqv_nmax,c_int32_t),int(fqv_ntau,c_int32_t),int(fqv_window,c_int32_t)),'pigs_fqv_init')
-     call pigs_check(fqv_count(ctx,fx_count),'pigs_fqv_count')
-     nfx = int(fx_count)
-     ! (second index: lag l + 1)
-     allocate (fx_n(dim,nfx),fx_shell(nfx),fx_raw(nfx,fqv_ntau+1,NW),fx_smp(NW),fx_reset(NW),fxb(nfx,fqv_ntau+1))
-     call pigs_check(fqv_vectors(ctx,fx_n),'pigs_fqv_vectors')
-     call sqv_shells(ep,nfx,fx_n,fx_shell,nfsh,fx_q,fx_mult)
-     allocate (fxs(nfsh,fqv_ntau+1))
-     call series_create(sFx,nfx*(fqv_ntau+1),NW,nvec)
-     call series_create(sFs,nfsh*(fqv_ntau+1),NW)
-     call count_create(cFx,nvec)
-     fx_reset = 1
-  end if
-
-  if (tau_profile) then
-     ! (second index: slice b + 1)
-     allocate (tq_raw(4,2*Nb+1,NW),tq_smp(NW),tq_reset(NW),tqb(4,2*Nb+1))
-     call series_create(sTq,4*(2*Nb+1),NW,nvec)
-     call count_create(cTq,nvec)
-     tq_reset = 1
-     call pigs_check(tau_init(ctx),'pigs_tau_init')
-  end if
-
-  if (fq_self) then
-     call pigs_check(fqs_init(ctx,int(fqs_nmax,c_int32_t),int(fqs_ntau,c_int32_t),int(fqs_window,c_int32_t)),'pigs_fqs_init')
-     call pigs_check(fqs_count(ctx,zs_count),'pigs_fqs_count')
-     nzx = int(zs_count)
-     ! (second index: lag l + 1)
-     allocate (zs_n(dim,nzx),zs_shell(nzx),zs_raw(nzx,fqs_ntau+1,NW),zs_draw(2,fqs_ntau+1,NW),zs_smp(NW),zs_reset(NW))
-     allocate (zsb(nzx,fqs_ntau+1),zsm(2,fqs_ntau+1))
-     call pigs_check(fqs_vectors(ctx,zs_n),'pigs_fqs_vectors')
-     call sqv_shells(ep,nzx,zs_n,zs_shell,nzsh,zs_q,zs_mult)
-     allocate (zss(nzsh,fqs_ntau+1))
-     call series_create(sZx,nzx*(fqs_ntau+1),NW,nvec)
-     call series_create(sZm,2*(fqs_ntau+1),NW,nvec)
-     call series_create(sZs,nzsh*(fqs_ntau+1),NW)
-     call count_create(cZs,nvec)
-     zs_reset = 1
-  end if
+  frun%Nb = Nb; frun%dt = dt; frun%density = density; frun%rcut = rcut
+  frun%averages = NWtot>1 .and. ish==1
+  allocate (frun%suffix(NW))
+  do w=1,NW
+     frun%suffix(w) = walker_suffix(w0+w-1)
+  end do
+  call fams%create(fk)
+  call fams%setup(fk,frun,ctx,ep,NW,nvec)
   allocate (vec(nvec))
 
   allocate (perm(NW))
@@ -762,19 +530,6 @@ contains
   if (NWtot>1 .and. ish==1) then
      open (newunit=ueav,file='e_vpi.out')
      open (newunit=utav,file='et_vpi.out')
-  end if
-  if (tau_profile .and. .not. trap) then
-     ! the virial pressure per block (periodic runs): per walker, and the walker average where there are several
-     allocate (up(NW))
-     do w=1,NW
-        suffix = walker_suffix(w0+w-1)
-        open (newunit=up(w),file='press_vpi'//trim(suffix)//'.out')
-        call press_header(up(w))
-     end do
-     if (NWtot>1 .and. ish==1) then
-        open (newunit=upav,file='press_vpi.out')
-        call press_header(upav)
-     end if
   end if
 
   do iblock=1,Nblock
@@ -979,22 +734,8 @@ contains
                    & en9,c_null_ptr,c_null_ptr),'pigs_diagonal_estimators')
               est_have = .true.
            end if
-           ! the same walkers' slice Nb into the density accumulators: queued on the context's stream behind the
-           ! snapshot of _begin (device-resident sampler) / the flushed commits (host-driven), before the next step
-           if (density_profile) call pigs_check(dens_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_density_accumulate')
-           ! and, at the same place, their window slices into the F(q,tau) sums
-           if (fq_tau) call pigs_check(fqt_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqt_accumulate')
-           ! and into the sums of the vector S(q)
-           if (sq_vector) call pigs_check(sqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sqv_accumulate')
-           ! and into the counts of the vector g(r)
-           if (gr_vector) call pigs_check(grv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_grv_accumulate')
-           ! and into the sums of the vector F(q,tau)
-           if (fq_vector) call pigs_check(fqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqv_accumulate')
-           ! and every slice into the imaginary-time profiles
-           if (tau_profile) call pigs_check(tau_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_tau_accumulate')
-           ! and the window slices into the sums of the self part of F(q,tau) and of the displacement: diagonal-sector
-           ! walkers only (an open worm cuts the worldline at Nb)
-           if (fq_self) call pigs_check(fqs_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqs_accumulate')
+           ! the same walkers' slices into the accumulators of the estimator keys
+           call fams%queue(ctx,nd,wl)
         end if
 
      end do   ! istep
@@ -1019,13 +760,8 @@ contains
            nrho = dev_nrho
         end if
      end if
-     if (density_profile) call pigs_check(dens_read(ctx,dc_pl,dc_rad,dc_pair,dc_smp,dc_reset),'pigs_density_read')
-     if (fq_tau) call pigs_check(fqt_read(ctx,fq_raw,fq_smp,fq_reset),'pigs_fqt_read')
-     if (sq_vector) call pigs_check(sqv_read(ctx,sq_raw,sq_smp,sq_reset),'pigs_sqv_read')
-     if (gr_vector) call pigs_check(grv_read(ctx,gv_vec,gv_rad,gv_smp,gv_reset),'pigs_grv_read')
-     if (fq_vector) call pigs_check(fqv_read(ctx,fx_raw,fx_smp,fx_reset),'pigs_fqv_read')
-     if (tau_profile) call pigs_check(tau_read(ctx,tq_raw,tq_smp,tq_reset),'pigs_tau_read')
-     if (fq_self) call pigs_check(fqs_read(ctx,zs_raw,zs_draw,zs_smp,zs_reset),'pigs_fqs_read')
+     call fams%read(ctx)
+     info%iblock = iblock
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
      do w=1,NW
@@ -1042,57 +778,8 @@ contains
               call series_add(sSk,w,Sk(:,:,w),vec)
               call count_add(cGr,vec)
            end if
-           if (density_profile) then
-              call normalize_density(dim,Np,Nbin,rcut/2.d0,int(dc_smp(w),8),dc_pl(:,w),dc_rad(:,w),dc_pair(:,w),dpl,drad,dpair)
-              call series_add(sDpl,w,dpl,vec)
-              call series_add(sDrad,w,drad,vec)
-              call series_add(sDpair,w,dpair,vec)
-              call count_add(cDens,vec)
-           end if
-           if (fq_tau) then
-              call normalize_fqt(ep,fq_ntau,fq_window,int(fq_smp(w),8),fq_raw(:,:,:,w),fqb)
-              call series_add(sFq,w,fqb,vec)
-              call count_add(cFq,vec)
-           end if
-           if (sq_vector) then
-              call normalize_sqv(Np,sq_window,int(sq_smp(w),8),nsq,sq_raw(:,w),sqb)
-              call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sqb,shb)
-              call series_add(sSq,w,sqb,vec)
-              call series_add(sSh,w,shb,vec)
-              call count_add(cSq,vec)
-           end if
-           if (gr_vector) then
-              call normalize_grv(ep,density,gr_window,int(gv_smp(w),8),gr_nbin,ngb,gv_vec(:,w),gv_rad(:,w),gvb,gwb)
-              call series_add(sGv,w,gvb,vec)
-              call series_add(sGw,w,gwb,vec)
-              call count_add(cGv,vec)
-           end if
-           if (fq_vector) then
-              call normalize_fqv(Np,fqv_ntau,fqv_window,int(fx_smp(w),8),nfx,fx_raw(:,:,w),fxb)
-              call shell_means_lags(nfx,fx_shell,nfsh,fx_mult,fqv_ntau,fxb,fxs)
-              call series_add(sFx,w,fxb,vec)
-              call series_add(sFs,w,fxs,vec)
-              call count_add(cFx,vec)
-           end if
-           if (tau_profile) then
-              call normalize_tau(dim,Np,Nb,dt,int(tq_smp(w),8),tq_raw(:,:,w),tqb)
-              call series_add(sTq,w,tqb,vec)
-              call count_add(cTq,vec)
-              if (.not. trap) then
-                 ! W/Np over the window, the block's Kin/N of e_vpi.out, P = density/dim (2 Kin/N - W/N)
-                 wwin = virial_window(tqb)
-                 write (up(w),'(20g20.10e3)') real(iblock),wwin,BE(2,w)/Np,density/real(dim,8)*(2.d0*(BE(2,w)/Np)-wwin)
-              end if
-           end if
-           if (fq_self) then
-              call normalize_fqv(Np,fqs_ntau,fqs_window,int(zs_smp(w),8),nzx,zs_raw(:,:,w),zsb)
-              call normalize_msd(Np,fqs_ntau,fqs_window,int(zs_smp(w),8),zs_draw(:,:,w),zsm)
-              call shell_means_lags(nzx,zs_shell,nzsh,zs_mult,fqs_ntau,zsb,zss)
-              call series_add(sZx,w,zsb,vec)
-              call series_add(sZm,w,zsm,vec)
-              call series_add(sZs,w,zss,vec)
-              call count_add(cZs,vec)
-           end if
+           info%kin = BE(2,w)/Np
+           call fams%block(w,info,vec)
            write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
            write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
            write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
@@ -1129,60 +816,9 @@ contains
         end if
         nall = count_reduced(cNr,vec)
         if (nall>0) call series_average(sNr,vec,nall)
-        if (density_profile) then
-           nall = count_reduced(cDens,vec)
-           if (nall>0) then
-              call series_average(sDpl,vec,nall)
-              call series_average(sDrad,vec,nall)
-              call series_average(sDpair,vec,nall)
-           end if
-        end if
-        if (fq_tau) then
-           nall = count_reduced(cFq,vec)
-           if (nall>0) call series_average(sFq,vec,nall)
-        end if
-        if (sq_vector) then                  ! the shell means are those of the averaged vectors
-           nall = count_reduced(cSq,vec)
-           if (nall>0) then
-              call series_average(sSq,vec,nall)
-              call sqv_shell_means(nsq,sq_shell,nsh,sq_mult,sSq%mean,shb)
-              call series_add_mean(sSh,shb)
-           end if
-        end if
-        if (gr_vector) then
-           nall = count_reduced(cGv,vec)
-           if (nall>0) then
-              call series_average(sGv,vec,nall)
-              call series_average(sGw,vec,nall)
-           end if
-        end if
-        if (fq_vector) then
-           nall = count_reduced(cFx,vec)
-           if (nall>0) then
-              call series_average(sFx,vec,nall)
-              call shell_means_lags(nfx,fx_shell,nfsh,fx_mult,fqv_ntau,sFx%mean,fxs)
-              call series_add_mean(sFs,fxs)
-           end if
-        end if
-        if (tau_profile) then
-           nall = count_reduced(cTq,vec)
-           if (nall>0) then
-              call series_average(sTq,vec,nall)
-              if (.not. trap .and. ndall>0) then
-                 wwin = virial_window(sTq%mean)
-                 write (upav,'(20g20.10e3)') real(iblock),wwin,mE(2)/ndall,density/real(dim,8)*(2.d0*(mE(2)/ndall)-wwin)
-              end if
-           end if
-        end if
-        if (fq_self) then
-           nall = count_reduced(cZs,vec)
-           if (nall>0) then
-              call series_average(sZx,vec,nall)
-              call series_average(sZm,vec,nall)
-              call shell_means_lags(nzx,zs_shell,nzsh,zs_mult,fqs_ntau,sZx%mean,zss)
-              call series_add_mean(sZs,zss)
-           end if
-        end if
+        info%ndall = ndall
+        if (ndall>0) info%kin = mE(2)/ndall
+        call fams%average(info,vec)
      end if
      ! ---- checkpoint (reference vpi.f90:541-545, vpi_mod.f90:263-309): text worldline, particle-major
      if (checkpointing) then
@@ -1195,33 +831,7 @@ contains
            call pigs_check(pigs_sampler_get_worm(ctx,dev_open,dev_iworm,s%xend),'pigs_sampler_get_worm')
            s%isopen = dev_open/=0; s%iworm = dev_iworm
         end if
-        do w=1,NW
-           suffix = walker_suffix(w0+w-1)
-           open (newunit=ucfg,file='checkpoint'//trim(suffix)//'.dat')
-           if (trap) then
-              write (ucfg,*) ".True."
-           else
-              write (ucfg,*) ".False."
-           end if
-           if (s%isopen(w)) then
-              write (ucfg,*) ".True."
-           else
-              write (ucfg,*) ".False."
-           end if
-           write (ucfg,*) s%iworm(w)
-           do ip=1,Np
-              do ib=0,2*Nb
-                 write (ucfg,*) (s%Path(k,ip,ib,w),k=1,dim)
-              end do
-           end do
-           write (ucfg,*)
-           write (ucfg,*)
-           do j=1,2
-              write (ucfg,*) (s%xend(k,j,w),k=1,dim)
-           end do
-           close (ucfg)
-           call mt_save(s%rng(w),'rand_state'//trim(suffix))
-        end do
+        call write_checkpoints(s,w0)
      end if
      call system_clock(c1)
      t0 = 0.d0; t1 = dble(c1-c0)/dble(crate)
@@ -1266,33 +876,7 @@ contains
         call write_sk('sk_vpi'//trim(suffix)//'.out',ep,diag_bl(w),sSk%sum(:,w),sSk%sq(:,w))
         call write_nr('nr_vpi'//trim(suffix)//'.out',ep,obdm_bl(w),sNr%sum(:,w),sNr%sq(:,w))
      end if
-     if (density_profile) then
-        call write_density('dens_vpi'//trim(suffix)//'.out',dim,Nbin,rcut/2.d0,diag_bl(w),sDpl%sum(:,w),sDpl%sq(:,w))
-        call write_profile('rho_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),sDrad%sum(:,w),sDrad%sq(:,w))
-        call write_profile('pr_vpi'//trim(suffix)//'.out',Nbin,rcut/2.d0,diag_bl(w),sDpair%sum(:,w),sDpair%sq(:,w))
-     end if
-     if (fq_tau) call write_fqt('fqt_vpi'//trim(suffix)//'.out',ep,fq_ntau,fq_window,dt,diag_bl(w),sFq%sum(:,w),sFq%sq(:,w))
-     if (sq_vector) then
-        call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',ep,nsq,sq_n,diag_bl(w),sSq%sum(:,w),sSq%sq(:,w))
-        call write_sqshell('sq_vpi'//trim(suffix)//'.out',nsh,sq_q,sq_mult,diag_bl(w),sSh%sum(:,w),sSh%sq(:,w))
-     end if
-     if (gr_vector) then
-        call write_grvec('grvec_vpi'//trim(suffix)//'.out',ep,gr_nbin,ngb,diag_bl(w),sGv%sum(:,w),sGv%sq(:,w))
-        call write_radial('grw_vpi'//trim(suffix)//'.out',ep,diag_bl(w),sGw%sum(:,w),sGw%sq(:,w))
-     end if
-     if (fq_vector) then
-        call write_fqvec('fqvec_vpi'//trim(suffix)//'.out',ep,fqv_ntau,dt,nfx,fx_n,diag_bl(w),sFx%sum(:,w),sFx%sq(:,w))
-        call write_fqshell('fqsh_vpi'//trim(suffix)//'.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,diag_bl(w),sFs%sum(:,w),sFs%sq(:,w))
-     end if
-     if (fq_self) then
-        call write_fqvec('fqself_vpi'//trim(suffix)//'.out',ep,fqs_ntau,dt,nzx,zs_n,diag_bl(w),sZx%sum(:,w),sZx%sq(:,w))
-        call write_fqshell('fqssh_vpi'//trim(suffix)//'.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,diag_bl(w),sZs%sum(:,w),sZs%sq(:,w))
-        call write_msd('msd_vpi'//trim(suffix)//'.out',dim,fqs_ntau,dt,diag_bl(w),sZm%sum(:,w),sZm%sq(:,w))
-     end if
-     if (tau_profile) then
-        call write_tau('tau_vpi'//trim(suffix)//'.out',Nb,dt,diag_bl(w),sTq%sum(:,w),sTq%sq(:,w))
-        if (.not. trap) close (up(w))
-     end if
+     call fams%write_walker(suffix,w,diag_bl(w))
   end do
   if (NWtot>1 .and. ish==1) then
      close (ueav); close (utav)
@@ -1301,33 +885,7 @@ contains
         call write_sk('sk_vpi.out',ep,cGr%nav,sSk%asum,sSk%asq)
         call write_nr('nr_vpi.out',ep,cNr%nav,sNr%asum,sNr%asq)
      end if
-     if (density_profile) then
-        call write_density('dens_vpi.out',dim,Nbin,rcut/2.d0,cDens%nav,sDpl%asum,sDpl%asq)
-        call write_profile('rho_vpi.out',Nbin,rcut/2.d0,cDens%nav,sDrad%asum,sDrad%asq)
-        call write_profile('pr_vpi.out',Nbin,rcut/2.d0,cDens%nav,sDpair%asum,sDpair%asq)
-     end if
-     if (fq_tau) call write_fqt('fqt_vpi.out',ep,fq_ntau,fq_window,dt,cFq%nav,sFq%asum,sFq%asq)
-     if (sq_vector) then
-        call write_sqvec('sqvec_vpi.out',ep,nsq,sq_n,cSq%nav,sSq%asum,sSq%asq)
-        call write_sqshell('sq_vpi.out',nsh,sq_q,sq_mult,cSq%nav,sSh%asum,sSh%asq)
-     end if
-     if (gr_vector) then
-        call write_grvec('grvec_vpi.out',ep,gr_nbin,ngb,cGv%nav,sGv%asum,sGv%asq)
-        call write_radial('grw_vpi.out',ep,cGv%nav,sGw%asum,sGw%asq)
-     end if
-     if (fq_vector) then
-        call write_fqvec('fqvec_vpi.out',ep,fqv_ntau,dt,nfx,fx_n,cFx%nav,sFx%asum,sFx%asq)
-        call write_fqshell('fqsh_vpi.out',fqv_ntau,dt,nfsh,fx_q,fx_mult,cFx%nav,sFs%asum,sFs%asq)
-     end if
-     if (fq_self) then
-        call write_fqvec('fqself_vpi.out',ep,fqs_ntau,dt,nzx,zs_n,cZs%nav,sZx%asum,sZx%asq)
-        call write_fqshell('fqssh_vpi.out',fqs_ntau,dt,nzsh,zs_q,zs_mult,cZs%nav,sZs%asum,sZs%asq)
-        call write_msd('msd_vpi.out',dim,fqs_ntau,dt,cZs%nav,sZm%asum,sZm%asq)
-     end if
-     if (tau_profile) then
-        call write_tau('tau_vpi.out',Nb,dt,cTq%nav,sTq%asum,sTq%asq)
-        if (.not. trap) close (upav)
-     end if
+     call fams%write_average()
   end if
 
   do w=1,NW
@@ -1361,29 +919,6 @@ contains
   call sampler_free(s)
   end subroutine run_shard
 
-  ! the keys of fq_vector and fq_self (pre = fqv, fqs): pre_nmax within what the device stores, the lags 0..pre_ntau
-  ! within the window Nb-pre_window..Nb+pre_window (left out: the smallest window that holds them), the window on the path
-  subroutine check_vectors_and_lags(key,pre,nmax,ntau,window)
-    character(len=*), intent(in) :: key,pre
-    integer, intent(in)    :: nmax,ntau
-    integer, intent(inout) :: window
-    if (nmax<1 .or. nmax>merge(16,64,dim==3)) then
-       write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: '//key//' = T: '//pre//'_nmax = ',nmax,' must lie in 1 .. ',merge(16,64,dim==3), &
-            & ' (dim = ',dim,')'
-       stop 2
-    end if
-    if (window<0) window = (max(ntau,0)+1)/2                   ! ceiling(ntau/2)
-    if (ntau<0 .or. ntau>2*window) then
-       write (0,'(a,i0,a,i0,a)') ' pigs_vpi: '//key//' = T: '//pre//'_ntau = ',ntau,' must lie in 0 .. 2*'//pre//'_window = ',2*window, &
-            & ' (lags between the slices Nb-'//pre//'_window .. Nb+'//pre//'_window)'
-       stop 2
-    end if
-    if (window>Nb) then
-       write (0,'(a,i0,a,i0)') ' pigs_vpi: '//key//' = T: '//pre//'_window = ',window,' must not exceed Nb = ',Nb
-       stop 2
-    end if
-  end subroutine check_vectors_and_lags
-
   ! what the files of walker w (global, 0-based) carry behind their name: .wNNNN, nothing in a run of one walker
   function walker_suffix(w) result(suffix)
     integer, intent(in) :: w
@@ -1391,31 +926,5 @@ contains
     suffix = ''
     if (NWtot>1) write (suffix,'(a,i4.4)') '.w',w
   end function walker_suffix
-
-  ! the |q|-shell means of every lag of F(Nq,0:Ntau)
-  subroutine shell_means_lags(Nq,shell,nsh,mult,Ntau,F,Fsh)
-    integer, intent(in)  :: Nq,nsh,shell(Nq),mult(nsh),Ntau
-    real(8), intent(in)  :: F(Nq,0:Ntau)
-    real(8), intent(out) :: Fsh(nsh,0:Ntau)
-    integer :: l
-    do l=0,Ntau
-       call sqv_shell_means(Nq,shell,nsh,mult,F(:,l),Fsh(:,l))
-    end do
-  end subroutine shell_means_lags
-
-  ! W/Np of the profiles T averaged over the slices Nb-tau_window..Nb+tau_window
-  function virial_window(T) result(wwin)
-    real(8), intent(in) :: T(4,2*Nb+1)
-    real(8) :: wwin
-    wwin = sum(T(3,Nb+1-tau_window:Nb+1+tau_window))/real(2*tau_window+1,8)
-  end function virial_window
-
-  ! first line of press_vpi*.out
-  subroutine press_header(u)
-    integer, intent(in) :: u
-    write (u,'(a,i0,a,i0,a)') '# block, W/Np = <sum r dv/dr>/Np over the slices Nb-',tau_window,'..Nb+',tau_window, &
-         & ' (W stops at rcut: pairs beyond it are not counted, no tail correction), Kin/Np as e_vpi.out, '// &
-         & 'P = density/dim (2 Kin/Np - W/Np)'
-  end subroutine press_header
 
 end program pigs_vpi
