@@ -27,6 +27,7 @@
 
 #include "pigs_comm.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 
 using namespace pigs;
 
@@ -369,10 +370,7 @@ int pigs_ctx_create(const pigs_params *p, const double *VTable, const double *Lo
     HIPCHK(c->d_VTimg.alloc(img.size()));
     HIPCHK(hipMemcpy(c->d_VTimg.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(c->d_paths.p, 0, np * sizeof(double)));
-    {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, device_id) == hipSuccess && pr.multiProcessorCount > 0) c->n_cu = pr.multiProcessorCount;
-    }
+    c->n_cu = device_cus();                     // (the context's device is current since hipSetDevice above)
     g_live_ctx[device_id & 63].fetch_add(1);
     *out = c.release();
     return PIGS_OK;

@@ -27,6 +27,7 @@
 #include "pigs_k1_device.h"
 #include "pigs_kernels.h"
 #include "pigs_sampler_device.h"
+#include "pigs_launch.h"
 
 #include <cstdlib>
 
@@ -261,22 +262,18 @@ hipError_t launch_cm(const DevParams &P, const SweepParams &sp, int H, unsigned 
     const int nt = cm_threads(P, H);
     if (nt == 0) return hipErrorInvalidValue;
     const size_t lds = cm_layout(P, nt / kWave, H).total;
-    hipError_t e = hipSuccess;
     DevParams Pk = P;
     SweepParams spk = sp;
     void *args[] = {&Pk, &spk, &H, &seq0, &paths, &VTimg, &WF, &rng, &counters, &worm, &xch, &err};
-#define CALLC(D, NT)                                                                                               \
-    do {                                                                                                           \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cm<D, NT>),                                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                             \
-        if (e == hipSuccess)                                                                                       \
-            e = hipLaunchKernel(reinterpret_cast<const void *>(k_cm<D, NT>), dim3(P.nW * H), dim3(NT), args,       \
-                                (unsigned int)lds, st);                                                            \
-    } while (0)
-    if (nt == 1024) { if (P.dim == 1) CALLC(1, 1024); else if (P.dim == 2) CALLC(2, 1024); else CALLC(3, 1024); }
-    else            { if (P.dim == 1) CALLC(1, 512); else if (P.dim == 2) CALLC(2, 512); else CALLC(3, 512); }
-#undef CALLC
-    return e;
+    return with_flag(nt == 1024, [&](auto big) {
+        return with_dim(P.dim, [&](auto D) {
+            constexpr int NT = big() ? 1024 : 512;
+            const hipError_t e = grant_lds<k_cm<D(), NT>>(lds);
+            if (e != hipSuccess) return e;
+            return hipLaunchKernel(reinterpret_cast<const void *>(k_cm<D(), NT>), dim3(P.nW * H), dim3(NT), args,
+                                   (unsigned int)lds, st);
+        });
+    });
 }
 
 } // namespace pigs

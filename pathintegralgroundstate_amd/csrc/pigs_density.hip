@@ -18,6 +18,7 @@
 // Compile with -ffp-contract=off: the squared distances are summed left to right without fused multiply-adds.
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 
 namespace pigs {
 
@@ -130,14 +131,11 @@ hipError_t launch_density(const DevParams &P, const double *paths, int n, const 
     const int tile = min(P.Np, kDensTile);
     const int lds_hist = Nbin <= kDensLdsBins;
     const size_t lds = (size_t)P.dim * tile * sizeof(double) + (lds_hist ? (size_t)Nbin * sizeof(unsigned int) : 0);
-#define CALL(D)                                                                                                       \
-    hipLaunchKernelGGL((k_density<D>), dim3(n), dim3(kDensThreads), lds, st, P, paths, list, tile, Nbin, h, b, br,      \
-                       lds_hist, planar, radial, pair, samples)
-    if (P.dim == 1) CALL(1);
-    else if (P.dim == 2) CALL(2);
-    else CALL(3);
-#undef CALL
-    return hipGetLastError();
+    if (lds > kLdsNoGrant) return hipErrorInvalidValue;
+    return with_dim(P.dim, [&](auto D) {
+        return launch<k_density<D()>>(dim3(n), dim3(kDensThreads), lds, st, P, paths, list, tile, Nbin, h, b, br, lds_hist, planar,
+                                      radial, pair, samples);
+    });
 }
 
 } // namespace pigs

@@ -24,6 +24,7 @@
 #include "pigs_k1_device.h"
 #include "pigs_kernels.h"
 #include "pigs_sampler_device.h"
+#include "pigs_launch.h"
 
 namespace pigs {
 
@@ -584,19 +585,9 @@ hipError_t launch_diag(const DevParams &P, const SweepParams &sp, int threads, d
     const int nt = diag_form(P, sp, threads);
     if (nt == 0 || !diag_supported(P, sp)) return hipErrorInvalidValue;
     const size_t lds = diag_layout(P, sp, nt / kWave).total;
-    hipError_t e = hipSuccess;
-#define CALLD(D)                                                                                               \
-    do {                                                                                                       \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_diag<D, 512>),                                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        if (e == hipSuccess)                                                                                   \
-            hipLaunchKernelGGL((k_diag<D, 512>), dim3(P.nW), dim3(512), lds, st, P, sp, paths, VTimg, WF, rng, \
-                               counters, worm);                                                                \
-    } while (0)
-    if (P.dim == 1) CALLD(1); else if (P.dim == 2) CALLD(2); else CALLD(3);
-#undef CALLD
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
+    return with_dim(P.dim, [&](auto D) {
+        return launch<k_diag<D(), 512>>(dim3(P.nW), dim3(512), lds, st, P, sp, paths, VTimg, WF, rng, counters, worm);
+    });
 }
 
 } // namespace pigs

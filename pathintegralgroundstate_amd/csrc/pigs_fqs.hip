@@ -31,6 +31,7 @@
 
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 #include "pigs_sqv_device.h"
 
 namespace pigs {
@@ -199,25 +200,16 @@ hipError_t launch_fqs(const DevParams &P, const double *paths, int n, const Walk
     const long long ntiles = (q.Nq + s.width - 1) / s.width;
     if (ntiles * n > 0x7fffffffll || (long long)n * (Ntau + 1) > 0x7fffffffll) return hipErrorInvalidValue;
     const int bs = std::min(256, ((P.Np + 63) / 64) * 64);
-    // Order: what can refuse goes first -- the dynamic-LDS limit of k_fqs is raised before anything is queued -- then
-    // k_fqs_msd, and k_fqs, which adds 1 to samples, last: a call that fails before its last launch has not counted.
-#define CALL(D)                                                                                                          \
-    do {                                                                                                                 \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fqs<D>),                                     \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds);                      \
-        if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL((k_fqs_msd<D>), dim3((unsigned)(n * (Ntau + 1))), dim3(bs), 0, st, P, paths, list, window,    \
-                           Ntau, dsp);                                                                                   \
-        e = hipGetLastError();                                                                                           \
-        if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL((k_fqs<D>), dim3((unsigned)(ntiles * n)), dim3(kFqsThreads), s.lds, st, P, paths, list,       \
-                           window, Ntau, nmax, s.width, (int)ntiles, q.Nq, pi, acc, samples);                            \
-    } while (0)
-    if (P.dim == 1) CALL(1);
-    else if (P.dim == 2) CALL(2);
-    else CALL(3);
-#undef CALL
-    return hipGetLastError();
+    // Order: k_fqs_msd, then k_fqs, which adds 1 to samples, last: a call that fails before its last launch has not
+    // counted.  (k_fqs needs no grant that could refuse in between: fqs_shape keeps its LDS within kFqsLdsBudget, which is
+    // the limit every kernel has without one.)
+    static_assert(kFqsLdsBudget <= kLdsNoGrant, "k_fqs would need its grant before k_fqs_msd is queued");
+    return with_dim(P.dim, [&](auto D) {
+        const hipError_t e = launch<k_fqs_msd<D()>>(dim3((unsigned)(n * (Ntau + 1))), dim3(bs), 0, st, P, paths, list, window, Ntau, dsp);
+        if (e != hipSuccess) return e;
+        return launch<k_fqs<D()>>(dim3((unsigned)(ntiles * n)), dim3(kFqsThreads), s.lds, st, P, paths, list, window, Ntau, nmax,
+                                  s.width, (int)ntiles, q.Nq, pi, acc, samples);
+    });
 }
 
 } // namespace pigs

@@ -23,6 +23,7 @@
 
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 
 namespace pigs {
 
@@ -117,18 +118,14 @@ hipError_t launch_fqt(const DevParams &P, const double *paths, int n, const Walk
     const int ns = 2 * window + 1, T = Nk * P.dim;
     const int threads = 64 * std::min(4, (P.Np + 63) / 64);
     const double pi = acos(-1.0);
-#define CALL(D) hipLaunchKernelGGL((k_fqt_rho<D>), dim3(n * ns), dim3(threads), 0, st, P, paths, list, window, Nk, pi, rho)
-    if (P.dim == 1) CALL(1);
-    else if (P.dim == 2) CALL(2);
-    else CALL(3);
-#undef CALL
-    hipError_t e = hipGetLastError();
+    const hipError_t e = with_dim(P.dim, [&](auto D) {
+        return launch<k_fqt_rho<D()>>(dim3(n * ns), dim3(threads), 0, st, P, paths, list, window, Nk, pi, rho);
+    });
     if (e != hipSuccess) return e;
     const size_t total = (size_t)n * (Ntau + 1) * T;
     if ((total + 255) / 256 > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_fqt_correlate, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, list, n, window, Ntau, T,
-                       rho, acc, samples);
-    return hipGetLastError();
+    return launch<k_fqt_correlate>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, list, n, window, Ntau, T,
+                                   rho, acc, samples);
 }
 
 } // namespace pigs

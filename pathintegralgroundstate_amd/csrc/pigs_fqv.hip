@@ -24,6 +24,7 @@
 
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 #include "pigs_sqv_device.h"
 
 namespace pigs {
@@ -93,20 +94,15 @@ hipError_t launch_fqv(const DevParams &P, const double *paths, int n, const Walk
     const int width = fqv_width(ns);
     if (!width) return hipErrorInvalidValue;
     const double pi = acos(-1.0);
-#define CALL(D)                                                                                                         \
-    hipLaunchKernelGGL((k_fqv_rho<D>), dim3(n * ns), dim3(s.threads), s.lds, st, P, paths, list, window, nmax, s.tile, \
-                       s.nprefix, s.nchunk, s.Nq, pi, rho)
-    if (P.dim == 1) CALL(1);
-    else if (P.dim == 2) CALL(2);
-    else CALL(3);
-#undef CALL
-    hipError_t e = hipGetLastError();
+    const hipError_t e = with_dim(P.dim, [&](auto D) {
+        return launch<k_fqv_rho<D()>>(dim3(n * ns), dim3(s.threads), s.lds, st, P, paths, list, window, nmax, s.tile, s.nprefix,
+                                      s.nchunk, s.Nq, pi, rho);
+    });
     if (e != hipSuccess) return e;
     const long long ntiles = (s.Nq + width - 1) / width;
     if (ntiles * n > 0x7fffffffll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_fqv_correlate, dim3((unsigned)(ntiles * n)), dim3(kFqvThreads), (size_t)ns * width * sizeof(c2), st,
-                       list, ns, Ntau, width, (int)ntiles, s.Nq, rho, acc, samples);
-    return hipGetLastError();
+    return launch<k_fqv_correlate>(dim3((unsigned)(ntiles * n)), dim3(kFqvThreads), (size_t)ns * width * sizeof(c2), st,
+                                   list, ns, Ntau, width, (int)ntiles, s.Nq, rho, acc, samples);
 }
 
 } // namespace pigs

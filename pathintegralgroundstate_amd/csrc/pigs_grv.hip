@@ -24,10 +24,10 @@
 //   * u32 overflow: the host sets flush_every so that flush_every * Np (Np - 1) / 2 <= 2^32 - 1; a bin can gain at most
 //     one count per pair, so no LDS counter can wrap between two flushes.  Flushes skip empty bins.
 #include <algorithm>
-#include <atomic>
 
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 
 namespace pigs {
 
@@ -154,24 +154,6 @@ __global__ __launch_bounds__(kGrvThreadsMax) void k_grv(
     if (chunk == 0 && threadIdx.x == 0) atomicAdd(&samples[w], 1ull);
 }
 
-// raise a kernel's dynamic-LDS limit once per (kernel, device), and again only for a larger request
-template <auto Kern>
-hipError_t grv_set_lds(size_t bytes)
-{
-    if (bytes <= 64 * 1024) return hipSuccess;
-    constexpr int kMaxDev = 64;
-    static std::atomic<size_t> granted[kMaxDev];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = -1;
-    if (dev >= 0 && bytes <= granted[dev].load(std::memory_order_acquire)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess && dev >= 0) {
-        size_t g = granted[dev].load(std::memory_order_relaxed);
-        while (g < bytes && !granted[dev].compare_exchange_weak(g, bytes, std::memory_order_release)) {}
-    }
-    return e;
-}
-
 } // namespace
 
 GrvShape grv_shape(int dim, int Np, int Nbin, int Nr, int window, int form, int n_list, int n_cu)
@@ -220,27 +202,14 @@ hipError_t launch_grv(const DevParams &P, const double *paths, int n, const Walk
     A.nvec = 1;
     for (int k = 0; k < P.dim; ++k) { A.nvec *= (unsigned int)Nbin; A.b[k] = P.Lbox[k] / (double)Nbin; }
     A.rbin = rbin;
-    hipError_t e = hipSuccess;
-#define CALL(D, V, R)                                                                                                    \
-    do {                                                                                                                 \
-        e = grv_set_lds<k_grv<D, V, R>>(s.lds);                                                                          \
-        if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL((k_grv<D, V, R>), dim3(n * s.nchunk), dim3(s.threads), s.lds, st, P, paths, list, A, vec,     \
-                           radial, samples);                                                                             \
-    } while (0)
-#define CALL_D(V, R)                                                                                                     \
-    do {                                                                                                                 \
-        if (P.dim == 1) CALL(1, V, R);                                                                                   \
-        else if (P.dim == 2) CALL(2, V, R);                                                                              \
-        else CALL(3, V, R);                                                                                              \
-    } while (0)
-    if (s.vec_lds && s.rad_lds) CALL_D(true, true);
-    else if (s.vec_lds) CALL_D(true, false);
-    else if (s.rad_lds) CALL_D(false, true);
-    else CALL_D(false, false);
-#undef CALL_D
-#undef CALL
-    return hipGetLastError();
+    return with_flag(s.vec_lds, [&](auto V) {
+        return with_flag(s.rad_lds, [&](auto R) {
+            return with_dim(P.dim, [&](auto D) {
+                return launch<k_grv<D(), V(), R()>>(dim3(n * s.nchunk), dim3(s.threads), s.lds, st, P, paths, list, A, vec, radial,
+                                                    samples);
+            });
+        });
+    });
 }
 
 } // namespace pigs

@@ -22,11 +22,11 @@
 //            depend on how many other items share its launch
 //   14 reference order (validation): exact-term arithmetic, per-partner terms parked in LDS and added by one lane
 //            per accumulator in the reference's jp order -- every bit of Delta S equals the reference's
-#include <atomic>
 
 #include "pigs_device.h"
 #include "pigs_k1_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 
 namespace pigs {
 
@@ -711,57 +711,10 @@ __global__ void k_selftest_fastmath(DevParams P, unsigned long long seed, int it
 // =====================================================================================
 // launcher
 // =====================================================================================
-#define PIGS_DISPATCH(P, CALL)                                              \
-    do {                                                                    \
-        if ((P).trap) {                                                     \
-            if ((P).dim == 1) { CALL(1, true); }                            \
-            else if ((P).dim == 2) { CALL(2, true); }                       \
-            else { CALL(3, true); }                                         \
-        } else {                                                            \
-            if ((P).dim == 1) { CALL(1, false); }                           \
-            else if ((P).dim == 2) { CALL(2, false); }                      \
-            else { CALL(3, false); }                                        \
-        }                                                                   \
-    } while (0)
-
 static int k1_grid(int n_items, int waves_per_block, int cap_blocks)
 {
     int blocks = (n_items + waves_per_block - 1) / waves_per_block;
     return blocks < cap_blocks ? (blocks > 0 ? blocks : 1) : cap_blocks;
-}
-
-// persistent grid of the pipelined kernel: one 1024-thread workgroup per CU
-static int k1_pipe_blocks()
-{
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-            n = pr.multiProcessorCount;
-        else
-            n = 256;
-    }
-    return n;
-}
-
-// raise a kernel's dynamic-LDS limit once per (kernel, device) -- and again only for a larger request -- instead of on
-// every launch: hipFuncSetAttribute is a host call on the enqueue path of every step
-template <auto Kern>
-static hipError_t set_lds(size_t bytes)
-{
-    if (bytes <= 64 * 1024) return hipSuccess;
-    constexpr int kMaxDev = 64;
-    static std::atomic<size_t> granted[kMaxDev];                // one table per kernel instantiation, zero-initialised
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = -1;
-    if (dev >= 0 && bytes <= granted[dev].load(std::memory_order_acquire)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess && dev >= 0) {
-        size_t g = granted[dev].load(std::memory_order_relaxed);
-        while (g < bytes && !granted[dev].compare_exchange_weak(g, bytes, std::memory_order_release)) {}
-    }
-    return e;
 }
 
 hipError_t launch_delta_action(const DevParams &P, int variant, const double *paths, const double *VT,
@@ -778,89 +731,67 @@ hipError_t launch_delta_action(const DevParams &P, int variant, const double *pa
         // 16 waves per CU several times over, the same per-item code on a plain grid below that (identical bits);
         // periodic systems beyond 256 particles the short arithmetic on the global table.
         if (P.trap) variant = K1_V2;
-        else if (can_pipe) variant = (n_items >= 16 * k1_pipe_blocks() && !parts) ? K1_PIPE2 : K1_GRID;
+        else if (can_pipe) variant = (n_items >= 16 * device_cus() && !parts) ? K1_PIPE2 : K1_GRID;
         else variant = K1_FAST;
     }
     if ((variant == K1_PIPE2 || variant == K1_GRID) && !can_pipe) variant = P.trap ? K1_V2 : K1_FAST;
     if (variant == K1_PIPE2 && parts) variant = K1_GRID;        // pipe2 has no registers to spare for the diagnostic output: same arithmetic on the grid
     if (variant == K1_FAST_PREFETCH && P.Np > 256) variant = K1_FAST;
     if ((variant == K1_FAST || variant == K1_FAST_PREFETCH) && P.trap) variant = K1_V2;   // no cutoff in the trap: exact path
-    hipError_t e = hipSuccess;
     switch (variant) {
-    case K1_V1: {
-#define CALL(D, T)                                                                              \
-    hipLaunchKernelGGL((k_delta_action_v1<D, T>), dim3(k1_grid(n_items, 4, 2048)), dim3(256), 0, st, P, \
-                       paths, VT, WF, n_items, walker, ip, ib, xnew, xold, out, parts)
-        PIGS_DISPATCH(P, CALL);
-#undef CALL
-        break;
-    }
+    case K1_V1:
+        return with_flag(P.trap, [&](auto T) {
+            return with_dim(P.dim, [&](auto D) {
+                return launch<k_delta_action_v1<D(), T()>>(dim3(k1_grid(n_items, 4, 2048)), dim3(256), 0, st, P, paths, VT, WF,
+                                                           n_items, walker, ip, ib, xnew, xold, out, parts);
+            });
+        });
     case K1_V2:
     case K1_FAST:
     case K1_FAST_PREFETCH: {
         const size_t lds = 4 * kWaveLds;
-        const int grid = k1_grid(n_items, 4, 1 << 22);
-#define CALL(D, T)                                                                                             \
-    do {                                                                                                       \
-        if (variant == K1_V2)                                                                                  \
-            hipLaunchKernelGGL((k_delta_action_v2<D, T, 256, false, false>), dim3(grid), dim3(256), lds, st, P, \
-                               paths, VT, WF, n_items, walker, ip, ib, xnew, xold, out, parts);                \
-        else if (variant == K1_FAST)                                                                           \
-            hipLaunchKernelGGL((k_delta_action_v2<D, T, 256, false, true>), dim3(grid), dim3(256), lds, st, P, \
-                               paths, VT, WF, n_items, walker, ip, ib, xnew, xold, out, parts);                \
-        else                                                                                                   \
-            hipLaunchKernelGGL((k_delta_action_v2<D, T, 256, true, true>), dim3(grid), dim3(256), lds, st, P,  \
-                               paths, VT, WF, n_items, walker, ip, ib, xnew, xold, out, parts);                \
-    } while (0)
-        PIGS_DISPATCH(P, CALL);
-#undef CALL
-        break;
+        const dim3 grid(k1_grid(n_items, 4, 1 << 22));
+        return with_flag(P.trap, [&](auto T) {
+            return with_dim(P.dim, [&](auto D) {
+                if (variant == K1_V2)
+                    return launch<k_delta_action_v2<D(), T(), 256, false, false>>(grid, dim3(256), lds, st, P, paths, VT, WF, n_items,
+                                                                                 walker, ip, ib, xnew, xold, out, parts);
+                if (variant == K1_FAST)
+                    return launch<k_delta_action_v2<D(), T(), 256, false, true>>(grid, dim3(256), lds, st, P, paths, VT, WF, n_items,
+                                                                                walker, ip, ib, xnew, xold, out, parts);
+                return launch<k_delta_action_v2<D(), T(), 256, true, true>>(grid, dim3(256), lds, st, P, paths, VT, WF, n_items,
+                                                                           walker, ip, ib, xnew, xold, out, parts);
+            });
+        });
     }
-    case K1_GRID: {
-        const size_t lds = 4 * kWaveLds;
-        const int grid = k1_grid(n_items, 4, 1 << 22);
-#define CALLP(D)                                                                                        \
-    hipLaunchKernelGGL((k_delta_action_grid<D>), dim3(grid), dim3(256), lds, st, P, paths, VTimg, WF,   \
-                       n_items, walker, ip, ib, xnew, xold, out, parts)
-        if (P.dim == 1) CALLP(1); else if (P.dim == 2) CALLP(2); else CALLP(3);
-#undef CALLP
-        break;
-    }
+    case K1_GRID:
+        return with_dim(P.dim, [&](auto D) {
+            return launch<k_delta_action_grid<D()>>(dim3(k1_grid(n_items, 4, 1 << 22)), dim3(256), 4 * kWaveLds, st, P, paths,
+                                                    VTimg, WF, n_items, walker, ip, ib, xnew, xold, out, parts);
+        });
     case K1_PIPE2: {
         const size_t lds = pipe_bytes + 16 * kWaveLds;
         int blocks = (n_items + 15) / 16;
-        if (blocks > k1_pipe_blocks()) blocks = k1_pipe_blocks();
-#define CALLP(D)                                                                                        \
-    do {                                                                                                \
-        e = set_lds<k_delta_action_pipe2<D>>(lds);                                                      \
-        if (e == hipSuccess)                                                                            \
-            hipLaunchKernelGGL((k_delta_action_pipe2<D>), dim3(blocks), dim3(1024), lds, st, P, paths,  \
-                               VT, WF, n_items, walker, ip, ib, xnew, xold, out, parts);                \
-    } while (0)
-        if (P.dim == 1) CALLP(1); else if (P.dim == 2) CALLP(2); else CALLP(3);
-#undef CALLP
-        break;
+        if (blocks > device_cus()) blocks = device_cus();       // persistent grid: one 1024-thread workgroup per CU
+        return with_dim(P.dim, [&](auto D) {
+            return launch<k_delta_action_pipe2<D()>>(dim3(blocks), dim3(1024), lds, st, P, paths, VT, WF, n_items, walker, ip, ib,
+                                                     xnew, xold, out, parts);
+        });
     }
     case K1_REFORDER: {
         const size_t lds = (size_t)P.Np * 8 * sizeof(double);
         if (lds > 160 * 1024) return hipErrorInvalidValue;
         const int grid = n_items < (1 << 16) ? n_items : (1 << 16);
-#define CALL(D, T)                                                                                      \
-    do {                                                                                                \
-        e = set_lds<k_delta_action_reforder<D, T>>(lds);                                                \
-        if (e == hipSuccess)                                                                            \
-            hipLaunchKernelGGL((k_delta_action_reforder<D, T>), dim3(grid), dim3(64), lds, st, P, paths, VT, WF, \
-                               n_items, walker, ip, ib, xnew, xold, out, parts);                        \
-    } while (0)
-        PIGS_DISPATCH(P, CALL);
-#undef CALL
-        break;
+        return with_flag(P.trap, [&](auto T) {
+            return with_dim(P.dim, [&](auto D) {
+                return launch<k_delta_action_reforder<D(), T()>>(dim3(grid), dim3(64), lds, st, P, paths, VT, WF, n_items, walker,
+                                                                 ip, ib, xnew, xold, out, parts);
+            });
+        });
     }
     default:
         return hipErrorInvalidValue;
     }
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
 }
 
 #ifdef PIGS_EXPERIMENT_K1_CLOCK
@@ -877,8 +808,7 @@ extern "C" int pigs_k1_clock_read(unsigned long long *dst, int n_waves)
 hipError_t launch_selftest_fastmath(const DevParams &P, unsigned long long seed, int blocks, int iters,
                                     unsigned long long *d_bad, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_selftest_fastmath, dim3(blocks), dim3(256), 0, st, P, seed, iters, d_bad);
-    return hipGetLastError();
+    return launch<k_selftest_fastmath>(dim3(blocks), dim3(256), 0, st, P, seed, iters, d_bad);
 }
 
 } // namespace pigs

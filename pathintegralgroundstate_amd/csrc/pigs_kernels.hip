@@ -12,6 +12,7 @@
 #include "pigs_device.h"
 #include "pigs_k1_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 #include "pigs_log_host.h"
 
 namespace pigs {
@@ -473,19 +474,6 @@ __global__ void k_unpack(DevParams P, const double *__restrict__ paths, double *
 // =====================================================================================
 // launchers (host)
 // =====================================================================================
-#define PIGS_DISPATCH(P, CALL)                                              \
-    do {                                                                    \
-        if ((P).trap) {                                                     \
-            if ((P).dim == 1) { CALL(1, true); }                            \
-            else if ((P).dim == 2) { CALL(2, true); }                       \
-            else { CALL(3, true); }                                         \
-        } else {                                                            \
-            if ((P).dim == 1) { CALL(1, false); }                           \
-            else if ((P).dim == 2) { CALL(2, false); }                      \
-            else { CALL(3, false); }                                        \
-        }                                                                   \
-    } while (0)
-
 static int slice_block(const DevParams &P)
 {
     int t = ((P.Np + 63) / 64) * 64;
@@ -500,45 +488,33 @@ hipError_t launch_slice_energy(const DevParams &P, const double *paths, const do
     // many slices of a periodic system: the persistent LDS-table kernel (one workgroup per CU, 4 slices at a time)
     {
         const size_t lds = ((((size_t)P.Nmax + 8) * 8 + 15) & ~(size_t)15) + ((size_t)4 * P.dim * P.NpPad + 48) * sizeof(double);
-        int dev = 0, ncu = 256;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-            ncu = pr.multiProcessorCount;
+        const int ncu = device_cus();
         if (!P.trap && VTimg && P.Np <= 256 && !(P.Nmax & 1) && lds <= 160 * 1024 && n_slots >= 8 * ncu) {
             int blocks = (n_slots + 3) / 4;
             if (blocks > ncu) blocks = ncu;
             if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-            hipError_t e = hipSuccess;
-#define CALLL(D)                                                                                          \
-    do {                                                                                                  \
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_slice_energy_lds<D>),                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
-        if (e == hipSuccess)                                                                              \
-            hipLaunchKernelGGL((k_slice_energy_lds<D>), dim3(blocks), dim3(1024), lds, st, P, paths,      \
-                               VTimg, n_slots, slot_walker, slot_ib, force_mode, want_spring, out);       \
-    } while (0)
-            if (P.dim == 1) CALLL(1); else if (P.dim == 2) CALLL(2); else CALLL(3);
-#undef CALLL
-            if (e != hipSuccess) return e;
-            return hipGetLastError();
+            return with_dim(P.dim, [&](auto D) {
+                return launch<k_slice_energy_lds<D()>>(dim3(blocks), dim3(1024), lds, st, P, paths, VTimg, n_slots, slot_walker,
+                                                       slot_ib, force_mode, want_spring, out);
+            });
         }
     }
     const int bs = slice_block(P);
     const size_t lds = ((size_t)P.dim * P.NpPad + 3 * (bs / 64)) * sizeof(double);
-#define CALL(D, T)                                                                       \
-    hipLaunchKernelGGL((k_slice_energy<D, T>), dim3(n_slots), dim3(bs), lds, st, P, paths, \
-                       VT, n_slots, slot_walker, slot_ib, force_mode, want_spring, out)
-    PIGS_DISPATCH(P, CALL);
-#undef CALL
-    return hipGetLastError();
+    if (lds > kLdsNoGrant) return hipErrorInvalidValue;
+    return with_flag(P.trap, [&](auto T) {
+        return with_dim(P.dim, [&](auto D) {
+            return launch<k_slice_energy<D(), T()>>(dim3(n_slots), dim3(bs), lds, st, P, paths, VT, n_slots, slot_walker, slot_ib,
+                                                    force_mode, want_spring, out);
+        });
+    });
 }
 
 hipError_t launch_therm_combine(const DevParams &P, int n, const double *slices, double *E,
                                 double *Ec, double *Ep, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_therm_combine, dim3((n + 63) / 64), dim3(64), 0, st, P, n, slices, E, Ec, Ep);
-    return hipGetLastError();
+    return launch<k_therm_combine>(dim3((n + 63) / 64), dim3(64), 0, st, P, n, slices, E, Ec, Ep);
 }
 
 hipError_t launch_local_energy(const DevParams &P, const double *paths, const double *VT,
@@ -548,12 +524,13 @@ hipError_t launch_local_energy(const DevParams &P, const double *paths, const do
     if (n_slots <= 0) return hipSuccess;
     const int bs = slice_block(P);
     const size_t lds = ((size_t)P.dim * P.NpPad + 4 * (bs / 64)) * sizeof(double);
-#define CALL(D, T)                                                                       \
-    hipLaunchKernelGGL((k_local_energy<D, T>), dim3(n_slots), dim3(bs), lds, st, P, paths, \
-                       VT, WF, n_slots, slot_walker, ib, out)
-    PIGS_DISPATCH(P, CALL);
-#undef CALL
-    return hipGetLastError();
+    if (lds > kLdsNoGrant) return hipErrorInvalidValue;
+    return with_flag(P.trap, [&](auto T) {
+        return with_dim(P.dim, [&](auto D) {
+            return launch<k_local_energy<D(), T()>>(dim3(n_slots), dim3(bs), lds, st, P, paths, VT, WF, n_slots, slot_walker, ib,
+                                                    out);
+        });
+    });
 }
 
 hipError_t launch_structure(const DevParams &P, const double *paths, int n_slots, const int32_t *slot_walker,
@@ -561,11 +538,12 @@ hipError_t launch_structure(const DevParams &P, const double *paths, int n_slots
 {
     if (n_slots <= 0) return hipSuccess;
     const size_t lds = (size_t)P.dim * P.NpPad * sizeof(double) + (size_t)Nbin * sizeof(unsigned int);
+    if (lds > kLdsNoGrant) return hipErrorInvalidValue;
     const double pi = acos(-1.0);
-    if (P.dim == 1) hipLaunchKernelGGL((k_structure<1>), dim3(n_slots), dim3(256), lds, st, P, paths, n_slots, slot_walker, ib, Nbin, rbin, Nk, pi, gr, Sk);
-    else if (P.dim == 2) hipLaunchKernelGGL((k_structure<2>), dim3(n_slots), dim3(256), lds, st, P, paths, n_slots, slot_walker, ib, Nbin, rbin, Nk, pi, gr, Sk);
-    else hipLaunchKernelGGL((k_structure<3>), dim3(n_slots), dim3(256), lds, st, P, paths, n_slots, slot_walker, ib, Nbin, rbin, Nk, pi, gr, Sk);
-    return hipGetLastError();
+    return with_dim(P.dim, [&](auto D) {
+        return launch<k_structure<D()>>(dim3(n_slots), dim3(256), lds, st, P, paths, n_slots, slot_walker, ib, Nbin, rbin, Nk, pi,
+                                        gr, Sk);
+    });
 }
 
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
@@ -573,32 +551,28 @@ hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, con
 {
     if (n <= 0) return hipSuccess;
     const int64_t tot = n * P.dim;
-    hipLaunchKernelGGL(k_commit_beads, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P,
-                       paths, n, walker, ip, ib, x);
-    return hipGetLastError();
+    return launch<k_commit_beads>(dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P, paths, n,
+                                  walker, ip, ib, x);
 }
 
 hipError_t launch_swap_tails(const DevParams &P, double *paths, int walker, int iw, int ik, hipStream_t st)
 {
     const int tot = (P.Nb + 1) * P.dim;
-    hipLaunchKernelGGL(k_swap_tails, dim3((tot + 255) / 256), dim3(256), 0, st, P, paths, walker, iw, ik);
-    return hipGetLastError();
+    return launch<k_swap_tails>(dim3((tot + 255) / 256), dim3(256), 0, st, P, paths, walker, iw, ik);
 }
 
 hipError_t launch_pack(const DevParams &P, double *paths, const double *raw, int w0, int nw, hipStream_t st)
 {
     const size_t tot = (size_t)P.dim * P.Np * P.M * nw;
     if (!tot) return hipSuccess;
-    hipLaunchKernelGGL(k_pack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P, paths, raw, w0, nw);
-    return hipGetLastError();
+    return launch<k_pack>(dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P, paths, raw, w0, nw);
 }
 
 hipError_t launch_unpack(const DevParams &P, const double *paths, double *raw, int w0, int nw, hipStream_t st)
 {
     const size_t tot = (size_t)P.dim * P.Np * P.M * nw;
     if (!tot) return hipSuccess;
-    hipLaunchKernelGGL(k_unpack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P, paths, raw, w0, nw);
-    return hipGetLastError();
+    return launch<k_unpack>(dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P, paths, raw, w0, nw);
 }
 
 // ---- measurement aid: a plain streaming read of the resident worldlines (what a kernel that only READS the bytes K1
@@ -625,14 +599,12 @@ __global__ void k_selftest_log(unsigned long long first, unsigned long long n, u
 
 hipError_t launch_selftest_log(unsigned long long first, unsigned long long n, unsigned long long seed, double *d_out, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_selftest_log, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, first, n, seed, d_out);
-    return hipGetLastError();
+    return launch<k_selftest_log>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, first, n, seed, d_out);
 }
 
 hipError_t launch_stream_read(const double *a, size_t doubles, int blocks, double *sink, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_stream_read, dim3(blocks), dim3(1024), 0, st, reinterpret_cast<const double2 *>(a), doubles / 2, sink);
-    return hipGetLastError();
+    return launch<k_stream_read>(dim3(blocks), dim3(1024), 0, st, reinterpret_cast<const double2 *>(a), doubles / 2, sink);
 }
 
 } // namespace pigs

@@ -30,6 +30,7 @@
 
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 #include "pigs_sqv_device.h"
 
 namespace pigs {
@@ -93,19 +94,14 @@ hipError_t launch_sqv(const DevParams &P, const double *paths, int n, const Walk
     const SqvShape s = sqv_shape(P.dim, nmax);
     const int ns = 2 * window + 1;
     const double pi = acos(-1.0);
-#define CALL(D)                                                                                                          \
-    hipLaunchKernelGGL((k_sqv_rho2<D>), dim3(n * ns), dim3(s.threads), s.lds, st, P, paths, list, window, nmax, s.tile, \
-                       s.nprefix, s.nchunk, s.Nq, pi, rho2)
-    if (P.dim == 1) CALL(1);
-    else if (P.dim == 2) CALL(2);
-    else CALL(3);
-#undef CALL
-    hipError_t e = hipGetLastError();
+    const hipError_t e = with_dim(P.dim, [&](auto D) {
+        return launch<k_sqv_rho2<D()>>(dim3(n * ns), dim3(s.threads), s.lds, st, P, paths, list, window, nmax, s.tile, s.nprefix,
+                                       s.nchunk, s.Nq, pi, rho2);
+    });
     if (e != hipSuccess) return e;
     const size_t total = (size_t)n * s.Nq;
-    hipLaunchKernelGGL(k_sqv_combine, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, list, n, ns, s.Nq, rho2, acc,
-                       samples);
-    return hipGetLastError();
+    return launch<k_sqv_combine>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, list, n, ns, s.Nq, rho2, acc,
+                                 samples);
 }
 
 } // namespace pigs

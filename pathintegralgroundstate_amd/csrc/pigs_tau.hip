@@ -30,6 +30,7 @@
 
 #include "pigs_device.h"
 #include "pigs_kernels.h"
+#include "pigs_launch.h"
 
 namespace pigs {
 
@@ -135,12 +136,12 @@ hipError_t launch_tau(const DevParams &P, const double *paths, const double *VT,
     const int n_slots = n * P.M;
     const int bs = std::min(256, ((P.Np + 63) / 64) * 64);
     const size_t lds = ((size_t)P.dim * P.NpPad + 4 * (bs / 64)) * sizeof(double);
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-#define CALL(D, T) hipLaunchKernelGGL((k_tau<D, T>), dim3(n_slots), dim3(bs), lds, st, P, paths, VT, list, acc, samples)
-    if (P.trap) { if (P.dim == 1) CALL(1, true); else if (P.dim == 2) CALL(2, true); else CALL(3, true); }
-    else { if (P.dim == 1) CALL(1, false); else if (P.dim == 2) CALL(2, false); else CALL(3, false); }
-#undef CALL
-    return hipGetLastError();
+    if (lds > kLdsNoGrant) return hipErrorInvalidValue;
+    return with_flag(P.trap, [&](auto T) {
+        return with_dim(P.dim, [&](auto D) {
+            return launch<k_tau<D(), T()>>(dim3(n_slots), dim3(bs), lds, st, P, paths, VT, list, acc, samples);
+        });
+    });
 }
 
 } // namespace pigs
