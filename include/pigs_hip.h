@@ -488,6 +488,57 @@ int pigs_grv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_grv_init. */
 int pigs_grv_read(pigs_ctx *ctx, int64_t *vec, int64_t *radial, int64_t *samples, const int32_t *reset);
 
+/* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
+ * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
+ * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for
+ * dim = 1.
+ * For every listed walker and every slice a = Nb-window..Nb+window:
+ * - Bonds.  For particles i and j take d_k = x_k(i) - x_k(j), folded once as pbc_mod.f90:40-41 does (min_image<DIM>: the
+ *   two compares, each against LboxHalf), and r2 the sum of the squares, left to right, with no fused multiply-adds
+ *   (pigs_grv_*'s arithmetic; r2 of (j, i) has the bits of r2 of (i, j)).  j is a neighbour of i if and only if
+ *   0 < r2 and r2 < rnb*rnb hold in double.  The particle itself, a coincident partner (r2 = 0) and a non-finite r2 are
+ *   no bonds.  n_i is the number of neighbours of i.  rnb <= min_k Lbox[k]/2 makes the minimum image of a bond unique.
+ * - 3D, l = 4 and 6.  q_lm(i) = (1/n_i) sum_j Y_lm(d_ij/|d_ij|), and 0 where n_i = 0; only m = 0..l are kept (Y_l,-m
+ *   follows by symmetry).  q_l(i) = sqrt(4 pi/(2l+1) sum_{m=-l..l} |q_lm(i)|^2) is the local invariant, and
+ *   Q_l = sqrt(4 pi/(2l+1) sum_m |Q_lm|^2) with Q_lm = (1/Np) sum_i q_lm(i) the slice invariant.
+ * - 2D, n = 4 and 6.  psi_n(i) = (1/n_i) sum_j e^{i n theta_ij}; |psi_n(i)| and Psi_n = |(1/Np) sum_i psi_n(i)| take the
+ *   slots of q_l(i) and Q_l in every array below.
+ * - Correlation (Nr > 0).  For the pairs i < j with r2 <= rcut2 and u = sqrt(r2)/rbin < Nr (pigs_grv_*'s radial rule,
+ *   coincident pairs included), c_ij = (4 pi/13) Re sum_{m=-6..6} q_6m(i) q_6m(j)* in 3D and Re psi_6(i) psi_6(j)* in 2D
+ *   (|c_ij| <= 1) is added to bin (int)u, and 1 to the bin's pair count.  G6(r) = G/GN.
+ * Accumulators per walker, all 8-byte elements:
+ *   S[w][8]      doubles, each summed over the window slices of every call: Q4, Q4^2, Q6, Q6^2, (1/Np) sum_i q4(i),
+ *                (1/Np) sum_i q6(i), sum_i n_i (an exact integer), and a reserved slot that stays 0
+ *   H[w][2][Nh]  int64: the counts of q4(i) and of q6(i) over [0, 1], bin min((int)(q Nh), Nh - 1), decided in double
+ *                before the conversion (a particle without neighbours counts in bin 0); every slice adds Np to each
+ *   G[w][Nr]     doubles: the sums of c_ij per radial bin;  GN[w][Nr] int64: the pairs per bin
+ *   samples[w]   int64: calls, not slices, as pigs_sqv_* counts them; a call adds 2 window + 1 slices
+ * Order of the sums (no floating-point atomics; the same worldline gives the same bits whatever the walker list, its
+ * order, the launch split at 256 walkers or the number of walkers of the context): the bonds of a particle in ascending
+ * j; the particle sums per lane in ascending i, the wave by a fixed butterfly, the waves in wave order; the slices in
+ * ascending order, then acc += value.  The per-bin sums of c_ij are kept in fixed point within a slice: c_ij 2^40
+ * rounded to nearest, added as int64 (which no order changes), converted to double once per slice and bin -- each
+ * c_ij carries an error of at most 2^-41 from it.  A bin holds at most Np (Np - 1)/2 pairs of a slice, and
+ * Np (Np - 1)/2 2^40 stays below 2^63 up to Np = 4096; pigs_bop_init refuses a larger Np where Nr > 0.
+ * One workgroup holds a slice in LDS: 8 dim Np bytes for the positions, with Nr > 0 another 8 c Np for the l = 6
+ * components (c = 13 in 3D, 2 in 2D) and 16 Nr for the bins, and 800 (3D) or 224 (2D) bytes of reduction space;
+ * pigs_bop_init refuses (PIGS_ERR_ARG) what passes the 160 KiB of a CU.  Without the correlation that is Np <= 6793 in
+ * 3D and Np <= 10226 in 2D; with Nr = 100 it is Np <= 1261 in 3D, and in 2D the rule above (4096) comes first.
+ *
+ * pigs_bop_init allocates and zeroes the accumulators (again: resizes and zeroes).  PIGS_ERR_ARG unless rnb is finite
+ * with 0 < rnb <= min_k Lbox[k]/2, 0 <= window <= Nb, 1 <= Nh <= 4096, Nr >= 0 (0 switches the correlation off; rbin
+ * is then ignored), and for Nr > 0 rbin is finite and positive; and for the two limits on Np above. */
+int pigs_bop_init(pigs_ctx *ctx, double rnb, int32_t window, int32_t Nh, int32_t Nr, double rbin);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_bop_init, for n < 0 or for a walker out of range. */
+int pigs_bop_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' S[n_walkers][8], H[n_walkers][2][Nh], G[n_walkers][Nr], GN[n_walkers][Nr] and samples[n_walkers]; then
+ * zeroes those of the walkers w with reset[w] != 0 (reset == NULL: none).  G and GN may be NULL where Nr = 0.
+ * Synchronises the context.  PIGS_ERR_ARG before pigs_bop_init. */
+int pigs_bop_read(pigs_ctx *ctx, double *S, int64_t *H, double *G, int64_t *GN, int64_t *samples, const int32_t *reset);
+
 /* ---- imaginary-time profiles of the potential energy, the virial and the link lengths (new: pigs_fqt_*, pigs_sqv_*,
  * pigs_fqv_*, pigs_grv_* and the density profiles all take a slice window "inside the converged part of the path"; this
  * is the quantity that shows where that part is) ----------------------------------------------------------------------

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "pigs_fqs_init", "pigs_fqs_count", "pigs_fqs_vectors", "pigs_fqs_accumulate", "pigs_fqs_read",
     "pigs_grv_init", "pigs_grv_accumulate", "pigs_grv_read",
     "pigs_tau_init", "pigs_tau_accumulate", "pigs_tau_read",
+    "pigs_bop_init", "pigs_bop_accumulate", "pigs_bop_read",
 ]
 
 
@@ -157,6 +158,9 @@ def load_library(path=LIB_PATH):
     L.pigs_grv_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32]
     L.pigs_grv_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_grv_read.argtypes = [vp, _lp, _lp, _lp, _ip]
+    L.pigs_bop_init.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double]
+    L.pigs_bop_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_bop_read.argtypes = [vp, _dp, _lp, _dp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -665,6 +669,37 @@ class PigsContext:
                "samples": np.zeros(W, np.int64)}
         mask = self._reset_mask(reset)
         _chk(self.L, self.L.pigs_grv_read(self.h, *(_l(out[k]) for k in ("vec", "radial", "samples")), mask), "pigs_grv_read")
+        return out
+
+    # ---- bond-orientational order over a slice window (pigs_bop_*: raw sums and 64-bit counts per walker)
+    def bop_init(self, rnb, window=0, Nh=50, Nr=None, rbin=None):
+        """Allocate and zero the accumulators of Q4, Q6 (2D: Psi_4, Psi_6), their local distributions in Nh bins over
+        [0, 1] and G6(r) over the slices Nb-window..Nb+window of a periodic system in 2D or 3D; bonds are the pairs
+        closer than rnb (at most half the shortest side).  Nr radial bins of width rbin (defaults: the context's Nbin
+        and rcut / float32(Nbin), as grv_init); Nr = 0 switches G6(r) off.  Calling it again resizes and zeroes."""
+        c = self.cfg
+        nr = c.Nbin if Nr is None else int(Nr)
+        rb = (c.rcut / float(np.float32(nr)) if nr > 0 else 0.0) if rbin is None else float(rbin)
+        _chk(self.L, self.L.pigs_bop_init(self.h, float(rnb), int(window), int(Nh), nr, rb), "pigs_bop_init")
+        self._bop_shape = (int(Nh), nr)
+
+    def bop_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_bop_accumulate", walkers)
+
+    def bop_read(self, reset=None):
+        """dict: S [W, 8] (the sums of Q4, Q4^2, Q6, Q6^2, mean q4(i), mean q6(i), sum n_i, 0), H [W, 2, Nh] (int64), G
+        [W, Nr], GN [W, Nr] (int64) and samples [W] (int64); profiles.normalize_bop divides them.  reset: None, True (all
+        walkers) or a per-walker mask of walkers whose accumulators are zeroed after the copy."""
+        shp = getattr(self, "_bop_shape", None)
+        if shp is None:
+            raise PigsError("bop_read: bop_init first")
+        W = self.n_walkers
+        out = {"S": np.zeros((W, 8)), "H": np.zeros((W, 2, shp[0]), np.int64), "G": np.zeros((W, shp[1])),
+               "GN": np.zeros((W, shp[1]), np.int64), "samples": np.zeros(W, np.int64)}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_bop_read(self.h, _d(out["S"]), _l(out["H"]), _d(out["G"]), _l(out["GN"]), _l(out["samples"]),
+                                          mask), "pigs_bop_read")
         return out
 
     # ---- K5

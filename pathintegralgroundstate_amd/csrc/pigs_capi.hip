@@ -240,6 +240,14 @@ struct pigs_ctx {
     DevBuf<double> d_tau_acc;
     DevBuf<unsigned long long> d_tau_samples;
     bool        tau_ready = false;          // pigs_tau_init called
+    // bond-orientational order over a slice window (pigs_bop_*): raw sums S [walker][8] and G [walker][Nr], the counts
+    // H [walker][2][Nh] and GN [walker][Nr], the samples per walker, and the scratch of one launch's window slices
+    // ([bop_slots][2 window + 1][8 + Nr])
+    DevBuf<double> d_bop_S, d_bop_G, d_bop_scratch;
+    DevBuf<unsigned long long> d_bop_H, d_bop_GN, d_bop_samples;
+    int         bop_nh = 0;                 // 0: pigs_bop_init not called yet
+    int         bop_nr = 0, bop_window = 0, bop_slots = 0;
+    double      bop_rnb2 = 0.0, bop_rbin = 0.0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -1343,7 +1351,7 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     return PIGS_OK;
 }
 
-// ---- what the seven per-walker accumulator families below share ----------------------------------
+// ---- what the eight per-walker accumulator families below share ----------------------------------
 extern "C++" {      // templates
 
 // *_init, once the request is accepted: no accumulate may be in flight on the buffers being replaced, and until the new
@@ -1383,7 +1391,8 @@ static int each_launch(pigs_ctx *c, const std::vector<int32_t> &sw, const int32_
 
 } // extern "C++"
 
-// *_read: one accumulator array of 8-byte elements, `per` of them per walker, walker-major, and where its copy goes
+// *_read: one accumulator array of 8-byte elements, `per` of them per walker (0: an array that is switched off), walker-major,
+// and where its copy goes
 struct AccArray { void *dev; size_t per; void *host; };
 
 // copy every array to the host, then zero the flagged walkers (one memset per array and run of consecutive walkers), wait
@@ -1391,12 +1400,14 @@ static int read_and_reset(pigs_ctx *c, std::initializer_list<AccArray> arrays, c
 {
     const size_t W = (size_t)c->n_walkers, u = 8;
     hipStream_t s = c->stream;
-    for (const AccArray &a : arrays) HIPCHK(hipMemcpyAsync(a.host, a.dev, W * a.per * u, hipMemcpyDeviceToHost, s));
+    for (const AccArray &a : arrays)
+        if (a.per) HIPCHK(hipMemcpyAsync(a.host, a.dev, W * a.per * u, hipMemcpyDeviceToHost, s));
     for (size_t w = 0; reset && w < W;) {
         if (!reset[w]) { ++w; continue; }
         size_t e = w;
         while (e < W && reset[e]) ++e;
-        for (const AccArray &a : arrays) HIPCHK(hipMemsetAsync((char *)a.dev + w * a.per * u, 0, (e - w) * a.per * u, s));
+        for (const AccArray &a : arrays)
+            if (a.per) HIPCHK(hipMemsetAsync((char *)a.dev + w * a.per * u, 0, (e - w) * a.per * u, s));
         w = e;
     }
     SYNC_CHECKED(c);
@@ -1816,6 +1827,71 @@ int pigs_grv_read(pigs_ctx *c, int64_t *vec, int64_t *radial, int64_t *samples, 
     if (!vec || !radial || !samples) return fail(PIGS_ERR_ARG, "null output");
     return read_and_reset(c, {{c->d_grv_vec.p, c->grv_nvec, vec}, {c->d_grv_radial.p, (size_t)c->grv_nr, radial},
                               {c->d_grv_samples.p, 1, samples}}, reset);
+}
+
+// ---- bond-orientational order of a periodic system over a slice window ---------------------------
+// Raw sums and integer counts per walker (pigs_bop.hip), accumulated on the device and read per block.
+int pigs_bop_init(pigs_ctx *c, double rnb, int32_t window, int32_t Nh, int32_t Nr, double rbin)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "bond-orientational order is defined for periodic systems only (bonds are minimum images)");
+    if (c->P.dim < 2) return fail(PIGS_ERR_UNSUPPORTED, "bond-orientational order is defined in 2D and 3D only");
+    bool rnb_ok = std::isfinite(rnb) && rnb > 0.0;
+    for (int k = 0; k < c->P.dim; ++k) rnb_ok = rnb_ok && rnb <= c->P.LboxHalf[k];
+    if (!rnb_ok || window < 0 || window > c->P.Nb || Nh < 1 || Nh > kBopHistMax || Nr < 0 ||
+        (Nr > 0 && (!(rbin > 0.0) || !std::isfinite(rbin))))
+        return fail(PIGS_ERR_ARG, "pigs_bop_init: rnb=%g (0 < rnb <= half the shortest side) window=%d (0..Nb=%d) Nh=%d (1..%d) Nr=%d rbin=%g",
+                    rnb, window, c->P.Nb, Nh, kBopHistMax, Nr, rbin);
+    if (Nr > 0 && c->P.Np > kBopNpMax)
+        return fail(PIGS_ERR_ARG, "pigs_bop_init: Np=%d passes %d, where a fixed-point bin of G6(r) could overflow", c->P.Np, kBopNpMax);
+    const size_t lds = bop_lds_bytes(c->P.dim, c->P.Np, Nr);
+    if (lds > kBopLdsBudget)
+        return fail(PIGS_ERR_ARG, "pigs_bop_init: Np=%d Nr=%d need %zu bytes of LDS for one slice (%zu at most)", c->P.Np, Nr, lds,
+                    kBopLdsBudget);
+    const size_t W = (size_t)c->n_walkers, per = (size_t)8 + Nr;
+    const int slots = std::min(c->n_walkers, kWalkerListMax);
+    rc = init_begin(c, c->bop_nh); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_bop_S, W * 8));
+    HIPCHK(alloc_zeroed(c, c->d_bop_H, W * 2 * Nh));
+    HIPCHK(alloc_zeroed(c, c->d_bop_G, W * std::max(Nr, 1)));
+    HIPCHK(alloc_zeroed(c, c->d_bop_GN, W * std::max(Nr, 1)));
+    HIPCHK(alloc_zeroed(c, c->d_bop_samples, W));
+    HIPCHK(c->d_bop_scratch.alloc((size_t)slots * (2 * window + 1) * per));
+    SYNC_CHECKED(c);
+    c->bop_nh = Nh;
+    c->bop_nr = Nr;
+    c->bop_window = window;
+    c->bop_slots = slots;
+    c->bop_rnb2 = rnb * rnb;
+    c->bop_rbin = Nr > 0 ? rbin : 1.0;
+    return PIGS_OK;
+}
+
+int pigs_bop_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->bop_nh) return fail(PIGS_ERR_ARG, "pigs_bop_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // one thread owns an accumulator element per launch, and the scratch holds bop_slots walkers
+    return each_launch(c, sw, walkers, true, c->bop_slots, "launch_bop", [&](int m, const WalkerList &L) {
+        return launch_bop(c->P, c->d_paths.p, m, L, c->bop_window, c->bop_nh, c->bop_nr, c->bop_rnb2, c->bop_rbin,
+                          c->d_bop_scratch.p, c->d_bop_S.p, c->d_bop_H.p, c->d_bop_G.p, c->d_bop_GN.p, c->d_bop_samples.p,
+                          c->stream);
+    });
+}
+
+int pigs_bop_read(pigs_ctx *c, double *S, int64_t *H, double *G, int64_t *GN, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->bop_nh) return fail(PIGS_ERR_ARG, "pigs_bop_init first");
+    if (!S || !H || !samples || (c->bop_nr > 0 && (!G || !GN))) return fail(PIGS_ERR_ARG, "null output");
+    const size_t nr = (size_t)c->bop_nr;
+    return read_and_reset(c, {{c->d_bop_S.p, 8, S}, {c->d_bop_H.p, (size_t)2 * c->bop_nh, H}, {c->d_bop_G.p, nr, G},
+                              {c->d_bop_GN.p, nr, GN}, {c->d_bop_samples.p, 1, samples}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

@@ -130,6 +130,24 @@ hipError_t launch_grv(const DevParams &P, const double *paths, int n, const Walk
 hipError_t launch_tau(const DevParams &P, const double *paths, const double *VT, int n, const WalkerList &list, double *acc,
                       unsigned long long *samples, hipStream_t st);
 
+// pigs_bop.hip: bond-orientational order over the window slices (pigs_bop_accumulate).  k_bop, one workgroup per (listed
+// walker, slice) with the whole slice and the table of the particles' l = 6 components in LDS, adds the local invariants
+// to hist ([walker][2][Nh], integer atomics) and the pair counts of G6(r) to gn ([walker][Nr]), and writes the slice's 8
+// scalars and Nr bins to scratch ([slot][slice][8 + Nr]); k_bop_combine adds the slices in ascending order to S
+// ([walker][8]) and G ([walker][Nr]) and 1 to samples.  One thread owns an accumulator element per launch: the caller
+// never lists a walker twice in ONE launch.  The per-bin sums of c_ij are kept in fixed point, c 2^40 rounded to nearest
+// in an int64, which no order of the pairs changes; a bin holds at most Np (Np - 1) / 2 pairs with |c| <= 1, which stays
+// below 2^63 up to kBopNpMax particles.  bop_lds_bytes is the dynamic LDS of k_bop, which has to fit kBopLdsBudget.
+constexpr int kBopThreads = 256;
+constexpr double kBopFixScale = 1099511627776.0; // 2^40
+constexpr int kBopNpMax = 4096;                  // 4096 * 4095 / 2 < 2^23
+constexpr int kBopHistMax = 4096;
+constexpr size_t kBopLdsBudget = 160 * 1024;     // LDS of one CU on gfx950
+size_t bop_lds_bytes(int dim, int Np, int Nr);
+hipError_t launch_bop(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Nh, int Nr,
+                      double rnb2, double rbin, double *scratch, double *S, unsigned long long *hist, double *G,
+                      unsigned long long *gn, unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

@@ -559,6 +559,29 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_tau_read_t
+
+     ! bond-orientational order over a slice window (include/pigs_hip.h, pigs_bop_*): looked up at run time, see bop_bind;
+     ! _accumulate has the signature of pigs_fqt_accumulate
+     function pigs_bop_init_t(ctx,rnb,window,Nh,Nr,rbin) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value        :: ctx
+       real(c_double), value     :: rnb
+       integer(c_int32_t), value :: window,Nh,Nr
+       real(c_double), value     :: rbin
+       integer(c_int) :: rc
+     end function pigs_bop_init_t
+
+     function pigs_bop_read_t(ctx,S,H,G,GN,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: S(*)          ! raw sums (8,n_walkers)
+       integer(c_int64_t)             :: H(*)          ! counts (Nh,2,n_walkers)
+       real(c_double)                 :: G(*)          ! raw sums (Nr,n_walkers)
+       integer(c_int64_t)             :: GN(*)         ! pairs (Nr,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_bop_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -601,6 +624,11 @@ module pigs_capi
   procedure(pigs_tau_init_t), pointer       :: tau_init => null()
   procedure(pigs_fqt_accumulate_t), pointer :: tau_accumulate => null()
   procedure(pigs_tau_read_t), pointer       :: tau_read => null()
+
+  ! bound by bop_bind (null until then)
+  procedure(pigs_bop_init_t), pointer       :: bop_init => null()
+  procedure(pigs_fqt_accumulate_t), pointer :: bop_accumulate => null()
+  procedure(pigs_bop_read_t), pointer       :: bop_read => null()
 
 contains
 
@@ -711,6 +739,16 @@ contains
     call c_f_procpointer(f(2),tau_accumulate)
     call c_f_procpointer(f(3),tau_read)
   end function tau_bind
+
+  ! The bond-orientational-order entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function bop_bind()
+    type(c_funptr) :: f(3)
+    bop_bind = resolve_all('pigs_bop',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. bop_bind) return
+    call c_f_procpointer(f(1),bop_init)
+    call c_f_procpointer(f(2),bop_accumulate)
+    call c_f_procpointer(f(3),bop_read)
+  end function bop_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

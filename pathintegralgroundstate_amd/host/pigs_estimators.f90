@@ -18,6 +18,7 @@ module pigs_estimators
   public :: normalize_msd, write_msd
   public :: normalize_grv, write_grvec
   public :: normalize_tau, write_tau
+  public :: normalize_bop, write_bo, write_boh
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -303,6 +304,56 @@ contains
     end do
     close (u)
   end subroutine write_tau
+
+  ! ---- bond-orientational order (raw sums and counts of pigs_bop_read over the window slices Nb-window..Nb+window) -> one
+  ! walker's block values with S samples, n = S (2 window + 1) slices: B = Q4, Q6, the particle means of q4(i) and q6(i),
+  ! each per slice, and the coordination sum n_i/(Np n); P(:,l) the distributions of q4(i), q6(i) as probability densities
+  ! on [0,1] (counts Nh/(n Np)); G6 = G/GN per radial bin (0 in a bin that held no pair in this block)
+  subroutine normalize_bop(Np,window,S,Nh,Nr,rawS,H,G,GN,B,P,G6)
+    integer, intent(in)    :: Np,window,Nh,Nr
+    integer(8), intent(in) :: S
+    real(8), intent(in)    :: rawS(8),G(Nr)
+    integer(8), intent(in) :: H(Nh,2),GN(Nr)
+    real(8), intent(out)   :: B(5),P(Nh,2),G6(Nr)
+    real(8) :: n
+    integer :: j
+    n = real(S,8)*real(2*window+1,8)
+    B(1) = rawS(1)/n; B(2) = rawS(3)/n; B(3) = rawS(5)/n; B(4) = rawS(6)/n
+    B(5) = rawS(7)/(n*real(Np,8))
+    P = real(H,8)*real(Nh,8)/(n*real(Np,8))
+    do j=1,Nr
+       G6(j) = 0.d0
+       if (GN(j)>0) G6(j) = G(j)/real(GN(j),8)
+    end do
+  end subroutine normalize_bop
+
+  ! bo_vpi.out: one row: mean and error of Q4, Q6, <q4(i)>, <q6(i)> and the coordination
+  subroutine write_bo(fname,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: n
+    real(8), intent(inout) :: av(5),av2(5)
+    integer :: k,u
+    open (newunit=u,file=fname)
+    av  = av/real(n)
+    av2 = av2/real(n)
+    write (u,'(20g20.10e3)') (av(k),variance(n,av(k),av2(k)),k=1,5)
+    close (u)
+  end subroutine write_bo
+
+  ! boh_vpi.out: one row per bin of [0,1]: centre, then mean and error of P(q4) and of P(q6)
+  subroutine write_boh(fname,Nh,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: Nh,n
+    real(8), intent(inout) :: av(Nh,2),av2(Nh,2)
+    integer :: j,k,u
+    open (newunit=u,file=fname)
+    av  = av/real(n)
+    av2 = av2/real(n)
+    do j=1,Nh
+       write (u,'(20g20.10e3)') (real(j,8)-0.5d0)/real(Nh,8),(av(j,k),variance(n,av(j,k),av2(j,k)),k=1,2)
+    end do
+    close (u)
+  end subroutine write_boh
 
   ! ---- vector structure factor on the full reciprocal grid (raw sums of pigs_sqv_read: window slices
   ! Nb-window..Nb+window) -> one walker's S(q) of one block with S samples: raw/(S (2 window + 1) Np)

@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -47,6 +47,10 @@ module pigs_families
      integer :: tau_window = 0
      logical :: fq_self = .false.
      integer :: fqs_nmax = 8, fqs_ntau = 0, fqs_window = -1
+     logical :: bond_order = .false.
+     real(8) :: bo_rnb = 0.d0
+     integer :: bo_nhist = 50, bo_nr = -1, bo_window = 0     ! bo_nr < 0: the run's g(r) grid
+     real(8) :: half_side = 0.d0                    ! half the shortest side of a periodic box (what bo_rnb may not pass)
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -270,16 +274,37 @@ module pigs_families
      procedure :: write_average => tau_write_average
   end type tau_family
 
-  integer, parameter :: NFAM = 7
+  ! bond-orientational order: the block's raw sums and counts from the device, the normalised block values (the five
+  ! scalars, the two distributions, G6 per radial bin); epr is ep with the radial grid of G6
+  type, extends(family) :: bop_family
+     integer :: nh = 0, nr = 0, window = 0
+     real(8) :: rnb = 0.d0
+     type(est_params) :: epr
+     real(8), allocatable :: rawS(:,:),rawG(:,:),b(:),bh(:,:),bg(:)
+     integer(c_int64_t), allocatable :: H(:,:,:),GN(:,:)
+     type(block_series) :: sB,sH,sG
+   contains
+     procedure :: check => bop_check
+     procedure :: banner => bop_banner
+     procedure :: setup => bop_setup
+     procedure :: queue => bop_queue
+     procedure :: read => bop_read_block
+     procedure :: block => bop_block
+     procedure :: average => bop_average
+     procedure :: write_walker => bop_write_walker
+     procedure :: write_average => bop_write_average
+  end type bop_family
+
+  integer, parameter :: NFAM = 8
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
-  ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self
+  ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -311,6 +336,7 @@ contains
     if (keys%fq_vector)       allocate (fs%slot(5)%f,source=fqv_family())
     if (keys%tau_profile)     allocate (tau_family :: fs%slot(6)%f)
     if (keys%fq_self)         allocate (fs%slot(7)%f,source=fqs_family())
+    if (keys%bond_order)      allocate (bop_family :: fs%slot(8)%f)
   end subroutine set_create
 
   ! refuses what the keys cannot have (exit status 2) and fills in the windows that were left out
@@ -1172,5 +1198,126 @@ contains
     call write_tau('tau_vpi.out',f%run%Nb,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
     if (.not. f%ep%trap) close (f%upav)
   end subroutine tau_write_average
+
+  !---------------------------------------------------------------------
+  ! bond_order: the bond-orientational order of a periodic system in 2D or 3D over the slices Nb-bo_window..Nb+bo_window,
+  ! bonds closer than bo_rnb -- bo_vpi.out (Q4, Q6, the means of q4(i), q6(i), the coordination), boh_vpi.out (the
+  ! distributions of q4(i), q6(i) on bo_nhist bins) and g6_vpi.out (G6(r) on bo_nr bins up to rcut, gr_vpi.out's format)
+
+  subroutine bop_check(f,keys,dim,Nb,trap)
+    class(bop_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('bond_order','its bonds are minimum images in the box')
+    if (dim<2) then
+       write (0,'(a,i0)') ' pigs_vpi: bond_order = T needs dim = 2 or 3: there is no bond orientation in dim = ',dim
+       stop 2
+    end if
+    if (.not. (keys%bo_rnb>0.d0) .or. keys%bo_rnb>keys%half_side) then
+       write (0,'(a,g0,a,g0)') ' pigs_vpi: bond_order = T: bo_rnb = ',keys%bo_rnb, &
+            & ' (required) must be positive and at most half the shortest side of the box = ',keys%half_side
+       stop 2
+    end if
+    if (keys%bo_nhist<1 .or. keys%bo_nhist>4096) then
+       write (0,'(a,i0,a)') ' pigs_vpi: bond_order = T: bo_nhist = ',keys%bo_nhist,' must lie in 1 .. 4096'
+       stop 2
+    end if
+    if (keys%bo_nr>8192) then
+       write (0,'(a,i0,a)') ' pigs_vpi: bond_order = T: bo_nr = ',keys%bo_nr,' must lie in 0 .. 8192 (left out: the g(r) grid)'
+       stop 2
+    end if
+    call check_window('bond_order','bo',keys%bo_window,Nb)
+    if (.not. bop_bind()) call no_backend('bond_order','pigs_bop_init / _accumulate / _read','the bond-orientational order runs')
+  end subroutine bop_check
+
+  subroutine bop_banner(f,keys,trap)
+    class(bop_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,g0.6,a,i0,a,i0,a)', '  > Bond order Q4, Q6   : on (bonds below ',keys%bo_rnb,', slices Nb-',keys%bo_window,'..Nb+',keys%bo_window, &
+         & ': bo_vpi.out, boh_vpi.out, g6_vpi.out)'
+  end subroutine bop_banner
+
+  subroutine bop_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(bop_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%nh = keys%bo_nhist; f%window = keys%bo_window; f%rnb = keys%bo_rnb
+    f%epr = ep
+    if (keys%bo_nr>=0) then
+       f%epr%Nbin = keys%bo_nr
+       if (keys%bo_nr>0) f%epr%rbin = run%rcut/real(keys%bo_nr,8)
+    end if
+    f%nr = f%epr%Nbin
+    allocate (f%rawS(8,NW),f%H(f%nh,2,NW),f%rawG(max(f%nr,1),NW),f%GN(max(f%nr,1),NW),f%b(5),f%bh(f%nh,2),f%bg(f%nr))
+    call series_create(f%sB,5,NW,nvec)
+    call series_create(f%sH,2*f%nh,NW,nvec)
+    call series_create(f%sG,f%nr,NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(bop_init(ctx,real(f%rnb,c_double),int(f%window,c_int32_t),int(f%nh,c_int32_t),int(f%nr,c_int32_t), &
+         & real(f%epr%rbin,c_double)),'pigs_bop_init')
+  end subroutine bop_setup
+
+  subroutine bop_queue(f,ctx,nd,wl)
+    class(bop_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(bop_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_bop_accumulate')
+  end subroutine bop_queue
+
+  subroutine bop_read_block(f,ctx)
+    class(bop_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(bop_read(ctx,f%rawS,f%H,f%rawG,f%GN,f%smp,f%reset),'pigs_bop_read')
+  end subroutine bop_read_block
+
+  subroutine bop_block(f,w,info,vec)
+    class(bop_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_bop(f%ep%Np,f%window,int(f%smp(w),8),f%nh,f%nr,f%rawS(:,w),f%H(:,:,w),f%rawG(1:f%nr,w),f%GN(1:f%nr,w), &
+         & f%b,f%bh,f%bg)
+    call series_add(f%sB,w,f%b,vec)
+    call series_add(f%sH,w,f%bh,vec)
+    call series_add(f%sG,w,f%bg,vec)
+    call count_add(f%cnt,vec)
+  end subroutine bop_block
+
+  subroutine bop_average(f,info,vec)
+    class(bop_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sB,vec,nall)
+       call series_average(f%sH,vec,nall)
+       call series_average(f%sG,vec,nall)
+    end if
+  end subroutine bop_average
+
+  subroutine bop_write_walker(f,suffix,w,nblocks)
+    class(bop_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_bo('bo_vpi'//trim(suffix)//'.out',nblocks,f%sB%sum(:,w),f%sB%sq(:,w))
+    call write_boh('boh_vpi'//trim(suffix)//'.out',f%nh,nblocks,f%sH%sum(:,w),f%sH%sq(:,w))
+    call write_radial('g6_vpi'//trim(suffix)//'.out',f%epr,nblocks,f%sG%sum(:,w),f%sG%sq(:,w))
+  end subroutine bop_write_walker
+
+  subroutine bop_write_average(f)
+    class(bop_family), intent(inout) :: f
+    call write_bo('bo_vpi.out',f%cnt%nav,f%sB%asum,f%sB%asq)
+    call write_boh('boh_vpi.out',f%nh,f%cnt%nav,f%sH%asum,f%sH%asq)
+    call write_radial('g6_vpi.out',f%epr,f%cnt%nav,f%sG%asum,f%sG%asq)
+  end subroutine bop_write_average
 
 end module pigs_families

@@ -40,6 +40,12 @@
 ! GPU -- tau_vpi.out; the plateau of V(tau) around slice Nb is the converged part of the path, in which the windows above
 ! must stay.  Periodic runs also write press_vpi.out, the virial pressure per block with W averaged over the slices
 ! Nb-tau_window..Nb+tau_window (default 0); W stops at rcut and no tail correction is made)
+! (bond_order = T, periodic systems in 2D and 3D only: the bond-orientational order over the slices
+! Nb-bo_window..Nb+bo_window (default 0), bonds being the pairs closer than bo_rnb (required, at most half the shortest
+! side of the box), accumulated on the GPU -- bo_vpi.out, one line: Q4, Q6, the particle means of q4(i), q6(i) and the
+! coordination, each with its error (2D: Psi4, Psi6, |psi4(i)|, |psi6(i)|); boh_vpi.out, one line per bin of bo_nhist
+! (default 50) over [0,1]: centre, P(q4), P(q6) with their errors; g6_vpi.out: r and G6(r) on bo_nr bins of width
+! rcut/bo_nr (default: the run's Nbin and rbin) in gr_vpi.out's format, bins without pairs in a block counting as 0)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -84,6 +90,9 @@ program pigs_vpi
   integer           :: fqs_nmax,fqs_ntau,fqs_window
   logical           :: tau_profile
   integer           :: tau_window
+  logical           :: bond_order
+  real (kind=8)     :: bo_rnb
+  integer           :: bo_nhist,bo_nr,bo_window
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
   logical           :: sampler_auto
@@ -102,7 +111,8 @@ program pigs_vpi
        &             gr_vector,gr_nbin,gr_window, &
        &             fq_vector,fqv_nmax,fqv_ntau,fqv_window, &
        &             tau_profile,tau_window, &
-       &             fq_self,fqs_nmax,fqs_ntau,fqs_window
+       &             fq_self,fqs_nmax,fqs_ntau,fqs_window, &
+       &             bond_order,bo_rnb,bo_nhist,bo_nr,bo_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -131,6 +141,7 @@ program pigs_vpi
   fq_vector = .false.; fqv_nmax = 8; fqv_ntau = 0; fqv_window = -1
   tau_profile = .false.; tau_window = 0
   fq_self = .false.; fqs_nmax = 8; fqs_ntau = 0; fqs_window = -1
+  bond_order = .false.; bo_rnb = 0.d0; bo_nhist = 50; bo_nr = -1; bo_window = 0
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -153,13 +164,6 @@ program pigs_vpi
      write (0,*) 'pigs_vpi: v_table = T is required (the reference Force() is a stub: system_mod.f90:186-209)'
      stop 2
   end if
-  ! the estimator keys: refused values end the run before the backend is asked for the key's entry points
-  fk = family_keys(density_profile=density_profile,fq_tau=fq_tau,fq_ntau=fq_ntau,fq_window=fq_window, &
-       & sq_vector=sq_vector,sq_nmax=sq_nmax,sq_window=sq_window,gr_vector=gr_vector,gr_nbin=gr_nbin,gr_window=gr_window, &
-       & fq_vector=fq_vector,fqv_nmax=fqv_nmax,fqv_ntau=fqv_ntau,fqv_window=fqv_window,tau_profile=tau_profile, &
-       & tau_window=tau_window,fq_self=fq_self,fqs_nmax=fqs_nmax,fqs_ntau=fqs_ntau,fqs_window=fqs_window)
-  call keyed%create(fk)
-  call keyed%check(fk,dim,Nb,trap)
   NWtot = n_walkers
   G = max(1,min(n_gpus,NWtot))
   pi = acos(-1.d0)
@@ -201,6 +205,16 @@ program pigs_vpi
   end if
   rcut2 = rcut*rcut
   rbin  = rcut/real(Nbin)
+
+  ! the estimator keys: refused values end the run before the backend is asked for the key's entry points
+  ! (after the box: bo_rnb is measured against half its shortest side, which is rcut in a periodic system)
+  fk = family_keys(density_profile=density_profile,fq_tau=fq_tau,fq_ntau=fq_ntau,fq_window=fq_window, &
+       & sq_vector=sq_vector,sq_nmax=sq_nmax,sq_window=sq_window,gr_vector=gr_vector,gr_nbin=gr_nbin,gr_window=gr_window, &
+       & fq_vector=fq_vector,fqv_nmax=fqv_nmax,fqv_ntau=fqv_ntau,fqv_window=fqv_window,tau_profile=tau_profile, &
+       & tau_window=tau_window,fq_self=fq_self,fqs_nmax=fqs_nmax,fqs_ntau=fqs_ntau,fqs_window=fqs_window, &
+       & bond_order=bond_order,bo_rnb=bo_rnb,bo_nhist=bo_nhist,bo_nr=bo_nr,bo_window=bo_window,half_side=rcut)
+  call keyed%create(fk)
+  call keyed%check(fk,dim,Nb,trap)
 
   ! tables on the host (reference vpi_mod.f90:84-145), then the GPU context
   allocate (VTable(0:Nmax+1),LogWF(0:Nmax+1))

@@ -46,6 +46,12 @@ D2 = sum_i |x_i(b) - x_i(b+1)|^2 of slice b = 0..2Nb, so per particle
   vpair, vext, w = raw[..., 0..2] / (S * Np),   klink[b] = dim/(2*dt) - D2[b] / (2*dt**2 * Np * S)  for the 2Nb links,
 at tau_b = (b - Nb)*dt; the plateau of vpair + vext around tau = 0 is the converged part of the path.  The pressure of a
 periodic system is P = density/dim * (2*K/N - W/N).
+
+Bond-orientational order (normalize_bop, PigsContext.bop_read, pigs_bop_*): S holds, per sample, the sums over the
+2*window + 1 window slices of Q4, Q4^2, Q6, Q6^2, the particle means of q4(i) and q6(i), and sum_i n_i; H the counts of
+q4(i), q6(i) in Nh bins over [0, 1]; G and GN the sums of c_ij and the pairs per radial bin:
+  <Q_l> = S / (S_w * (2*window + 1)),  coordination = S[6] / (S_w * (2*window + 1) * Np),
+  P(q_l) = H * Nh / (S_w * (2*window + 1) * Np),   G6(r_j) = G[j] / GN[j]   (S_w the walker's samples)
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -233,6 +239,33 @@ def normalize_tau(raw, Np, dim, dt):
         klink = dim / (2.0 * dt) - Q[..., :M - 1, 3] / (2.0 * dt * dt * float(Np) * Sb)
     tau = (np.arange(M, dtype=np.float64) - Nb) * dt
     return {"vpair": per[..., 0], "vext": per[..., 1], "w": per[..., 2], "klink": klink, "tau": tau}
+
+
+def normalize_bop(raw, Np, window, rbin=None):
+    """raw: the dict of bop_read (S [W, 8], H [W, 2, Nh], G [W, Nr], GN [W, Nr], samples [W]) or one walker's slice of
+    it.  With n = samples * (2*window + 1) slices, returns a dict: Q4, Q4sq, Q6, Q6sq (the slice invariants and their
+    squares per slice), q4, q6 (the particle means of the local invariants per slice), coordination = sum n_i / (Np n),
+    P4, P6 ([.., Nh]: the distributions of q4(i), q6(i) as probability densities on [0, 1]) with the bin centres q, and
+    G6 = G / GN ([.., Nr]; NaN in a bin without pairs) with the bin centres r where rbin is given.  In 2D Psi_4, Psi_6
+    and |psi_n(i)| stand in the same places.  A walker without samples gives NaN."""
+    S = np.asarray(raw["S"], dtype=np.float64)
+    H = np.asarray(raw["H"], dtype=np.float64)
+    G = np.asarray(raw["G"], dtype=np.float64)
+    GN = np.asarray(raw["GN"], dtype=np.float64)
+    n = np.asarray(raw["samples"], dtype=np.float64) * (2.0 * window + 1.0)
+    if S.shape[-1] != 8 or H.shape[-2] != 2:
+        raise ValueError("S must be [.., 8] and H [.., 2, Nh]")
+    Nh, Nr = H.shape[-1], G.shape[-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per = S / n[..., None]
+        P = H * float(Nh) / (n[..., None, None] * float(Np))           # counts / (particles counted * bin width 1/Nh)
+        G6 = np.where(GN > 0, G / GN, np.nan)
+    out = {"Q4": per[..., 0], "Q4sq": per[..., 1], "Q6": per[..., 2], "Q6sq": per[..., 3], "q4": per[..., 4],
+           "q6": per[..., 5], "coordination": per[..., 6] / float(Np), "P4": P[..., 0, :], "P6": P[..., 1, :],
+           "q": (np.arange(Nh, dtype=np.float64) + 0.5) / float(Nh), "G6": G6}
+    if rbin is not None:
+        out["r"] = (np.arange(1, Nr + 1, dtype=np.float64) - 0.5) * rbin
+    return out
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
