@@ -488,6 +488,57 @@ int pigs_grv_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_grv_init. */
 int pigs_grv_read(pigs_ctx *ctx, int64_t *vec, int64_t *radial, int64_t *samples, const int32_t *reset);
 
+/* ---- the van Hove functions G_s(r,tau) and G_d(r,tau) of a PERIODIC system, over a slice window (new: nothing in real
+ * space had a lag; these are to pigs_grv_* what pigs_fqs_* and pigs_fqv_* are to pigs_sqv_*) ------------------------------
+ * Two integer histograms per walker and lag, accumulated on the device.  Scope: periodic contexts with dim = 1, 2 or 3.
+ * - Window, lags and slice pairs.  The window and lags are those of pigs_fqv_*: slices Nb-window .. Nb+window
+ *   (0 <= window <= Nb) and lags l = 0 .. Ntau (0 <= Ntau <= 2 window).  For every listed walker w and every lag l there
+ *   are n_pairs(l) = 2 window + 1 - l slice pairs (a, a+l), with a = Nb-window .. Nb+window-l.
+ * - Displacements.  Take d_k = x_k(i, a+l) - x_k(j, a).  Fold it once as pbc_mod.f90:40-41 does (min_image<DIM>: the two
+ *   compares against LboxHalf).  Let r2 be the sum of the squares, left to right, with nothing fused.  This is exactly
+ *   pigs_grv_*'s arithmetic.
+ * - Distinct part (all ordered pairs i != j).  If r2 <= rcut2, take u = sqrt(r2)/rbin.  If u < Nr holds in double, add +1
+ *   to dist[w][l][(int)u].  This is pigs_grv_*'s radial rule, so at l = 0 dist equals 2 x pigs_grv_read's `radial` for
+ *   the same Nr, rbin, window and worldline, bin for bin.
+ * - Self part (j = i).  Take u = sqrt(r2)/sbin.  If u < Ns holds in double, add +1 to self[w][l][(int)u].  No rcut
+ *   condition applies.  The self part has its own grid (Ns, sbin): an imaginary-time displacement is a few tenths of
+ *   sigma, while the distinct part lives on 0..rcut, so one grid cannot serve both.  At lag 0 every particle lands in
+ *   bin 0.  As for pigs_fqs_*, this is the true displacement only while |d_k| stays below Lbox[k]/2 (particle labels are
+ *   continuous in imaginary time: pigs_swap_tails keeps them so).  The library does not judge that.
+ * - Decisions.  Every decision is taken in double before any conversion to an integer.  NaN, +-Inf and a difference that
+ *   one fold leaves far outside drop out without undefined behaviour.
+ * - Samples.  samples[w] counts calls, as every other family does.
+ * Accumulators: 64-bit integers per walker; self is [n_walkers][Ntau+1][Ns], dist is [n_walkers][Ntau+1][Nr], samples is
+ * [n_walkers].  The estimators are the caller's divisions (tau_l = l dt):
+ *   G_d(r_b; tau_l) = dist / (samples n_pairs(l) Np density dV_b)    dV_b the shell volume of the reference's NormAvGr,
+ *                                                                    as in grw_vpi.out; 1 - 1/Np for an ideal gas
+ *   G_s(r_b; tau_l) = self / (samples n_pairs(l) Np dV_b)            on the self grid: a probability density whose
+ *                                                                    integral over space is 1 when nothing was dropped
+ * Counts are integer atomics only (LDS u32 flushed into global u64, or global u64): the result depends on neither the
+ * walker list, its order, the launch split at 256 walkers, the kernel form nor the context.
+ * Kernel forms and limits.  One workgroup holds the base slice a in LDS, 8 dim Np bytes, and pigs_vh_init refuses
+ * (PIGS_ERR_ARG) a system with
+ *   8 dim Np > 163840                                  (the 160 KiB of a CU: Np <= 6826 in 3D, 10240 in 2D, 20480 in 1D).
+ * The histograms of all lags are privatised in LDS as u32 counters beside the slice where
+ *   8 dim Np + 4 (Ntau + 1) (Nr + Ns) <= 163840,
+ * and take global u64 atomics otherwise (tuning key "vh_form": -1 automatic, 0 global atomics, 1 LDS; a forced LDS form
+ * that does not fit returns PIGS_ERR_ARG at the next accumulate and queues nothing).  A u32 counter belongs to one lag of
+ * one base slice and gains at most one count per (i, j), Np^2 in all, before the workgroup's single flush; Np^2 stays
+ * below 2^32 up to Np = 65535, which the slice limit above never lets through: no u32 counter can wrap.
+ *
+ * pigs_vh_init allocates and zeroes the counts (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context;
+ * PIGS_ERR_ARG for Nr < 1 or Ns < 1, rbin or sbin not finite and positive, window < 0 or window > Nb, Ntau < 0 or
+ * Ntau > 2 window, accumulators larger than 2 GiB in total, or the slice limit above. */
+int pigs_vh_init(pigs_ctx *ctx, int32_t Ntau, int32_t window, int32_t Nr, double rbin, int32_t Ns, double sbin);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_vh_init, for n < 0 or for a walker out of range. */
+int pigs_vh_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' counts self[n_walkers][Ntau+1][Ns], dist[n_walkers][Ntau+1][Nr] and samples[n_walkers]; then zeroes those of
+ * the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_vh_init. */
+int pigs_vh_read(pigs_ctx *ctx, int64_t *self, int64_t *dist, int64_t *samples, const int32_t *reset);
+
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
  * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for

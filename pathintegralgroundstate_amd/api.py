@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "pigs_grv_init", "pigs_grv_accumulate", "pigs_grv_read",
     "pigs_tau_init", "pigs_tau_accumulate", "pigs_tau_read",
     "pigs_bop_init", "pigs_bop_accumulate", "pigs_bop_read",
+    "pigs_vh_init", "pigs_vh_accumulate", "pigs_vh_read",
 ]
 
 
@@ -161,6 +162,9 @@ def load_library(path=LIB_PATH):
     L.pigs_bop_init.argtypes = [vp, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double]
     L.pigs_bop_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_bop_read.argtypes = [vp, _dp, _lp, _dp, _lp, _lp, _ip]
+    L.pigs_vh_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double]
+    L.pigs_vh_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_vh_read.argtypes = [vp, _lp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -700,6 +704,37 @@ class PigsContext:
         mask = self._reset_mask(reset)
         _chk(self.L, self.L.pigs_bop_read(self.h, _d(out["S"]), _l(out["H"]), _d(out["G"]), _l(out["GN"]), _l(out["samples"]),
                                           mask), "pigs_bop_read")
+        return out
+
+    # ---- van Hove functions over a slice window (pigs_vh_*: 64-bit counts per walker and lag)
+    def vh_init(self, Ntau, window, Nr=None, rbin=None, Ns=50, sbin=None):
+        """Allocate and zero the counts of the distinct and the self van Hove function for the lags 0..Ntau over the
+        slices Nb-window..Nb+window of a periodic system: Nr radial bins of width rbin for |x_i(a+l) - x_j(a)|, i != j
+        (defaults: the context's Nbin and rcut / float32(Nbin), as grv_init), and Ns bins of width sbin for the
+        displacement |x_i(a+l) - x_i(a)| (default sbin: rcut / Ns).  Calling it again resizes and zeroes."""
+        c = self.cfg
+        nr = c.Nbin if Nr is None else int(Nr)
+        rb = c.rcut / float(np.float32(nr)) if rbin is None else float(rbin)
+        sb = c.rcut / float(Ns) if sbin is None else float(sbin)
+        _chk(self.L, self.L.pigs_vh_init(self.h, int(Ntau), int(window), nr, rb, int(Ns), sb), "pigs_vh_init")
+        self._vh_shape = (int(Ntau) + 1, nr, int(Ns))
+
+    def vh_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_vh_accumulate", walkers)
+
+    def vh_read(self, reset=None):
+        """dict of int64 arrays: self [W, Ntau+1, Ns], distinct [W, Ntau+1, Nr], samples [W] (profiles.normalize_vh turns
+        them into G_s and G_d).  reset: None, True (all walkers) or a per-walker mask of walkers whose counts are zeroed
+        after the copy."""
+        shp = getattr(self, "_vh_shape", None)
+        if shp is None:
+            raise PigsError("vh_read: vh_init first")
+        W = self.n_walkers
+        out = {"self": np.zeros((W, shp[0], shp[2]), np.int64), "distinct": np.zeros((W, shp[0], shp[1]), np.int64),
+               "samples": np.zeros(W, np.int64)}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_vh_read(self.h, *(_l(out[k]) for k in ("self", "distinct", "samples")), mask), "pigs_vh_read")
         return out
 
     # ---- K5

@@ -248,6 +248,13 @@ struct pigs_ctx {
     int         bop_nh = 0;                 // 0: pigs_bop_init not called yet
     int         bop_nr = 0, bop_window = 0, bop_slots = 0;
     double      bop_rnb2 = 0.0, bop_rbin = 0.0;
+    // van Hove functions over a slice window (pigs_vh_*): per-walker 64-bit counts, self [walker][Ntau+1][Ns] and dist
+    // [walker][Ntau+1][Nr], and the samples per walker
+    DevBuf<unsigned long long> d_vh_self, d_vh_dist, d_vh_samples;
+    int         vh_nr = 0;                  // 0: pigs_vh_init not called yet
+    int         vh_ns = 0, vh_ntau = 0, vh_window = 0;
+    int         vh_form = -1;               // tuning key "vh_form": -1 automatic, 0 global atomics, 1 histograms privatised in LDS
+    double      vh_rbin = 0.0, vh_sbin = 0.0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -377,7 +384,10 @@ int pigs_ctx_create(const pigs_params *p, const double *VTable, const double *Lo
     memcpy(&img[2], VTable, tb);
     HIPCHK(c->d_VTimg.alloc(img.size()));
     HIPCHK(hipMemcpy(c->d_VTimg.p, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(c->d_paths.p, 0, np * sizeof(double)));
+    // on the context's own stream, and waited for: that stream is non-blocking, so a fill on the default stream is not
+    // ordered against the first upload, which could then be overwritten with zeros in part
+    HIPCHK(hipMemsetAsync(c->d_paths.p, 0, np * sizeof(double), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     c->n_cu = device_cus();                     // (the context's device is current since hipSetDevice above)
     g_live_ctx[device_id & 63].fetch_add(1);
     *out = c.release();
@@ -456,6 +466,11 @@ int pigs_set_tuning(pigs_ctx *c, const char *key, int32_t value)
     }
     if (!strcmp(key, "cm_exclusive")) {         // 1: other contexts of this process on the device are idle while this one samples
         c->cm_exclusive = value != 0;           // (bench.py's extra legs next to its main context): cooperating workgroups allowed
+        return PIGS_OK;
+    }
+    if (!strcmp(key, "vh_form")) {              // histograms of pigs_vh_accumulate: -1 automatic, 0 global atomics, 1 privatised in LDS
+        if (value < -1 || value > 1) return fail(PIGS_ERR_ARG, "vh_form=%d", value);
+        c->vh_form = value;
         return PIGS_OK;
     }
     if (!strcmp(key, "grv_form")) {             // vector grid of pigs_grv_accumulate: -1 automatic, 0 global atomics, 1 privatised in LDS
@@ -1351,7 +1366,7 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     return PIGS_OK;
 }
 
-// ---- what the eight per-walker accumulator families below share ----------------------------------
+// ---- what the nine per-walker accumulator families below share ----------------------------------
 extern "C++" {      // templates
 
 // *_init, once the request is accepted: no accumulate may be in flight on the buffers being replaced, and until the new
@@ -1892,6 +1907,67 @@ int pigs_bop_read(pigs_ctx *c, double *S, int64_t *H, double *G, int64_t *GN, in
     const size_t nr = (size_t)c->bop_nr;
     return read_and_reset(c, {{c->d_bop_S.p, 8, S}, {c->d_bop_H.p, (size_t)2 * c->bop_nh, H}, {c->d_bop_G.p, nr, G},
                               {c->d_bop_GN.p, nr, GN}, {c->d_bop_samples.p, 1, samples}}, reset);
+}
+
+// ---- van Hove functions G_s(r,tau), G_d(r,tau) of a periodic system over a slice window -----------
+// Integer counts per walker and lag (pigs_vh.hip), accumulated on the device and read per block.
+int pigs_vh_init(pigs_ctx *c, int32_t Ntau, int32_t window, int32_t Nr, double rbin, int32_t Ns, double sbin)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the van Hove functions are defined for periodic systems only (their displacements are minimum images)");
+    if (Nr < 1 || Ns < 1 || !(rbin > 0.0) || !std::isfinite(rbin) || !(sbin > 0.0) || !std::isfinite(sbin) || window < 0 ||
+        window > c->P.Nb || Ntau < 0 || Ntau > 2 * window)
+        return fail(PIGS_ERR_ARG, "pigs_vh_init: Ntau=%d (0..2 window) window=%d (0..Nb=%d) Nr=%d rbin=%g Ns=%d sbin=%g", Ntau, window,
+                    c->P.Nb, Nr, rbin, Ns, sbin);
+    const size_t W = (size_t)c->n_walkers, nl = (size_t)Ntau + 1;
+    if ((double)W * ((double)nl * ((double)Nr + (double)Ns) + 1.0) * 8.0 > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_vh_init: %zu walkers x (%zu x (%d + %d) + 1) counters pass 2 GiB", W, nl, Nr, Ns);
+    if (!vh_shape(c->P.dim, c->P.Np, Ntau, Nr, Ns, 0).slice_fits)
+        return fail(PIGS_ERR_ARG, "pigs_vh_init: a slice of Np=%d particles in %dD needs %zu bytes of LDS (%zu at most)", c->P.Np,
+                    c->P.dim, sizeof(double) * (size_t)c->P.dim * (size_t)c->P.Np, kVhLdsBudget);
+    rc = init_begin(c, c->vh_nr); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_vh_self, W * nl * Ns));
+    HIPCHK(alloc_zeroed(c, c->d_vh_dist, W * nl * Nr));
+    HIPCHK(alloc_zeroed(c, c->d_vh_samples, W));
+    SYNC_CHECKED(c);
+    c->vh_nr = Nr;
+    c->vh_ns = Ns;
+    c->vh_ntau = Ntau;
+    c->vh_window = window;
+    c->vh_rbin = rbin;
+    c->vh_sbin = sbin;
+    return PIGS_OK;
+}
+
+int pigs_vh_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->vh_nr) return fail(PIGS_ERR_ARG, "pigs_vh_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    // a forced LDS form that does not fit is refused before anything is queued
+    const VhShape sh = vh_shape(c->P.dim, c->P.Np, c->vh_ntau, c->vh_nr, c->vh_ns, c->vh_form);
+    if (sh.hist_lds && !sh.hist_fits)
+        return fail(PIGS_ERR_ARG, "pigs_vh_accumulate: vh_form = 1, but %d x (%d + %d) counters do not fit the LDS beside the slice",
+                    c->vh_ntau + 1, c->vh_nr, c->vh_ns);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // integer atomics: a walker may appear twice in one launch
+    return each_launch(c, sw, walkers, false, kWalkerListMax, "launch_vh", [&](int m, const WalkerList &L) {
+        return launch_vh(c->P, c->d_paths.p, m, L, sh, c->vh_window, c->vh_ntau, c->vh_nr, c->vh_rbin, c->vh_ns, c->vh_sbin,
+                         c->d_vh_self.p, c->d_vh_dist.p, c->d_vh_samples.p, c->stream);
+    });
+}
+
+int pigs_vh_read(pigs_ctx *c, int64_t *self, int64_t *dist, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->vh_nr) return fail(PIGS_ERR_ARG, "pigs_vh_init first");
+    if (!self || !dist || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t nl = (size_t)c->vh_ntau + 1;
+    return read_and_reset(c, {{c->d_vh_self.p, nl * c->vh_ns, self}, {c->d_vh_dist.p, nl * c->vh_nr, dist},
+                              {c->d_vh_samples.p, 1, samples}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

@@ -148,6 +148,21 @@ hipError_t launch_bop(const DevParams &P, const double *paths, int n, const Walk
                       double rnb2, double rbin, double *scratch, double *S, unsigned long long *hist, double *G,
                       unsigned long long *gn, unsigned long long *samples, hipStream_t st);
 
+// pigs_vh.hip: the van Hove functions over the window slices (pigs_vh_accumulate): 64-bit counts per walker and lag,
+// self [walker][Ntau + 1][Ns] and dist [walker][Ntau + 1][Nr].  k_vh, one workgroup per (listed walker, base slice), holds
+// the base slice in LDS and walks the particles of the slices a + l against it.  A walker may be listed twice in one
+// launch (integer atomics).  vh_shape decides the form: the histograms of all lags privatised in LDS as u32 (form 1, or
+// automatic wherever 8 dim Np + 4 (Ntau + 1)(Nr + Ns) <= kVhLdsBudget), or global u64 atomics (form 0); the slice itself
+// always sits in LDS, 8 dim Np <= kVhLdsBudget, which pigs_vh_init checks.  hist_lds && !hist_fits is a forced LDS form
+// that does not fit, which the caller refuses.
+constexpr int kVhThreads = 256;                  // a power of two (the owner rounds split by powers of two)
+constexpr size_t kVhLdsBudget = 160 * 1024;      // LDS of one CU on gfx950
+struct VhShape { int slice_fits, hist_fits, hist_lds; size_t lds; };
+VhShape vh_shape(int dim, int Np, int Ntau, int Nr, int Ns, int form);
+hipError_t launch_vh(const DevParams &P, const double *paths, int n, const WalkerList &list, const VhShape &s, int window,
+                     int Ntau, int Nr, double rbin, int Ns, double sbin, unsigned long long *self, unsigned long long *dist,
+                     unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

@@ -582,6 +582,28 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_bop_read_t
+
+     ! van Hove functions over a slice window (include/pigs_hip.h, pigs_vh_*): looked up at run time, see vh_bind;
+     ! _accumulate has the signature of pigs_grv_accumulate
+     function pigs_vh_init_t(ctx,Ntau,window,Nr,rbin,Ns,sbin) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value        :: ctx
+       integer(c_int32_t), value :: Ntau,window,Nr
+       real(c_double), value     :: rbin
+       integer(c_int32_t), value :: Ns
+       real(c_double), value     :: sbin
+       integer(c_int) :: rc
+     end function pigs_vh_init_t
+
+     function pigs_vh_read_t(ctx,self,dist,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int64_t)             :: self(*)       ! counts (Ns,Ntau+1,n_walkers)
+       integer(c_int64_t)             :: dist(*)       ! counts (Nr,Ntau+1,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its counts after the copy
+       integer(c_int) :: rc
+     end function pigs_vh_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -629,6 +651,11 @@ module pigs_capi
   procedure(pigs_bop_init_t), pointer       :: bop_init => null()
   procedure(pigs_fqt_accumulate_t), pointer :: bop_accumulate => null()
   procedure(pigs_bop_read_t), pointer       :: bop_read => null()
+
+  ! bound by vh_bind (null until then)
+  procedure(pigs_vh_init_t), pointer        :: vh_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: vh_accumulate => null()
+  procedure(pigs_vh_read_t), pointer        :: vh_read => null()
 
 contains
 
@@ -749,6 +776,16 @@ contains
     call c_f_procpointer(f(2),bop_accumulate)
     call c_f_procpointer(f(3),bop_read)
   end function bop_bind
+
+  ! The van Hove entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function vh_bind()
+    type(c_funptr) :: f(3)
+    vh_bind = resolve_all('pigs_vh',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. vh_bind) return
+    call c_f_procpointer(f(1),vh_init)
+    call c_f_procpointer(f(2),vh_accumulate)
+    call c_f_procpointer(f(3),vh_read)
+  end function vh_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

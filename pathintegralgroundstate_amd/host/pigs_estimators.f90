@@ -19,6 +19,7 @@ module pigs_estimators
   public :: normalize_grv, write_grvec
   public :: normalize_tau, write_tau
   public :: normalize_bop, write_bo, write_boh
+  public :: normalize_vh, write_vh
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -620,6 +621,45 @@ contains
     grw = 2.d0*real(crad,8)
     call normalize_gr(p,density,int(S)*(2*window+1),grw)
   end subroutine normalize_grv
+
+  ! ---- van Hove functions over a slice window (counts of pigs_vh_read: lags 0..Ntau between the window slices
+  ! Nb-window..Nb+window; the distinct part on the radial grid of p (Nbin, rbin), the self part on that of ps) -> one
+  ! walker's block values with S samples.  Lag l has 2 window + 1 - l slice pairs, and both parts go through normalize_gr
+  ! with S (2 window + 1 - l) of them: G_d = dist/(S n_pairs Np density dV), which at l = 0 is grw_vpi.out's g(r) (the
+  ! device counts the ordered pairs i /= j, twice the pairs i < j), and G_s = self/(S n_pairs Np dV), density 1.
+  subroutine normalize_vh(p,ps,density,window,S,Ntau,cself,cdist,gs,gd)
+    type(est_params), intent(in) :: p,ps
+    real(8), intent(in)    :: density
+    integer, intent(in)    :: window,Ntau
+    integer(8), intent(in) :: S,cself(ps%Nbin,0:Ntau),cdist(p%Nbin,0:Ntau)
+    real(8), intent(out)   :: gs(ps%Nbin,0:Ntau),gd(p%Nbin,0:Ntau)
+    integer :: l
+    gd = real(cdist,8)
+    gs = real(cself,8)
+    do l=0,Ntau
+       call normalize_gr(p,density,int(S)*(2*window+1-l),gd(:,l))
+       call normalize_gr(ps,1.d0,int(S)*(2*window+1-l),gs(:,l))
+    end do
+  end subroutine normalize_vh
+
+  ! gd_vpi.out, gs_vpi.out: one line per (lag, bin), lags outermost: tau_l = l dt, r at the bin centre, G, error over the n blocks
+  subroutine write_vh(fname,p,dt,Ntau,n,av,av2)
+    character(len=*), intent(in) :: fname
+    type(est_params), intent(in) :: p
+    real(8), intent(in)    :: dt
+    integer, intent(in)    :: Ntau,n
+    real(8), intent(inout) :: av(p%Nbin,0:Ntau),av2(p%Nbin,0:Ntau)
+    integer :: j,l,u
+    open (newunit=u,file=fname)
+    av  = av/real(n)
+    av2 = av2/real(n)
+    do l=0,Ntau
+       do j=1,p%Nbin
+          write (u,'(20g20.10e3)') real(l,8)*dt,(real(j)-0.5d0)*p%rbin,av(j,l),variance(n,av(j,l),av2(j,l))
+       end do
+    end do
+    close (u)
+  end subroutine write_vh
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

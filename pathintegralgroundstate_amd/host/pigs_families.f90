@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -51,6 +51,9 @@ module pigs_families
      real(8) :: bo_rnb = 0.d0
      integer :: bo_nhist = 50, bo_nr = -1, bo_window = 0     ! bo_nr < 0: the run's g(r) grid
      real(8) :: half_side = 0.d0                    ! half the shortest side of a periodic box (what bo_rnb may not pass)
+     logical :: van_hove = .false.
+     integer :: vh_ntau = 0, vh_window = -1, vh_nself = 50
+     real(8) :: vh_rself = 0.d0                     ! <= 0: the run's rcut
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -295,16 +298,37 @@ module pigs_families
      procedure :: write_average => bop_write_average
   end type bop_family
 
-  integer, parameter :: NFAM = 8
+  ! van Hove functions: the block's counts from the device and the normalised block values G_s (self grid eps) and G_d
+  ! (the run's radial grid), per lag
+  type, extends(family) :: vh_family
+     integer :: ntau = 0, window = 0, ns = 0
+     type(est_params) :: eps
+     integer(c_int64_t), allocatable :: cself(:,:,:),cdist(:,:,:)
+     real(8), allocatable :: bs(:,:),bd(:,:)
+     type(block_series) :: sS,sD
+   contains
+     procedure :: check => vh_check
+     procedure :: banner => vh_banner
+     procedure :: setup => vh_setup
+     procedure :: queue => vh_queue
+     procedure :: read => vh_read_block
+     procedure :: block => vh_block
+     procedure :: average => vh_average
+     procedure :: write_walker => vh_write_walker
+     procedure :: write_average => vh_write_average
+  end type vh_family
+
+  integer, parameter :: NFAM = 9
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
-  ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order
+  ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
+  ! 9 van_hove
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -337,6 +361,7 @@ contains
     if (keys%tau_profile)     allocate (tau_family :: fs%slot(6)%f)
     if (keys%fq_self)         allocate (fs%slot(7)%f,source=fqs_family())
     if (keys%bond_order)      allocate (bop_family :: fs%slot(8)%f)
+    if (keys%van_hove)        allocate (vh_family :: fs%slot(9)%f)
   end subroutine set_create
 
   ! refuses what the keys cannot have (exit status 2) and fills in the windows that were left out
@@ -1319,5 +1344,108 @@ contains
     call write_boh('boh_vpi.out',f%nh,f%cnt%nav,f%sH%asum,f%sH%asq)
     call write_radial('g6_vpi.out',f%epr,f%cnt%nav,f%sG%asum,f%sG%asq)
   end subroutine bop_write_average
+
+  !---------------------------------------------------------------------
+  ! van_hove: the van Hove functions of a periodic system for the lags 0..vh_ntau between the slices
+  ! Nb-vh_window..Nb+vh_window -- gd_vpi.out (the distinct part on the run's own Nbin/rbin grid) and gs_vpi.out (the self
+  ! part on vh_nself bins over [0, vh_rself)), one line per (lag, bin): tau_l, r, G and its error
+
+  subroutine vh_check(f,keys,dim,Nb,trap)
+    class(vh_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('van_hove','its displacements are minimum images in the box')
+    if (keys%vh_nself<1) then
+       write (0,'(a,i0,a)') ' pigs_vpi: van_hove = T: vh_nself = ',keys%vh_nself,' must be at least 1'
+       stop 2
+    end if
+    if (.not. (keys%vh_rself<=huge(1.d0))) then
+       write (0,'(a,g0,a)') ' pigs_vpi: van_hove = T: vh_rself = ',keys%vh_rself,' must be finite (left out or <= 0: rcut)'
+       stop 2
+    end if
+    call check_lags('van_hove','vh',keys%vh_ntau,keys%vh_window,Nb)
+    if (.not. vh_bind()) call no_backend('van_hove','pigs_vh_init / _accumulate / _read','the van Hove functions run')
+  end subroutine vh_check
+
+  subroutine vh_banner(f,keys,trap)
+    class(vh_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,i0,a,i0,a,i0,a)', '  > Van Hove G_s, G_d   : on (lags 0..',keys%vh_ntau,', slices Nb-',keys%vh_window,'..Nb+',keys%vh_window, &
+         & ': gd_vpi.out, gs_vpi.out)'
+  end subroutine vh_banner
+
+  subroutine vh_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(vh_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%ntau = keys%vh_ntau; f%window = keys%vh_window; f%ns = keys%vh_nself
+    f%eps = ep
+    f%eps%Nbin = f%ns
+    f%eps%rbin = merge(keys%vh_rself,run%rcut,keys%vh_rself>0.d0)/real(f%ns,8)
+    call pigs_check(vh_init(ctx,int(f%ntau,c_int32_t),int(f%window,c_int32_t),int(ep%Nbin,c_int32_t),real(ep%rbin,c_double), &
+         & int(f%ns,c_int32_t),real(f%eps%rbin,c_double)),'pigs_vh_init')
+    allocate (f%cself(f%ns,0:f%ntau,NW),f%cdist(ep%Nbin,0:f%ntau,NW),f%bs(f%ns,0:f%ntau),f%bd(ep%Nbin,0:f%ntau))
+    call series_create(f%sS,f%ns*(f%ntau+1),NW,nvec)
+    call series_create(f%sD,ep%Nbin*(f%ntau+1),NW,nvec)
+    call count_create(f%cnt,nvec)
+  end subroutine vh_setup
+
+  subroutine vh_queue(f,ctx,nd,wl)
+    class(vh_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(vh_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_vh_accumulate')
+  end subroutine vh_queue
+
+  subroutine vh_read_block(f,ctx)
+    class(vh_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(vh_read(ctx,f%cself,f%cdist,f%smp,f%reset),'pigs_vh_read')
+  end subroutine vh_read_block
+
+  subroutine vh_block(f,w,info,vec)
+    class(vh_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_vh(f%ep,f%eps,f%run%density,f%window,int(f%smp(w),8),f%ntau,f%cself(:,:,w),f%cdist(:,:,w),f%bs,f%bd)
+    call series_add(f%sS,w,reshape(f%bs,[size(f%bs)]),vec)
+    call series_add(f%sD,w,reshape(f%bd,[size(f%bd)]),vec)
+    call count_add(f%cnt,vec)
+  end subroutine vh_block
+
+  subroutine vh_average(f,info,vec)
+    class(vh_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sS,vec,nall)
+       call series_average(f%sD,vec,nall)
+    end if
+  end subroutine vh_average
+
+  subroutine vh_write_walker(f,suffix,w,nblocks)
+    class(vh_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_vh('gd_vpi'//trim(suffix)//'.out',f%ep,f%run%dt,f%ntau,nblocks,f%sD%sum(:,w),f%sD%sq(:,w))
+    call write_vh('gs_vpi'//trim(suffix)//'.out',f%eps,f%run%dt,f%ntau,nblocks,f%sS%sum(:,w),f%sS%sq(:,w))
+  end subroutine vh_write_walker
+
+  subroutine vh_write_average(f)
+    class(vh_family), intent(inout) :: f
+    call write_vh('gd_vpi.out',f%ep,f%run%dt,f%ntau,f%cnt%nav,f%sD%asum,f%sD%asq)
+    call write_vh('gs_vpi.out',f%eps,f%run%dt,f%ntau,f%cnt%nav,f%sS%asum,f%sS%asq)
+  end subroutine vh_write_average
 
 end module pigs_families

@@ -9,6 +9,7 @@ module pigs_host_hooks
   use pigs_capi
   use pigs_rng
   use pigs_sampler
+  use pigs_estimators, only: est_params, normalize_vh, write_vh
 
   implicit none
   private
@@ -169,5 +170,45 @@ contains
        call mt_gauss(st,g(i))
     end do
   end subroutine hs_gauss_stream
+
+  ! The van Hove normalisation and writers of the front end on given counts: nb blocks of one walker, cself
+  ! (Ns,0:Ntau,nb), cdist (Nr,0:Ntau,nb) and S samples per block -> gs, gd of the LAST block, and the two files with the
+  ! mean and error over the blocks (names: C strings)
+  subroutine hs_vh_files(dim,Np,density,window,Ntau,Nr,rbin,Ns,sbin,dt,nb,S,cself,cdist,gs,gd,fd,fs) bind(C,name='hs_vh_files')
+    integer(c_int), value :: dim,Np,window,Ntau,Nr,Ns,nb
+    real(c_double), value :: density,rbin,sbin,dt
+    integer(c_int64_t), intent(in) :: S(nb),cself(Ns,0:Ntau,nb),cdist(Nr,0:Ntau,nb)
+    real(c_double), intent(out)    :: gs(Ns,0:Ntau),gd(Nr,0:Ntau)
+    character(kind=c_char), intent(in) :: fd(*),fs(*)
+    type(est_params) :: p,ps
+    real(8), allocatable :: ad(:,:),ad2(:,:),as(:,:),as2(:,:)
+    integer :: b
+    p%dim = dim; p%Np = Np; p%Nbin = Nr; p%rbin = rbin; p%pi = acos(-1.d0)
+    ps = p
+    ps%Nbin = Ns; ps%rbin = sbin
+    allocate (ad(Nr,0:Ntau),ad2(Nr,0:Ntau),as(Ns,0:Ntau),as2(Ns,0:Ntau))
+    ad = 0.d0; ad2 = 0.d0; as = 0.d0; as2 = 0.d0
+    do b=1,nb
+       call normalize_vh(p,ps,density,window,int(S(b),8),Ntau,cself(:,:,b),cdist(:,:,b),gs,gd)
+       ad = ad+gd; ad2 = ad2+gd*gd
+       as = as+gs; as2 = as2+gs*gs
+    end do
+    call write_vh(cname(fd),p,dt,Ntau,nb,ad,ad2)
+    call write_vh(cname(fs),ps,dt,Ntau,nb,as,as2)
+  contains
+    function cname(c) result(f)
+      character(kind=c_char), intent(in) :: c(*)
+      character(len=:), allocatable :: f
+      integer :: n,i
+      n = 0
+      do while (c(n+1)/=c_null_char)
+         n = n+1
+      end do
+      allocate (character(len=n) :: f)
+      do i=1,n
+         f(i:i) = c(i)
+      end do
+    end function cname
+  end subroutine hs_vh_files
 
 end module pigs_host_hooks

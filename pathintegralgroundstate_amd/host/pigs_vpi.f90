@@ -46,6 +46,12 @@
 ! coordination, each with its error (2D: Psi4, Psi6, |psi4(i)|, |psi6(i)|); boh_vpi.out, one line per bin of bo_nhist
 ! (default 50) over [0,1]: centre, P(q4), P(q6) with their errors; g6_vpi.out: r and G6(r) on bo_nr bins of width
 ! rcut/bo_nr (default: the run's Nbin and rbin) in gr_vpi.out's format, bins without pairs in a block counting as 0)
+! (van_hove = T, periodic systems only: the van Hove functions for the lags tau_l = l*dt, l = 0..vh_ntau, between the slices
+! Nb-vh_window..Nb+vh_window (vh_window left out: the smallest window that holds the lags), accumulated on the GPU --
+! gd_vpi.out: the distinct part G_d(r,tau), the histogram of |x_i(tau0+tau) - x_j(tau0)| over i /= j on the run's own
+! Nbin/rbin grid, normalised like gr_vpi.out (lag 0 IS g(r)); gs_vpi.out: the self part G_s(r,tau), the probability
+! density of the displacement |x_i(tau0+tau) - x_i(tau0)| on vh_nself bins (default 50) over [0, vh_rself) (default
+! rcut); both one line per (lag, bin): tau_l, r, G and its error)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -93,6 +99,9 @@ program pigs_vpi
   logical           :: bond_order
   real (kind=8)     :: bo_rnb
   integer           :: bo_nhist,bo_nr,bo_window
+  logical           :: van_hove
+  integer           :: vh_ntau,vh_window,vh_nself
+  real (kind=8)     :: vh_rself
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
   logical           :: sampler_auto
@@ -112,7 +121,8 @@ program pigs_vpi
        &             fq_vector,fqv_nmax,fqv_ntau,fqv_window, &
        &             tau_profile,tau_window, &
        &             fq_self,fqs_nmax,fqs_ntau,fqs_window, &
-       &             bond_order,bo_rnb,bo_nhist,bo_nr,bo_window
+       &             bond_order,bo_rnb,bo_nhist,bo_nr,bo_window, &
+       &             van_hove,vh_ntau,vh_window,vh_nself,vh_rself
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -142,6 +152,7 @@ program pigs_vpi
   tau_profile = .false.; tau_window = 0
   fq_self = .false.; fqs_nmax = 8; fqs_ntau = 0; fqs_window = -1
   bond_order = .false.; bo_rnb = 0.d0; bo_nhist = 50; bo_nr = -1; bo_window = 0
+  van_hove = .false.; vh_ntau = 0; vh_window = -1; vh_nself = 50; vh_rself = 0.d0
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -212,7 +223,8 @@ program pigs_vpi
        & sq_vector=sq_vector,sq_nmax=sq_nmax,sq_window=sq_window,gr_vector=gr_vector,gr_nbin=gr_nbin,gr_window=gr_window, &
        & fq_vector=fq_vector,fqv_nmax=fqv_nmax,fqv_ntau=fqv_ntau,fqv_window=fqv_window,tau_profile=tau_profile, &
        & tau_window=tau_window,fq_self=fq_self,fqs_nmax=fqs_nmax,fqs_ntau=fqs_ntau,fqs_window=fqs_window, &
-       & bond_order=bond_order,bo_rnb=bo_rnb,bo_nhist=bo_nhist,bo_nr=bo_nr,bo_window=bo_window,half_side=rcut)
+       & bond_order=bond_order,bo_rnb=bo_rnb,bo_nhist=bo_nhist,bo_nr=bo_nr,bo_window=bo_window,half_side=rcut, &
+       & van_hove=van_hove,vh_ntau=vh_ntau,vh_window=vh_window,vh_nself=vh_nself,vh_rself=vh_rself)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 

@@ -52,6 +52,12 @@ Bond-orientational order (normalize_bop, PigsContext.bop_read, pigs_bop_*): S ho
 q4(i), q6(i) in Nh bins over [0, 1]; G and GN the sums of c_ij and the pairs per radial bin:
   <Q_l> = S / (S_w * (2*window + 1)),  coordination = S[6] / (S_w * (2*window + 1) * Np),
   P(q_l) = H * Nh / (S_w * (2*window + 1) * Np),   G6(r_j) = G[j] / GN[j]   (S_w the walker's samples)
+
+Van Hove functions (normalize_vh, PigsContext.vh_read, pigs_vh_*): `distinct` counts |x_i(a+l) - x_j(a)| over the ordered
+pairs i != j and `self` counts |x_i(a+l) - x_i(a)|, per lag l = 0..Ntau, over the n_pairs(l) = 2*window + 1 - l slice pairs
+of the window; with dV_b the volume of the shell of bin b (radial grid Nr, rbin; self grid Ns, sbin):
+  G_d(r_b, tau_l) = distinct / (S_w * n_pairs(l) * Np * density * dV_b)     (g(r) at tau = 0; 1 - 1/Np for an ideal gas)
+  G_s(r_b, tau_l) = self / (S_w * n_pairs(l) * Np * dV_b)                   (a probability density: sum_b G_s dV_b = 1)
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -265,6 +271,31 @@ def normalize_bop(raw, Np, window, rbin=None):
            "q": (np.arange(Nh, dtype=np.float64) + 0.5) / float(Nh), "G6": G6}
     if rbin is not None:
         out["r"] = (np.arange(1, Nr + 1, dtype=np.float64) - 0.5) * rbin
+    return out
+
+
+def normalize_vh(counts, Np, window, density, rbin, sbin, dim, dt=None):
+    """counts: the dict of vh_read (self [W, Ntau+1, Ns], distinct [W, Ntau+1, Nr], samples [W]) or one walker's slice
+    of it.  Returns a dict: G_d (same shape as distinct) with its bin centres r, G_s (same shape as self) with its bin
+    centres rs, the slice pairs n_pairs [Ntau+1] and, where dt is given, tau [Ntau+1] = l*dt.  The shell volumes are the
+    reference's (NormAvGr), so the lag 0 of G_d is normalize_grv's g_r.  A walker without samples gives NaN."""
+    dist = np.asarray(counts["distinct"], dtype=np.float64)
+    slf = np.asarray(counts["self"], dtype=np.float64)
+    S = np.asarray(counts["samples"], dtype=np.float64)
+    nl, Nr, Ns = dist.shape[-2], dist.shape[-1], slf.shape[-1]
+    if slf.shape[-2] != nl or nl > 2 * window + 1:
+        raise ValueError("self and distinct must have the same lags, at most 2*window + 1 of them")
+    n_pairs = 2.0 * window + 1.0 - np.arange(nl, dtype=np.float64)
+    r = (np.arange(1, Nr + 1, dtype=np.float64) - 0.5) * rbin
+    rs = (np.arange(1, Ns + 1, dtype=np.float64) - 0.5) * sbin
+    kn = unit_ball(dim)
+    nid = density * kn * ((r + 0.5 * rbin) ** dim - (r - 0.5 * rbin) ** dim)
+    dv = 1.0 * kn * ((rs + 0.5 * sbin) ** dim - (rs - 0.5 * sbin) ** dim)
+    norm = S.reshape(S.shape + (1, 1)) * n_pairs[:, None] * float(Np)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = {"G_d": dist / (nid * norm), "r": r, "G_s": slf / (dv * norm), "rs": rs, "n_pairs": n_pairs}
+    if dt is not None:
+        out["tau"] = np.arange(nl, dtype=np.float64) * dt
     return out
 
 
