@@ -539,6 +539,61 @@ int pigs_vh_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_vh_init. */
 int pigs_vh_read(pigs_ctx *ctx, int64_t *self, int64_t *dist, int64_t *samples, const int32_t *reset);
 
+/* ---- the triplet distribution g3(r, s, cos theta) of a PERIODIC system in 2D or 3D, over a slice window (new: every
+ * family above comes from pair visits; this is the first three-body correlation: the Kirkwood superposition test, and in
+ * its first-shell section the bond-angle distribution P(cos theta)) ------------------------------------------------------
+ * Scope: periodic contexts with dim = 2 or 3.
+ * Parameters: Nr, rbin: the radial grid, the radius is rmax = Nr rbin.  Na: the number of bins of cos theta on [-1, 1].
+ * window: slices a = Nb-window .. Nb+window.
+ * For every listed walker w, every window slice a and every vertex i:
+ * - Legs.  For each j != i take d_k(j) = x_k(i,a) - x_k(j,a), folded once by min_image<DIM> (the two compares against
+ *   LboxHalf).  r2(j) is the sum of the squares, left to right, with nothing fused.  s(j) = sqrt(r2(j)) and
+ *   u(j) = s(j)/rbin.  j is a leg of i iff 0 < r2(j) and u(j) < Nr both hold in double.  So a coincident partner, a partner
+ *   at exactly rmax, and a NaN or +-Inf are not legs.  Its radial bin is b(j) = (int)u(j).  Every leg adds +1 to
+ *   pair[w][b(j)].  These are ordered pairs, so each pair is counted from both ends.
+ * - Triplets.  For every unordered pair {j,k} of legs of i take dot = d_1(j) d_1(k) + ... + d_DIM(j) d_DIM(k), products
+ *   summed left to right and unfused.  Take c = dot / (s(j) s(k)) and v = (c + 1.0) (0.5 Na).  If v is NaN the triplet is
+ *   dropped.  Otherwise the angle bin is q = v < 0 ? 0 : min((int)v, Na-1) (v >= Na, +Inf included, gives Na-1 without a
+ *   conversion).  This clamps c rounded past +-1 and keeps collinear triplets.  With lo = min(b(j),b(k)) and
+ *   hi = max(b(j),b(k)), add +1 to trip[w][p][q], where p = lo Nr - lo(lo-1)/2 + (hi - lo) indexes the packed upper
+ *   triangle of Nr(Nr+1)/2 leg pairs.  Every operation commutes in (j,k), so the count does not depend on the order in
+ *   which a pair of legs is met.
+ * - Samples.  samples[w] gains 1 per call and listed walker.
+ * Accumulators: 64-bit integers per walker; trip is [n_walkers][Nr(Nr+1)/2][Na], pair is [n_walkers][Nr], samples is
+ * [n_walkers].  Integer atomics only: the result depends on neither the walker list, its order, the split at 256 walkers
+ * per launch, the kernel form nor the context.
+ * Normalisation, on the host (profiles.normalize_g3, pigs_estimators.f90).  S = samples (2 window + 1); vol(b) is the
+ * d-ball shell volume of bin b, as normalize_grv uses it:
+ *   g2(b)       = pair[b] / (S Np density vol(b))
+ *   g3(lo,hi,q) = trip / (S Np density^2 vol(lo) vol(hi) w(q) m),   m = 1 for lo < hi and 1/2 for lo = hi,
+ *   w(q) = 1/Na in 3D;  w(q) = (acos(c_q) - acos(c_{q+1}))/pi in 2D, with c_q = -1 + 2q/Na.
+ * An uncorrelated system gives 1 up to O(1/Np).
+ * Kernel forms and limits.  One workgroup of 4 waves holds a slice in LDS, 8 dim Np bytes, and each wave a list of the
+ * legs of its vertex with room for all Np - 1 partners, 8 (dim + 1) + 4 bytes each: a list cannot overflow whatever the
+ * configuration.  pigs_g3_init refuses (PIGS_ERR_ARG) a system with
+ *   8 dim Np + 4 Np (8 (dim + 1) + 4) > 163840            (the 160 KiB of a CU: Np <= 975 in 3D, 1280 in 2D),
+ * so every Np <= 512 is served with rmax up to half the box.  The counters are privatised in LDS as u32 beside them where
+ *   8 dim Np + 4 Np (8 (dim + 1) + 4) + 4 (Nr(Nr+1)/2 Na + Nr) <= 163840   and   Np (Np-1)(Np-2)/2 <= 2^32 - 1,
+ * and take global u64 atomics otherwise (tuning key "g3_form": -1 automatic, 0 global atomics, 1 LDS; a forced LDS form
+ * that does not fit returns PIGS_ERR_ARG at the next accumulate and queues nothing).  A u32 counter belongs to one slice of
+ * one walker and gains at most one count per triplet of that slice before the workgroup's single flush; a slice has at most
+ * Np (Np-1)(Np-2)/2 triplets (and Np (Np-1) ordered pairs, which is less from Np = 4 on), so under the second condition no
+ * u32 counter can wrap.  (The LDS limit above keeps Np far below the 2050 where it would first fail.)
+ *
+ * pigs_g3_init allocates and zeroes the counts (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context
+ * or dim = 1; PIGS_ERR_ARG for Nr < 1 or Na < 1, Nr or Na > 1024, rbin not finite and positive, rmax beyond half the
+ * shortest side (as pigs_bop_init treats rnb; Nr rbin may pass it by 4 ulps, so that rbin = half / Nr is always taken), window < 0 or window > Nb, accumulators larger than 2 GiB in total, or the
+ * size limit above. */
+int pigs_g3_init(pigs_ctx *ctx, int32_t Nr, double rbin, int32_t Na, int32_t window);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_g3_init, for n < 0 or for a walker out of range. */
+int pigs_g3_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' counts trip[n_walkers][Nr(Nr+1)/2][Na], pair[n_walkers][Nr] and samples[n_walkers]; then zeroes those of
+ * the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_g3_init. */
+int pigs_g3_read(pigs_ctx *ctx, int64_t *trip, int64_t *pair, int64_t *samples, const int32_t *reset);
+
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
  * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for

@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "pigs_tau_init", "pigs_tau_accumulate", "pigs_tau_read",
     "pigs_bop_init", "pigs_bop_accumulate", "pigs_bop_read",
     "pigs_vh_init", "pigs_vh_accumulate", "pigs_vh_read",
+    "pigs_g3_init", "pigs_g3_accumulate", "pigs_g3_read",
 ]
 
 
@@ -165,6 +166,9 @@ def load_library(path=LIB_PATH):
     L.pigs_vh_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double]
     L.pigs_vh_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_vh_read.argtypes = [vp, _lp, _lp, _lp, _ip]
+    L.pigs_g3_init.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32]
+    L.pigs_g3_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_g3_read.argtypes = [vp, _lp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -735,6 +739,32 @@ class PigsContext:
                "samples": np.zeros(W, np.int64)}
         mask = self._reset_mask(reset)
         _chk(self.L, self.L.pigs_vh_read(self.h, *(_l(out[k]) for k in ("self", "distinct", "samples")), mask), "pigs_vh_read")
+        return out
+
+    # ---- triplet distribution over a slice window (pigs_g3_*: 64-bit counts per walker)
+    def g3_init(self, Nr, rbin, Na, window=0):
+        """Allocate and zero the counts of the triplet distribution over the slices Nb-window..Nb+window of a periodic 2D
+        or 3D system: legs within rmax = Nr*rbin (at most half the shortest side) on Nr radial bins, the angle between two
+        legs of a vertex on Na bins of cos(theta) over [-1, 1].  Calling it again resizes and zeroes."""
+        _chk(self.L, self.L.pigs_g3_init(self.h, int(Nr), float(rbin), int(Na), int(window)), "pigs_g3_init")
+        self._g3_shape = (int(Nr) * (int(Nr) + 1) // 2, int(Na), int(Nr))
+
+    def g3_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_g3_accumulate", walkers)
+
+    def g3_read(self, reset=None):
+        """dict of int64 arrays: trip [W, Nr(Nr+1)/2, Na] on the packed upper triangle of leg-bin pairs (lo <= hi at
+        lo*Nr - lo*(lo-1)/2 + hi - lo), pair [W, Nr], samples [W] (profiles.normalize_g3 turns them into g2 and g3).
+        reset: None, True (all walkers) or a per-walker mask of walkers whose counts are zeroed after the copy."""
+        shp = getattr(self, "_g3_shape", None)
+        if shp is None:
+            raise PigsError("g3_read: g3_init first")
+        W = self.n_walkers
+        out = {"trip": np.zeros((W, shp[0], shp[1]), np.int64), "pair": np.zeros((W, shp[2]), np.int64),
+               "samples": np.zeros(W, np.int64)}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_g3_read(self.h, *(_l(out[k]) for k in ("trip", "pair", "samples")), mask), "pigs_g3_read")
         return out
 
     # ---- K5

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -255,6 +256,13 @@ struct pigs_ctx {
     int         vh_ns = 0, vh_ntau = 0, vh_window = 0;
     int         vh_form = -1;               // tuning key "vh_form": -1 automatic, 0 global atomics, 1 histograms privatised in LDS
     double      vh_rbin = 0.0, vh_sbin = 0.0;
+    // triplet distribution over a slice window (pigs_g3_*): per-walker 64-bit counts, trip [walker][Nr (Nr + 1) / 2][Na] and
+    // pair [walker][Nr], and the samples per walker
+    DevBuf<unsigned long long> d_g3_trip, d_g3_pair, d_g3_samples;
+    int         g3_nr = 0;                  // 0: pigs_g3_init not called yet
+    int         g3_na = 0, g3_window = 0;
+    int         g3_form = -1;               // tuning key "g3_form": -1 automatic, 0 global atomics, 1 counters privatised in LDS
+    double      g3_rbin = 0.0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -471,6 +479,11 @@ int pigs_set_tuning(pigs_ctx *c, const char *key, int32_t value)
     if (!strcmp(key, "vh_form")) {              // histograms of pigs_vh_accumulate: -1 automatic, 0 global atomics, 1 privatised in LDS
         if (value < -1 || value > 1) return fail(PIGS_ERR_ARG, "vh_form=%d", value);
         c->vh_form = value;
+        return PIGS_OK;
+    }
+    if (!strcmp(key, "g3_form")) {              // counters of pigs_g3_accumulate: -1 automatic, 0 global atomics, 1 privatised in LDS
+        if (value < -1 || value > 1) return fail(PIGS_ERR_ARG, "g3_form=%d", value);
+        c->g3_form = value;
         return PIGS_OK;
     }
     if (!strcmp(key, "grv_form")) {             // vector grid of pigs_grv_accumulate: -1 automatic, 0 global atomics, 1 privatised in LDS
@@ -1366,7 +1379,7 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     return PIGS_OK;
 }
 
-// ---- what the nine per-walker accumulator families below share ----------------------------------
+// ---- what the ten per-walker accumulator families below share ----------------------------------
 extern "C++" {      // templates
 
 // *_init, once the request is accepted: no accumulate may be in flight on the buffers being replaced, and until the new
@@ -1968,6 +1981,72 @@ int pigs_vh_read(pigs_ctx *c, int64_t *self, int64_t *dist, int64_t *samples, co
     const size_t nl = (size_t)c->vh_ntau + 1;
     return read_and_reset(c, {{c->d_vh_self.p, nl * c->vh_ns, self}, {c->d_vh_dist.p, nl * c->vh_nr, dist},
                               {c->d_vh_samples.p, 1, samples}}, reset);
+}
+
+// ---- triplet distribution g3(r, s, cos theta) of a periodic system over a slice window ------------
+// Integer counts per walker (pigs_g3.hip), accumulated on the device and read per block.
+int pigs_g3_init(pigs_ctx *c, int32_t Nr, double rbin, int32_t Na, int32_t window)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the triplet distribution is defined for periodic systems only (its legs are minimum images)");
+    if (c->P.dim < 2) return fail(PIGS_ERR_UNSUPPORTED, "the triplet distribution is defined in 2D and 3D only");
+    if (Nr < 1 || Nr > kG3GridMax || Na < 1 || Na > kG3GridMax || !(rbin > 0.0) || !std::isfinite(rbin) || window < 0 ||
+        window > c->P.Nb)
+        return fail(PIGS_ERR_ARG, "pigs_g3_init: Nr=%d Na=%d (1..%d) rbin=%g window=%d (0..Nb=%d)", Nr, Na, kG3GridMax, rbin, window,
+                    c->P.Nb);
+    // rbin = (half a side) / Nr is the natural call, and Nr rbin may then round a few ulps past the half side
+    const double rmax = (double)Nr * rbin;
+    bool rmax_ok = std::isfinite(rmax);
+    for (int k = 0; k < c->P.dim; ++k) rmax_ok = rmax_ok && rmax <= c->P.LboxHalf[k] * (1.0 + 4.0 * DBL_EPSILON);
+    if (!rmax_ok) return fail(PIGS_ERR_ARG, "pigs_g3_init: rmax = Nr rbin = %g (0 < rmax <= half the shortest side)", rmax);
+    const size_t W = (size_t)c->n_walkers, ntrip = (size_t)Nr * ((size_t)Nr + 1) / 2 * (size_t)Na;
+    if ((double)W * ((double)ntrip + (double)Nr + 1.0) * 8.0 > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_g3_init: %zu walkers x (%zu + %d + 1) counters pass 2 GiB", W, ntrip, Nr);
+    const G3Shape sh = g3_shape(c->P.dim, c->P.Np, Nr, Na, 0);
+    if (!sh.fits)
+        return fail(PIGS_ERR_ARG, "pigs_g3_init: a slice of Np=%d particles in %dD and its leg lists need %zu bytes of LDS (%zu at most)",
+                    c->P.Np, c->P.dim, sh.lds, kG3LdsBudget);
+    rc = init_begin(c, c->g3_nr); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_g3_trip, W * ntrip));
+    HIPCHK(alloc_zeroed(c, c->d_g3_pair, W * Nr));
+    HIPCHK(alloc_zeroed(c, c->d_g3_samples, W));
+    SYNC_CHECKED(c);
+    c->g3_nr = Nr;
+    c->g3_na = Na;
+    c->g3_window = window;
+    c->g3_rbin = rbin;
+    return PIGS_OK;
+}
+
+int pigs_g3_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->g3_nr) return fail(PIGS_ERR_ARG, "pigs_g3_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    // a forced LDS form that does not fit is refused before anything is queued
+    const G3Shape sh = g3_shape(c->P.dim, c->P.Np, c->g3_nr, c->g3_na, c->g3_form);
+    if (sh.hist_lds && !sh.hist_fits)
+        return fail(PIGS_ERR_ARG, "pigs_g3_accumulate: g3_form = 1, but %d x %d x %d / 2 counters do not fit the LDS beside the slice and the leg lists",
+                    c->g3_nr, c->g3_nr + 1, c->g3_na);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // integer atomics: a walker may appear twice in one launch
+    return each_launch(c, sw, walkers, false, kWalkerListMax, "launch_g3", [&](int m, const WalkerList &L) {
+        return launch_g3(c->P, c->d_paths.p, m, L, sh, c->g3_window, c->g3_nr, c->g3_rbin, c->g3_na, c->d_g3_trip.p,
+                         c->d_g3_pair.p, c->d_g3_samples.p, c->stream);
+    });
+}
+
+int pigs_g3_read(pigs_ctx *c, int64_t *trip, int64_t *pair, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->g3_nr) return fail(PIGS_ERR_ARG, "pigs_g3_init first");
+    if (!trip || !pair || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t ntrip = (size_t)c->g3_nr * ((size_t)c->g3_nr + 1) / 2 * (size_t)c->g3_na;
+    return read_and_reset(c, {{c->d_g3_trip.p, ntrip, trip}, {c->d_g3_pair.p, (size_t)c->g3_nr, pair},
+                              {c->d_g3_samples.p, 1, samples}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

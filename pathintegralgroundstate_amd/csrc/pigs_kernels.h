@@ -163,6 +163,26 @@ hipError_t launch_vh(const DevParams &P, const double *paths, int n, const Walke
                      int Ntau, int Nr, double rbin, int Ns, double sbin, unsigned long long *self, unsigned long long *dist,
                      unsigned long long *samples, hipStream_t st);
 
+// pigs_g3.hip: the triplet distribution over the window slices (pigs_g3_accumulate): 64-bit counts per walker, trip
+// [walker][Nr (Nr + 1) / 2][Na] and pair [walker][Nr].  k_g3, one workgroup of kG3Waves waves per (listed walker, slice),
+// holds the slice in LDS; a wave owns a vertex, compacts its legs into a list of its own in LDS (capacity Np: a vertex
+// has at most Np - 1 legs) and shares the pairs of legs among its lanes.  A walker may be listed twice in one launch
+// (integer atomics).  g3_shape decides the form.  The slice and the lists always sit in LDS,
+//   8 dim Np + kG3Waves Np (8 (dim + 1) + 4) <= kG3LdsBudget         (fits; pigs_g3_init checks it),
+// and the counters are privatised beside them as u32 (form 1, or automatic) wherever
+//   that + 4 (Nr (Nr + 1) / 2 Na + Nr) <= kG3LdsBudget   and   Np (Np - 1)(Np - 2) / 2 <= 2^32 - 1   (hist_fits),
+// global u64 atomics otherwise (form 0).  hist_lds && !hist_fits is a forced LDS form that does not fit, which the
+// caller refuses.
+constexpr int kG3Waves = 4;
+constexpr int kG3Threads = kG3Waves * 64;
+constexpr int kG3GridMax = 1024;                 // Nr and Na at most
+constexpr size_t kG3LdsBudget = 160 * 1024;      // LDS of one CU on gfx950
+struct G3Shape { int fits, hist_fits, hist_lds, cap; size_t lds; };
+G3Shape g3_shape(int dim, int Np, int Nr, int Na, int form);
+hipError_t launch_g3(const DevParams &P, const double *paths, int n, const WalkerList &list, const G3Shape &s, int window,
+                     int Nr, double rbin, int Na, unsigned long long *trip, unsigned long long *pair,
+                     unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

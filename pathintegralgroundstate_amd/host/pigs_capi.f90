@@ -604,6 +604,27 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its counts after the copy
        integer(c_int) :: rc
      end function pigs_vh_read_t
+
+     ! triplet distribution over a slice window (include/pigs_hip.h, pigs_g3_*): looked up at run time, see g3_bind;
+     ! _accumulate has the signature of pigs_grv_accumulate
+     function pigs_g3_init_t(ctx,Nr,rbin,Na,window) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value        :: ctx
+       integer(c_int32_t), value :: Nr
+       real(c_double), value     :: rbin
+       integer(c_int32_t), value :: Na,window
+       integer(c_int) :: rc
+     end function pigs_g3_init_t
+
+     function pigs_g3_read_t(ctx,trip,pair,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int64_t)             :: trip(*)       ! counts (Na,Nr(Nr+1)/2,n_walkers)
+       integer(c_int64_t)             :: pair(*)       ! counts (Nr,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its counts after the copy
+       integer(c_int) :: rc
+     end function pigs_g3_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -656,6 +677,11 @@ module pigs_capi
   procedure(pigs_vh_init_t), pointer        :: vh_init => null()
   procedure(pigs_grv_accumulate_t), pointer :: vh_accumulate => null()
   procedure(pigs_vh_read_t), pointer        :: vh_read => null()
+
+  ! bound by g3_bind (null until then)
+  procedure(pigs_g3_init_t), pointer        :: g3_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: g3_accumulate => null()
+  procedure(pigs_g3_read_t), pointer        :: g3_read => null()
 
 contains
 
@@ -786,6 +812,16 @@ contains
     call c_f_procpointer(f(2),vh_accumulate)
     call c_f_procpointer(f(3),vh_read)
   end function vh_bind
+
+  ! The triplet entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function g3_bind()
+    type(c_funptr) :: f(3)
+    g3_bind = resolve_all('pigs_g3',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. g3_bind) return
+    call c_f_procpointer(f(1),g3_init)
+    call c_f_procpointer(f(2),g3_accumulate)
+    call c_f_procpointer(f(3),g3_read)
+  end function g3_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

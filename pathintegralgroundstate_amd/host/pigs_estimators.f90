@@ -20,6 +20,7 @@ module pigs_estimators
   public :: normalize_tau, write_tau
   public :: normalize_bop, write_bo, write_boh
   public :: normalize_vh, write_vh
+  public :: normalize_g3, write_g3, write_g3ang
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -660,6 +661,92 @@ contains
     end do
     close (u)
   end subroutine write_vh
+
+  ! ---- triplet distribution over a slice window (counts of pigs_g3_read on the radial grid of p, Nbin = Nr bins of rbin, and
+  ! Na bins of cos(theta) on [-1,1]; trip on the packed upper triangle of the leg bins lo <= hi, rows lo) -> one walker's
+  ! block values with S samples, St = S (2 window + 1), vol(b) the shell volume of normalize_gr:
+  !   g2(b)       = pair/(St Np density vol(b))
+  !   g3(q,lo,hi) = trip/(St Np density^2 vol(lo) vol(hi) w(q) m),  m = 1 for lo < hi and 1/2 for lo = hi,
+  !   w(q) = 1/Na in 3D and (acos(c_q) - acos(c_q+1))/pi in 2D, c_q = -1 + 2 q/Na
+  !   pang(q)     = P(cos theta) of all pairs of legs, normalised to integrate to 1 over [-1,1]; 0 without triplets
+  subroutine normalize_g3(p,density,window,S,Na,ctrip,cpair,g2,g3,pang)
+    type(est_params), intent(in) :: p
+    real(8), intent(in)    :: density
+    integer, intent(in)    :: window,Na
+    integer(8), intent(in) :: S,ctrip(Na,p%Nbin*(p%Nbin+1)/2),cpair(p%Nbin)
+    real(8), intent(out)   :: g2(p%Nbin),g3(Na,p%Nbin*(p%Nbin+1)/2),pang(Na)
+    real(8) :: kn,St,r,vol(p%Nbin),w(Na),m,tot,c0,c1
+    integer :: b,lo,hi,q,k
+    kn = unit_ball(p)
+    St = real(S,8)*real(2*window+1,8)
+    do b=1,p%Nbin
+       r      = (real(b,8)-0.5d0)*p%rbin
+       vol(b) = kn*((r+0.5d0*p%rbin)**p%dim-(r-0.5d0*p%rbin)**p%dim)
+       g2(b)  = real(cpair(b),8)/(St*real(p%Np,8)*density*vol(b))
+    end do
+    do q=1,Na
+       if (p%dim==3) then
+          w(q) = 1.d0/real(Na,8)
+       else
+          c0   = max(-1.d0,min(1.d0,-1.d0+2.d0*real(q-1,8)/real(Na,8)))
+          c1   = max(-1.d0,min(1.d0,-1.d0+2.d0*real(q,8)/real(Na,8)))
+          w(q) = (acos(c0)-acos(c1))/p%pi
+       end if
+    end do
+    k = 0
+    pang = 0.d0
+    do lo=1,p%Nbin
+       do hi=lo,p%Nbin
+          k = k+1
+          m = merge(0.5d0,1.d0,lo==hi)
+          do q=1,Na
+             g3(q,k) = real(ctrip(q,k),8)/(St*real(p%Np,8)*density**2*(vol(lo)*vol(hi)*m)*w(q))
+             pang(q) = pang(q)+real(ctrip(q,k),8)
+          end do
+       end do
+    end do
+    tot = sum(pang)*(2.d0/real(Na,8))
+    if (tot>0.d0) pang = pang/tot
+  end subroutine normalize_g3
+
+  ! g3_vpi.out: one line per (lo, hi, q), q fastest, in the packed order: r_lo, r_hi and cos(theta) at the bin centres, g3,
+  ! error over the n blocks
+  subroutine write_g3(fname,p,Na,n,av,av2)
+    character(len=*), intent(in) :: fname
+    type(est_params), intent(in) :: p
+    integer, intent(in)    :: Na,n
+    real(8), intent(inout) :: av(Na,p%Nbin*(p%Nbin+1)/2),av2(Na,p%Nbin*(p%Nbin+1)/2)
+    integer :: lo,hi,q,k,u
+    open (newunit=u,file=fname)
+    av  = av/real(n)
+    av2 = av2/real(n)
+    k = 0
+    do lo=1,p%Nbin
+       do hi=lo,p%Nbin
+          k = k+1
+          do q=1,Na
+             write (u,'(20g20.10e3)') (real(lo,8)-0.5d0)*p%rbin,(real(hi,8)-0.5d0)*p%rbin, &
+                  & -1.d0+(real(q,8)-0.5d0)*(2.d0/real(Na,8)),av(q,k),variance(n,av(q,k),av2(q,k))
+          end do
+       end do
+    end do
+    close (u)
+  end subroutine write_g3
+
+  ! g3ang_vpi.out: one line per bin of cos(theta): its centre, P(cos theta), error over the n blocks
+  subroutine write_g3ang(fname,Na,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: Na,n
+    real(8), intent(inout) :: av(Na),av2(Na)
+    integer :: q,u
+    open (newunit=u,file=fname)
+    av  = av/real(n)
+    av2 = av2/real(n)
+    do q=1,Na
+       write (u,'(20g20.10e3)') -1.d0+(real(q,8)-0.5d0)*(2.d0/real(Na,8)),av(q),variance(n,av(q),av2(q))
+    end do
+    close (u)
+  end subroutine write_g3ang
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order, van_hove.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove, triplet.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -54,6 +54,9 @@ module pigs_families
      logical :: van_hove = .false.
      integer :: vh_ntau = 0, vh_window = -1, vh_nself = 50
      real(8) :: vh_rself = 0.d0                     ! <= 0: the run's rcut
+     logical :: triplet = .false.
+     integer :: g3_nr = 10, g3_na = 20, g3_window = -1       ! g3_window < 0: slice Nb alone
+     real(8) :: g3_rmax = 0.d0                      ! <= 0: the run's rcut (half the shortest side)
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -318,17 +321,37 @@ module pigs_families
      procedure :: write_average => vh_write_average
   end type vh_family
 
-  integer, parameter :: NFAM = 9
+  ! triplet distribution: the block's counts from the device and the normalised block values g3 (packed triangle of leg
+  ! bins x angle bins, on the grid epr) and P(cos theta)
+  type, extends(family) :: g3_family
+     integer :: na = 0, window = 0, npk = 0
+     type(est_params) :: epr
+     integer(c_int64_t), allocatable :: ctrip(:,:,:),cpair(:,:)
+     real(8), allocatable :: b2(:),b3(:,:),ba(:)
+     type(block_series) :: s3,sA
+   contains
+     procedure :: check => g3_check
+     procedure :: banner => g3_banner
+     procedure :: setup => g3_setup
+     procedure :: queue => g3_queue
+     procedure :: read => g3_read_block
+     procedure :: block => g3_block
+     procedure :: average => g3_average
+     procedure :: write_walker => g3_write_walker
+     procedure :: write_average => g3_write_average
+  end type g3_family
+
+  integer, parameter :: NFAM = 10
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
   ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
-  ! 9 van_hove
+  ! 9 van_hove, 10 triplet
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -362,6 +385,7 @@ contains
     if (keys%fq_self)         allocate (fs%slot(7)%f,source=fqs_family())
     if (keys%bond_order)      allocate (bop_family :: fs%slot(8)%f)
     if (keys%van_hove)        allocate (vh_family :: fs%slot(9)%f)
+    if (keys%triplet)         allocate (g3_family :: fs%slot(10)%f)
   end subroutine set_create
 
   ! refuses what the keys cannot have (exit status 2) and fills in the windows that were left out
@@ -1447,5 +1471,120 @@ contains
     call write_vh('gd_vpi.out',f%ep,f%run%dt,f%ntau,f%cnt%nav,f%sD%asum,f%sD%asq)
     call write_vh('gs_vpi.out',f%eps,f%run%dt,f%ntau,f%cnt%nav,f%sS%asum,f%sS%asq)
   end subroutine vh_write_average
+
+  !---------------------------------------------------------------------
+  ! triplet: the triplet distribution of a periodic system in 2D or 3D over the slices Nb-g3_window..Nb+g3_window, legs
+  ! closer than g3_rmax on g3_nr radial bins, the angle between two legs on g3_na bins of cos(theta) -- g3_vpi.out (one line
+  ! per (lo, hi, q): r_lo, r_hi, cos(theta), g3 and its error) and g3ang_vpi.out (P(cos theta) of the legs below g3_rmax)
+
+  subroutine g3_check(f,keys,dim,Nb,trap)
+    class(g3_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('triplet','its legs are minimum images in the box')
+    if (dim<2) then
+       write (0,'(a,i0)') ' pigs_vpi: triplet = T needs dim = 2 or 3: there is no angle between two legs in dim = ',dim
+       stop 2
+    end if
+    if (keys%g3_nr<1 .or. keys%g3_nr>1024) then
+       write (0,'(a,i0,a)') ' pigs_vpi: triplet = T: g3_nr = ',keys%g3_nr,' must lie in 1 .. 1024'
+       stop 2
+    end if
+    if (keys%g3_na<1 .or. keys%g3_na>1024) then
+       write (0,'(a,i0,a)') ' pigs_vpi: triplet = T: g3_na = ',keys%g3_na,' must lie in 1 .. 1024'
+       stop 2
+    end if
+    if (.not. (keys%g3_rmax>0.d0)) keys%g3_rmax = keys%half_side        ! left out: the run's rcut
+    if (.not. (keys%g3_rmax<=keys%half_side)) then
+       write (0,'(a,g0,a,g0)') ' pigs_vpi: triplet = T: g3_rmax = ',keys%g3_rmax, &
+            & ' must be at most half the shortest side of the box = ',keys%half_side
+       stop 2
+    end if
+    if (keys%g3_window<0) keys%g3_window = 0
+    call check_window('triplet','g3',keys%g3_window,Nb)
+    if (.not. g3_bind()) call no_backend('triplet','pigs_g3_init / _accumulate / _read','the triplet distribution runs')
+  end subroutine g3_check
+
+  subroutine g3_banner(f,keys,trap)
+    class(g3_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,g0.6,a,i0,a,i0,a)', '  > Triplet g3          : on (legs below ',keys%g3_rmax,', slices Nb-',keys%g3_window,'..Nb+',keys%g3_window, &
+         & ': g3_vpi.out, g3ang_vpi.out)'
+  end subroutine g3_banner
+
+  subroutine g3_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(g3_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%na = keys%g3_na; f%window = keys%g3_window
+    f%epr = ep
+    f%epr%Nbin = keys%g3_nr
+    f%epr%rbin = merge(keys%g3_rmax,run%rcut,keys%g3_rmax>0.d0)/real(keys%g3_nr,8)
+    f%npk = keys%g3_nr*(keys%g3_nr+1)/2
+    call pigs_check(g3_init(ctx,int(f%epr%Nbin,c_int32_t),real(f%epr%rbin,c_double),int(f%na,c_int32_t),int(f%window,c_int32_t)), &
+         & 'pigs_g3_init')
+    allocate (f%ctrip(f%na,f%npk,NW),f%cpair(f%epr%Nbin,NW),f%b2(f%epr%Nbin),f%b3(f%na,f%npk),f%ba(f%na))
+    call series_create(f%s3,f%na*f%npk,NW,nvec)
+    call series_create(f%sA,f%na,NW,nvec)
+    call count_create(f%cnt,nvec)
+  end subroutine g3_setup
+
+  subroutine g3_queue(f,ctx,nd,wl)
+    class(g3_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(g3_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_g3_accumulate')
+  end subroutine g3_queue
+
+  subroutine g3_read_block(f,ctx)
+    class(g3_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(g3_read(ctx,f%ctrip,f%cpair,f%smp,f%reset),'pigs_g3_read')
+  end subroutine g3_read_block
+
+  subroutine g3_block(f,w,info,vec)
+    class(g3_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_g3(f%epr,f%run%density,f%window,int(f%smp(w),8),f%na,f%ctrip(:,:,w),f%cpair(:,w),f%b2,f%b3,f%ba)
+    call series_add(f%s3,w,reshape(f%b3,[size(f%b3)]),vec)
+    call series_add(f%sA,w,f%ba,vec)
+    call count_add(f%cnt,vec)
+  end subroutine g3_block
+
+  subroutine g3_average(f,info,vec)
+    class(g3_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%s3,vec,nall)
+       call series_average(f%sA,vec,nall)
+    end if
+  end subroutine g3_average
+
+  subroutine g3_write_walker(f,suffix,w,nblocks)
+    class(g3_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_g3('g3_vpi'//trim(suffix)//'.out',f%epr,f%na,nblocks,f%s3%sum(:,w),f%s3%sq(:,w))
+    call write_g3ang('g3ang_vpi'//trim(suffix)//'.out',f%na,nblocks,f%sA%sum(:,w),f%sA%sq(:,w))
+  end subroutine g3_write_walker
+
+  subroutine g3_write_average(f)
+    class(g3_family), intent(inout) :: f
+    call write_g3('g3_vpi.out',f%epr,f%na,f%cnt%nav,f%s3%asum,f%s3%asq)
+    call write_g3ang('g3ang_vpi.out',f%na,f%cnt%nav,f%sA%asum,f%sA%asq)
+  end subroutine g3_write_average
 
 end module pigs_families

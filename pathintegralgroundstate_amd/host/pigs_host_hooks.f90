@@ -9,7 +9,7 @@ module pigs_host_hooks
   use pigs_capi
   use pigs_rng
   use pigs_sampler
-  use pigs_estimators, only: est_params, normalize_vh, write_vh
+  use pigs_estimators, only: est_params, normalize_vh, write_vh, normalize_g3, write_g3, write_g3ang
 
   implicit none
   private
@@ -210,5 +210,44 @@ contains
       end do
     end function cname
   end subroutine hs_vh_files
+
+  ! The triplet normalisation and writers of the front end on given counts: nb blocks of one walker, ctrip
+  ! (Na,Nr(Nr+1)/2,nb), cpair (Nr,nb) and S samples per block -> g2, g3, pang of the LAST block, and the two files with the
+  ! mean and error over the blocks (names: C strings)
+  subroutine hs_g3_files(dim,Np,density,window,Nr,rbin,Na,nb,S,ctrip,cpair,g2,g3,pang,f3,fa) bind(C,name='hs_g3_files')
+    integer(c_int), value :: dim,Np,window,Nr,Na,nb
+    real(c_double), value :: density,rbin
+    integer(c_int64_t), intent(in) :: S(nb),ctrip(Na,Nr*(Nr+1)/2,nb),cpair(Nr,nb)
+    real(c_double), intent(out)    :: g2(Nr),g3(Na,Nr*(Nr+1)/2),pang(Na)
+    character(kind=c_char), intent(in) :: f3(*),fa(*)
+    type(est_params) :: p
+    real(8), allocatable :: a3(:,:),a32(:,:),aa(:),aa2(:)
+    integer :: b
+    p%dim = dim; p%Np = Np; p%Nbin = Nr; p%rbin = rbin; p%pi = acos(-1.d0)
+    allocate (a3(Na,Nr*(Nr+1)/2),a32(Na,Nr*(Nr+1)/2),aa(Na),aa2(Na))
+    a3 = 0.d0; a32 = 0.d0; aa = 0.d0; aa2 = 0.d0
+    do b=1,nb
+       call normalize_g3(p,density,window,int(S(b),8),Na,ctrip(:,:,b),cpair(:,b),g2,g3,pang)
+       a3 = a3+g3; a32 = a32+g3*g3
+       aa = aa+pang; aa2 = aa2+pang*pang
+    end do
+    call write_g3(cstring(f3),p,Na,nb,a3,a32)
+    call write_g3ang(cstring(fa),Na,nb,aa,aa2)
+  end subroutine hs_g3_files
+
+  ! a C string as a Fortran one
+  function cstring(c) result(f)
+    character(kind=c_char), intent(in) :: c(*)
+    character(len=:), allocatable :: f
+    integer :: n,i
+    n = 0
+    do while (c(n+1)/=c_null_char)
+       n = n+1
+    end do
+    allocate (character(len=n) :: f)
+    do i=1,n
+       f(i:i) = c(i)
+    end do
+  end function cstring
 
 end module pigs_host_hooks

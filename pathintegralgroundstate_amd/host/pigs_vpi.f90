@@ -52,6 +52,12 @@
 ! Nbin/rbin grid, normalised like gr_vpi.out (lag 0 IS g(r)); gs_vpi.out: the self part G_s(r,tau), the probability
 ! density of the displacement |x_i(tau0+tau) - x_i(tau0)| on vh_nself bins (default 50) over [0, vh_rself) (default
 ! rcut); both one line per (lag, bin): tau_l, r, G and its error)
+! (triplet = T, periodic systems in 2D and 3D only: the triplet distribution over the slices Nb-g3_window..Nb+g3_window
+! (default 0), accumulated on the GPU: for every vertex the pairs of its legs, the partners closer than g3_rmax (left out
+! or <= 0: rcut; at most half the shortest side), on g3_nr radial bins (default 10) and g3_na bins of cos(theta) (default
+! 20) -- g3_vpi.out, one line per (lo, hi, q) with the leg bins lo <= hi: r_lo, r_hi, cos(theta), g3 and its error,
+! normalised to 1 for an uncorrelated system; g3ang_vpi.out: cos(theta), the bond-angle distribution P(cos theta) of the
+! legs below g3_rmax, which integrates to 1, and its error)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -102,6 +108,9 @@ program pigs_vpi
   logical           :: van_hove
   integer           :: vh_ntau,vh_window,vh_nself
   real (kind=8)     :: vh_rself
+  logical           :: triplet
+  integer           :: g3_nr,g3_na,g3_window
+  real (kind=8)     :: g3_rmax
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
   logical           :: sampler_auto
@@ -122,7 +131,8 @@ program pigs_vpi
        &             tau_profile,tau_window, &
        &             fq_self,fqs_nmax,fqs_ntau,fqs_window, &
        &             bond_order,bo_rnb,bo_nhist,bo_nr,bo_window, &
-       &             van_hove,vh_ntau,vh_window,vh_nself,vh_rself
+       &             van_hove,vh_ntau,vh_window,vh_nself,vh_rself, &
+       &             triplet,g3_nr,g3_na,g3_rmax,g3_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -153,6 +163,7 @@ program pigs_vpi
   fq_self = .false.; fqs_nmax = 8; fqs_ntau = 0; fqs_window = -1
   bond_order = .false.; bo_rnb = 0.d0; bo_nhist = 50; bo_nr = -1; bo_window = 0
   van_hove = .false.; vh_ntau = 0; vh_window = -1; vh_nself = 50; vh_rself = 0.d0
+  triplet = .false.; g3_nr = 10; g3_na = 20; g3_rmax = 0.d0; g3_window = -1
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -224,7 +235,8 @@ program pigs_vpi
        & fq_vector=fq_vector,fqv_nmax=fqv_nmax,fqv_ntau=fqv_ntau,fqv_window=fqv_window,tau_profile=tau_profile, &
        & tau_window=tau_window,fq_self=fq_self,fqs_nmax=fqs_nmax,fqs_ntau=fqs_ntau,fqs_window=fqs_window, &
        & bond_order=bond_order,bo_rnb=bo_rnb,bo_nhist=bo_nhist,bo_nr=bo_nr,bo_window=bo_window,half_side=rcut, &
-       & van_hove=van_hove,vh_ntau=vh_ntau,vh_window=vh_window,vh_nself=vh_nself,vh_rself=vh_rself)
+       & van_hove=van_hove,vh_ntau=vh_ntau,vh_window=vh_window,vh_nself=vh_nself,vh_rself=vh_rself, &
+       & triplet=triplet,g3_nr=g3_nr,g3_na=g3_na,g3_rmax=g3_rmax,g3_window=g3_window)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 

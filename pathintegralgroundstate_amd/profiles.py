@@ -58,6 +58,14 @@ pairs i != j and `self` counts |x_i(a+l) - x_i(a)|, per lag l = 0..Ntau, over th
 of the window; with dV_b the volume of the shell of bin b (radial grid Nr, rbin; self grid Ns, sbin):
   G_d(r_b, tau_l) = distinct / (S_w * n_pairs(l) * Np * density * dV_b)     (g(r) at tau = 0; 1 - 1/Np for an ideal gas)
   G_s(r_b, tau_l) = self / (S_w * n_pairs(l) * Np * dV_b)                   (a probability density: sum_b G_s dV_b = 1)
+
+Triplet distribution (normalize_g3, PigsContext.g3_read, pigs_g3_*): `pair` counts the legs of every vertex per radial bin
+(ordered pairs) and `trip` the unordered pairs of legs of a vertex per (lo, hi, q): lo <= hi their radial bins, packed at
+p = lo*Nr - lo*(lo-1)/2 + hi - lo, and q the bin of cos(theta) on [-1, 1]; with S = S_w * (2*window + 1):
+  g2(b)         = pair / (S * Np * density * dV_b)
+  g3(lo, hi, q) = trip / (S * Np * density**2 * dV_lo * dV_hi * w_q * m),   m = 1 for lo < hi, 1/2 for lo = hi,
+  w_q = 1/Na in 3D, (acos(c_q) - acos(c_{q+1}))/pi in 2D with c_q = -1 + 2q/Na      (1 + O(1/Np) without correlations)
+bond_angle sums trip over the legs of the first bins into P(cos theta); kirkwood_g3 is g(r) g(s) g(t) on the same grid.
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -297,6 +305,98 @@ def normalize_vh(counts, Np, window, density, rbin, sbin, dim, dt=None):
     if dt is not None:
         out["tau"] = np.arange(nl, dtype=np.float64) * dt
     return out
+
+
+def g3_pairs(Nr):
+    """(lo, hi): the radial bins of the two legs at every index p of the packed upper triangle, p = lo*Nr - lo*(lo-1)/2 +
+    hi - lo (rows lo = 0..Nr-1, hi = lo..Nr-1 within a row)."""
+    lo, hi = np.triu_indices(int(Nr))
+    return lo, hi
+
+
+def g3_nr(npairs):
+    """Nr of a packed triangle of npairs = Nr*(Nr+1)/2 leg-bin pairs."""
+    Nr = (math.isqrt(8 * int(npairs) + 1) - 1) // 2
+    if Nr * (Nr + 1) // 2 != int(npairs):
+        raise ValueError("%d is not Nr*(Nr+1)/2" % npairs)
+    return Nr
+
+
+def unpack_g3(packed):
+    """[.., Nr*(Nr+1)/2, Na] on the packed triangle -> [.., Nr, Nr, Na], symmetric in the two legs (counts of a diagonal
+    bin lo = hi are not doubled)."""
+    a = np.asarray(packed)
+    Nr = g3_nr(a.shape[-2])
+    lo, hi = g3_pairs(Nr)
+    out = np.zeros(a.shape[:-2] + (Nr, Nr, a.shape[-1]), a.dtype)
+    out[..., lo, hi, :] = a
+    out[..., hi, lo, :] = a
+    return out
+
+
+def g3_angle_weights(Na, dim):
+    """w_q, q = 0..Na-1: the share of bin q of cos(theta) for two independent directions; sums to 1."""
+    if dim == 3:
+        return np.full(int(Na), 1.0 / float(Na))
+    if dim != 2:
+        raise ValueError("the triplet distribution is defined in 2D and 3D")
+    c = np.clip(-1.0 + 2.0 * np.arange(int(Na) + 1, dtype=np.float64) / float(Na), -1.0, 1.0)
+    return (np.arccos(c[:-1]) - np.arccos(c[1:])) / math.pi
+
+
+def normalize_g3(counts, Np, window, density, rbin, dim):
+    """counts: the dict of g3_read (trip [W, Nr(Nr+1)/2, Na], pair [W, Nr], samples [W]) or one walker's slice of it.
+    Returns a dict: r [Nr] and cos [Na] the bin mid-points, g2 (same shape as pair), g3 (same shape as trip, on the packed
+    triangle: unpack_g3 gives [.., Nr, Nr, Na]), lo and hi the leg bins of the packed index.  The shell volumes are
+    normalize_grv's.  A walker without samples gives NaN."""
+    trip = np.asarray(counts["trip"], dtype=np.float64)
+    pair = np.asarray(counts["pair"], dtype=np.float64)
+    S = np.asarray(counts["samples"], dtype=np.float64) * (2.0 * window + 1.0)
+    Nr, Na = pair.shape[-1], trip.shape[-1]
+    if trip.shape[-2] != Nr * (Nr + 1) // 2:
+        raise ValueError("trip must hold Nr*(Nr+1)/2 leg pairs")
+    r = (np.arange(1, Nr + 1, dtype=np.float64) - 0.5) * rbin
+    vol = unit_ball(dim) * ((r + 0.5 * rbin) ** dim - (r - 0.5 * rbin) ** dim)
+    lo, hi = g3_pairs(Nr)
+    m = np.where(lo == hi, 0.5, 1.0)
+    w = g3_angle_weights(Na, dim)
+    cosm = -1.0 + (np.arange(Na, dtype=np.float64) + 0.5) * (2.0 / float(Na))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g2 = pair / (S.reshape(S.shape + (1,)) * float(Np) * density * vol)
+        g3 = trip / (S.reshape(S.shape + (1, 1)) * float(Np) * density ** 2 * (vol[lo] * vol[hi] * m)[:, None] * w)
+    return {"r": r, "cos": cosm, "g2": g2, "g3": g3, "lo": lo, "hi": hi}
+
+
+def bond_angle(trip, nshell):
+    """P(cos theta) [.., Na] of the pairs of legs that both lie in the radial bins < nshell (trip: counts on the packed
+    triangle, [.., Nr(Nr+1)/2, Na]), normalised to integrate to 1 over cos(theta) in [-1, 1]; all zero where there is no
+    such triplet."""
+    a = np.asarray(trip, dtype=np.float64)
+    Nr, Na = g3_nr(a.shape[-2]), a.shape[-1]
+    if not 1 <= int(nshell) <= Nr:
+        raise ValueError("nshell must be 1..Nr")
+    _, hi = g3_pairs(Nr)
+    h = a[..., hi < int(nshell), :].sum(axis=-2)
+    tot = h.sum(axis=-1, keepdims=True) * (2.0 / float(Na))
+    return np.divide(h, tot, out=np.zeros_like(h), where=tot > 0)
+
+
+def kirkwood_g3(g2, rbin, Na):
+    """The Kirkwood superposition g(r) g(s) g(t) on normalize_g3's grid, [Nr(Nr+1)/2, Na] on the packed triangle, from one
+    g2 [Nr]: r, s and cos(theta) at the bin mid-points, t = sqrt(r^2 + s^2 - 2 r s cos(theta)) the third side, g(t) by
+    linear interpolation between the mid-points of g2 (its first value below the first mid-point, its last beyond the
+    last), NaN where t >= rmax = Nr*rbin."""
+    g = np.asarray(g2, dtype=np.float64)
+    if g.ndim != 1:
+        raise ValueError("kirkwood_g3 takes one g2 [Nr]")
+    Nr = g.shape[0]
+    r = (np.arange(Nr, dtype=np.float64) + 0.5) * rbin
+    c = -1.0 + (np.arange(int(Na), dtype=np.float64) + 0.5) * (2.0 / float(Na))
+    lo, hi = g3_pairs(Nr)
+    t2 = (r[lo] ** 2 + r[hi] ** 2)[:, None] - 2.0 * (r[lo] * r[hi])[:, None] * c
+    t = np.sqrt(np.maximum(t2, 0.0))
+    gt = np.interp(t, r, g)
+    return np.where(t < Nr * rbin, (g[lo] * g[hi])[:, None] * gt, np.nan)
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
