@@ -594,6 +594,59 @@ int pigs_g3_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_g3_init. */
 int pigs_g3_read(pigs_ctx *ctx, int64_t *trip, int64_t *pair, int64_t *samples, const int32_t *reset);
 
+/* ---- the Axilrod-Teller-Muto (triple-dipole) three-body energy <V3> of a PERIODIC system in 2D or 3D, over a slice window
+ * (new: the first three-body ENERGY; evaluated perturbatively on the configurations that the pair potential sampled) -------
+ * Scope: periodic contexts with dim = 2 or 3.
+ * Parameters: rc, the cutoff of every side of a triplet; window: slices a = Nb-window .. Nb+window.
+ * For a listed walker w and every window slice a = Nb-window .. Nb+window:
+ * 1. For each pair of particles, take the coordinate difference, fold it once by min_image<DIM>, and sum r^2 left to right.
+ *    This is pigs_grv_*'s arithmetic.
+ * 2. For every triplet i < j < k, let a2 = r^2(i,j), b2 = r^2(i,k), c2 = r^2(j,k).  Each pair is at its own nearest image.
+ * 3. The triplet counts if and only if  a2 <= rc2 && b2 <= rc2 && c2 <= rc2,  compared in double.  NaN compares false and
+ *    drops the triplet.  The host computes rc2 = rc*rc.
+ * 4. The triplet's term, with -ffp-contract=off, is exactly these operations in this order:
+ *      p   = (a2 * b2) * c2
+ *      s   = sqrt(p)
+ *      num = ((a2 + b2 - c2) * (a2 + c2 - b2)) * (b2 + c2 - a2)
+ *      t   = (p + 0.375 * num) / ((p * p) * s)
+ *    This equals (1 + 3 cos(gamma_i) cos(gamma_j) cos(gamma_k)) / (r_ij r_ik r_jk)^3.
+ * The term is a function of the three side lengths only.  It is therefore defined when the three nearest images do not
+ * close into a triangle, which can happen once rc > L/4 (three particles on a line at 0, 0.4 L and 0.8 L have the sides
+ * 0.4 L, 0.2 L and 0.4 L: the term is the isosceles triangle's, not a collinear one's).
+ * One accumulate call adds per (w, a):
+ *   T[w][a]     += sum of t, as a double
+ *   ntrip[w][a] += the number of counted triplets, as int64
+ *   samples[w]  += 1
+ * The coupling nu never reaches the device.  The estimators are the caller's divisions (profiles.normalize_atm,
+ * pigs_estimators.f90):
+ *   V3/N(tau_a) = nu T / (samples Np);   V3/N averages that over the window.
+ *   Pressure contribution P3 = 9 nu <T> / (dim Volume): the sum is homogeneous of degree -9.  It is cut at rc and has no
+ *   tail correction, which is the same policy as the pair virial.
+ * A coincident pair (p = 0) gives a non-finite term.  That term stays in its own (w, a) element, as in pigs_tau_*.
+ * Summation.  No floating-point atomics and one fixed order: per lane, then across the wave, then across the waves in wave
+ * order, then acc += value by the one thread that owns (w, a) in the launch.  The same worldline gives the same bits
+ * whatever the walker list, its order, the launch split or the number of walkers in the context; a walker listed twice
+ * counts twice (in two launches), with bits equal to 2 x one count.  An element of one term (Np = 3) has that term's bits.
+ * Limit.  One workgroup of 4 waves holds a slice in LDS, 8 dim Np bytes, and each wave a list of the legs of its vertex
+ * with room for all Np - 1 partners, 8 (dim + 1) bytes each (the partner's coordinates and a2): a list cannot overflow
+ * whatever the configuration.  pigs_atm_init refuses (PIGS_ERR_ARG) a system with
+ *   8 dim Np + 4 Np 8 (dim + 1) + 64 > 163840             (the 160 KiB of a CU: Np <= 1077 in 3D, 1462 in 2D),
+ * which serves every system that pigs_g3_init serves.
+ *
+ * pigs_atm_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context or
+ * dim = 1; PIGS_ERR_ARG unless rc is finite with 0 < rc <= half the shortest side and 0 <= window <= Nb, and for the size
+ * limit above. */
+int pigs_atm_init(pigs_ctx *ctx, double rc, int32_t window);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_atm_init, for n < 0 or for a walker out of range. */
+int pigs_atm_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' sums T[n_walkers][2 window + 1], counts ntrip[n_walkers][2 window + 1] and samples[n_walkers]; then zeroes
+ * those of the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before
+ * pigs_atm_init. */
+int pigs_atm_read(pigs_ctx *ctx, double *T, int64_t *ntrip, int64_t *samples, const int32_t *reset);
+
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
  * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for

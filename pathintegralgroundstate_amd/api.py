@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "pigs_bop_init", "pigs_bop_accumulate", "pigs_bop_read",
     "pigs_vh_init", "pigs_vh_accumulate", "pigs_vh_read",
     "pigs_g3_init", "pigs_g3_accumulate", "pigs_g3_read",
+    "pigs_atm_init", "pigs_atm_accumulate", "pigs_atm_read",
 ]
 
 
@@ -169,6 +170,9 @@ def load_library(path=LIB_PATH):
     L.pigs_g3_init.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32]
     L.pigs_g3_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_g3_read.argtypes = [vp, _lp, _lp, _lp, _ip]
+    L.pigs_atm_init.argtypes = [vp, C.c_double, C.c_int32]
+    L.pigs_atm_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_atm_read.argtypes = [vp, _dp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -765,6 +769,32 @@ class PigsContext:
                "samples": np.zeros(W, np.int64)}
         mask = self._reset_mask(reset)
         _chk(self.L, self.L.pigs_g3_read(self.h, *(_l(out[k]) for k in ("trip", "pair", "samples")), mask), "pigs_g3_read")
+        return out
+
+    # ---- Axilrod-Teller-Muto three-body sum over a slice window (pigs_atm_*: a double and a 64-bit count per walker and slice)
+    def atm_init(self, rc, window=0):
+        """Allocate and zero the three-body sums over the slices Nb-window..Nb+window of a periodic 2D or 3D system: the
+        triplets whose three nearest-image sides all lie within rc (at most half the shortest side).  Calling it again
+        resizes and zeroes."""
+        _chk(self.L, self.L.pigs_atm_init(self.h, float(rc), int(window)), "pigs_atm_init")
+        self._atm_ns = 2 * int(window) + 1
+
+    def atm_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_atm_accumulate", walkers)
+
+    def atm_read(self, reset=None):
+        """dict: T [W, 2 window + 1], the raw geometric sums of (1 + 3 cos cos cos)/(r r r)^3 (float64), ntrip, the
+        triplets counted, of the same shape (int64), and samples [W] (int64); profiles.normalize_atm multiplies by the
+        coupling and divides.  reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed
+        after the copy."""
+        ns = getattr(self, "_atm_ns", None)
+        if ns is None:
+            raise PigsError("atm_read: atm_init first")
+        W = self.n_walkers
+        out = {"T": np.zeros((W, ns)), "ntrip": np.zeros((W, ns), np.int64), "samples": np.zeros(W, np.int64)}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_atm_read(self.h, _d(out["T"]), _l(out["ntrip"]), _l(out["samples"]), mask), "pigs_atm_read")
         return out
 
     # ---- K5

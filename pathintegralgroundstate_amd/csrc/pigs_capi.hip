@@ -263,6 +263,13 @@ struct pigs_ctx {
     int         g3_na = 0, g3_window = 0;
     int         g3_form = -1;               // tuning key "g3_form": -1 automatic, 0 global atomics, 1 counters privatised in LDS
     double      g3_rbin = 0.0;
+    // Axilrod-Teller-Muto geometric sum over a slice window (pigs_atm_*): raw sums T [walker][2 window + 1], the triplets
+    // counted ntrip [walker][2 window + 1], and the samples per walker
+    DevBuf<double> d_atm_T;
+    DevBuf<unsigned long long> d_atm_ntrip, d_atm_samples;
+    bool        atm_ready = false;          // pigs_atm_init called
+    int         atm_window = 0;
+    double      atm_rc2 = 0.0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -1379,7 +1386,7 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     return PIGS_OK;
 }
 
-// ---- what the ten per-walker accumulator families below share ----------------------------------
+// ---- what the eleven per-walker accumulator families below share ----------------------------------
 extern "C++" {      // templates
 
 // *_init, once the request is accepted: no accumulate may be in flight on the buffers being replaced, and until the new
@@ -2047,6 +2054,60 @@ int pigs_g3_read(pigs_ctx *c, int64_t *trip, int64_t *pair, int64_t *samples, co
     const size_t ntrip = (size_t)c->g3_nr * ((size_t)c->g3_nr + 1) / 2 * (size_t)c->g3_na;
     return read_and_reset(c, {{c->d_g3_trip.p, ntrip, trip}, {c->d_g3_pair.p, (size_t)c->g3_nr, pair},
                               {c->d_g3_samples.p, 1, samples}}, reset);
+}
+
+// ---- Axilrod-Teller-Muto three-body geometric sum of a periodic system over a slice window -------
+// Raw sums per walker and window slice (pigs_atm.hip), accumulated on the device and read per block.
+int pigs_atm_init(pigs_ctx *c, double rc, int32_t window)
+{
+    int rc_ = check_ctx(c); if (rc_) return rc_;
+    rc_ = check_cm(c); if (rc_) return rc_;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the three-body energy is defined for periodic systems only (its sides are minimum images)");
+    if (c->P.dim < 2) return fail(PIGS_ERR_UNSUPPORTED, "the three-body energy is defined in 2D and 3D only");
+    if (!(rc > 0.0) || !std::isfinite(rc) || window < 0 || window > c->P.Nb)
+        return fail(PIGS_ERR_ARG, "pigs_atm_init: rc=%g window=%d (0..Nb=%d)", rc, window, c->P.Nb);
+    for (int k = 0; k < c->P.dim; ++k)
+        if (!(rc <= c->P.LboxHalf[k]))
+            return fail(PIGS_ERR_ARG, "pigs_atm_init: rc = %g (0 < rc <= half the shortest side)", rc);
+    const AtmShape sh = atm_shape(c->P.dim, c->P.Np);
+    if (!sh.fits)
+        return fail(PIGS_ERR_ARG, "pigs_atm_init: a slice of Np=%d particles in %dD and its leg lists need %zu bytes of LDS (%zu at most)",
+                    c->P.Np, c->P.dim, sh.lds, kAtmLdsBudget);
+    const size_t W = (size_t)c->n_walkers, per = 2 * (size_t)window + 1;
+    rc_ = init_begin(c, c->atm_ready); if (rc_) return rc_;
+    HIPCHK(alloc_zeroed(c, c->d_atm_T, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_atm_ntrip, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_atm_samples, W));
+    SYNC_CHECKED(c);
+    c->atm_window = window;
+    c->atm_rc2 = rc * rc;
+    c->atm_ready = true;
+    return PIGS_OK;
+}
+
+int pigs_atm_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->atm_ready) return fail(PIGS_ERR_ARG, "pigs_atm_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    const AtmShape sh = atm_shape(c->P.dim, c->P.Np);
+    // one workgroup owns an accumulator element per launch
+    return each_launch(c, sw, walkers, true, kWalkerListMax, "launch_atm", [&](int m, const WalkerList &L) {
+        return launch_atm(c->P, c->d_paths.p, m, L, sh, c->atm_window, c->atm_rc2, c->d_atm_T.p, c->d_atm_ntrip.p,
+                          c->d_atm_samples.p, c->stream);
+    });
+}
+
+int pigs_atm_read(pigs_ctx *c, double *T, int64_t *ntrip, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->atm_ready) return fail(PIGS_ERR_ARG, "pigs_atm_init first");
+    if (!T || !ntrip || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t per = 2 * (size_t)c->atm_window + 1;
+    return read_and_reset(c, {{c->d_atm_T.p, per, T}, {c->d_atm_ntrip.p, per, ntrip}, {c->d_atm_samples.p, 1, samples}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

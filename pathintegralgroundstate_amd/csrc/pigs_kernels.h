@@ -183,6 +183,22 @@ hipError_t launch_g3(const DevParams &P, const double *paths, int n, const Walke
                      int Nr, double rbin, int Na, unsigned long long *trip, unsigned long long *pair,
                      unsigned long long *samples, hipStream_t st);
 
+// pigs_atm.hip: the Axilrod-Teller-Muto geometric sum over the window slices (pigs_atm_accumulate): per walker and slice
+// a double T and a 64-bit count of the triplets within rc.  k_atm, one workgroup of kAtmWaves waves per (listed walker,
+// slice), holds the slice in LDS; a wave owns a vertex i, compacts its legs j > i into a list of its own in LDS (capacity
+// Np: a vertex has at most Np - 1 legs) and shares the pairs of legs among its lanes.  One thread owns an element (w, a)
+// per launch: a walker must not be listed twice in ONE launch.  The slice, the lists and the reduction's tail always sit in
+// LDS,
+//   8 dim Np + kAtmWaves Np 8 (dim + 1) + kAtmLdsTail <= kAtmLdsBudget         (fits; pigs_atm_init checks it).
+constexpr int kAtmWaves = 4;
+constexpr int kAtmThreads = kAtmWaves * 64;
+constexpr size_t kAtmLdsTail = 64;                // the waves' partial sums and counts
+constexpr size_t kAtmLdsBudget = 160 * 1024;      // LDS of one CU on gfx950
+struct AtmShape { int fits, cap; size_t lds; };
+AtmShape atm_shape(int dim, int Np);
+hipError_t launch_atm(const DevParams &P, const double *paths, int n, const WalkerList &list, const AtmShape &s, int window,
+                      double rc2, double *T, unsigned long long *ntrip, unsigned long long *samples, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

@@ -625,6 +625,26 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its counts after the copy
        integer(c_int) :: rc
      end function pigs_g3_read_t
+
+     ! Axilrod-Teller-Muto three-body sum over a slice window (include/pigs_hip.h, pigs_atm_*): looked up at run time, see
+     ! atm_bind; _accumulate has the signature of pigs_grv_accumulate
+     function pigs_atm_init_t(ctx,rc,window) bind(C) result(st)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value        :: ctx
+       real(c_double), value     :: rc
+       integer(c_int32_t), value :: window
+       integer(c_int) :: st
+     end function pigs_atm_init_t
+
+     function pigs_atm_read_t(ctx,T,ntrip,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: T(*)          ! raw sums (2 window + 1,n_walkers)
+       integer(c_int64_t)             :: ntrip(*)      ! counts (2 window + 1,n_walkers)
+       integer(c_int64_t)             :: samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_atm_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -682,6 +702,11 @@ module pigs_capi
   procedure(pigs_g3_init_t), pointer        :: g3_init => null()
   procedure(pigs_grv_accumulate_t), pointer :: g3_accumulate => null()
   procedure(pigs_g3_read_t), pointer        :: g3_read => null()
+
+  ! bound by atm_bind (null until then)
+  procedure(pigs_atm_init_t), pointer       :: atm_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: atm_accumulate => null()
+  procedure(pigs_atm_read_t), pointer       :: atm_read => null()
 
 contains
 
@@ -822,6 +847,16 @@ contains
     call c_f_procpointer(f(2),g3_accumulate)
     call c_f_procpointer(f(3),g3_read)
   end function g3_bind
+
+  ! The three-body entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function atm_bind()
+    type(c_funptr) :: f(3)
+    atm_bind = resolve_all('pigs_atm',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. atm_bind) return
+    call c_f_procpointer(f(1),atm_init)
+    call c_f_procpointer(f(2),atm_accumulate)
+    call c_f_procpointer(f(3),atm_read)
+  end function atm_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -21,6 +21,7 @@ module pigs_estimators
   public :: normalize_bop, write_bo, write_boh
   public :: normalize_vh, write_vh
   public :: normalize_g3, write_g3, write_g3ang
+  public :: normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -747,6 +748,60 @@ contains
     end do
     close (u)
   end subroutine write_g3ang
+
+  ! ---- Axilrod-Teller-Muto three-body energy over a slice window (raw sums T and counts ntrip of pigs_atm_read, one value
+  ! per window slice a = Nb-window..Nb+window) -> one walker's block values with S samples and the coupling nu:
+  !   B(1,a) = V3/Np of slice a = nu T(a)/(S Np);   B(2,a) = the mean number of triplets within rc = ntrip(a)/S
+  subroutine normalize_atm(Np,window,nu,S,T,ntrip,B)
+    integer, intent(in)    :: Np,window
+    real(8), intent(in)    :: nu,T(-window:window)
+    integer(8), intent(in) :: S,ntrip(-window:window)
+    real(8), intent(out)   :: B(2,-window:window)
+    integer :: a
+    do a=-window,window
+       B(1,a) = nu*T(a)/(real(S,8)*real(Np,8))
+       B(2,a) = real(ntrip(a),8)/real(S,8)
+    end do
+  end subroutine normalize_atm
+
+  ! V3/Np of the block values B averaged over the window
+  function atm_window_mean(window,B) result(v3)
+    integer, intent(in) :: window
+    real(8), intent(in) :: B(2,-window:window)
+    real(8) :: v3
+    v3 = sum(B(1,:))/real(2*window+1,8)
+  end function atm_window_mean
+
+  ! first line of v3_vpi*.out
+  subroutine v3_header(u,window)
+    integer, intent(in) :: u,window
+    write (u,'(a,i0,a,i0,a)') '# block, V3/Np = nu <sum_{i<j<k} (1 + 3 cos cos cos)/(r r r)^3>/Np over the slices Nb-',window,'..Nb+', &
+         & window,' (triplets with a side beyond atm_rc are not counted, no tail correction), P3 = 9 density (V3/Np)/dim'
+  end subroutine v3_header
+
+  ! one line of v3_vpi*.out: the block, V3/Np over the window, and its pressure P3 = 9 nu <T>/(dim Volume)
+  subroutine write_v3_block(u,iblock,dim,density,v3)
+    integer, intent(in) :: u,iblock,dim
+    real(8), intent(in) :: density,v3
+    write (u,'(20g20.10e3)') real(iblock),v3,9.d0*density*v3/real(dim,8)
+  end subroutine write_v3_block
+
+  ! v3tau_vpi.out: one row per window slice a: a, tau_a = (a-Nb) dt, mean and error of V3/Np over the n blocks, and the mean
+  ! number of triplets within rc
+  subroutine write_v3tau(fname,Nb,window,dt,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in)    :: Nb,window,n
+    real(8), intent(in)    :: dt
+    real(8), intent(inout) :: av(2,-window:window),av2(2,-window:window)
+    integer :: a,u
+    open (newunit=u,file=fname)
+    av  = av/real(n)
+    av2 = av2/real(n)
+    do a=-window,window
+       write (u,'(20g20.10e3)') real(Nb+a,8),real(a,8)*dt,av(1,a),variance(n,av(1,a),av2(1,a)),av(2,a)
+    end do
+    close (u)
+  end subroutine write_v3tau
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order, van_hove, triplet.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove, triplet, three_body.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -57,6 +57,11 @@ module pigs_families
      logical :: triplet = .false.
      integer :: g3_nr = 10, g3_na = 20, g3_window = -1       ! g3_window < 0: slice Nb alone
      real(8) :: g3_rmax = 0.d0                      ! <= 0: the run's rcut (half the shortest side)
+     logical :: three_body = .false.
+     logical :: atm_nu_given = .false.              ! F: atm_nu was left out, the files hold the bare geometric sum
+     real(8) :: atm_nu = 1.d0                       ! the triple-dipole coupling, in the run's units (energy length^9)
+     real(8) :: atm_rc = 0.d0                       ! <= 0: half the shortest side
+     integer :: atm_window = -1                     ! < 0: slice Nb alone
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -341,17 +346,39 @@ module pigs_families
      procedure :: write_average => g3_write_average
   end type g3_family
 
-  integer, parameter :: NFAM = 10
+  ! Axilrod-Teller-Muto three-body energy: the block's raw sums and triplet counts from the device per window slice, the
+  ! normalised block values (V3/Np and the mean triplets per slice); the units of v3_vpi*.out
+  type, extends(family) :: atm_family
+     integer :: window = 0
+     real(8) :: nu = 1.d0, rc = 0.d0
+     real(8), allocatable :: raw(:,:),b(:,:)        ! (first index of raw, second of b: slice a - (Nb-window) + 1)
+     integer(c_int64_t), allocatable :: ntrip(:,:)
+     type(block_series) :: s
+     integer, allocatable :: up(:)
+     integer :: upav = -1
+   contains
+     procedure :: check => atm_check
+     procedure :: banner => atm_banner
+     procedure :: setup => atm_setup
+     procedure :: queue => atm_queue
+     procedure :: read => atm_read_block
+     procedure :: block => atm_block
+     procedure :: average => atm_average
+     procedure :: write_walker => atm_write_walker
+     procedure :: write_average => atm_write_average
+  end type atm_family
+
+  integer, parameter :: NFAM = 11
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
   ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
-  ! 9 van_hove, 10 triplet
+  ! 9 van_hove, 10 triplet, 11 three_body
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -386,6 +413,7 @@ contains
     if (keys%bond_order)      allocate (bop_family :: fs%slot(8)%f)
     if (keys%van_hove)        allocate (vh_family :: fs%slot(9)%f)
     if (keys%triplet)         allocate (g3_family :: fs%slot(10)%f)
+    if (keys%three_body)      allocate (atm_family :: fs%slot(11)%f)
   end subroutine set_create
 
   ! refuses what the keys cannot have (exit status 2) and fills in the windows that were left out
@@ -1586,5 +1614,125 @@ contains
     call write_g3('g3_vpi.out',f%epr,f%na,f%cnt%nav,f%s3%asum,f%s3%asq)
     call write_g3ang('g3ang_vpi.out',f%na,f%cnt%nav,f%sA%asum,f%sA%asq)
   end subroutine g3_write_average
+
+  !---------------------------------------------------------------------
+  ! three_body: the Axilrod-Teller-Muto (triple-dipole) energy of a periodic system in 2D or 3D, evaluated on the sampled
+  ! configurations over the slices Nb-atm_window..Nb+atm_window, every side of a triplet within atm_rc -- v3_vpi*.out (one
+  ! line per block: V3/Np over the window and its pressure P3; per walker, and the walker average where there are several)
+  ! and v3tau_vpi.out (one line per window slice: a, tau, V3/Np and its error, the mean number of triplets)
+
+  subroutine atm_check(f,keys,dim,Nb,trap)
+    class(atm_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('three_body','the sides of its triplets are minimum images in the box')
+    if (dim<2) then
+       write (0,'(a,i0)') ' pigs_vpi: three_body = T needs dim = 2 or 3: there is no triangle in dim = ',dim
+       stop 2
+    end if
+    if (.not. (keys%atm_rc>0.d0)) keys%atm_rc = keys%half_side          ! left out: half the shortest side
+    if (.not. (keys%atm_rc<=keys%half_side)) then
+       write (0,'(a,g0,a,g0)') ' pigs_vpi: three_body = T: atm_rc = ',keys%atm_rc, &
+            & ' must be at most half the shortest side of the box = ',keys%half_side
+       stop 2
+    end if
+    if (keys%atm_window<0) keys%atm_window = 0
+    call check_window('three_body','atm',keys%atm_window,Nb)
+    if (.not. atm_bind()) call no_backend('three_body','pigs_atm_init / _accumulate / _read','the three-body energy runs')
+  end subroutine atm_check
+
+  subroutine atm_banner(f,keys,trap)
+    class(atm_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    if (keys%atm_nu_given) then
+       print '(a,g0.6,a,g0.6,a,i0,a,i0,a)', '  > Three-body V3       : on (nu = ',keys%atm_nu,', sides below ',keys%atm_rc,', slices Nb-', &
+            & keys%atm_window,'..Nb+',keys%atm_window,': v3_vpi.out, v3tau_vpi.out)'
+    else
+       print '(a,g0.6,a,i0,a,i0,a)', '  > Three-body V3       : on (atm_nu left out: nu = 1, the files hold the bare geometric sum; sides below ', &
+            & keys%atm_rc,', slices Nb-',keys%atm_window,'..Nb+',keys%atm_window,': v3_vpi.out, v3tau_vpi.out)'
+    end if
+  end subroutine atm_banner
+
+  subroutine atm_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(atm_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: w,ns
+    call family_begin(f,run,ep,NW)
+    f%window = max(keys%atm_window,0)
+    f%nu = keys%atm_nu
+    f%rc = merge(keys%atm_rc,keys%half_side,keys%atm_rc>0.d0)
+    ns = 2*f%window+1
+    allocate (f%raw(ns,NW),f%ntrip(ns,NW),f%b(2,ns))
+    call series_create(f%s,2*ns,NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(atm_init(ctx,real(f%rc,c_double),int(f%window,c_int32_t)),'pigs_atm_init')
+    allocate (f%up(NW))
+    do w=1,NW
+       open (newunit=f%up(w),file='v3_vpi'//trim(run%suffix(w))//'.out')
+       call v3_header(f%up(w),f%window)
+    end do
+    if (run%averages) then
+       open (newunit=f%upav,file='v3_vpi.out')
+       call v3_header(f%upav,f%window)
+    end if
+  end subroutine atm_setup
+
+  subroutine atm_queue(f,ctx,nd,wl)
+    class(atm_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(atm_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_atm_accumulate')
+  end subroutine atm_queue
+
+  subroutine atm_read_block(f,ctx)
+    class(atm_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(atm_read(ctx,f%raw,f%ntrip,f%smp,f%reset),'pigs_atm_read')
+  end subroutine atm_read_block
+
+  subroutine atm_block(f,w,info,vec)
+    class(atm_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_atm(f%ep%Np,f%window,f%nu,int(f%smp(w),8),f%raw(:,w),int(f%ntrip(:,w),8),f%b)
+    call series_add(f%s,w,reshape(f%b,[size(f%b)]),vec)
+    call count_add(f%cnt,vec)
+    call write_v3_block(f%up(w),info%iblock,f%ep%dim,f%run%density,atm_window_mean(f%window,f%b))
+  end subroutine atm_block
+
+  subroutine atm_average(f,info,vec)
+    class(atm_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%s,vec,nall)
+       if (info%ndall>0) call write_v3_block(f%upav,info%iblock,f%ep%dim,f%run%density,atm_window_mean(f%window,f%s%mean))
+    end if
+  end subroutine atm_average
+
+  subroutine atm_write_walker(f,suffix,w,nblocks)
+    class(atm_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_v3tau('v3tau_vpi'//trim(suffix)//'.out',f%run%Nb,f%window,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+    close (f%up(w))
+  end subroutine atm_write_walker
+
+  subroutine atm_write_average(f)
+    class(atm_family), intent(inout) :: f
+    call write_v3tau('v3tau_vpi.out',f%run%Nb,f%window,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
+    close (f%upav)
+  end subroutine atm_write_average
 
 end module pigs_families

@@ -9,7 +9,8 @@ module pigs_host_hooks
   use pigs_capi
   use pigs_rng
   use pigs_sampler
-  use pigs_estimators, only: est_params, normalize_vh, write_vh, normalize_g3, write_g3, write_g3ang
+  use pigs_estimators, only: est_params, normalize_vh, write_vh, normalize_g3, write_g3, write_g3ang, &
+       & normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau
 
   implicit none
   private
@@ -234,6 +235,33 @@ contains
     call write_g3(cstring(f3),p,Na,nb,a3,a32)
     call write_g3ang(cstring(fa),Na,nb,aa,aa2)
   end subroutine hs_g3_files
+
+  ! The three-body normalisation and writers of the front end on given sums: nblk blocks of one walker, T and ntrip
+  ! (2 window + 1,nblk) and S samples per block, the coupling nu -> v3, cnt of the LAST block and its window mean, and the two
+  ! files: fb one line per block (v3_vpi.out), ft mean and error over the blocks per slice (v3tau_vpi.out) (names: C strings)
+  subroutine hs_atm_files(dim,Np,density,Nb,window,dt,nu,nblk,S,T,ntrip,v3,cnt,v3mean,fb,ft) bind(C,name='hs_atm_files')
+    integer(c_int), value :: dim,Np,Nb,window,nblk
+    real(c_double), value :: density,dt,nu
+    integer(c_int64_t), intent(in) :: S(nblk),ntrip(2*window+1,nblk)
+    real(c_double), intent(in)     :: T(2*window+1,nblk)
+    real(c_double), intent(out)    :: v3(2*window+1),cnt(2*window+1),v3mean
+    character(kind=c_char), intent(in) :: fb(*),ft(*)
+    real(8), allocatable :: B(:,:),a(:,:),a2(:,:)
+    integer :: ib,u
+    allocate (B(2,2*window+1),a(2,2*window+1),a2(2,2*window+1))
+    a = 0.d0; a2 = 0.d0
+    open (newunit=u,file=cstring(fb))
+    call v3_header(u,window)
+    do ib=1,nblk
+       call normalize_atm(Np,window,nu,int(S(ib),8),T(:,ib),int(ntrip(:,ib),8),B)
+       a = a+B; a2 = a2+B*B
+       v3mean = atm_window_mean(window,B)
+       call write_v3_block(u,ib,dim,density,v3mean)
+    end do
+    close (u)
+    v3 = B(1,:); cnt = B(2,:)
+    call write_v3tau(cstring(ft),Nb,window,dt,nblk,a,a2)
+  end subroutine hs_atm_files
 
   ! a C string as a Fortran one
   function cstring(c) result(f)

@@ -58,6 +58,13 @@
 ! 20) -- g3_vpi.out, one line per (lo, hi, q) with the leg bins lo <= hi: r_lo, r_hi, cos(theta), g3 and its error,
 ! normalised to 1 for an uncorrelated system; g3ang_vpi.out: cos(theta), the bond-angle distribution P(cos theta) of the
 ! legs below g3_rmax, which integrates to 1, and its error)
+! (three_body = T, periodic systems in 2D and 3D only: the Axilrod-Teller-Muto (triple-dipole) energy, evaluated on the GPU on
+! the sampled configurations over the slices Nb-atm_window..Nb+atm_window (default 0): the sum over the triplets i < j < k
+! whose three nearest-image sides all lie within atm_rc (left out or <= 0: half the shortest side) of
+! nu (1 + 3 cos cos cos)/(r_ij r_ik r_jk)^3, with the coupling atm_nu in the run's own units (energy length^9; left out: 1,
+! the bare geometric sum) -- v3_vpi.out, one line per block: the block, V3/Np over the window, and its pressure
+! P3 = 9 density (V3/Np)/dim (cut at atm_rc, no tail correction); v3tau_vpi.out, one line per window slice: a,
+! tau_a = (a-Nb) dt, V3/Np and its error, the mean number of triplets)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -111,6 +118,9 @@ program pigs_vpi
   logical           :: triplet
   integer           :: g3_nr,g3_na,g3_window
   real (kind=8)     :: g3_rmax
+  logical           :: three_body
+  integer           :: atm_window
+  real (kind=8)     :: atm_nu,atm_rc
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
   logical           :: sampler_auto
@@ -132,7 +142,8 @@ program pigs_vpi
        &             fq_self,fqs_nmax,fqs_ntau,fqs_window, &
        &             bond_order,bo_rnb,bo_nhist,bo_nr,bo_window, &
        &             van_hove,vh_ntau,vh_window,vh_nself,vh_rself, &
-       &             triplet,g3_nr,g3_na,g3_rmax,g3_window
+       &             triplet,g3_nr,g3_na,g3_rmax,g3_window, &
+       &             three_body,atm_nu,atm_rc,atm_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -164,6 +175,7 @@ program pigs_vpi
   bond_order = .false.; bo_rnb = 0.d0; bo_nhist = 50; bo_nr = -1; bo_window = 0
   van_hove = .false.; vh_ntau = 0; vh_window = -1; vh_nself = 50; vh_rself = 0.d0
   triplet = .false.; g3_nr = 10; g3_na = 20; g3_rmax = 0.d0; g3_window = -1
+  three_body = .false.; atm_nu = -huge(1.d0); atm_rc = 0.d0; atm_window = -1        ! (atm_nu: a value nobody gives, left out -> 1)
 
   read (5,nml=system,iostat=ios);  rewind (5)
   read (5,nml=samp,iostat=ios);    rewind (5)
@@ -236,7 +248,9 @@ program pigs_vpi
        & tau_window=tau_window,fq_self=fq_self,fqs_nmax=fqs_nmax,fqs_ntau=fqs_ntau,fqs_window=fqs_window, &
        & bond_order=bond_order,bo_rnb=bo_rnb,bo_nhist=bo_nhist,bo_nr=bo_nr,bo_window=bo_window,half_side=rcut, &
        & van_hove=van_hove,vh_ntau=vh_ntau,vh_window=vh_window,vh_nself=vh_nself,vh_rself=vh_rself, &
-       & triplet=triplet,g3_nr=g3_nr,g3_na=g3_na,g3_rmax=g3_rmax,g3_window=g3_window)
+       & triplet=triplet,g3_nr=g3_nr,g3_na=g3_na,g3_rmax=g3_rmax,g3_window=g3_window, &
+       & three_body=three_body,atm_nu_given=atm_nu/=-huge(1.d0),atm_nu=merge(atm_nu,1.d0,atm_nu/=-huge(1.d0)), &
+       & atm_rc=atm_rc,atm_window=atm_window)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 

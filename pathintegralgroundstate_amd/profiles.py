@@ -66,6 +66,12 @@ p = lo*Nr - lo*(lo-1)/2 + hi - lo, and q the bin of cos(theta) on [-1, 1]; with 
   g3(lo, hi, q) = trip / (S * Np * density**2 * dV_lo * dV_hi * w_q * m),   m = 1 for lo < hi, 1/2 for lo = hi,
   w_q = 1/Na in 3D, (acos(c_q) - acos(c_{q+1}))/pi in 2D with c_q = -1 + 2q/Na      (1 + O(1/Np) without correlations)
 bond_angle sums trip over the legs of the first bins into P(cos theta); kirkwood_g3 is g(r) g(s) g(t) on the same grid.
+
+Axilrod-Teller-Muto three-body energy (normalize_atm, PigsContext.atm_read, pigs_atm_*): T sums, per window slice, the
+geometric term (1 + 3 cos cos cos)/(r_ij r_ik r_jk)**3 over the triplets whose three nearest-image sides lie within rc, and
+ntrip counts them; with the coupling nu in the run's own units (energy * length**9; the library knows no element):
+  V3/N(tau_a) = nu * T / (S_w * Np)                     (its window mean is the perturbative <V3>/N)
+  P3          = 9 * density * (V3/N) / dim              (pressure_atm: the sum is homogeneous of degree -9; cut at rc, no tail)
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -397,6 +403,31 @@ def kirkwood_g3(g2, rbin, Na):
     t = np.sqrt(np.maximum(t2, 0.0))
     gt = np.interp(t, r, g)
     return np.where(t < Nr * rbin, (g[lo] * g[hi])[:, None] * gt, np.nan)
+
+
+def normalize_atm(raw, Np, nu=1.0):
+    """raw: the dict of atm_read (T [W, 2 window + 1] raw sums, ntrip likewise, samples [W]) or one walker's slice of it.
+    nu: the triple-dipole coupling (energy * length**9 in the run's units; 1: the bare geometric sum).
+    Returns a dict: v3 [.., 2 window + 1] = nu*T/(samples*Np), the three-body energy per particle of every window slice,
+    v3_mean [..] its mean over the window, and ntrip [.., 2 window + 1] the mean number of triplets within rc per slice.
+    A walker without samples gives NaN."""
+    T = np.asarray(raw["T"], dtype=np.float64)
+    n = np.asarray(raw["ntrip"], dtype=np.float64)
+    S = np.asarray(raw["samples"], dtype=np.float64)
+    if T.shape != n.shape or T.shape[-1] % 2 == 0:
+        raise ValueError("T and ntrip must be [.., 2 window + 1]")
+    Sb = S.reshape(S.shape + (1,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v3 = float(nu) * T / (Sb * float(Np))
+        cnt = n / Sb
+    return {"v3": v3, "v3_mean": v3.mean(axis=-1), "ntrip": cnt}
+
+
+def pressure_atm(v3_per_particle, density, dim):
+    """The three-body contribution to the pressure, P3 = 9 * density * (V3/N) / dim, of a periodic system: the
+    Axilrod-Teller-Muto sum is homogeneous of degree -9 in the lengths, so its virial is 9 V3 (P3 = 9 nu <T>/(dim Volume)
+    with V3/N as normalize_atm gives it).  Triplets with a side beyond rc are not in V3 and no tail correction is made."""
+    return 9.0 * density * np.asarray(v3_per_particle, np.float64) / dim
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
