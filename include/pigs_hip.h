@@ -647,6 +647,59 @@ int pigs_atm_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * pigs_atm_init. */
 int pigs_atm_read(pigs_ctx *ctx, double *T, int64_t *ntrip, int64_t *samples, const int32_t *reset);
 
+/* ---- the momentum distribution n(k) and the one-body density matrix rho1(r) of a PERIODIC system (new: the first
+ * off-diagonal estimator beyond the reference's radial histogram nrho, which is cut at rcut, binned and angle-averaged) ------
+ * Scope: periodic contexts.  A SAMPLE is the end-to-end vector of an open worldline, x_k = head_k - tail_k, folded once:
+ *   if (x_k >  LboxHalf(k)) x_k = x_k - Lbox(k);   if (x_k < -LboxHalf(k)) x_k = x_k + Lbox(k)
+ * which is what the sampler's OBDM histogram takes (sample_mod.f90:477-526).
+ * Vectors: exactly those of pigs_sqv_*, in its enumeration order (half space, |n_k| <= nmax, n = 0 left out);
+ * pigs_nk_count and pigs_nk_vectors hand them out.  For k = 2 pi (n_1/Lbox(1), ..) the phase k.x does not depend on the
+ * periodic image, so every sample counts, those beyond rcut too.  Per sample of a listed walker w the device adds
+ *   C[w][iq]   += cos(k_iq . x)                as a double, the samples in tape order, one add to C per launch
+ *   H[w][flat] += 1   flat = j_1 + nbin j_2 + nbin^2 j_3, j_k = (int)t_k, t_k = (x_k + LboxHalf(k)) / (Lbox(k)/nbin), iff
+ *                     0 <= t_k < nbin holds in double for every k: the cell and bin-edge rule of pigs_grv_*
+ *   nopen[w]   += 1   (this is the sum of the vector n = 0: C(0) = nopen exactly)
+ *   ninside[w] += 1   iff r2 <= rcut2 in double, r2 = sum_k x_k^2 left to right: the histogram's own comparison
+ * cos(k.x) is the real part of the product of per-axis phasors exp(i real(m) (2 pi/Lbox(k)) x_k), m = |n_k|, each from one
+ * sincos of the phase rounded as pigs_sqv_* rounds it (m = 0 gives exactly 1), multiplied in the order k = 1..dim.
+ * No floating-point atomics and one fixed order: the same samples give the same bits, and a walker listed twice counts
+ * twice (in two launches) with bits equal to 2 x one count.
+ * The estimators are the caller's divisions (profiles.normalize_nk, normalize_nrvec; pigs_estimators.f90), in the
+ * reference's NormalizeNr convention with zconf the number of diagonal configurations of the block:
+ *   n(k) = C / (CWorm zconf Nobdm),   n(0) = nopen / (CWorm zconf Nobdm),   n0 = n(0)/Np,   sum over all k of n(k) = Np
+ *   rho1(bin)/density = H / (CWorm zconf Nobdm density cell volume/nbin^dim)
+ * Samples are staged in tiles of PIGS_NK_TILE in LDS, 16 dim PIGS_NK_TILE (nmax + 1) bytes.  A walker with at most one tile
+ * of samples (every Nobdm <= PIGS_NK_TILE on the tape path) has its table built once.  With more, the tables of all its
+ * tiles are built again for every 256 vectors (Nq/256 times: 70 at nmax = 16 in 3D): correct, but pigs_nk_add is then
+ * cheaper in calls of at most PIGS_NK_TILE pairs per walker.
+ *
+ * pigs_nk_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context
+ * (there rho1 is not translation-invariant, and the reference takes no OBDM either); PIGS_ERR_ARG for nmax < 1, nmax > 16
+ * in 3D, nmax > 64 in 1D or 2D (pigs_sqv_init's limits), nbin < 1, nbin > 128 in 3D, 1024 in 2D, 4096 in 1D, or sums
+ * beyond 2 GiB (pigs_grv_init's limits). */
+#define PIGS_NK_TILE 64
+int pigs_nk_init(pigs_ctx *ctx, int32_t nmax, int32_t nbin);
+/* Nq, and the vectors n[Nq][dim] in the enumeration order of pigs_sqv_vectors.  PIGS_ERR_ARG before pigs_nk_init. */
+int pigs_nk_count(pigs_ctx *ctx, int64_t *Nq);
+int pigs_nk_vectors(pigs_ctx *ctx, int32_t *n);
+/* Adds, for walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice), the samples of the LAST pigs_sampler_step:
+ * the Nobdm end-to-end vectors that its worm loop handed to the OBDM histogram if the walker went through that loop
+ * (it was open after the open / close attempt), none otherwise.  Queued on the context's stream, no upload, no host
+ * synchronisation.  It must be queued before the next pigs_sampler_step, which overwrites the tape.  A second call after
+ * the same step counts that step's samples again.  Before the first step it adds nothing.
+ * PIGS_ERR_ARG before pigs_nk_init, unless pigs_sampler_init was called with CWorm > 0, for n < 0 or for a walker out of
+ * range. */
+int pigs_nk_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* The same sums from the host (the host-driven sampler, tests; needs no sampler): listed walker i brings nsamp[i] >= 0
+ * pairs, xend(dim, 2, sum nsamp) in Fortran order: head (dim doubles) then tail of every pair, the pairs of walker 0 first.
+ * Folds head - tail once as above and runs the kernel of pigs_nk_accumulate.  Uploads and waits for the upload.
+ * PIGS_ERR_ARG before pigs_nk_init, for n < 0, a negative nsamp or a walker out of range. */
+int pigs_nk_add(pigs_ctx *ctx, int32_t n, const int32_t *walkers, const int32_t *nsamp, const double *xend);
+/* All walkers' C[n_walkers][Nq], H[n_walkers][nbin^dim] (x fastest), nopen[n_walkers] and ninside[n_walkers]; then zeroes
+ * those of the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before
+ * pigs_nk_init. */
+int pigs_nk_read(pigs_ctx *ctx, double *C, int64_t *H, int64_t *nopen, int64_t *ninside, const int32_t *reset);
+
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
  * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "pigs_vh_init", "pigs_vh_accumulate", "pigs_vh_read",
     "pigs_g3_init", "pigs_g3_accumulate", "pigs_g3_read",
     "pigs_atm_init", "pigs_atm_accumulate", "pigs_atm_read",
+    "pigs_nk_init", "pigs_nk_count", "pigs_nk_vectors", "pigs_nk_accumulate", "pigs_nk_add", "pigs_nk_read",
 ]
 
 
@@ -173,6 +174,12 @@ def load_library(path=LIB_PATH):
     L.pigs_atm_init.argtypes = [vp, C.c_double, C.c_int32]
     L.pigs_atm_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_atm_read.argtypes = [vp, _dp, _lp, _lp, _ip]
+    L.pigs_nk_init.argtypes = [vp, C.c_int32, C.c_int32]
+    L.pigs_nk_count.argtypes = [vp, _lp]
+    L.pigs_nk_vectors.argtypes = [vp, _ip]
+    L.pigs_nk_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_nk_add.argtypes = [vp, C.c_int32, _ip, _ip, _dp]
+    L.pigs_nk_read.argtypes = [vp, _dp, _lp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -795,6 +802,63 @@ class PigsContext:
         out = {"T": np.zeros((W, ns)), "ntrip": np.zeros((W, ns), np.int64), "samples": np.zeros(W, np.int64)}
         mask = self._reset_mask(reset)
         _chk(self.L, self.L.pigs_atm_read(self.h, _d(out["T"]), _l(out["ntrip"]), _l(out["samples"]), mask), "pigs_atm_read")
+        return out
+
+    # ---- momentum distribution and one-body density matrix (pigs_nk_*: cosine sums per walker and vector, 64-bit counts)
+    def nk_init(self, nmax, nbin):
+        """Allocate and zero the sums of the momentum distribution of a periodic system on the vectors of sqv_init(nmax)
+        (nk_vectors lists them) and the counts of the end-to-end vector on nbin bins per axis of the minimum-image cell.
+        Calling it again resizes and zeroes."""
+        _chk(self.L, self.L.pigs_nk_init(self.h, int(nmax), int(nbin)), "pigs_nk_init")
+        nq = C.c_int64(0)
+        _chk(self.L, self.L.pigs_nk_count(self.h, C.byref(nq)), "pigs_nk_count")
+        self._nk_nq, self._nk_nbin = int(nq.value), int(nbin)
+
+    def nk_vectors(self):
+        """The stored vectors n [Nq, dim] (int32) in the library's enumeration order (that of sqv_vectors)."""
+        nq = getattr(self, "_nk_nq", None)
+        if nq is None:
+            raise PigsError("nk_vectors: nk_init first")
+        n = np.zeros((nq, self.cfg.dim), np.int32)
+        _chk(self.L, self.L.pigs_nk_vectors(self.h, _i(n)), "pigs_nk_vectors")
+        return n
+
+    def nk_accumulate(self, walkers=None):
+        """Queue the open-sector samples of the last sampler_step of `walkers` (None: all) on the context's stream; does
+        not wait.  To be queued before the next step; a second call after the same step counts it again."""
+        self._accumulate("pigs_nk_accumulate", walkers)
+
+    def nk_add(self, walkers, nsamp, xend):
+        """Add head/tail pairs from the host: nsamp[i] pairs for walkers[i] (None: walker i), xend [sum nsamp, 2, dim]
+        (head, tail), the pairs of the first listed walker first.  Needs no sampler."""
+        ns = _i32(nsamp).ravel()
+        x = np.ascontiguousarray(xend, dtype=np.float64).reshape(-1)
+        if x.size != int(ns.sum()) * 2 * self.cfg.dim:
+            raise ValueError("xend needs 2*dim doubles per pair")
+        if x.size == 0:
+            x = np.zeros(1)
+        if walkers is None:
+            _chk(self.L, self.L.pigs_nk_add(self.h, ns.size, None, _i(ns), _d(x)), "pigs_nk_add")
+        else:
+            wl = _i32(walkers).ravel()
+            if wl.size != ns.size:
+                raise ValueError("one nsamp per listed walker")
+            _chk(self.L, self.L.pigs_nk_add(self.h, wl.size, _i(wl), _i(ns), _d(x)), "pigs_nk_add")
+
+    def nk_read(self, reset=None):
+        """dict: C [W, Nq], the sums of cos(k.x) over the samples (float64), H [W, nbin, ..dim times] (array axis -1-k is
+        axis k of the box), nopen [W] the samples (the sum of the vector n = 0) and ninside [W] those within rcut (int64);
+        profiles.normalize_nk and normalize_nrvec divide them.  reset: None, True (all walkers) or a per-walker mask of
+        walkers whose sums are zeroed after the copy."""
+        nq = getattr(self, "_nk_nq", None)
+        if nq is None:
+            raise PigsError("nk_read: nk_init first")
+        W = self.n_walkers
+        out = {"C": np.zeros((W, nq)), "H": np.zeros((W,) + (self._nk_nbin,) * self.cfg.dim, np.int64),
+               "nopen": np.zeros(W, np.int64), "ninside": np.zeros(W, np.int64)}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_nk_read(self.h, _d(out["C"]), _l(out["H"]), _l(out["nopen"]), _l(out["ninside"]), mask),
+             "pigs_nk_read")
         return out
 
     # ---- K5

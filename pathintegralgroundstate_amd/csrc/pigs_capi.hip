@@ -270,6 +270,19 @@ struct pigs_ctx {
     bool        atm_ready = false;          // pigs_atm_init called
     int         atm_window = 0;
     double      atm_rc2 = 0.0;
+    // the sampler's end tape (periodic context, CWorm > 0): per walker the samples of the last step and their once-folded
+    // end-to-end vectors [walker][Nobdm][dim] (SweepParams.tape_count, tape_x)
+    DevBuf<int32_t> d_tape_count;
+    DevBuf<double>  d_tape_x;
+    // momentum distribution and one-body density matrix (pigs_nk_*): cosine sums C [walker][Nq], counts H [walker][nbin^dim],
+    // nopen and ninside [walker]; the samples that pigs_nk_add brings from the host ([position][cap][dim] and their numbers)
+    DevBuf<double> d_nk_C, d_nk_x;
+    DevBuf<unsigned long long> d_nk_H, d_nk_nopen, d_nk_ninside;
+    DevBuf<int32_t> d_nk_cnt;
+    int         nk_nmax = 0;                // 0: pigs_nk_init not called yet
+    int         nk_nbin = 0;
+    int64_t     nk_nq = 0;
+    size_t      nk_nvec = 0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -883,6 +896,15 @@ int pigs_sampler_init(pigs_ctx *c, const pigs_sweep_params *sp)
     HIPCHK(c->d_nrho.alloc(c->nrho_doubles));
     HIPCHK(c->d_dklog.alloc(dk.size()));
     hipStream_t s = c->stream;
+    if (worm && !c->P.trap) {
+        // the end tape of pigs_nk_accumulate: a step writes every walker's count, the worm loop the vectors
+        HIPCHK(c->d_tape_count.alloc(W));
+        HIPCHK(c->d_tape_x.alloc(std::max<size_t>(1, W * (size_t)k.Nobdm * c->P.dim)));
+        HIPCHK(hipMemsetAsync(c->d_tape_count.p, 0, W * sizeof(int32_t), s));
+        HIPCHK(hipMemsetAsync(c->d_tape_x.p, 0, c->d_tape_x.cap * sizeof(double), s));
+        k.tape_count = c->d_tape_count.p;
+        k.tape_x = c->d_tape_x.p;
+    }
     HIPCHK(hipMemcpyAsync(c->d_dklog.p, dk.data(), dk.size() * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(c->d_counters.p, 0, W * kCounters * sizeof(unsigned long long), s));
     HIPCHK(hipMemsetAsync(c->d_worm.p, 0, W * kWormDoubles * sizeof(double), s));
@@ -1386,7 +1408,7 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     return PIGS_OK;
 }
 
-// ---- what the eleven per-walker accumulator families below share ----------------------------------
+// ---- what the twelve per-walker accumulator families below share ----------------------------------
 extern "C++" {      // templates
 
 // *_init, once the request is accepted: no accumulate may be in flight on the buffers being replaced, and until the new
@@ -2108,6 +2130,118 @@ int pigs_atm_read(pigs_ctx *c, double *T, int64_t *ntrip, int64_t *samples, cons
     if (!T || !ntrip || !samples) return fail(PIGS_ERR_ARG, "null output");
     const size_t per = 2 * (size_t)c->atm_window + 1;
     return read_and_reset(c, {{c->d_atm_T.p, per, T}, {c->d_atm_ntrip.p, per, ntrip}, {c->d_atm_samples.p, 1, samples}}, reset);
+}
+
+// ---- momentum distribution n(k) and one-body density matrix of a periodic system -----------------
+// Cosine sums per walker and vector and integer counts per walker (pigs_nk.hip) of the end-to-end vectors of open
+// worldlines, taken from the sampler's end tape (pigs_nk_accumulate) or from the host (pigs_nk_add); read per block.
+int pigs_nk_init(pigs_ctx *c, int32_t nmax, int32_t nbin)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the momentum distribution is defined for periodic systems only (in a trap the one-body density matrix is not translation-invariant)");
+    const int nmmax = c->P.dim == 3 ? 16 : 64, nbmax = c->P.dim == 3 ? 128 : c->P.dim == 2 ? 1024 : 4096;
+    if (nmax < 1 || nmax > nmmax || nbin < 1 || nbin > nbmax)
+        return fail(PIGS_ERR_ARG, "pigs_nk_init: nmax=%d (1..%d in %dD) nbin=%d (1..%d in %dD)", nmax, nmmax, c->P.dim, nbin, nbmax, c->P.dim);
+    size_t nv = 1;
+    for (int k = 0; k < c->P.dim; ++k) nv *= (size_t)nbin;
+    const SqvShape sh = sqv_shape(c->P.dim, nmax);
+    const size_t W = (size_t)c->n_walkers;
+    const double bytes = (double)W * ((double)nv + (double)sh.Nq + 2.0) * 8.0;
+    if (bytes > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_nk_init: %zu walkers x (%zu + %lld + 2) accumulators pass 2 GiB", W, nv, (long long)sh.Nq);
+    rc = init_begin(c, c->nk_nmax); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_nk_C, W * (size_t)sh.Nq));
+    HIPCHK(alloc_zeroed(c, c->d_nk_H, W * nv));
+    HIPCHK(alloc_zeroed(c, c->d_nk_nopen, W));
+    HIPCHK(alloc_zeroed(c, c->d_nk_ninside, W));
+    SYNC_CHECKED(c);
+    c->nk_nmax = nmax;
+    c->nk_nbin = nbin;
+    c->nk_nq = sh.Nq;
+    c->nk_nvec = nv;
+    return PIGS_OK;
+}
+
+int pigs_nk_count(pigs_ctx *c, int64_t *Nq)
+{
+    return c ? grid_count(c, "nk", c->nk_nmax, c->nk_nq, Nq) : fail(PIGS_ERR_ARG, "null context");
+}
+
+int pigs_nk_vectors(pigs_ctx *c, int32_t *n)
+{
+    return c ? grid_vectors(c, "nk", c->nk_nmax, c->nk_nq, n) : fail(PIGS_ERR_ARG, "null context");
+}
+
+int pigs_nk_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->nk_nmax) return fail(PIGS_ERR_ARG, "pigs_nk_init first");
+    if (!c->sampler_ready || !c->sweep.worm || !c->sweep.tape_count)
+        return fail(PIGS_ERR_ARG, "pigs_nk_accumulate: pigs_sampler_init with CWorm > 0 first (there is no open sector to sample)");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // one thread owns an element of C per launch
+    return each_launch(c, sw, walkers, true, kWalkerListMax, "launch_nk", [&](int m, const WalkerList &L) {
+        return launch_nk(c->P, m, L, c->nk_nmax, c->nk_nbin, c->nk_nq, 1, 0, c->sweep.Nobdm, c->sweep.tape_count, c->sweep.tape_x,
+                         c->d_nk_C.p, c->d_nk_H.p, c->d_nk_nopen.p, c->d_nk_ninside.p, c->stream);
+    });
+}
+
+int pigs_nk_add(pigs_ctx *c, int32_t n, const int32_t *walkers, const int32_t *nsamp, const double *xend)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->nk_nmax) return fail(PIGS_ERR_ARG, "pigs_nk_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    if (n > 0 && !nsamp) return fail(PIGS_ERR_ARG, "null nsamp");
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    int cap = 0;
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (nsamp[i] < 0) return fail(PIGS_ERR_ARG, "nsamp[%d]=%d", i, nsamp[i]);
+        cap = std::max(cap, (int)nsamp[i]);
+        total += (size_t)nsamp[i];
+    }
+    if (total && !xend) return fail(PIGS_ERR_ARG, "null xend");
+    if (!total) return PIGS_OK;
+    // head - tail of every pair, folded once as the sampler's OBDM histogram folds it, at [position][cap][dim]
+    const int d = c->P.dim;
+    std::vector<double> x((size_t)n * cap * d, 0.0);
+    const double *src = xend;
+    for (int i = 0; i < n; ++i)
+        for (int s = 0; s < nsamp[i]; ++s, src += 2 * d)
+            for (int k = 0; k < d; ++k) {
+                double v = src[k] - src[d + k];
+                if (v >  c->P.LboxHalf[k]) v = v - c->P.Lbox[k];
+                if (v < -c->P.LboxHalf[k]) v = v + c->P.Lbox[k];
+                x[((size_t)i * cap + s) * d + k] = v;
+            }
+    // (a grown buffer is a new allocation: freeing the old one waits for the launches that read it)
+    HIPCHK(c->d_nk_x.reserve(x.size()));
+    HIPCHK(c->d_nk_cnt.reserve((size_t)n));
+    HIPCHK(hipMemcpyAsync(c->d_nk_x.p, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_nk_cnt.p, nsamp, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // x leaves scope: the copies have left the host
+    int base = 0;
+    return each_launch(c, sw, walkers, true, kWalkerListMax, "launch_nk", [&](int m, const WalkerList &L) {
+        const hipError_t e = launch_nk(c->P, m, L, c->nk_nmax, c->nk_nbin, c->nk_nq, 0, base, cap, c->d_nk_cnt.p, c->d_nk_x.p,
+                                       c->d_nk_C.p, c->d_nk_H.p, c->d_nk_nopen.p, c->d_nk_ninside.p, c->stream);
+        base += m;
+        return e;
+    });
+}
+
+int pigs_nk_read(pigs_ctx *c, double *C, int64_t *H, int64_t *nopen, int64_t *ninside, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->nk_nmax) return fail(PIGS_ERR_ARG, "pigs_nk_init first");
+    if (!C || !H || !nopen || !ninside) return fail(PIGS_ERR_ARG, "null output");
+    return read_and_reset(c, {{c->d_nk_C.p, (size_t)c->nk_nq, C}, {c->d_nk_H.p, c->nk_nvec, H}, {c->d_nk_nopen.p, 1, nopen},
+                              {c->d_nk_ninside.p, 1, ninside}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

@@ -199,6 +199,22 @@ AtmShape atm_shape(int dim, int Np);
 hipError_t launch_atm(const DevParams &P, const double *paths, int n, const WalkerList &list, const AtmShape &s, int window,
                       double rc2, double *T, unsigned long long *ntrip, unsigned long long *samples, hipStream_t st);
 
+// pigs_nk.hip: the momentum distribution on the vectors of pigs_sqv_* and the one-body density matrix on the Cartesian grid
+// of the minimum-image cell (pigs_nk_accumulate, pigs_nk_add).  k_nk, one workgroup of kNkThreads threads per listed walker,
+// reads that walker's samples (once-folded end-to-end vectors) from a tape: cnt[j] samples (at most cap) at
+// xs + j cap dim, j the walker (by_walker: the sampler's end tape) or base + the position in the list (pigs_nk_add).  Tiles of
+// kNkTile samples are staged in LDS as per-axis phasor tables, nk_lds_bytes = 16 dim kNkTile (nmax + 1) <= kNkLdsBudget for
+// every nmax that pigs_nk_init accepts.  A thread owns vectors and adds once to C [walker][Nq]; H [walker][nbin^dim],
+// nopen and ninside [walker] are 64-bit counts.  One thread owns an element of C per launch: a walker must not be listed
+// twice in ONE launch.
+constexpr int kNkThreads = 256;
+constexpr int kNkTile = 64;                      // samples staged per tile (PIGS_NK_TILE of include/pigs_hip.h)
+constexpr size_t kNkLdsBudget = 160 * 1024;      // LDS of one CU on gfx950
+size_t nk_lds_bytes(int dim, int nmax);
+hipError_t launch_nk(const DevParams &P, int n, const WalkerList &list, int nmax, int nbin, long long Nq, int by_walker,
+                     int base, int cap, const int *cnt, const double *xs, double *C, unsigned long long *H,
+                     unsigned long long *nopen, unsigned long long *ninside, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 
@@ -220,6 +236,10 @@ struct SweepParams {
                                                   // ONLY (tuning key "cm_fault"): the last range of every walker in k_cm withholds
                                                   // its Delta S and waiting workgroups give up after 2048 polls (forces the time-out path)
     double  delta_cm, log_cworm_density, rbin;
+    // the end tape (null: none): per walker and step, tape_count[w] = Nobdm if the worm loop ran, 0 otherwise, and
+    // tape_x[w][iobdm][dim] the once-folded end-to-end vector that the OBDM histogram of iteration iobdm took (pigs_nk_*)
+    int32_t *tape_count;
+    double  *tape_x;
 };
 hipError_t launch_sweep(const DevParams &P, const SweepParams &sp, int threads, double *paths, const double *VT,
                         const double *VTimg, const double *WF, uint32_t *rng, unsigned long long *counters, double *worm,

@@ -645,6 +645,27 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_atm_read_t
+
+     ! momentum distribution and one-body density matrix (include/pigs_hip.h, pigs_nk_*): looked up at run time, see
+     ! nk_bind; _init, _count, _vectors and _accumulate have the signatures of the pigs_sqv_* ones
+     function pigs_nk_add_t(ctx,n,walkers,nsamp,xend) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int32_t), value      :: n
+       integer(c_int32_t), intent(in) :: walkers(*),nsamp(*)
+       real(c_double), intent(in)     :: xend(*)       ! (dim,2,sum nsamp): head, tail of every pair
+       integer(c_int) :: rc
+     end function pigs_nk_add_t
+
+     function pigs_nk_read_t(ctx,C,H,nopen,ninside,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: C(*)          ! cosine sums (Nq,n_walkers)
+       integer(c_int64_t)             :: H(*)          ! counts (nbin**dim,n_walkers)
+       integer(c_int64_t)             :: nopen(*),ninside(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_nk_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -707,6 +728,14 @@ module pigs_capi
   procedure(pigs_atm_init_t), pointer       :: atm_init => null()
   procedure(pigs_grv_accumulate_t), pointer :: atm_accumulate => null()
   procedure(pigs_atm_read_t), pointer       :: atm_read => null()
+
+  ! bound by nk_bind (null until then)
+  procedure(pigs_sqv_init_t), pointer       :: nk_init => null()
+  procedure(pigs_sqv_count_t), pointer      :: nk_count => null()
+  procedure(pigs_sqv_vectors_t), pointer    :: nk_vectors => null()
+  procedure(pigs_sqv_accumulate_t), pointer :: nk_accumulate => null()
+  procedure(pigs_nk_add_t), pointer         :: nk_add => null()
+  procedure(pigs_nk_read_t), pointer        :: nk_read => null()
 
 contains
 
@@ -857,6 +886,19 @@ contains
     call c_f_procpointer(f(2),atm_accumulate)
     call c_f_procpointer(f(3),atm_read)
   end function atm_bind
+
+  ! The momentum-distribution entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function nk_bind()
+    type(c_funptr) :: f(6)
+    nk_bind = resolve_all('pigs_nk',[character(len=10) :: 'init','count','vectors','accumulate','add','read'],f)
+    if (.not. nk_bind) return
+    call c_f_procpointer(f(1),nk_init)
+    call c_f_procpointer(f(2),nk_count)
+    call c_f_procpointer(f(3),nk_vectors)
+    call c_f_procpointer(f(4),nk_accumulate)
+    call c_f_procpointer(f(5),nk_add)
+    call c_f_procpointer(f(6),nk_read)
+  end function nk_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -22,6 +22,7 @@ module pigs_estimators
   public :: normalize_vh, write_vh
   public :: normalize_g3, write_g3, write_g3ang
   public :: normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau
+  public :: normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec
 
   type est_params
      integer :: dim = 3, Np = 0, Nbin = 100, Nk = 50, Npw = 0
@@ -802,6 +803,75 @@ contains
     end do
     close (u)
   end subroutine write_v3tau
+
+  ! ---- momentum distribution (cosine sums C and the sample count nopen of pigs_nk_read) -> one walker's n(k) of one block
+  ! in the reference's NormalizeNr convention, zconf the diagonal configurations of the block:
+  !   B(0) = n(0) = nopen/(CWorm zconf Nobdm);   B(i) = n(k_i) = C(i)/(CWorm zconf Nobdm);   n0 = B(0)/Np
+  subroutine normalize_nk(cworm,zconf,Nobdm,Nq,C,nopen,B)
+    real(8), intent(in)    :: cworm,zconf,C(Nq)
+    integer, intent(in)    :: Nobdm,Nq
+    integer(8), intent(in) :: nopen
+    real(8), intent(out)   :: B(0:Nq)
+    real(8) :: den
+    den = cworm*zconf*real(Nobdm,8)
+    B(0)  = real(nopen,8)/den
+    B(1:) = C/den
+  end subroutine normalize_nk
+
+  ! one-body density matrix over the density per Cartesian bin of the minimum-image cell (counts H of pigs_nk_read, Ng
+  ! bins per axis): H/(CWorm zconf Nobdm density bin volume), 1 at r -> 0 like nr_vpi.out
+  subroutine normalize_nrvec(p,cworm,zconf,Nobdm,density,Ng,nv,H,R)
+    type(est_params), intent(in) :: p
+    real(8), intent(in)    :: cworm,zconf,density
+    integer, intent(in)    :: Nobdm,Ng,nv
+    integer(8), intent(in) :: H(nv)
+    real(8), intent(out)   :: R(nv)
+    real(8) :: den
+    integer :: k
+    den = cworm*zconf*real(Nobdm,8)*density
+    do k=1,p%dim
+       den = den*(p%Lbox(k)/real(Ng,8))
+    end do
+    R = real(H,8)/den
+  end subroutine normalize_nrvec
+
+  ! first line of n0_vpi*.out
+  subroutine n0_header(u)
+    integer, intent(in) :: u
+    write (u,'(a)') '# block, condensate fraction n0 = n(k=0)/Np, n(k=0) = open samples/(CWorm zconf Nobdm)'
+  end subroutine n0_header
+
+  ! one line of n0_vpi*.out
+  subroutine write_n0_block(u,iblock,Np,nk0)
+    integer, intent(in) :: u,iblock,Np
+    real(8), intent(in) :: nk0
+    write (u,'(20g20.10e3)') real(iblock),nk0/real(Np,8),nk0
+  end subroutine write_n0_block
+
+  ! nkvec_vpi.out: one line per vector, n = 0 first and then the stored ones: n_1..n_dim, |k|, n(k), error over the n blocks
+  subroutine write_nkvec(fname,p,Nq,nv,n,av,av2)
+    character(len=*), intent(in) :: fname
+    type(est_params), intent(in) :: p
+    integer, intent(in)    :: Nq,n
+    integer(4), intent(in) :: nv(p%dim,Nq)
+    real(8), intent(inout) :: av(0:Nq),av2(0:Nq)
+    integer :: i,k,u
+    real(8) :: q2
+    character(len=24) :: fmt
+    write (fmt,'(a,i0,a)') '(',p%dim,'i6,3g20.10e3)'
+    open (newunit=u,file=fname)
+    av  = av/real(n)
+    av2 = av2/real(n)
+    write (u,fmt) (0,k=1,p%dim),0.d0,av(0),variance(n,av(0),av2(0))
+    do i=1,Nq
+       q2 = 0.d0
+       do k=1,p%dim
+          q2 = q2+(real(nv(k,i),8)*p%qbin(k))**2
+       end do
+       write (u,fmt) (nv(k,i),k=1,p%dim),sqrt(q2),av(i),variance(n,av(i),av2(i))
+    end do
+    close (u)
+  end subroutine write_nkvec
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

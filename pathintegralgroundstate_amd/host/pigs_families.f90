@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order, van_hove, triplet, three_body.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -62,6 +62,10 @@ module pigs_families
      real(8) :: atm_nu = 1.d0                       ! the triple-dipole coupling, in the run's units (energy length^9)
      real(8) :: atm_rc = 0.d0                       ! <= 0: half the shortest side
      integer :: atm_window = -1                     ! < 0: slice Nb alone
+     logical :: momentum = .false.
+     integer :: nk_nmax = 8, nk_nbin = 32
+     real(8) :: cworm = 0.d0                        ! the run's CWorm and Nobdm (momentum needs the worm sector)
+     integer :: nobdm = 0
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -368,17 +372,41 @@ module pigs_families
      procedure :: write_average => atm_write_average
   end type atm_family
 
-  integer, parameter :: NFAM = 11
+  ! momentum: the off-diagonal family.  Its samples are the end-to-end vectors of the open walkers, so it is queued for all
+  ! walkers after a step (step / add) and not with the diagonal ones (queue does nothing); its block is the one that
+  ! normalises nr_vpi.out, with zconf = idiag_aux(w) (read_nk / block_nk; read and block do nothing), and a walker's files
+  ! average over the blocks it counted there (nbl).
+  type, extends(family) :: nk_family
+     integer :: nbin = 0, nv = 0, nobdm = 0
+     type(qgrid) :: g
+     real(8), allocatable :: raw(:,:),b(:),sh(:),br(:)      ! (b: index 1 is n = 0, index i + 1 the stored vector i)
+     integer(c_int64_t), allocatable :: h(:,:),nopen(:),nin(:)
+     integer, allocatable :: nbl(:),un(:)
+     integer :: unav = -1
+     type(block_series) :: sVec,sSh,sR
+   contains
+     procedure :: check => nk_check
+     procedure :: banner => nk_banner
+     procedure :: setup => nk_setup
+     procedure :: queue => nk_queue
+     procedure :: read => nk_read_nothing
+     procedure :: block => nk_block_nothing
+     procedure :: average => nk_average
+     procedure :: write_walker => nk_write_walker
+     procedure :: write_average => nk_write_average
+  end type nk_family
+
+  integer, parameter :: NFAM = 12
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
   ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
-  ! 9 van_hove, 10 triplet, 11 three_body
+  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -392,6 +420,10 @@ module pigs_families
      procedure :: average => set_average
      procedure :: write_walker => set_write_walker
      procedure :: write_average => set_write_average
+     procedure :: nk_step => set_nk_step
+     procedure :: nk_add => set_nk_add
+     procedure :: nk_read => set_nk_read
+     procedure :: nk_block => set_nk_block
   end type family_set
 
 contains
@@ -414,7 +446,74 @@ contains
     if (keys%van_hove)        allocate (vh_family :: fs%slot(9)%f)
     if (keys%triplet)         allocate (g3_family :: fs%slot(10)%f)
     if (keys%three_body)      allocate (atm_family :: fs%slot(11)%f)
+    if (keys%momentum)        allocate (nk_family :: fs%slot(12)%f)
   end subroutine set_create
+
+  ! momentum, device-resident sampler: the samples of the step just queued, of all NW walkers
+  subroutine set_nk_step(fs,ctx,NW)
+    class(family_set), intent(inout) :: fs
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: NW
+    integer :: w
+    if (.not. allocated(fs%slot(12)%f)) return
+    call pigs_check(nk_accumulate(ctx,int(NW,c_int32_t),[(int(w-1,c_int32_t),w=1,NW)]),'pigs_nk_accumulate')
+  end subroutine set_nk_step
+
+  ! momentum, host-driven sampler: xend(dim,2,NW) of the walkers with act, where their OBDM histogram is taken
+  subroutine set_nk_add(fs,ctx,NW,act,xend)
+    class(family_set), intent(inout) :: fs
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: NW
+    logical, intent(in)     :: act(NW)
+    real(8), intent(in)     :: xend(:,:,:)
+    integer(c_int32_t) :: wl(NW),ns(NW)
+    real(8) :: x(size(xend,1),2,NW)
+    integer :: w,n
+    if (.not. allocated(fs%slot(12)%f)) return
+    n = 0
+    do w=1,NW
+       if (.not. act(w)) cycle
+       n = n+1
+       wl(n) = w-1; ns(n) = 1; x(:,:,n) = xend(:,:,w)
+    end do
+    if (n>0) call pigs_check(nk_add(ctx,int(n,c_int32_t),wl,ns,x),'pigs_nk_add')
+  end subroutine set_nk_add
+
+  ! momentum, end of a block: the sums of every walker; those of the walkers with norm are zeroed on the device (the others
+  ! go on accumulating until the block that normalises them, like the OBDM histogram)
+  subroutine set_nk_read(fs,ctx,norm)
+    class(family_set), intent(inout) :: fs
+    type(c_ptr), intent(in) :: ctx
+    logical, intent(in)     :: norm(:)
+    if (.not. allocated(fs%slot(12)%f)) return
+    select type (f => fs%slot(12)%f)
+    type is (nk_family)
+       f%reset = merge(1_c_int32_t,0_c_int32_t,norm)
+       call pigs_check(nk_read(ctx,f%raw,f%h,f%nopen,f%nin,f%reset),'pigs_nk_read')
+    end select
+  end subroutine set_nk_read
+
+  ! momentum: walker w normalises the block, with zconf diagonal configurations
+  subroutine set_nk_block(fs,w,zconf,info,vec)
+    class(family_set), intent(inout) :: fs
+    integer, intent(in)           :: w
+    real(8), intent(in)           :: zconf
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    if (.not. allocated(fs%slot(12)%f)) return
+    select type (f => fs%slot(12)%f)
+    type is (nk_family)
+       call normalize_nk(f%ep%CWorm,zconf,f%nobdm,f%g%nq,f%raw(:,w),int(f%nopen(w),8),f%b)
+       call sqv_shell_means(f%g%nq,f%g%shell,f%g%nsh,f%g%mult,f%b(2:),f%sh)
+       call normalize_nrvec(f%ep,f%ep%CWorm,zconf,f%nobdm,f%run%density,f%nbin,f%nv,int(f%h(:,w),8),f%br)
+       call series_add(f%sVec,w,f%b,vec)
+       call series_add(f%sSh,w,f%sh,vec)
+       call series_add(f%sR,w,f%br,vec)
+       call count_add(f%cnt,vec)
+       f%nbl(w) = f%nbl(w)+1
+       call write_n0_block(f%un(w),info%iblock,f%ep%Np,f%b(1))
+    end select
+  end subroutine set_nk_block
 
   ! refuses what the keys cannot have (exit status 2) and fills in the windows that were left out
   subroutine set_check(fs,keys,dim,Nb,trap)
@@ -1734,5 +1833,127 @@ contains
     call write_v3tau('v3tau_vpi.out',f%run%Nb,f%window,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
     close (f%upav)
   end subroutine atm_write_average
+
+  !---------------------------------------------------------------------
+  ! momentum: the momentum distribution n(k) of a periodic system with the worm sector on, on the box-commensurate vectors
+  ! |n_k| <= nk_nmax, the condensate fraction and the one-body density matrix on nk_nbin bins per axis of the minimum-image
+  ! cell -- nkvec_vpi.out (one line per vector, n = 0 first), nk_vpi.out (one line per |k| shell), n0_vpi.out (one line per
+  ! block) and nrvec_vpi.out (one line per bin), normalised in the blocks and with the zconf of nr_vpi.out
+
+  subroutine nk_check(f,keys,dim,Nb,trap)
+    class(nk_family), intent(inout)  :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    integer :: nbmax
+    if (trap) call needs_periodic('momentum','in a trap the one-body density matrix is not translation-invariant')
+    if (.not. (keys%cworm>0.d0)) then
+       write (0,'(a)') ' pigs_vpi: momentum = T needs the worm sector (CWorm > 0): its samples are the open worldlines'
+       stop 2
+    end if
+    call check_vectors('momentum','nk',keys%nk_nmax,dim)
+    nbmax = merge(128,merge(1024,4096,dim==2),dim==3)
+    if (keys%nk_nbin<1 .or. keys%nk_nbin>nbmax) then
+       write (0,'(a,i0,a,i0,a,i0,a)') ' pigs_vpi: momentum = T: nk_nbin = ',keys%nk_nbin,' must lie in 1 .. ',nbmax,' (dim = ',dim,')'
+       stop 2
+    end if
+    if (.not. nk_bind()) call no_backend('momentum','pigs_nk_init / _count / _vectors / _accumulate / _add / _read', &
+         & 'the momentum distribution runs')
+  end subroutine nk_check
+
+  subroutine nk_banner(f,keys,trap)
+    class(nk_family), intent(in)  :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,i0,a,i0,a)', '  > Momentum n(k), n0   : on (|n_k| <= ',keys%nk_nmax,', ',keys%nk_nbin, &
+         & ' bins per axis: nkvec_vpi.out, nk_vpi.out, n0_vpi.out, nrvec_vpi.out)'
+  end subroutine nk_banner
+
+  subroutine nk_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(nk_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: w
+    call family_begin(f,run,ep,NW)
+    f%nbin = keys%nk_nbin
+    f%nobdm = keys%nobdm
+    f%nv = f%nbin**ep%dim
+    call pigs_check(nk_init(ctx,int(keys%nk_nmax,c_int32_t),int(f%nbin,c_int32_t)),'pigs_nk_init')
+    call qgrid_fill(f%g,ctx,ep,nk_count,nk_vectors,'pigs_nk')
+    allocate (f%raw(f%g%nq,NW),f%h(f%nv,NW),f%nopen(NW),f%nin(NW),f%b(f%g%nq+1),f%sh(f%g%nsh),f%br(f%nv),f%nbl(NW),f%un(NW))
+    f%nbl = 0
+    call series_create(f%sVec,f%g%nq+1,NW,nvec)
+    call series_create(f%sSh,f%g%nsh,NW)
+    call series_create(f%sR,f%nv,NW,nvec)
+    call count_create(f%cnt,nvec)
+    do w=1,NW
+       open (newunit=f%un(w),file='n0_vpi'//trim(run%suffix(w))//'.out')
+       call n0_header(f%un(w))
+    end do
+    if (run%averages) then
+       open (newunit=f%unav,file='n0_vpi.out')
+       call n0_header(f%unav)
+    end if
+  end subroutine nk_setup
+
+  ! (the diagonal walkers of a step bring no sample: see set_nk_step, set_nk_add)
+  subroutine nk_queue(f,ctx,nd,wl)
+    class(nk_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+  end subroutine nk_queue
+
+  ! (set_nk_read)
+  subroutine nk_read_nothing(f,ctx)
+    class(nk_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+  end subroutine nk_read_nothing
+
+  ! (set_nk_block)
+  subroutine nk_block_nothing(f,w,info,vec)
+    class(nk_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+  end subroutine nk_block_nothing
+
+  ! (the shell means are those of the averaged vectors)
+  subroutine nk_average(f,info,vec)
+    class(nk_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sVec,vec,nall)
+       call series_average(f%sR,vec,nall)
+       call sqv_shell_means(f%g%nq,f%g%shell,f%g%nsh,f%g%mult,f%sVec%mean(2:),f%sh)
+       call series_add_mean(f%sSh,f%sh)
+       call write_n0_block(f%unav,info%iblock,f%ep%Np,f%sVec%mean(1))
+    end if
+  end subroutine nk_average
+
+  subroutine nk_write_walker(f,suffix,w,nblocks)
+    class(nk_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_nkvec('nkvec_vpi'//trim(suffix)//'.out',f%ep,f%g%nq,f%g%n,f%nbl(w),f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_sqshell('nk_vpi'//trim(suffix)//'.out',f%g%nsh,f%g%q,f%g%mult,f%nbl(w),f%sSh%sum(:,w),f%sSh%sq(:,w))
+    call write_grvec('nrvec_vpi'//trim(suffix)//'.out',f%ep,f%nbin,f%nv,f%nbl(w),f%sR%sum(:,w),f%sR%sq(:,w))
+    close (f%un(w))
+  end subroutine nk_write_walker
+
+  subroutine nk_write_average(f)
+    class(nk_family), intent(inout) :: f
+    call write_nkvec('nkvec_vpi.out',f%ep,f%g%nq,f%g%n,f%cnt%nav,f%sVec%asum,f%sVec%asq)
+    call write_sqshell('nk_vpi.out',f%g%nsh,f%g%q,f%g%mult,f%cnt%nav,f%sSh%asum,f%sSh%asq)
+    call write_grvec('nrvec_vpi.out',f%ep,f%nbin,f%nv,f%cnt%nav,f%sR%asum,f%sR%asq)
+    close (f%unav)
+  end subroutine nk_write_average
 
 end module pigs_families

@@ -10,7 +10,9 @@ module pigs_host_hooks
   use pigs_rng
   use pigs_sampler
   use pigs_estimators, only: est_params, normalize_vh, write_vh, normalize_g3, write_g3, write_g3ang, &
-       & normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau
+       & normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau, &
+       & normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec, write_sqshell, write_grvec, &
+       & sqv_shells, sqv_shell_means
 
   implicit none
   private
@@ -262,6 +264,46 @@ contains
     v3 = B(1,:); cnt = B(2,:)
     call write_v3tau(cstring(ft),Nb,window,dt,nblk,a,a2)
   end subroutine hs_atm_files
+
+  ! The momentum-distribution normalisation and writers of the front end on given sums: nblk blocks of one walker, cosine
+  ! sums C (Nq,nblk) on the vectors nvq (dim,Nq), counts H (nbin**dim,nblk), nopen and zconf per block -> nk (0:Nq) and rho1 of
+  ! the LAST block, and the four files (names: C strings): fv per vector, fs per shell, f0 per block, fr per bin
+  subroutine hs_nk_files(dim,Np,Lbox,density,cworm,Nobdm,Nq,nvq,nbin,nblk,zconf,C,nopen,H,nk,rho1,fv,fs,f0,fr) &
+       & bind(C,name='hs_nk_files')
+    integer(c_int), value :: dim,Np,Nobdm,Nq,nbin,nblk
+    real(c_double), value :: density,cworm
+    real(c_double), intent(in)     :: Lbox(dim),zconf(nblk),C(Nq,nblk)
+    integer(c_int32_t), intent(in) :: nvq(dim,Nq)
+    integer(c_int64_t), intent(in) :: nopen(nblk),H(nbin**dim,nblk)
+    real(c_double), intent(out)    :: nk(0:Nq),rho1(nbin**dim)
+    character(kind=c_char), intent(in) :: fv(*),fs(*),f0(*),fr(*)
+    type(est_params) :: p
+    real(8), allocatable :: a(:),a2(:),ar(:),ar2(:),sh(:),as(:),as2(:),q(:)
+    integer, allocatable :: shell(:),mult(:)
+    integer :: ib,u,nsh,nv
+    p%dim = dim; p%Np = Np; p%pi = acos(-1.d0); p%CWorm = cworm
+    p%Lbox = 1.d0; p%Lbox(1:dim) = Lbox; p%LboxHalf = 0.5d0*p%Lbox; p%qbin = 2.d0*p%pi/p%Lbox
+    nv = nbin**dim
+    allocate (shell(Nq))
+    call sqv_shells(p,Nq,nvq,shell,nsh,q,mult)
+    allocate (a(0:Nq),a2(0:Nq),ar(nv),ar2(nv),sh(nsh),as(nsh),as2(nsh))
+    a = 0.d0; a2 = 0.d0; ar = 0.d0; ar2 = 0.d0; as = 0.d0; as2 = 0.d0
+    open (newunit=u,file=cstring(f0))
+    call n0_header(u)
+    do ib=1,nblk
+       call normalize_nk(cworm,zconf(ib),Nobdm,Nq,C(:,ib),int(nopen(ib),8),nk)
+       call sqv_shell_means(Nq,shell,nsh,mult,nk(1:),sh)
+       call normalize_nrvec(p,cworm,zconf(ib),Nobdm,density,nbin,nv,int(H(:,ib),8),rho1)
+       a = a+nk; a2 = a2+nk*nk
+       as = as+sh; as2 = as2+sh*sh
+       ar = ar+rho1; ar2 = ar2+rho1*rho1
+       call write_n0_block(u,ib,Np,nk(0))
+    end do
+    close (u)
+    call write_nkvec(cstring(fv),p,Nq,nvq,nblk,a,a2)
+    call write_sqshell(cstring(fs),nsh,q,mult,nblk,as,as2)
+    call write_grvec(cstring(fr),p,nbin,nv,nblk,ar,ar2)
+  end subroutine hs_nk_files
 
   ! a C string as a Fortran one
   function cstring(c) result(f)

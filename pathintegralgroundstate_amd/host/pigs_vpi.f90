@@ -65,6 +65,12 @@
 ! the bare geometric sum) -- v3_vpi.out, one line per block: the block, V3/Np over the window, and its pressure
 ! P3 = 9 density (V3/Np)/dim (cut at atm_rc, no tail correction); v3tau_vpi.out, one line per window slice: a,
 ! tau_a = (a-Nb) dt, V3/Np and its error, the mean number of triplets)
+! (momentum = T, periodic systems with CWorm > 0 only: the momentum distribution on the box-commensurate vectors
+! |n_k| <= nk_nmax (default 8) from the end-to-end vectors of the open worldlines, every sample of the OBDM histogram and
+! those beyond rcut too, and the one-body density matrix on nk_nbin (default 32) bins per axis of the minimum-image cell,
+! normalised with nr_vpi.out's zconf in the blocks that normalise nr_vpi.out -- nkvec_vpi.out, one line per vector (n = 0
+! first): n_1..n_dim, |k|, n(k), error; nk_vpi.out, one line per |k| shell; n0_vpi.out, one line per block: block, n0,
+! n(k=0); nrvec_vpi.out, one line per bin: the bin centre, rho1/density, error)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -121,6 +127,8 @@ program pigs_vpi
   logical           :: three_body
   integer           :: atm_window
   real (kind=8)     :: atm_nu,atm_rc
+  logical           :: momentum
+  integer           :: nk_nmax,nk_nbin
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
   logical           :: sampler_auto
@@ -143,7 +151,8 @@ program pigs_vpi
        &             bond_order,bo_rnb,bo_nhist,bo_nr,bo_window, &
        &             van_hove,vh_ntau,vh_window,vh_nself,vh_rself, &
        &             triplet,g3_nr,g3_na,g3_rmax,g3_window, &
-       &             three_body,atm_nu,atm_rc,atm_window
+       &             three_body,atm_nu,atm_rc,atm_window, &
+       &             momentum,nk_nmax,nk_nbin
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -175,6 +184,7 @@ program pigs_vpi
   bond_order = .false.; bo_rnb = 0.d0; bo_nhist = 50; bo_nr = -1; bo_window = 0
   van_hove = .false.; vh_ntau = 0; vh_window = -1; vh_nself = 50; vh_rself = 0.d0
   triplet = .false.; g3_nr = 10; g3_na = 20; g3_rmax = 0.d0; g3_window = -1
+  momentum = .false.; nk_nmax = 8; nk_nbin = 32
   three_body = .false.; atm_nu = -huge(1.d0); atm_rc = 0.d0; atm_window = -1        ! (atm_nu: a value nobody gives, left out -> 1)
 
   read (5,nml=system,iostat=ios);  rewind (5)
@@ -250,7 +260,8 @@ program pigs_vpi
        & van_hove=van_hove,vh_ntau=vh_ntau,vh_window=vh_window,vh_nself=vh_nself,vh_rself=vh_rself, &
        & triplet=triplet,g3_nr=g3_nr,g3_na=g3_na,g3_rmax=g3_rmax,g3_window=g3_window, &
        & three_body=three_body,atm_nu_given=atm_nu/=-huge(1.d0),atm_nu=merge(atm_nu,1.d0,atm_nu/=-huge(1.d0)), &
-       & atm_rc=atm_rc,atm_window=atm_window)
+       & atm_rc=atm_rc,atm_window=atm_window, &
+       & momentum=momentum,nk_nmax=nk_nmax,nk_nbin=nk_nbin,cworm=CWorm,nobdm=Nobdm)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 
@@ -669,6 +680,8 @@ contains
                     end do
                  end if
               end do
+              ! the end-to-end vectors that the step's worm loops handed to the OBDM histogram (momentum = T)
+              call fams%nk_step(ctx,NW)
            end if
         else
         ! ---- open / close attempt (reference vpi.f90:302-323)
@@ -751,6 +764,7 @@ contains
                  do w=1,NW
                     if (act(w)) call obdm_accumulate(ep,s%xend(:,:,w),nrho(:,:,w))
                  end do
+                 call fams%nk_add(ctx,NW,act,s%xend)
               end if
            end do
         end if
@@ -813,6 +827,7 @@ contains
         end if
      end if
      call fams%read(ctx)
+     if (.not. trap) call fams%nk_read(ctx,idiag_aux/Nstep>=1)
      info%iblock = iblock
      mE = 0.d0; mT = 0.d0; nd = 0
      vec = 0.d0
@@ -843,6 +858,7 @@ contains
               call normalize_nr(ep,density,real(idiag_aux(w),8),Nobdm,nrho(:,:,w))
               call series_add(sNr,w,nrho(:,:,w),vec)
               call count_add(cNr,vec)
+              call fams%nk_block(w,real(idiag_aux(w),8),info,vec)
            end if
            idiag_aux(w) = 0
            nrho(:,:,w)  = 0.d0

@@ -72,6 +72,14 @@ geometric term (1 + 3 cos cos cos)/(r_ij r_ik r_jk)**3 over the triplets whose t
 ntrip counts them; with the coupling nu in the run's own units (energy * length**9; the library knows no element):
   V3/N(tau_a) = nu * T / (S_w * Np)                     (its window mean is the perturbative <V3>/N)
   P3          = 9 * density * (V3/N) / dim              (pressure_atm: the sum is homogeneous of degree -9; cut at rc, no tail)
+
+Momentum distribution and one-body density matrix (normalize_nk, normalize_nrvec, PigsContext.nk_read, pigs_nk_*): C sums
+cos(k.x) over the end-to-end vectors x of the open worldlines on the box-commensurate vectors, nopen counts them (the sum of
+k = 0) and H bins them on the Cartesian grid of the minimum-image cell.  In the reference's NormalizeNr convention (zconf
+the diagonal configurations of the block, rho1(r)/density -> 1 at r -> 0):
+  n(k)              = C / (CWorm * zconf * Nobdm),   n(0) = nopen / (CWorm * zconf * Nobdm),   n0 = n(0) / Np
+  rho1(bin)/density = H / (CWorm * zconf * Nobdm * density * bin volume)
+and the sum of n(k) over all k, -k included, is Np.
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -428,6 +436,43 @@ def pressure_atm(v3_per_particle, density, dim):
     Axilrod-Teller-Muto sum is homogeneous of degree -9 in the lengths, so its virial is 9 V3 (P3 = 9 nu <T>/(dim Volume)
     with V3/N as normalize_atm gives it).  Triplets with a side beyond rc are not in V3 and no tail correction is made."""
     return 9.0 * density * np.asarray(v3_per_particle, np.float64) / dim
+
+
+def normalize_nk(sums, cworm, zconf, nobdm, Np, n=None, Lbox=None):
+    """sums: the dict of nk_read (C [W, Nq], nopen [W]) or one walker's slice of it; cworm, nobdm: the run's CWorm and
+    Nobdm; zconf: the diagonal configurations of the block ([W] or a scalar), the reference's NormalizeNr divisor.
+    Returns a dict: nk [.., Nq] = C/(cworm*zconf*nobdm), the momentum distribution per stored vector (-k has the same
+    value), nk0 [..] that of k = 0, n0 [..] = nk0/Np the condensate fraction, and, with the vectors n [Nq, dim]
+    (nk_vectors) and Lbox given, k, nk_shell [.., n_shells] and mult from shell_average.  A block without diagonal
+    configurations gives no finite value."""
+    Cs = np.asarray(sums["C"], dtype=np.float64)
+    no = np.asarray(sums["nopen"], dtype=np.float64)
+    z = np.broadcast_to(np.asarray(zconf, dtype=np.float64), no.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = float(cworm) * z * float(nobdm)
+        nk = Cs / den.reshape(den.shape + (1,))
+        nk0 = no / den
+    out = {"nk": nk, "nk0": nk0, "n0": nk0 / float(Np)}
+    if n is not None:
+        out["k"], out["nk_shell"], out["mult"] = shell_average(n, Lbox, nk)
+    return out
+
+
+def normalize_nrvec(sums, cworm, zconf, nobdm, density, Lbox, dim):
+    """sums: the dict of nk_read (H [W, nbin, ..dim times]) or one walker's slice of it.  Returns a dict: rho1 (same
+    shape as H) = H/(cworm*zconf*nobdm*density*bin volume), the one-body density matrix over the density per Cartesian
+    bin of the minimum-image cell in the reference's normalisation (1 at r -> 0), and the bin centres x (a list of dim
+    arrays, x[k] along axis k of the box; array axis -1-k).  A block without diagonal configurations gives no finite value."""
+    H = np.asarray(sums["H"], dtype=np.float64)
+    nbin = H.shape[-1]
+    L = np.asarray(Lbox, dtype=np.float64)[:dim]
+    b = L / float(nbin)
+    z = np.broadcast_to(np.asarray(zconf, dtype=np.float64), H.shape[:H.ndim - dim])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = float(cworm) * z * float(nobdm) * float(density) * float(np.prod(b))
+        rho1 = H / den.reshape(den.shape + (1,) * dim)
+    x = [-0.5 * L[k] + (np.arange(nbin) + 0.5) * b[k] for k in range(dim)]
+    return {"rho1": rho1, "x": x}
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
