@@ -11,6 +11,17 @@ Normalisations (one walker, one block with S samples, i.e. S diagonal steps in t
   trap profiles        planar c / (S b^min(dim,2)), radial c / (S dV_j), pair c / (S Np dV_j); b = 2h/Nbin, br = h/Nbin
   pressure             density / dim (2 Kin/Np - W/Np), W/Np the mean over the slices Nb-window..Nb+window
   |q| shells           the mean of the block values over the stored vectors of equal |q|
+  bond order           n = S (2 window + 1) slices: Q4, Q6, <q4(i)>, <q6(i)>: raw / n; coordination sum n_i / (n Np);
+                       P(q_l) = counts Nh / (n Np); G6 = G / GN per radial bin, 0 in a bin without a pair
+  van Hove             G_d = distinct / (S n_pairs(l) Np density dV_j), G_s = self / (S n_pairs(l) Np dV_j),
+                       dV_j = V_d(j b) - V_d((j-1) b) on the grid of either part
+  triplets             g3 = trip / (n Np density^2 dV_lo dV_hi m w_q), m = 1/2 for lo = hi, w_q = 1/Na in 3D and
+                       (acos c_q - acos c_q+1)/pi in 2D, c_q = -1 + 2 q/Na; P(cos theta) = sum over the leg bins of trip,
+                       divided by its integral over [-1, 1] (0 without a triplet)
+  three-body energy    V3/N = nu T / (S Np) per window slice, the mean triplets ntrip / S, P3 = 9 density (V3/N) / dim
+  momentum             n(k) = C / (CWorm zconf Nobdm), n(0) = open samples / (CWorm zconf Nobdm), n0 = n(0) / Np;
+                       rho_1/rho per Cartesian bin = H / (CWorm zconf Nobdm density prod_k L_k / Ng); zconf the diagonal
+                       configurations since the walker's last normalised block
 
 Statistics: a block counts for a walker only if the walker had a diagonal step in it.  A file's mean is the mean of the
 counted block values; its error the "variance" of the reference's files, sqrt((<b^2> - <b>^2) / n) over the n counted
@@ -143,6 +154,89 @@ def norm_density(planar, radial, pair, S, dim, Np, Nbin, h):
         return (planar / (_s(S, planar.ndim - np.ndim(S)) * b ** min(dim, 2)),
                 np.asarray(radial, np.float64) / (_s(S, 1) * dv),
                 np.asarray(pair, np.float64) / (_s(S, 1) * Np * dv))
+
+
+def shell_volumes(dim, n, b):
+    j = np.arange(1, n + 1, dtype=np.float64)
+    return ball(dim) * ((j * b) ** dim - ((j - 1.0) * b) ** dim)
+
+
+def norm_bop(rawS, H, G, GN, S, Np, window):
+    """rawS [..., 8], H [..., 2, Nh], G, GN [..., Nr], S [...].  Returns (B [..., 5]: Q4, Q6, <q4(i)>, <q6(i)>, coordination;
+    P [..., 2, Nh]; G6 [..., Nr])."""
+    rawS, H = np.asarray(rawS, np.float64), np.asarray(H, np.float64)
+    G, GN = np.asarray(G, np.float64), np.asarray(GN, np.float64)
+    Nh = H.shape[-1]
+    with np.errstate(all="ignore"):
+        n = _s(S, 1) * (2 * window + 1)
+        B = np.stack([rawS[..., 0], rawS[..., 2], rawS[..., 4], rawS[..., 5], rawS[..., 6] / Np], axis=-1) / n
+        P = H * Nh / (_s(S, 2) * (2 * window + 1) * Np)
+        G6 = np.where(GN > 0, G / np.where(GN > 0, GN, 1.0), 0.0)
+    return B, P, G6
+
+
+def norm_vh(cself, cdist, S, Np, window, density, rbin, sbin, dim):
+    """cself [..., Ntau+1, Ns], cdist [..., Ntau+1, Nr], S [...].  Returns (G_s, G_d)."""
+    cself, cdist = np.asarray(cself, np.float64), np.asarray(cdist, np.float64)
+    nl = cdist.shape[-2]
+    pairs = (2 * window + 1 - np.arange(nl)).astype(np.float64)[:, None]
+    with np.errstate(all="ignore"):
+        den = _s(S, 2) * pairs * Np
+        return (cself / (den * shell_volumes(dim, cself.shape[-1], sbin)),
+                cdist / (den * density * shell_volumes(dim, cdist.shape[-1], rbin)))
+
+
+def norm_g3(trip, pair, S, Np, window, density, rbin, dim):
+    """trip [..., Nr (Nr+1)/2, Na] on the packed triangle lo <= hi (rows lo), pair [..., Nr], S [...].  Returns (g2, g3,
+    P(cos theta) [..., Na])."""
+    trip, pair = np.asarray(trip, np.float64), np.asarray(pair, np.float64)
+    Nr, Na = pair.shape[-1], trip.shape[-1]
+    vol = shell_volumes(dim, Nr, rbin)
+    lo = np.array([a for a in range(Nr) for _ in range(a, Nr)])
+    hi = np.array([b for a in range(Nr) for b in range(a, Nr)])
+    assert lo.size == trip.shape[-2]
+    m = np.where(lo == hi, 0.5, 1.0)
+    if dim == 3:
+        w = np.full(Na, 1.0 / Na)
+    else:
+        c = np.clip(-1.0 + 2.0 * np.arange(Na + 1) / Na, -1.0, 1.0)
+        w = (np.arccos(c[:-1]) - np.arccos(c[1:])) / math.pi
+    h = trip.sum(axis=-2)
+    tot = h.sum(axis=-1, keepdims=True) * (2.0 / Na)
+    with np.errstate(all="ignore"):
+        n = _s(S, 1) * (2 * window + 1)
+        g2 = pair / (n * Np * density * vol)
+        g3 = trip / (n[..., None] * Np * density ** 2 * (vol[lo] * vol[hi] * m)[:, None] * w)
+        pang = np.where(tot > 0, h / np.where(tot > 0, tot, 1.0), 0.0)
+    return g2, g3, pang
+
+
+def norm_atm(T, ntrip, S, Np, nu, density, dim):
+    """T, ntrip [..., 2 window + 1], S [...].  Returns (V3/N per slice, mean triplets per slice, V3/N over the window,
+    P3 of that)."""
+    with np.errstate(all="ignore"):
+        v3 = nu * np.asarray(T, np.float64) / (_s(S, 1) * Np)
+        nt = np.asarray(ntrip, np.float64) / _s(S, 1)
+    win = v3.sum(axis=-1) / v3.shape[-1]
+    return v3, nt, win, 9.0 * density * win / dim
+
+
+def norm_nk(C, nopen, cworm, zconf, nobdm, Np):
+    """C [..., Nq], nopen, zconf [...].  Returns (n(k) [..., Nq + 1] with k = 0 first, n0 [...])."""
+    with np.errstate(all="ignore"):
+        den = cworm * np.asarray(zconf, np.float64) * nobdm
+        nk = np.concatenate([np.asarray(nopen, np.float64)[..., None], np.asarray(C, np.float64)], axis=-1) / den[..., None]
+    return nk, nk[..., 0] / Np
+
+
+def norm_nrvec(H, cworm, zconf, nobdm, density, Lbox, dim):
+    """H [..., Ng (dim axes)], zconf [...]."""
+    H = np.asarray(H, np.float64)
+    cell = 1.0
+    for k in range(dim):
+        cell = cell * (float(Lbox[k]) / H.shape[-1])
+    with np.errstate(all="ignore"):
+        return H / (_s(cworm * np.asarray(zconf, np.float64) * nobdm, dim) * density * cell)
 
 
 def pressure(kin, w, density, dim):

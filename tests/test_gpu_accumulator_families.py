@@ -1,7 +1,9 @@
 """The per-walker accumulator families on the MI355X where they meet: one context keeps ONE set of launch marks
 (csrc/pigs_walker_split.h) for the five families that may not list a walker twice in a launch.  Interleaved calls of
 fqt, sqv, tau, fqv and fqs with repeated walkers must leave in every family exactly the bits and sample counts that the
-same calls of that family alone leave in a fresh context on the same worldlines."""
+same calls of that family alone leave in a fresh context on the same worldlines.  The same again with bop, atm and nk
+(pigs_nk_add), which take launches on the same marks, and grv, vh and g3, which advance the launch counter without
+checking it, interleaved between them."""
 import numpy as np
 import pytest
 
@@ -40,4 +42,54 @@ def test_interleaved_families_keep_their_own_bits(gpu_lib):
             t = together[f][k]
             assert a.shape == t.shape and a.dtype == t.dtype and a.dtype.itemsize == 8, (f, k)
             assert np.any(a != 0), (f, k)
+            assert np.array_equal(a.view(np.uint64), t.view(np.uint64)), (f, k)
+
+
+# bop, atm and nk (through nk_add) take launches on the same marks; grv, vh and g3 advance the same launch counter and
+# may list a walker twice in a launch.  (walkers, and for nk the samples per listed walker)
+MORE = [("bop", [2, 0, 2]), ("grv", [1, 1, 0]), ("fqt", [2, 0, 2]), ("atm", [0, 2, 0]), ("vh", [2, 2, 1]), ("nk", [1, 1, 2], [2, 1, 3]),
+        ("sqv", [2, 2]), ("g3", [0, 1, 0, 0]), ("bop", None), ("tau", [0, 2, 0]), ("atm", [1, 1, 2]), ("nk", [2, 0], [1, 2]),
+        ("fqv", [1, 1, 2]), ("grv", None), ("g3", [2, 2]), ("fqs", [2, 1, 2]), ("vh", [0, 0, 0]), ("atm", None), ("fqt", None)]
+LISTED = {"fqt": [2, 1, 3], "sqv": [0, 0, 2], "tau": [2, 0, 1], "fqv": [0, 2, 1], "fqs": [0, 1, 2], "bop": [2, 1, 3],
+          "atm": [3, 3, 3], "grv": [2, 3, 1], "vh": [3, 1, 2], "g3": [3, 1, 2], "nk": [2, 3, 4]}
+
+
+def _run_more(gpu_lib, cfg, VT, WF, P, init, pairs, families):
+    with gpu_lib.PigsContext(cfg, VT, WF, n_walkers=P.shape[0]) as ctx:
+        ctx.upload_all(P)
+        for f in families:
+            getattr(ctx, f + "_init")(*init[f])
+        at = 0
+        for f, walkers, *nsamp in MORE:
+            if f == "nk":                                           # the same pairs whether nk is alone or not
+                n = sum(nsamp[0])
+                if f in families:
+                    ctx.nk_add(walkers, nsamp[0], pairs[at:at + n])
+                at += n
+            elif f in families:
+                getattr(ctx, f + "_accumulate")(walkers)
+        return {f: getattr(ctx, f + "_read")() for f in families}
+
+
+def test_interleaved_eleven_families_keep_their_own_bits(gpu_lib):
+    """The five families above with bop, atm, nk, grv, vh and g3 between them, walkers repeated within the lists: in every
+    family the bits and the sample counts of that family's calls alone in a fresh context."""
+    W = 3
+    cfg = SystemConfig(dim=2, Np=5, Nb=3, density=0.25)
+    VT, WF = gpu_lib.build_tables(cfg)
+    L = np.asarray(cfg.Lbox[:cfg.dim])
+    rng = np.random.default_rng(20261020)
+    P = rng.uniform(-0.5, 0.5, (W,) + tuple(cfg.path_shape)) * L
+    pairs = rng.uniform(-0.5, 0.5, (sum(sum(c[2]) for c in MORE if c[0] == "nk"), 2, cfg.dim)) * L
+    init = dict(INIT, bop=(cfg.rcut, 1, 4, 3, cfg.rcut / 3.0), atm=(cfg.rcut, 1), nk=(2, 3), grv=(4, 1, 3, cfg.rcut / 3.0),
+                vh=(2, 1, 3, cfg.rcut / 3.0, 4, cfg.rcut / 4.0), g3=(2, cfg.rcut / 2.0, 3, 1))
+    together = _run_more(gpu_lib, cfg, VT, WF, P, init, pairs, list(init))
+    for f in init:
+        alone = _run_more(gpu_lib, cfg, VT, WF, P, init, pairs, [f])[f]
+        assert sorted(alone) == sorted(together[f])
+        assert alone["nopen" if f == "nk" else "samples"].tolist() == LISTED[f], f
+        assert any(np.any(a != 0) for k, a in alone.items() if k not in ("samples", "nopen")), f
+        for k, a in alone.items():
+            t = together[f][k]
+            assert a.shape == t.shape and a.dtype == t.dtype and a.dtype.itemsize == 8, (f, k)
             assert np.array_equal(a.view(np.uint64), t.view(np.uint64)), (f, k)
