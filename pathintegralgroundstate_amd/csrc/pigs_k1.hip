@@ -421,36 +421,66 @@ __device__ __forceinline__ PipeTab pipe_table_dma_finish(unsigned char *smem, in
 // consecutive beads spread over all CUs) from an LDS counter, because odd beads cost more than even ones.  The two
 // distances of a pass are branch-free, independent chains (masked lanes look up the table's zero cell).  A wave
 // that started every item with its dependent chain -- scalar loads of the item record, then the slice loads whose
-// address they give, ~3 us -- reached 78 % VALU occupancy; here (a) the record of the item AFTER the next one is requested with vector loads
-// (lanes 0..2: walker/ip/ib, lanes 0..2*DIM-1: xnew,xold; vmcnt is in order, unlike scalar loads it does not
-// force an lgkmcnt drain at the next LDS gather) and decoded one item later with v_readlane, (b) the
-// partner coordinates run two passes ahead: pass m+2 of this item, then passes 0/1 of the next item, are
-// requested before pass m is evaluated, in the same 4 x DIM registers.
+// address they give, ~3 us -- reached 78 % VALU occupancy; here (a) a wave draws its next item from the queue at the
+// top of the current one and requests that record with vector loads before anything else (vmcnt is in order, so the
+// record lands ahead of the pass-2 coordinates the wave has to wait for anyway; unlike scalar loads, vector loads do
+// not force an lgkmcnt drain at the next LDS gather); it is decoded after pass 1 with v_readfirstlane / v_readlane;
+// (b) the partner coordinates run two passes ahead: pass m+2 of this item, then passes 0/1 of the next item, are
+// requested before pass m is evaluated, in the same 4 x DIM registers.  A wave thus owns its current item and ONE
+// claimed item, never two: when the queue runs dry no wave sits on two unstarted items while another has none.
 // =====================================================================================
 template <int DIM>
 struct ItemMeta {                                   // wave-uniform (SGPRs)
     int    p, b, ok;
     const double *S;
-    int    nb;                                      // bytes of a coordinate row (0 for a malformed record)
+    int    nb;                                      // bytes of a coordinate row (0 for a malformed or empty record)
+    int    np;                                      // partners' rows: Np (0 likewise).  Per item on purpose: tested against
+                                                    // P.Np, the four passes' lane masks are loop invariants that get hoisted and then spill
     double xn[DIM], xo[DIM];
 };
 
+// an item record as it arrives: walker / ip / ib in every lane (wave-uniform loads), xnew / xold in lanes 0..DIM-1
 struct ItemRaw {
-    int    i;      // lane 0 walker, 1 ip, 2 ib
-    double x;      // lanes 0..DIM-1 xnew, DIM..2*DIM-1 xold
+    int    w, ip, ib;
+    double xn, xo;
 };
 
+// the item arrays of a launch and the workgroup's queue over them (wave-uniform)
+struct PipeQueue {
+    const int32_t *walker, *ipv, *ibv;
+    const double *xnew, *xold;
+    int *next;                                      // LDS counter: the next queue index nobody has drawn yet
+    int n_local;                                    // items of this workgroup: blockIdx + k * gridDim, k < n_local
+};
+
+constexpr int kPipeBufFlags = 0x00020000;           // raw buffer, 32-bit data format: out-of-range lanes read 0
+
+// Request the record of queue index k.  The index is wave-uniform, so the five addresses are SALU work: each field
+// comes through a buffer descriptor that covers exactly that item's entry -- 4 bytes of walker / ip / ib at offset 0
+// (no VGPR address at all), DIM*8 bytes of xnew / xold at the lane's lane*8 (lanes >= DIM are out of range: 0).
+// Vector loads all the same (see above: vmcnt is in order and leaves lgkmcnt to the LDS gathers).  k >= n_local:
+// empty descriptors, no memory traffic, and the record reads as ip = 0 -- a malformed record, so whatever looks ahead
+// through it gets the empty slice without a case of its own.
 template <int DIM>
-__device__ __forceinline__ ItemRaw pipe2_request(int it, const int32_t *__restrict__ walker,
-                                                 const int32_t *__restrict__ ipv, const int32_t *__restrict__ ibv,
-                                                 const double *__restrict__ xnew, const double *__restrict__ xold, int lane)
+__device__ __forceinline__ ItemRaw pipe2_request(const PipeQueue &Q, int k, int lane)
 {
+    const bool has = k < Q.n_local;
+    const int it = (int)blockIdx.x + (has ? k : 0) * (int)gridDim.x;
+    const int ni = has ? 4 : 0, nx = has ? DIM * 8 : 0;
+    const auto ld_i = [&](const int32_t *a) {
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(a + it), 0, ni, kPipeBufFlags);
+        return (int)__builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0);
+    };
+    const auto ld_x = [&](const double *a) {
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(a + (size_t)it * DIM), 0, nx, kPipeBufFlags);
+        return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (unsigned)lane * 8u, 0, 0));
+    };
     ItemRaw r;
-    const int32_t *ai = lane == 0 ? walker : (lane == 1 ? ipv : ibv);
-    r.i = ai[it];
-    const int k = lane < DIM ? lane : (lane < 2 * DIM ? lane - DIM : 0);
-    const double *ax = lane < DIM ? xnew : xold;
-    r.x = ax[(size_t)it * DIM + k];
+    r.w  = ld_i(Q.walker);
+    r.ip = ld_i(Q.ipv);
+    r.ib = ld_i(Q.ibv);
+    r.xn = ld_x(Q.xnew);
+    r.xo = ld_x(Q.xold);
     return r;
 }
 
@@ -463,38 +493,30 @@ __device__ __forceinline__ double bcast_lane(double v, int lane_id)
     return u.d;
 }
 
+// The two halves of a record's decode.  The slice half (indices, range check, slice address) is what the coordinate
+// look-ahead needs mid-item; the coordinate half waits for the item's own turn, so that two items' xnew / xold never
+// compete for SGPRs.  A malformed or empty record gets nb = 0: every load of its slice is a no-op.
 template <int DIM>
-__device__ __forceinline__ void pipe2_decode(const DevParams &P, const double *__restrict__ paths, const ItemRaw &r,
-                                             size_t sl, ItemMeta<DIM> &R)
+__device__ __forceinline__ void pipe2_decode_slice(const DevParams &P, const double *__restrict__ paths, const ItemRaw &r,
+                                                   size_t sl, ItemMeta<DIM> &R)
 {
-    const int w = __builtin_amdgcn_readlane(r.i, 0);
-    R.p = __builtin_amdgcn_readlane(r.i, 1) - 1;
-    R.b = __builtin_amdgcn_readlane(r.i, 2);
+    const int w = __builtin_amdgcn_readfirstlane(r.w);
+    R.p = __builtin_amdgcn_readfirstlane(r.ip) - 1;
+    R.b = __builtin_amdgcn_readfirstlane(r.ib);
     R.ok = (unsigned)w < (unsigned)P.nW && (unsigned)R.p < (unsigned)P.Np && (unsigned)R.b < (unsigned)P.M;
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-        R.xn[k] = bcast_lane(r.x, k);
-        R.xo[k] = bcast_lane(r.x, DIM + k);
-    }
     R.S = paths + (R.ok ? ((size_t)w * P.M + R.b) * sl : 0);
     R.nb = R.ok ? P.NpPad * 8 : 0;
+    R.np = R.ok ? P.Np : 0;
 }
 
-// only the slice of a record (what the coordinate lookahead needs mid-item; the full decode waits for the item's
-// own turn so that two decoded records never compete for SGPRs).  has = false: no item, no loads (nb = 0).
-struct SliceRef {
-    const double *S;
-    int nb;
-};
-
-__device__ __forceinline__ SliceRef pipe2_slice(const DevParams &P, const double *__restrict__ paths, const ItemRaw &r,
-                                                size_t sl, bool has)
+template <int DIM>
+__device__ __forceinline__ void pipe2_decode_coords(const ItemRaw &r, ItemMeta<DIM> &R)
 {
-    const int w = __builtin_amdgcn_readlane(r.i, 0);
-    const int p = __builtin_amdgcn_readlane(r.i, 1) - 1;
-    const int b = __builtin_amdgcn_readlane(r.i, 2);
-    const bool ok = has && (unsigned)w < (unsigned)P.nW && (unsigned)p < (unsigned)P.Np && (unsigned)b < (unsigned)P.M;
-    return SliceRef{paths + (ok ? ((size_t)w * P.M + b) * sl : 0), ok ? P.NpPad * 8 : 0};
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+        R.xn[k] = bcast_lane(r.xn, k);
+        R.xo[k] = bcast_lane(r.xo, k);
+    }
 }
 
 // Partner coordinates of pass m through one buffer descriptor per coordinate row (base S + k NpPad, NpPad*8 bytes;
@@ -523,7 +545,7 @@ __device__ __forceinline__ void pipe2_pass(const DevParams &P, PipeTab VT, const
                                            const ItemMeta<DIM> &R, const double (&rjm)[DIM], int lane, Acc<DIM, CLS> &A)
 {
     const int j = M * kWave + lane;
-    const bool valid = j < P.Np && j != R.p;
+    const bool valid = j < R.np && j != R.p;
     double dn[DIM], dold[DIM];
 #pragma unroll
     for (int k = 0; k < DIM; ++k) {
@@ -542,45 +564,58 @@ __device__ __forceinline__ void pipe2_pass(const DevParams &P, PipeTab VT, const
 // per-wave pipeline state that crosses items
 template <int DIM>
 struct PipeState {
-    ItemRaw raw_next;         // the next item's record (requested one item ago; decoded when its turn comes)
-    ItemRaw raw_nn;           // record of the item after it (requested mid-item)
-    int k_nn;                 // queue index of that item
-    bool has_next;            // the wave has a next item
-    double a0[DIM], a1[DIM];  // passes 0/1: of the current item on entry, of the next item on exit
+    int k_next;               // queue index of the claimed item (>= n_local: none, and its record is empty)
+    ItemRaw raw_next;         // its record: requested at the top of the current item, coordinates decoded at its turn
+    ItemMeta<DIM> next;       // the slice half of its decode (after pass 1); xn / xo follow at its turn
+    double a0[DIM], a1[DIM];  // passes 0/1: of the current item on entry, of the claimed item on exit
 };
+
+// The look-ahead of one item in three steps, shared by pipe2_item and by the malformed-record path of the kernel:
+//   claim   draw the next queue index and request its record -- the first VMEM instructions of the item, so the record
+//           lands before the item's own pass-2 coordinates do.  A draw past the end tells the wave that the current
+//           item is its last; the record request and the loads below still run (a branch there costs ~40 spilled
+//           VGPRs), on empty descriptors: no memory traffic at all;
+//   ahead0  (after pass 1) decode the record's slice and request its pass-0 coordinates;
+//   ahead1  request its pass-1 coordinates.
+template <int DIM>
+__device__ __forceinline__ void pipe2_claim(const PipeQueue &Q, int lane, PipeState<DIM> &st)
+{
+    int kn = 0;
+    if (lane == 0) kn = atomicAdd(Q.next, 1);
+    st.k_next = __builtin_amdgcn_readfirstlane(kn);
+    st.raw_next = pipe2_request<DIM>(Q, st.k_next, lane);
+}
+
+template <int DIM>
+__device__ __forceinline__ void pipe2_ahead0(const DevParams &P, const double *__restrict__ paths, size_t sl, int lane,
+                                             PipeState<DIM> &st)
+{
+    pipe2_decode_slice<DIM>(P, paths, st.raw_next, sl, st.next);
+    pipe2_load<DIM>(P, st.next.S, st.next.nb, st.next.p, 0, lane, st.a0);
+}
+
+template <int DIM>
+__device__ __forceinline__ void pipe2_ahead1(const DevParams &P, int lane, PipeState<DIM> &st)
+{
+    pipe2_load<DIM>(P, st.next.S, st.next.nb, st.next.p, 1, lane, st.a1);
+}
 
 template <int DIM, int CLS>
 __device__ __forceinline__ void pipe2_item(const DevParams &P, PipeTab VT, const double *__restrict__ WF,
-                                           const double *__restrict__ paths, size_t sl, int n_local, int *queue,
-                                           const int32_t *__restrict__ walker, const int32_t *__restrict__ ipv,
-                                           const int32_t *__restrict__ ibv, const double *__restrict__ xnew,
-                                           const double *__restrict__ xold,
-                                           const ItemMeta<DIM> &R, PipeState<DIM> &st, int k_self, int lane, double *red,
+                                           const double *__restrict__ paths, size_t sl, const PipeQueue &Q,
+                                           const ItemMeta<DIM> &R, PipeState<DIM> &st, int lane, double *red,
                                            double *out, double *parts)
 {
     Acc<DIM, CLS> A;
     double b0[DIM], b1[DIM];
+    pipe2_claim<DIM>(Q, lane, st);
     pipe2_load<DIM>(P, R.S, R.nb, R.p, 2, lane, b0);
     pipe2_pass<DIM, CLS, 0>(P, VT, WF, R, st.a0, lane, A);
     pipe2_load<DIM>(P, R.S, R.nb, R.p, 3, lane, b1);
     pipe2_pass<DIM, CLS, 1>(P, VT, WF, R, st.a1, lane, A);
-    // the next item's record arrived an item ago; the one after it is drawn from the queue and requested now
-    // no next item: the look-ahead loads still run (a branch here costs 40 spilled VGPRs) on an empty descriptor:
-    // no memory traffic at all
-    const SliceRef Snext = pipe2_slice(P, paths, st.raw_next, sl, st.has_next);
-    {
-        int kn = 0;
-        if (lane == 0) kn = atomicAdd(queue, 1);
-        kn = __builtin_amdgcn_readfirstlane(kn);
-        st.k_nn = kn;
-        const int kq = kn < n_local ? kn : k_self;                    // past the end: this item's own record again (its
-                                                                      // slice is in L2: the look-ahead loads cost no HBM traffic)
-        st.raw_nn = pipe2_request<DIM>((int)blockIdx.x + kq * (int)gridDim.x, walker, ipv, ibv, xnew, xold, lane);
-    }
-    const int pnext = __builtin_amdgcn_readlane(st.raw_next.i, 1) - 1;    // (a wave without a next item re-reads a stale record: any row does)
-    pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 0, lane, st.a0);
+    pipe2_ahead0<DIM>(P, paths, sl, lane, st);
     pipe2_pass<DIM, CLS, 2>(P, VT, WF, R, b0, lane, A);
-    pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 1, lane, st.a1);
+    pipe2_ahead1<DIM>(P, lane, st);
     pipe2_pass<DIM, CLS, 3>(P, VT, WF, R, b1, lane, A);
     finish_item<DIM, CLS>(P, lane, R.b, A, red, out, parts);
 }
@@ -614,8 +649,10 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     const size_t sl = slice_doubles(DIM, P.NpPad);
     const int n_local = (n_items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
 
-    // first two items of this wave: static (k = wid, wid + 16); the queue starts behind them
-    int k_cur = wid, k_nx = wid + 16;
+    // only the first item of a wave is static (k = wid); the queue starts behind those 16, and every further item is
+    // drawn from it one item ahead (pipe2_claim)
+    int k_cur = wid;
+    const PipeQueue Q{walker, ipv, ibv, xnew, xold, &next_local, n_local};
     ItemMeta<DIM> cur;
     PipeState<DIM> st;
     const int nt = P.Nmax + 2;
@@ -623,18 +660,16 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     pipe_table_dma_issue(smem, VTg, nt, wid, lane);              // L2 hits, issued ahead of the HBM requests below
     const double tail = VTg[nt - 1];                             // the odd last entry (used when nt is odd)
     {
-        const ItemRaw r0 = pipe2_request<DIM>((int)blockIdx.x + (k_cur < n_local ? k_cur : 0) * (int)gridDim.x,
-                                              walker, ipv, ibv, xnew, xold, lane);
-        st.raw_next = pipe2_request<DIM>((int)blockIdx.x + (k_nx < n_local ? k_nx : (k_cur < n_local ? k_cur : 0)) * (int)gridDim.x,
-                                         walker, ipv, ibv, xnew, xold, lane);
-        pipe2_decode<DIM>(P, paths, r0, sl, cur);
+        const ItemRaw r0 = pipe2_request<DIM>(Q, k_cur, lane);   // (a wave without a first item: the empty record)
+        pipe2_decode_slice<DIM>(P, paths, r0, sl, cur);
+        pipe2_decode_coords<DIM>(r0, cur);
         pipe2_load<DIM>(P, cur.S, cur.nb, cur.p, 0, lane, st.a0);
         pipe2_load<DIM>(P, cur.S, cur.nb, cur.p, 1, lane, st.a1);
     }
 
     const PipeTab VT = pipe_table_dma_finish<2 * DIM>(smem, nt, tail);   // passes 0/1 stay in flight
     K1STAMP(t_loaded);
-    if (threadIdx.x == 0) next_local = 32;
+    if (threadIdx.x == 0) next_local = 16;
     double *red = reinterpret_cast<double *>(smem + pipe_tab_bytes(nt) + (size_t)wid * kWaveLds);
     __syncthreads();                                            // the only workgroup barrier
     K1STAMP(t_ready);
@@ -643,34 +678,25 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
 #endif
 
     while (k_cur < n_local) {                                   // wave-uniform
-        st.has_next = k_nx < n_local;
         const int it = (int)blockIdx.x + k_cur * (int)gridDim.x;
         double *o = out + it;
         double *q = nullptr;                                     // the (DeltaPot, DeltaF2, DeltaPsi) diagnostic runs on the plain grid
         if (!cur.ok) {
             // malformed item: NaN result; keep the pipeline moving without evaluating anything
             if (lane == 0) *o = __builtin_nan("");
-            const SliceRef Snext = pipe2_slice(P, paths, st.raw_next, sl, st.has_next);
-            int kn = 0;
-            if (lane == 0) kn = atomicAdd(&next_local, 1);
-            kn = __builtin_amdgcn_readfirstlane(kn);
-            st.k_nn = kn;
-            st.raw_nn = pipe2_request<DIM>((int)blockIdx.x + (kn < n_local ? kn : k_cur) * (int)gridDim.x,
-                                           walker, ipv, ibv, xnew, xold, lane);
-            const int pnext = __builtin_amdgcn_readlane(st.raw_next.i, 1) - 1;
-            pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 0, lane, st.a0);
-            pipe2_load<DIM>(P, Snext.S, Snext.nb, pnext, 1, lane, st.a1);
+            pipe2_claim<DIM>(Q, lane, st);
+            pipe2_ahead0<DIM>(P, paths, sl, lane, st);
+            pipe2_ahead1<DIM>(P, lane, st);
         } else {
             const bool odd  = (cur.b & 1) != 0;
             const bool endb = (cur.b == 0) || (cur.b == 2 * P.Nb);
-            if (odd)       pipe2_item<DIM, CLS_ODD>(P, VT, WF, paths, sl, n_local, &next_local, walker, ipv, ibv, xnew, xold, cur, st, k_cur, lane, red, o, q);
-            else if (endb) pipe2_item<DIM, CLS_END>(P, VT, WF, paths, sl, n_local, &next_local, walker, ipv, ibv, xnew, xold, cur, st, k_cur, lane, red, o, q);
-            else           pipe2_item<DIM, CLS_EVEN>(P, VT, WF, paths, sl, n_local, &next_local, walker, ipv, ibv, xnew, xold, cur, st, k_cur, lane, red, o, q);
+            if (odd)       pipe2_item<DIM, CLS_ODD>(P, VT, WF, paths, sl, Q, cur, st, lane, red, o, q);
+            else if (endb) pipe2_item<DIM, CLS_END>(P, VT, WF, paths, sl, Q, cur, st, lane, red, o, q);
+            else           pipe2_item<DIM, CLS_EVEN>(P, VT, WF, paths, sl, Q, cur, st, lane, red, o, q);
         }
-        pipe2_decode<DIM>(P, paths, st.raw_next, sl, cur);       // arrived long ago: readlanes only
-        k_cur = k_nx;
-        k_nx = st.k_nn;
-        st.raw_next = st.raw_nn;
+        pipe2_decode_slice<DIM>(P, paths, st.raw_next, sl, cur);  // arrived long ago: readlanes only
+        pipe2_decode_coords<DIM>(st.raw_next, cur);
+        k_cur = st.k_next;
 #ifdef PIGS_EXPERIMENT_K1_CLOCK
         ++n_done;
 #endif
