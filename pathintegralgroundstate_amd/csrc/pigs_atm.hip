@@ -28,9 +28,10 @@
 //     writes (pass 1), its reads (pass 2) and the next vertex's writes.
 // Nothing in the order depends on the walker list, the launch split or the context, so the same worldline gives the same
 // bits.  Compile with -ffp-contract=off.
-#include "pigs_device.h"
+// The slice address is pigs_slice_device.h's.
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 
 namespace pigs {
 
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(kAtmThreads) void k_atm(
     const int js = blockIdx.x / A.n, slot = blockIdx.x - js * A.n;
     const int w = list.w[slot];
     const int a = P.Nb - A.window + js;
-    const double *Sa = paths + ((size_t)w * P.M + a) * slice_doubles(DIM, NpPad);
+    const double *Sa = window_slice<DIM>(P, paths, w, a);
 
     for (int t = threadIdx.x; t < DIM * Np; t += blockDim.x) {
         const int k = t / Np, ii = t - k * Np;

@@ -24,11 +24,9 @@
 //   element that this thread alone owns in this launch.
 // No floating-point atomics: the same worldline gives the same bits whatever the list, the split or the context.
 // Compile with -ffp-contract=off.
-#include <algorithm>
-
-#include "pigs_device.h"
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 
 namespace pigs {
 
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(kBopThreads) void k_bop(
     const int slot = blockIdx.x / ns, js = blockIdx.x - slot * ns;
     const int w = list.w[slot];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const double *S = paths + ((size_t)w * P.M + (P.Nb - A.window + js)) * slice_doubles(DIM, P.NpPad);
+    const double *S = window_slice<DIM>(P, paths, w, P.Nb - A.window + js);
 
     for (int t = threadIdx.x; t < DIM * Np; t += blockDim.x) {
         const int k = t / Np, ii = t - k * Np;

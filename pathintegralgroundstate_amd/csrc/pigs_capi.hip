@@ -196,7 +196,7 @@ struct pigs_ctx {
     std::vector<int32_t> a_sw, a_sb;        // slot lists: must outlive the asynchronous upload
     struct { bool on = false, launched = false; EstBatch b; } a_pend;
     Event       ev_gate;                    // recorded behind the TranslateChain kernel of the next step (see launch_pending_estimators)
-    // the launches of the seven accumulator families below (each_launch): which walkers the current one holds
+    // the launches of the accumulator families below (each_launch): which walkers the current one holds
     WalkerMarks list_marks;
     // density profiles of a trapped system (pigs_density_*): per-walker 64-bit counts, walker-major
     DevBuf<unsigned long long> d_dplanar, d_dradial, d_dpair, d_dsamples;
@@ -1408,7 +1408,7 @@ int pigs_diagonal_estimators_end(pigs_ctx *c, double *en, double *gr, double *Sk
     return PIGS_OK;
 }
 
-// ---- what the twelve per-walker accumulator families below share ----------------------------------
+// ---- what the per-walker accumulator families below share -----------------------------------------
 extern "C++" {      // templates
 
 // *_init, once the request is accepted: no accumulate may be in flight on the buffers being replaced, and until the new

@@ -16,9 +16,10 @@
 // NaN, +-Inf, 1e300 -- is dropped without undefined behaviour).  Counts are 64-bit integer atomics: the result does
 // not depend on the order of additions, and a walker listed twice counts twice.
 // Compile with -ffp-contract=off: the squared distances are summed left to right without fused multiply-adds.
-#include "pigs_device.h"
+// The tile staging and the flush of the LDS counters are pigs_slice_device.h's.
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 
 namespace pigs {
 
@@ -84,10 +85,7 @@ __global__ __launch_bounds__(kDensThreads) void k_density(
             const int m = min(tile, Np - j0);
             if (j0 != staged) {
                 __syncthreads();
-                for (int t = threadIdx.x; t < DIM * m; t += blockDim.x) {
-                    const int k = t / m, jj = t - k * m;
-                    sx[k * tile + jj] = S[(size_t)k * NpPad + j0 + jj];
-                }
+                stage_rows<DIM>(sx, tile, S, NpPad, j0, m);
                 __syncthreads();
                 staged = j0;
             }
@@ -113,10 +111,7 @@ __global__ __launch_bounds__(kDensThreads) void k_density(
     }
     if (lds_hist) {
         __syncthreads();
-        for (int t = threadIdx.x; t < Nbin; t += blockDim.x) {
-            const unsigned int c = hist[t];
-            if (c) atomicAdd(&pa[t], 2ull * c);
-        }
+        flush_counts(hist, Nbin, [&](int t) { return &pa[t]; }, 2ull);
     }
     if (threadIdx.x == 0) atomicAdd(&samples[w], 1ull);
 }

@@ -21,9 +21,9 @@
 // Compile with -ffp-contract=off: products and sums round one by one.
 #include <algorithm>
 
-#include "pigs_device.h"
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 
 namespace pigs {
 
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_fqt_rho(
     const int w = list.w[slot];
     const int Np = P.Np, NpPad = P.NpPad;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const double *S = paths + ((size_t)w * P.M + (P.Nb - window + j)) * slice_doubles(DIM, NpPad);
+    const double *S = window_slice<DIM>(P, paths, w, P.Nb - window + j);
     double *out = rho + ((size_t)slot * ns + j) * (2 * (size_t)Nk * DIM);
     const int ng = (Nk + 3) >> 2, G = DIM * ng;
 

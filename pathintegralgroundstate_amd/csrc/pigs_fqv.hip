@@ -20,11 +20,9 @@
 //                    launch (the host never puts a walker twice into one launch).
 // No floating-point atomics; every sum has one fixed order that depends on neither the walker list, the launch split
 // nor the tile width.  Compile with -ffp-contract=off: only the fma written out in sqv_rho_slice is fused.
-#include <algorithm>
-
-#include "pigs_device.h"
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 #include "pigs_sqv_device.h"
 
 namespace pigs {
@@ -40,7 +38,7 @@ __global__ __launch_bounds__(kSqvThreadsMax) void k_fqv_rho(
     const int ns = 2 * window + 1;
     const int slot = blockIdx.x / ns, j = blockIdx.x - slot * ns;
     const int w = list.w[slot];
-    const double *X = paths + ((size_t)w * P.M + (P.Nb - window + j)) * slice_doubles(DIM, P.NpPad);
+    const double *X = window_slice<DIM>(P, paths, w, P.Nb - window + j);
     sqv_rho_slice<DIM, true>(P, X, tab, nmax, tile, nprefix, nchunk, Nq, pi, rho + ((size_t)slot * ns + j) * 2 * (size_t)Nq);
 }
 

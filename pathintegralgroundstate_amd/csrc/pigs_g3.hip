@@ -30,9 +30,10 @@
 //     writes (pass 1), its reads (pass 2) and the next vertex's writes.
 // Integer atomics only: the result depends on neither the walker list, its order, the launch split, the form nor the
 // context.  Compile with -ffp-contract=off.
-#include "pigs_device.h"
+// The slice address and its staging are pigs_slice_device.h's.
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 
 namespace pigs {
 
@@ -62,14 +63,11 @@ __global__ __launch_bounds__(kG3Threads) void k_g3(
     const int js = blockIdx.x / A.n, slot = blockIdx.x - js * A.n;
     const int w = list.w[slot];
     const int a = P.Nb - A.window + js;
-    const double *Sa = paths + ((size_t)w * P.M + a) * slice_doubles(DIM, NpPad);
+    const double *Sa = window_slice<DIM>(P, paths, w, a);
     unsigned long long *gt = trip + (size_t)w * ntrip;
     unsigned long long *gp = pair + (size_t)w * Nr;
 
-    for (int t = threadIdx.x; t < DIM * Np; t += blockDim.x) {
-        const int k = t / Np, ii = t - k * Np;
-        sx[t] = Sa[(size_t)k * NpPad + ii];
-    }
+    stage_rows<DIM>(sx, Np, Sa, NpPad, 0, Np);
     if (HIST_LDS)
         for (int t = threadIdx.x; t < ntrip + Nr; t += blockDim.x) hist[t] = 0u;
     __syncthreads();

@@ -28,9 +28,9 @@
 // split: the same worldline gives the same bits.  Compile with -ffp-contract=off: only the fma written out is fused.
 #include <algorithm>
 
-#include "pigs_device.h"
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 #include "pigs_sqv_device.h"
 
 namespace pigs {
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kSqvThreadsMax) void k_sqv_rho2(
     const int ns = 2 * window + 1;
     const int slot = blockIdx.x / ns, j = blockIdx.x - slot * ns;
     const int w = list.w[slot];
-    const double *X = paths + ((size_t)w * P.M + (P.Nb - window + j)) * slice_doubles(DIM, P.NpPad);
+    const double *X = window_slice<DIM>(P, paths, w, P.Nb - window + j);
     sqv_rho_slice<DIM, false>(P, X, tab, nmax, tile, nprefix, nchunk, Nq, pi, rho2 + ((size_t)slot * ns + j) * (size_t)Nq);
 }
 

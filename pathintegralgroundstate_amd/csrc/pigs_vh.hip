@@ -25,12 +25,11 @@
 //   * Balance.  A base slice near the window's upper end has fewer lags.  The grid is slice-major, walker-minor, so the
 //     workgroups with all their lags are dispatched first and the short ones fill in the launch's tail.
 // Integer atomics only: the result depends on neither the walker list, its order, the launch split, the form nor the
-// context.  Compile with -ffp-contract=off.
-#include <algorithm>
-
-#include "pigs_device.h"
+// context.  Compile with -ffp-contract=off.  The slice address, the staging and the flush are
+// pigs_slice_device.h's.
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
+#include "pigs_slice_device.h"
 
 namespace pigs {
 
@@ -55,13 +54,9 @@ __global__ __launch_bounds__(kVhThreads) void k_vh(
     const int w = list.w[slot];
     const int a = P.Nb - A.window + js;
     const int nlag = min(A.Ntau, 2 * A.window - js) + 1;                    // a + l <= Nb + window
-    const size_t sd = slice_doubles(DIM, NpPad);
-    const double *Sa = paths + ((size_t)w * P.M + a) * sd;
+    const double *Sa = window_slice<DIM>(P, paths, w, a);
 
-    for (int t = threadIdx.x; t < DIM * Np; t += blockDim.x) {
-        const int k = t / Np, ii = t - k * Np;
-        sx[t] = Sa[(size_t)k * NpPad + ii];
-    }
+    stage_rows<DIM>(sx, Np, Sa, NpPad, 0, Np);
     if (HIST_LDS)
         for (int t = threadIdx.x; t < nlag * per; t += blockDim.x) hist[t] = 0u;
     __syncthreads();
@@ -70,7 +65,7 @@ __global__ __launch_bounds__(kVhThreads) void k_vh(
     const double inf = __builtin_huge_val();
     const int T = (int)blockDim.x;
     for (int l = 0; l < nlag; ++l) {
-        const double *Sl = Sa + (size_t)l * sd;                             // slice a + l
+        const double *Sl = Sa + (size_t)l * slice_doubles(DIM, NpPad);      // slice a + l
         unsigned int *hl = hist + l * per;
         unsigned long long *gd = dist + ((size_t)w * (A.Ntau + 1) + l) * Nr;
         unsigned long long *gs = self + ((size_t)w * (A.Ntau + 1) + l) * Ns;
@@ -105,14 +100,11 @@ __global__ __launch_bounds__(kVhThreads) void k_vh(
     }
     if (HIST_LDS) {
         __syncthreads();
-        for (int t = threadIdx.x; t < nlag * per; t += blockDim.x) {
-            const unsigned int c = hist[t];
-            if (c) {
-                const int l = t / per, b = t - l * per;
-                const size_t wl = (size_t)w * (A.Ntau + 1) + l;
-                atomicAdd(b < Nr ? &dist[wl * Nr + b] : &self[wl * Ns + (b - Nr)], (unsigned long long)c);
-            }
-        }
+        flush_counts(hist, nlag * per, [&](int t) {
+            const int l = t / per, b = t - l * per;
+            const size_t wl = (size_t)w * (A.Ntau + 1) + l;
+            return b < Nr ? &dist[wl * Nr + b] : &self[wl * Ns + (b - Nr)];
+        });
     }
     if (js == 0 && threadIdx.x == 0) atomicAdd(&samples[w], 1ull);
 }
