@@ -700,6 +700,68 @@ int pigs_nk_add(pigs_ctx *ctx, int32_t n, const int32_t *walkers, const int32_t 
  * pigs_nk_init. */
 int pigs_nk_read(pigs_ctx *ctx, double *C, int64_t *H, int64_t *nopen, int64_t *ninside, const int32_t *reset);
 
+/* ---- a crystal seen from its lattice: Lindemann moments, site occupancy and site hops of a PERIODIC system in 2D or 3D,
+ * over a slice window (new: every family above is translation-invariant; this is the first that takes the lattice the
+ * run was started from as input) -----------------------------------------------------------------------------------------
+ * Scope: periodic contexts with dim = 2 or 3.
+ * Sites: R(dim, nsite), column-major like Path (site s at sites[s*dim .. s*dim + dim)), uploaded once by pigs_lat_init into
+ * rows laid out as a slice's.  nsite need not equal Np: nsite = Np + 1 is a vacancy run, nsite = Np - 1 forces a double
+ * occupancy.
+ * For a listed walker w, every window slice a = Nb-window .. Nb+window and every particle i:
+ * 1. Assignment.  For every site s take d_k = x_k(i) - R_k(s), fold it once by min_image<DIM> (the two compares, each
+ *    against LboxHalf) and sum r2 left to right, nothing fused: pigs_grv_*'s arithmetic.  The assigned site s(i) is the
+ *    smallest s of the minimal r2: `r2 < best`, strictly, with s ascending and best = +infinity at first.  A NaN never
+ *    wins, nor does +infinity: a particle none of whose r2 compares below +infinity is LOST: s(i) = -1, it adds to no sum
+ *    and no histogram, to no occupancy and no hop, and it counts in nlost.  u(i) is the folded d of the assigned site.
+ *    THE SINGLE FOLD GIVES THE NEAREST IMAGE ONLY WHILE |x_k(i) - R_k(s)| < 3 Lbox[k]/2.  Both samplers wrap every bead
+ *    they move once into [-Lbox/2, Lbox/2] (pigs_sampler.f90 wrap_coord and its device twin), and their proposals lie
+ *    within a fraction of the box of a bead that is inside, so the beads stay in the primary cell; with sites inside it
+ *    too |d_k| < Lbox[k] and the fold is exact.  Sites or uploaded paths far outside the primary cell are the caller's;
+ *    the library does not judge it.
+ * 2. Centre of mass, cm = 1: c_k = (sum_i u_k(i)) / n_assigned, the sum in ASCENDING PARTICLE ORDER from 0.0, one addition
+ *    after the other (a lost particle adds 0.0) -- numpy's cumsum has its bits.  v(i) = u(i) - c.  cm = 0: v = u.
+ *    The assignment itself always uses the uncorrected positions, whatever cm.
+ * 3. Per assigned particle: m2 = sum_k v_k*v_k left to right, m4 = m2*m2.
+ * One accumulate call adds per walker, js = a - (Nb - window):
+ *   mom[w][js][0] += sum_i m2;  mom[w][js][1] += sum_i m4;  mom[w][js][2 + k] += sum_i v_k*v_k        (doubles)
+ *   nassigned[w][js] += the assigned particles;   nlost[w] += the lost ones of every window slice
+ *   occ[w][js][q] += the sites that hold q = 0, 1, 2 particles, q = 3: three or more
+ *   hr[w][b] += 1, b = (int)t, t = sqrt(m2)/rbin, iff t < nbin in double, rbin = rmax/nbin (k_vh's self rule: every
+ *     decision in double before the conversion, NaN drops out), over every window slice
+ *   hx[w][k][b] += 1, b = (int)t, t = (v_k + rmax)/rbin, iff 0 <= t < 2 nbin in double: v_k over [-rmax, rmax)
+ *   hop1[w] += sum over the window slices a but the last and over i of [s_i(a+1) != s_i(a)]
+ *   hopw[w] += sum over i of [s_i(first slice) != s_i(last slice)]; a lost end drops the comparison in both
+ *   samples[w] += 1
+ * The hops follow a particle LABEL along tau, which the resident worldlines keep (pigs_fqs_* relies on the same).
+ * Summation of mom.  No floating-point atomics and one fixed order: with 256 lanes, lane j takes the particles j, j + 256,
+ * .. in ascending order; the 64 lanes of a wave are added by a butterfly (partner lane ^ 32, 16, .., 1), the waves in
+ * wave order from 0.0, then acc += value by the one thread that owns (w, a) in the launch.  The same worldline gives the
+ * same bits whatever the walker list, its order, the launch split or the number of walkers of the context; a walker
+ * listed twice counts twice (in two launches), with bits equal to 2 x one count.
+ * The estimators are the caller's divisions (profiles.normalize_lat, pigs_estimators.f90):
+ *   <u^2>(tau_a) = mom[..][0]/nassigned, the Lindemann ratio gamma = sqrt(<u^2>)/a_nn with a_nn the sites' nearest-
+ *   neighbour distance, alpha_2 = dim <u^4> / ((dim + 2) <u^2>^2) - 1, the vacant fraction occ[0]/(samples nsite), ...
+ * Limit.  A workgroup keeps a tile of 256 sites, u of the slice, the occupancy and the histograms in LDS; pigs_lat_init
+ * refuses (PIGS_ERR_ARG) a system with
+ *   8 (256 dim + dim Np + 36) + 4 (nsite + (1 + 2 dim) nbin + 8) > 65536,
+ * which serves Np = nsite = 1077 in 3D with up to 1032 bins.
+ *
+ * pigs_lat_init uploads the sites, allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a
+ * trapped context or dim = 1; PIGS_ERR_ARG for nsite < 1, a site coordinate that is not finite, nbin < 1, rmax not finite
+ * or not > 0, window < 0 or window > Nb, cm not 0 or 1, and for the size limit above. */
+int pigs_lat_init(pigs_ctx *ctx, int32_t nsite, const double *sites, int32_t nbin, double rmax, int32_t window, int32_t cm);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_lat_init, for n < 0 or for a walker out of range. */
+int pigs_lat_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' mom[n_walkers][2 window + 1][2 + dim], nassigned[n_walkers][2 window + 1], nlost[n_walkers],
+ * occ[n_walkers][2 window + 1][4], hr[n_walkers][nbin], hx[n_walkers][dim][2 nbin], hop1, hopw and samples [n_walkers];
+ * then zeroes those of the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG
+ * before pigs_lat_init. */
+int pigs_lat_read(pigs_ctx *ctx, double *mom, int64_t *nassigned, int64_t *nlost, int64_t *occ, int64_t *hr, int64_t *hx,
+                  int64_t *hop1, int64_t *hopw, int64_t *samples, const int32_t *reset);
+
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
  * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for

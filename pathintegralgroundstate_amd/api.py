@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "pigs_g3_init", "pigs_g3_accumulate", "pigs_g3_read",
     "pigs_atm_init", "pigs_atm_accumulate", "pigs_atm_read",
     "pigs_nk_init", "pigs_nk_count", "pigs_nk_vectors", "pigs_nk_accumulate", "pigs_nk_add", "pigs_nk_read",
+    "pigs_lat_init", "pigs_lat_accumulate", "pigs_lat_read",
 ]
 
 
@@ -180,6 +181,9 @@ def load_library(path=LIB_PATH):
     L.pigs_nk_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_nk_add.argtypes = [vp, C.c_int32, _ip, _ip, _dp]
     L.pigs_nk_read.argtypes = [vp, _dp, _lp, _lp, _lp, _ip]
+    L.pigs_lat_init.argtypes = [vp, C.c_int32, _dp, C.c_int32, C.c_double, C.c_int32, C.c_int32]
+    L.pigs_lat_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_lat_read.argtypes = [vp, _dp, _lp, _lp, _lp, _lp, _lp, _lp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -859,6 +863,40 @@ class PigsContext:
         mask = self._reset_mask(reset)
         _chk(self.L, self.L.pigs_nk_read(self.h, _d(out["C"]), _l(out["H"]), _l(out["nopen"]), _l(out["ninside"]), mask),
              "pigs_nk_read")
+        return out
+
+    # ---- a crystal seen from its lattice (pigs_lat_*: moments of the displacement from the nearest site, 64-bit counts)
+    def lat_init(self, sites, nbin, rmax, window=0, cm=True):
+        """Upload the lattice sites [nsite, dim] and allocate and zero the sums over the slices Nb-window..Nb+window of a
+        periodic 2D or 3D system: nbin bins of |v| over [0, rmax) and 2 nbin bins of every v_k over [-rmax, rmax); cm:
+        subtract the centre of mass of the displacements of every slice.  Calling it again resizes and zeroes."""
+        R = np.ascontiguousarray(sites, dtype=np.float64)
+        if R.ndim != 2 or R.shape[1] != self.cfg.dim:
+            raise PigsError(f"lat_init: sites must be [nsite, {self.cfg.dim}]")
+        if cm not in (0, 1, False, True):
+            raise PigsError("lat_init: cm is 0 or 1")
+        _chk(self.L, self.L.pigs_lat_init(self.h, R.shape[0], _d(R), int(nbin), float(rmax), int(window), int(cm)), "pigs_lat_init")
+        self._lat = (2 * int(window) + 1, int(nbin))
+
+    def lat_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_lat_accumulate", walkers)
+
+    def lat_read(self, reset=None):
+        """dict of the raw sums: mom [W, 2 window + 1, 2 + dim] (float64: sum |v|^2, sum |v|^4, sum v_k^2), and as int64
+        nassigned [W, 2 window + 1], nlost [W], occ [W, 2 window + 1, 4] (sites with 0, 1, 2, >= 3 particles), hr [W, nbin],
+        hx [W, dim, 2 nbin], hop1 [W], hopw [W], samples [W]; profiles.normalize_lat divides them.  reset: None, True (all
+        walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        if getattr(self, "_lat", None) is None:
+            raise PigsError("lat_read: lat_init first")
+        ns, nbin = self._lat
+        W, dim = self.n_walkers, self.cfg.dim
+        i64 = lambda *shape: np.zeros(shape, np.int64)
+        out = {"mom": np.zeros((W, ns, 2 + dim)), "nassigned": i64(W, ns), "nlost": i64(W), "occ": i64(W, ns, 4),
+               "hr": i64(W, nbin), "hx": i64(W, dim, 2 * nbin), "hop1": i64(W), "hopw": i64(W), "samples": i64(W)}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_lat_read(self.h, _d(out["mom"]), *(_l(out[k]) for k in (
+            "nassigned", "nlost", "occ", "hr", "hx", "hop1", "hopw", "samples")), mask), "pigs_lat_read")
         return out
 
     # ---- K5

@@ -283,6 +283,15 @@ struct pigs_ctx {
     int         nk_nbin = 0;
     int64_t     nk_nq = 0;
     size_t      nk_nvec = 0;
+    // a crystal seen from its lattice (pigs_lat_*): the site rows [dim][NsPad], per walker the moments
+    // mom [2 window + 1][2 + dim], nassigned [2 window + 1], occ [2 window + 1][4], hr [nbin], hx [dim][2 nbin], nlost, hop1,
+    // hopw and samples; the assigned sites of one launch, sidx [min(n_walkers, 256)][2 window + 1][NpPad]
+    DevBuf<double> d_lat_sites, d_lat_mom;
+    DevBuf<unsigned long long> d_lat_nass, d_lat_nlost, d_lat_occ, d_lat_hr, d_lat_hx, d_lat_hop1, d_lat_hopw, d_lat_samples;
+    DevBuf<int32_t> d_lat_sidx;
+    bool        lat_ready = false;          // pigs_lat_init called
+    int         lat_nsite = 0, lat_nspad = 0, lat_nbin = 0, lat_window = 0, lat_cm = 0;
+    double      lat_rmax = 0.0;
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -2242,6 +2251,80 @@ int pigs_nk_read(pigs_ctx *c, double *C, int64_t *H, int64_t *nopen, int64_t *ni
     if (!C || !H || !nopen || !ninside) return fail(PIGS_ERR_ARG, "null output");
     return read_and_reset(c, {{c->d_nk_C.p, (size_t)c->nk_nq, C}, {c->d_nk_H.p, c->nk_nvec, H}, {c->d_nk_nopen.p, 1, nopen},
                               {c->d_nk_ninside.p, 1, ninside}}, reset);
+}
+
+// ---- a crystal seen from its lattice: Lindemann moments, site occupancy and site hops over a slice window ------
+// Raw sums per walker (pigs_lat.hip), accumulated on the device and read per block.  The first family with an input of its
+// own: the sites are uploaded here, once, into rows laid out as a slice's.
+int pigs_lat_init(pigs_ctx *c, int32_t nsite, const double *sites, int32_t nbin, double rmax, int32_t window, int32_t cm)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the lattice estimators are defined for periodic systems only (a site is reached by a minimum image)");
+    if (c->P.dim < 2) return fail(PIGS_ERR_UNSUPPORTED, "the lattice estimators are defined in 2D and 3D only");
+    if (nsite < 1 || !sites || nbin < 1 || !(rmax > 0.0) || !std::isfinite(rmax) || window < 0 || window > c->P.Nb || (cm != 0 && cm != 1))
+        return fail(PIGS_ERR_ARG, "pigs_lat_init: nsite=%d nbin=%d rmax=%g window=%d (0..Nb=%d) cm=%d (0 or 1)", nsite, nbin, rmax,
+                    window, c->P.Nb, cm);
+    const int dim = c->P.dim;
+    for (size_t t = 0; t < (size_t)dim * (size_t)nsite; ++t)
+        if (!std::isfinite(sites[t])) return fail(PIGS_ERR_ARG, "pigs_lat_init: site %zu has a coordinate that is not finite", t / dim);
+    const LatShape sh = lat_shape(dim, c->P.Np, nsite, nbin);
+    if (!sh.fits)
+        return fail(PIGS_ERR_ARG, "pigs_lat_init: Np=%d particles, %d sites and %d bins in %dD need %zu bytes of LDS (%zu at most)",
+                    c->P.Np, nsite, nbin, dim, sh.lds, kLatLdsBudget);
+    const size_t W = (size_t)c->n_walkers, ns = 2 * (size_t)window + 1;
+    const int NsPad = (nsite + 7) / 8 * 8;
+    std::vector<double> rows((size_t)dim * NsPad, 0.0);               // R(dim, nsite) column-major -> dim rows of NsPad
+    for (int s = 0; s < nsite; ++s)
+        for (int k = 0; k < dim; ++k) rows[(size_t)k * NsPad + s] = sites[(size_t)s * dim + k];
+    rc = init_begin(c, c->lat_ready); if (rc) return rc;
+    HIPCHK(c->d_lat_sites.alloc(rows.size()));
+    HIPCHK(hipMemcpyAsync(c->d_lat_sites.p, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(alloc_zeroed(c, c->d_lat_mom, W * ns * (2 + (size_t)dim)));
+    HIPCHK(alloc_zeroed(c, c->d_lat_nass, W * ns));
+    HIPCHK(alloc_zeroed(c, c->d_lat_occ, W * ns * 4));
+    HIPCHK(alloc_zeroed(c, c->d_lat_hr, W * (size_t)nbin));
+    HIPCHK(alloc_zeroed(c, c->d_lat_hx, W * (size_t)dim * 2 * (size_t)nbin));
+    HIPCHK(alloc_zeroed(c, c->d_lat_nlost, W));
+    HIPCHK(alloc_zeroed(c, c->d_lat_hop1, W));
+    HIPCHK(alloc_zeroed(c, c->d_lat_hopw, W));
+    HIPCHK(alloc_zeroed(c, c->d_lat_samples, W));
+    HIPCHK(alloc_zeroed(c, c->d_lat_sidx, std::min(W, (size_t)kWalkerListMax) * ns * (size_t)c->P.NpPad));
+    SYNC_CHECKED(c);                                                  // (rows lives until here)
+    c->lat_nsite = nsite; c->lat_nspad = NsPad; c->lat_nbin = nbin; c->lat_window = window; c->lat_cm = cm;
+    c->lat_rmax = rmax;
+    c->lat_ready = true;
+    return PIGS_OK;
+}
+
+int pigs_lat_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->lat_ready) return fail(PIGS_ERR_ARG, "pigs_lat_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    const LatShape sh = lat_shape(c->P.dim, c->P.Np, c->lat_nsite, c->lat_nbin);
+    // one workgroup owns an accumulator element per launch; a launch's distinct walkers fit the scratch
+    return each_launch(c, sw, walkers, true, kWalkerListMax, "launch_lat", [&](int m, const WalkerList &L) {
+        return launch_lat(c->P, c->d_paths.p, m, L, sh, c->lat_window, c->lat_cm, c->lat_nsite, c->lat_nspad, c->d_lat_sites.p,
+                          c->lat_nbin, c->lat_rmax, c->d_lat_mom.p, c->d_lat_nass.p, c->d_lat_nlost.p, c->d_lat_occ.p,
+                          c->d_lat_hr.p, c->d_lat_hx.p, c->d_lat_hop1.p, c->d_lat_hopw.p, c->d_lat_samples.p, c->d_lat_sidx.p,
+                          c->stream);
+    });
+}
+
+int pigs_lat_read(pigs_ctx *c, double *mom, int64_t *nassigned, int64_t *nlost, int64_t *occ, int64_t *hr, int64_t *hx,
+                  int64_t *hop1, int64_t *hopw, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->lat_ready) return fail(PIGS_ERR_ARG, "pigs_lat_init first");
+    if (!mom || !nassigned || !nlost || !occ || !hr || !hx || !hop1 || !hopw || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t ns = 2 * (size_t)c->lat_window + 1, dim = (size_t)c->P.dim, nb = (size_t)c->lat_nbin;
+    return read_and_reset(c, {{c->d_lat_mom.p, ns * (2 + dim), mom}, {c->d_lat_nass.p, ns, nassigned}, {c->d_lat_nlost.p, 1, nlost},
+                              {c->d_lat_occ.p, ns * 4, occ}, {c->d_lat_hr.p, nb, hr}, {c->d_lat_hx.p, dim * 2 * nb, hx},
+                              {c->d_lat_hop1.p, 1, hop1}, {c->d_lat_hopw.p, 1, hopw}, {c->d_lat_samples.p, 1, samples}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

@@ -215,6 +215,25 @@ hipError_t launch_nk(const DevParams &P, int n, const WalkerList &list, int nmax
                      int base, int cap, const int *cnt, const double *xs, double *C, unsigned long long *H,
                      unsigned long long *nopen, unsigned long long *ninside, hipStream_t st);
 
+// pigs_lat.hip: a crystal seen from its lattice over the window slices (pigs_lat_accumulate): the nearest site of every
+// particle, the moments and histograms of its displacement from that site, the occupation of the sites and the hops
+// between sites along imaginary time.  k_lat, one workgroup per (listed walker, slice), stages the site rows in LDS in
+// tiles of kLatTile and leaves every particle's site in the scratch sidx [slot][2 window + 1][NpPad]; k_lat_hops, one
+// workgroup per listed walker, reads it.  One thread owns an element (w, a) per launch: a walker must not be listed twice
+// in ONE launch.  A site tile, u of the slice, the occupancy and the histograms always sit in LDS,
+//   8 (dim kLatTile + dim Np + 4 + 8 kLatThreads/64) + 4 (nsite + (1 + 2 dim) nbin + 8) <= kLatLdsBudget
+// (fits; pigs_lat_init checks it), within what a kernel may ask for without a grant.
+constexpr int kLatThreads = 256;
+constexpr int kLatTile = 256;
+constexpr size_t kLatLdsBudget = 64 * 1024;
+struct LatShape { int fits; size_t lds; };
+LatShape lat_shape(int dim, int Np, int nsite, int nbin);
+hipError_t launch_lat(const DevParams &P, const double *paths, int n, const WalkerList &list, const LatShape &s, int window,
+                      int cm, int nsite, int NsPad, const double *sites, int nbin, double rmax, double *mom,
+                      unsigned long long *nassigned, unsigned long long *nlost, unsigned long long *occ,
+                      unsigned long long *hr, unsigned long long *hx, unsigned long long *hop1, unsigned long long *hopw,
+                      unsigned long long *samples, int *sidx, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

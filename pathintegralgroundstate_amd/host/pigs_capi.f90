@@ -666,6 +666,29 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_nk_read_t
+
+     ! a crystal seen from its lattice (include/pigs_hip.h, pigs_lat_*): looked up at run time, see lat_bind; _accumulate has
+     ! the signature of pigs_grv_accumulate
+     function pigs_lat_init_t(ctx,nsite,sites,nbin,rmax,window,cm) bind(C) result(st)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value         :: ctx
+       integer(c_int32_t), value  :: nsite,nbin,window,cm
+       real(c_double), intent(in) :: sites(*)          ! R(dim,nsite)
+       real(c_double), value      :: rmax
+       integer(c_int) :: st
+     end function pigs_lat_init_t
+
+     function pigs_lat_read_t(ctx,mom,nassigned,nlost,occ,hr,hx,hop1,hopw,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: mom(*)        ! (2+dim,2 window + 1,n_walkers)
+       integer(c_int64_t)             :: nassigned(*)  ! (2 window + 1,n_walkers)
+       integer(c_int64_t)             :: occ(*)        ! (4,2 window + 1,n_walkers)
+       integer(c_int64_t)             :: hr(*),hx(*)   ! (nbin,n_walkers), (2 nbin,dim,n_walkers)
+       integer(c_int64_t)             :: nlost(*),hop1(*),hopw(*),samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_lat_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -736,6 +759,11 @@ module pigs_capi
   procedure(pigs_sqv_accumulate_t), pointer :: nk_accumulate => null()
   procedure(pigs_nk_add_t), pointer         :: nk_add => null()
   procedure(pigs_nk_read_t), pointer        :: nk_read => null()
+
+  ! bound by lat_bind (null until then)
+  procedure(pigs_lat_init_t), pointer       :: lat_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: lat_accumulate => null()
+  procedure(pigs_lat_read_t), pointer       :: lat_read => null()
 
 contains
 
@@ -899,6 +927,16 @@ contains
     call c_f_procpointer(f(5),nk_add)
     call c_f_procpointer(f(6),nk_read)
   end function nk_bind
+
+  ! The lattice entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function lat_bind()
+    type(c_funptr) :: f(3)
+    lat_bind = resolve_all('pigs_lat',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. lat_bind) return
+    call c_f_procpointer(f(1),lat_init)
+    call c_f_procpointer(f(2),lat_accumulate)
+    call c_f_procpointer(f(3),lat_read)
+  end function lat_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

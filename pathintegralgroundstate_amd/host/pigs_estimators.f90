@@ -22,6 +22,7 @@ module pigs_estimators
   public :: normalize_vh, write_vh
   public :: normalize_g3, write_g3, write_g3ang
   public :: normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau
+  public :: normalize_lat, lat_nn_distance, lind_header, write_lind_block, write_lindtau, write_usite
   public :: normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec
 
   type est_params
@@ -872,6 +873,119 @@ contains
     end do
     close (u)
   end subroutine write_nkvec
+
+  ! ---- a crystal seen from its lattice (raw sums of pigs_lat_read of one walker and block, S samples) -> the block values
+  !   BL(1:7)    = <u^2> over the window, gamma = sqrt(<u^2>)/ann, alpha_2 = dim <u^4>/((dim+2) <u^2>^2) - 1, the vacant
+  !                fraction, the multiply occupied fraction, hops per particle and link, hops per particle across the window
+  !   BT(:,a)    = <u^2>(tau_a), <u_k^2>(tau_a) k = 1..dim, gamma(tau_a)           (per window slice)
+  !   BU(1:nbin) = rho_site(r) = hr/(S ns nsite shell volume);  BU(nbin + (k-1) 2 nbin + b) = P(u_k) = hx(b,k)/(N rbin)
+  ! with N the assigned particles of the window (profiles.normalize_lat has the same expressions)
+  subroutine normalize_lat(dim,Np,nsite,window,nbin,ann,rmax,pi,S,mom,nass,occ,hr,hx,hop1,hopw,BL,BT,BU)
+    integer, intent(in)    :: dim,Np,nsite,window,nbin
+    real(8), intent(in)    :: ann,rmax,pi,mom(2+dim,2*window+1)
+    integer(8), intent(in) :: S,nass(2*window+1),occ(4,2*window+1),hr(nbin),hx(2*nbin,dim),hop1,hopw
+    real(8), intent(out)   :: BL(7),BT(2+dim,2*window+1),BU(nbin*(1+2*dim))
+    integer :: a,b,k,ns
+    real(8) :: ntot,u2,u4,sites,rbin,shell,lo,hi
+    ns = 2*window+1
+    do a=1,ns
+       BT(1,a) = mom(1,a)/real(nass(a),8)
+       do k=1,dim
+          BT(1+k,a) = mom(2+k,a)/real(nass(a),8)
+       end do
+       BT(2+dim,a) = sqrt(BT(1,a))/ann
+    end do
+    ntot  = real(sum(nass),8)
+    u2    = sum(mom(1,:))/ntot
+    u4    = sum(mom(2,:))/ntot
+    sites = real(S,8)*real(ns,8)*real(nsite,8)
+    BL(1) = u2
+    BL(2) = sqrt(u2)/ann
+    BL(3) = real(dim,8)*u4/(real(dim+2,8)*u2*u2)-1.d0
+    BL(4) = real(sum(occ(1,:)),8)/sites
+    BL(5) = real(sum(occ(3,:))+sum(occ(4,:)),8)/sites
+    BL(6) = 0.d0
+    if (ns>1) BL(6) = real(hop1,8)/(real(S,8)*real(Np,8)*real(ns-1,8))
+    BL(7) = real(hopw,8)/(real(S,8)*real(Np,8))
+    rbin = rmax/real(nbin,8)
+    do b=1,nbin
+       lo = real(b-1,8)*rbin; hi = real(b,8)*rbin
+       if (dim==2) then
+          shell = pi*(hi**2-lo**2)
+       else
+          shell = 4.d0*pi/3.d0*(hi**3-lo**3)
+       end if
+       BU(b) = real(hr(b),8)/(sites*shell)
+    end do
+    do k=1,dim
+       do b=1,2*nbin
+          BU(nbin+(k-1)*2*nbin+b) = real(hx(b,k),8)/(ntot*rbin)
+       end do
+    end do
+  end subroutine normalize_lat
+
+  ! the shortest minimum-image distance between two of the sites R(dim,nsite) in the box (huge for a single site)
+  function lat_nn_distance(dim,nsite,R,Lbox) result(ann)
+    integer, intent(in) :: dim,nsite
+    real(8), intent(in) :: R(dim,nsite),Lbox(dim)
+    real(8) :: ann,d,r2
+    integer :: i,j,k
+    ann = huge(1.d0)
+    do i=1,nsite-1
+       do j=i+1,nsite
+          r2 = 0.d0
+          do k=1,dim
+             d  = R(k,j)-R(k,i)
+             d  = d-Lbox(k)*anint(d/Lbox(k))
+             r2 = r2+d*d
+          end do
+          ann = min(ann,r2)
+       end do
+    end do
+    if (nsite>1) ann = sqrt(ann)
+  end function lat_nn_distance
+
+  ! first line of lind_vpi*.out
+  subroutine lind_header(u,window)
+    integer, intent(in) :: u,window
+    write (u,'(a,i0,a,i0,a)') '# block, <u^2> over the slices Nb-',window,'..Nb+',window, &
+         & ', Lindemann ratio sqrt(<u^2>)/a_nn, alpha_2, vacant fraction, multiply occupied fraction, hops per particle and link, hops per particle across the window'
+  end subroutine lind_header
+
+  ! one line of lind_vpi*.out
+  subroutine write_lind_block(u,iblock,BL)
+    integer, intent(in) :: u,iblock
+    real(8), intent(in) :: BL(7)
+    write (u,'(20g20.10e3)') real(iblock),BL
+  end subroutine write_lind_block
+
+  ! lindtau_vpi.out: one row per window slice: tau_a = (a-Nb) dt, then the means over the n blocks of <u^2>, <u_k^2> and gamma
+  subroutine write_lindtau(fname,dim,window,dt,n,av)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: dim,window,n
+    real(8), intent(in) :: dt,av(2+dim,-window:window)
+    integer :: a,u
+    open (newunit=u,file=fname)
+    do a=-window,window
+       write (u,'(20g20.10e3)') real(a,8)*dt,av(:,a)/real(n,8)
+    end do
+    close (u)
+  end subroutine write_lindtau
+
+  ! usite_vpi.out: one row per bin b: r at the bin centre, rho_site(r), then per axis k P(u_k = -r) and P(u_k = +r), means
+  ! over the n blocks
+  subroutine write_usite(fname,dim,nbin,rmax,n,av)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: dim,nbin,n
+    real(8), intent(in) :: rmax,av(nbin*(1+2*dim))
+    integer :: b,k,u
+    open (newunit=u,file=fname)
+    do b=1,nbin
+       write (u,'(20g20.10e3)') (real(b,8)-0.5d0)*rmax/real(nbin,8),av(b)/real(n,8), &
+            & (av(nbin+(k-1)*2*nbin+nbin+1-b)/real(n,8),av(nbin+(k-1)*2*nbin+nbin+b)/real(n,8),k=1,dim)
+    end do
+    close (u)
+  end subroutine write_usite
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

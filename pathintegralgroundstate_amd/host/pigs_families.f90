@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum, lattice.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -66,6 +66,16 @@ module pigs_families
      integer :: nk_nmax = 8, nk_nbin = 32
      real(8) :: cworm = 0.d0                        ! the run's CWorm and Nobdm (momentum needs the worm sector)
      integer :: nobdm = 0
+     logical :: lattice = .false.
+     integer :: lat_nbin = 0                        ! <= 0: the run's Nbin (nbin_run)
+     real(8) :: lat_rmax = 0.d0                     ! <= 0: half the sites' nearest-neighbour distance
+     integer :: lat_window = -1                     ! < 0: slice Nb alone
+     logical :: lat_cm = .true.
+     integer :: nbin_run = 0                        ! the run's Nbin and box (what lattice measures its sites in)
+     real(8) :: box(3) = 0.d0
+     integer :: lat_nsite = 0                       ! filled in by the check from config_ini.in: the sites and their
+     real(8) :: lat_ann = 0.d0                      ! nearest-neighbour distance
+     real(8), allocatable :: lat_sites(:,:)         ! (dim,lat_nsite)
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -396,17 +406,40 @@ module pigs_families
      procedure :: write_average => nk_write_average
   end type nk_family
 
-  integer, parameter :: NFAM = 12
+  ! a crystal seen from its lattice: the block's raw sums from the device, the normalised block values of the three files
+  ! (lind_vpi*.out per block; lindtau_vpi.out per window slice; usite_vpi.out per bin); the units of lind_vpi*.out
+  type, extends(family) :: lat_family
+     integer :: window = 0, nbin = 0, nsite = 0
+     real(8) :: rmax = 0.d0, ann = 0.d0
+     real(8), allocatable :: mom(:,:,:),bt(:,:),bu(:)
+     real(8) :: bl(7)
+     integer(c_int64_t), allocatable :: nass(:,:),occ(:,:,:),hr(:,:),hx(:,:,:),nlost(:),hop1(:),hopw(:)
+     type(block_series) :: sL,sT,sU
+     integer, allocatable :: up(:)
+     integer :: upav = -1
+   contains
+     procedure :: check => lat_check
+     procedure :: banner => lat_banner
+     procedure :: setup => lat_setup
+     procedure :: queue => lat_queue
+     procedure :: read => lat_read_block
+     procedure :: block => lat_block
+     procedure :: average => lat_average
+     procedure :: write_walker => lat_write_walker
+     procedure :: write_average => lat_write_average
+  end type lat_family
+
+  integer, parameter :: NFAM = 13
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12,13]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12,13]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
   ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
-  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum
+  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum, 13 lattice
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -447,6 +480,7 @@ contains
     if (keys%triplet)         allocate (g3_family :: fs%slot(10)%f)
     if (keys%three_body)      allocate (atm_family :: fs%slot(11)%f)
     if (keys%momentum)        allocate (nk_family :: fs%slot(12)%f)
+    if (keys%lattice)         allocate (lat_family :: fs%slot(13)%f)
   end subroutine set_create
 
   ! momentum, device-resident sampler: the samples of the step just queued, of all NW walkers
@@ -1955,5 +1989,159 @@ contains
     call write_grvec('nrvec_vpi.out',f%ep,f%nbin,f%nv,f%cnt%nav,f%sR%asum,f%sR%asq)
     close (f%unav)
   end subroutine nk_write_average
+
+  !---------------------------------------------------------------------
+  ! lattice: a crystal seen from the lattice of config_ini.in, over the slices Nb-lat_window..Nb+lat_window of a periodic
+  ! system in 2D or 3D -- lind_vpi*.out (one line per block: <u^2>, the Lindemann ratio, alpha_2, the vacant and the
+  ! multiply occupied fraction of the sites, the hops per particle and link and across the window; per walker, and the
+  ! walker average where there are several), lindtau_vpi.out (one line per window slice: tau, <u^2>, <u_k^2>, gamma) and
+  ! usite_vpi.out (one line per bin: r, rho_site(r), P(u_k = -r) and P(u_k = +r) per axis)
+
+  subroutine lat_check(f,keys,dim,Nb,trap)
+    class(lat_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    logical :: there
+    integer :: u,s,k,ios
+    if (trap) call needs_periodic('lattice','a particle reaches its site by a minimum image in the box')
+    if (dim<2) then
+       write (0,'(a,i0)') ' pigs_vpi: lattice = T needs dim = 2 or 3, not dim = ',dim
+       stop 2
+    end if
+    inquire (file='config_ini.in',exist=there)
+    if (.not. there) then
+       write (0,'(a)') ' pigs_vpi: lattice = T needs the lattice sites: there is no config_ini.in in the run directory'
+       stop 2
+    end if
+    open (newunit=u,file='config_ini.in',status='old')
+    read (u,*,iostat=ios) keys%lat_nsite
+    if (ios==0) read (u,*,iostat=ios)
+    if (ios==0) read (u,*,iostat=ios)
+    if (ios/=0 .or. keys%lat_nsite<1) then
+       write (0,'(a)') ' pigs_vpi: lattice = T: config_ini.in does not start with a number of sites, the box and the density'
+       stop 2
+    end if
+    if (allocated(keys%lat_sites)) deallocate (keys%lat_sites)
+    allocate (keys%lat_sites(dim,keys%lat_nsite))
+    do s=1,keys%lat_nsite
+       read (u,*,iostat=ios) (keys%lat_sites(k,s),k=1,dim)
+       if (ios/=0) then
+          write (0,'(a,i0,a,i0)') ' pigs_vpi: lattice = T: config_ini.in ends before site ',s,' of ',keys%lat_nsite
+          stop 2
+       end if
+    end do
+    close (u)
+    keys%lat_ann = lat_nn_distance(dim,keys%lat_nsite,keys%lat_sites,keys%box(1:dim))
+    if (keys%lat_nsite<2 .or. .not. (keys%lat_ann>0.d0)) then
+       write (0,'(a)') ' pigs_vpi: lattice = T needs two sites or more, no two of them at the same place'
+       stop 2
+    end if
+    if (keys%lat_nbin<=0) keys%lat_nbin = keys%nbin_run
+    if (.not. (keys%lat_rmax>0.d0)) keys%lat_rmax = 0.5d0*keys%lat_ann       ! left out: half the nearest-neighbour distance
+    if (keys%lat_window<0) keys%lat_window = 0
+    call check_window('lattice','lat',keys%lat_window,Nb)
+    if (.not. lat_bind()) call no_backend('lattice','pigs_lat_init / _accumulate / _read','the lattice estimators run')
+  end subroutine lat_check
+
+  subroutine lat_banner(f,keys,trap)
+    class(lat_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,i0,a,g0.6,a,g0.6,a,i0,a,i0,a,l1,a)', '  > Lattice sites        : on (',keys%lat_nsite,' sites of config_ini.in, a_nn = ', &
+         & keys%lat_ann,', displacements below ',keys%lat_rmax,', slices Nb-',keys%lat_window,'..Nb+',keys%lat_window, &
+         & ', centre of mass removed: ',keys%lat_cm,': lind_vpi.out, lindtau_vpi.out, usite_vpi.out)'
+  end subroutine lat_banner
+
+  subroutine lat_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(lat_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: w,ns,dim
+    call family_begin(f,run,ep,NW)
+    f%window = max(keys%lat_window,0)
+    f%nbin = keys%lat_nbin; f%nsite = keys%lat_nsite; f%rmax = keys%lat_rmax; f%ann = keys%lat_ann
+    ns = 2*f%window+1; dim = ep%dim
+    allocate (f%mom(2+dim,ns,NW),f%nass(ns,NW),f%occ(4,ns,NW),f%hr(f%nbin,NW),f%hx(2*f%nbin,dim,NW))
+    allocate (f%nlost(NW),f%hop1(NW),f%hopw(NW),f%bt(2+dim,ns),f%bu(f%nbin*(1+2*dim)))
+    call series_create(f%sL,7,NW,nvec)
+    call series_create(f%sT,(2+dim)*ns,NW,nvec)
+    call series_create(f%sU,f%nbin*(1+2*dim),NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(lat_init(ctx,int(f%nsite,c_int32_t),keys%lat_sites,int(f%nbin,c_int32_t),real(f%rmax,c_double), &
+         & int(f%window,c_int32_t),int(merge(1,0,keys%lat_cm),c_int32_t)),'pigs_lat_init')
+    allocate (f%up(NW))
+    do w=1,NW
+       open (newunit=f%up(w),file='lind_vpi'//trim(run%suffix(w))//'.out')
+       call lind_header(f%up(w),f%window)
+    end do
+    if (run%averages) then
+       open (newunit=f%upav,file='lind_vpi.out')
+       call lind_header(f%upav,f%window)
+    end if
+  end subroutine lat_setup
+
+  subroutine lat_queue(f,ctx,nd,wl)
+    class(lat_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(lat_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_lat_accumulate')
+  end subroutine lat_queue
+
+  subroutine lat_read_block(f,ctx)
+    class(lat_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(lat_read(ctx,f%mom,f%nass,f%nlost,f%occ,f%hr,f%hx,f%hop1,f%hopw,f%smp,f%reset),'pigs_lat_read')
+  end subroutine lat_read_block
+
+  subroutine lat_block(f,w,info,vec)
+    class(lat_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_lat(f%ep%dim,f%ep%Np,f%nsite,f%window,f%nbin,f%ann,f%rmax,f%ep%pi,int(f%smp(w),8),f%mom(:,:,w), &
+         & int(f%nass(:,w),8),int(f%occ(:,:,w),8),int(f%hr(:,w),8),int(f%hx(:,:,w),8),int(f%hop1(w),8),int(f%hopw(w),8), &
+         & f%bl,f%bt,f%bu)
+    call series_add(f%sL,w,f%bl,vec)
+    call series_add(f%sT,w,reshape(f%bt,[size(f%bt)]),vec)
+    call series_add(f%sU,w,f%bu,vec)
+    call count_add(f%cnt,vec)
+    call write_lind_block(f%up(w),info%iblock,f%bl)
+  end subroutine lat_block
+
+  subroutine lat_average(f,info,vec)
+    class(lat_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%sL,vec,nall)
+       call series_average(f%sT,vec,nall)
+       call series_average(f%sU,vec,nall)
+       if (info%ndall>0) call write_lind_block(f%upav,info%iblock,f%sL%mean)
+    end if
+  end subroutine lat_average
+
+  subroutine lat_write_walker(f,suffix,w,nblocks)
+    class(lat_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_lindtau('lindtau_vpi'//trim(suffix)//'.out',f%ep%dim,f%window,f%run%dt,nblocks,f%sT%sum(:,w))
+    call write_usite('usite_vpi'//trim(suffix)//'.out',f%ep%dim,f%nbin,f%rmax,nblocks,f%sU%sum(:,w))
+    close (f%up(w))
+  end subroutine lat_write_walker
+
+  subroutine lat_write_average(f)
+    class(lat_family), intent(inout) :: f
+    call write_lindtau('lindtau_vpi.out',f%ep%dim,f%window,f%run%dt,f%cnt%nav,f%sT%asum)
+    call write_usite('usite_vpi.out',f%ep%dim,f%nbin,f%rmax,f%cnt%nav,f%sU%asum)
+    close (f%upav)
+  end subroutine lat_write_average
 
 end module pigs_families

@@ -11,6 +11,7 @@ module pigs_host_hooks
   use pigs_sampler
   use pigs_estimators, only: est_params, normalize_vh, write_vh, normalize_g3, write_g3, write_g3ang, &
        & normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau, &
+       & normalize_lat, lind_header, write_lind_block, write_lindtau, write_usite, &
        & normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec, write_sqshell, write_grvec, &
        & sqv_shells, sqv_shell_means
 
@@ -304,6 +305,35 @@ contains
     call write_sqshell(cstring(fs),nsh,q,mult,nblk,as,as2)
     call write_grvec(cstring(fr),p,nbin,nv,nblk,ar,ar2)
   end subroutine hs_nk_files
+
+  ! The lattice normalisation and writers of the front end on given sums: nblk blocks of one walker, the arrays of
+  ! pigs_lat_read per block and S samples per block -> the three files: fl one line per block (lind_vpi.out), ft the means
+  ! over the blocks per window slice (lindtau_vpi.out), fu per bin (usite_vpi.out) (names: C strings)
+  subroutine hs_lat_files(dim,Np,nsite,window,nbin,dt,ann,rmax,nblk,S,mom,nass,occ,hr,hx,hop1,hopw,fl,ft,fu) &
+       & bind(C,name='hs_lat_files')
+    integer(c_int), value :: dim,Np,nsite,window,nbin,nblk
+    real(c_double), value :: dt,ann,rmax
+    integer(c_int64_t), intent(in) :: S(nblk),nass(2*window+1,nblk),occ(4,2*window+1,nblk),hr(nbin,nblk),hx(2*nbin,dim,nblk)
+    integer(c_int64_t), intent(in) :: hop1(nblk),hopw(nblk)
+    real(c_double), intent(in)     :: mom(2+dim,2*window+1,nblk)
+    character(kind=c_char), intent(in) :: fl(*),ft(*),fu(*)
+    real(8), allocatable :: BT(:,:),BU(:),aT(:,:),aU(:)
+    real(8) :: BL(7)
+    integer :: ib,u
+    allocate (BT(2+dim,2*window+1),aT(2+dim,2*window+1),BU(nbin*(1+2*dim)),aU(nbin*(1+2*dim)))
+    aT = 0.d0; aU = 0.d0
+    open (newunit=u,file=cstring(fl))
+    call lind_header(u,window)
+    do ib=1,nblk
+       call normalize_lat(dim,Np,nsite,window,nbin,ann,rmax,acos(-1.d0),int(S(ib),8),mom(:,:,ib),int(nass(:,ib),8), &
+            & int(occ(:,:,ib),8),int(hr(:,ib),8),int(hx(:,:,ib),8),int(hop1(ib),8),int(hopw(ib),8),BL,BT,BU)
+       aT = aT+BT; aU = aU+BU
+       call write_lind_block(u,ib,BL)
+    end do
+    close (u)
+    call write_lindtau(cstring(ft),dim,window,dt,nblk,aT)
+    call write_usite(cstring(fu),dim,nbin,rmax,nblk,aU)
+  end subroutine hs_lat_files
 
   ! a C string as a Fortran one
   function cstring(c) result(f)

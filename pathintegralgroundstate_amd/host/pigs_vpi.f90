@@ -71,6 +71,13 @@
 ! normalised with nr_vpi.out's zconf in the blocks that normalise nr_vpi.out -- nkvec_vpi.out, one line per vector (n = 0
 ! first): n_1..n_dim, |k|, n(k), error; nk_vpi.out, one line per |k| shell; n0_vpi.out, one line per block: block, n0,
 ! n(k=0); nrvec_vpi.out, one line per bin: the bin centre, rho1/density, error)
+! (lattice = T, periodic systems in 2D and 3D only: a crystal seen from the lattice sites, the coordinate lines of
+! config_ini.in (their number is its first line and need not be Np), over the slices Nb-lat_window..Nb+lat_window (default 0):
+! every particle is assigned to its nearest site on the GPU; lat_cm = T (default) removes the mean displacement of every
+! slice; lat_nbin bins (default Nbin) up to lat_rmax (default half the sites' nearest-neighbour distance) -- lind_vpi.out,
+! one line per block: the block, <u^2>, the Lindemann ratio, alpha_2, the vacant and the multiply occupied fraction of the
+! sites, hops per particle and link, hops per particle across the window; lindtau_vpi.out, one line per window slice: tau,
+! <u^2>, <u_k^2>, gamma; usite_vpi.out, one line per bin: r, rho_site(r), P(u_k = -r) and P(u_k = +r) per axis)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -128,6 +135,9 @@ program pigs_vpi
   integer           :: atm_window
   real (kind=8)     :: atm_nu,atm_rc
   logical           :: momentum
+  logical           :: lattice,lat_cm
+  integer           :: lat_nbin,lat_window
+  real (kind=8)     :: lat_rmax
   integer           :: nk_nmax,nk_nbin
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
@@ -152,7 +162,8 @@ program pigs_vpi
        &             van_hove,vh_ntau,vh_window,vh_nself,vh_rself, &
        &             triplet,g3_nr,g3_na,g3_rmax,g3_window, &
        &             three_body,atm_nu,atm_rc,atm_window, &
-       &             momentum,nk_nmax,nk_nbin
+       &             momentum,nk_nmax,nk_nbin, &
+       &             lattice,lat_nbin,lat_rmax,lat_window,lat_cm
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -185,6 +196,7 @@ program pigs_vpi
   van_hove = .false.; vh_ntau = 0; vh_window = -1; vh_nself = 50; vh_rself = 0.d0
   triplet = .false.; g3_nr = 10; g3_na = 20; g3_rmax = 0.d0; g3_window = -1
   momentum = .false.; nk_nmax = 8; nk_nbin = 32
+  lattice = .false.; lat_nbin = 0; lat_rmax = 0.d0; lat_window = -1; lat_cm = .true.
   three_body = .false.; atm_nu = -huge(1.d0); atm_rc = 0.d0; atm_window = -1        ! (atm_nu: a value nobody gives, left out -> 1)
 
   read (5,nml=system,iostat=ios);  rewind (5)
@@ -261,7 +273,8 @@ program pigs_vpi
        & triplet=triplet,g3_nr=g3_nr,g3_na=g3_na,g3_rmax=g3_rmax,g3_window=g3_window, &
        & three_body=three_body,atm_nu_given=atm_nu/=-huge(1.d0),atm_nu=merge(atm_nu,1.d0,atm_nu/=-huge(1.d0)), &
        & atm_rc=atm_rc,atm_window=atm_window, &
-       & momentum=momentum,nk_nmax=nk_nmax,nk_nbin=nk_nbin,cworm=CWorm,nobdm=Nobdm)
+       & momentum=momentum,nk_nmax=nk_nmax,nk_nbin=nk_nbin,cworm=CWorm,nobdm=Nobdm, &
+       & lattice=lattice,lat_nbin=lat_nbin,lat_rmax=lat_rmax,lat_window=lat_window,lat_cm=lat_cm,nbin_run=Nbin,box=Lbox)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 

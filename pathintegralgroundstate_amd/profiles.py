@@ -80,6 +80,15 @@ the diagonal configurations of the block, rho1(r)/density -> 1 at r -> 0):
   n(k)              = C / (CWorm * zconf * Nobdm),   n(0) = nopen / (CWorm * zconf * Nobdm),   n0 = n(0) / Np
   rho1(bin)/density = H / (CWorm * zconf * Nobdm * density * bin volume)
 and the sum of n(k) over all k, -k included, is Np.
+Lattice estimators of a crystal (normalize_lat, nearest_neighbour_distance, PigsContext.lat_read, pigs_lat_*): every
+particle of a window slice is assigned to its nearest lattice site, u is its displacement from it (less the slice's mean
+displacement with cm), and with N_a = nassigned of slice a, S = samples and ns = 2 window + 1:
+  <u^2>(tau_a) = mom[a, 0] / N_a,  <u_k^2>(tau_a) = mom[a, 2 + k] / N_a;  over the window: sum_a mom / sum_a N_a
+  gamma   = sqrt(<u^2>) / a_nn                                           (the Lindemann ratio)
+  alpha_2 = dim <u^4> / ((dim + 2) <u^2>^2) - 1                          (normalize_msd's expression; 0 for a Gaussian)
+  vacant  = sum_a occ[a, 0] / (S ns nsite),   multiple = sum_a (occ[a, 2] + occ[a, 3]) / (S ns nsite)
+  hops per particle and link = hop1 / (S Np (ns - 1)),   across the window = hopw / (S Np)
+  rho_site(r) = hr / (S ns nsite shell volume),   P(u_k) = hx[k] / (sum_a N_a rbin)
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -473,6 +482,56 @@ def normalize_nrvec(sums, cworm, zconf, nobdm, density, Lbox, dim):
         rho1 = H / den.reshape(den.shape + (1,) * dim)
     x = [-0.5 * L[k] + (np.arange(nbin) + 0.5) * b[k] for k in range(dim)]
     return {"rho1": rho1, "x": x}
+
+
+def nearest_neighbour_distance(sites, Lbox):
+    """The shortest minimum-image distance between two of the lattice sites [nsite, dim] in the periodic box Lbox (every
+    coordinate difference folded by its nearest multiple of the side); inf for a single site."""
+    R = np.asarray(sites, dtype=np.float64)
+    if R.ndim != 2:
+        raise ValueError("sites must be [nsite, dim]")
+    L = np.asarray(Lbox, dtype=np.float64)[:R.shape[1]]
+    best = np.inf
+    for s in range(R.shape[0] - 1):
+        d = R[s + 1:] - R[s]
+        d = d - L * np.rint(d / L)
+        best = min(best, float(np.sqrt((d * d).sum(axis=1).min())))
+    return best
+
+
+def normalize_lat(raw, Np, nsite, a_nn, rmax):
+    """raw: the dict of lat_read (mom [W, ns, 2 + dim], nassigned [W, ns], nlost, occ [W, ns, 4], hr [W, nbin],
+    hx [W, dim, 2 nbin], hop1, hopw, samples [W]) or one walker's slice of it; a_nn: the sites' nearest-neighbour distance;
+    rmax: the range of the histograms.  Returns a dict: u2 [.., ns], uk2 [.., ns, dim] and gamma_tau [.., ns] per window
+    slice; over the window u2_mean, gamma, alpha2, vacant, multiple, hops_link, hops_window [..]; r [nbin] and
+    rho_site [.., nbin]; x [2 nbin] and pu [.., dim, 2 nbin].  A walker without samples gives NaN."""
+    mom = np.asarray(raw["mom"], dtype=np.float64)
+    n = np.asarray(raw["nassigned"], dtype=np.float64)
+    occ = np.asarray(raw["occ"], dtype=np.float64)
+    hr = np.asarray(raw["hr"], dtype=np.float64)
+    hx = np.asarray(raw["hx"], dtype=np.float64)
+    S = np.asarray(raw["samples"], dtype=np.float64)
+    dim, ns, nbin = mom.shape[-1] - 2, mom.shape[-2], hr.shape[-1]
+    if dim not in (2, 3) or n.shape != mom.shape[:-1] or occ.shape != n.shape + (4,) or hx.shape[-2:] != (dim, 2 * nbin):
+        raise ValueError("the arrays of lat_read do not fit each other")
+    rbin = float(rmax) / nbin
+    edges = np.arange(nbin + 1) * rbin
+    shell = np.pi * np.diff(edges ** 2) if dim == 2 else 4.0 * np.pi / 3.0 * np.diff(edges ** 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u2 = mom[..., 0] / n
+        uk2 = mom[..., 2:] / n[..., None]
+        ntot = n.sum(axis=-1)
+        u2m = mom[..., 0].sum(axis=-1) / ntot
+        u4m = mom[..., 1].sum(axis=-1) / ntot
+        sites = S * ns * float(nsite)
+        out = {"u2": u2, "uk2": uk2, "gamma_tau": np.sqrt(u2) / a_nn, "u2_mean": u2m, "gamma": np.sqrt(u2m) / a_nn,
+               "alpha2": dim * u4m / ((dim + 2) * u2m * u2m) - 1.0,
+               "vacant": occ[..., 0].sum(axis=-1) / sites, "multiple": (occ[..., 2] + occ[..., 3]).sum(axis=-1) / sites,
+               "hops_link": (np.asarray(raw["hop1"], dtype=np.float64) / (S * Np * (ns - 1)) if ns > 1 else 0.0 * S),
+               "hops_window": np.asarray(raw["hopw"], dtype=np.float64) / (S * Np),
+               "r": 0.5 * (edges[1:] + edges[:-1]), "rho_site": hr / (sites[..., None] * shell),
+               "x": -float(rmax) + (np.arange(2 * nbin) + 0.5) * rbin, "pu": hx / (ntot[..., None, None] * rbin)}
+    return out
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
