@@ -409,6 +409,8 @@ contains
        end if
        call mt_seed(s%rng(w),seed+w0+w-1)
        if (crystal .and. .not. trap) then
+          ! one shard at a time: the shards are threads of one process, and a file may be connected to one unit only
+          !$omp critical (config_ini)
           open (newunit=ucfg,file='config_ini.in',status='old')
           read (ucfg,*)
           read (ucfg,*)
@@ -417,6 +419,7 @@ contains
              read (ucfg,*) (s%Path(k,ip,0,w),k=1,dim)
           end do
           close (ucfg)
+          !$omp end critical (config_ini)
        else
           do ip=1,Np
              do k=1,dim

@@ -22,6 +22,10 @@ Normalisations (one walker, one block with S samples, i.e. S diagonal steps in t
   momentum             n(k) = C / (CWorm zconf Nobdm), n(0) = open samples / (CWorm zconf Nobdm), n0 = n(0) / Np;
                        rho_1/rho per Cartesian bin = H / (CWorm zconf Nobdm density prod_k L_k / Ng); zconf the diagonal
                        configurations since the walker's last normalised block
+  lattice              ns = 2 window + 1: <u^2>(tau_a) = mom_0(a) / assigned(a); over the window the sums over a of both;
+                       gamma = sqrt(<u^2>) / a_nn; alpha_2 = dim <u^4> / ((dim + 2) <u^2>^2) - 1; vacant and multiply
+                       occupied: sites / (S ns nsite); hops / (S Np (ns - 1)) per link and / (S Np) across the window;
+                       rho_site = hr / (S ns nsite dV_j); P(u_k) = hx / (assigned of the window x rmax / nbin)
 
 Statistics: a block counts for a walker only if the walker had a diagonal step in it.  A file's mean is the mean of the
 counted block values; its error the "variance" of the reference's files, sqrt((<b^2> - <b>^2) / n) over the n counted
@@ -237,6 +241,45 @@ def norm_nrvec(H, cworm, zconf, nobdm, density, Lbox, dim):
         cell = cell * (float(Lbox[k]) / H.shape[-1])
     with np.errstate(all="ignore"):
         return H / (_s(cworm * np.asarray(zconf, np.float64) * nobdm, dim) * density * cell)
+
+
+def norm_lat(mom, nass, occ, hr, hx, hop1, hopw, S, Np, nsite, a_nn, rmax, dim):
+    """mom [..., ns, 2 + dim], nass [..., ns], occ [..., ns, 4], hr [..., nbin], hx [..., dim, 2 nbin], hop1, hopw, S [...]:
+    the block values of the lattice family, from include/pigs_hip.h and the column text of pigs_vpi.f90.  Per window slice
+    <u^2> = sum m2 / assigned, <u_k^2> and gamma = sqrt(<u^2>) / a_nn; over the window the same with both sums taken over
+    the slices first, alpha_2 = dim <u^4> / ((dim + 2) <u^2>^2) - 1; the vacant and the multiply occupied (2, or 3 and
+    more) fraction of the S ns nsite site-slices; hops per PARTICLE and link (ns - 1 links; none: 0) and per particle
+    across the window; rho_site = hr / (site-slices x shell volume); P(u_k) = hx / (assigned of the window x bin width)."""
+    mom, nass, occ = np.asarray(mom, np.float64), np.asarray(nass, np.float64), np.asarray(occ, np.float64)
+    hr, hx = np.asarray(hr, np.float64), np.asarray(hx, np.float64)
+    ns, nbin = mom.shape[-2], hr.shape[-1]
+    rbin = float(rmax) / nbin
+    N, m2, m4 = np.zeros(nass.shape[:-1]), np.zeros(nass.shape[:-1]), np.zeros(nass.shape[:-1])
+    empty, many = np.zeros(nass.shape[:-1]), np.zeros(nass.shape[:-1])
+    for a in range(ns):
+        N, m2, m4 = N + nass[..., a], m2 + mom[..., a, 0], m4 + mom[..., a, 1]
+        empty, many = empty + occ[..., a, 0], many + occ[..., a, 2] + occ[..., a, 3]
+    with np.errstate(all="ignore"):
+        S = np.asarray(S, np.float64)
+        slices = S * ns * nsite
+        u2 = mom[..., 0] / nass
+        um = m2 / N
+        links = np.asarray(hop1, np.float64) / (S * Np * (ns - 1)) if ns > 1 else np.zeros(S.shape)
+        return {"u2": u2, "uk2": mom[..., 2:2 + dim] / nass[..., None], "gamma_tau": np.sqrt(u2) / a_nn, "u2_mean": um,
+                "gamma": np.sqrt(um) / a_nn, "alpha2": dim * (m4 / N) / ((dim + 2.0) * um * um) - 1.0,
+                "vacant": empty / slices, "multiple": many / slices, "hops_link": links,
+                "hops_window": np.asarray(hopw, np.float64) / (S * Np),
+                "rho_site": hr / (_s(slices, 1) * shell_volumes(dim, nbin, rbin)), "pu": hx / (_s(N, 2) * rbin)}
+
+
+LAT_OUT = ("u2", "uk2", "gamma_tau", "u2_mean", "gamma", "alpha2", "vacant", "multiple", "hops_link", "hops_window",
+           "rho_site", "pu")
+
+
+def norm_lat_raw(raw, Np, nsite, a_nn, rmax):
+    """norm_lat on the dict of PigsContext.lat_read (or of lat_numpy's expected), any leading axes."""
+    return norm_lat(raw["mom"], raw["nassigned"], raw["occ"], raw["hr"], raw["hx"], raw["hop1"], raw["hopw"], raw["samples"],
+                    Np, nsite, a_nn, rmax, np.asarray(raw["mom"]).shape[-1] - 2)
 
 
 def pressure(kin, w, density, dim):

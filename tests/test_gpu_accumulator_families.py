@@ -1,12 +1,13 @@
 """The per-walker accumulator families on the MI355X where they meet: one context keeps ONE set of launch marks
 (csrc/pigs_walker_split.h) for the five families that may not list a walker twice in a launch.  Interleaved calls of
 fqt, sqv, tau, fqv and fqs with repeated walkers must leave in every family exactly the bits and sample counts that the
-same calls of that family alone leave in a fresh context on the same worldlines.  The same again with bop, atm and nk
-(pigs_nk_add), which take launches on the same marks, and grv, vh and g3, which advance the launch counter without
-checking it, interleaved between them."""
+same calls of that family alone leave in a fresh context on the same worldlines.  The same again with bop, atm, nk
+(pigs_nk_add) and lat, which take launches on the same marks, and grv, vh and g3, which advance the launch counter
+without checking it, interleaved between them."""
 import numpy as np
 import pytest
 
+import lat_numpy
 from pathintegralgroundstate_amd import SystemConfig
 
 pytestmark = pytest.mark.gpu
@@ -45,13 +46,14 @@ def test_interleaved_families_keep_their_own_bits(gpu_lib):
             assert np.array_equal(a.view(np.uint64), t.view(np.uint64)), (f, k)
 
 
-# bop, atm and nk (through nk_add) take launches on the same marks; grv, vh and g3 advance the same launch counter and
+# bop, atm, nk (through nk_add) and lat take launches on the same marks; grv, vh and g3 advance the same launch counter and
 # may list a walker twice in a launch.  (walkers, and for nk the samples per listed walker)
-MORE = [("bop", [2, 0, 2]), ("grv", [1, 1, 0]), ("fqt", [2, 0, 2]), ("atm", [0, 2, 0]), ("vh", [2, 2, 1]), ("nk", [1, 1, 2], [2, 1, 3]),
-        ("sqv", [2, 2]), ("g3", [0, 1, 0, 0]), ("bop", None), ("tau", [0, 2, 0]), ("atm", [1, 1, 2]), ("nk", [2, 0], [1, 2]),
-        ("fqv", [1, 1, 2]), ("grv", None), ("g3", [2, 2]), ("fqs", [2, 1, 2]), ("vh", [0, 0, 0]), ("atm", None), ("fqt", None)]
+MORE = [("bop", [2, 0, 2]), ("grv", [1, 1, 0]), ("lat", [2, 0, 2]), ("fqt", [2, 0, 2]), ("atm", [0, 2, 0]), ("vh", [2, 2, 1]),
+        ("nk", [1, 1, 2], [2, 1, 3]), ("sqv", [2, 2]), ("g3", [0, 1, 0, 0]), ("bop", None), ("lat", None), ("tau", [0, 2, 0]),
+        ("atm", [1, 1, 2]), ("nk", [2, 0], [1, 2]), ("fqv", [1, 1, 2]), ("grv", None), ("g3", [2, 2]), ("fqs", [2, 1, 2]),
+        ("lat", [2, 2, 1]), ("vh", [0, 0, 0]), ("atm", None), ("fqt", None)]
 LISTED = {"fqt": [2, 1, 3], "sqv": [0, 0, 2], "tau": [2, 0, 1], "fqv": [0, 2, 1], "fqs": [0, 1, 2], "bop": [2, 1, 3],
-          "atm": [3, 3, 3], "grv": [2, 3, 1], "vh": [3, 1, 2], "g3": [3, 1, 2], "nk": [2, 3, 4]}
+          "atm": [3, 3, 3], "grv": [2, 3, 1], "vh": [3, 1, 2], "g3": [3, 1, 2], "nk": [2, 3, 4], "lat": [2, 2, 5]}
 
 
 def _run_more(gpu_lib, cfg, VT, WF, P, init, pairs, families):
@@ -71,9 +73,10 @@ def _run_more(gpu_lib, cfg, VT, WF, P, init, pairs, families):
         return {f: getattr(ctx, f + "_read")() for f in families}
 
 
-def test_interleaved_eleven_families_keep_their_own_bits(gpu_lib):
-    """The five families above with bop, atm, nk, grv, vh and g3 between them, walkers repeated within the lists: in every
-    family the bits and the sample counts of that family's calls alone in a fresh context."""
+def test_interleaved_twelve_families_keep_their_own_bits(gpu_lib):
+    """The five families above with bop, atm, nk, lat, grv, vh and g3 between them, walkers repeated within the lists: in
+    every family the bits and the sample counts of that family's calls alone in a fresh context.  lat: three calls, one of
+    them with every walker, on the first five centres of a 3 x 3 grid, window 2, the centre of mass removed."""
     W = 3
     cfg = SystemConfig(dim=2, Np=5, Nb=3, density=0.25)
     VT, WF = gpu_lib.build_tables(cfg)
@@ -82,7 +85,9 @@ def test_interleaved_eleven_families_keep_their_own_bits(gpu_lib):
     P = rng.uniform(-0.5, 0.5, (W,) + tuple(cfg.path_shape)) * L
     pairs = rng.uniform(-0.5, 0.5, (sum(sum(c[2]) for c in MORE if c[0] == "nk"), 2, cfg.dim)) * L
     init = dict(INIT, bop=(cfg.rcut, 1, 4, 3, cfg.rcut / 3.0), atm=(cfg.rcut, 1), nk=(2, 3), grv=(4, 1, 3, cfg.rcut / 3.0),
-                vh=(2, 1, 3, cfg.rcut / 3.0, 4, cfg.rcut / 4.0), g3=(2, cfg.rcut / 2.0, 3, 1))
+                vh=(2, 1, 3, cfg.rcut / 3.0, 4, cfg.rcut / 4.0), g3=(2, cfg.rcut / 2.0, 3, 1),
+                lat=(lat_numpy.grid_sites(2, 3, cfg.Lbox, cfg.Np), 4, cfg.rcut, 2, 1))
+    assert init["lat"][0].shape == (cfg.Np, cfg.dim) and np.all(np.isfinite(init["lat"][0]))
     together = _run_more(gpu_lib, cfg, VT, WF, P, init, pairs, list(init))
     for f in init:
         alone = _run_more(gpu_lib, cfg, VT, WF, P, init, pairs, [f])[f]

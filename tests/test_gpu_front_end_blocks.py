@@ -21,7 +21,8 @@ normalises n(k), the carry-over, zconf and the normalisation are restated here (
 The newer families where they meet the others: A+ (all ten periodic diagonal keys in one 3D run, single keys against
 it), B+ and D+ (the worm run with all ten keys, unsharded and on two contexts: partial and empty blocks, momentum's own
 block count next to the diagonal families' on one all-reduced vector), E (boxes with unequal sides, the box-dependent
-defaults left out).
+defaults left out), L (lattice beside the ten periodic diagonal keys on he4_crystal, its raw sums from lat_numpy on the
+replay's snapshots and its columns from block_stats_numpy.norm_lat).
 
 Tolerances: the restatements' own per-element bounds, carried through the block sums, the normalisation and the means,
 plus one unit of the tenth printed digit (PRINT); integer histograms: PRINT alone; error columns, the root of a
@@ -47,6 +48,7 @@ gpu = pytest.mark.gpu
 # estimator grids: small, so that numpy stays fast
 NMAX, WINDOW, NTAU, GR_NBIN = 2, 2, 3, 8
 BO_NH, BO_NR, G3_NR, G3_NA, ATM_NU, NK_NMAX, NK_NBIN = 8, 8, 3, 4, 2.5, 2, 4
+LAT_NBIN = 6
 # (the self part of van Hove at lag 0 is one full bin, the same value in every block: an ill-conditioned error bar by the
 # expectation alone.  25 bins x 4 lags keep that one row within 1 % of the file's rows; bins of 0.08 resolve the displacements)
 VH_NS, VH_RSELF = 25, 2.0
@@ -62,12 +64,15 @@ KEYS = {"fq_tau": f"fq_tau = T, fq_ntau = {NTAU}, fq_window = {WINDOW}",
         "van_hove": f"van_hove = T, vh_ntau = {NTAU}, vh_window = {WINDOW}, vh_nself = {VH_NS}, vh_rself = {VH_RSELF!r}d0",
         "triplet": f"triplet = T, g3_nr = {G3_NR}, g3_na = {G3_NA}, g3_window = {WINDOW}",
         "three_body": f"three_body = T, atm_window = {WINDOW}, atm_nu = {ATM_NU!r}d0",
-        "momentum": f"momentum = T, nk_nmax = {NK_NMAX}, nk_nbin = {NK_NBIN}"}
+        "momentum": f"momentum = T, nk_nmax = {NK_NMAX}, nk_nbin = {NK_NBIN}",
+        # (RMAX: the range of the displacement histograms, which scenario L fills in)
+        "lattice": f"lattice = T, lat_window = {WINDOW}, lat_nbin = {LAT_NBIN}, lat_rmax = RMAX"}
 FILES = {"fq_tau": ["fqt_vpi"], "sq_vector": ["sqvec_vpi", "sq_vpi"], "fq_vector": ["fqvec_vpi", "fqsh_vpi"],
          "fq_self": ["fqself_vpi", "fqssh_vpi", "msd_vpi"], "gr_vector": ["grvec_vpi", "grw_vpi"],
          "tau_profile": ["tau_vpi"], "density_profile": ["dens_vpi", "rho_vpi", "pr_vpi"],
          "bond_order": ["bo_vpi", "boh_vpi", "g6_vpi"], "van_hove": ["gd_vpi", "gs_vpi"], "triplet": ["g3_vpi", "g3ang_vpi"],
-         "three_body": ["v3tau_vpi"], "momentum": ["nkvec_vpi", "nk_vpi", "nrvec_vpi"]}
+         "three_body": ["v3tau_vpi"], "momentum": ["nkvec_vpi", "nk_vpi", "nrvec_vpi"],
+         "lattice": ["lind_vpi", "lindtau_vpi", "usite_vpi"]}
 # the files with one line per block, which check_v3 and check_n0 read
 BLOCK_FILES = {"tau_profile": ["press_vpi"], "three_body": ["v3_vpi"], "momentum": ["n0_vpi"]}
 # scenario B: (Nblock, Nstep) of he4_wormbusy_s7 with four walkers, chosen from the replay's open / closed pattern over 60
@@ -975,3 +980,156 @@ def test_trapped_run_profiles_three_blocks(gpu_lib, oracle, exe, tmp_path):
     out = _run(exe, txt + _gpu_group(C_KEYS, 2, "device_sampler = T, "), d)
     check_run(d, out, rep, E, C_KEYS, "C:")
     assert not os.path.exists(os.path.join(d, "press_vpi.out"))
+
+
+# ---- L: the lattice family beside the ten periodic diagonal keys, on a crystal -----------------------------------------
+L_WALKERS, L_BLOCKS, L_STEPS = 3, 3, 4
+L_KEYS = A_PLUS + ["lattice"]
+LIND = ("u2_mean", "gamma", "alpha2", "vacant", "multiple", "hops_link", "hops_window")
+# mom lies within 1e-12 of itself (test_gpu_lat.py): <u^2> and gamma carry that, alpha_2 + 1 = dim <u^4> / ((dim + 2) <u^2>^2)
+# three times that; the other four columns are ratios of integers
+LIND_REL = np.array([1e-12, 1e-12, 3e-12, 0.0, 0.0, 0.0, 0.0])
+
+
+def _crystal_dir(base, name):
+    import shutil
+    d = os.path.join(str(base), name)
+    os.makedirs(d)
+    shutil.copy(os.path.join(RUNS, "he4_crystal", "config_ini.in"), d)
+    return d
+
+
+@pytest.fixture(scope="module")
+def scn_l(gpu_lib, oracle):
+    """he4_crystal: 27 particles started on the sites of config_ini.in, worm sector on.  The raw lattice sums of every
+    diagonal step from lat_numpy on the replay's snapshots, the columns from block_stats_numpy.norm_lat."""
+    import lat_numpy
+    from pathintegralgroundstate_amd import SystemConfig
+    W = L_WALKERS
+    txt, _ = _input("he4_crystal", L_BLOCKS, L_STEPS)
+    ini = open(os.path.join(RUNS, "he4_crystal", "config_ini.in")).read().split("\n")
+    Np, L, dens = int(ini[0]), [float(x) for x in ini[1].split()], float(ini[2])
+    cfg = SystemConfig.from_namelists(txt, Np=Np, density=dens, Lbox=L)
+    assert cfg.CWorm > 0 and cfg.dim == 3
+    R = np.array([[float(x) for x in l.split()] for l in ini[3:3 + Np]])
+    assert R.shape == (Np, cfg.dim)
+    # the sites' nearest-neighbour distance, every difference folded by the nearest multiple of the side
+    d = R[:, None, :] - R[None, :, :]
+    d = d - np.asarray(L) * np.rint(d / np.asarray(L))
+    r2 = (d * d).sum(axis=-1)
+    r2[np.diag_indices(Np)] = np.inf
+    ann = float(np.sqrt(r2.min()))
+    rmax = float(np.floor(0.5 * ann * 1e6) / 1e6)      # six decimals: the namelist and numpy read the same double
+    rep = replay(gpu_lib, oracle, cfg, W, L_BLOCKS, L_STEPS, start=R)
+    S = _blocks(rep["diag"].astype(np.int64), rep)
+    print("scenario L: diagonal steps per (walker, block):", S.tolist())
+    steps = []
+    for t in range(rep["snaps"].shape[0]):
+        ws = [int(w) for w in np.flatnonzero(rep["diag"][t])]
+        steps.append(lat_numpy.Window(rep["snaps"][t], cfg.Nb, WINDOW, cfg.Lbox, R, LAT_NBIN, rmax, 1).expected(ws))
+    raw = {k: _blocks(np.stack([e[k] for e in steps]), rep) for k in steps[0]}
+    cnt = S > 0
+    assert np.array_equal(raw["samples"], S) and cnt.any()
+    assert (S == 0).any() and ((S >= 1) & (S < L_STEPS)).any(), "no empty or no partial (walker, block)"
+    assert (cnt.sum(axis=0) == 1).any() and cnt.any(axis=0).all()       # a block of one walker alone; no block of nobody
+    v = bs.norm_lat_raw(raw, Np, Np, ann, rmax)
+
+    def clean(x):
+        x = np.array(x, np.float64)
+        x[~cnt] = 0.0
+        return x
+
+    lind = clean(np.stack([v[k] for k in LIND], axis=-1))
+    tau = clean(np.concatenate([v["u2"][..., None], v["uk2"], v["gamma_tau"][..., None]], axis=-1))
+    pu = v["pu"]                                                        # [W, Nblock, dim, 2 nbin]: -rmax .. rmax
+    cols = [v["rho_site"]]
+    for k in range(cfg.dim):
+        cols += [pu[..., k, LAT_NBIN - 1::-1], pu[..., k, LAT_NBIN:]]    # P(u_k = -r), P(u_k = +r) at r ascending
+    us = clean(np.stack(cols, axis=-1))
+    scale = np.abs(lind)
+    scale[..., 2] += 1.0
+    vals = {"lind_vpi": (lind, (PRINT + LIND_REL) * scale), "lindtau_vpi": (tau, (PRINT + 1e-12) * np.abs(tau)),
+            "usite_vpi": (us, PRINT * np.abs(us))}
+    assert np.all(lind[cnt][:, 0] > 0) and np.all(lind[cnt][:, 1] < 0.5) and us[cnt].any()
+    group = _gpu_group(L_KEYS, W, "device_sampler = T, ", cfg).replace("RMAX", f"{rmax:.6f}d0")
+    return dict(txt=txt, rep=rep, cfg=cfg, cnt=cnt, vals=vals, rmax=rmax, group=group)
+
+
+def check_lattice(d, sc, what, per_walker=True):
+    """lind_vpi*.out: one line per block that the walker (or, merged, some walker) counted; lindtau_vpi*.out and
+    usite_vpi*.out: the means over those blocks.  Merged: per block the mean over the walkers that counted it."""
+    rep, cfg, cnt = sc["rep"], sc["cfg"], sc["cnt"]
+    W, dim, ns = rep["W"], cfg.dim, 2 * WINDOW + 1
+    for w in (list(range(W)) if per_walker else []) + [None]:
+        suffix = f".w{w:04d}" if w is not None else ""
+        tag = f"{what} walker {w}"
+        v, t = sc["vals"]["lind_vpi"]
+        if w is None:
+            (v, cb), t = bs.walker_average(v, cnt), bs.walker_average(t, cnt)[0]
+        else:
+            v, t, cb = v[w], t[w], cnt[w]
+        path = os.path.join(d, f"lind_vpi{suffix}.out")
+        assert open(path).readline().startswith(f"# block, <u^2> over the slices Nb-{WINDOW}..Nb+{WINDOW}, Lindemann ratio"), tag
+        rows = np.array(_rows(path)).reshape(-1, 8)
+        blocks = np.flatnonzero(cb)
+        assert rows[:, 0].tolist() == (blocks + 1.0).tolist(), (tag, rows[:, 0].tolist(), cb.tolist())
+        err = np.abs(rows[:, 1:] - v[blocks])
+        assert np.all(np.isfinite(rows)) and np.all(err <= t[blocks]), (tag, "lind", (err / np.maximum(t[blocks], 1e-300)).max())
+        index = {"lindtau_vpi": (np.arange(ns) - WINDOW) * cfg.dt, "usite_vpi": (np.arange(LAT_NBIN) + 0.5) * sc["rmax"] / LAT_NBIN}
+        for base, ncol in (("lindtau_vpi", 2 + dim), ("usite_vpi", 1 + 2 * dim)):
+            v, t = sc["vals"][base]
+            m, _, n = bs.walker_stats(v, cnt, w) if w is not None else bs.average_stats(v, cnt)
+            assert n == blocks.size
+            tab = _table(os.path.join(d, f"{base}{suffix}.out"), (index[base].size, 1 + ncol))
+            assert np.allclose(tab[:, 0], index[base], rtol=PRINT, atol=1e-300), (tag, base)
+            if n == 0:                                                  # never diagonal: a mean over no block
+                assert np.all(np.isnan(tab[:, 1:])), (tag, base)
+                continue
+            err, tol = np.abs(tab[:, 1:] - m), bs.mean_bound(t, cnt, w)
+            assert np.all(np.isfinite(tab)) and np.all(err <= tol), (tag, base, (err / np.maximum(tol, 1e-300)).max())
+            assert m.any(), (tag, base)
+
+
+@pytest.fixture(scope="module")
+def run_l(exe, scn_l, tmp_path_factory):
+    """Scenario L's run with all eleven keys, unsharded."""
+    d = _crystal_dir(tmp_path_factory.mktemp("L"), "all")
+    return d, _run(exe, scn_l["txt"] + scn_l["group"], d)
+
+
+@gpu
+def test_crystal_run_lattice_beside_ten_keys(exe, scn_l, run_l, tmp_path):
+    """he4_crystal, Nblock = 3, Nstep = 4, three walkers, worm sector on, lattice (window 2, 6 bins) behind the ten
+    periodic diagonal keys on one all-reduced block vector.  The replay is the run; the three lattice files of every
+    walker and the merged ones -- lind_vpi.out with the walker average of every block that some walker counted,
+    lindtau_vpi.out and usite_vpi.out with the all-reduced means -- against lat_numpy on the replay's snapshots and
+    norm_lat.  A run with the key alone writes the same characters into all of them.
+    Diagonal steps per block of this fixture: walker 0: 4 0 0, walker 1: 4 4 4, walker 2: 1 0 1 -- empty blocks behind a
+    counted one, a partial block, a block that one walker alone counted; the scenario asserts that both kinds are there."""
+    d, out = run_l
+    assert "Lattice sites" in out
+    check_replay_is_the_run(d, out, scn_l["rep"])
+    check_lattice(d, scn_l, "L all keys:")
+    one = _crystal_dir(tmp_path, "alone")
+    group = _gpu_group(["lattice"], L_WALKERS, "device_sampler = T, ", scn_l["cfg"]).replace("RMAX", f"{scn_l['rmax']:.6f}d0")
+    out1 = _run(exe, scn_l["txt"] + group, one)
+    check_replay_is_the_run(one, out1, scn_l["rep"])
+    _same_files(d, one, ["lattice"], L_WALKERS)
+
+
+@gpu
+def test_crystal_run_lattice_sharded(exe, scn_l, run_l, tmp_path):
+    """Scenario L on two contexts of one GPU (two walkers and one): the merged files, whose block values meet in the
+    all-reduced vector, against the expectation and, number for number to the printed digits, against the unsharded run;
+    the per-walker files byte for byte."""
+    d, _ = run_l
+    two = _crystal_dir(tmp_path, "two")
+    out = _run(exe, scn_l["txt"] + scn_l["group"].replace("device_sampler = T, ", "device_sampler = T, device = 0, n_gpus = 2, same_device = T, "), two)
+    assert re.search(r"GPUs \(walker shards\):\s*2\b", out), out[:3000]
+    check_replay_is_the_run(two, out, scn_l["rep"])
+    check_lattice(two, scn_l, "L sharded:")
+    for base in FILES["lattice"]:
+        for w in range(L_WALKERS):
+            assert _same(d, two, f"{base}.w{w:04d}.out"), (base, w)
+        a, b = np.array(_rows(os.path.join(d, base + ".out"))), np.array(_rows(os.path.join(two, base + ".out")))
+        assert a.shape == b.shape and np.allclose(a, b, rtol=2 * PRINT, atol=2 * PRINT, equal_nan=True), base

@@ -6,6 +6,9 @@ per element is 1e-12 * Sum|terms| from the numpy side, the project's bound for a
 every term is a square, so Sum|terms| is the sum itself.  Where an element holds one non-zero term it must have the
 restatement's bits.  No comparison masks or skips elements.  The inputs are jittered lattices in a box of unequal sides:
 particle i sits near site i (mod the sites), so nsite = Np - 1 doubles one site and nsite = Np + 1 leaves one empty.
+Such a lattice of cell centres never reaches the fold of the winner's displacement, the tile boundary of the site loop,
+the class "three or more", the assigned count below Np with cm = 1 or the ends of the axis histograms: section 2b builds
+those by hand and asserts on the numpy side that each case reaches its branch.
 
 Largest |got - want| / bound seen on the MI355X: see DESIGN.md (the lattice section)."""
 import ctypes as C
@@ -126,11 +129,12 @@ def test_exchanged_labels_along_tau(gpu_lib, dim):
 
 
 # ---- 2. edges: bit for bit ---------------------------------------------------------------------------------------------
-def _one_moving(dim, x, nbin, rmax):
-    """Three particles and three sites in a wide box: particles 1 and 2 sit on sites 1 and 2, particle 0 at x."""
+def _one_moving(dim, x, nbin, rmax, x0=-1.0):
+    """Three particles and three sites in a wide box: particles 1 and 2 sit on sites 1 and 2, particle 0 at x; site 0 at
+    (x0, 0, ..)."""
     cfg = SystemConfig(dim=dim, Np=3, Nb=1, density=3.0 / 40.0 ** dim)
     R = np.zeros((3, dim))
-    R[0, 0], R[1, 0], R[2, 1] = -1.0, 1.0, 9.0
+    R[0, 0], R[1, 0], R[2, 1] = x0, 1.0, 9.0
     X = R.copy()
     X[0] = x
     P = np.broadcast_to(X, (1, 3, 3, dim)).copy()
@@ -180,6 +184,241 @@ def test_nan_coordinate_is_lost(gpu_lib):
     assert got["nlost"].tolist() == [1] and got["nassigned"].tolist() == [[Np, Np - 1, Np]]
     assert got["occ"][0, 1].tolist() == [1, Np - 1, 0, 0] and np.array_equal(got["occ"][0, ::2], clean["occ"][0, ::2])
     assert got["hop1"].tolist() == [0] and int(got["hr"].sum()) == int(clean["hr"].sum()) - 1
+
+
+# ---- 2b. the branches that a jittered lattice of cell centres never takes -------------------------------------------------
+# Every condition that makes a case meaningful is asserted on the numpy side, so that a case which no longer reaches its
+# branch fails rather than passes.
+_tile = re.search(r"constexpr\s+int\s+kLatTile\s*=\s*(\d+)\s*;", open(os.path.join(
+    ROOT, "pathintegralgroundstate_amd", "csrc", "pigs_kernels.h")).read())
+assert _tile, "kLatTile is not in csrc/pigs_kernels.h"
+TILE = int(_tile.group(1))
+ROUND = 256                     # kLatThreads: the classification loop takes the sites in rounds of 256
+
+
+def _face_lattice(dim):
+    """8 x 8 or 4 x 4 x 4 sites ON the faces of a box of unequal sides: grid_sites' grid shifted by half a cell, so the
+    first row of every axis sits at -L_k/2; particles jittered by 0.3 of the smallest spacing and wrapped."""
+    n = 8 if dim == 2 else 4
+    cfg = _cfg(dim, 64, 1)
+    L = np.asarray(cfg.Lbox[:dim])
+    idx = np.stack(np.unravel_index(np.arange(n ** dim), (n,) * dim), axis=1).astype(np.float64)
+    R = idx * (L / n) - 0.5 * L
+    assert R.shape == (64, dim) and np.all(R.min(axis=0) == -0.5 * L) and np.all(R.max(axis=0) < 0.5 * L)
+    P = ln.jittered(R, 1, 3, 64, cfg.Lbox, np.random.default_rng(40 + dim), 0.3 * min(L) / n)
+    return cfg, R, P
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_winner_across_a_periodic_face(gpu_lib, dim):
+    """Sites on the box faces: a particle jittered below -L_k/2 is wrapped to the far side of the box, so its own site wins
+    only through the fold, and the winner's u is the folded difference.  Window 1, cm 0 and 1."""
+    cfg, R, P = _face_lattice(dim)
+    L = np.asarray(cfg.Lbox[:dim])
+    for a in range(3):
+        site, u = ln.assign(P[0, a], R, cfg.Lbox)
+        raw = P[0, a] - R[site]
+        assert np.array_equal(site, np.arange(64))
+        assert np.all((np.abs(raw) > 0.5 * L).sum(axis=0) >= 1), "no winner across a face on some axis"
+        assert np.all(np.abs(u) < 0.5 * L) and np.any(u != raw)
+    rmax = 0.35 * min(L) / (8 if dim == 2 else 4)
+    VT, WF = gpu_lib.build_tables(cfg)
+    with gpu_lib.PigsContext(cfg, VT, WF, n_walkers=1) as ctx:
+        ctx.upload_all(P)
+        for cm in (0, 1):
+            exp = ln.Window(P, 1, 1, cfg.Lbox, R, 8, rmax, cm).expected([0])
+            assert np.all(exp["nassigned"] == 64) and np.all(exp["occ"] == [0, 64, 0, 0]) and exp["nlost"].tolist() == [0]
+            ctx.lat_init(R, 8, rmax, 1, cm)
+            ctx.lat_accumulate()
+            _assert_same(ctx.lat_read(), exp, f"face dim {dim} cm {cm}")
+
+
+def _line_case(dim, nsite):
+    """Sites on a line along x, 0.25 apart (every difference, square and sum is exact), in a box of 256 x 16 (x 16) that
+    holds them without a fold.  One slice.  Particles ON sites 0, TILE-1, TILE, nsite-1 and 2 TILE-1 (the first and the last
+    column of a tile, on either side of a tile boundary), one at the exact midpoint of sites TILE-1 and TILE, three on
+    site ROUND+44 and four on site ROUND+144 -- whichever of these sites exist at this nsite."""
+    x = lambda s: np.array([0.25 * s - 64.0] + [0.0] * (dim - 1))
+    R = np.stack([x(s) for s in range(nsite)])
+    on = sorted({s for s in (0, TILE - 1, TILE, nsite - 1, 2 * TILE - 1) if 0 <= s < nsite})
+    X = [x(s) for s in on]
+    tie = TILE < nsite
+    if tie:
+        X.append(0.5 * (x(TILE - 1) + x(TILE)))
+    loads = {s: n for s, n in ((ROUND + 44, 3), (ROUND + 144, 4)) if s < nsite and s not in on}
+    for s, n in loads.items():
+        X += [x(s)] * n
+    X = np.stack(X)
+    Np = X.shape[0]
+    Lbox = [256.0, 16.0] if dim == 2 else [256.0, 16.0, 16.0]
+    cfg = SystemConfig(dim=dim, Np=Np, Nb=1, density=Np / float(np.prod(Lbox)), Lbox=Lbox)
+    P = np.broadcast_to(X, (1, 3, Np, dim)).copy()
+    return cfg, R, P, on, tie, loads
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+@pytest.mark.parametrize("dn", ["T-1", "T", "T+1", "2T+1"])
+def test_tile_boundary_of_the_site_loop(gpu_lib, dim, dn):
+    """nsite = kLatTile - 1, kLatTile, kLatTile + 1 and 2 kLatTile + 1: winners in the first and the last column of a tile;
+    a tie between the last site of one tile and the first of the next, where `best` must carry over with a strict `<`;
+    sites with three and with four particles in the classifier's second round.  cm = 0 and exact arithmetic: bit for bit."""
+    nsite = {"T-1": TILE - 1, "T": TILE, "T+1": TILE + 1, "2T+1": 2 * TILE + 1}[dn]
+    cfg, R, P, on, tie, loads = _line_case(dim, nsite)
+    X = P[0, 1]
+    site, u = ln.assign(X, R, cfg.Lbox)
+    assert site[:len(on)].tolist() == on and not np.any(u[:len(on)]) and {0, nsite - 1, min(TILE - 1, nsite - 1)} <= set(on)
+    if tie:
+        i = len(on)
+        d = ln.fold(X[i] - R[[TILE - 1, TILE]], cfg.Lbox)
+        r2 = ln.r2_of(d)
+        assert same_bits(r2[0], r2[1]) and r2[0] == 0.125 ** 2 and site[i] == TILE - 1 and u[i, 0] == 0.125
+    assert (nsite > TILE) == tie and (nsite == 2 * TILE + 1) == (len(loads) == 2)
+    exp = ln.Window(P, 1, 0, cfg.Lbox, R, 8, 1.0, 0).expected([0])
+    per = np.bincount(site, minlength=nsite)
+    if loads:                                                           # both flavours of "three or more", beyond site 255
+        assert min(loads) >= ROUND and sorted(per[per >= 3].tolist()) == [3, 4] and np.all(np.flatnonzero(per >= 3) >= ROUND)
+        assert exp["occ"][0, 0, 3] == 2 and per[2 * TILE - 1] == 1 and per[nsite - 1] == 1
+    assert exp["occ"][0, 0].tolist() == [int((per == q).sum()) for q in (0, 1, 2)] + [int((per >= 3).sum())]
+    got = _run(gpu_lib, cfg, P, R, 8, 1.0, 0, 0, [None])
+    _assert_same(got, exp, f"tile dim {dim} nsite {nsite}")
+    assert same_bits(got["mom"], exp["mom"])
+    assert got["mom"][0, 0, 0] == (0.125 ** 2 if tie else 0.0)
+
+
+@pytest.mark.parametrize("Np,nsite", [(1077, 5), (5, 1077)])
+def test_many_particles_on_few_sites_and_few_on_many(gpu_lib, Np, nsite):
+    """Np = 1077 on nsite = 5 (five rounds of particles, one short tile, every site holds 215 or more) and Np = 5 on
+    nsite = 1077 (five tiles and five rounds of the classifier, 1072 vacant sites), 3D, one slice."""
+    cfg = _cfg(3, Np, 1)
+    R = ln.grid_sites(3, 11, cfg.Lbox, nsite)
+    a = min(cfg.Lbox) / 11
+    P = ln.jittered(R, 1, 3, Np, cfg.Lbox, np.random.default_rng(Np), 0.2 * a)
+    exp = ln.Window(P, 1, 0, cfg.Lbox, R, 20, 0.4 * a, 1).expected([0])
+    assert exp["occ"][0, 0].tolist() == ([0, 0, 0, 5] if nsite == 5 else [1072, 5, 0, 0]) and exp["nassigned"][0, 0] == Np
+    got = _run(gpu_lib, cfg, P, R, 20, 0.4 * a, 0, 1, [None])
+    _assert_same(got, exp, f"Np {Np} nsite {nsite}")
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_occupancy_ladder(gpu_lib, dim):
+    """Ten particles on six sites with 0, 1, 2, 3, 4 and 0 particles: two vacant, one single, one double, two of class
+    "three or more"."""
+    cfg = _cfg(dim, 10, 1)
+    R, a = _lattice(cfg, 6)
+    home = np.array([1, 2, 2, 3, 3, 3, 4, 4, 4, 4])
+    L = np.asarray(cfg.Lbox[:dim])
+    P = R[home][None, None] + np.random.default_rng(6 + dim).uniform(-0.2 * a, 0.2 * a, (1, 3, 10, dim))
+    P = P - L * np.floor((P + 0.5 * L) / L)
+    exp = ln.Window(P, 1, 1, cfg.Lbox, R, 8, 0.4 * a, 1).expected([0])
+    assert np.all(exp["occ"][0] == [2, 1, 1, 2]) and np.all(exp["nassigned"] == 10)
+    got = _run(gpu_lib, cfg, P, R, 8, 0.4 * a, 1, 1, [None])
+    _assert_same(got, exp, f"ladder dim {dim}")
+    assert got["occ"][0].tolist() == [[2, 1, 1, 2]] * 3
+
+
+def _lost_base():
+    Np, Nb = 65, 2
+    cfg = _cfg(3, Np, Nb)
+    R, a = _lattice(cfg, Np)
+    return cfg, R, a, ln.jittered(R, 1, 2 * Nb + 1, Np, cfg.Lbox, np.random.default_rng(65), 0.1 * a)
+
+
+@pytest.mark.parametrize("how", ["nan", "inf"])
+def test_lost_particles_and_the_centre_of_mass(gpu_lib, how):
+    """cm = 1 with lost particles on the middle slice (one NaN coordinate; three particles with a +inf coordinate): the
+    centre of mass divides by the ASSIGNED particles.  Dividing by Np would move mom of that slice by far more than its
+    bound, which is asserted first."""
+    cfg, R, a, P = _lost_base()
+    Np, Nb = cfg.Np, cfg.Nb
+    if how == "nan":
+        P[0, Nb, 7, 1] = np.nan
+    else:
+        P[0, Nb, [3, 30, 64], [0, 2, 1]] = np.inf
+    nl = 1 if how == "nan" else 3
+    exp = ln.Window(P, Nb, Nb, cfg.Lbox, R, 8, 0.5 * a, 1).expected([0])
+    site, u = ln.assign(P[0, Nb], R, cfg.Lbox)
+    ok = site >= 0
+    tot = np.array([np.cumsum(np.concatenate(([0.0], u[:, k])))[-1] for k in range(3)])
+    m2 = lambda c: float(ln.r2_of((u - c)[ok]).sum())
+    assert int(ok.sum()) == Np - nl and same_bits(m2(tot / float(Np - nl)), exp["mom"][0, Nb, 0])
+    assert abs(m2(tot / float(Np)) - m2(tot / float(Np - nl))) > 1e3 * 1e-12 * exp["mom"][0, Nb, 0]
+    got = _run(gpu_lib, cfg, P, R, 8, 0.5 * a, Nb, 1, [None])
+    _assert_same(got, exp, f"lost ({how}) with cm")
+    assert got["nlost"].tolist() == [nl] and got["nassigned"][0].tolist() == [Np, Np, Np - nl, Np, Np]
+    assert got["occ"][0, Nb].tolist() == [nl, Np - nl, 0, 0]
+
+
+def test_a_slice_with_every_particle_lost(gpu_lib):
+    """Every particle of the middle slice has a NaN coordinate: nothing is assigned there, the division of the centre of
+    mass is not taken, mom of the slice stays exactly 0.0 and every site is vacant; the other slices keep the bits of the
+    clean run."""
+    cfg, R, a, P = _lost_base()
+    Np, Nb = cfg.Np, cfg.Nb
+    clean = _run(gpu_lib, cfg, P, R, 8, 0.5 * a, Nb, 1, [None])
+    P[0, Nb, :, 2] = np.nan
+    exp = ln.Window(P, Nb, Nb, cfg.Lbox, R, 8, 0.5 * a, 1).expected([0])
+    assert exp["nassigned"][0].tolist() == [Np, Np, 0, Np, Np] and not np.any(exp["mom"][0, Nb])
+    got = _run(gpu_lib, cfg, P, R, 8, 0.5 * a, Nb, 1, [None])
+    _assert_same(got, exp, "a slice lost")
+    others = [0, 1, 3, 4]
+    assert got["nassigned"][0, Nb] == 0 and got["nlost"].tolist() == [Np] and got["occ"][0, Nb].tolist() == [Np, 0, 0, 0]
+    assert same_bits(got["mom"][0, Nb], np.zeros(5)) and same_bits(got["mom"][0, others], clean["mom"][0, others])
+    assert np.array_equal(got["occ"][0, others], clean["occ"][0, others]) and got["hop1"].tolist() == [0]
+    assert np.array_equal(got["nassigned"][0, others], clean["nassigned"][0, others]) and got["hopw"].tolist() == [0]
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+@pytest.mark.parametrize("where", ["-rmax", "below -rmax", "+rmax", "below +rmax"])
+def test_axis_histogram_edges(gpu_lib, dim, where):
+    """v_x of particle 0 at the two ends of [-rmax, rmax), rmax = 0.5 in 2 x 4 bins of 0.125 (the division is exact):
+    -rmax is t = 0.0, the first bin; one ulp below it is out; +rmax is t = 2 nbin, out; one ulp below +rmax is wherever
+    (v + rmax) / rbin rounds to in double, which is written out here.  Site 0 sits at x = -0.25, so that x - R is exact."""
+    rmax, nbin = 0.5, 4
+    v = {"-rmax": -rmax, "below -rmax": np.nextafter(-rmax, -1.0), "+rmax": rmax, "below +rmax": np.nextafter(rmax, 0.0)}[where]
+    x = np.zeros(dim)
+    x[0] = -0.25 + v
+    cfg, R, P = _one_moving(dim, x, nbin, rmax, x0=-0.25)
+    site, u = ln.assign(P[0, 1], R, cfg.Lbox)
+    assert site.tolist() == [0, 1, 2] and same_bits(u[0, 0], v) and not np.any(u[1:]) and not np.any(u[0, 1:])
+    t = (float(v) + rmax) / (rmax / float(nbin))
+    inside = 0.0 <= t < float(2 * nbin)
+    assert inside == {"-rmax": True, "below -rmax": False, "+rmax": False}.get(where, inside)
+    assert where != "-rmax" or t == 0.0
+    exp = ln.Window(P, 1, 0, cfg.Lbox, R, nbin, rmax, 0).expected([0])
+    want = np.zeros(2 * nbin, np.int64)
+    want[nbin] = 2                                                      # particles 1 and 2: v = 0
+    if inside:
+        want[int(t)] += 1
+    assert exp["hx"][0, 0].tolist() == want.tolist() and np.all(exp["hx"][0, 1:, nbin] == 3)
+    got = _run(gpu_lib, cfg, P, R, nbin, rmax, 0, 0, [None])
+    _assert_same(got, exp, f"axis edge {where} dim {dim}")
+    assert same_bits(got["mom"], exp["mom"]) and got["hx"][0, 0].tolist() == want.tolist()
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_hop_patterns(gpu_lib, dim):
+    """Five slices.  Particle 5 goes A B A A A: two link hops, none across the window.  Particle 20 goes A A lost B B: no
+    link hop (a lost end drops the comparison), one across the window.  Particle 40 is lost on the first slice, sits on A
+    on the second and on C from the third on: one link hop, none across the window."""
+    Np, Nb = 65, 2
+    cfg = _cfg(dim, Np, Nb)
+    R, a = _lattice(cfg, Np)
+    P = ln.jittered(R, 1, 5, Np, cfg.Lbox, np.random.default_rng(50 + dim), 0.1 * a)
+    quiet = ln.Window(P, Nb, Nb, cfg.Lbox, R, 8, 0.5 * a, 1).expected([0])
+    assert quiet["hop1"].tolist() == [0] and quiet["hopw"].tolist() == [0]
+    P[0, 1, 5] = P[0, 1, 6]
+    P[0, 2, 20, 0] = np.nan
+    P[0, 3:, 20] = P[0, 3:, 21]
+    P[0, 0, 40, dim - 1] = np.nan
+    P[0, 2:, 40] = P[0, 2:, 41]
+    w = ln.Window(P, Nb, Nb, cfg.Lbox, R, 8, 0.5 * a, 1)
+    exp = w.expected([0])
+    S = np.stack([ln.assign(P[0, s], R, cfg.Lbox)[0] for s in range(5)])
+    assert S[:, 5].tolist() == [5, 6, 5, 5, 5] and S[:, 20].tolist() == [20, 20, -1, 21, 21] and S[:, 40].tolist() == [-1, 40, 41, 41, 41]
+    assert exp["hop1"].tolist() == [3] and exp["hopw"].tolist() == [1] and exp["nlost"].tolist() == [2]
+    got = _run(gpu_lib, cfg, P, R, 8, 0.5 * a, Nb, 1, [None])
+    _assert_same(got, exp, f"hops dim {dim}")
+    assert got["hop1"].tolist() == [2 + 0 + 1] and got["hopw"].tolist() == [0 + 1 + 0]
 
 
 # ---- 3. lists, launches, resets, neighbours ------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Pins tests/lat_numpy.py, the restatement that tests/test_gpu_lat.py holds the device to, on the CPU: against a literal
-triple loop and against configurations whose sums are known in closed form."""
+triple loop and against configurations whose sums are known in closed form.  Also pins block_stats_numpy.norm_lat, the
+independent statement of the family's normalisation, to figures divided by hand, and holds profiles.normalize_lat to it."""
 import numpy as np
 import pytest
 
@@ -171,3 +172,70 @@ def test_site_density_integrates_to_the_occupation():
     shell = 4 * np.pi / 3 * np.diff(edges ** 3)
     assert np.allclose((n["rho_site"] * shell).sum(axis=-1), 1.0) and np.allclose(n["pu"].sum(axis=-1) * 0.1, 1.0)
     assert np.allclose(n["uk2"].sum(axis=-1), n["u2"]) and n["x"][0] == pytest.approx(-0.95) and n["r"][-1] == pytest.approx(0.95)
+
+
+# ---- the independent normalisation, block_stats_numpy.norm_lat -----------------------------------------------------------
+def _both(raw, Np, nsite, a_nn, rmax):
+    """norm_lat and profiles.normalize_lat on the same sums."""
+    import block_stats_numpy as bs
+    with np.errstate(all="ignore"):
+        return bs.norm_lat_raw(raw, Np, nsite, a_nn, rmax), normalize_lat(raw, Np, nsite, a_nn, rmax)
+
+
+def test_norm_lat_one_slice_2d_by_hand():
+    """One sample of one slice in 2D, four particles on five sites (two vacant, one doubly occupied), rmax = 2 in two bins:
+    shell areas pi and 3 pi.  Every figure divides by hand; the site fractions divide by the SITES (2/5, 1/5), not by the
+    particles (2/4, 1/4); one slice has no link."""
+    raw = {"mom": np.array([[8.0, 32.0, 4.0, 4.0]]), "nassigned": np.array([4]), "nlost": 0, "occ": np.array([[2, 2, 1, 0]]),
+           "hr": np.array([1, 3]), "hx": np.array([[4, 0, 0, 0], [0, 2, 1, 0]]), "hop1": 0, "hopw": 0, "samples": 1}
+    for n in _both(raw, 4, 5, 2.0, 2.0):
+        assert n["u2"].tolist() == [2.0] and n["uk2"].tolist() == [[1.0, 1.0]] and n["u2_mean"] == 2.0
+        assert n["gamma_tau"].tolist() == [2.0 ** 0.5 / 2.0] and n["gamma"] == 2.0 ** 0.5 / 2.0
+        assert n["alpha2"] == 2 * 8.0 / (4 * 4.0) - 1 == 0.0
+        assert n["vacant"] == pytest.approx(0.4, rel=1e-15) and n["multiple"] == pytest.approx(0.2, rel=1e-15)
+        assert n["hops_link"] == 0.0 and n["hops_window"] == 0.0
+        assert np.allclose(n["rho_site"], [1 / (5 * np.pi), 3 / (5 * 3 * np.pi)], rtol=1e-15, atol=0)
+        assert n["pu"].tolist() == [[1.0, 0.0, 0.0, 0.0], [0.0, 0.5, 0.25, 0.0]]
+
+
+def test_norm_lat_three_slices_3d_by_hand():
+    """Two samples of three slices in 3D, Np = 4 on nsite = 3, four particles lost on the last slice: the window's means
+    weigh the slices by their assigned particles, the hops divide by the PARTICLES (8 / (2 4 2), not 8 / (2 3 2)), the
+    shells are 4 pi / 3 (1, 7)."""
+    raw = {"mom": np.array([[16.0, 40.0, 8.0, 4.0, 4.0], [8.0, 20.0, 4.0, 2.0, 2.0], [4.0, 10.0, 2.0, 1.0, 1.0]]),
+           "nassigned": np.array([8, 8, 4]), "nlost": 4, "occ": np.array([[2, 3, 1, 0], [3, 2, 0, 1], [4, 1, 1, 0]]),
+           "hr": np.array([18, 126]), "hx": np.array([[20, 0, 0, 0], [0, 10, 5, 0], [0, 0, 0, 40]]), "hop1": 8, "hopw": 2,
+           "samples": 2}
+    v = 4.0 * np.pi / 3.0
+    for n in _both(raw, 4, 3, 0.5, 2.0):
+        assert n["u2"].tolist() == [2.0, 1.0, 1.0] and n["uk2"].tolist() == [[1.0, 0.5, 0.5], [0.5, 0.25, 0.25], [0.5, 0.25, 0.25]]
+        assert n["gamma_tau"].tolist() == [2.0 ** 0.5 / 0.5, 2.0, 2.0]
+        assert n["u2_mean"] == pytest.approx(1.4, rel=1e-15) and n["gamma"] == pytest.approx(1.4 ** 0.5 / 0.5, rel=1e-15)
+        assert n["alpha2"] == pytest.approx(3 * 3.5 / (5 * 1.96) - 1.0, rel=1e-14)
+        assert n["vacant"] == 9.0 / 18.0 and n["multiple"] == pytest.approx(3.0 / 18.0, rel=1e-15)
+        assert n["hops_link"] == 0.5 and n["hops_window"] == 0.25
+        assert np.allclose(n["rho_site"], [18 / (18 * v), 126 / (18 * 7 * v)], rtol=1e-15, atol=0)
+        assert n["pu"].tolist() == [[1.0, 0.0, 0.0, 0.0], [0.0, 0.5, 0.25, 0.0], [0.0, 0.0, 0.0, 2.0]]
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+@pytest.mark.parametrize("ns", [1, 5])
+def test_normalize_lat_equals_norm_lat_on_random_sums(dim, ns):
+    """profiles.normalize_lat against the helper on random sums of [W, Nblock] walkers and blocks, nsite != Np, every output."""
+    import block_stats_numpy as bs
+    rng = np.random.default_rng(10 * dim + ns)
+    lead, nbin, Np, nsite = (3, 4), 7, 11, 13
+    raw = {"mom": rng.uniform(0.5, 9.0, lead + (ns, 2 + dim)), "nassigned": rng.integers(1, 60, lead + (ns,)),
+           "nlost": rng.integers(0, 5, lead), "occ": rng.integers(0, 50, lead + (ns, 4)), "hr": rng.integers(0, 90, lead + (nbin,)),
+           "hx": rng.integers(0, 90, lead + (dim, 2 * nbin)), "hop1": rng.integers(0, 30, lead), "hopw": rng.integers(0, 30, lead),
+           "samples": rng.integers(1, 6, lead)}
+    mine, theirs = _both(raw, Np, nsite, 1.7, 0.9)
+    for k in bs.LAT_OUT:
+        assert np.shape(theirs[k]) == mine[k].shape and np.all(np.isfinite(mine[k])), k
+        assert np.allclose(theirs[k], mine[k], rtol=1e-13, atol=0), k
+        assert np.any(mine[k] != 0) or (k == "hops_link" and ns == 1), k
+    # one walker's slice of the dict, as the docstring of normalize_lat allows
+    one = {k: v[1, 2] for k, v in raw.items()}
+    mine1, theirs1 = _both(one, Np, nsite, 1.7, 0.9)
+    for k in bs.LAT_OUT:
+        assert np.allclose(theirs1[k], mine[k][1, 2], rtol=1e-13, atol=0) and np.array_equal(mine1[k], mine[k][1, 2]), k
