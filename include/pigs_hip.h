@@ -98,7 +98,9 @@ int pigs_stream(pigs_ctx *ctx, void **hip_stream);
  *      next to the other contexts' sweep kernels -- set "cm_split" so that H x walkers + the others' walkers <= CUs
  *      (two contexts of 64 walkers on 256 CUs: 3).  The shards then run staggered: one's TranslateChain on the CUs the
  *      other's bisection phase leaves idle.
- *   "cm_fault": TEST ONLY -- forces the time-out of that exchange once. */
+ *   "cm_fault": TEST ONLY -- forces the time-out of that exchange once.
+ *   "sf_scratch_mib": the MiB that the unfolded paths of one pigs_sf_accumulate launch may take (1..2048, default 256);
+ *      the next pigs_sf_init reads it. */
 int pigs_set_tuning(pigs_ctx *ctx, const char *key, int32_t value);
 /* Device self-test: the kernels' short exact division / sqrt forms against IEEE `/` and sqrt()
  * on blocks*256*iters random operands; bad[0..3] = mismatch counts (sqrt, n/r, r/dr, n/dr). */
@@ -761,6 +763,76 @@ int pigs_lat_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * before pigs_lat_init. */
 int pigs_lat_read(pigs_ctx *ctx, double *mom, int64_t *nassigned, int64_t *nlost, int64_t *occ, int64_t *hr, int64_t *hx,
                   int64_t *hop1, int64_t *hopw, int64_t *samples, const int32_t *reset);
+
+/* ---- the superfluid fraction from the diffusion of the centre of mass along imaginary time, and the unfolded
+ * displacement of a particle, of a PERIODIC system (new: every family above is either blind to a wrap -- phasors at box
+ * vectors -- or folds a displacement once; this one follows a worldline link by link) ---------------------------------
+ * A ground-state path has no winding number.  The estimator used at T = 0 (Zhang, Kawashima, Carlson and Gubernatis 1995;
+ * the one diffusion Monte Carlo uses) is
+ *   rho_s,k / rho = lim_{tau -> inf} < ( sum_i [x_k(i, tau0 + tau) - x_k(i, tau0)] )^2 > / (2 lambda Np tau),  per box axis k
+ * with lambda = hbar^2/2m and the displacement of every particle followed UNFOLDED through the periodic box.
+ * Scope.  Periodic contexts with dim = 1, 2 or 3.  A trapped context gets PIGS_ERR_UNSUPPORTED.
+ * Window and lags.  These are the rules of pigs_fqs_*:
+ *   window slices a0 = Nb-window .. a1 = Nb+window, ns = 2 window + 1;
+ *   links a = a0 .. a1-1;
+ *   lags l = 0 .. Ntau with 0 <= Ntau <= 2 window;
+ *   n_pairs(l) = ns - l.
+ * For a listed walker w:
+ * 1. Link vector.
+ *    d_k(i,a) = x_k(i,a+1) - x_k(i,a), folded once by min_image<DIM>.  That is the two compares, each against LboxHalf,
+ *    with nothing fused.
+ *    nwrap[w] += the number of (i, a, k) on which a compare fired: raw d_k > LboxHalf[k] or < -LboxHalf[k].
+ *    THE FOLD GIVES THE TRUE LINK ONLY WHILE THE LINK IS SHORTER THAN Lbox[k]/2.  This holds for any sampled path, since a
+ *    link is about sqrt(dt).  The library does not judge it.
+ * 2. Unfolded particle path.  U_k(i,a0) = 0.0 and U_k(i,a+1) = U_k(i,a) + d_k(i,a), one addition after the other.  numpy's
+ *    cumsum has these bits.
+ * 3. Centre of mass.
+ *    The link sum is s_k(a) = sum_i d_k(i,a) in the lattice family's order: 256 lanes, lane j takes particles j, j+256, ..
+ *    ascending from 0.0, then wave_sum (partner lane ^32, 16, .., 1), then the waves in wave order from 0.0.
+ *    W_k(a0) = 0.0 and W_k(a+1) = W_k(a) + s_k(a).
+ *    W is Np times the unfolded centre of mass.
+ *    This order is restatable bit for bit in numpy: pad to 256 with +0.0, add the strided rows, then apply
+ *    v = v + v[idx ^ m] per wave for each m.  tests/sf_numpy.py restates it that way.
+ * 4. Sums of one call.
+ *    C[w][l][k] += one running sum from 0.0 over a = a0 .. a1-l ascending of delta*delta, with
+ *    delta = W_k(a+l) - W_k(a).  Given the orders above, C of a single call has the restatement's bits.
+ *    D[w][l][k] += sum over i and a of delta_i*delta_i, with delta_i = U_k(i,a+l) - U_k(i,a).  The order is that of
+ *    pigs_fqs_*'s D:
+ *      lane j takes particles j, j+256, .. ascending;
+ *      per particle, a ascending;
+ *      then butterfly, then waves in wave order from 0.0;
+ *      then acc += value by the one thread that owns (w, l, k) in the launch.
+ *    Lag 0 adds exactly 0.0 to both.
+ *    samples[w] += 1.
+ * Determinism.  No floating-point atomics.  The same worldline gives the same bits whatever the walker list, its order,
+ * the launch split or the number of walkers of the context.  A walker listed twice counts twice, in two launches.
+ * Caller's divisions.  profiles.normalize_sf(got, Np, dt, lam=0.5) returns:
+ *   tau_l = l dt;
+ *   Dcm[l][k] = C/(samples n_pairs Np);
+ *   rhos[l][k] = Dcm/(2 lam tau_l), NaN at l = 0, and its mean over the axes;
+ *   msd[l][k] = D/(samples n_pairs Np);
+ *   cross = Dcm - msd.
+ * lam = 1/2 is the run's own unit: the spring term of ThermEnergy is 1/2 |dr|^2/dt^2, so a free link has variance dt per
+ * axis.  profiles.superfluid_fraction(tau, Dcm_k, tmin) is the least-squares slope of Dcm over tau >= tmin, divided by
+ * 2 lam, with the fit's own standard error.
+ * (The lanes are 256 whatever Np, so with Np < 256 the idle lanes add +0.0: unlike pigs_fqs_*'s D, whose lanes follow Np.)
+ * Scratch.  The unfolded paths of one launch, 8 (2 window + 1) dim NpPad bytes per walker, sit in device memory between
+ * the two kernels of a launch.  pigs_sf_init allocates min(n_walkers, 256, what fits 256 MiB) walkers of it, one at the
+ * least, and pigs_sf_accumulate puts no more walkers into a launch; pigs_set_tuning "sf_scratch_mib" (1..2048, read by the
+ * next pigs_sf_init) sets another budget.  The bits do not depend on it.
+ *
+ * pigs_sf_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context;
+ * PIGS_ERR_ARG for window < 0, window > Nb, Ntau < 0, Ntau > 2 window, more than 3072 lags, or accumulators beyond 2 GiB. */
+int pigs_sf_init(pigs_ctx *ctx, int32_t Ntau, int32_t window);
+/* Adds the window of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's stream,
+ * no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next step's.
+ * The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_sf_init, for n < 0 or for a walker out of range. */
+int pigs_sf_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' C[n_walkers][Ntau+1][dim] and D[n_walkers][Ntau+1][dim] (doubles), nwrap[n_walkers] and samples[n_walkers]
+ * (int64); then zeroes those of the walkers w with reset[w] != 0 (reset == NULL: none).  Synchronises the context.
+ * PIGS_ERR_ARG before pigs_sf_init. */
+int pigs_sf_read(pigs_ctx *ctx, double *C, double *D, int64_t *nwrap, int64_t *samples, const int32_t *reset);
 
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "pigs_atm_init", "pigs_atm_accumulate", "pigs_atm_read",
     "pigs_nk_init", "pigs_nk_count", "pigs_nk_vectors", "pigs_nk_accumulate", "pigs_nk_add", "pigs_nk_read",
     "pigs_lat_init", "pigs_lat_accumulate", "pigs_lat_read",
+    "pigs_sf_init", "pigs_sf_accumulate", "pigs_sf_read",
 ]
 
 
@@ -184,6 +185,9 @@ def load_library(path=LIB_PATH):
     L.pigs_lat_init.argtypes = [vp, C.c_int32, _dp, C.c_int32, C.c_double, C.c_int32, C.c_int32]
     L.pigs_lat_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_lat_read.argtypes = [vp, _dp, _lp, _lp, _lp, _lp, _lp, _lp, _lp, _lp, _ip]
+    L.pigs_sf_init.argtypes = [vp, C.c_int32, C.c_int32]
+    L.pigs_sf_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_sf_read.argtypes = [vp, _dp, _dp, _lp, _lp, _ip]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -897,6 +901,35 @@ class PigsContext:
         mask = self._reset_mask(reset)
         _chk(self.L, self.L.pigs_lat_read(self.h, _d(out["mom"]), *(_l(out[k]) for k in (
             "nassigned", "nlost", "occ", "hr", "hx", "hop1", "hopw", "samples")), mask), "pigs_lat_read")
+        return out
+
+    # ---- the superfluid fraction from the centre-of-mass diffusion along tau (pigs_sf_*: raw sums per walker, lag and axis)
+    def sf_init(self, Ntau=0, window=0):
+        """Allocate and zero the sums of the squared unfolded displacement of the centre of mass (times Np) and of a
+        particle over the lags l = 0..Ntau (0 <= Ntau <= 2 window), over the slices Nb-window..Nb+window of a periodic
+        system.  Calling it again resizes and zeroes."""
+        _chk(self.L, self.L.pigs_sf_init(self.h, int(Ntau), int(window)), "pigs_sf_init")
+        self._sf = (int(Ntau) + 1, int(window))
+
+    def sf_accumulate(self, walkers=None):
+        """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_sf_accumulate", walkers)
+
+    def sf_read(self, reset=None):
+        """dict of the raw sums: C and D [W, Ntau+1, dim] (float64: the squared displacement over lag l of Np times the
+        unfolded centre of mass, and of the unfolded particles), nwrap [W] (int64: the link components that were folded)
+        and samples [W] (int64); and "window", the window they were taken over, which profiles.normalize_sf divides by.
+        reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        if getattr(self, "_sf", None) is None:
+            raise PigsError("sf_read: sf_init first")
+        nl, window = self._sf
+        W, dim = self.n_walkers, self.cfg.dim
+        out = {"C": np.zeros((W, nl, dim)), "D": np.zeros((W, nl, dim)), "nwrap": np.zeros(W, np.int64),
+               "samples": np.zeros(W, np.int64)}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_sf_read(self.h, _d(out["C"]), _d(out["D"]), _l(out["nwrap"]), _l(out["samples"]), mask),
+             "pigs_sf_read")
+        out["window"] = window
         return out
 
     # ---- K5

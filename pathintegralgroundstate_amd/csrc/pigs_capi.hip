@@ -292,6 +292,14 @@ struct pigs_ctx {
     bool        lat_ready = false;          // pigs_lat_init called
     int         lat_nsite = 0, lat_nspad = 0, lat_nbin = 0, lat_window = 0, lat_cm = 0;
     double      lat_rmax = 0.0;
+    // centre-of-mass diffusion along tau (pigs_sf_*): per walker C and D [Ntau + 1][dim], nwrap and samples; the unfolded
+    // coordinates of one launch, U [sf_slots][2 window + 1][dim][NpPad], and its centre of mass Wcm [sf_slots][2 window + 1][dim]
+    DevBuf<double> d_sf_C, d_sf_D, d_sf_U, d_sf_W;
+    DevBuf<unsigned long long> d_sf_nwrap, d_sf_samples;
+    bool        sf_ready = false;           // pigs_sf_init called
+    int         sf_ntau = 0, sf_window = 0;
+    int         sf_slots = 0;               // walkers per launch: what the scratch holds
+    int         sf_scratch_mib = kSfScratchMiB;   // pigs_set_tuning "sf_scratch_mib": the budget of U at the next pigs_sf_init
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -518,6 +526,11 @@ int pigs_set_tuning(pigs_ctx *c, const char *key, int32_t value)
     if (!strcmp(key, "grv_form")) {             // vector grid of pigs_grv_accumulate: -1 automatic, 0 global atomics, 1 privatised in LDS
         if (value < -1 || value > 1) return fail(PIGS_ERR_ARG, "grv_form=%d", value);
         c->grv_form = value;
+        return PIGS_OK;
+    }
+    if (!strcmp(key, "sf_scratch_mib")) {       // MiB the unfolded paths of one pigs_sf_accumulate launch may take; read by pigs_sf_init
+        if (value < 1 || value > 2048) return fail(PIGS_ERR_ARG, "sf_scratch_mib=%d", value);
+        c->sf_scratch_mib = value;
         return PIGS_OK;
     }
     if (!strcmp(key, "sweep_threads")) {
@@ -2325,6 +2338,61 @@ int pigs_lat_read(pigs_ctx *c, double *mom, int64_t *nassigned, int64_t *nlost, 
     return read_and_reset(c, {{c->d_lat_mom.p, ns * (2 + dim), mom}, {c->d_lat_nass.p, ns, nassigned}, {c->d_lat_nlost.p, 1, nlost},
                               {c->d_lat_occ.p, ns * 4, occ}, {c->d_lat_hr.p, nb, hr}, {c->d_lat_hx.p, dim * 2 * nb, hx},
                               {c->d_lat_hop1.p, 1, hop1}, {c->d_lat_hopw.p, 1, hopw}, {c->d_lat_samples.p, 1, samples}}, reset);
+}
+
+// ---- the superfluid fraction: centre-of-mass diffusion along tau and the unfolded displacement --------------------
+// Raw sums per walker, lag and axis (pigs_sf.hip), accumulated on the device and read per block.  The unfolded paths of a
+// launch sit in a scratch whose size pigs_sf_init bounds; the launches are cut to the walkers it holds.
+int pigs_sf_init(pigs_ctx *c, int32_t Ntau, int32_t window)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "the centre-of-mass diffusion is defined for periodic systems only (a link is unfolded through the box)");
+    if (window < 0 || window > c->P.Nb || Ntau < 0 || Ntau > 2 * window || Ntau + 1 > kSfLagsMax)
+        return fail(PIGS_ERR_ARG, "pigs_sf_init: Ntau=%d (0..2 window, %d lags at most) window=%d (0..Nb=%d)", Ntau, kSfLagsMax,
+                    window, c->P.Nb);
+    const size_t W = (size_t)c->n_walkers, per = (size_t)(Ntau + 1) * (size_t)c->P.dim, ns = 2 * (size_t)window + 1;
+    if ((double)W * (2.0 * (double)per + 2.0) * 8.0 > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_sf_init: %zu walkers x (2 x %d x %d + 2) sums pass 2 GiB", W, Ntau + 1, c->P.dim);
+    const size_t slot = sf_slot_doubles(c->P.dim, c->P.NpPad, window);
+    const size_t fit = ((size_t)c->sf_scratch_mib << 20) / (slot * sizeof(double));
+    const size_t slots = std::max<size_t>(1, std::min({W, (size_t)kWalkerListMax, fit}));
+    rc = init_begin(c, c->sf_ready); if (rc) return rc;
+    HIPCHK(alloc_zeroed(c, c->d_sf_C, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_sf_D, W * per));
+    HIPCHK(alloc_zeroed(c, c->d_sf_nwrap, W));
+    HIPCHK(alloc_zeroed(c, c->d_sf_samples, W));
+    HIPCHK(alloc_zeroed(c, c->d_sf_U, slots * slot));
+    HIPCHK(alloc_zeroed(c, c->d_sf_W, slots * ns * (size_t)c->P.dim));
+    SYNC_CHECKED(c);
+    c->sf_ntau = Ntau; c->sf_window = window; c->sf_slots = (int)slots;
+    c->sf_ready = true;
+    return PIGS_OK;
+}
+
+int pigs_sf_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    rc = check_cm(c); if (rc) return rc;
+    if (!c->sf_ready) return fail(PIGS_ERR_ARG, "pigs_sf_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    rc = walker_list(c, n, walkers, sw); if (rc) return rc;
+    // one thread owns an accumulator element per launch; a launch's walkers fit the scratch
+    return each_launch(c, sw, walkers, true, c->sf_slots, "launch_sf", [&](int m, const WalkerList &L) {
+        return launch_sf(c->P, c->d_paths.p, m, L, c->sf_window, c->sf_ntau, c->d_sf_U.p, c->d_sf_W.p, c->d_sf_C.p, c->d_sf_D.p,
+                         c->d_sf_nwrap.p, c->d_sf_samples.p, c->stream);
+    });
+}
+
+int pigs_sf_read(pigs_ctx *c, double *C, double *D, int64_t *nwrap, int64_t *samples, const int32_t *reset)
+{
+    int rc = check_ctx(c); if (rc) return rc;
+    if (!c->sf_ready) return fail(PIGS_ERR_ARG, "pigs_sf_init first");
+    if (!C || !D || !nwrap || !samples) return fail(PIGS_ERR_ARG, "null output");
+    const size_t per = (size_t)(c->sf_ntau + 1) * (size_t)c->P.dim;
+    return read_and_reset(c, {{c->d_sf_C.p, per, C}, {c->d_sf_D.p, per, D}, {c->d_sf_nwrap.p, 1, nwrap},
+                              {c->d_sf_samples.p, 1, samples}}, reset);
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

@@ -234,6 +234,21 @@ hipError_t launch_lat(const DevParams &P, const double *paths, int n, const Walk
                       unsigned long long *hr, unsigned long long *hx, unsigned long long *hop1, unsigned long long *hopw,
                       unsigned long long *samples, int *sidx, hipStream_t st);
 
+// pigs_sf.hip: the diffusion of the centre of mass along imaginary time and the unfolded displacement of a particle
+// (pigs_sf_accumulate).  k_sf_links, one workgroup per listed walker, folds every link of the window once, adds the
+// folded links up and leaves the unfolded coordinates in the scratch U [slot][2 window + 1][dim][NpPad] and the unfolded
+// centre of mass (times Np) in Wcm [slot][2 window + 1][dim]; k_sf_lags, one workgroup per (listed walker, lag), reads
+// both.  One thread owns an element (w, l, k) per launch: a walker must not be listed twice in ONE launch.  A slot of U
+// takes sf_slot_doubles doubles; pigs_sf_init sizes the scratch (at most kSfScratchMiB MiB by default, one slot at the
+// least) and pigs_sf_accumulate cuts its launches to the slots there are.  Static LDS only.
+constexpr int kSfThreads = 256;
+constexpr int kSfScratchMiB = 256;
+constexpr int kSfLagsMax = 3072;
+size_t sf_slot_doubles(int dim, int NpPad, int window);
+hipError_t launch_sf(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int Ntau, double *U,
+                     double *Wcm, double *C, double *D, unsigned long long *nwrap, unsigned long long *samples,
+                     hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

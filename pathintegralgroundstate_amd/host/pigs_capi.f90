@@ -689,6 +689,24 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_lat_read_t
+
+     ! the superfluid fraction from the centre-of-mass diffusion along tau (include/pigs_hip.h, pigs_sf_*): looked up at
+     ! run time, see sf_bind; _accumulate has the signature of pigs_grv_accumulate
+     function pigs_sf_init_t(ctx,Ntau,window) bind(C) result(st)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value         :: ctx
+       integer(c_int32_t), value  :: Ntau,window
+       integer(c_int) :: st
+     end function pigs_sf_init_t
+
+     function pigs_sf_read_t(ctx,C,D,nwrap,samples,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       real(c_double)                 :: C(*),D(*)     ! (dim,0:Ntau,n_walkers)
+       integer(c_int64_t)             :: nwrap(*),samples(*)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_sf_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -764,6 +782,11 @@ module pigs_capi
   procedure(pigs_lat_init_t), pointer       :: lat_init => null()
   procedure(pigs_grv_accumulate_t), pointer :: lat_accumulate => null()
   procedure(pigs_lat_read_t), pointer       :: lat_read => null()
+
+  ! bound by sf_bind (null until then)
+  procedure(pigs_sf_init_t), pointer        :: sf_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: sf_accumulate => null()
+  procedure(pigs_sf_read_t), pointer        :: sf_read => null()
 
 contains
 
@@ -937,6 +960,16 @@ contains
     call c_f_procpointer(f(2),lat_accumulate)
     call c_f_procpointer(f(3),lat_read)
   end function lat_bind
+
+  ! The centre-of-mass diffusion entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function sf_bind()
+    type(c_funptr) :: f(3)
+    sf_bind = resolve_all('pigs_sf',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. sf_bind) return
+    call c_f_procpointer(f(1),sf_init)
+    call c_f_procpointer(f(2),sf_accumulate)
+    call c_f_procpointer(f(3),sf_read)
+  end function sf_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

@@ -23,6 +23,7 @@ module pigs_estimators
   public :: normalize_g3, write_g3, write_g3ang
   public :: normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau
   public :: normalize_lat, lat_nn_distance, lind_header, write_lind_block, write_lindtau, write_usite
+  public :: normalize_sf, sf_columns, write_rhos, write_msdu
   public :: normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec
 
   type est_params
@@ -986,6 +987,76 @@ contains
     end do
     close (u)
   end subroutine write_usite
+
+  ! ---- the superfluid fraction from the centre-of-mass diffusion along tau (raw sums C, D of pigs_sf_read of one walker
+  ! and block, S samples) -> the block values per lag l = 0..Ntau, sf_columns(dim) = 4 dim + 2 of them:
+  !   B(1:dim,l)           Dcm_k  = C/(S n_pairs(l) Np)            n_pairs(l) = 2 window + 1 - l
+  !   B(dim+1:2dim,l)      rhos_k = Dcm_k/(2 lam l dt), 0 at l = 0 (rhos_vpi.out has no line for it)
+  !   B(2dim+1,l)          the mean of rhos_k over the axes
+  !   B(2dim+2:3dim+1,l)   msd_k  = D/(S n_pairs(l) Np)
+  !   B(3dim+2,l)          the sum of msd_k over the axes
+  !   B(3dim+3:4dim+2,l)   cross_k = Dcm_k - msd_k
+  ! (profiles.normalize_sf has the same expressions)
+  integer function sf_columns(dim)
+    integer, intent(in) :: dim
+    sf_columns = 4*dim+2
+  end function sf_columns
+
+  subroutine normalize_sf(dim,Np,Ntau,window,dt,lam,S,C,D,B)
+    integer, intent(in)    :: dim,Np,Ntau,window
+    real(8), intent(in)    :: dt,lam,C(dim,0:Ntau),D(dim,0:Ntau)
+    integer(8), intent(in) :: S
+    real(8), intent(out)   :: B(4*dim+2,0:Ntau)
+    integer :: l,k
+    real(8) :: norm,tau
+    do l=0,Ntau
+       norm = real(S,8)*real(2*window+1-l,8)*real(Np,8)
+       tau  = real(l,8)*dt
+       do k=1,dim
+          B(k,l) = C(k,l)/norm
+          B(dim+k,l) = 0.d0
+          if (l>0) B(dim+k,l) = B(k,l)/(2.d0*lam*tau)
+          B(2*dim+1+k,l) = D(k,l)/norm
+          B(3*dim+2+k,l) = B(k,l)-B(2*dim+1+k,l)
+       end do
+       B(2*dim+1,l) = sum(B(dim+1:2*dim,l))/real(dim,8)
+       B(3*dim+2,l) = sum(B(2*dim+2:3*dim+1,l))
+    end do
+  end subroutine normalize_sf
+
+  ! rhos_vpi.out: one line per lag l >= 1: tau_l = l dt; Dcm_k and its error over the n blocks, per axis; rhos_k and its
+  ! error, per axis; the mean of rhos_k over the axes and its error
+  subroutine write_rhos(fname,dim,Ntau,dt,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: dim,Ntau,n
+    real(8), intent(in) :: dt,av(4*dim+2,0:Ntau),av2(4*dim+2,0:Ntau)
+    integer :: l,j,u
+    real(8) :: a(2*dim+1),a2(2*dim+1)
+    open (newunit=u,file=fname)
+    do l=1,Ntau
+       a  = av(1:2*dim+1,l)/real(n)
+       a2 = av2(1:2*dim+1,l)/real(n)
+       write (u,'(40g20.10e3)') real(l,8)*dt,(a(j),variance(n,a(j),a2(j)),j=1,2*dim+1)
+    end do
+    close (u)
+  end subroutine write_rhos
+
+  ! msdu_vpi.out: one line per lag l >= 0: tau_l; the unfolded msd_k and its error over the n blocks, per axis; their sum
+  ! over the axes and its error; cross_k = Dcm_k - msd_k and its error, per axis
+  subroutine write_msdu(fname,dim,Ntau,dt,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: dim,Ntau,n
+    real(8), intent(in) :: dt,av(4*dim+2,0:Ntau),av2(4*dim+2,0:Ntau)
+    integer :: l,j,u
+    real(8) :: a(2*dim+1),a2(2*dim+1)
+    open (newunit=u,file=fname)
+    do l=0,Ntau
+       a  = av(2*dim+2:4*dim+2,l)/real(n)
+       a2 = av2(2*dim+2:4*dim+2,l)/real(n)
+       write (u,'(40g20.10e3)') real(l,8)*dt,(a(j),variance(n,a(j),a2(j)),j=1,2*dim+1)
+    end do
+    close (u)
+  end subroutine write_msdu
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum, lattice.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum, lattice, superfluid.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -76,6 +76,8 @@ module pigs_families
      integer :: lat_nsite = 0                       ! filled in by the check from config_ini.in: the sites and their
      real(8) :: lat_ann = 0.d0                      ! nearest-neighbour distance
      real(8), allocatable :: lat_sites(:,:)         ! (dim,lat_nsite)
+     logical :: superfluid = .false.
+     integer :: sf_ntau = 0, sf_window = -1         ! sf_window < 0: the smallest window that holds the lags
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -429,17 +431,37 @@ module pigs_families
      procedure :: write_average => lat_write_average
   end type lat_family
 
-  integer, parameter :: NFAM = 13
+  ! the superfluid fraction from the centre-of-mass diffusion along tau: the block's raw sums from the device and the
+  ! normalised block values per lag (pigs_estimators normalize_sf) behind rhos_vpi.out and msdu_vpi.out
+  type, extends(family) :: sf_family
+     integer :: ntau = 0, window = 0
+     real(8) :: lam = 0.5d0                         ! hbar^2/2m in the run's units (the spring term of ThermEnergy)
+     real(8), allocatable :: c(:,:,:),d(:,:,:),b(:,:)
+     integer(c_int64_t), allocatable :: nwrap(:)
+     type(block_series) :: s
+   contains
+     procedure :: check => sf_check
+     procedure :: banner => sf_banner
+     procedure :: setup => sf_setup
+     procedure :: queue => sf_queue
+     procedure :: read => sf_read_block
+     procedure :: block => sf_block
+     procedure :: average => sf_average
+     procedure :: write_walker => sf_write_walker
+     procedure :: write_average => sf_write_average
+  end type sf_family
+
+  integer, parameter :: NFAM = 14
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12,13]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12,13]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12,13,14]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12,13,14]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
   ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
-  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum, 13 lattice
+  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum, 13 lattice, 14 superfluid
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -481,6 +503,7 @@ contains
     if (keys%three_body)      allocate (atm_family :: fs%slot(11)%f)
     if (keys%momentum)        allocate (nk_family :: fs%slot(12)%f)
     if (keys%lattice)         allocate (lat_family :: fs%slot(13)%f)
+    if (keys%superfluid)      allocate (sf_family :: fs%slot(14)%f)
   end subroutine set_create
 
   ! momentum, device-resident sampler: the samples of the step just queued, of all NW walkers
@@ -2143,5 +2166,96 @@ contains
     call write_usite('usite_vpi.out',f%ep%dim,f%nbin,f%rmax,f%cnt%nav,f%sU%asum)
     close (f%upav)
   end subroutine lat_write_average
+
+  !---------------------------------------------------------------------
+  ! superfluid: the diffusion of the centre of mass along imaginary time over the slices Nb-sf_window..Nb+sf_window of a
+  ! periodic system, every link folded once and the folded links added up -- rhos_vpi.out (one line per lag l >= 1: tau,
+  ! Dcm and rhos per axis, their mean) and msdu_vpi.out (one line per lag: tau, the unfolded msd per axis and in total,
+  ! the cross term per axis), every value with its error over the blocks; per walker, and walker-averaged
+
+  subroutine sf_check(f,keys,dim,Nb,trap)
+    class(sf_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('superfluid','a worldline is unfolded through the periodic box')
+    call check_lags('superfluid','sf',keys%sf_ntau,keys%sf_window,Nb)
+    if (keys%sf_ntau+1>3072) then
+       write (0,'(a,i0,a)') ' pigs_vpi: superfluid = T: sf_ntau = ',keys%sf_ntau,' must lie below 3072'
+       stop 2
+    end if
+    if (.not. sf_bind()) call no_backend('superfluid','pigs_sf_init / _accumulate / _read','the centre-of-mass diffusion runs')
+  end subroutine sf_check
+
+  subroutine sf_banner(f,keys,trap)
+    class(sf_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,i0,a,i0,a,i0,a)', '  > Superfluid fraction  : on (centre-of-mass diffusion, lags 0..',keys%sf_ntau,', slices Nb-', &
+         & keys%sf_window,'..Nb+',keys%sf_window,': rhos_vpi.out, msdu_vpi.out)'
+  end subroutine sf_banner
+
+  subroutine sf_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(sf_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    call family_begin(f,run,ep,NW)
+    f%ntau = keys%sf_ntau; f%window = max(keys%sf_window,0)
+    allocate (f%c(ep%dim,0:f%ntau,NW),f%d(ep%dim,0:f%ntau,NW),f%nwrap(NW),f%b(sf_columns(ep%dim),0:f%ntau))
+    call series_create(f%s,sf_columns(ep%dim)*(f%ntau+1),NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(sf_init(ctx,int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_sf_init')
+  end subroutine sf_setup
+
+  subroutine sf_queue(f,ctx,nd,wl)
+    class(sf_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(sf_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sf_accumulate')
+  end subroutine sf_queue
+
+  subroutine sf_read_block(f,ctx)
+    class(sf_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(sf_read(ctx,f%c,f%d,f%nwrap,f%smp,f%reset),'pigs_sf_read')
+  end subroutine sf_read_block
+
+  subroutine sf_block(f,w,info,vec)
+    class(sf_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_sf(f%ep%dim,f%ep%Np,f%ntau,f%window,f%run%dt,f%lam,int(f%smp(w),8),f%c(:,:,w),f%d(:,:,w),f%b)
+    call series_add(f%s,w,reshape(f%b,[size(f%b)]),vec)
+    call count_add(f%cnt,vec)
+  end subroutine sf_block
+
+  subroutine sf_average(f,info,vec)
+    class(sf_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) call series_average(f%s,vec,nall)
+  end subroutine sf_average
+
+  subroutine sf_write_walker(f,suffix,w,nblocks)
+    class(sf_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_rhos('rhos_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+    call write_msdu('msdu_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+  end subroutine sf_write_walker
+
+  subroutine sf_write_average(f)
+    class(sf_family), intent(inout) :: f
+    call write_rhos('rhos_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
+    call write_msdu('msdu_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
+  end subroutine sf_write_average
 
 end module pigs_families

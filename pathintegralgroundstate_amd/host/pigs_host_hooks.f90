@@ -12,6 +12,7 @@ module pigs_host_hooks
   use pigs_estimators, only: est_params, normalize_vh, write_vh, normalize_g3, write_g3, write_g3ang, &
        & normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau, &
        & normalize_lat, lind_header, write_lind_block, write_lindtau, write_usite, &
+       & normalize_sf, sf_columns, write_rhos, write_msdu, &
        & normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec, write_sqshell, write_grvec, &
        & sqv_shells, sqv_shell_means
 
@@ -334,6 +335,31 @@ contains
     call write_lindtau(cstring(ft),dim,window,dt,nblk,aT)
     call write_usite(cstring(fu),dim,nbin,rmax,nblk,aU)
   end subroutine hs_lat_files
+
+  ! The centre-of-mass diffusion normalisation and writers of the front end on given sums: nblk blocks of one walker, C and
+  ! D of pigs_sf_read per block and S samples per block -> fr (rhos_vpi.out) and fm (msdu_vpi.out), the means and errors
+  ! over the blocks through a block_series, as the front end takes them (names: C strings)
+  subroutine hs_sf_files(dim,Np,Ntau,window,dt,lam,nblk,S,C,D,fr,fm) bind(C,name='hs_sf_files')
+    use pigs_block_stats, only: block_series,series_create,series_add
+    integer(c_int), value :: dim,Np,Ntau,window,nblk
+    real(c_double), value :: dt,lam
+    integer(c_int64_t), intent(in) :: S(nblk)
+    real(c_double), intent(in)     :: C(dim,Ntau+1,nblk),D(dim,Ntau+1,nblk)     ! (second index: lag l + 1)
+    character(kind=c_char), intent(in) :: fr(*),fm(*)
+    real(8), allocatable :: B(:,:)
+    real(8) :: none(1)
+    type(block_series) :: sr
+    integer :: ib,nq
+    nq = sf_columns(dim)
+    allocate (B(nq,Ntau+1))
+    call series_create(sr,nq*(Ntau+1),1)
+    do ib=1,nblk
+       call normalize_sf(dim,Np,Ntau,window,dt,lam,int(S(ib),8),C(:,:,ib),D(:,:,ib),B)
+       call series_add(sr,1,reshape(B,[size(B)]),none)
+    end do
+    call write_rhos(cstring(fr),dim,Ntau,dt,nblk,sr%sum(:,1),sr%sq(:,1))
+    call write_msdu(cstring(fm),dim,Ntau,dt,nblk,sr%sum(:,1),sr%sq(:,1))
+  end subroutine hs_sf_files
 
   ! a C string as a Fortran one
   function cstring(c) result(f)

@@ -78,6 +78,12 @@
 ! one line per block: the block, <u^2>, the Lindemann ratio, alpha_2, the vacant and the multiply occupied fraction of the
 ! sites, hops per particle and link, hops per particle across the window; lindtau_vpi.out, one line per window slice: tau,
 ! <u^2>, <u_k^2>, gamma; usite_vpi.out, one line per bin: r, rho_site(r), P(u_k = -r) and P(u_k = +r) per axis)
+! (superfluid = T, periodic systems only: the superfluid fraction at T = 0 from the diffusion of the centre of mass along
+! imaginary time, every link folded once and the folded links added up on the GPU, over the lags 0..sf_ntau (default 0)
+! between the slices Nb-sf_window..Nb+sf_window (default: the smallest window that holds the lags) -- rhos_vpi.out, one line
+! per lag l >= 1: tau, then value and error of Dcm per axis, of rhos = Dcm/(2 lambda tau) per axis (lambda = 1/2) and of
+! their mean; msdu_vpi.out, one line per lag: tau, then value and error of the unfolded <dx_k^2> per axis, of their sum and
+! of the cross term Dcm - <dx_k^2> per axis)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -138,6 +144,8 @@ program pigs_vpi
   logical           :: lattice,lat_cm
   integer           :: lat_nbin,lat_window
   real (kind=8)     :: lat_rmax
+  logical           :: superfluid
+  integer           :: sf_ntau,sf_window
   integer           :: nk_nmax,nk_nbin
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
@@ -163,7 +171,8 @@ program pigs_vpi
        &             triplet,g3_nr,g3_na,g3_rmax,g3_window, &
        &             three_body,atm_nu,atm_rc,atm_window, &
        &             momentum,nk_nmax,nk_nbin, &
-       &             lattice,lat_nbin,lat_rmax,lat_window,lat_cm
+       &             lattice,lat_nbin,lat_rmax,lat_window,lat_cm, &
+       &             superfluid,sf_ntau,sf_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -197,6 +206,7 @@ program pigs_vpi
   triplet = .false.; g3_nr = 10; g3_na = 20; g3_rmax = 0.d0; g3_window = -1
   momentum = .false.; nk_nmax = 8; nk_nbin = 32
   lattice = .false.; lat_nbin = 0; lat_rmax = 0.d0; lat_window = -1; lat_cm = .true.
+  superfluid = .false.; sf_ntau = 0; sf_window = -1
   three_body = .false.; atm_nu = -huge(1.d0); atm_rc = 0.d0; atm_window = -1        ! (atm_nu: a value nobody gives, left out -> 1)
 
   read (5,nml=system,iostat=ios);  rewind (5)
@@ -274,7 +284,8 @@ program pigs_vpi
        & three_body=three_body,atm_nu_given=atm_nu/=-huge(1.d0),atm_nu=merge(atm_nu,1.d0,atm_nu/=-huge(1.d0)), &
        & atm_rc=atm_rc,atm_window=atm_window, &
        & momentum=momentum,nk_nmax=nk_nmax,nk_nbin=nk_nbin,cworm=CWorm,nobdm=Nobdm, &
-       & lattice=lattice,lat_nbin=lat_nbin,lat_rmax=lat_rmax,lat_window=lat_window,lat_cm=lat_cm,nbin_run=Nbin,box=Lbox)
+       & lattice=lattice,lat_nbin=lat_nbin,lat_rmax=lat_rmax,lat_window=lat_window,lat_cm=lat_cm,nbin_run=Nbin,box=Lbox, &
+       & superfluid=superfluid,sf_ntau=sf_ntau,sf_window=sf_window)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 

@@ -89,6 +89,14 @@ displacement with cm), and with N_a = nassigned of slice a, S = samples and ns =
   vacant  = sum_a occ[a, 0] / (S ns nsite),   multiple = sum_a (occ[a, 2] + occ[a, 3]) / (S ns nsite)
   hops per particle and link = hop1 / (S Np (ns - 1)),   across the window = hopw / (S Np)
   rho_site(r) = hr / (S ns nsite shell volume),   P(u_k) = hx[k] / (sum_a N_a rbin)
+Superfluid fraction at T = 0 (normalize_sf, superfluid_fraction, PigsContext.sf_read, pigs_sf_*): every link of the window
+is folded once and the folded links are added up, so the displacement over a lag is the unfolded one; with
+n_pairs(l) = 2 window + 1 - l, S = samples, tau_l = l dt and lam = hbar^2/2m (1/2 in the run's units):
+  Dcm[l, k]  = C / (S n_pairs Np)        <(sum_i dx_k(i))^2> / Np: Np times the squared displacement of the centre of mass
+  rhos[l, k] = Dcm / (2 lam tau_l)       -> rho_s,k / rho for tau -> inf; 1 for a free gas; NaN at l = 0
+  msd[l, k]  = D / (S n_pairs Np)        the single-particle displacement per axis, with no half-box limit
+  cross      = Dcm - msd                 sum_{i != j} <dx_i dx_j> / Np
+and rho_s,k / rho is the slope of Dcm over tau at large tau, divided by 2 lam (superfluid_fraction).
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -532,6 +540,58 @@ def normalize_lat(raw, Np, nsite, a_nn, rmax):
                "r": 0.5 * (edges[1:] + edges[:-1]), "rho_site": hr / (sites[..., None] * shell),
                "x": -float(rmax) + (np.arange(2 * nbin) + 0.5) * rbin, "pu": hx / (ntot[..., None, None] * rbin)}
     return out
+
+
+def normalize_sf(got, Np, dt, lam=0.5, window=None):
+    """got: the dict of sf_read (C and D [W, Ntau+1, dim], samples [W], window) or one walker's slice of it; window: the
+    window of sf_init where got does not carry it.  lam = hbar^2/2m; 1/2 is the run's own unit (a free link has variance
+    dt per axis).  Returns a dict: tau [Ntau+1] = l dt; Dcm [.., Ntau+1, dim] = C / (samples n_pairs(l) Np);
+    rhos [.., Ntau+1, dim] = Dcm / (2 lam tau_l), NaN at l = 0, and rhos_mean [.., Ntau+1], its mean over the axes;
+    msd [.., Ntau+1, dim] = D / (samples n_pairs(l) Np); cross = Dcm - msd.  A walker without samples gives NaN."""
+    Cs = np.asarray(got["C"], dtype=np.float64)
+    Ds = np.asarray(got["D"], dtype=np.float64)
+    S = np.asarray(got["samples"], dtype=np.float64)
+    if window is None:
+        window = got.get("window") if hasattr(got, "get") else None
+    if window is None:
+        raise ValueError("normalize_sf needs the window of sf_init (got['window'] or window=)")
+    window = int(window)
+    if Cs.ndim < 2 or Cs.shape != Ds.shape or S.shape != Cs.shape[:-2]:
+        raise ValueError("the arrays of sf_read do not fit each other")
+    nl = Cs.shape[-2]
+    if nl > 2 * window + 1:
+        raise ValueError("more lags than the window holds")
+    n_pairs = 2.0 * window + 1.0 - np.arange(nl, dtype=np.float64)
+    tau = np.arange(nl, dtype=np.float64) * float(dt)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        norm = S[..., None, None] * n_pairs[:, None] * float(Np)
+        Dcm = Cs / norm
+        msd = Ds / norm
+        rhos = Dcm / (2.0 * float(lam) * tau[:, None])
+        rhos[..., 0, :] = np.nan
+        return {"tau": tau, "Dcm": Dcm, "rhos": rhos, "rhos_mean": rhos.mean(axis=-1), "msd": msd, "cross": Dcm - msd}
+
+
+def superfluid_fraction(tau, Dcm_k, tmin, lam=0.5):
+    """The superfluid fraction along one axis from the diffusion of the centre of mass: the slope of the least-squares
+    line (with an intercept: a crystal's plateau goes there) through Dcm_k [Ntau+1] over the lags with tau >= tmin,
+    divided by 2 lam.  Returns (rho_s / rho, its standard error): the error is the fit's own, from the residuals with
+    n - 2 degrees of freedom (NaN for two points), and knows nothing of the statistical error of Dcm."""
+    t = np.asarray(tau, dtype=np.float64)
+    y = np.asarray(Dcm_k, dtype=np.float64)
+    if t.ndim != 1 or t.shape != y.shape:
+        raise ValueError("tau and Dcm_k must be two vectors of one length")
+    keep = t >= float(tmin)
+    t, y = t[keep], y[keep]
+    n = t.size
+    if n < 2:
+        raise ValueError("a slope needs two lags or more at tau >= tmin")
+    tm, ym = t.mean(), y.mean()
+    sxx = float(((t - tm) ** 2).sum())
+    slope = float(((t - tm) * (y - ym)).sum()) / sxx
+    res = y - (ym + slope * (t - tm))
+    err = math.sqrt(float((res * res).sum()) / (n - 2) / sxx) if n > 2 else float("nan")
+    return slope / (2.0 * float(lam)), err / (2.0 * float(lam))
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
