@@ -374,39 +374,58 @@ __global__ __launch_bounds__(64) void k_delta_action_reforder(
 __device__ __forceinline__ size_t pipe_tab_bytes(int nt) { return ((size_t)(nt + 6) * sizeof(double) + 15) & ~(size_t)15; }
 
 // Staging the table image with the LDS-DMA form of the global load (global_load_lds_dwordx4: 16 bytes per lane
-// straight into LDS at M0 + lane*16, no VGPRs, no ds_write): issued as the very first instructions of the
-// kernel, ahead of the HBM requests of the first items; completion is a vmcnt matter, and vmcnt retires in order,
-// so the wait before the workgroup barrier leaves the first item's slice loads -- the last VMEM requests a wave
-// issues before it -- in flight: the barrier overlaps their latency.  A wave issues the chunk
+// straight into LDS at M0 + lane*16, no VGPRs, no ds_write).  Completion is a vmcnt matter, and vmcnt retires in
+// order.  The chunks are no quick L2 hits -- every CU of an XCD pulls the same table through that XCD's L2 at the same
+// moment -- so nothing the first item needs may queue behind them.  The order of a wave's head is therefore:
+//   1. the static first record, through the scalar unit (pipe2_request_first: lgkmcnt, independent of vmcnt);
+//   2. the table chunks, then the odd last entry (the last wave: one more LDS-DMA load, two lanes of a dword each);
+//   3. as soon as the record is in (lgkmcnt(0), the chunks still in flight): the first item's slice loads.
+// The wait before the workgroup barrier (pipe_table_dma_finish) then leaves exactly those slice loads -- the last VMEM
+// requests the wave issued -- in flight, so a wave's own loads cost max(table, record + slice) and the barrier
+// overlaps the rest of the slice latency.  (With the record on vector loads behind the chunks, the slice's HBM
+// latency started only after the table was in: max(table, record) + slice.)  A wave issues the chunk
 // [u*blockDim + wid*64, +64) only if it starts inside the table; lanes past the end are masked off.  The odd last
-// entry (if any) is loaded at entry too, ahead of the slice loads, so the same wait covers it (loaded after them, it
-// made wave 0 -- and with it the barrier -- wait for wave 0's slices).
+// entry stays ahead of the slice loads so that the same wait covers it, and goes to LDS by DMA like the rest: as a
+// load into a register it stayed pending in the compiler's books past that wait, and drew a vmcnt(0) of its own.
+
+constexpr int kPipeThreads = 1024;                  // the persistent kernel's workgroup: 16 waves, a constant so that the
+                                                    // chunk loop needs no dispatch-packet load behind the first record's
 
 __device__ __forceinline__ void pipe_table_dma_issue(unsigned char *smem, const double *__restrict__ VTg, int nt, int wid, int lane)
 {
 #ifndef PIGS_EXPERIMENT_NO_STAGE
     const double2 *src = reinterpret_cast<const double2 *>(VTg);
     const int n2 = nt / 2;
-    for (int cb = wid * kWave; cb < n2; cb += (int)blockDim.x) {      // wave-uniform
+    for (int cb = wid * kWave; cb < n2; cb += kPipeThreads) {         // wave-uniform
         const int idx = cb + lane;
         auto *l = reinterpret_cast<__attribute__((address_space(3))) void *>(
             (__attribute__((address_space(3))) unsigned char *)smem + 16 + (size_t)cb * 16);
         // lanes past the end of the table are masked off (EXEC): they neither load nor write their LDS slot
         if (idx < n2) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + idx), l, 16, 0, 0);
     }
+    if ((nt & 1) && wid == kPipeThreads / kWave - 1) {                // the odd last entry: two dwords, lanes 0 and 1 of the last wave
+        const int32_t *t = reinterpret_cast<const int32_t *>(VTg + (nt - 1));
+        auto *l = reinterpret_cast<__attribute__((address_space(3))) void *>(
+            (__attribute__((address_space(3))) unsigned char *)smem + 16 + (size_t)(nt - 1) * 8);
+        if (lane < 2) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(t + lane), l, 4, 0, 0);
+    }
 #endif
 }
 
 // after this and a workgroup barrier the image is complete.  IN_FLIGHT: the VMEM requests the wave issued after
-// the table chunks (its first item's slice loads) that may stay outstanding; `tail` = VTg[nt - 1] when nt is odd.
+// the table chunks (its first item's slice loads) that may stay outstanding.  The wait is the builtin, not inline
+// assembly: the compiler has to see it.  Its own books count an LDS-DMA load as pending on vmcnt out of order until a
+// wait it knows of; nothing else in the head waits on vmcnt any more, and without this one it put a vmcnt(0) -- the
+// slice loads included -- in front of the barrier.  (gfx9 encoding: vmcnt in bits 3:0, expcnt 6:4 and lgkmcnt 11:8
+// left at their maxima.)
 template <int IN_FLIGHT>
-__device__ __forceinline__ PipeTab pipe_table_dma_finish(unsigned char *smem, int nt, double tail)
+__device__ __forceinline__ PipeTab pipe_table_dma_finish(unsigned char *smem, int nt)
 {
     double *base = reinterpret_cast<double *>(smem);          // base[1] = leading copy, base[2..] = table
     double *tab  = base + 2;
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(IN_FLIGHT) : "memory");
+    static_assert(IN_FLIGHT >= 0 && IN_FLIGHT < 16, "vmcnt beyond the low four bits");
+    __builtin_amdgcn_s_waitcnt(0x0F70 | IN_FLIGHT);
     if (threadIdx.x == 0) {
-        if (nt & 1) tab[nt - 1] = tail;
         base[0] = 0.0; base[1] = tab[0];                          // wave 0 staged chunk 0 itself: tab[0] has landed
         tab[nt] = 0.0; tab[nt + 1] = 0.0; tab[nt + 2] = 0.0; tab[nt + 3] = 0.0;
     }
@@ -484,6 +503,34 @@ __device__ __forceinline__ ItemRaw pipe2_request(const PipeQueue &Q, int k, int 
     return r;
 }
 
+// The record of a wave's STATIC first item (queue index wid), at the kernel's entry only: through the scalar unit.
+// Its address is known from the launch alone, and scalar loads count on lgkmcnt, so the record does not queue behind
+// the wave's table chunks on the in-order vmcnt (see pipe_table_dma_issue); the lgkmcnt drain that keeps scalar loads
+// out of the steady state costs nothing here, where no LDS gather has been issued yet.  The fields land in SGPRs:
+// no readlanes.  A wave without a first item reads nothing and gets the empty record of pipe2_request (ip = 0).
+template <int DIM>
+struct ItemFirst {                                  // wave-uniform (SGPRs)
+    int    w, ip, ib;
+    double xn[DIM], xo[DIM];
+};
+
+template <int DIM>
+__device__ __forceinline__ ItemFirst<DIM> pipe2_request_first(const PipeQueue &Q, int it, bool has)
+{
+    ItemFirst<DIM> r = {};
+    if (has) {                                      // wave-uniform: `it` is blockIdx + wid * gridDim
+        r.w  = Q.walker[it];
+        r.ip = Q.ipv[it];
+        r.ib = Q.ibv[it];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) {
+            r.xn[k] = Q.xnew[(size_t)it * DIM + k];
+            r.xo[k] = Q.xold[(size_t)it * DIM + k];
+        }
+    }
+    return r;
+}
+
 __device__ __forceinline__ double bcast_lane(double v, int lane_id)
 {
     union { double d; int i[2]; } u;
@@ -497,16 +544,23 @@ __device__ __forceinline__ double bcast_lane(double v, int lane_id)
 // look-ahead needs mid-item; the coordinate half waits for the item's own turn, so that two items' xnew / xold never
 // compete for SGPRs.  A malformed or empty record gets nb = 0: every load of its slice is a no-op.
 template <int DIM>
-__device__ __forceinline__ void pipe2_decode_slice(const DevParams &P, const double *__restrict__ paths, const ItemRaw &r,
-                                                   size_t sl, ItemMeta<DIM> &R)
+__device__ __forceinline__ void pipe2_slice_of(const DevParams &P, const double *__restrict__ paths, int w, int ip, int ib,
+                                               size_t sl, ItemMeta<DIM> &R)
 {
-    const int w = __builtin_amdgcn_readfirstlane(r.w);
-    R.p = __builtin_amdgcn_readfirstlane(r.ip) - 1;
-    R.b = __builtin_amdgcn_readfirstlane(r.ib);
+    R.p = ip - 1;
+    R.b = ib;
     R.ok = (unsigned)w < (unsigned)P.nW && (unsigned)R.p < (unsigned)P.Np && (unsigned)R.b < (unsigned)P.M;
     R.S = paths + (R.ok ? ((size_t)w * P.M + R.b) * sl : 0);
     R.nb = R.ok ? P.NpPad * 8 : 0;
     R.np = R.ok ? P.Np : 0;
+}
+
+template <int DIM>
+__device__ __forceinline__ void pipe2_decode_slice(const DevParams &P, const double *__restrict__ paths, const ItemRaw &r,
+                                                   size_t sl, ItemMeta<DIM> &R)
+{
+    pipe2_slice_of<DIM>(P, paths, __builtin_amdgcn_readfirstlane(r.w), __builtin_amdgcn_readfirstlane(r.ip),
+                        __builtin_amdgcn_readfirstlane(r.ib), sl, R);
 }
 
 template <int DIM>
@@ -635,7 +689,7 @@ __device__ unsigned long long k1_clock[kK1ClockWaves * 5];
 #endif
 
 template <int DIM>
-__global__ __launch_bounds__(1024) void k_delta_action_pipe2(
+__global__ __launch_bounds__(kPipeThreads) void k_delta_action_pipe2(
     DevParams P, const double *__restrict__ paths, const double *__restrict__ VTg,
     const double *__restrict__ WF, int n_items, const int32_t *__restrict__ walker,
     const int32_t *__restrict__ ipv, const int32_t *__restrict__ ibv,
@@ -657,17 +711,20 @@ __global__ __launch_bounds__(1024) void k_delta_action_pipe2(
     PipeState<DIM> st;
     const int nt = P.Nmax + 2;
     K1STAMP(t_entry);
-    pipe_table_dma_issue(smem, VTg, nt, wid, lane);              // L2 hits, issued ahead of the HBM requests below
-    const double tail = VTg[nt - 1];                             // the odd last entry (used when nt is odd)
+    // the head: record (scalar, lgkmcnt) -> table chunks + tail (vmcnt) -> slice loads behind them, issued as soon as
+    // the record is in and while the chunks are still in flight.  it0 < n_items is wid < n_local without the division.
+    const int it0 = (int)blockIdx.x + wid * (int)gridDim.x;
+    const ItemFirst<DIM> r0 = pipe2_request_first<DIM>(Q, it0, it0 < n_items);   // (no first item: the empty record)
+    pipe_table_dma_issue(smem, VTg, nt, wid, lane);
     {
-        const ItemRaw r0 = pipe2_request<DIM>(Q, k_cur, lane);   // (a wave without a first item: the empty record)
-        pipe2_decode_slice<DIM>(P, paths, r0, sl, cur);
-        pipe2_decode_coords<DIM>(r0, cur);
+        pipe2_slice_of<DIM>(P, paths, r0.w, r0.ip, r0.ib, sl, cur);
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) { cur.xn[k] = r0.xn[k]; cur.xo[k] = r0.xo[k]; }
         pipe2_load<DIM>(P, cur.S, cur.nb, cur.p, 0, lane, st.a0);
         pipe2_load<DIM>(P, cur.S, cur.nb, cur.p, 1, lane, st.a1);
     }
 
-    const PipeTab VT = pipe_table_dma_finish<2 * DIM>(smem, nt, tail);   // passes 0/1 stay in flight
+    const PipeTab VT = pipe_table_dma_finish<2 * DIM>(smem, nt);   // passes 0/1 stay in flight
     K1STAMP(t_loaded);
     if (threadIdx.x == 0) next_local = 16;
     double *red = reinterpret_cast<double *>(smem + pipe_tab_bytes(nt) + (size_t)wid * kWaveLds);
@@ -800,7 +857,7 @@ hipError_t launch_delta_action(const DevParams &P, int variant, const double *pa
         int blocks = (n_items + 15) / 16;
         if (blocks > device_cus()) blocks = device_cus();       // persistent grid: one 1024-thread workgroup per CU
         return with_dim(P.dim, [&](auto D) {
-            return launch<k_delta_action_pipe2<D()>>(dim3(blocks), dim3(1024), lds, st, P, paths, VT, WF, n_items, walker, ip, ib,
+            return launch<k_delta_action_pipe2<D()>>(dim3(blocks), dim3(kPipeThreads), lds, st, P, paths, VT, WF, n_items, walker, ip, ib,
                                                      xnew, xold, out, parts);
         });
     }
