@@ -26,6 +26,8 @@ Normalisations (one walker, one block with S samples, i.e. S diagonal steps in t
                        gamma = sqrt(<u^2>) / a_nn; alpha_2 = dim <u^4> / ((dim + 2) <u^2>^2) - 1; vacant and multiply
                        occupied: sites / (S ns nsite); hops / (S Np (ns - 1)) per link and / (S Np) across the window;
                        rho_site = hr / (S ns nsite dV_j); P(u_k) = hx / (assigned of the window x rmax / nbin)
+  superfluid           Dcm_k = C / (S n_pairs(l) Np), rhos_k = Dcm_k / (2 lam l dt) and its mean over the axes (no lag 0),
+                       the unfolded msd_k = D / (S n_pairs(l) Np), cross_k = Dcm_k - msd_k; lam = 1/2
 
 Statistics: a block counts for a walker only if the walker had a diagonal step in it.  A file's mean is the mean of the
 counted block values; its error the "variance" of the reference's files, sqrt((<b^2> - <b>^2) / n) over the n counted
@@ -270,6 +272,34 @@ def norm_lat(mom, nass, occ, hr, hx, hop1, hopw, S, Np, nsite, a_nn, rmax, dim):
                 "vacant": empty / slices, "multiple": many / slices, "hops_link": links,
                 "hops_window": np.asarray(hopw, np.float64) / (S * Np),
                 "rho_site": hr / (_s(slices, 1) * shell_volumes(dim, nbin, rbin)), "pu": hx / (_s(N, 2) * rbin)}
+
+
+def norm_sf(C, D, S, window, Np, dt, lam=0.5):
+    """C, D [..., Ntau + 1, dim], S [...]: the block values of the superfluid family, from include/pigs_hip.h and the column
+    text of pigs_vpi.f90.  n_pairs(l) = 2 window + 1 - l slice pairs lie l apart and tau_l = l dt.  Dcm_k = C / (S n_pairs
+    Np), the squared displacement of the centre of mass times Np; rhos_k = Dcm_k / (2 lam tau_l) and rhos_mean its mean
+    over the axes, both NaN at lag 0 (rhos_vpi.out has no line for it); msd_k = D / (S n_pairs Np), the unfolded squared
+    displacement of a particle; cross_k = Dcm_k - msd_k.  A block without a sample gives NaN."""
+    C, D = np.asarray(C, np.float64), np.asarray(D, np.float64)
+    nl, dim = C.shape[-2], C.shape[-1]
+    assert C.shape == D.shape and nl <= 2 * window + 1
+    out = {k: np.full(C.shape, np.nan) for k in ("Dcm", "rhos", "msd", "cross")}
+    out["rhos_mean"] = np.full(C.shape[:-1], np.nan)
+    with np.errstate(all="ignore"):
+        for l in range(nl):
+            den = np.asarray(S, np.float64) * (2 * window + 1 - l) * Np
+            for k in range(dim):
+                out["Dcm"][..., l, k] = C[..., l, k] / den
+                out["msd"][..., l, k] = D[..., l, k] / den
+                out["cross"][..., l, k] = out["Dcm"][..., l, k] - out["msd"][..., l, k]
+                if l > 0:
+                    out["rhos"][..., l, k] = out["Dcm"][..., l, k] / (2.0 * lam * (l * dt))
+            if l > 0:
+                tot = np.zeros(C.shape[:-2])
+                for k in range(dim):
+                    tot = tot + out["rhos"][..., l, k]
+                out["rhos_mean"][..., l] = tot / dim
+    return out
 
 
 LAT_OUT = ("u2", "uk2", "gamma_tau", "u2_mean", "gamma", "alpha2", "vacant", "multiple", "hops_link", "hops_window",

@@ -22,7 +22,9 @@ The newer families where they meet the others: A+ (all ten periodic diagonal key
 it), B+ and D+ (the worm run with all ten keys, unsharded and on two contexts: partial and empty blocks, momentum's own
 block count next to the diagonal families' on one all-reduced vector), E (boxes with unequal sides, the box-dependent
 defaults left out), L (lattice beside the ten periodic diagonal keys on he4_crystal, its raw sums from lat_numpy on the
-replay's snapshots and its columns from block_stats_numpy.norm_lat).
+replay's snapshots and its columns from block_stats_numpy.norm_lat), S (superfluid behind those eleven on the same run,
+its raw sums from sf_numpy on the replay's snapshots and its columns from block_stats_numpy.norm_sf, per walker and
+all-reduced).
 
 Tolerances: the restatements' own per-element bounds, carried through the block sums, the normalisation and the means,
 plus one unit of the tenth printed digit (PRINT); integer histograms: PRINT alone; error columns, the root of a
@@ -49,6 +51,7 @@ gpu = pytest.mark.gpu
 NMAX, WINDOW, NTAU, GR_NBIN = 2, 2, 3, 8
 BO_NH, BO_NR, G3_NR, G3_NA, ATM_NU, NK_NMAX, NK_NBIN = 8, 8, 3, 4, 2.5, 2, 4
 LAT_NBIN = 6
+SF_NTAU = 3
 # (the self part of van Hove at lag 0 is one full bin, the same value in every block: an ill-conditioned error bar by the
 # expectation alone.  25 bins x 4 lags keep that one row within 1 % of the file's rows; bins of 0.08 resolve the displacements)
 VH_NS, VH_RSELF = 25, 2.0
@@ -66,13 +69,15 @@ KEYS = {"fq_tau": f"fq_tau = T, fq_ntau = {NTAU}, fq_window = {WINDOW}",
         "three_body": f"three_body = T, atm_window = {WINDOW}, atm_nu = {ATM_NU!r}d0",
         "momentum": f"momentum = T, nk_nmax = {NK_NMAX}, nk_nbin = {NK_NBIN}",
         # (RMAX: the range of the displacement histograms, which scenario L fills in)
-        "lattice": f"lattice = T, lat_window = {WINDOW}, lat_nbin = {LAT_NBIN}, lat_rmax = RMAX"}
+        "lattice": f"lattice = T, lat_window = {WINDOW}, lat_nbin = {LAT_NBIN}, lat_rmax = RMAX",
+        # (fewer lags than the window of five slices holds)
+        "superfluid": f"superfluid = T, sf_ntau = {SF_NTAU}, sf_window = {WINDOW}"}
 FILES = {"fq_tau": ["fqt_vpi"], "sq_vector": ["sqvec_vpi", "sq_vpi"], "fq_vector": ["fqvec_vpi", "fqsh_vpi"],
          "fq_self": ["fqself_vpi", "fqssh_vpi", "msd_vpi"], "gr_vector": ["grvec_vpi", "grw_vpi"],
          "tau_profile": ["tau_vpi"], "density_profile": ["dens_vpi", "rho_vpi", "pr_vpi"],
          "bond_order": ["bo_vpi", "boh_vpi", "g6_vpi"], "van_hove": ["gd_vpi", "gs_vpi"], "triplet": ["g3_vpi", "g3ang_vpi"],
          "three_body": ["v3tau_vpi"], "momentum": ["nkvec_vpi", "nk_vpi", "nrvec_vpi"],
-         "lattice": ["lind_vpi", "lindtau_vpi", "usite_vpi"]}
+         "lattice": ["lind_vpi", "lindtau_vpi", "usite_vpi"], "superfluid": ["rhos_vpi", "msdu_vpi"]}
 # the files with one line per block, which check_v3 and check_n0 read
 BLOCK_FILES = {"tau_profile": ["press_vpi"], "three_body": ["v3_vpi"], "momentum": ["n0_vpi"]}
 # scenario B: (Nblock, Nstep) of he4_wormbusy_s7 with four walkers, chosen from the replay's open / closed pattern over 60
@@ -1115,6 +1120,90 @@ def test_crystal_run_lattice_beside_ten_keys(exe, scn_l, run_l, tmp_path):
     out1 = _run(exe, scn_l["txt"] + group, one)
     check_replay_is_the_run(one, out1, scn_l["rep"])
     _same_files(d, one, ["lattice"], L_WALKERS)
+
+
+def superfluid_blocks(rep):
+    """The block values of the superfluid family from the replay: the raw sums of every diagonal step from sf_numpy on the
+    step's snapshot, added over the steps of a block here, and block_stats_numpy.norm_sf.  Returns ({name: [W, Nblock,
+    ..]}, counted [W, Nblock])."""
+    import sf_numpy
+    cfg = rep["cfg"]
+    steps = []
+    for t in range(rep["snaps"].shape[0]):
+        ws = [int(w) for w in np.flatnonzero(rep["diag"][t])]
+        steps.append(sf_numpy.Window(rep["snaps"][t], cfg.Nb, WINDOW, cfg.Lbox[:cfg.dim], SF_NTAU).expected(ws))
+    raw = {k: _blocks(np.stack([e[k] for e in steps]), rep) for k in steps[0]}
+    S = _blocks(rep["diag"].astype(np.int64), rep)
+    assert np.array_equal(raw["samples"], S) and raw["C"].shape == raw["D"].shape == S.shape + (SF_NTAU + 1, cfg.dim)
+    return bs.norm_sf(raw["C"], raw["D"], S, WINDOW, cfg.Np, cfg.dt), S > 0
+
+
+def check_superfluid(d, vals, cnt, rep, what, per_walker=True):
+    """rhos_vpi*.out and msdu_vpi*.out of the directory d against the block values: walker w's files take the blocks that
+    the walker counted; the all-reduced files take, of every block that some walker counted, the mean over the walkers that
+    counted it (block_stats_numpy.walker_average, the rule of pigs_block_stats.f90).  test_sf_host.check_files: the means
+    to the printed digits, the block errors to 1e-6 of the values' scale."""
+    from test_sf_host import check_files
+    cfg, W = rep["cfg"], rep["W"]
+    for w in (list(range(W)) if per_walker else []) + [None]:
+        if w is None:
+            avg = {k: bs.walker_average(v, cnt) for k, v in vals.items()}
+            mine, cb = {k: a[0] for k, a in avg.items()}, avg["Dcm"][1]
+            assert np.array_equal(cb, cnt.any(axis=0))
+        else:
+            mine, cb = {k: v[w] for k, v in vals.items()}, cnt[w]
+        blocks = [{k: v[b] for k, v in mine.items()} for b in np.flatnonzero(cb)]
+        assert blocks, (what, w)
+        for b in blocks:                                                # counted: every lag beyond 0 is a number
+            assert all(np.all(np.isfinite(b[k][1:])) for k in b) and np.all(b["msd"][1:] > 0), (what, w)
+        suffix = f".w{w:04d}" if w is not None else ""
+        print(f"{what} rhos_vpi{suffix}.out, msdu_vpi{suffix}.out: {len(blocks)} blocks")
+        check_files(os.path.join(d, f"rhos_vpi{suffix}.out"), os.path.join(d, f"msdu_vpi{suffix}.out"), blocks, cfg.dim, SF_NTAU, cfg.dt)
+
+
+@gpu
+def test_crystal_run_superfluid_beside_eleven_keys(exe, scn_l, run_l, tmp_path):
+    """Scenario L with superfluid (lags 0..3 of window 2: fewer than the window holds) behind the eleven keys, the last
+    claim on the all-reduced block vector.  The expectation is independent of pigs_sf_*: sf_numpy on the replay's
+    snapshots, norm_sf, and the block statistics restated in block_stats_numpy.  Checked: the two files of every walker
+    (a walker's mean is over the blocks in which it was diagonal and no others: walker 0 counts one block of three, walker
+    2 two); the all-reduced rhos_vpi.out and msdu_vpi.out; a run with the key alone writes the same characters into all
+    four kinds of file; every file of the run without the key is unchanged byte for byte; on two contexts of one GPU the
+    all-reduced files meet the same expectation and the per-walker files are the one-shard run's byte for byte."""
+    sc = scn_l
+    rep, cfg, cnt, W = sc["rep"], sc["cfg"], sc["cnt"], L_WALKERS
+    vals, counted = superfluid_blocks(rep)
+    assert np.array_equal(counted, cnt) and cnt.all(axis=1).any() and (cnt.sum(axis=1) < L_BLOCKS).any() and cnt.any(axis=1).all()
+    assert SF_NTAU < 2 * WINDOW and not cfg.trap and cfg.Nb >= WINDOW
+    group = _gpu_group(L_KEYS + ["superfluid"], W, "device_sampler = T, ", cfg).replace("RMAX", f"{sc['rmax']:.6f}d0")
+    assert group.replace(", " + KEYS["superfluid"], "") == sc["group"]
+    plain, _ = run_l
+    d = _crystal_dir(tmp_path, "all")
+    out = _run(exe, sc["txt"] + group, d)
+    assert "Superfluid fraction" in out and "Lattice sites" in out
+    check_replay_is_the_run(d, out, rep)
+    check_superfluid(d, vals, cnt, rep, "S all keys:")
+    # the other keys' files: unchanged by the key; the new files: the four kinds and nothing else
+    old = sorted(os.listdir(plain))
+    new = sorted(set(os.listdir(d)) - set(old))
+    assert new == sorted(f"{base}{s}.out" for base in FILES["superfluid"] for s in _suffixes(W)), new
+    for f in old:
+        if f not in ("stdout.txt", "vpi.in"):
+            assert _same(plain, d, f), f
+    # the key alone
+    one = _crystal_dir(tmp_path, "alone")
+    out1 = _run(exe, sc["txt"] + _gpu_group(["superfluid"], W, "device_sampler = T, ", cfg), one)
+    check_replay_is_the_run(one, out1, rep)
+    _same_files(d, one, ["superfluid"], W)
+    # two contexts of one GPU
+    two = _crystal_dir(tmp_path, "two")
+    out2 = _run(exe, sc["txt"] + group.replace("device_sampler = T, ", "device_sampler = T, device = 0, n_gpus = 2, same_device = T, "), two)
+    assert re.search(r"GPUs \(walker shards\):\s*2\b", out2), out2[:3000]
+    check_replay_is_the_run(two, out2, rep)
+    check_superfluid(two, vals, cnt, rep, "S sharded:", per_walker=False)
+    for base in FILES["superfluid"]:
+        for w in range(W):
+            assert _same(d, two, f"{base}.w{w:04d}.out"), (base, w)
 
 
 @gpu

@@ -151,6 +151,39 @@ def test_normalize_sf_by_hand():
         normalize_sf(got, 4, 0.25, window=0)                                 # three lags in one slice
 
 
+@pytest.mark.parametrize("dim", [1, 2, 3])
+def test_block_stats_norm_sf_equals_normalize_sf(dim):
+    """block_stats_numpy.norm_sf, which the front-end tests take their expected block values from, against
+    profiles.normalize_sf: random positive sums of two walkers x three blocks, one of them without a sample; then the
+    figures of test_normalize_sf_by_hand, divided there by hand."""
+    import block_stats_numpy as bs
+    rng = np.random.default_rng(40 + dim)
+    window, Ntau, Np, dt = 3, 5, 37, 0.0125
+    S = np.array([[4, 0, 7], [1, 3, 2]], np.int64)
+    lag = np.arange(Ntau + 1.0)[:, None]
+    Cs = rng.uniform(0.5, 2.0, (2, 3, Ntau + 1, dim)) * lag * np.maximum(S, 1)[..., None, None] * Np
+    Ds = rng.uniform(0.5, 2.0, (2, 3, Ntau + 1, dim)) * lag * np.maximum(S, 1)[..., None, None] * Np
+    Cs[0, 1], Ds[0, 1] = 0.0, 0.0                                          # what a read leaves of a block without a sample
+    mine = bs.norm_sf(Cs, Ds, S, window, Np, dt)
+    want = normalize_sf({"C": Cs, "D": Ds, "samples": S, "window": window}, Np, dt)
+    assert sorted(mine) == sorted(k for k in want if k != "tau")
+    for k, v in mine.items():
+        assert v.shape == want[k].shape and np.array_equal(np.isnan(v), np.isnan(want[k])), k
+        assert np.allclose(v, want[k], rtol=1e-14, atol=0, equal_nan=True), k
+        assert np.all(np.isnan(v[0, 1])), k                                # the block without a sample
+        fin = v[S > 0]
+        assert np.all(np.isfinite(fin[:, 1:])) and (np.all(np.isnan(fin[:, 0])) if k.startswith("rhos") else not np.any(fin[:, 0])), k
+    assert np.all(mine["Dcm"][S > 0][:, 1:] > 0) and np.all(mine["rhos"][S > 0][:, 1:] > 0)
+    for k, v in bs.norm_sf(Cs, Ds, S, window, Np, dt, lam=2.0).items():
+        assert np.allclose(v, normalize_sf({"C": Cs, "D": Ds, "samples": S, "window": window}, Np, dt, lam=2.0)[k],
+                           rtol=1e-14, atol=0, equal_nan=True), k
+    if dim == 2:
+        n = bs.norm_sf([[0.0, 0.0], [48.0, 96.0], [64.0, 16.0]], [[0.0, 0.0], [24.0, 48.0], [8.0, 32.0]], 2, 1, 4, 0.25)
+        assert n["Dcm"].tolist() == [[0.0, 0.0], [3.0, 6.0], [8.0, 2.0]] and n["msd"].tolist() == [[0.0, 0.0], [1.5, 3.0], [1.0, 4.0]]
+        assert n["cross"].tolist() == [[0.0, 0.0], [1.5, 3.0], [7.0, -2.0]] and n["rhos"][1:].tolist() == [[12.0, 24.0], [16.0, 4.0]]
+        assert n["rhos_mean"][1:].tolist() == [18.0, 10.0] and np.all(np.isnan(n["rhos"][0])) and math.isnan(n["rhos_mean"][0])
+
+
 def test_superfluid_fraction_on_a_straight_line():
     tau = 0.125 * np.arange(9)
     y = 0.75 * tau + 0.5
