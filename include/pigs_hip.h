@@ -834,6 +834,68 @@ int pigs_sf_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
  * PIGS_ERR_ARG before pigs_sf_init. */
 int pigs_sf_read(pigs_ctx *ctx, double *C, double *D, int64_t *nwrap, int64_t *samples, const int32_t *reset);
 
+/* ---- the cluster-size distribution of a PERIODIC system, over a slice window (new: the structural families above look
+ * at pairs or triplets inside a radius; this one says which particles belong together -- connected components of the
+ * bond graph, an iterative, data-dependent pass whose result, a partition, has no summation order) -------------------
+ * Scope.  Periodic contexts with dim = 1, 2 or 3 and Np <= PIGS_CL_NP_MAX.  A trapped context gets PIGS_ERR_UNSUPPORTED.
+ * The window covers slices a = Nb-window .. Nb+window.  For each window slice of a listed walker:
+ * Bond.  i != j are bonded iff 0 < r2 < rc2 in double.  This is pigs_bop_*'s rule, so a coincident pair and a non-finite
+ *   r2 are no bond.
+ *   r2 is the squares of d = x(i) - x(j) summed left to right, d folded once by min_image<DIM>.
+ *   rc2 = rc*rc is computed once on the host.
+ *   Padding particles (index >= Np) never take part.
+ * Label.  label(i) is the smallest particle index in i's connected component of the bond graph.  A cluster's root is that
+ *   index, and its size s is the number of its members.
+ * Integer sums (int64, per walker w):
+ *   nsize[w][s-1] += 1 per cluster of size s (s = 1..Np).
+ *   nlarge[w][smax-1] += 1 per slice, smax being the slice's largest size.
+ *   nbond[w] += the slice's bonds (i < j).
+ *   samples[w] += 1 per slice.
+ *   It follows that sum_s s nsize = Np samples and sum_s nlarge = samples.
+ * Radius of gyration (double, rg2[w][s-1]), summed in one fixed order:
+ *   For each i: t_i = 0.0; for j = i+1..Np-1 ascending with label(j) == label(i): t_i = t_i + r2_ij (the r2 above).
+ *   For each cluster: T = 0.0; over its members i ascending: T = T + t_i; then g = T / ((double)s*(double)s).  For s = 1
+ *   this gives g = 0.
+ *   For each size: G_slice[s] = 0.0, plus the g of that size's clusters in ascending root order.
+ *   rg2[w][s-1] = rg2[w][s-1] + G_slice[s], slices ascending, one add per slice and size.
+ *   No floating-point atomics.
+ *   g = (1/s^2) sum_{i<j} r_ij^2 is the true Rg^2 of the cluster ONLY WHILE THE CLUSTER'S EXTENT STAYS BELOW HALF THE BOX:
+ *   beyond, the folded r_ij of two members is no longer their separation along the cluster.  The library does not judge it.
+ * Determinism.  The same worldline gives the same counts and the same bits of rg2 whatever the walker list, its order, the
+ * launch split, the scratch budget or the number of walkers of the context.  A walker listed twice counts twice, in two
+ * launches.
+ * Caller's divisions.  profiles.normalize_cl(got, Np) returns n(s) per sample, the particle fraction s n(s)/Np,
+ * P_largest(s), <Rg^2>(s) = rg2/nsize (NaN where n(s) = 0), the mean number of clusters, <smax>/Np, the mean cluster size
+ * S = sum s^2 n(s) / sum s n(s) and the bonds per particle.
+ * Kernel.  One workgroup labels a slice in LDS by min-label hooking and pointer jumping until a sweep changes nothing
+ * (a vote, not a fixed count).  Up to 256 particles the bonds are kept as bit rows in LDS; beyond, every sweep computes the
+ * distances again.  The counts do not depend on it.  PIGS_CL_NP_MAX is what the slice, the labels and the counters of one
+ * workgroup hold in LDS.
+ * Scratch.  The per-slice sums of one launch, 8 (2 window + 1) Np bytes per walker, sit in device memory between the two
+ * kernels of a launch.  pigs_cl_init allocates min(n_walkers, 256, what fits 256 MiB) walkers of it, one at the least, and
+ * pigs_cl_accumulate puts no more walkers into a launch; pigs_set_tuning "cl_scratch_mib" (1..2048, read by the next
+ * pigs_cl_init) sets another budget.  The bits do not depend on it.
+ *
+ * pigs_cl_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context;
+ * PIGS_ERR_ARG for rc not finite or <= 0, rc beyond half the shortest side, window < 0, window > Nb, Np > PIGS_CL_NP_MAX,
+ * or sums beyond 2 GiB. */
+#define PIGS_CL_NP_MAX 2048
+int pigs_cl_np_max(void);                /* PIGS_CL_NP_MAX of the library that is loaded */
+int pigs_cl_init(pigs_ctx *ctx, double rc, int32_t window);
+/* Adds every window slice of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts twice).  Queued on the context's
+ * stream, no upload, no host synchronisation: it sees the worldline every call queued before it left, never the next
+ * step's.  The list travels in the kernel arguments, at most 256 walkers per launch and more in further launches.
+ * PIGS_ERR_ARG before pigs_cl_init, for n < 0 or for a walker out of range. */
+int pigs_cl_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' nsize[n_walkers][Np], nlarge[n_walkers][Np], nbond[n_walkers], samples[n_walkers] (int64) and
+ * rg2[n_walkers][Np] (doubles); then zeroes those of the walkers w with reset[w] != 0 (reset == NULL: none).
+ * Synchronises the context.  PIGS_ERR_ARG before pigs_cl_init. */
+int pigs_cl_read(pigs_ctx *ctx, int64_t *nsize, int64_t *nlarge, int64_t *nbond, int64_t *samples, double *rg2,
+                 const int32_t *reset);
+/* The largest number of labelling sweeps that any (walker, slice) needed since pigs_cl_init: a report for benchmarks, no
+ * part of the result.  Synchronises the context.  PIGS_ERR_ARG before pigs_cl_init. */
+int pigs_cl_sweeps(pigs_ctx *ctx, int32_t *max_sweeps);
+
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
  * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for

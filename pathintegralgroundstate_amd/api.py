@@ -24,6 +24,8 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
 
+CL_NP_MAX = 2048           # PIGS_CL_NP_MAX of include/pigs_hip.h (pigs_cl_np_max() of the library)
+
 # every symbol include/pigs_hip.h declares
 ABI_SYMBOLS = [
     "pigs_ctx_create", "pigs_ctx_destroy", "pigs_last_error", "pigs_abi_version",
@@ -53,6 +55,7 @@ ABI_SYMBOLS = [
     "pigs_nk_init", "pigs_nk_count", "pigs_nk_vectors", "pigs_nk_accumulate", "pigs_nk_add", "pigs_nk_read",
     "pigs_lat_init", "pigs_lat_accumulate", "pigs_lat_read",
     "pigs_sf_init", "pigs_sf_accumulate", "pigs_sf_read",
+    "pigs_cl_np_max", "pigs_cl_init", "pigs_cl_accumulate", "pigs_cl_read", "pigs_cl_sweeps",
 ]
 
 
@@ -188,6 +191,11 @@ def load_library(path=LIB_PATH):
     L.pigs_sf_init.argtypes = [vp, C.c_int32, C.c_int32]
     L.pigs_sf_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_sf_read.argtypes = [vp, _dp, _dp, _lp, _lp, _ip]
+    L.pigs_cl_np_max.argtypes = []
+    L.pigs_cl_init.argtypes = [vp, C.c_double, C.c_int32]
+    L.pigs_cl_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_cl_read.argtypes = [vp, _lp, _lp, _lp, _lp, _dp, _ip]
+    L.pigs_cl_sweeps.argtypes = [vp, C.POINTER(C.c_int32)]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -931,6 +939,42 @@ class PigsContext:
              "pigs_sf_read")
         out["window"] = window
         return out
+
+    # ---- the cluster-size distribution over a slice window (pigs_cl_*: 64-bit counts and the sums of Rg^2 per walker and size)
+    def cl_init(self, rc, window=0):
+        """Allocate and zero the cluster sums of a periodic system: i and j are bonded iff 0 < r_ij^2 < rc^2 (minimum
+        image, rc at most half the shortest side), a cluster is a connected component of that graph, over the slices
+        Nb-window..Nb+window.  At most CL_NP_MAX particles.  Calling it again resizes and zeroes."""
+        if self.cfg.Np > CL_NP_MAX:
+            raise PigsError(f"cl_init: Np={self.cfg.Np} passes the {CL_NP_MAX} particles a workgroup labels")
+        _chk(self.L, self.L.pigs_cl_init(self.h, float(rc), int(window)), "pigs_cl_init")
+        self._cl = int(window)
+
+    def cl_accumulate(self, walkers=None):
+        """Queue one sample of every window slice of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_cl_accumulate", walkers)
+
+    def cl_read(self, reset=None):
+        """dict of the raw sums: nsize [W, Np] (int64: clusters of size s at s - 1), nlarge [W, Np] (int64: slices whose
+        largest cluster has size s), nbond [W] and samples [W] (int64: bonds, and slices), rg2 [W, Np] (float64: the sum
+        of the clusters' Rg^2 per size); and "window".  profiles.normalize_cl divides them.  reset: None, True (all
+        walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
+        if getattr(self, "_cl", None) is None:
+            raise PigsError("cl_read: cl_init first")
+        W, Np = self.n_walkers, self.cfg.Np
+        out = {"nsize": np.zeros((W, Np), np.int64), "nlarge": np.zeros((W, Np), np.int64), "nbond": np.zeros(W, np.int64),
+               "samples": np.zeros(W, np.int64), "rg2": np.zeros((W, Np))}
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_cl_read(self.h, _l(out["nsize"]), _l(out["nlarge"]), _l(out["nbond"]), _l(out["samples"]),
+                                         _d(out["rg2"]), mask), "pigs_cl_read")
+        out["window"] = self._cl
+        return out
+
+    def cl_sweeps(self):
+        """The largest number of labelling sweeps any (walker, slice) needed since cl_init (a report, no result)."""
+        v = C.c_int32(0)
+        _chk(self.L, self.L.pigs_cl_sweeps(self.h, C.byref(v)), "pigs_cl_sweeps")
+        return int(v.value)
 
     # ---- K5
     def commit_beads(self, walker, ip, ib, x):

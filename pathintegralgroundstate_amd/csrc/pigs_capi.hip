@@ -300,6 +300,16 @@ struct pigs_ctx {
     int         sf_ntau = 0, sf_window = 0;
     int         sf_slots = 0;               // walkers per launch: what the scratch holds
     int         sf_scratch_mib = kSfScratchMiB;   // pigs_set_tuning "sf_scratch_mib": the budget of U at the next pigs_sf_init
+    // cluster-size distribution over a slice window (pigs_cl_*): per walker nsize, nlarge and rg2 [Np], nbond and samples;
+    // the per-slice sums of g per size of one launch ([cl_slots][2 window + 1][Np]); the largest sweep count so far
+    DevBuf<unsigned long long> d_cl_nsize, d_cl_nlarge, d_cl_nbond, d_cl_samples;
+    DevBuf<double> d_cl_rg2, d_cl_scratch;
+    DevBuf<unsigned int> d_cl_sweeps;
+    bool        cl_ready = false;           // pigs_cl_init called
+    int         cl_window = 0;
+    int         cl_slots = 0;               // walkers per launch: what the scratch holds
+    double      cl_rc2 = 0.0;
+    int         cl_scratch_mib = kClScratchMiB;   // pigs_set_tuning "cl_scratch_mib": the budget of the scratch at the next pigs_cl_init
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -531,6 +541,11 @@ int pigs_set_tuning(pigs_ctx *c, const char *key, int32_t value)
     if (!strcmp(key, "sf_scratch_mib")) {       // MiB the unfolded paths of one pigs_sf_accumulate launch may take; read by pigs_sf_init
         if (value < 1 || value > 2048) return fail(PIGS_ERR_ARG, "sf_scratch_mib=%d", value);
         c->sf_scratch_mib = value;
+        return PIGS_OK;
+    }
+    if (!strcmp(key, "cl_scratch_mib")) {       // MiB the per-slice sums of one pigs_cl_accumulate launch may take; read by pigs_cl_init
+        if (value < 1 || value > 2048) return fail(PIGS_ERR_ARG, "cl_scratch_mib=%d", value);
+        c->cl_scratch_mib = value;
         return PIGS_OK;
     }
     if (!strcmp(key, "sweep_threads")) {
@@ -2393,6 +2408,79 @@ int pigs_sf_read(pigs_ctx *c, double *C, double *D, int64_t *nwrap, int64_t *sam
     const size_t per = (size_t)(c->sf_ntau + 1) * (size_t)c->P.dim;
     return read_and_reset(c, {{c->d_sf_C.p, per, C}, {c->d_sf_D.p, per, D}, {c->d_sf_nwrap.p, 1, nwrap},
                               {c->d_sf_samples.p, 1, samples}}, reset);
+}
+
+// ---- the cluster-size distribution of a periodic system over a slice window -----------------------
+// Integer counts and the sums of Rg^2 per walker and size (pigs_cl.hip), accumulated on the device and read per block.  The
+// per-slice sums of a launch sit in a scratch whose size pigs_cl_init bounds; the launches are cut to the walkers it holds.
+int pigs_cl_np_max(void) { return kClNpMax; }
+
+int pigs_cl_init(pigs_ctx *c, double rc, int32_t window)
+{
+    int st = check_ctx(c); if (st) return st;
+    st = check_cm(c); if (st) return st;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "clusters are defined for periodic systems only (bonds are minimum images)");
+    bool rc_ok = std::isfinite(rc) && rc > 0.0;
+    for (int k = 0; k < c->P.dim; ++k) rc_ok = rc_ok && rc <= c->P.LboxHalf[k];
+    if (!rc_ok || window < 0 || window > c->P.Nb)
+        return fail(PIGS_ERR_ARG, "pigs_cl_init: rc=%g (0 < rc <= half the shortest side) window=%d (0..Nb=%d)", rc, window, c->P.Nb);
+    if (c->P.Np > kClNpMax || cl_lds_bytes(c->P.dim, c->P.Np) > kClLdsBudget)
+        return fail(PIGS_ERR_ARG, "pigs_cl_init: Np=%d passes the %d particles a workgroup labels in LDS", c->P.Np, kClNpMax);
+    const size_t W = (size_t)c->n_walkers, np = (size_t)c->P.Np;
+    if ((double)W * (3.0 * (double)np + 2.0) * 8.0 > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_cl_init: %zu walkers x (3 x %d + 2) sums pass 2 GiB", W, c->P.Np);
+    const size_t slot = cl_slot_doubles(c->P.Np, window);
+    const size_t fit = ((size_t)c->cl_scratch_mib << 20) / (slot * sizeof(double));
+    const size_t slots = std::max<size_t>(1, std::min({W, (size_t)kWalkerListMax, fit}));
+    st = init_begin(c, c->cl_ready); if (st) return st;
+    HIPCHK(alloc_zeroed(c, c->d_cl_nsize, W * np));
+    HIPCHK(alloc_zeroed(c, c->d_cl_nlarge, W * np));
+    HIPCHK(alloc_zeroed(c, c->d_cl_nbond, W));
+    HIPCHK(alloc_zeroed(c, c->d_cl_samples, W));
+    HIPCHK(alloc_zeroed(c, c->d_cl_rg2, W * np));
+    HIPCHK(alloc_zeroed(c, c->d_cl_scratch, slots * slot));
+    HIPCHK(alloc_zeroed(c, c->d_cl_sweeps, 1));
+    SYNC_CHECKED(c);
+    c->cl_window = window; c->cl_slots = (int)slots; c->cl_rc2 = rc * rc;
+    c->cl_ready = true;
+    return PIGS_OK;
+}
+
+int pigs_cl_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int st = check_ctx(c); if (st) return st;
+    st = check_cm(c); if (st) return st;
+    if (!c->cl_ready) return fail(PIGS_ERR_ARG, "pigs_cl_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    st = walker_list(c, n, walkers, sw); if (st) return st;
+    // one thread owns an element of rg2 per launch; a launch's walkers fit the scratch
+    return each_launch(c, sw, walkers, true, c->cl_slots, "launch_cl", [&](int m, const WalkerList &L) {
+        return launch_cl(c->P, c->d_paths.p, m, L, c->cl_window, c->cl_rc2, c->d_cl_scratch.p, c->d_cl_nsize.p, c->d_cl_nlarge.p,
+                         c->d_cl_nbond.p, c->d_cl_samples.p, c->d_cl_rg2.p, c->d_cl_sweeps.p, c->stream);
+    });
+}
+
+int pigs_cl_read(pigs_ctx *c, int64_t *nsize, int64_t *nlarge, int64_t *nbond, int64_t *samples, double *rg2, const int32_t *reset)
+{
+    int st = check_ctx(c); if (st) return st;
+    if (!c->cl_ready) return fail(PIGS_ERR_ARG, "pigs_cl_init first");
+    if (!nsize || !nlarge || !nbond || !samples || !rg2) return fail(PIGS_ERR_ARG, "null output");
+    const size_t np = (size_t)c->P.Np;
+    return read_and_reset(c, {{c->d_cl_nsize.p, np, nsize}, {c->d_cl_nlarge.p, np, nlarge}, {c->d_cl_nbond.p, 1, nbond},
+                              {c->d_cl_samples.p, 1, samples}, {c->d_cl_rg2.p, np, rg2}}, reset);
+}
+
+int pigs_cl_sweeps(pigs_ctx *c, int32_t *max_sweeps)
+{
+    int st = check_ctx(c); if (st) return st;
+    if (!c->cl_ready) return fail(PIGS_ERR_ARG, "pigs_cl_init first");
+    if (!max_sweeps) return fail(PIGS_ERR_ARG, "null output");
+    unsigned int v = 0u;
+    HIPCHK(hipMemcpyAsync(&v, c->d_cl_sweeps.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    SYNC_CHECKED(c);
+    *max_sweeps = (int32_t)v;
+    return PIGS_OK;
 }
 
 // ---- multi-GPU ---------------------------------------------------------------------------

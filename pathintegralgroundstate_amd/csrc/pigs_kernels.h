@@ -249,6 +249,28 @@ hipError_t launch_sf(const DevParams &P, const double *paths, int n, const Walke
                      double *Wcm, double *C, double *D, unsigned long long *nwrap, unsigned long long *samples,
                      hipStream_t st);
 
+// pigs_cl.hip: the cluster-size distribution over the window slices (pigs_cl_accumulate).  k_cl, one workgroup per (listed
+// walker, slice) with the slice in LDS, labels the connected components of the bond graph 0 < r2 < rc2 by hook and
+// pointer jump until a sweep changes nothing, adds the sizes to nsize and the largest to nlarge ([walker][Np]), the bonds
+// to nbond and 1 per slice to samples (integer atomics), and writes the slice's sums of g per size to scratch
+// ([slot][slice][Np]); k_cl_combine adds the slices in ascending order to rg2 ([walker][Np]).  One thread owns an element
+// of rg2 per launch: the caller never lists a walker twice in ONE launch.  Up to kClAdjNpMax particles the bonds are kept
+// as bit rows in LDS beside the slice (Np^2/8 bytes: 8 KB at 256, under the 64 KB that need no grant); beyond, every sweep
+// computes the distances again.  kClNpMax: the u32 counters and the slice, labels and sums in LDS (cl_lds_bytes, which has
+// to fit kClLdsBudget).  A slot of the scratch takes cl_slot_doubles doubles; pigs_cl_init sizes it (kClScratchMiB MiB by
+// default, one slot at the least) and pigs_cl_accumulate cuts its launches to the slots there are.  sweeps (may be null):
+// the largest number of labelling sweeps of any workgroup so far.
+constexpr int kClThreads = 256;
+constexpr int kClAdjNpMax = 256;
+constexpr int kClNpMax = 2048;
+constexpr int kClScratchMiB = 256;
+constexpr size_t kClLdsBudget = 160 * 1024;      // LDS of one CU on gfx950
+size_t cl_lds_bytes(int dim, int Np);
+size_t cl_slot_doubles(int Np, int window);
+hipError_t launch_cl(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, double rc2,
+                     double *scratch, unsigned long long *nsize, unsigned long long *nlarge, unsigned long long *nbond,
+                     unsigned long long *samples, double *rg2, unsigned int *sweeps, hipStream_t st);
+
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);
 

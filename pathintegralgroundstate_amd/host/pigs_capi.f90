@@ -707,6 +707,26 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_sf_read_t
+
+     ! the cluster-size distribution over a slice window (include/pigs_hip.h, pigs_cl_*): looked up at run time, see
+     ! cl_bind; _accumulate has the signature of pigs_grv_accumulate
+     function pigs_cl_init_t(ctx,rc,window) bind(C) result(st)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value         :: ctx
+       real(c_double), value      :: rc
+       integer(c_int32_t), value  :: window
+       integer(c_int) :: st
+     end function pigs_cl_init_t
+
+     function pigs_cl_read_t(ctx,nsize,nlarge,nbond,samples,rg2,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int64_t)             :: nsize(*),nlarge(*)     ! (Np,n_walkers)
+       integer(c_int64_t)             :: nbond(*),samples(*)
+       real(c_double)                 :: rg2(*)                 ! (Np,n_walkers)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_cl_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -787,6 +807,11 @@ module pigs_capi
   procedure(pigs_sf_init_t), pointer        :: sf_init => null()
   procedure(pigs_grv_accumulate_t), pointer :: sf_accumulate => null()
   procedure(pigs_sf_read_t), pointer        :: sf_read => null()
+
+  ! bound by cl_bind (null until then)
+  procedure(pigs_cl_init_t), pointer        :: cl_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: cl_accumulate => null()
+  procedure(pigs_cl_read_t), pointer        :: cl_read => null()
 
 contains
 
@@ -970,6 +995,16 @@ contains
     call c_f_procpointer(f(2),sf_accumulate)
     call c_f_procpointer(f(3),sf_read)
   end function sf_bind
+
+  ! The cluster entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function cl_bind()
+    type(c_funptr) :: f(3)
+    cl_bind = resolve_all('pigs_cl',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. cl_bind) return
+    call c_f_procpointer(f(1),cl_init)
+    call c_f_procpointer(f(2),cl_accumulate)
+    call c_f_procpointer(f(3),cl_read)
+  end function cl_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

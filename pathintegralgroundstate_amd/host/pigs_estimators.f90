@@ -24,6 +24,7 @@ module pigs_estimators
   public :: normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau
   public :: normalize_lat, lat_nn_distance, lind_header, write_lind_block, write_lindtau, write_usite
   public :: normalize_sf, sf_columns, write_rhos, write_msdu
+  public :: normalize_cl, clus_header, write_clus_block, write_clus
   public :: normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec
 
   type est_params
@@ -1057,6 +1058,72 @@ contains
     end do
     close (u)
   end subroutine write_msdu
+
+  ! ---- clusters (raw sums of pigs_cl_read of one walker and block, S samples = window slices) -> the block values
+  !   BS(1,s) n(s) = nsize/S            the clusters of size s per slice
+  !   BS(2,s) s n(s)/Np                 the share of the particles in clusters of size s
+  !   BS(3,s) nlarge/S                  the probability that the largest cluster has size s
+  !   BS(4,s) rg2/S                     the sum of Rg^2 over the clusters of size s, per slice (additive over blocks; <Rg^2>(s)
+  !                                     = rg2/nsize, as profiles.normalize_cl has it, is BS(4,s)/BS(1,s))
+  !   BB(1) clusters per slice = sum_s n(s);  BB(2) <smax>/Np = sum_s s nlarge/(S Np);  BB(3) the mean cluster size
+  !   sum s^2 nsize / sum s nsize;  BB(4) bonds per particle = nbond/(S Np)
+  subroutine normalize_cl(Np,S,nsize,nlarge,nbond,rg2,BS,BB)
+    integer, intent(in)    :: Np
+    integer(8), intent(in) :: S,nsize(Np),nlarge(Np),nbond
+    real(8), intent(in)    :: rg2(Np)
+    real(8), intent(out)   :: BS(4,Np),BB(4)
+    integer :: i
+    real(8) :: rs,s1,s2,sl
+    rs = real(S,8)
+    s1 = 0.d0; s2 = 0.d0; sl = 0.d0
+    BB = 0.d0
+    do i=1,Np
+       BS(1,i) = real(nsize(i),8)/rs
+       BS(2,i) = real(i,8)*BS(1,i)/real(Np,8)
+       BS(3,i) = real(nlarge(i),8)/rs
+       BS(4,i) = rg2(i)/rs
+       BB(1) = BB(1)+BS(1,i)
+       sl = sl+real(i,8)*real(nlarge(i),8)
+       s1 = s1+real(i,8)*real(nsize(i),8)
+       s2 = s2+real(i,8)*real(i,8)*real(nsize(i),8)
+    end do
+    BB(2) = sl/(rs*real(Np,8))
+    BB(3) = s2/s1
+    BB(4) = real(nbond,8)/(rs*real(Np,8))
+  end subroutine normalize_cl
+
+  ! first line of clusblk_vpi*.out
+  subroutine clus_header(u,rc,window)
+    integer, intent(in) :: u,window
+    real(8), intent(in) :: rc
+    write (u,'(a,g0,a,i0,a,i0,a)') '# block, clusters per slice (bonds below rc = ',rc,', slices Nb-',window,'..Nb+',window, &
+         & '), <largest cluster>/Np, mean cluster size sum s^2 n(s) / sum s n(s), bonds per particle'
+  end subroutine clus_header
+
+  ! one line of clusblk_vpi*.out
+  subroutine write_clus_block(u,iblock,BB)
+    integer, intent(in) :: u,iblock
+    real(8), intent(in) :: BB(4)
+    write (u,'(20g20.10e3)') real(iblock),BB
+  end subroutine write_clus_block
+
+  ! clus_vpi.out: one line per size s that occurred: s; n(s), s n(s)/Np and P_largest(s), each with its error over the n
+  ! blocks; <Rg^2>(s) = <rg2/S> / <n(s)>, the two means over the blocks, and the error of its numerator over <n(s)>
+  subroutine write_clus(fname,Np,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: Np,n
+    real(8), intent(in) :: av(4,Np),av2(4,Np)
+    integer :: i,j,u
+    real(8) :: a(4),a2(4)
+    open (newunit=u,file=fname)
+    do i=1,Np
+       if (.not. (av(1,i)>0.d0)) cycle
+       a  = av(:,i)/real(n)
+       a2 = av2(:,i)/real(n)
+       write (u,'(i8,20g20.10e3)') i,(a(j),variance(n,a(j),a2(j)),j=1,3),a(4)/a(1),variance(n,a(4),a2(4))/a(1)
+    end do
+    close (u)
+  end subroutine write_clus
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

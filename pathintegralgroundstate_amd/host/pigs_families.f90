@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum, lattice, superfluid.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum, lattice, superfluid, clusters.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -78,6 +78,9 @@ module pigs_families
      real(8), allocatable :: lat_sites(:,:)         ! (dim,lat_nsite)
      logical :: superfluid = .false.
      integer :: sf_ntau = 0, sf_window = -1         ! sf_window < 0: the smallest window that holds the lags
+     logical :: clusters = .false.
+     real(8) :: cl_rc = 0.d0                        ! <= 0: the run's rcut (half the shortest side)
+     integer :: cl_window = -1                      ! < 0: 0
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -451,17 +454,40 @@ module pigs_families
      procedure :: write_average => sf_write_average
   end type sf_family
 
-  integer, parameter :: NFAM = 14
+  ! clusters: the block's raw sums from the device and the normalised block values per size and per block
+  ! (pigs_estimators normalize_cl) behind clus_vpi.out and clusblk_vpi.out
+  type, extends(family) :: cl_family
+     integer :: window = 0
+     real(8) :: rc = 0.d0
+     integer(c_int64_t), allocatable :: nsize(:,:),nlarge(:,:),nbond(:)
+     real(8), allocatable :: rg2(:,:),bs(:,:)
+     real(8) :: bb(4) = 0.d0
+     type(block_series) :: s,sb
+     integer, allocatable :: up(:)
+     integer :: upav = -1
+   contains
+     procedure :: check => cl_check
+     procedure :: banner => cl_banner
+     procedure :: setup => cl_setup
+     procedure :: queue => cl_queue
+     procedure :: read => cl_read_block
+     procedure :: block => cl_block
+     procedure :: average => cl_average
+     procedure :: write_walker => cl_write_walker
+     procedure :: write_average => cl_write_average
+  end type cl_family
+
+  integer, parameter :: NFAM = 15
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12,13,14]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12,13,14]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12,13,14,15]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12,13,14,15]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
   ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
-  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum, 13 lattice, 14 superfluid
+  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum, 13 lattice, 14 superfluid, 15 clusters
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -504,6 +530,7 @@ contains
     if (keys%momentum)        allocate (nk_family :: fs%slot(12)%f)
     if (keys%lattice)         allocate (lat_family :: fs%slot(13)%f)
     if (keys%superfluid)      allocate (sf_family :: fs%slot(14)%f)
+    if (keys%clusters)        allocate (cl_family :: fs%slot(15)%f)
   end subroutine set_create
 
   ! momentum, device-resident sampler: the samples of the step just queued, of all NW walkers
@@ -2257,5 +2284,120 @@ contains
     call write_rhos('rhos_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
     call write_msdu('msdu_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
   end subroutine sf_write_average
+
+  !---------------------------------------------------------------------
+  ! clusters: the connected components of the bond graph r < cl_rc over the slices Nb-cl_window..Nb+cl_window of a periodic
+  ! system -- clus_vpi.out (one line per size s that occurred: n(s), the particle fraction s n(s)/Np, P_largest(s) and
+  ! <Rg^2>(s), each with its error over the blocks) and clusblk_vpi.out (one line per block: clusters per slice,
+  ! <largest cluster>/Np, the mean cluster size, bonds per particle); per walker, and walker-averaged
+
+  subroutine cl_check(f,keys,dim,Nb,trap)
+    class(cl_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('clusters','its bonds are minimum images in the box')
+    if (keys%cl_rc/=keys%cl_rc .or. abs(keys%cl_rc)>huge(1.d0)) then
+       write (0,'(a,g0,a)') ' pigs_vpi: clusters = T: cl_rc = ',keys%cl_rc,' must be finite (left out or <= 0: rcut)'
+       stop 2
+    end if
+    if (.not. (keys%cl_rc>0.d0)) keys%cl_rc = keys%half_side            ! left out: the run's rcut
+    if (.not. (keys%cl_rc<=keys%half_side)) then
+       write (0,'(a,g0,a,g0)') ' pigs_vpi: clusters = T: cl_rc = ',keys%cl_rc, &
+            & ' must be at most half the shortest side of the box = ',keys%half_side
+       stop 2
+    end if
+    if (keys%cl_window<0) keys%cl_window = 0
+    call check_window('clusters','cl',keys%cl_window,Nb)
+    if (.not. cl_bind()) call no_backend('clusters','pigs_cl_init / _accumulate / _read','the cluster labelling runs')
+  end subroutine cl_check
+
+  subroutine cl_banner(f,keys,trap)
+    class(cl_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,g0,a,i0,a,i0,a)', '  > Clusters             : on (bonds below cl_rc = ',keys%cl_rc,', slices Nb-', &
+         & keys%cl_window,'..Nb+',keys%cl_window,': clus_vpi.out, clusblk_vpi.out)'
+  end subroutine cl_banner
+
+  subroutine cl_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(cl_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: w
+    call family_begin(f,run,ep,NW)
+    f%window = max(keys%cl_window,0); f%rc = keys%cl_rc
+    allocate (f%nsize(ep%Np,NW),f%nlarge(ep%Np,NW),f%nbond(NW),f%rg2(ep%Np,NW),f%bs(4,ep%Np))
+    call series_create(f%s,4*ep%Np,NW,nvec)
+    call series_create(f%sb,4,NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(cl_init(ctx,real(f%rc,c_double),int(f%window,c_int32_t)),'pigs_cl_init')
+    allocate (f%up(NW))
+    do w=1,NW
+       open (newunit=f%up(w),file='clusblk_vpi'//trim(run%suffix(w))//'.out')
+       call clus_header(f%up(w),f%rc,f%window)
+    end do
+    if (run%averages) then
+       open (newunit=f%upav,file='clusblk_vpi.out')
+       call clus_header(f%upav,f%rc,f%window)
+    end if
+  end subroutine cl_setup
+
+  subroutine cl_queue(f,ctx,nd,wl)
+    class(cl_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(cl_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_cl_accumulate')
+  end subroutine cl_queue
+
+  subroutine cl_read_block(f,ctx)
+    class(cl_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(cl_read(ctx,f%nsize,f%nlarge,f%nbond,f%smp,f%rg2,f%reset),'pigs_cl_read')
+  end subroutine cl_read_block
+
+  subroutine cl_block(f,w,info,vec)
+    class(cl_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_cl(f%ep%Np,int(f%smp(w),8),int(f%nsize(:,w),8),int(f%nlarge(:,w),8),int(f%nbond(w),8),f%rg2(:,w),f%bs,f%bb)
+    call series_add(f%s,w,reshape(f%bs,[size(f%bs)]),vec)
+    call series_add(f%sb,w,f%bb,vec)
+    call count_add(f%cnt,vec)
+    call write_clus_block(f%up(w),info%iblock,f%bb)
+  end subroutine cl_block
+
+  subroutine cl_average(f,info,vec)
+    class(cl_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%s,vec,nall)
+       call series_average(f%sb,vec,nall)
+       if (info%ndall>0) call write_clus_block(f%upav,info%iblock,f%sb%mean)
+    end if
+  end subroutine cl_average
+
+  subroutine cl_write_walker(f,suffix,w,nblocks)
+    class(cl_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_clus('clus_vpi'//trim(suffix)//'.out',f%ep%Np,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+    close (f%up(w))
+  end subroutine cl_write_walker
+
+  subroutine cl_write_average(f)
+    class(cl_family), intent(inout) :: f
+    call write_clus('clus_vpi.out',f%ep%Np,f%cnt%nav,f%s%asum,f%s%asq)
+    close (f%upav)
+  end subroutine cl_write_average
 
 end module pigs_families

@@ -13,6 +13,7 @@ module pigs_host_hooks
        & normalize_atm, atm_window_mean, v3_header, write_v3_block, write_v3tau, &
        & normalize_lat, lind_header, write_lind_block, write_lindtau, write_usite, &
        & normalize_sf, sf_columns, write_rhos, write_msdu, &
+       & normalize_cl, clus_header, write_clus_block, write_clus, &
        & normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec, write_sqshell, write_grvec, &
        & sqv_shells, sqv_shell_means
 
@@ -360,6 +361,33 @@ contains
     call write_rhos(cstring(fr),dim,Ntau,dt,nblk,sr%sum(:,1),sr%sq(:,1))
     call write_msdu(cstring(fm),dim,Ntau,dt,nblk,sr%sum(:,1),sr%sq(:,1))
   end subroutine hs_sf_files
+
+  ! The cluster normalisation and writers of the front end on given sums: nblk blocks of one walker, the arrays of
+  ! pigs_cl_read per block and S samples per block -> fc (clus_vpi.out) and fb (clusblk_vpi.out), the means and errors over
+  ! the blocks through a block_series, as the front end takes them (names: C strings)
+  subroutine hs_cl_files(Np,window,rc,nblk,S,nsize,nlarge,nbond,rg2,fc,fb) bind(C,name='hs_cl_files')
+    use pigs_block_stats, only: block_series,series_create,series_add
+    integer(c_int), value :: Np,window,nblk
+    real(c_double), value :: rc
+    integer(c_int64_t), intent(in) :: S(nblk),nsize(Np,nblk),nlarge(Np,nblk),nbond(nblk)
+    real(c_double), intent(in)     :: rg2(Np,nblk)
+    character(kind=c_char), intent(in) :: fc(*),fb(*)
+    real(8), allocatable :: BS(:,:)
+    real(8) :: BB(4),none(1)
+    type(block_series) :: sr
+    integer :: ib,u
+    allocate (BS(4,Np))
+    call series_create(sr,4*Np,1)
+    open (newunit=u,file=cstring(fb))
+    call clus_header(u,rc,window)
+    do ib=1,nblk
+       call normalize_cl(Np,int(S(ib),8),int(nsize(:,ib),8),int(nlarge(:,ib),8),int(nbond(ib),8),rg2(:,ib),BS,BB)
+       call series_add(sr,1,reshape(BS,[size(BS)]),none)
+       call write_clus_block(u,ib,BB)
+    end do
+    close (u)
+    call write_clus(cstring(fc),Np,nblk,sr%sum(:,1),sr%sq(:,1))
+  end subroutine hs_cl_files
 
   ! a C string as a Fortran one
   function cstring(c) result(f)

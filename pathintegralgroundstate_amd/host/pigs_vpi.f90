@@ -84,6 +84,12 @@
 ! per lag l >= 1: tau, then value and error of Dcm per axis, of rhos = Dcm/(2 lambda tau) per axis (lambda = 1/2) and of
 ! their mean; msdu_vpi.out, one line per lag: tau, then value and error of the unfolded <dx_k^2> per axis, of their sum and
 ! of the cross term Dcm - <dx_k^2> per axis)
+! (clusters = T, periodic systems only: the connected components of the bond graph r_ij < cl_rc (minimum image; left out or
+! <= 0: rcut; at most half the shortest side) of every slice Nb-cl_window..Nb+cl_window (default 0), labelled on the GPU --
+! clus_vpi.out, one line per cluster size s that occurred: s, then value and error over the blocks of n(s), the clusters of
+! size s per slice, of the particle fraction s n(s)/Np and of P_largest(s), then <Rg^2>(s) = <sum of Rg^2 per slice> / <n(s)>
+! and the error of its numerator over <n(s)>; clusblk_vpi.out, one line per block: the block, clusters per slice, <largest
+! cluster>/Np, the mean cluster size sum s^2 n(s) / sum s n(s), bonds per particle)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -146,6 +152,9 @@ program pigs_vpi
   real (kind=8)     :: lat_rmax
   logical           :: superfluid
   integer           :: sf_ntau,sf_window
+  logical           :: clusters
+  real (kind=8)     :: cl_rc
+  integer           :: cl_window
   integer           :: nk_nmax,nk_nbin
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
@@ -172,7 +181,8 @@ program pigs_vpi
        &             three_body,atm_nu,atm_rc,atm_window, &
        &             momentum,nk_nmax,nk_nbin, &
        &             lattice,lat_nbin,lat_rmax,lat_window,lat_cm, &
-       &             superfluid,sf_ntau,sf_window
+       &             superfluid,sf_ntau,sf_window, &
+       &             clusters,cl_rc,cl_window
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -207,6 +217,7 @@ program pigs_vpi
   momentum = .false.; nk_nmax = 8; nk_nbin = 32
   lattice = .false.; lat_nbin = 0; lat_rmax = 0.d0; lat_window = -1; lat_cm = .true.
   superfluid = .false.; sf_ntau = 0; sf_window = -1
+  clusters = .false.; cl_rc = 0.d0; cl_window = -1
   three_body = .false.; atm_nu = -huge(1.d0); atm_rc = 0.d0; atm_window = -1        ! (atm_nu: a value nobody gives, left out -> 1)
 
   read (5,nml=system,iostat=ios);  rewind (5)
@@ -285,7 +296,8 @@ program pigs_vpi
        & atm_rc=atm_rc,atm_window=atm_window, &
        & momentum=momentum,nk_nmax=nk_nmax,nk_nbin=nk_nbin,cworm=CWorm,nobdm=Nobdm, &
        & lattice=lattice,lat_nbin=lat_nbin,lat_rmax=lat_rmax,lat_window=lat_window,lat_cm=lat_cm,nbin_run=Nbin,box=Lbox, &
-       & superfluid=superfluid,sf_ntau=sf_ntau,sf_window=sf_window)
+       & superfluid=superfluid,sf_ntau=sf_ntau,sf_window=sf_window, &
+       & clusters=clusters,cl_rc=cl_rc,cl_window=cl_window)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 

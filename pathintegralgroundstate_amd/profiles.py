@@ -97,6 +97,11 @@ n_pairs(l) = 2 window + 1 - l, S = samples, tau_l = l dt and lam = hbar^2/2m (1/
   msd[l, k]  = D / (S n_pairs Np)        the single-particle displacement per axis, with no half-box limit
   cross      = Dcm - msd                 sum_{i != j} <dx_i dx_j> / Np
 and rho_s,k / rho is the slope of Dcm over tau at large tau, divided by 2 lam (superfluid_fraction).
+Clusters (normalize_cl, PigsContext.cl_read, pigs_cl_*): i and j are bonded iff 0 < r_ij^2 < rc^2 and a cluster is a
+connected component of that graph in one window slice; with S = samples (slices) and s = 1..Np:
+  n(s) = nsize / S,   fraction(s) = s n(s) / Np,   P_largest(s) = nlarge / S,   <Rg^2>(s) = rg2 / nsize (NaN: no such cluster)
+  clusters per slice = sum_s n(s),   <smax>/Np = sum_s s nlarge / (S Np),   S_mean = sum s^2 nsize / sum s nsize
+  bonds per particle = nbond / (S Np)
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -592,6 +597,33 @@ def superfluid_fraction(tau, Dcm_k, tmin, lam=0.5):
     res = y - (ym + slope * (t - tm))
     err = math.sqrt(float((res * res).sum()) / (n - 2) / sxx) if n > 2 else float("nan")
     return slope / (2.0 * float(lam)), err / (2.0 * float(lam))
+
+
+def normalize_cl(got, Np, summed=False):
+    """got: the dict of cl_read (nsize, nlarge, rg2 [W, Np], nbond, samples [W]) or one walker's slice of it; summed:
+    add the walkers' sums first.  With S = samples (window slices) and s = 1..Np, returns a dict:
+    s [Np]; n [.., Np] = nsize / S, the clusters of size s per sample; fraction [.., Np] = s n(s) / Np, the share of the
+    particles that sit in clusters of size s; p_largest [.., Np] = nlarge / S; rg2 [.., Np] = rg2 / nsize, NaN where
+    n(s) = 0; n_clusters [..] = sum_s n(s); smax [..] = sum_s s nlarge / (S Np), the mean largest cluster over Np;
+    mean_size [..] = sum s^2 nsize / sum s nsize; bonds [..] = nbond / (S Np), the bonds per particle.  A walker without
+    samples gives NaN."""
+    ns = np.asarray(got["nsize"], dtype=np.float64)
+    nl = np.asarray(got["nlarge"], dtype=np.float64)
+    rg = np.asarray(got["rg2"], dtype=np.float64)
+    nb = np.asarray(got["nbond"], dtype=np.float64)
+    S = np.asarray(got["samples"], dtype=np.float64)
+    if ns.ndim < 1 or ns.shape[-1] != int(Np) or nl.shape != ns.shape or rg.shape != ns.shape or \
+            S.shape != ns.shape[:-1] or nb.shape != S.shape:
+        raise ValueError("the arrays of cl_read do not fit each other or Np")
+    if summed and ns.ndim > 1:
+        ns, nl, rg, nb, S = ns.sum(axis=0), nl.sum(axis=0), rg.sum(axis=0), nb.sum(axis=0), S.sum(axis=0)
+    s = np.arange(1, int(Np) + 1, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = ns / S[..., None]
+        return {"s": s, "n": n, "fraction": s * n / float(Np), "p_largest": nl / S[..., None],
+                "rg2": np.where(ns > 0, rg / ns, np.nan), "n_clusters": n.sum(axis=-1),
+                "smax": (s * nl).sum(axis=-1) / (S * float(Np)),
+                "mean_size": (s * s * ns).sum(axis=-1) / (s * ns).sum(axis=-1), "bonds": nb / (S * float(Np))}
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
