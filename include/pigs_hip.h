@@ -896,6 +896,74 @@ int pigs_cl_read(pigs_ctx *ctx, int64_t *nsize, int64_t *nlarge, int64_t *nbond,
  * part of the result.  Synchronises the context.  PIGS_ERR_ARG before pigs_cl_init. */
 int pigs_cl_sweeps(pigs_ctx *ctx, int32_t *max_sweeps);
 
+/* ---- wrapping clusters, their true extent and cluster persistence along tau (new: pigs_cl_* above cannot tell a cluster
+ * that wraps the box, its rg2 is no extent beyond half a box side, and it never compares the clusters of two slices) -----
+ * Periodic systems only.  Everything is per slice of the window Nb-window .. Nb+window of a walker.
+ * Bonds and clusters are pigs_cl_*'s.  Take d = x(i) - x(j), folded once per axis by min_image, with r2 summed left to
+ *   right.  A bond exists iff 0 < r2 < rc2.  A cluster is a connected component, labelled by its smallest index.
+ * Fold number.  n_ij[k] describes the fold min_image applied to d[k]: +1 where v - L was taken, -1 where v + L was taken,
+ *   0 where none was.  n_ji = -n_ij, because d == +-L/2 folds in neither direction.  For a bond every |folded d[k]| < rc
+ *   <= L_k/2.
+ * Wrapping.  A cluster wraps along axis k iff it contains a closed walk of bonds whose fold numbers add up to a non-zero
+ *   value along k.
+ *   Its wrap mask has bit k set for every such axis.  Mask 0 means finite.
+ *   The definition is free of any spanning tree.
+ *   Equivalently, choose image numbers m_i (integers per axis, m_root = 0) with m_i = m_j + n_ij along the edges of any
+ *   spanning tree.  Bit k is set iff some bond of the cluster has m_i[k] - m_j[k] != n_ij[k].
+ *   For a finite cluster the m_i are unique.
+ * Unfolded separation in a finite cluster: du[k] = (x_i[k] - x_j[k]) - c*L[k] with c = (double)(m_i[k] - m_j[k]).
+ *   The product comes first, then the subtraction, nothing fused.
+ *   ru2 is summed left to right from 0.0.
+ *   With c in {0, +-1} this has min_image's bits.  On a cluster whose pairs all lie within half the box, g below therefore
+ *   equals pigs_cl's g bit for bit.
+ * Sums per walker.  Every integer sum is int64 and must equal any correct algorithm's:
+ *   nwrap[8]   (index = mask)  clusters with that wrap mask
+ *   mwrap[8]   (index = mask)  particles in clusters with that wrap mask
+ *   swrap[8]   (index = mask)  slices whose OR over all cluster masks is that mask
+ *   nfin[Np]   (index s-1)     finite clusters of size s
+ *   samples                    slices
+ *   rg2u[Np]   (double)        over the finite clusters of size s, the sum of g = sum_{i<j} ru2 / s^2
+ *   rg2u is summed in pigs_cl's fixed order: t_i over j ascending, T over the members ascending, the roots ascending, the
+ *   slices ascending.  Wrapping clusters contribute nothing to nfin or rg2u.
+ * Persistence.  For the lags l = 0..ntau and every origin a with a and a+l both in the window, call i<j "together in
+ *   slice a" when they carry the same label there.  Each of the following has shape [ntau+1]:
+ *   first[l]  += pairs together in a.
+ *   second[l] += pairs together in a+l.
+ *   both[l]   += pairs together in both.
+ *   norig[l]  += 1.
+ *   At l = 0 the three pair counts are sum_clusters s(s-1)/2.
+ * Determinism.  As pigs_cl_*: the same worldline gives the same counts and the same bits of rg2u whatever the walker list,
+ * its order, the launch split, the scratch budget or the number of walkers of the context.  A walker listed twice counts
+ * twice, in two launches.
+ * Caller's divisions.  profiles.normalize_pc(got, Np) returns the wrapping probabilities per axis, for any and for all
+ * axes, the strength P_inf, the finite n(s)/Np, the mean finite cluster size, <Rg^2>(s) of the finite clusters, the
+ * persistence C(l) = both/first and the Jaccard index both/(first + second - both); NaN where a denominator is zero.
+ * Kernel.  pigs_cl's labelling; then image numbers spread from every root over the bonds, sweep by sweep, until a vote
+ * finds a sweep that assigned nobody (at most Np - 1 sweeps, for a chain), the wrap check over the bonds, and a second
+ * kernel that counts the pairs per (walker, origin).  Limits: PIGS_CL_NP_MAX particles.
+ * Scratch.  The per-slice sums and the labels of one launch, 12 (2 window + 1) Np bytes per walker, sit in device memory
+ * between the kernels of a launch.  pigs_pc_init allocates min(n_walkers, 256, what fits 256 MiB) walkers of it, one at the
+ * least, and pigs_pc_accumulate puts no more walkers into a launch; pigs_set_tuning "pc_scratch_mib" (1..2048, read by the
+ * next pigs_pc_init) sets another budget.  The bits do not depend on it.
+ *
+ * pigs_pc_init allocates and zeroes the sums (again: resizes and zeroes).  PIGS_ERR_UNSUPPORTED on a trapped context;
+ * PIGS_ERR_ARG for rc not finite or <= 0, rc beyond half the shortest side, window < 0, window > Nb, ntau < 0,
+ * ntau > 2 window, Np > PIGS_CL_NP_MAX, or sums beyond 2 GiB.  It works beside an initialised pigs_cl_* of the context. */
+int pigs_pc_np_max(void);                /* PIGS_CL_NP_MAX of the library that is loaded */
+int pigs_pc_init(pigs_ctx *ctx, double rc, int32_t window, int32_t ntau);
+/* pigs_cl_accumulate's contract: adds every window slice of walkers[0..n) (NULL: 0..n-1; a walker listed twice counts
+ * twice), queued on the context's stream with no upload and no host synchronisation, at most 256 walkers per launch.
+ * PIGS_ERR_ARG before pigs_pc_init, for n < 0 or for a walker out of range. */
+int pigs_pc_accumulate(pigs_ctx *ctx, int32_t n, const int32_t *walkers);
+/* All walkers' nwrap, mwrap, swrap [n_walkers][8], nfin [n_walkers][Np], samples [n_walkers] (int64), rg2u [n_walkers][Np]
+ * (doubles) and first, second, both, norig [n_walkers][ntau+1] (int64); then zeroes those of the walkers w with
+ * reset[w] != 0 (reset == NULL: none).  Synchronises the context.  PIGS_ERR_ARG before pigs_pc_init. */
+int pigs_pc_read(pigs_ctx *ctx, int64_t *nwrap, int64_t *mwrap, int64_t *swrap, int64_t *nfin, int64_t *samples, double *rg2u,
+                 int64_t *first, int64_t *second, int64_t *both, int64_t *norig, const int32_t *reset);
+/* The largest numbers of labelling sweeps and of image-number sweeps that any (walker, slice) needed since pigs_pc_init: a
+ * report for benchmarks, no part of the result.  Synchronises the context.  PIGS_ERR_ARG before pigs_pc_init. */
+int pigs_pc_sweeps(pigs_ctx *ctx, int32_t *label_sweeps, int32_t *image_sweeps);
+
 /* ---- bond-orientational order of a PERIODIC system in 2D or 3D, over a slice window (new: every family above is a
  * density correlation; this one tells fcc from hcp from bcc, a hexatic from a liquid, and gives a per-particle measure)
  * Scope: periodic contexts with dim = 2 or 3.  pigs_bop_init returns PIGS_ERR_UNSUPPORTED on a trapped context and for

@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "pigs_lat_init", "pigs_lat_accumulate", "pigs_lat_read",
     "pigs_sf_init", "pigs_sf_accumulate", "pigs_sf_read",
     "pigs_cl_np_max", "pigs_cl_init", "pigs_cl_accumulate", "pigs_cl_read", "pigs_cl_sweeps",
+    "pigs_pc_np_max", "pigs_pc_init", "pigs_pc_accumulate", "pigs_pc_read", "pigs_pc_sweeps",
 ]
 
 
@@ -196,6 +197,11 @@ def load_library(path=LIB_PATH):
     L.pigs_cl_accumulate.argtypes = [vp, C.c_int32, _ip]
     L.pigs_cl_read.argtypes = [vp, _lp, _lp, _lp, _lp, _dp, _ip]
     L.pigs_cl_sweeps.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.pigs_pc_np_max.argtypes = []
+    L.pigs_pc_init.argtypes = [vp, C.c_double, C.c_int32, C.c_int32]
+    L.pigs_pc_accumulate.argtypes = [vp, C.c_int32, _ip]
+    L.pigs_pc_read.argtypes = [vp, _lp, _lp, _lp, _lp, _lp, _dp, _lp, _lp, _lp, _lp, _ip]
+    L.pigs_pc_sweeps.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.pigs_set_tuning.argtypes = [vp, C.c_char_p, C.c_int32]
     L.pigs_selftest_fastmath.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
     L.pigs_selftest_stream_read.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -975,6 +981,47 @@ class PigsContext:
         v = C.c_int32(0)
         _chk(self.L, self.L.pigs_cl_sweeps(self.h, C.byref(v)), "pigs_cl_sweeps")
         return int(v.value)
+
+    # ---- wrapping clusters, the finite clusters' unfolded Rg^2 and cluster persistence along tau (pigs_pc_*)
+    def pc_init(self, rc, window=0, ntau=0):
+        """Allocate and zero the percolation sums of a periodic system: cl_init's bonds and clusters over the slices
+        Nb-window..Nb+window, and the persistence lags 0..ntau (at most 2 window).  At most CL_NP_MAX particles.  Works
+        beside cl_init on the same context.  Calling it again resizes and zeroes."""
+        if self.cfg.Np > CL_NP_MAX:
+            raise PigsError(f"pc_init: Np={self.cfg.Np} passes the {CL_NP_MAX} particles a workgroup labels")
+        _chk(self.L, self.L.pigs_pc_init(self.h, float(rc), int(window), int(ntau)), "pigs_pc_init")
+        self._pc = (int(window), int(ntau))
+
+    def pc_accumulate(self, walkers=None):
+        """Queue one sample of every window slice of `walkers` (None: all) on the context's stream; does not wait."""
+        self._accumulate("pigs_pc_accumulate", walkers)
+
+    def pc_read(self, reset=None):
+        """dict of the raw sums: nwrap, mwrap, swrap [W, 8] (int64, index = wrap mask: clusters, their particles, and slices
+        by the OR of their clusters' masks), nfin [W, Np] (int64: finite clusters of size s at s - 1), samples [W] (int64:
+        slices), rg2u [W, Np] (float64: the sum of the finite clusters' unfolded Rg^2 per size), first, second, both, norig
+        [W, ntau + 1] (int64: pairs together in slice a, in a + l, in both, and the origins per lag); and "window", "ntau".
+        profiles.normalize_pc divides them.  reset: None, True (all walkers) or a per-walker mask of walkers whose sums are
+        zeroed after the copy."""
+        if getattr(self, "_pc", None) is None:
+            raise PigsError("pc_read: pc_init first")
+        W, Np, nl = self.n_walkers, self.cfg.Np, self._pc[1] + 1
+        out = {k: np.zeros((W, 8), np.int64) for k in ("nwrap", "mwrap", "swrap")}
+        out.update({"nfin": np.zeros((W, Np), np.int64), "samples": np.zeros(W, np.int64), "rg2u": np.zeros((W, Np))})
+        out.update({k: np.zeros((W, nl), np.int64) for k in ("first", "second", "both", "norig")})
+        mask = self._reset_mask(reset)
+        _chk(self.L, self.L.pigs_pc_read(self.h, _l(out["nwrap"]), _l(out["mwrap"]), _l(out["swrap"]), _l(out["nfin"]),
+                                         _l(out["samples"]), _d(out["rg2u"]), _l(out["first"]), _l(out["second"]),
+                                         _l(out["both"]), _l(out["norig"]), mask), "pigs_pc_read")
+        out["window"], out["ntau"] = self._pc
+        return out
+
+    def pc_sweeps(self):
+        """(labelling sweeps, image-number sweeps): the largest counts any (walker, slice) needed since pc_init (a report,
+        no result)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _chk(self.L, self.L.pigs_pc_sweeps(self.h, C.byref(a), C.byref(b)), "pigs_pc_sweeps")
+        return int(a.value), int(b.value)
 
     # ---- K5
     def commit_beads(self, walker, ip, ib, x):

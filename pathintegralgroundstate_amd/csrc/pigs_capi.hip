@@ -310,6 +310,19 @@ struct pigs_ctx {
     int         cl_slots = 0;               // walkers per launch: what the scratch holds
     double      cl_rc2 = 0.0;
     int         cl_scratch_mib = kClScratchMiB;   // pigs_set_tuning "cl_scratch_mib": the budget of the scratch at the next pigs_cl_init
+    // wrapping clusters and cluster persistence over a slice window (pigs_pc_*): per walker nwrap, mwrap, swrap [8], nfin and
+    // rg2u [Np], samples, and first, second, both, norig [ntau + 1]; the per-slice sums of g and the labels of one launch
+    // ([pc_slots][2 window + 1][Np] each); the largest labelling and image sweep counts so far
+    DevBuf<unsigned long long> d_pc_nwrap, d_pc_mwrap, d_pc_swrap, d_pc_nfin, d_pc_samples, d_pc_first, d_pc_second, d_pc_both,
+                               d_pc_norig;
+    DevBuf<double> d_pc_rg2u, d_pc_scratch;
+    DevBuf<int> d_pc_labels;
+    DevBuf<unsigned int> d_pc_sweeps;
+    bool        pc_ready = false;           // pigs_pc_init called
+    int         pc_window = 0, pc_ntau = 0;
+    int         pc_slots = 0;               // walkers per launch: what the two scratches hold
+    double      pc_rc2 = 0.0;
+    int         pc_scratch_mib = kPcScratchMiB;   // pigs_set_tuning "pc_scratch_mib": the budget of the scratches at the next pigs_pc_init
 };
 
 // live contexts per device of this process: the TranslateChain helpers (pigs_cm.hip) assume that the walkers of ONE
@@ -546,6 +559,11 @@ int pigs_set_tuning(pigs_ctx *c, const char *key, int32_t value)
     if (!strcmp(key, "cl_scratch_mib")) {       // MiB the per-slice sums of one pigs_cl_accumulate launch may take; read by pigs_cl_init
         if (value < 1 || value > 2048) return fail(PIGS_ERR_ARG, "cl_scratch_mib=%d", value);
         c->cl_scratch_mib = value;
+        return PIGS_OK;
+    }
+    if (!strcmp(key, "pc_scratch_mib")) {       // MiB the per-slice sums and labels of one pigs_pc_accumulate launch may take; read by pigs_pc_init
+        if (value < 1 || value > 2048) return fail(PIGS_ERR_ARG, "pc_scratch_mib=%d", value);
+        c->pc_scratch_mib = value;
         return PIGS_OK;
     }
     if (!strcmp(key, "sweep_threads")) {
@@ -2480,6 +2498,94 @@ int pigs_cl_sweeps(pigs_ctx *c, int32_t *max_sweeps)
     HIPCHK(hipMemcpyAsync(&v, c->d_cl_sweeps.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
     SYNC_CHECKED(c);
     *max_sweeps = (int32_t)v;
+    return PIGS_OK;
+}
+
+// ---- wrapping clusters, their unfolded extent and the persistence of clusters along tau -------------
+// Integer counts, the finite clusters' sums of Rg^2 and the pair counts per lag (pigs_pc.hip), accumulated on the device and
+// read per block.  The per-slice sums and the labels of a launch sit in two scratches whose size pigs_pc_init bounds; the
+// launches are cut to the walkers they hold.
+int pigs_pc_np_max(void) { return kClNpMax; }
+
+int pigs_pc_init(pigs_ctx *c, double rc, int32_t window, int32_t ntau)
+{
+    int st = check_ctx(c); if (st) return st;
+    st = check_cm(c); if (st) return st;
+    if (c->P.trap) return fail(PIGS_ERR_UNSUPPORTED, "wrapping clusters are defined for periodic systems only (bonds are minimum images)");
+    bool rc_ok = std::isfinite(rc) && rc > 0.0;
+    for (int k = 0; k < c->P.dim; ++k) rc_ok = rc_ok && rc <= c->P.LboxHalf[k];
+    if (!rc_ok || window < 0 || window > c->P.Nb || ntau < 0 || ntau > 2 * window)
+        return fail(PIGS_ERR_ARG, "pigs_pc_init: rc=%g (0 < rc <= half the shortest side) window=%d (0..Nb=%d) ntau=%d (0..2 window)",
+                    rc, window, c->P.Nb, ntau);
+    if (c->P.Np > kClNpMax || pc_lds_bytes(c->P.dim, c->P.Np) > kClLdsBudget)
+        return fail(PIGS_ERR_ARG, "pigs_pc_init: Np=%d passes the %d particles a workgroup labels in LDS", c->P.Np, kClNpMax);
+    const size_t W = (size_t)c->n_walkers, np = (size_t)c->P.Np, nl = (size_t)ntau + 1;
+    if ((double)W * (2.0 * (double)np + 25.0 + 4.0 * (double)nl) * 8.0 > 2147483648.0)
+        return fail(PIGS_ERR_ARG, "pigs_pc_init: %zu walkers x (2 x %d + 25 + 4 x %zu) sums pass 2 GiB", W, c->P.Np, nl);
+    const size_t per = (2 * (size_t)window + 1) * np;
+    const size_t fit = ((size_t)c->pc_scratch_mib << 20) / pc_slot_bytes(c->P.Np, window);
+    const size_t slots = std::max<size_t>(1, std::min({W, (size_t)kWalkerListMax, fit}));
+    st = init_begin(c, c->pc_ready); if (st) return st;
+    HIPCHK(alloc_zeroed(c, c->d_pc_nwrap, W * 8));
+    HIPCHK(alloc_zeroed(c, c->d_pc_mwrap, W * 8));
+    HIPCHK(alloc_zeroed(c, c->d_pc_swrap, W * 8));
+    HIPCHK(alloc_zeroed(c, c->d_pc_nfin, W * np));
+    HIPCHK(alloc_zeroed(c, c->d_pc_samples, W));
+    HIPCHK(alloc_zeroed(c, c->d_pc_first, W * nl));
+    HIPCHK(alloc_zeroed(c, c->d_pc_second, W * nl));
+    HIPCHK(alloc_zeroed(c, c->d_pc_both, W * nl));
+    HIPCHK(alloc_zeroed(c, c->d_pc_norig, W * nl));
+    HIPCHK(alloc_zeroed(c, c->d_pc_rg2u, W * np));
+    HIPCHK(alloc_zeroed(c, c->d_pc_scratch, slots * per));
+    HIPCHK(alloc_zeroed(c, c->d_pc_labels, slots * per));
+    HIPCHK(alloc_zeroed(c, c->d_pc_sweeps, 2));
+    SYNC_CHECKED(c);
+    c->pc_window = window; c->pc_ntau = ntau; c->pc_slots = (int)slots; c->pc_rc2 = rc * rc;
+    c->pc_ready = true;
+    return PIGS_OK;
+}
+
+int pigs_pc_accumulate(pigs_ctx *c, int32_t n, const int32_t *walkers)
+{
+    int st = check_ctx(c); if (st) return st;
+    st = check_cm(c); if (st) return st;
+    if (!c->pc_ready) return fail(PIGS_ERR_ARG, "pigs_pc_init first");
+    if (n < 0) return fail(PIGS_ERR_ARG, "n=%d", n);
+    std::vector<int32_t> sw;
+    st = walker_list(c, n, walkers, sw); if (st) return st;
+    const PcSums sums{c->d_pc_nwrap.p, c->d_pc_mwrap.p, c->d_pc_swrap.p, c->d_pc_nfin.p, c->d_pc_samples.p, c->d_pc_first.p,
+                      c->d_pc_second.p, c->d_pc_both.p, c->d_pc_norig.p, c->d_pc_rg2u.p};
+    // one thread owns an element of rg2u per launch; a launch's walkers fit the scratches
+    return each_launch(c, sw, walkers, true, c->pc_slots, "launch_pc", [&](int m, const WalkerList &L) {
+        return launch_pc(c->P, c->d_paths.p, m, L, c->pc_window, c->pc_ntau, c->pc_rc2, c->d_pc_scratch.p, c->d_pc_labels.p, sums,
+                         c->d_pc_sweeps.p, c->stream);
+    });
+}
+
+int pigs_pc_read(pigs_ctx *c, int64_t *nwrap, int64_t *mwrap, int64_t *swrap, int64_t *nfin, int64_t *samples, double *rg2u,
+                 int64_t *first, int64_t *second, int64_t *both, int64_t *norig, const int32_t *reset)
+{
+    int st = check_ctx(c); if (st) return st;
+    if (!c->pc_ready) return fail(PIGS_ERR_ARG, "pigs_pc_init first");
+    if (!nwrap || !mwrap || !swrap || !nfin || !samples || !rg2u || !first || !second || !both || !norig)
+        return fail(PIGS_ERR_ARG, "null output");
+    const size_t np = (size_t)c->P.Np, nl = (size_t)c->pc_ntau + 1;
+    return read_and_reset(c, {{c->d_pc_nwrap.p, 8, nwrap}, {c->d_pc_mwrap.p, 8, mwrap}, {c->d_pc_swrap.p, 8, swrap},
+                              {c->d_pc_nfin.p, np, nfin}, {c->d_pc_samples.p, 1, samples}, {c->d_pc_rg2u.p, np, rg2u},
+                              {c->d_pc_first.p, nl, first}, {c->d_pc_second.p, nl, second}, {c->d_pc_both.p, nl, both},
+                              {c->d_pc_norig.p, nl, norig}}, reset);
+}
+
+int pigs_pc_sweeps(pigs_ctx *c, int32_t *label_sweeps, int32_t *image_sweeps)
+{
+    int st = check_ctx(c); if (st) return st;
+    if (!c->pc_ready) return fail(PIGS_ERR_ARG, "pigs_pc_init first");
+    if (!label_sweeps || !image_sweeps) return fail(PIGS_ERR_ARG, "null output");
+    unsigned int v[2] = {0u, 0u};
+    HIPCHK(hipMemcpyAsync(v, c->d_pc_sweeps.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    SYNC_CHECKED(c);
+    *label_sweeps = (int32_t)v[0];
+    *image_sweeps = (int32_t)v[1];
     return PIGS_OK;
 }
 

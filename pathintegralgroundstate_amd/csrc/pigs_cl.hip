@@ -10,7 +10,8 @@
 //     bit mask (so the particle itself, a coincident partner and a non-finite r2 are no bonds).  The bits with j > i are
 //     the slice's bonds.  ADJ (Np <= kClAdjNpMax): the masks are kept as the particle's bit row of ceil(Np/64) u64 in LDS
 //     and the sweeps below read the rows; otherwise every sweep computes the distances again.
-//   * Labelling.  label[i] = i; then sweeps of (hook) m = min(label[i], label[j] of every bonded j), and where m is
+//   * Labelling (label_components of pigs_cl_device.h, shared with k_pc of pigs_pc.hip).  label[i] = i; then sweeps
+//     of (hook) m = min(label[i], label[j] of every bonded j), and where m is
 //     smaller, atomicMin of m into label[i] and into label[label[i]]; barrier; (jump) label[i] = label[label[i]]; until
 //     a workgroup-wide vote (__syncthreads_or) says that a whole sweep changed nothing.  A label is always the index of a
 //     particle of the same component and never above the particle's own index, and labels only fall, so concurrent reads
@@ -41,39 +42,11 @@
 #include "pigs_kernels.h"
 #include "pigs_launch.h"
 #include "pigs_slice_device.h"
+#include "pigs_cl_device.h"
 
 namespace pigs {
 
 namespace {
-
-__device__ __forceinline__ int lds_load(const int *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// the bonds of particle i (at xi) among the partners j0 .. j0 + mj - 1 of the staged slice, bit jj for partner j0 + jj
-template <int DIM>
-__device__ __forceinline__ unsigned long long bond_mask(const DevParams &P, const double *sx, int Np, const double (&xi)[DIM],
-                                                        int j0, int mj, double rc2)
-{
-    unsigned long long bonds = 0ull;
-    for (int jj = 0; jj < mj; ++jj) {
-        double d[DIM];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) d[k] = xi[k] - sx[k * Np + j0 + jj];
-        const double r2 = min_image<DIM>(d, P);
-        if (r2 > 0.0 && r2 < rc2) bonds |= 1ull << jj;                 // (j == i: r2 is 0 or NaN)
-    }
-    return bonds;
-}
-
-// the bits of a mask over the partners j0 .. j0 + 63 that lie above particle i
-__device__ __forceinline__ unsigned long long above(int i, int j0)
-{
-    if (i < j0) return ~0ull;
-    if (i >= j0 + 63) return 0ull;
-    return ~0ull << (i - j0 + 1);
-}
 
 // scratch: [slot][2 window + 1][Np]; nsize, nlarge: [walker][Np]
 template <int DIM, bool ADJ>
@@ -120,46 +93,7 @@ __global__ __launch_bounds__(kClThreads) void k_cl(
     }
 
     // ---- labelling: hook and pointer jump until a whole sweep changes nothing
-    unsigned int nsweep = 0u;
-    for (;;) {
-        int changed = 0;
-        for (int i = tid; i < Np; i += kClThreads) {
-            double xi[DIM];
-#pragma unroll
-            for (int k = 0; k < DIM; ++k) xi[k] = sx[k * Np + i];
-            const int li = lds_load(&label[i]);
-            int m = li;
-            for (int j0 = 0, b = 0; j0 < Np; j0 += 64, ++b) {
-                unsigned long long bonds;
-                if (ADJ) bonds = adj[(size_t)i * nw + b];
-                else {
-                    bonds = bond_mask<DIM>(P, sx, Np, xi, j0, min(64, Np - j0), rc2);
-                    if (nsweep == 0u) nb += (unsigned int)__popcll(bonds & above(i, j0));
-                }
-                while (bonds) {
-                    const int jj = __ffsll((long long)bonds) - 1;
-                    bonds &= bonds - 1ull;
-                    m = min(m, lds_load(&label[j0 + jj]));
-                }
-            }
-            if (m < li) {
-                atomicMin(&label[li], m);
-                atomicMin(&label[i], m);
-                changed = 1;
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < Np; i += kClThreads) {
-            const int l = lds_load(&label[i]);
-            const int ll = lds_load(&label[l]);
-            if (ll < l) {
-                atomicMin(&label[i], ll);
-                changed = 1;
-            }
-        }
-        ++nsweep;
-        if (!__syncthreads_or(changed)) break;
-    }
+    const unsigned int nsweep = label_components<DIM, ADJ>(P, sx, Np, nw, adj, label, rc2, tid, nb);
     if (tid == 0 && sweeps) atomicMax(sweeps, nsweep);
 
     // ---- sizes
@@ -256,6 +190,12 @@ size_t cl_slot_doubles(int Np, int window)
     return (2 * (size_t)window + 1) * (size_t)Np;
 }
 
+hipError_t launch_cl_combine(const WalkerList &list, int n, int ns, int Np, const double *scratch, double *rg2, hipStream_t st)
+{
+    const size_t total = (size_t)n * Np;
+    return launch<k_cl_combine>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, list, n, ns, Np, scratch, rg2);
+}
+
 hipError_t launch_cl(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, double rc2,
                      double *scratch, unsigned long long *nsize, unsigned long long *nlarge, unsigned long long *nbond,
                      unsigned long long *samples, double *rg2, unsigned int *sweeps, hipStream_t st)
@@ -272,9 +212,7 @@ hipError_t launch_cl(const DevParams &P, const double *paths, int n, const Walke
         });
     });
     if (e != hipSuccess) return e;
-    const size_t total = (size_t)n * P.Np;
-    return launch<k_cl_combine>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, list, n, ns, (int)P.Np,
-                                (const double *)scratch, rg2);
+    return launch_cl_combine(list, n, ns, P.Np, scratch, rg2, st);
 }
 
 } // namespace pigs

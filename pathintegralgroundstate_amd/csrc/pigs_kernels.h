@@ -270,6 +270,29 @@ size_t cl_slot_doubles(int Np, int window);
 hipError_t launch_cl(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, double rc2,
                      double *scratch, unsigned long long *nsize, unsigned long long *nlarge, unsigned long long *nbond,
                      unsigned long long *samples, double *rg2, unsigned int *sweeps, hipStream_t st);
+// k_cl_combine alone: dst[walker][Np] += scratch[slot][slice][Np], slices ascending (pigs_pc.hip ends its launch with it too)
+hipError_t launch_cl_combine(const WalkerList &list, int n, int ns, int Np, const double *scratch, double *dst, hipStream_t st);
+
+// pigs_pc.hip: wrapping clusters, the unfolded extent of the finite ones and the persistence of clusters along tau
+// (pigs_pc_accumulate).  k_pc has k_cl's shape, limits (kClThreads, kClAdjNpMax, kClNpMax, kClLdsBudget) and labelling loop
+// (pigs_cl_device.h); after the labels it spreads image numbers from every root over the bonds until a sweep assigns
+// nobody, takes the wrap mask of every cluster from the bonds that the image numbers do not explain, counts clusters and
+// particles per mask (nwrap, mwrap: [walker][8]), slices per OR of their masks (swrap: [walker][8]), the finite clusters
+// per size (nfin: [walker][Np]) and the slices (samples), and writes the finite clusters' sums of g per size, from
+// unfolded separations, to scratch and the labels to `labels` (both [slot][slice][Np]).  k_cl_combine adds the slices to
+// rg2u ([walker][Np]); k_pc_persist, one workgroup per (slot, origin), counts the pairs together in slice a, in a + l
+// and in both for l = 0..ntau (first, second, both, norig: [walker][ntau + 1]).  One thread owns an element of rg2u per
+// launch: the caller never lists a walker twice in ONE launch.  A slot of the two scratches takes pc_slot_bytes bytes.
+// sweeps: two counters, the largest number of labelling and of image sweeps of any workgroup so far.
+constexpr int kPcScratchMiB = 256;
+struct PcSums {
+    unsigned long long *nwrap, *mwrap, *swrap, *nfin, *samples, *first, *second, *both, *norig;
+    double *rg2u;
+};
+size_t pc_lds_bytes(int dim, int Np);
+size_t pc_slot_bytes(int Np, int window);
+hipError_t launch_pc(const DevParams &P, const double *paths, int n, const WalkerList &list, int window, int ntau, double rc2,
+                     double *scratch, int *labels, const PcSums &s, unsigned int *sweeps, hipStream_t st);
 
 hipError_t launch_commit_beads(const DevParams &P, double *paths, int64_t n, const int32_t *walker,
                                const int32_t *ip, const int32_t *ib, const double *x, hipStream_t st);

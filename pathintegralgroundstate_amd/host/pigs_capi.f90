@@ -727,6 +727,27 @@ module pigs_capi
        integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
        integer(c_int) :: rc
      end function pigs_cl_read_t
+
+     ! wrapping clusters and cluster persistence over a slice window (include/pigs_hip.h, pigs_pc_*): looked up at run
+     ! time, see pc_bind; _accumulate has the signature of pigs_grv_accumulate
+     function pigs_pc_init_t(ctx,rc,window,ntau) bind(C) result(st)
+       import :: c_int, c_int32_t, c_double, c_ptr
+       type(c_ptr), value         :: ctx
+       real(c_double), value      :: rc
+       integer(c_int32_t), value  :: window,ntau
+       integer(c_int) :: st
+     end function pigs_pc_init_t
+
+     function pigs_pc_read_t(ctx,nwrap,mwrap,swrap,nfin,samples,rg2u,first,second,both,norig,reset) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int64_t)             :: nwrap(*),mwrap(*),swrap(*)        ! (8,n_walkers), index = wrap mask
+       integer(c_int64_t)             :: nfin(*),samples(*)                ! (Np,n_walkers)
+       real(c_double)                 :: rg2u(*)                           ! (Np,n_walkers)
+       integer(c_int64_t)             :: first(*),second(*),both(*),norig(*)   ! (ntau+1,n_walkers)
+       integer(c_int32_t), intent(in) :: reset(*)      ! per walker: 1 = zero its sums after the copy
+       integer(c_int) :: rc
+     end function pigs_pc_read_t
   end interface
 
   ! bound by density_bind (null until then)
@@ -812,6 +833,11 @@ module pigs_capi
   procedure(pigs_cl_init_t), pointer        :: cl_init => null()
   procedure(pigs_grv_accumulate_t), pointer :: cl_accumulate => null()
   procedure(pigs_cl_read_t), pointer        :: cl_read => null()
+
+  ! bound by pc_bind (null until then)
+  procedure(pigs_pc_init_t), pointer        :: pc_init => null()
+  procedure(pigs_grv_accumulate_t), pointer :: pc_accumulate => null()
+  procedure(pigs_pc_read_t), pointer        :: pc_read => null()
 
 contains
 
@@ -1005,6 +1031,16 @@ contains
     call c_f_procpointer(f(2),cl_accumulate)
     call c_f_procpointer(f(3),cl_read)
   end function cl_bind
+
+  ! The percolation entry points, found like the F(q,tau) ones: at run time, only when a run asks for them.
+  logical function pc_bind()
+    type(c_funptr) :: f(3)
+    pc_bind = resolve_all('pigs_pc',[character(len=10) :: 'init','accumulate','read'],f)
+    if (.not. pc_bind) return
+    call c_f_procpointer(f(1),pc_init)
+    call c_f_procpointer(f(2),pc_accumulate)
+    call c_f_procpointer(f(3),pc_read)
+  end function pc_bind
 
   ! Stop with the library's error text: the host-side policy (the library itself never stops).
   subroutine pigs_check(rc,what)

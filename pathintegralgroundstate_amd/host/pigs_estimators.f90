@@ -25,6 +25,7 @@ module pigs_estimators
   public :: normalize_lat, lat_nn_distance, lind_header, write_lind_block, write_lindtau, write_usite
   public :: normalize_sf, sf_columns, write_rhos, write_msdu
   public :: normalize_cl, clus_header, write_clus_block, write_clus
+  public :: normalize_pc, perc_header, write_perc_block, write_percsz, write_clpers
   public :: normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec
 
   type est_params
@@ -1124,6 +1125,102 @@ contains
     end do
     close (u)
   end subroutine write_clus
+
+  ! ---- percolation (raw sums of pigs_pc_read of one walker and block, S samples = window slices) -> the block values
+  !   BB(k) k = 1..3   the share of the slices with a cluster that wraps along axis k (0 beyond dim)
+  !   BB(4), BB(5)     the same along any axis and along all dim axes
+  !   BB(6)            P_inf = sum_{mask /= 0} mwrap/(Np S), the share of the particles in wrapping clusters
+  !   BB(7)            the mean finite cluster size sum s^2 nfin / sum s nfin (0 in a block without a finite cluster)
+  !   BS(1,s) nfin/(Np S)   the finite clusters of size s per particle
+  !   BS(2,s) rg2u/S        the sum of the unfolded Rg^2 over the finite clusters of size s, per slice (additive over the
+  !                         blocks; <Rg^2>(s) = rg2u/nfin, as profiles.normalize_pc has it, is BS(2,s)/(Np BS(1,s)))
+  !   BP(1:3,l) first, second, both per origin (/norig): additive over the blocks; C(l) = BP(3)/BP(1)
+  subroutine normalize_pc(Np,dim,ntau,S,nwrap,mwrap,swrap,nfin,rg2u,first,second,both,norig,BB,BS,BP)
+    integer, intent(in)    :: Np,dim,ntau
+    integer(8), intent(in) :: S,nwrap(0:7),mwrap(0:7),swrap(0:7),nfin(Np)
+    integer(8), intent(in) :: first(0:ntau),second(0:ntau),both(0:ntau),norig(0:ntau)
+    real(8), intent(in)    :: rg2u(Np)
+    real(8), intent(out)   :: BB(7),BS(2,Np),BP(3,0:ntau)
+    integer :: i,k,m,l
+    real(8) :: rs,s1,s2
+    rs = real(S,8)
+    BB = 0.d0
+    do m=1,7
+       do k=1,dim
+          if (btest(m,k-1)) BB(k) = BB(k)+real(swrap(m),8)/rs
+       end do
+       BB(4) = BB(4)+real(swrap(m),8)/rs
+       BB(6) = BB(6)+real(mwrap(m),8)/(rs*real(Np,8))
+    end do
+    BB(5) = real(swrap(2**dim-1),8)/rs
+    s1 = 0.d0; s2 = 0.d0
+    do i=1,Np
+       BS(1,i) = real(nfin(i),8)/(rs*real(Np,8))
+       BS(2,i) = rg2u(i)/rs
+       s1 = s1+real(i,8)*real(nfin(i),8)
+       s2 = s2+real(i,8)*real(i,8)*real(nfin(i),8)
+    end do
+    if (s1>0.d0) BB(7) = s2/s1
+    do l=0,ntau
+       BP(1,l) = real(first(l),8)/real(norig(l),8)
+       BP(2,l) = real(second(l),8)/real(norig(l),8)
+       BP(3,l) = real(both(l),8)/real(norig(l),8)
+    end do
+  end subroutine normalize_pc
+
+  ! first line of perc_vpi*.out
+  subroutine perc_header(u,rc,window)
+    integer, intent(in) :: u,window
+    real(8), intent(in) :: rc
+    write (u,'(a,g0,a,i0,a,i0,a)') '# block, wrapping probability along x, y, z (bonds below rc = ',rc,', slices Nb-',window,'..Nb+', &
+         & window,'; 0 beyond dim), along any axis, along all axes, P_inf, mean finite cluster size'
+  end subroutine perc_header
+
+  ! one line of perc_vpi*.out
+  subroutine write_perc_block(u,iblock,BB)
+    integer, intent(in) :: u,iblock
+    real(8), intent(in) :: BB(7)
+    write (u,'(20g20.10e3)') real(iblock),BB
+  end subroutine write_perc_block
+
+  ! percsz_vpi.out: one line per finite size s that occurred: s; n_fin(s)/Np with its error over the n blocks; <Rg^2>(s) =
+  ! <rg2u/S> / <nfin/S>, the two means over the blocks, and the error of its numerator over <nfin/S>
+  subroutine write_percsz(fname,Np,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: Np,n
+    real(8), intent(in) :: av(2,Np),av2(2,Np)
+    integer :: i,u
+    real(8) :: a(2),a2(2)
+    open (newunit=u,file=fname)
+    do i=1,Np
+       if (.not. (av(1,i)>0.d0)) cycle
+       a  = av(:,i)/real(n)
+       a2 = av2(:,i)/real(n)
+       write (u,'(i8,20g20.10e3)') i,a(1),variance(n,a(1),a2(1)),a(2)/(a(1)*real(Np,8)),variance(n,a(2),a2(2))/(a(1)*real(Np,8))
+    end do
+    close (u)
+  end subroutine write_percsz
+
+  ! clpers_vpi.out: one line per lag l: l, tau = l dt, then value and error over the n blocks of the pairs per origin that
+  ! are together in slice a, in a+l and in both; the persistence C(l) = <both>/<first> and the Jaccard index
+  ! <both>/(<first>+<second>-<both>), ratios of block means (0 where the denominator is 0)
+  subroutine write_clpers(fname,ntau,dt,n,av,av2)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: ntau,n
+    real(8), intent(in) :: dt,av(3,0:ntau),av2(3,0:ntau)
+    integer :: l,j,u
+    real(8) :: a(3),a2(3),c,jac
+    open (newunit=u,file=fname)
+    do l=0,ntau
+       a  = av(:,l)/real(n)
+       a2 = av2(:,l)/real(n)
+       c = 0.d0; jac = 0.d0
+       if (a(1)>0.d0) c = a(3)/a(1)
+       if (a(1)+a(2)-a(3)>0.d0) jac = a(3)/(a(1)+a(2)-a(3))
+       write (u,'(i8,20g20.10e3)') l,real(l,8)*dt,(a(j),variance(n,a(j),a2(j)),j=1,3),c,jac
+    end do
+    close (u)
+  end subroutine write_clpers
 
   ! grvec_vpi.out: one line per bin in flat-index order (x fastest): r_1..r_dim at the bin centre, g, error over the n blocks
   subroutine write_grvec(fname,p,Ng,nv,n,av,av2)

@@ -2,7 +2,7 @@
 ! pigs_families -- the per-walker accumulator families of the front end (pigs_vpi.f90), one type each.
 !
 ! A family is what one estimator key of &gpu switches on: density_profile, fq_tau, sq_vector, gr_vector, fq_vector,
-! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum, lattice, superfluid, clusters.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
+! tau_profile, fq_self, bond_order, van_hove, triplet, three_body, momentum, lattice, superfluid, clusters, percolation.  On the device it is an accumulator that takes the diagonal walkers of every step and is read and
 ! reset once per block; on the host it is the raw block sums of every walker, their normalisation, one block_series per
 ! output file and one block_count (pigs_block_stats).  Everything a family does sits in its type, in the phases the front
 ! end walks through:
@@ -81,6 +81,9 @@ module pigs_families
      logical :: clusters = .false.
      real(8) :: cl_rc = 0.d0                        ! <= 0: the run's rcut (half the shortest side)
      integer :: cl_window = -1                      ! < 0: 0
+     logical :: percolation = .false.
+     real(8) :: pc_rc = 0.d0                        ! <= 0: the run's rcut (half the shortest side)
+     integer :: pc_window = -1, pc_ntau = 0         ! pc_window < 0: the smallest window that holds the lags
   end type family_keys
 
   ! what the families need to know of the run and of the shard
@@ -477,17 +480,41 @@ module pigs_families
      procedure :: write_average => cl_write_average
   end type cl_family
 
-  integer, parameter :: NFAM = 15
+  ! percolation: the block's raw sums from the device and the normalised block values per block, per size and per lag
+  ! (pigs_estimators normalize_pc) behind perc_vpi.out, percsz_vpi.out and clpers_vpi.out
+  type, extends(family) :: pc_family
+     integer :: window = 0, ntau = 0
+     real(8) :: rc = 0.d0
+     integer(c_int64_t), allocatable :: nwrap(:,:),mwrap(:,:),swrap(:,:),nfin(:,:),first(:,:),second(:,:),both(:,:),norig(:,:)
+     real(8), allocatable :: rg2u(:,:),bs(:,:),bp(:,:)
+     real(8) :: bb(7) = 0.d0
+     type(block_series) :: ss,sp,sb
+     integer, allocatable :: up(:)
+     integer :: upav = -1
+   contains
+     procedure :: check => pc_check
+     procedure :: banner => pc_banner
+     procedure :: setup => pc_setup
+     procedure :: queue => pc_queue
+     procedure :: read => pc_read_block
+     procedure :: block => pc_block
+     procedure :: average => pc_average
+     procedure :: write_walker => pc_write_walker
+     procedure :: write_average => pc_write_average
+  end type pc_family
+
+  integer, parameter :: NFAM = 16
   ! the order in which the keys are checked and in which the banner names them (numbers of the slots below)
-  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12,13,14,15]
-  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12,13,14,15]
+  integer, parameter :: CHECK_ORDER(NFAM)  = [1,2,3,4,5,7,6,8,9,10,11,12,13,14,15,16]
+  integer, parameter :: BANNER_ORDER(NFAM) = [1,2,6,3,4,5,7,8,9,10,11,12,13,14,15,16]
 
   type family_slot
      class(family), allocatable :: f
   end type family_slot
 
   ! slots: 1 density_profile, 2 fq_tau, 3 sq_vector, 4 gr_vector, 5 fq_vector, 6 tau_profile, 7 fq_self, 8 bond_order,
-  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum, 13 lattice, 14 superfluid, 15 clusters
+  ! 9 van_hove, 10 triplet, 11 three_body, 12 momentum, 13 lattice, 14 superfluid, 15 clusters,
+  ! 16 percolation
   type family_set
      type(family_slot) :: slot(NFAM)
    contains
@@ -531,6 +558,7 @@ contains
     if (keys%lattice)         allocate (lat_family :: fs%slot(13)%f)
     if (keys%superfluid)      allocate (sf_family :: fs%slot(14)%f)
     if (keys%clusters)        allocate (cl_family :: fs%slot(15)%f)
+    if (keys%percolation)     allocate (pc_family :: fs%slot(16)%f)
   end subroutine set_create
 
   ! momentum, device-resident sampler: the samples of the step just queued, of all NW walkers
@@ -2399,5 +2427,129 @@ contains
     call write_clus('clus_vpi.out',f%ep%Np,f%cnt%nav,f%s%asum,f%s%asq)
     close (f%upav)
   end subroutine cl_write_average
+
+  !---------------------------------------------------------------------
+  ! percolation: which clusters of the bond graph r < pc_rc wrap the periodic box, the finite ones with their unfolded
+  ! extent, and the persistence of clusters over the lags 0..pc_ntau, over the slices Nb-pc_window..Nb+pc_window --
+  ! perc_vpi.out (one line per block), percsz_vpi.out (one line per finite size that occurred) and clpers_vpi.out (one
+  ! line per lag); per walker, and walker-averaged
+
+  subroutine pc_check(f,keys,dim,Nb,trap)
+    class(pc_family), intent(inout) :: f
+    type(family_keys), intent(inout) :: keys
+    integer, intent(in) :: dim,Nb
+    logical, intent(in) :: trap
+    if (trap) call needs_periodic('percolation','a cluster wraps through the faces of the box')
+    if (keys%pc_rc/=keys%pc_rc .or. abs(keys%pc_rc)>huge(1.d0)) then
+       write (0,'(a,g0,a)') ' pigs_vpi: percolation = T: pc_rc = ',keys%pc_rc,' must be finite (left out or <= 0: rcut)'
+       stop 2
+    end if
+    if (.not. (keys%pc_rc>0.d0)) keys%pc_rc = keys%half_side            ! left out: the run's rcut
+    if (.not. (keys%pc_rc<=keys%half_side)) then
+       write (0,'(a,g0,a,g0)') ' pigs_vpi: percolation = T: pc_rc = ',keys%pc_rc, &
+            & ' must be at most half the shortest side of the box = ',keys%half_side
+       stop 2
+    end if
+    call check_lags('percolation','pc',keys%pc_ntau,keys%pc_window,Nb)
+    if (.not. pc_bind()) call no_backend('percolation','pigs_pc_init / _accumulate / _read','the cluster labelling runs')
+  end subroutine pc_check
+
+  subroutine pc_banner(f,keys,trap)
+    class(pc_family), intent(in) :: f
+    type(family_keys), intent(in) :: keys
+    logical, intent(in) :: trap
+    print '(a,g0,a,i0,a,i0,a,i0,a)', '  > Percolation          : on (bonds below pc_rc = ',keys%pc_rc,', slices Nb-', &
+         & keys%pc_window,'..Nb+',keys%pc_window,', lags 0..',keys%pc_ntau,': perc_vpi.out, percsz_vpi.out, clpers_vpi.out)'
+  end subroutine pc_banner
+
+  subroutine pc_setup(f,keys,run,ctx,ep,NW,nvec)
+    class(pc_family), intent(inout) :: f
+    type(family_keys), intent(in) :: keys
+    type(family_run), intent(in)  :: run
+    type(c_ptr), intent(in)       :: ctx
+    type(est_params), intent(in)  :: ep
+    integer, intent(in)    :: NW
+    integer, intent(inout) :: nvec
+    integer :: w
+    call family_begin(f,run,ep,NW)
+    f%window = max(keys%pc_window,0); f%ntau = keys%pc_ntau; f%rc = keys%pc_rc
+    allocate (f%nwrap(8,NW),f%mwrap(8,NW),f%swrap(8,NW),f%nfin(ep%Np,NW),f%rg2u(ep%Np,NW))
+    allocate (f%first(f%ntau+1,NW),f%second(f%ntau+1,NW),f%both(f%ntau+1,NW),f%norig(f%ntau+1,NW))   ! (first index: lag l + 1)
+    allocate (f%bs(2,ep%Np),f%bp(3,f%ntau+1))                         ! (second index: lag l + 1)
+    call series_create(f%ss,2*ep%Np,NW,nvec)
+    call series_create(f%sp,3*(f%ntau+1),NW,nvec)
+    call series_create(f%sb,7,NW,nvec)
+    call count_create(f%cnt,nvec)
+    call pigs_check(pc_init(ctx,real(f%rc,c_double),int(f%window,c_int32_t),int(f%ntau,c_int32_t)),'pigs_pc_init')
+    allocate (f%up(NW))
+    do w=1,NW
+       open (newunit=f%up(w),file='perc_vpi'//trim(run%suffix(w))//'.out')
+       call perc_header(f%up(w),f%rc,f%window)
+    end do
+    if (run%averages) then
+       open (newunit=f%upav,file='perc_vpi.out')
+       call perc_header(f%upav,f%rc,f%window)
+    end if
+  end subroutine pc_setup
+
+  subroutine pc_queue(f,ctx,nd,wl)
+    class(pc_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(pc_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_pc_accumulate')
+  end subroutine pc_queue
+
+  subroutine pc_read_block(f,ctx)
+    class(pc_family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    call pigs_check(pc_read(ctx,f%nwrap,f%mwrap,f%swrap,f%nfin,f%smp,f%rg2u,f%first,f%second,f%both,f%norig,f%reset), &
+         & 'pigs_pc_read')
+  end subroutine pc_read_block
+
+  subroutine pc_block(f,w,info,vec)
+    class(pc_family), intent(inout) :: f
+    integer, intent(in)           :: w
+    type(family_info), intent(in) :: info
+    real(8), intent(inout)        :: vec(:)
+    call normalize_pc(f%ep%Np,f%ep%dim,f%ntau,int(f%smp(w),8),int(f%nwrap(:,w),8),int(f%mwrap(:,w),8),int(f%swrap(:,w),8), &
+         & int(f%nfin(:,w),8),f%rg2u(:,w),int(f%first(:,w),8),int(f%second(:,w),8),int(f%both(:,w),8),int(f%norig(:,w),8), &
+         & f%bb,f%bs,f%bp)
+    call series_add(f%ss,w,reshape(f%bs,[size(f%bs)]),vec)
+    call series_add(f%sp,w,reshape(f%bp,[size(f%bp)]),vec)
+    call series_add(f%sb,w,f%bb,vec)
+    call count_add(f%cnt,vec)
+    call write_perc_block(f%up(w),info%iblock,f%bb)
+  end subroutine pc_block
+
+  subroutine pc_average(f,info,vec)
+    class(pc_family), intent(inout) :: f
+    type(family_info), intent(in) :: info
+    real(8), intent(in)           :: vec(:)
+    integer :: nall
+    nall = count_reduced(f%cnt,vec)
+    if (nall>0) then
+       call series_average(f%ss,vec,nall)
+       call series_average(f%sp,vec,nall)
+       call series_average(f%sb,vec,nall)
+       if (info%ndall>0) call write_perc_block(f%upav,info%iblock,f%sb%mean)
+    end if
+  end subroutine pc_average
+
+  subroutine pc_write_walker(f,suffix,w,nblocks)
+    class(pc_family), intent(inout) :: f
+    character(len=*), intent(in) :: suffix
+    integer, intent(in)          :: w,nblocks
+    call write_percsz('percsz_vpi'//trim(suffix)//'.out',f%ep%Np,nblocks,f%ss%sum(:,w),f%ss%sq(:,w))
+    call write_clpers('clpers_vpi'//trim(suffix)//'.out',f%ntau,f%run%dt,nblocks,f%sp%sum(:,w),f%sp%sq(:,w))
+    close (f%up(w))
+  end subroutine pc_write_walker
+
+  subroutine pc_write_average(f)
+    class(pc_family), intent(inout) :: f
+    call write_percsz('percsz_vpi.out',f%ep%Np,f%cnt%nav,f%ss%asum,f%ss%asq)
+    call write_clpers('clpers_vpi.out',f%ntau,f%run%dt,f%cnt%nav,f%sp%asum,f%sp%asq)
+    close (f%upav)
+  end subroutine pc_write_average
 
 end module pigs_families

@@ -14,6 +14,7 @@ module pigs_host_hooks
        & normalize_lat, lind_header, write_lind_block, write_lindtau, write_usite, &
        & normalize_sf, sf_columns, write_rhos, write_msdu, &
        & normalize_cl, clus_header, write_clus_block, write_clus, &
+       & normalize_pc, perc_header, write_perc_block, write_percsz, write_clpers, &
        & normalize_nk, normalize_nrvec, n0_header, write_n0_block, write_nkvec, write_sqshell, write_grvec, &
        & sqv_shells, sqv_shell_means
 
@@ -388,6 +389,39 @@ contains
     close (u)
     call write_clus(cstring(fc),Np,nblk,sr%sum(:,1),sr%sq(:,1))
   end subroutine hs_cl_files
+
+  ! The percolation normalisation and writers of the front end on given sums: nblk blocks of one walker, the arrays of
+  ! pigs_pc_read per block and S samples per block -> fb (perc_vpi.out), fs (percsz_vpi.out) and fp (clpers_vpi.out), the
+  ! means and errors over the blocks through block_series, as the front end takes them (names: C strings)
+  subroutine hs_pc_files(Np,dim,window,ntau,rc,dt,nblk,S,nwrap,mwrap,swrap,nfin,rg2u,first,second,both,norig,fb,fs,fp) &
+       & bind(C,name='hs_pc_files')
+    use pigs_block_stats, only: block_series,series_create,series_add
+    integer(c_int), value :: Np,dim,window,ntau,nblk
+    real(c_double), value :: rc,dt
+    integer(c_int64_t), intent(in) :: S(nblk),nwrap(8,nblk),mwrap(8,nblk),swrap(8,nblk),nfin(Np,nblk)
+    integer(c_int64_t), intent(in) :: first(ntau+1,nblk),second(ntau+1,nblk),both(ntau+1,nblk),norig(ntau+1,nblk)
+    real(c_double), intent(in)     :: rg2u(Np,nblk)
+    character(kind=c_char), intent(in) :: fb(*),fs(*),fp(*)
+    real(8), allocatable :: BS(:,:),BP(:,:)
+    real(8) :: BB(7),none(1)
+    type(block_series) :: ss,sp
+    integer :: ib,u
+    allocate (BS(2,Np),BP(3,ntau+1))                                 ! (second index: lag l + 1)
+    call series_create(ss,2*Np,1)
+    call series_create(sp,3*(ntau+1),1)
+    open (newunit=u,file=cstring(fb))
+    call perc_header(u,rc,window)
+    do ib=1,nblk
+       call normalize_pc(Np,dim,ntau,int(S(ib),8),int(nwrap(:,ib),8),int(mwrap(:,ib),8),int(swrap(:,ib),8),int(nfin(:,ib),8), &
+            & rg2u(:,ib),int(first(:,ib),8),int(second(:,ib),8),int(both(:,ib),8),int(norig(:,ib),8),BB,BS,BP)
+       call series_add(ss,1,reshape(BS,[size(BS)]),none)
+       call series_add(sp,1,reshape(BP,[size(BP)]),none)
+       call write_perc_block(u,ib,BB)
+    end do
+    close (u)
+    call write_percsz(cstring(fs),Np,nblk,ss%sum(:,1),ss%sq(:,1))
+    call write_clpers(cstring(fp),ntau,dt,nblk,sp%sum(:,1),sp%sq(:,1))
+  end subroutine hs_pc_files
 
   ! a C string as a Fortran one
   function cstring(c) result(f)

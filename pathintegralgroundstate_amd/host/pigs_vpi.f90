@@ -90,6 +90,15 @@
 ! size s per slice, of the particle fraction s n(s)/Np and of P_largest(s), then <Rg^2>(s) = <sum of Rg^2 per slice> / <n(s)>
 ! and the error of its numerator over <n(s)>; clusblk_vpi.out, one line per block: the block, clusters per slice, <largest
 ! cluster>/Np, the mean cluster size sum s^2 n(s) / sum s n(s), bonds per particle)
+! (percolation = T, periodic systems only: the clusters of the bond graph r_ij < pc_rc (as clusters = T has them; left out
+! or <= 0: rcut) of every slice Nb-pc_window..Nb+pc_window that wrap the box, the finite ones and their unfolded extent,
+! and the persistence of clusters over the lags 0..pc_ntau (default 0; pc_window left out: the smallest window that holds
+! the lags) -- perc_vpi.out, one line per block: the block, the share of the slices with a cluster that wraps along x, y,
+! z (0 beyond dim), along any axis, along all axes, the strength P_inf (the share of the particles in wrapping clusters)
+! and the mean finite cluster size; percsz_vpi.out, one line per finite cluster size s that occurred: s, value and error
+! of n_fin(s)/Np, then <Rg^2>(s) from unfolded separations as a ratio of two block means and the error of its numerator
+! over the denominator; clpers_vpi.out, one line per lag l: l, tau, value and error of the pairs per origin that share a
+! cluster in slice a, in a+l and in both, the persistence <both>/<first> and the Jaccard index)
 ! (device_sampler = T: the whole MC step of every walker runs on the GPU in one launch, kernel K6 -- every mover of
 ! the reference; F: the host-driven lock-step sampler, one K1 batch per move stage.  Left out: K6 wherever it serves
 ! the input, the host-driven sampler otherwise.  The two give the same files and the same worldlines, bit for bit.)
@@ -155,6 +164,9 @@ program pigs_vpi
   logical           :: clusters
   real (kind=8)     :: cl_rc
   integer           :: cl_window
+  logical           :: percolation
+  real (kind=8)     :: pc_rc
+  integer           :: pc_window,pc_ntau
   integer           :: nk_nmax,nk_nbin
   type(family_keys) :: fk                ! the estimator keys, as the families take them
   type(family_set)  :: keyed             ! (the main program's set checks the keys and prints the banner; every shard has its own)
@@ -182,7 +194,8 @@ program pigs_vpi
        &             momentum,nk_nmax,nk_nbin, &
        &             lattice,lat_nbin,lat_rmax,lat_window,lat_cm, &
        &             superfluid,sf_ntau,sf_window, &
-       &             clusters,cl_rc,cl_window
+       &             clusters,cl_rc,cl_window, &
+       &             percolation,pc_rc,pc_window,pc_ntau
 
 
   ! shared by the shards (read-only once the parallel region starts)
@@ -218,6 +231,7 @@ program pigs_vpi
   lattice = .false.; lat_nbin = 0; lat_rmax = 0.d0; lat_window = -1; lat_cm = .true.
   superfluid = .false.; sf_ntau = 0; sf_window = -1
   clusters = .false.; cl_rc = 0.d0; cl_window = -1
+  percolation = .false.; pc_rc = 0.d0; pc_window = -1; pc_ntau = 0
   three_body = .false.; atm_nu = -huge(1.d0); atm_rc = 0.d0; atm_window = -1        ! (atm_nu: a value nobody gives, left out -> 1)
 
   read (5,nml=system,iostat=ios);  rewind (5)
@@ -297,7 +311,8 @@ program pigs_vpi
        & momentum=momentum,nk_nmax=nk_nmax,nk_nbin=nk_nbin,cworm=CWorm,nobdm=Nobdm, &
        & lattice=lattice,lat_nbin=lat_nbin,lat_rmax=lat_rmax,lat_window=lat_window,lat_cm=lat_cm,nbin_run=Nbin,box=Lbox, &
        & superfluid=superfluid,sf_ntau=sf_ntau,sf_window=sf_window, &
-       & clusters=clusters,cl_rc=cl_rc,cl_window=cl_window)
+       & clusters=clusters,cl_rc=cl_rc,cl_window=cl_window, &
+       & percolation=percolation,pc_rc=pc_rc,pc_window=pc_window,pc_ntau=pc_ntau)
   call keyed%create(fk)
   call keyed%check(fk,dim,Nb,trap)
 

@@ -102,6 +102,12 @@ connected component of that graph in one window slice; with S = samples (slices)
   n(s) = nsize / S,   fraction(s) = s n(s) / Np,   P_largest(s) = nlarge / S,   <Rg^2>(s) = rg2 / nsize (NaN: no such cluster)
   clusters per slice = sum_s n(s),   <smax>/Np = sum_s s nlarge / (S Np),   S_mean = sum s^2 nsize / sum s nsize
   bonds per particle = nbond / (S Np)
+Wrapping clusters and persistence (normalize_pc, PigsContext.pc_read, pigs_pc_*): cl's bonds and clusters; a cluster's wrap
+mask has bit k set when it closes on itself through the faces along axis k; with S = samples and mask = 0..7:
+  P_wrap,k = sum_{mask with bit k} swrap / S,   P_any = sum_{mask != 0} swrap / S,   P_all = swrap[2^dim - 1] / S
+  P_inf = sum_{mask != 0} mwrap / (Np S),   n_fin(s) / Np = nfin / (Np S),   S_fin = sum s^2 nfin / sum s nfin
+  <Rg^2>(s) = rg2u / nfin  (finite clusters, from unfolded separations),   C(l) = both / first,
+  J(l) = both / (first + second - both);   NaN where a denominator is zero
 Pure numpy: it needs no GPU.
 """
 from __future__ import annotations
@@ -624,6 +630,40 @@ def normalize_cl(got, Np, summed=False):
                 "rg2": np.where(ns > 0, rg / ns, np.nan), "n_clusters": n.sum(axis=-1),
                 "smax": (s * nl).sum(axis=-1) / (S * float(Np)),
                 "mean_size": (s * s * ns).sum(axis=-1) / (s * ns).sum(axis=-1), "bonds": nb / (S * float(Np))}
+
+
+def normalize_pc(got, Np, dim, summed=False):
+    """got: the dict of pc_read (nwrap, mwrap, swrap [W, 8], nfin, rg2u [W, Np], samples [W], first, second, both, norig
+    [W, ntau + 1]) or one walker's slice of it; summed: add the walkers' sums first.  With S = samples (window slices) and
+    s = 1..Np, returns a dict:
+    s [Np]; p_wrap [.., dim] = the share of the slices with a cluster that wraps along axis k; p_any [..] and p_all [..],
+    along any axis and along all `dim` of them; p_inf [..] = sum_{mask != 0} mwrap / (Np S), the strength: the share of the
+    particles in wrapping clusters; n_fin [.., Np] = nfin / (Np S), the finite clusters of size s per particle; mean_size
+    [..] = sum s^2 nfin / sum s nfin over the finite clusters; rg2 [.., Np] = rg2u / nfin; persistence [.., ntau + 1] =
+    both / first; jaccard [.., ntau + 1] = both / (first + second - both).  Elements with a zero denominator are NaN."""
+    dim = int(dim)
+    if dim not in (1, 2, 3):
+        raise ValueError("dim is 1, 2 or 3")
+    f = lambda k: np.asarray(got[k], dtype=np.float64)
+    nw, mw, sw, nf, rg, S = f("nwrap"), f("mwrap"), f("swrap"), f("nfin"), f("rg2u"), f("samples")
+    fi, se, bo = f("first"), f("second"), f("both")
+    if nf.ndim < 1 or nf.shape[-1] != int(Np) or rg.shape != nf.shape or S.shape != nf.shape[:-1] or \
+            any(a.shape != S.shape + (8,) for a in (nw, mw, sw)) or fi.ndim != nf.ndim or fi.shape[:-1] != S.shape or \
+            se.shape != fi.shape or bo.shape != fi.shape:
+        raise ValueError("the arrays of pc_read do not fit each other or Np")
+    if summed and nf.ndim > 1:
+        nw, mw, sw, nf, rg, S, fi, se, bo = (a.sum(axis=0) for a in (nw, mw, sw, nf, rg, S, fi, se, bo))
+    s = np.arange(1, int(Np) + 1, dtype=np.float64)
+    masks = np.arange(8)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nan_if = lambda num, den: np.where(den != 0, num / np.where(den != 0, den, 1.0), np.nan)
+        p_wrap = np.stack([nan_if(sw[..., (masks >> k) & 1 == 1].sum(axis=-1), S) for k in range(dim)], axis=-1)
+        return {"s": s, "p_wrap": p_wrap, "p_any": nan_if(sw[..., 1:].sum(axis=-1), S),
+                "p_all": nan_if(sw[..., (1 << dim) - 1], S),
+                "p_inf": nan_if(mw[..., 1:].sum(axis=-1), S * float(Np)),
+                "n_fin": nan_if(nf, (S * float(Np))[..., None]),
+                "mean_size": nan_if((s * s * nf).sum(axis=-1), (s * nf).sum(axis=-1)),
+                "rg2": nan_if(rg, nf), "persistence": nan_if(bo, fi), "jaccard": nan_if(bo, fi + se - bo)}
 
 
 def pressure_virial(kin_per_particle, w_per_particle, density, dim):
