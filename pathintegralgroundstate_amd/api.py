@@ -239,6 +239,9 @@ def _l(a):
     return a.ctypes.data_as(_lp)
 
 
+_F, _N = np.float64, np.int64          # the two element types of the accumulator families (PigsContext._read)
+
+
 def device_count():
     L = load_library()
     n = C.c_int32(0)
@@ -509,6 +512,27 @@ class PigsContext:
             raise ValueError("reset mask needs one entry per walker")
         return _i(keep)
 
+    def _read(self, fam, state_attr, spec, reset):
+        """pigs_<fam>_read.  `state_attr` names what <fam>_init leaves on this object (None: nothing), `spec(state)` lists
+        (key, dtype, shape without the walker axis) in the order of the C arguments.  Returns the dict of those arrays;
+        the walkers flagged by `reset` are zeroed after the copy."""
+        state = None if state_attr is None else getattr(self, state_attr, None)
+        if state_attr is not None and state is None:
+            raise PigsError(f"{fam}_read: {fam}_init first")
+        spec, name = spec(state), f"pigs_{fam}_read"
+        out = {k: np.zeros((self.n_walkers,) + tuple(shape), dt) for k, dt, shape in spec}
+        mask = self._reset_mask(reset)
+        _chk(self.L, getattr(self.L, name)(self.h, *((_d if dt is _F else _l)(out[k]) for k, dt, _ in spec), mask), name)
+        return out
+
+    def _vectors(self, fam, nq):
+        """pigs_<fam>_vectors: the stored vectors n [Nq, dim] (int32); `nq` is None before <fam>_init."""
+        if nq is None:
+            raise PigsError(f"{fam}_vectors: {fam}_init first")
+        n, name = np.zeros((nq, self.cfg.dim), np.int32), f"pigs_{fam}_vectors"
+        _chk(self.L, getattr(self.L, name)(self.h, _i(n)), name)
+        return n
+
     # ---- density profiles of a trapped system (pigs_density_*: slice Nb, 64-bit counts per walker)
     def density_init(self, Nbin, half_width):
         """Allocate and zero the accumulators: Nbin bins per axis over [-half_width, half_width) (planar) and over
@@ -524,16 +548,9 @@ class PigsContext:
         """dict of int64 arrays: planar [W, Nbin] (dim 1) or [W, Nbin, Nbin] (x fastest in the last axis), radial
         [W, Nbin], pair [W, Nbin], samples [W].  reset: None, True (all walkers) or a per-walker mask of walkers whose
         accumulators are zeroed after the copy."""
-        nb = getattr(self, "_dens_nbin", 0)
-        if not nb:
-            raise PigsError("density_read: density_init first")
-        W, dp = self.n_walkers, min(self.cfg.dim, 2)
-        out = {"planar": np.zeros((W,) + (nb,) * dp, np.int64), "radial": np.zeros((W, nb), np.int64),
-               "pair": np.zeros((W, nb), np.int64), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_density_read(self.h, *(_l(out[k]) for k in ("planar", "radial", "pair", "samples")), mask),
-             "pigs_density_read")
-        return out
+        dp = min(self.cfg.dim, 2)
+        return self._read("density", "_dens_nbin", lambda nb: [
+            ("planar", _N, (nb,) * dp), ("radial", _N, (nb,)), ("pair", _N, (nb,)), ("samples", _N, ())], reset)
 
     # ---- imaginary-time density correlations of a periodic system (pigs_fqt_*: raw sums per walker, lag, harmonic, axis)
     def fqt_init(self, Nk, Ntau, window):
@@ -550,14 +567,7 @@ class PigsContext:
     def fqt_read(self, reset=None):
         """dict: F, the raw sums [W, Ntau+1, Nk, dim] (profiles.normalize_fqt divides them), and samples [W] (int64).
         reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        shape = getattr(self, "_fqt_shape", None)
-        if shape is None:
-            raise PigsError("fqt_read: fqt_init first")
-        W = self.n_walkers
-        out = {"F": np.zeros((W,) + shape), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_fqt_read(self.h, _d(out["F"]), _l(out["samples"]), mask), "pigs_fqt_read")
-        return out
+        return self._read("fqt", "_fqt_shape", lambda shape: [("F", _F, shape), ("samples", _N, ())], reset)
 
     # ---- imaginary-time profiles (pigs_tau_*: raw sums Vpair, Vext, W, D2 per walker and slice)
     def tau_init(self):
@@ -572,11 +582,7 @@ class PigsContext:
     def tau_read(self, reset=None):
         """dict: Q, the raw sums [W, 2Nb+1, 4] (Vpair, Vext, W, D2; profiles.normalize_tau divides them), and samples [W]
         (int64).  reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        W = self.n_walkers
-        out = {"Q": np.zeros((W, self.cfg.M, 4)), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_tau_read(self.h, _d(out["Q"]), _l(out["samples"]), mask), "pigs_tau_read")
-        return out
+        return self._read("tau", None, lambda _: [("Q", _F, (self.cfg.M, 4)), ("samples", _N, ())], reset)
 
     # ---- vector structure factor on the full reciprocal grid (pigs_sqv_*: raw sums per walker and vector)
     def sqv_init(self, nmax, window=0):
@@ -589,12 +595,7 @@ class PigsContext:
 
     def sqv_vectors(self):
         """The stored vectors n [Nq, dim] (int32) in the library's enumeration order."""
-        nq = getattr(self, "_sqv_nq", None)
-        if nq is None:
-            raise PigsError("sqv_vectors: sqv_init first")
-        n = np.zeros((nq, self.cfg.dim), np.int32)
-        _chk(self.L, self.L.pigs_sqv_vectors(self.h, _i(n)), "pigs_sqv_vectors")
-        return n
+        return self._vectors("sqv", getattr(self, "_sqv_nq", None))
 
     def sqv_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
@@ -603,14 +604,7 @@ class PigsContext:
     def sqv_read(self, reset=None):
         """dict: S, the raw sums [W, Nq] (profiles.normalize_sqv divides them), and samples [W] (int64).
         reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        nq = getattr(self, "_sqv_nq", None)
-        if nq is None:
-            raise PigsError("sqv_read: sqv_init first")
-        W = self.n_walkers
-        out = {"S": np.zeros((W, nq)), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_sqv_read(self.h, _d(out["S"]), _l(out["samples"]), mask), "pigs_sqv_read")
-        return out
+        return self._read("sqv", "_sqv_nq", lambda nq: [("S", _F, (nq,)), ("samples", _N, ())], reset)
 
     # ---- F(q,tau) on the full reciprocal grid (pigs_fqv_*: raw sums per walker, lag and vector)
     def fqv_init(self, nmax, Ntau=0, window=0):
@@ -624,12 +618,7 @@ class PigsContext:
 
     def fqv_vectors(self):
         """The stored vectors n [Nq, dim] (int32): those of sqv_vectors, in the same order."""
-        shape = getattr(self, "_fqv_shape", None)
-        if shape is None:
-            raise PigsError("fqv_vectors: fqv_init first")
-        n = np.zeros((shape[1], self.cfg.dim), np.int32)
-        _chk(self.L, self.L.pigs_fqv_vectors(self.h, _i(n)), "pigs_fqv_vectors")
-        return n
+        return self._vectors("fqv", getattr(self, "_fqv_shape", (0, None))[1])
 
     def fqv_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
@@ -638,14 +627,7 @@ class PigsContext:
     def fqv_read(self, reset=None):
         """dict: F, the raw sums [W, Ntau+1, Nq] (profiles.normalize_fqv divides them), and samples [W] (int64).
         reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        shape = getattr(self, "_fqv_shape", None)
-        if shape is None:
-            raise PigsError("fqv_read: fqv_init first")
-        W = self.n_walkers
-        out = {"F": np.zeros((W,) + shape), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_fqv_read(self.h, _d(out["F"]), _l(out["samples"]), mask), "pigs_fqv_read")
-        return out
+        return self._read("fqv", "_fqv_shape", lambda shape: [("F", _F, shape), ("samples", _N, ())], reset)
 
     # ---- self part of F(q,tau) and the imaginary-time displacement (pigs_fqs_*: raw sums per walker, lag and vector)
     def fqs_init(self, nmax, Ntau=0, window=0):
@@ -659,12 +641,7 @@ class PigsContext:
 
     def fqs_vectors(self):
         """The stored vectors n [Nq, dim] (int32): those of sqv_vectors, in the same order."""
-        shape = getattr(self, "_fqs_shape", None)
-        if shape is None:
-            raise PigsError("fqs_vectors: fqs_init first")
-        n = np.zeros((shape[1], self.cfg.dim), np.int32)
-        _chk(self.L, self.L.pigs_fqs_vectors(self.h, _i(n)), "pigs_fqs_vectors")
-        return n
+        return self._vectors("fqs", getattr(self, "_fqs_shape", (0, None))[1])
 
     def fqs_accumulate(self, walkers=None):
         """Queue one sample of the window of `walkers` (None: all) on the context's stream; does not wait."""
@@ -674,14 +651,8 @@ class PigsContext:
         """dict: F, the raw sums [W, Ntau+1, Nq] (profiles.normalize_fqs divides them), D, the raw sums of r^2 and r^4
         [W, Ntau+1, 2] (profiles.normalize_msd), and samples [W] (int64).
         reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        shape = getattr(self, "_fqs_shape", None)
-        if shape is None:
-            raise PigsError("fqs_read: fqs_init first")
-        W = self.n_walkers
-        out = {"F": np.zeros((W,) + shape), "D": np.zeros((W, shape[0], 2)), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_fqs_read(self.h, _d(out["F"]), _d(out["D"]), _l(out["samples"]), mask), "pigs_fqs_read")
-        return out
+        return self._read("fqs", "_fqs_shape", lambda shape: [
+            ("F", _F, shape), ("D", _F, (shape[0], 2)), ("samples", _N, ())], reset)
 
     # ---- pair distribution on the vector grid over a slice window (pigs_grv_*: 64-bit counts per walker)
     def grv_init(self, Nbin, window=0, Nr=None, rbin=None):
@@ -702,15 +673,9 @@ class PigsContext:
         """dict of int64 arrays: vec [W, Nbin, ..(dim times)] (x on the last axis), radial [W, Nr], samples [W]
         (profiles.normalize_grv turns them into g).  reset: None, True (all walkers) or a per-walker mask of walkers
         whose counts are zeroed after the copy."""
-        shp = getattr(self, "_grv_shape", None)
-        if shp is None:
-            raise PigsError("grv_read: grv_init first")
-        W = self.n_walkers
-        out = {"vec": np.zeros((W,) + (shp[0],) * self.cfg.dim, np.int64), "radial": np.zeros((W, shp[1]), np.int64),
-               "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_grv_read(self.h, *(_l(out[k]) for k in ("vec", "radial", "samples")), mask), "pigs_grv_read")
-        return out
+        dim = self.cfg.dim
+        return self._read("grv", "_grv_shape", lambda shp: [
+            ("vec", _N, (shp[0],) * dim), ("radial", _N, (shp[1],)), ("samples", _N, ())], reset)
 
     # ---- bond-orientational order over a slice window (pigs_bop_*: raw sums and 64-bit counts per walker)
     def bop_init(self, rnb, window=0, Nh=50, Nr=None, rbin=None):
@@ -732,16 +697,8 @@ class PigsContext:
         """dict: S [W, 8] (the sums of Q4, Q4^2, Q6, Q6^2, mean q4(i), mean q6(i), sum n_i, 0), H [W, 2, Nh] (int64), G
         [W, Nr], GN [W, Nr] (int64) and samples [W] (int64); profiles.normalize_bop divides them.  reset: None, True (all
         walkers) or a per-walker mask of walkers whose accumulators are zeroed after the copy."""
-        shp = getattr(self, "_bop_shape", None)
-        if shp is None:
-            raise PigsError("bop_read: bop_init first")
-        W = self.n_walkers
-        out = {"S": np.zeros((W, 8)), "H": np.zeros((W, 2, shp[0]), np.int64), "G": np.zeros((W, shp[1])),
-               "GN": np.zeros((W, shp[1]), np.int64), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_bop_read(self.h, _d(out["S"]), _l(out["H"]), _d(out["G"]), _l(out["GN"]), _l(out["samples"]),
-                                          mask), "pigs_bop_read")
-        return out
+        return self._read("bop", "_bop_shape", lambda shp: [
+            ("S", _F, (8,)), ("H", _N, (2, shp[0])), ("G", _F, (shp[1],)), ("GN", _N, (shp[1],)), ("samples", _N, ())], reset)
 
     # ---- van Hove functions over a slice window (pigs_vh_*: 64-bit counts per walker and lag)
     def vh_init(self, Ntau, window, Nr=None, rbin=None, Ns=50, sbin=None):
@@ -764,15 +721,8 @@ class PigsContext:
         """dict of int64 arrays: self [W, Ntau+1, Ns], distinct [W, Ntau+1, Nr], samples [W] (profiles.normalize_vh turns
         them into G_s and G_d).  reset: None, True (all walkers) or a per-walker mask of walkers whose counts are zeroed
         after the copy."""
-        shp = getattr(self, "_vh_shape", None)
-        if shp is None:
-            raise PigsError("vh_read: vh_init first")
-        W = self.n_walkers
-        out = {"self": np.zeros((W, shp[0], shp[2]), np.int64), "distinct": np.zeros((W, shp[0], shp[1]), np.int64),
-               "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_vh_read(self.h, *(_l(out[k]) for k in ("self", "distinct", "samples")), mask), "pigs_vh_read")
-        return out
+        return self._read("vh", "_vh_shape", lambda shp: [
+            ("self", _N, (shp[0], shp[2])), ("distinct", _N, (shp[0], shp[1])), ("samples", _N, ())], reset)
 
     # ---- triplet distribution over a slice window (pigs_g3_*: 64-bit counts per walker)
     def g3_init(self, Nr, rbin, Na, window=0):
@@ -790,15 +740,8 @@ class PigsContext:
         """dict of int64 arrays: trip [W, Nr(Nr+1)/2, Na] on the packed upper triangle of leg-bin pairs (lo <= hi at
         lo*Nr - lo*(lo-1)/2 + hi - lo), pair [W, Nr], samples [W] (profiles.normalize_g3 turns them into g2 and g3).
         reset: None, True (all walkers) or a per-walker mask of walkers whose counts are zeroed after the copy."""
-        shp = getattr(self, "_g3_shape", None)
-        if shp is None:
-            raise PigsError("g3_read: g3_init first")
-        W = self.n_walkers
-        out = {"trip": np.zeros((W, shp[0], shp[1]), np.int64), "pair": np.zeros((W, shp[2]), np.int64),
-               "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_g3_read(self.h, *(_l(out[k]) for k in ("trip", "pair", "samples")), mask), "pigs_g3_read")
-        return out
+        return self._read("g3", "_g3_shape", lambda shp: [
+            ("trip", _N, (shp[0], shp[1])), ("pair", _N, (shp[2],)), ("samples", _N, ())], reset)
 
     # ---- Axilrod-Teller-Muto three-body sum over a slice window (pigs_atm_*: a double and a 64-bit count per walker and slice)
     def atm_init(self, rc, window=0):
@@ -817,14 +760,7 @@ class PigsContext:
         triplets counted, of the same shape (int64), and samples [W] (int64); profiles.normalize_atm multiplies by the
         coupling and divides.  reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed
         after the copy."""
-        ns = getattr(self, "_atm_ns", None)
-        if ns is None:
-            raise PigsError("atm_read: atm_init first")
-        W = self.n_walkers
-        out = {"T": np.zeros((W, ns)), "ntrip": np.zeros((W, ns), np.int64), "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_atm_read(self.h, _d(out["T"]), _l(out["ntrip"]), _l(out["samples"]), mask), "pigs_atm_read")
-        return out
+        return self._read("atm", "_atm_ns", lambda ns: [("T", _F, (ns,)), ("ntrip", _N, (ns,)), ("samples", _N, ())], reset)
 
     # ---- momentum distribution and one-body density matrix (pigs_nk_*: cosine sums per walker and vector, 64-bit counts)
     def nk_init(self, nmax, nbin):
@@ -834,16 +770,11 @@ class PigsContext:
         _chk(self.L, self.L.pigs_nk_init(self.h, int(nmax), int(nbin)), "pigs_nk_init")
         nq = C.c_int64(0)
         _chk(self.L, self.L.pigs_nk_count(self.h, C.byref(nq)), "pigs_nk_count")
-        self._nk_nq, self._nk_nbin = int(nq.value), int(nbin)
+        self._nk = (int(nq.value), int(nbin))
 
     def nk_vectors(self):
         """The stored vectors n [Nq, dim] (int32) in the library's enumeration order (that of sqv_vectors)."""
-        nq = getattr(self, "_nk_nq", None)
-        if nq is None:
-            raise PigsError("nk_vectors: nk_init first")
-        n = np.zeros((nq, self.cfg.dim), np.int32)
-        _chk(self.L, self.L.pigs_nk_vectors(self.h, _i(n)), "pigs_nk_vectors")
-        return n
+        return self._vectors("nk", getattr(self, "_nk", (None,))[0])
 
     def nk_accumulate(self, walkers=None):
         """Queue the open-sector samples of the last sampler_step of `walkers` (None: all) on the context's stream; does
@@ -872,16 +803,9 @@ class PigsContext:
         axis k of the box), nopen [W] the samples (the sum of the vector n = 0) and ninside [W] those within rcut (int64);
         profiles.normalize_nk and normalize_nrvec divide them.  reset: None, True (all walkers) or a per-walker mask of
         walkers whose sums are zeroed after the copy."""
-        nq = getattr(self, "_nk_nq", None)
-        if nq is None:
-            raise PigsError("nk_read: nk_init first")
-        W = self.n_walkers
-        out = {"C": np.zeros((W, nq)), "H": np.zeros((W,) + (self._nk_nbin,) * self.cfg.dim, np.int64),
-               "nopen": np.zeros(W, np.int64), "ninside": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_nk_read(self.h, _d(out["C"]), _l(out["H"]), _l(out["nopen"]), _l(out["ninside"]), mask),
-             "pigs_nk_read")
-        return out
+        dim = self.cfg.dim
+        return self._read("nk", "_nk", lambda st: [
+            ("C", _F, (st[0],)), ("H", _N, (st[1],) * dim), ("nopen", _N, ()), ("ninside", _N, ())], reset)
 
     # ---- a crystal seen from its lattice (pigs_lat_*: moments of the displacement from the nearest site, 64-bit counts)
     def lat_init(self, sites, nbin, rmax, window=0, cm=True):
@@ -905,17 +829,10 @@ class PigsContext:
         nassigned [W, 2 window + 1], nlost [W], occ [W, 2 window + 1, 4] (sites with 0, 1, 2, >= 3 particles), hr [W, nbin],
         hx [W, dim, 2 nbin], hop1 [W], hopw [W], samples [W]; profiles.normalize_lat divides them.  reset: None, True (all
         walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        if getattr(self, "_lat", None) is None:
-            raise PigsError("lat_read: lat_init first")
-        ns, nbin = self._lat
-        W, dim = self.n_walkers, self.cfg.dim
-        i64 = lambda *shape: np.zeros(shape, np.int64)
-        out = {"mom": np.zeros((W, ns, 2 + dim)), "nassigned": i64(W, ns), "nlost": i64(W), "occ": i64(W, ns, 4),
-               "hr": i64(W, nbin), "hx": i64(W, dim, 2 * nbin), "hop1": i64(W), "hopw": i64(W), "samples": i64(W)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_lat_read(self.h, _d(out["mom"]), *(_l(out[k]) for k in (
-            "nassigned", "nlost", "occ", "hr", "hx", "hop1", "hopw", "samples")), mask), "pigs_lat_read")
-        return out
+        dim = self.cfg.dim
+        return self._read("lat", "_lat", lambda st: [
+            ("mom", _F, (st[0], 2 + dim)), ("nassigned", _N, (st[0],)), ("nlost", _N, ()), ("occ", _N, (st[0], 4)),
+            ("hr", _N, (st[1],)), ("hx", _N, (dim, 2 * st[1])), ("hop1", _N, ()), ("hopw", _N, ()), ("samples", _N, ())], reset)
 
     # ---- the superfluid fraction from the centre-of-mass diffusion along tau (pigs_sf_*: raw sums per walker, lag and axis)
     def sf_init(self, Ntau=0, window=0):
@@ -934,16 +851,10 @@ class PigsContext:
         unfolded centre of mass, and of the unfolded particles), nwrap [W] (int64: the link components that were folded)
         and samples [W] (int64); and "window", the window they were taken over, which profiles.normalize_sf divides by.
         reset: None, True (all walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        if getattr(self, "_sf", None) is None:
-            raise PigsError("sf_read: sf_init first")
-        nl, window = self._sf
-        W, dim = self.n_walkers, self.cfg.dim
-        out = {"C": np.zeros((W, nl, dim)), "D": np.zeros((W, nl, dim)), "nwrap": np.zeros(W, np.int64),
-               "samples": np.zeros(W, np.int64)}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_sf_read(self.h, _d(out["C"]), _d(out["D"]), _l(out["nwrap"]), _l(out["samples"]), mask),
-             "pigs_sf_read")
-        out["window"] = window
+        dim = self.cfg.dim
+        out = self._read("sf", "_sf", lambda st: [
+            ("C", _F, (st[0], dim)), ("D", _F, (st[0], dim)), ("nwrap", _N, ()), ("samples", _N, ())], reset)
+        out["window"] = self._sf[1]
         return out
 
     # ---- the cluster-size distribution over a slice window (pigs_cl_*: 64-bit counts and the sums of Rg^2 per walker and size)
@@ -965,14 +876,9 @@ class PigsContext:
         largest cluster has size s), nbond [W] and samples [W] (int64: bonds, and slices), rg2 [W, Np] (float64: the sum
         of the clusters' Rg^2 per size); and "window".  profiles.normalize_cl divides them.  reset: None, True (all
         walkers) or a per-walker mask of walkers whose sums are zeroed after the copy."""
-        if getattr(self, "_cl", None) is None:
-            raise PigsError("cl_read: cl_init first")
-        W, Np = self.n_walkers, self.cfg.Np
-        out = {"nsize": np.zeros((W, Np), np.int64), "nlarge": np.zeros((W, Np), np.int64), "nbond": np.zeros(W, np.int64),
-               "samples": np.zeros(W, np.int64), "rg2": np.zeros((W, Np))}
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_cl_read(self.h, _l(out["nsize"]), _l(out["nlarge"]), _l(out["nbond"]), _l(out["samples"]),
-                                         _d(out["rg2"]), mask), "pigs_cl_read")
+        Np = self.cfg.Np
+        out = self._read("cl", "_cl", lambda _: [
+            ("nsize", _N, (Np,)), ("nlarge", _N, (Np,)), ("nbond", _N, ()), ("samples", _N, ()), ("rg2", _F, (Np,))], reset)
         out["window"] = self._cl
         return out
 
@@ -1003,16 +909,10 @@ class PigsContext:
         [W, ntau + 1] (int64: pairs together in slice a, in a + l, in both, and the origins per lag); and "window", "ntau".
         profiles.normalize_pc divides them.  reset: None, True (all walkers) or a per-walker mask of walkers whose sums are
         zeroed after the copy."""
-        if getattr(self, "_pc", None) is None:
-            raise PigsError("pc_read: pc_init first")
-        W, Np, nl = self.n_walkers, self.cfg.Np, self._pc[1] + 1
-        out = {k: np.zeros((W, 8), np.int64) for k in ("nwrap", "mwrap", "swrap")}
-        out.update({"nfin": np.zeros((W, Np), np.int64), "samples": np.zeros(W, np.int64), "rg2u": np.zeros((W, Np))})
-        out.update({k: np.zeros((W, nl), np.int64) for k in ("first", "second", "both", "norig")})
-        mask = self._reset_mask(reset)
-        _chk(self.L, self.L.pigs_pc_read(self.h, _l(out["nwrap"]), _l(out["mwrap"]), _l(out["swrap"]), _l(out["nfin"]),
-                                         _l(out["samples"]), _d(out["rg2u"]), _l(out["first"]), _l(out["second"]),
-                                         _l(out["both"]), _l(out["norig"]), mask), "pigs_pc_read")
+        Np = self.cfg.Np
+        out = self._read("pc", "_pc", lambda st: [
+            ("nwrap", _N, (8,)), ("mwrap", _N, (8,)), ("swrap", _N, (8,)), ("nfin", _N, (Np,)), ("samples", _N, ()),
+            ("rg2u", _F, (Np,))] + [(k, _N, (st[1] + 1,)) for k in ("first", "second", "both", "norig")], reset)
         out["window"], out["ntau"] = self._pc
         return out
 

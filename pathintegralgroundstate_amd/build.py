@@ -9,8 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpigs_hip.so")
-SOURCES = ["pigs_k1.hip", "pigs_sampler.hip", "pigs_diag.hip", "pigs_cm.hip", "pigs_kernels.hip", "pigs_density.hip", "pigs_fqt.hip", "pigs_sqv.hip", "pigs_fqv.hip", "pigs_fqs.hip", "pigs_grv.hip", "pigs_tau.hip", "pigs_bop.hip", "pigs_vh.hip", "pigs_g3.hip", "pigs_atm.hip", "pigs_nk.hip", "pigs_lat.hip", "pigs_sf.hip", "pigs_cl.hip", "pigs_pc.hip", "pigs_capi.hip", "pigs_comm.cpp", "pigs_tables.cpp"]
-HEADERS = ["pigs_device.h", "pigs_k1_device.h", "pigs_kernels.h", "pigs_walker_split.h", "pigs_comm.h", "pigs_sampler_device.h", "pigs_sqv_device.h", "pigs_slice_device.h", "pigs_launch.h", "pigs_cl_device.h"]
+SOURCES = ["pigs_k1.hip", "pigs_sampler.hip", "pigs_diag.hip", "pigs_cm.hip", "pigs_kernels.hip", "pigs_density.hip", "pigs_fqt.hip", "pigs_sqv.hip", "pigs_fqv.hip", "pigs_fqs.hip", "pigs_grv.hip", "pigs_tau.hip", "pigs_bop.hip", "pigs_vh.hip", "pigs_g3.hip", "pigs_atm.hip", "pigs_nk.hip", "pigs_lat.hip", "pigs_sf.hip", "pigs_cl.hip", "pigs_pc.hip", "pigs_capi.hip", "pigs_capi_families.hip", "pigs_comm.cpp", "pigs_tables.cpp"]
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 # -ffp-contract=off: every per-pair term must round exactly like the reference's x86-64
 # build (no FMA); hipcc's default is fast contraction.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
@@ -61,7 +61,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), int(os.environ.get("MAX_JOBS", 16)))) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     lib = os.environ.get("PIGS_LIB_OUT", LIB)          # experiment builds go next to the product library
     cmd = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", lib, "-ldl"]

@@ -233,3 +233,61 @@ def test_walker_split_matches_the_stated_rule(tmp_path):
         for (cap, u, l, sw), ws, line in zip(cases, want, lines):
             got = [[int(x) for x in part.split()] for part in line.split(";") if part.strip()]
             assert [(g[0], g[2:]) for g in got] == ws and all(g[1] == len(g) - 2 for g in got), (name, cap, u, l, sw)
+
+
+def test_family_sizes_match_the_stated_rules(tmp_path):
+    """csrc/pigs_family_sizes.h (the verdicts every pigs_*_init asks for) compiled for the CPU against the rules restated
+    here, at their edges: the walkers a scratch budget holds one byte below, at and above k slots (k = 1, 2, 256, 257; W
+    below and above the list's 256; less than one slot gives 1), the 2 GiB refusal at the last accepted and the first
+    refused walker count (from exact integers: W x elements x 8 <= 2^31 is accepted) for 1, 3, 2^20 + 1 and 2^28
+    elements per walker, a cut-off at the smallest half side of an unequal 1D..3D box, one ulp above it and at (1 + 4 eps)
+    times it, without and with g3's tolerance, and nan, inf, 0 and a negative value, and the window and lag ranges at -1,
+    0, the limit and the limit + 1.  Once as built, once under -fsanitize=address,undefined."""
+    import math
+    import subprocess
+    eps = np.finfo(np.float64).eps
+    cases, want = [], []
+    for slot in (8, 24, 4096, 123457):
+        for k in (1, 2, 256, 257):
+            for budget in (k * slot - 1, k * slot, k * slot + 1):
+                for W in (1, 3, 255, 256, 257, 1000):
+                    cases.append("S %d 256 %d %d" % (W, budget, slot))
+                    want.append(max(1, min(W, 256, budget // slot)))
+        cases.append("S 64 256 %d %d" % (slot // 2, slot))
+        want.append(1)
+    assert {1, 2, 3, 255, 256} <= set(want) and 257 not in want
+    for e in (1, 3, 2 ** 20 + 1, 2 ** 28):
+        last = 2 ** 31 // (8 * e)                                   # the largest W with W e 8 <= 2^31
+        assert last * e * 8 <= 2 ** 31 < (last + 1) * e * 8
+        for W, refused in ((last, 0), (last + 1, 1), (1, 0), (2 * last + 1, 1)):
+            cases.append("G %d %d" % (W, e))
+            want.append(refused)
+    for half in ((1.75,), (3.1, 2.3), (2.3, 3.1), (4.0, 5.5, 3.3), (3.3, 5.5, 4.0), (5.5, 3.3, 4.0), (0.1 * 3, 7.0, 7.0)):
+        h = min(half)
+        for tol in (0.0, 4.0 * eps):
+            for r in (h, math.nextafter(h, math.inf), h * (1.0 + 4.0 * eps), 0.5 * h, 2.0 * h, math.nan, math.inf, 0.0, -h,
+                      -math.inf):
+                cases.append("C %d %s %s %s %s %s" % (len(half), *((float(x).hex() for x in (half + (1.0, 1.0))[:3])),
+                                                      float(r).hex() if math.isfinite(r) else repr(r), float(tol).hex()))
+                want.append(int(math.isfinite(r) and r > 0.0 and all(r <= x * (1.0 + tol) for x in half)))
+            # at, one ulp above and 4 eps above the smallest half side: the tolerance decides the last two
+            assert want[-10:-7] == ([1, 1, 1] if tol else [1, 0, 0]) and want[-7:] == [1, 0, 0, 0, 0, 0, 0]
+    for Nb in (1, 3, 40):
+        for window in (-1, 0, Nb, Nb + 1):
+            cases.append("W %d %d" % (window, Nb))
+            want.append(int(0 <= window <= Nb))
+    for window in (0, 1, 7):
+        for Ntau in (-1, 0, 2 * window, 2 * window + 1):
+            cases.append("L %d %d" % (Ntau, window))
+            want.append(int(0 <= Ntau <= 2 * window))
+    src = os.path.join(ROOT, "tests", "shim", "family_sizes_check.cpp")
+    inc = "-I" + os.path.join(ROOT, "pathintegralgroundstate_amd", "csrc")
+    for name, flags in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exe = str(tmp_path / ("family_sizes_" + name))
+        subprocess.check_call(["g++", "-std=c++17", "-Wall"] + flags + [inc, src, "-o", exe])
+        out = subprocess.run([exe], input="\n".join(cases) + "\n", capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, (name, out.returncode, out.stderr[-2000:])
+        got = [int(x) for x in out.stdout.split()]
+        assert len(got) == len(cases)
+        bad = [(c, w, g) for c, w, g in zip(cases, want, got) if w != g]
+        assert not bad, (name, bad[:5])
