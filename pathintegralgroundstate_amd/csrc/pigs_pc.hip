@@ -42,7 +42,8 @@
 //   k_pc<1> / <2> / <3>, recomputed:  62 / 62 / 62 VGPRs, no VGPR or SGPR spilled, 0 bytes of scratch memory per lane,
 //                                     8 waves per SIMD
 //     both: 256 bytes of static LDS (the vote of __syncthreads_or) beside the dynamic pc_lds_bytes: 24 644 bytes at
-//     Np = 256 in 3D with the bit rows, 19 268 bytes at Np = 300 without
+//     Np = 256 in 3D with the bit rows, 19 268 bytes at Np = 300 without, 131 140 bytes at Np = kClNpMax = 2048 (of
+//     kClLdsBudget = 163 840; the grant of launch<> starts at Np = 1023 in 3D, 1260 in 2D, 1488 in 1D)
 //   k_pc_persist:                     50 VGPRs, no spills, no scratch memory, 12 bytes of static LDS beside 8 Np dynamic,
 //                                     8 waves per SIMD
 //   k_cl with the labelling loop from pigs_cl_device.h keeps the figures of pigs_cl.hip's header, form by form.

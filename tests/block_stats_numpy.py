@@ -28,6 +28,16 @@ Normalisations (one walker, one block with S samples, i.e. S diagonal steps in t
                        rho_site = hr / (S ns nsite dV_j); P(u_k) = hx / (assigned of the window x rmax / nbin)
   superfluid           Dcm_k = C / (S n_pairs(l) Np), rhos_k = Dcm_k / (2 lam l dt) and its mean over the axes (no lag 0),
                        the unfolded msd_k = D / (S n_pairs(l) Np), cross_k = Dcm_k - msd_k; lam = 1/2
+  clusters             S slices: n(s) = nsize / S, fraction = s n(s) / Np, P_largest(s) = nlarge / S, the summed Rg^2 of size s
+                       per slice rg2 / S; per block the clusters per slice sum_s n(s), <largest>/Np = sum s nlarge / (S Np),
+                       the mean size sum s^2 nsize / sum s nsize, the bonds per particle nbond / (S Np).  The files' <Rg^2>(s) is
+                       a ratio of two block means: <rg2 / S> / <n(s)>, its error the numerator's over <n(s)>
+  percolation          the share of the slices whose OR of masks has bit k: sum swrap[mask with bit k] / S, along any axis
+                       (mask != 0) and along all dim; P_inf = sum_{mask != 0} mwrap / (S Np); the mean finite size
+                       sum s^2 nfin / sum s nfin, 0 -- not NaN -- in a block without finite clusters; n_fin(s) / Np =
+                       nfin / (S Np); the summed unfolded Rg^2 per slice rg2u / S, and <Rg^2>(s) = <rg2u / S> / (Np <n_fin/Np>);
+                       the pairs per origin first, second, both / norig per lag; C(l) = <both> / <first> and the Jaccard index
+                       <both> / (<first> + <second> - <both>), ratios of block means (0 for a zero denominator)
 
 Statistics: a block counts for a walker only if the walker had a diagonal step in it.  A file's mean is the mean of the
 counted block values; its error the "variance" of the reference's files, sqrt((<b^2> - <b>^2) / n) over the n counted
@@ -300,6 +310,57 @@ def norm_sf(C, D, S, window, Np, dt, lam=0.5):
                     tot = tot + out["rhos"][..., l, k]
                 out["rhos_mean"][..., l] = tot / dim
     return out
+
+
+def norm_cl(nsize, nlarge, nbond, rg2, S, Np):
+    """nsize, nlarge, rg2 [..., Np], nbond, S [...]: the block values of the cluster family, from include/pigs_hip.h and
+    INTEGRATION.md.  "n", "fraction", "p_largest", "G" [..., Np] (G: the summed Rg^2 of a size per slice -- additive, so
+    that the files' <Rg^2>(s) = <G> / <n> over the blocks) and "block" [..., 4]: clusters per slice, <largest cluster> / Np,
+    the mean cluster size, bonds per particle."""
+    nsize, nlarge, rg2 = (np.asarray(a, np.float64) for a in (nsize, nlarge, rg2))
+    s = np.arange(1, Np + 1, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        Sx = _s(S, 1)
+        S = np.asarray(S, np.float64)
+        n = nsize / Sx
+        block = np.stack([n.sum(axis=-1), (s * nlarge).sum(axis=-1) / (S * Np), (s * s * nsize).sum(axis=-1) / (s * nsize).sum(axis=-1),
+                          np.asarray(nbond, np.float64) / (S * Np)], axis=-1)
+        return {"n": n, "fraction": s * n / Np, "p_largest": nlarge / Sx, "G": rg2 / Sx, "block": block}
+
+
+def norm_pc(nwrap, mwrap, swrap, nfin, rg2u, first, second, both, norig, S, Np, dim):
+    """nwrap, mwrap, swrap [..., 8], nfin, rg2u [..., Np], first, second, both, norig [..., ntau + 1], S [...]: the block
+    values of the percolation family.  "block" [..., 7]: the share of the slices with a cluster that wraps along x, y, z (0
+    beyond dim), along any axis, along all dim axes, P_inf, and the mean finite size -- 0, not NaN, in a block without
+    finite clusters; "nfin" = nfin / (S Np) and "G" = rg2u / S [..., Np]; "pairs" [..., ntau + 1, 3]: first, second, both per
+    origin."""
+    del nwrap                                                           # (the clusters per mask reach no file)
+    mwrap, swrap, nfin, rg2u = (np.asarray(a, np.float64) for a in (mwrap, swrap, nfin, rg2u))
+    s = np.arange(1, Np + 1, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        Sx = _s(S, 1)
+        S = np.asarray(S, np.float64)
+        cols = []
+        for k in range(3):
+            share = np.zeros(S.shape)
+            for mask in range(8):
+                if k < dim and (mask >> k) & 1:
+                    share = share + swrap[..., mask]
+            cols.append(share / S if k < dim else share)
+        cols.append(swrap[..., 1:].sum(axis=-1) / S)
+        cols.append(swrap[..., (1 << dim) - 1] / S)
+        cols.append(mwrap[..., 1:].sum(axis=-1) / (S * Np))
+        den = (s * nfin).sum(axis=-1)
+        cols.append(np.where(den > 0, (s * s * nfin).sum(axis=-1) / np.where(den > 0, den, 1.0), 0.0))
+        no = np.asarray(norig, np.float64)
+        pairs = np.stack([np.asarray(a, np.float64) / no for a in (first, second, both)], axis=-1)
+        return {"block": np.stack(cols, axis=-1), "nfin": nfin / (Sx * Np), "G": rg2u / Sx, "pairs": pairs}
+
+
+def ratio_of_means(num, den):
+    """num / den where den > 0, else 0: <Rg^2>(s), C(l) and the Jaccard index of the cluster files."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
 
 
 LAT_OUT = ("u2", "uk2", "gamma_tau", "u2_mean", "gamma", "alpha2", "vacant", "multiple", "hops_link", "hops_window",

@@ -4,7 +4,7 @@ image numbers to its parent -- another algorithm than the device's sweeps from t
 that close a walk inside one tree, the unfolded separations of the finite clusters with the same IEEE operations in the
 same order, and a plain double loop over origins and lags for the persistence counts.  Pinned to a flood fill with image
 numbers, to rings, lattices and closed forms by tests/test_pc_numpy_host.py.  The input builders of the percolation tests
-are here too; those of cl_numpy serve as they are.
+are here too (among them the helices, whose image numbers run far from zero); those of cl_numpy serve as they are.
 
 Paths are [walker, slice, particle, axis]."""
 import numpy as np
@@ -187,6 +187,79 @@ def lattice(n, L, dim):
     return cn.wrap((g + 0.25) * (L / n), L)
 
 
+def root_mid_chain(n, at, seed):
+    """A shuffled order whose particle 0 -- the root of a cluster that holds it -- sits at point `at` of the line."""
+    order = np.random.default_rng(seed).permutation(n)
+    z = int(np.nonzero(order == 0)[0][0])
+    order[z], order[at] = order[at], 0
+    return order
+
+
+def _line(n, step, origin, L, order):
+    """(X, U): n points at origin + p step, particle order[p] at point p; U unfolded, X wrapped into the cell."""
+    U = np.zeros((n, len(step)))
+    U[np.asarray(order)] = np.asarray(origin, dtype=np.float64) + np.arange(n)[:, None] * np.asarray(step, dtype=np.float64)
+    return wrap_cell(U, L), U
+
+
+def wrap_cell(U, L):
+    X = cn.wrap(U, np.asarray(L, dtype=np.float64))
+    assert np.all(np.abs(X) < 0.5 * np.asarray(L)), "a point on a face"
+    return X
+
+
+HELIX_LX, HELIX_DX, HELIX_CLIMB = 8.0, 0.9, 1.2                         # in units of rc
+
+
+def helix(n, dim, sign=1, rc=1.0, order=None):
+    """A chain with steps of 0.9 rc along x (sign: towards +x or -x) in a cell of Lx = 8 rc, which climbs 1.2 rc along y per
+    turn in a cell too tall to wrap in y (3D: z constant, Lz = 8 rc): neighbours along the line are 0.91 rc apart, second
+    neighbours 1.82 rc and successive turns 1.19 rc, so the bonds are those of the line and the cluster is ONE finite
+    cluster that goes through the x faces once every 8.9 steps.  Returns (X, L, rc, U): U the unfolded points, on a
+    line at equal spacing; particle order[p] at point p (default: root_mid_chain at n // 3)."""
+    assert dim in (2, 3)
+    dy = HELIX_CLIMB * HELIX_DX / HELIX_LX
+    L = [HELIX_LX * rc, (n * dy + 4.0) * rc] + [8.0 * rc] * (dim - 2)
+    step = [sign * HELIX_DX * rc, dy * rc] + [0.0] * (dim - 2)
+    origin = [0.05 * rc, -0.5 * (n - 1) * dy * rc] + [1.0 * rc] * (dim - 2)
+    order = root_mid_chain(n, n // 3, n + dim) if order is None else order
+    X, U = _line(n, step, origin, L, order)
+    return X, L, rc, U
+
+
+def double_helix(n, sy=1, rc=1.0, order=None):
+    """3D: the line advances by (0.64, 0.48 sy) rc per step along the diagonal of a cell of 8 rc x 6 rc -- 12.5 steps per turn
+    through the x AND the y faces, after which it is back over its own track -- and climbs 1.2 rc along z per turn: one
+    finite cluster whose image numbers along x and y grow together (sy = +1) or with opposite signs (sy = -1)."""
+    dz = HELIX_CLIMB * 0.64 / 8.0
+    L = [8.0 * rc, 6.0 * rc, (n * dz + 4.0) * rc]
+    order = root_mid_chain(n, n // 3, n + 7 + sy) if order is None else order
+    X, U = _line(n, [0.64 * rc, 0.48 * sy * rc, dz * rc], [0.05 * rc, 0.03 * rc, -0.5 * (n - 1) * dz * rc], L, order)
+    return X, L, rc, U
+
+
+def double_winding(n, rc=1.0, order=None):
+    """2D: a closed line of n points that goes twice round x and once round y before its last point bonds to its first:
+    one wrapping cluster of mask 3 whose one closing bond has a mismatch of 2 along x and 1 along y.  Steps of
+    (0.6, 0.4) rc; the two strands are half the cell apart."""
+    L = [0.3 * n * rc, 0.4 * n * rc]
+    order = root_mid_chain(n, n // 3, n + 11) if order is None else order
+    X, U = _line(n, [2.0 * L[0] / n, L[1] / n], [0.05 * rc, 0.03 * rc], L, order)
+    return X, L, rc, U
+
+
+def far_images(n=300):
+    """name -> (X, L, rc, U): the slices whose image numbers leave {-1, 0, +1}."""
+    out = {}
+    for dim in (2, 3):
+        for sign, tag in ((1, "plus"), (-1, "minus")):
+            out[f"helix{dim}d_{tag}"] = helix(n, dim, sign)
+    out["double_helix_same"] = double_helix(n, 1)
+    out["double_helix_opposite"] = double_helix(n, -1)
+    out["double_winding"] = double_winding(n)
+    return out
+
+
 RING_L = [270.0, 8.0, 8.0]                                              # 300 points at spacing 0.9 close a ring along x
 FACE_L = [600.0, 8.0, 8.0]
 
@@ -209,4 +282,5 @@ def hand_built():
     X[:, 0] = -290.0 + 1.9 * np.arange(n)
     X[[63, 64, 255, 256]] = [[299.75, 2.0, 1.0], [-299.875, 2.0, 1.0], [-299.875, 2.375, 1.0], [-299.875, 2.375, 1.375]]
     out["words_and_face"] = (X, FACE_L, 0.5)
+    out.update({name: v[:3] for name, v in far_images(n).items()})
     return out

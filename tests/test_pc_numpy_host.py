@@ -141,3 +141,96 @@ def test_cluster_across_the_mask_words_and_a_face():
     assert np.array_equal(label, want) and smask == 0 and nfin[3] == 1 and nfin[0] == 296
     assert np.any(pn.fold_numbers(X, L)[63, 64] != 0)                   # the bond 63-64 goes through the face
     assert G[3] == cn.slice_sums(X, L, rc)[3][3] and G[3] > 0
+
+
+# ---- image numbers far from zero ---------------------------------------------------------------------------------------
+FAR = pn.far_images()
+
+
+def _crossings(U, L, root=0):
+    """Per particle and axis, the faces between the root's cell and the particle's, signed, from the unfolded points."""
+    cell = np.floor((U + 0.5 * np.asarray(L)) / np.asarray(L)).astype(np.int64)
+    return cell - cell[root]
+
+
+def check_helix(X, L, rc, U, axes):
+    """One finite cluster of all n particles whose image numbers are the cells of the unfolded line (far from zero along
+    `axes`, both signs), and whose unfolded Rg^2 is the closed form of n collinear points at equal spacing."""
+    n, dim = X.shape
+    bond, nf = pn.bonds_of(X, L, rc), pn.fold_numbers(X, L)
+    assert int(np.triu(bond, 1).sum()) == n - 1                         # the bonds of the line, none between turns
+    label, m, mask = pn.components(bond, nf)
+    assert np.unique(label).size == 1 and not np.any(label) and not np.any(mask)
+    cross = _crossings(U, L)
+    assert np.array_equal(np.abs(m), np.abs(cross)) and (np.array_equal(m, cross) or np.array_equal(m, -cross))
+    for k in range(dim):
+        if k in axes:
+            assert np.abs(m[:, k]).max() == np.abs(cross[:, k]).max() >= 15 and m[:, k].min() <= -5 and m[:, k].max() >= 5
+        else:
+            assert not np.any(m[:, k])
+    fl, fm, fmask = _flood(bond, nf)
+    assert np.array_equal(fl, label) and np.array_equal(fm, m) and not np.any(fmask)
+    nwrap, mwrap, smask, nfin, G, _, _ = pn.slice_sums(X, L, rc)
+    assert smask == 0 and nwrap.tolist() == [1] + [0] * 7 and mwrap[0] == n and nfin[n - 1] == 1 and nfin.sum() == 1
+    return m, G[n - 1]
+
+
+@pytest.mark.parametrize("name", ["helix2d_plus", "helix2d_minus", "helix3d_plus", "helix3d_minus", "double_helix_same",
+                                  "double_helix_opposite"])
+def test_helix_is_one_finite_cluster_with_the_closed_form(name):
+    X, L, rc, U = FAR[name]
+    n = X.shape[0]
+    axes = (0, 1) if name.startswith("double") else (0,)
+    m, g = check_helix(X, L, rc, U, axes)
+    climb = X.shape[1] - 1 if name.startswith("double") else 1          # the axis that never wraps sorts the line
+    s = U[np.argsort(U[:, climb])]
+    d2 = float(((s[1] - s[0]) ** 2).sum())
+    assert np.allclose(np.diff(s, axis=0), s[1] - s[0], rtol=0, atol=1e-9)     # collinear, equal steps
+    want = d2 * (n * n - 1) / 12.0
+    tol = (n * (n - 1) / 2 + n + 8) * 2.0 ** -53
+    print(f"{name}: max |m| {np.abs(m).max(axis=0).tolist()}, rg2u / closed form - 1 = {g / want - 1.0:.3e} (bound {tol:.3e})")
+    assert abs(g - want) <= tol * want
+    assert np.array_equal(X, pn.hand_built()[name][0])                 # the slice the GPU test runs
+    folded = cn.slice_sums(X, L, rc)[3][n - 1]
+    assert 0 < folded < 0.1 * want                                      # the folded r_ij stay within half the short side
+    if name == "double_helix_opposite":
+        assert np.array_equal(np.sign(m[:, 0]) * np.sign(m[:, 1]) <= 0, np.ones(n, bool)) and np.any(m[:, 0] * m[:, 1] < -25)
+    if name == "double_helix_same":
+        assert np.all(m[:, 0] * m[:, 1] >= 0) and np.any(m[:, 0] * m[:, 1] > 25)
+
+
+def test_helix_windings_mirror_each_other():
+    """Towards +x and towards -x: the image numbers along x have opposite signs, particle by particle."""
+    for dim in (2, 3):
+        a = pn.components(pn.bonds_of(*FAR[f"helix{dim}d_plus"][:3]), pn.fold_numbers(*FAR[f"helix{dim}d_plus"][:2]))[1]
+        b = pn.components(pn.bonds_of(*FAR[f"helix{dim}d_minus"][:3]), pn.fold_numbers(*FAR[f"helix{dim}d_minus"][:2]))[1]
+        assert np.abs(a[:, 0]).max() >= 20 and np.abs(np.abs(a[:, 0]) - np.abs(b[:, 0])).max() <= 1
+        assert np.all(a[:, 0] * b[:, 0] <= 0)
+
+
+def test_double_winding_wraps_with_mask_3_and_a_mismatch_of_two():
+    X, L, rc, U = FAR["double_winding"]
+    n = X.shape[0]
+    bond, nf = pn.bonds_of(X, L, rc), pn.fold_numbers(X, L)
+    assert int(np.triu(bond, 1).sum()) == n                             # n bonds on n particles: one closes the line
+    label, m, mask = pn.components(bond, nf)
+    assert not np.any(label) and np.all(mask == 3)
+    i, j = np.nonzero(np.triu(bond, 1))
+    mis = m[i] - m[j] - nf[i, j]
+    bad = np.nonzero(np.any(mis != 0, axis=1))[0]
+    assert bad.size == 1 and np.abs(mis[bad[0]]).tolist() == [2, 1]
+    assert np.array_equal(_flood(bond, nf)[2], mask)
+    nwrap, mwrap, smask, nfin, G, _, _ = pn.slice_sums(X, L, rc)
+    assert smask == 3 and nwrap[3] == 1 and mwrap[3] == n and nwrap.sum() == 1 and not np.any(nfin) and not np.any(G)
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+def test_helix_at_the_size_limit(dim):
+    """The slice tests/test_gpu_cl_pc_limits.py runs at kClNpMax = 2048: |m_x| passes 150."""
+    n = 2048
+    X, L, rc, U = pn.helix(n, dim)
+    m, g = check_helix(X, L, rc, U, (0,))
+    s = U[np.argsort(U[:, 1])]
+    want = float(((s[1] - s[0]) ** 2).sum()) * (n * n - 1) / 12.0
+    assert abs(g - want) <= (n * (n - 1) / 2 + n + 8) * 2.0 ** -53 * want
+    assert np.abs(m[:, 0]).max() >= 150 and m[:, 0].min() <= -70
