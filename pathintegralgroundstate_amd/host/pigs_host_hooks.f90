@@ -200,22 +200,8 @@ contains
        ad = ad+gd; ad2 = ad2+gd*gd
        as = as+gs; as2 = as2+gs*gs
     end do
-    call write_vh(cname(fd),p,dt,Ntau,nb,ad,ad2)
-    call write_vh(cname(fs),ps,dt,Ntau,nb,as,as2)
-  contains
-    function cname(c) result(f)
-      character(kind=c_char), intent(in) :: c(*)
-      character(len=:), allocatable :: f
-      integer :: n,i
-      n = 0
-      do while (c(n+1)/=c_null_char)
-         n = n+1
-      end do
-      allocate (character(len=n) :: f)
-      do i=1,n
-         f(i:i) = c(i)
-      end do
-    end function cname
+    call write_vh(cstring(fd),p,dt,Ntau,nb,ad,ad2)
+    call write_vh(cstring(fs),ps,dt,Ntau,nb,as,as2)
   end subroutine hs_vh_files
 
   ! The triplet normalisation and writers of the front end on given counts: nb blocks of one walker, ctrip

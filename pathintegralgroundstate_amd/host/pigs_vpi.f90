@@ -118,8 +118,8 @@ program pigs_vpi
   use pigs_rng
   use pigs_sampler
   use pigs_estimators
-  use pigs_block_stats
   use pigs_families
+  use pigs_shard
   use omp_lib
 
   implicit none
@@ -514,532 +514,488 @@ contains
 
   !---------------------------------------------------------------------
   ! one shard: the walkers lo(ish)..hi(ish) on context ctxs(ish), the reference's block / step structure
-  ! (vpi.f90:244-588) for all of them in lock-step.  Everything below is private to the calling thread.
+  ! (vpi.f90:244-588) for all of them in lock-step, one line per phase.  The shard's state (pigs_shard) is a local of this
+  ! procedure and so private to the calling thread.
   subroutine run_shard(ish)
-  integer, intent(in) :: ish
-  integer(c_int32_t) :: rpos
-  integer :: NW,w0
-  logical :: trace
-  character(len=8) :: envbuf
+    integer, intent(in) :: ish
+    type(shard_state) :: sh
+    integer    :: iblock,istep
+    integer(8) :: c0,c1,crate
 
-  type(sampler_t)    :: s
-  type(est_params)   :: ep
-  type(c_ptr)        :: ctx
-  type(perm_state), allocatable :: perm(:)
-  integer :: w,k,ip,istep,iblock,istag,iobdm,j,nd,i,nvec,ndall,nall
-  integer, allocatable :: ipv(:),iupd(:),partner(:),diag_list(:)
-  logical, allocatable :: act(:),isopen0(:),swp(:)
-  integer(c_int32_t), allocatable :: wl(:)
-  real(8), allocatable :: E1(:),E2(:),K1(:),P1(:),Et(:),Kt(:),Pt(:)
-  real(8) :: E,Kin,Pot
+    call shard_setup(sh,ish)
+    do iblock=1,Nblock
+       call system_clock(c0,crate)
+       call sh%moves%reset()
+       call sh%en%reset()
+       call sh%core%reset()
+       ! the estimators of a step are queued at its end and collected by the NEXT step (collect_estimators), those of the
+       ! block's last step behind the loop
+       do istep=1,Nstep
+          if (device_sampler) then
+             call step_device(sh,istep)
+          else
+             call step_host(sh,iblock,istep)
+          end if
+          call queue_estimators(sh)
+       end do
+       call collect_estimators(sh)
+       call block_end(sh,iblock)
+       if (checkpointing) call block_checkpoint(sh)
+       call system_clock(c1)
+       if (ish==1) call block_report(sh,iblock,dble(c1-c0)/dble(crate))
+    end do
+    call shard_finish(sh)
+  end subroutine run_shard
 
-  ! per-walker counters and accumulators (one column per walker)
-  integer, allocatable :: acc_cm(:),acc_bd(:),acc_head(:),acc_tail(:),acc_cm_half(:),acc_bd_half(:)
-  integer, allocatable :: acc_head_half(:),acc_tail_half(:),acc_open(:),acc_close(:),acc_swap(:)
-  integer, allocatable :: try_open(:),try_close(:),try_swap(:)
-  real(8), allocatable :: try_cm(:),try_stag(:),try_cm_half(:),try_stag_half(:)
-  integer, allocatable :: idiag(:),idiag_aux(:),idiag_block(:),obdm_bl(:),diag_bl(:),ngr(:)
-  real(8), allocatable :: BE(:,:),BE2(:,:),BT(:,:),BT2(:,:),AE(:,:),AE2(:,:),AT(:,:),AT2(:,:)
-  real(8), allocatable :: gr(:,:),Sk(:,:,:),nrho(:,:,:)
-  real(8) :: t0,t1,mE(3),mT(3)
-  integer, allocatable :: ue(:),ut(:),uh(:)
-  integer :: ueav,utav
-  integer(8) :: c0,c1,crate
-  type(pigs_sweep_params) :: swp_par
-  real(8), allocatable, target :: gr_inc(:,:),sk_inc(:,:,:)
-  real(8), allocatable :: en9(:,:)
-  logical :: est_pending,est_have,pend_struct
-  integer :: pend_nd
-  integer, allocatable :: pend_list(:)
-  integer(c_int64_t), allocatable :: dev_acc(:,:),dev_acc0(:,:)
-  integer(c_int32_t), allocatable :: dev_open(:),dev_iworm(:),dev_ev(:,:),dev_reset(:)
-  real(8), allocatable :: dev_nrho(:,:,:)
-  character(len=32) :: suffix
+  ! sampler, initial configuration, upload, the device-resident sampler's start state, block statistics, families, units
+  subroutine shard_setup(sh,ish)
+    type(shard_state), intent(inout) :: sh
+    integer, intent(in) :: ish
+    type(family_run)        :: frun
+    type(pigs_sweep_params) :: swp_par
+    integer(c_int32_t) :: nev
+    character(len=8)   :: envbuf
+    character(len=32)  :: suffix
+    integer :: NW,w
 
-  ! the vector that meets the other shards' once per block (nvec doubles), and the block statistics of every estimator
-  ! file: one series per file, one count per family (pigs_block_stats).  g(r) and S(k) share the count of the walkers with
-  ! a diagonal block, n(r) has the one of the walkers whose OBDM block is full.
-  real(8), allocatable :: vec(:)
-  real(8) :: cnt_all(13)
-  type(block_series) :: sGr,sSk,sNr
-  type(block_count)  :: cGr,cNr
-  ! the accumulator families of the estimator keys (pigs_families): the shard's own set, what it is told of the run, and
-  ! of every block
-  type(family_set)  :: fams
-  type(family_run)  :: frun
-  type(family_info) :: info
+    call get_environment_variable('PIGS_VPI_TRACE',envbuf)
+    sh%trace = envbuf(1:1)=='1'
+    NW = hi(ish)-lo(ish)+1
+    sh%ish = ish; sh%NW = NW; sh%w0 = lo(ish)-1; sh%ctx = ctxs(ish)
 
-  call get_environment_variable('PIGS_VPI_TRACE',envbuf)
-  trace = envbuf(1:1)=='1'
-  NW  = hi(ish)-lo(ish)+1
-  w0  = lo(ish)-1                        ! global walker index = w0 + local index
-  ctx = ctxs(ish)
+    call sampler_init(sh%s,dim,Np,Nb,NW,trap,dt,density,CWorm,Lbox(1:dim),sh%ctx)
+    if (ish==1 .and. .not. device_sampler) print '(a,i6)','  > host threads per stage:',sh%s%nthr
+    sh%ep%dim = dim; sh%ep%Np = Np; sh%ep%Nbin = Nbin; sh%ep%Nk = Nk; sh%ep%Npw = Npw; sh%ep%trap = trap
+    sh%ep%rcut2 = rcut2; sh%ep%rbin = rbin; sh%ep%pi = pi; sh%ep%CWorm = CWorm
+    sh%ep%Lbox = Lbox; sh%ep%LboxHalf = 0.5d0*Lbox; sh%ep%qbin = 2.d0*pi/Lbox
 
-  call sampler_init(s,dim,Np,Nb,NW,trap,dt,density,CWorm,Lbox(1:dim),ctx)
-  if (ish==1 .and. .not. device_sampler) print '(a,i6)','  > host threads per stage:',s%nthr
-  ep%dim = dim; ep%Np = Np; ep%Nbin = Nbin; ep%Nk = Nk; ep%Npw = Npw; ep%trap = trap
-  ep%rcut2 = rcut2; ep%rbin = rbin; ep%pi = pi; ep%CWorm = CWorm
-  ep%Lbox = Lbox; ep%LboxHalf = 0.5d0*Lbox; ep%qbin = 2.d0*pi/Lbox
+    call initial_configuration(sh%s,sh%w0)
+    call sampler_upload(sh%s)
+    if (device_sampler) then
+       call fill_sweep_params(swp_par)
+       call pigs_check(pigs_sampler_init(sh%ctx,swp_par),'pigs_sampler_init')
+       call pigs_check(pigs_sampler_event_ints(sh%ctx,nev),'pigs_sampler_event_ints')
+       allocate (sh%dev%isopen(NW),sh%dev%iworm(NW),sh%dev%ev(nev,NW),sh%dev%nrho(0:Npw,Nbin,NW),sh%dev%reset(NW))
+       sh%dev%isopen = merge(1,0,sh%s%isopen); sh%dev%iworm = sh%s%iworm
+       call pigs_check(pigs_sampler_set_worm(sh%ctx,sh%dev%isopen,sh%dev%iworm,sh%s%xend),'pigs_sampler_set_worm')
+       do w=1,NW
+          call pigs_check(pigs_sampler_set_rng(sh%ctx,int(w-1,c_int32_t),int(sh%s%rng(w)%pos,c_int32_t),sh%s%rng(w)%w), &
+               & 'pigs_sampler_set_rng')
+       end do
+       allocate (sh%pend%gr_inc(Nbin,NW),sh%pend%sk_inc(dim,Nk,NW),sh%dev%acc(NDEV_COUNTS,NW),sh%dev%acc0(NDEV_COUNTS,NW))
+       sh%dev%acc0 = 0
+    end if
 
-  call initial_configuration(s,w0)
-  call sampler_upload(s)
-  if (device_sampler) then
-     call fill_sweep_params(swp_par)
-     call pigs_check(pigs_sampler_init(ctx,swp_par),'pigs_sampler_init')
-     call pigs_check(pigs_sampler_event_ints(ctx,rpos),'pigs_sampler_event_ints')
-     allocate (dev_open(NW),dev_iworm(NW),dev_ev(rpos,NW),dev_nrho(0:Npw,Nbin,NW),dev_reset(NW))
-     dev_open = merge(1,0,s%isopen); dev_iworm = s%iworm
-     call pigs_check(pigs_sampler_set_worm(ctx,dev_open,dev_iworm,s%xend),'pigs_sampler_set_worm')
-     do w=1,NW
-        call pigs_check(pigs_sampler_set_rng(ctx,int(w-1,c_int32_t),int(s%rng(w)%pos,c_int32_t),s%rng(w)%w), &
-             & 'pigs_sampler_set_rng')
-     end do
-     allocate (gr_inc(Nbin,NW),sk_inc(dim,Nk,NW),dev_acc(16,NW),dev_acc0(16,NW))
-     dev_acc0 = 0
-  end if
+    ! the first 20 doubles of the block vector: number of walkers with a diagonal block, their summed block energies, the
+    ! block's counters; behind them the summed normalised g(r), S(k), n(r) and how many walkers contributed, then what the
+    ! estimator keys add
+    sh%nvec = 7+NSUMS
+    call sh%core%create(sh%ep,density,Nobdm,NW,sh%nvec)
+    frun%Nb = Nb; frun%dt = dt; frun%density = density; frun%rcut = rcut
+    frun%averages = NWtot>1 .and. ish==1
+    allocate (frun%suffix(NW))
+    do w=1,NW
+       frun%suffix(w) = walker_suffix(sh%w0+w-1)
+    end do
+    call sh%fams%create(fk)
+    call sh%fams%setup(fk,frun,sh%ctx,sh%ep,NW,sh%nvec)
+    allocate (sh%vec(sh%nvec))
 
-  ! the first 20 doubles of the block vector: number of walkers with a diagonal block, their summed block energies, the
-  ! block's counters; behind them the summed normalised g(r), S(k), n(r) and how many walkers contributed, then what the
-  ! estimator keys add
-  nvec = 20
-  call series_create(sGr,Nbin,NW,nvec)
-  call series_create(sSk,dim*Nk,NW,nvec)
-  call series_create(sNr,(Npw+1)*Nbin,NW,nvec)
-  call count_create(cGr,nvec)
-  call count_create(cNr,nvec)
+    allocate (sh%perm(NW))
+    do w=1,NW
+       allocate (sh%perm(w)%members(Np),sh%perm(w)%histogram(Np))
+       sh%perm(w)%members = 0; sh%perm(w)%histogram = 0
+    end do
+    allocate (sh%pend%en9(9,NW),sh%pend%list(NW))
+    call sh%moves%create(NW)
+    call sh%en%create(NW)
 
-  frun%Nb = Nb; frun%dt = dt; frun%density = density; frun%rcut = rcut
-  frun%averages = NWtot>1 .and. ish==1
-  allocate (frun%suffix(NW))
-  do w=1,NW
-     frun%suffix(w) = walker_suffix(w0+w-1)
-  end do
-  call fams%create(fk)
-  call fams%setup(fk,frun,ctx,ep,NW,nvec)
-  allocate (vec(nvec))
+    allocate (sh%ue(NW),sh%ut(NW),sh%uh(NW))
+    do w=1,NW
+       suffix = walker_suffix(sh%w0+w-1)
+       open (newunit=sh%ue(w),file='e_vpi'//trim(suffix)//'.out')
+       open (newunit=sh%ut(w),file='et_vpi'//trim(suffix)//'.out')
+       open (newunit=sh%uh(w),file='e_vpi'//trim(suffix)//'.hex')
+    end do
+    if (NWtot>1 .and. ish==1) then
+       open (newunit=sh%ueav,file='e_vpi.out')
+       open (newunit=sh%utav,file='et_vpi.out')
+    end if
+  end subroutine shard_setup
 
-  allocate (perm(NW))
-  do w=1,NW
-     allocate (perm(w)%members(Np),perm(w)%histogram(Np))
-     perm(w)%members = 0; perm(w)%histogram = 0
-  end do
+  ! one MC step of the host-driven sampler (reference vpi.f90:302-404), one K1 batch per move stage.  The previous step's
+  ! estimators are collected first: the mirror still holds that step's worldlines, which g(r) and S(k) are taken from.
+  subroutine step_host(sh,iblock,istep)
+    type(shard_state), intent(inout) :: sh
+    integer, intent(in) :: iblock,istep
+    integer :: ipv(sh%NW),iupd(sh%NW),partner(sh%NW)
+    logical :: act(sh%NW),isopen0(sh%NW),swp(sh%NW)
+    integer :: w,ip,istag,iobdm,j
 
-  allocate (ipv(NW),iupd(NW),partner(NW),diag_list(NW),act(NW),isopen0(NW),swp(NW),wl(NW))
-  allocate (E1(NW),E2(NW),K1(NW),P1(NW),Et(NW),Kt(NW),Pt(NW),en9(9,NW),pend_list(NW))
-  est_pending = .false.; est_have = .false.; pend_struct = .false.; pend_nd = 0
-  allocate (acc_cm(NW),acc_bd(NW),acc_head(NW),acc_tail(NW),acc_cm_half(NW),acc_bd_half(NW))
-  allocate (acc_head_half(NW),acc_tail_half(NW),acc_open(NW),acc_close(NW),acc_swap(NW))
-  allocate (try_open(NW),try_close(NW),try_swap(NW),try_cm(NW),try_stag(NW),try_cm_half(NW),try_stag_half(NW))
-  allocate (idiag(NW),idiag_aux(NW),idiag_block(NW),obdm_bl(NW),diag_bl(NW),ngr(NW))
-  allocate (BE(3,NW),BE2(3,NW),BT(3,NW),BT2(3,NW),AE(3,NW),AE2(3,NW),AT(3,NW),AT2(3,NW))
-  allocate (gr(Nbin,NW),Sk(dim,Nk,NW),nrho(0:Npw,Nbin,NW))
-  AE = 0.d0; AE2 = 0.d0; AT = 0.d0; AT2 = 0.d0
-  nrho = 0.d0
-  idiag = 0; idiag_aux = 0; obdm_bl = 0; diag_bl = 0
+    call collect_estimators(sh)
+    associate (s => sh%s, perm => sh%perm, n => sh%moves%n, try_cm => sh%moves%try_cm, try_stag => sh%moves%try_stag)
+    ! ---- open / close attempt (reference vpi.f90:302-323)
+    isopen0 = s%isopen
+    do w=1,sh%NW
+       iupd(w) = int(mt_real(s%rng(w))*2)
+    end do
+    act = isopen0 .and. iupd==0
+    if (any(act)) then
+       call mv_close(s,Lstag,act,n(:,ACC_CLOSE))
+       do w=1,sh%NW
+          if (.not. act(w)) cycle
+          perm(w)%end_cycle = .not. s%isopen(w)
+          n(w,TRY_CLOSE) = n(w,TRY_CLOSE)+1
+          if (swapping) call perm_sampling(perm(w),s%isopen(w),s%iworm(w))
+       end do
+    end if
+    act = (.not. isopen0) .and. iupd==1
+    if (any(act)) then
+       do w=1,sh%NW
+          if (act(w)) s%iworm(w) = min(int(mt_real(s%rng(w))*Np)+1,Np)
+       end do
+       call mv_open(s,Lstag,s%iworm,act,n(:,ACC_OPEN))
+       do w=1,sh%NW
+          if (.not. act(w)) cycle
+          perm(w)%new_cycle = s%isopen(w)
+          n(w,TRY_OPEN) = n(w,TRY_OPEN)+1
+          if (swapping) call perm_sampling(perm(w),s%isopen(w),s%iworm(w))
+       end do
+    end if
 
-  allocate (ue(NW),ut(NW),uh(NW))
-  do w=1,NW
-     suffix = walker_suffix(w0+w-1)
-     open (newunit=ue(w),file='e_vpi'//trim(suffix)//'.out')
-     open (newunit=ut(w),file='et_vpi'//trim(suffix)//'.out')
-     open (newunit=uh(w),file='e_vpi'//trim(suffix)//'.hex')
-  end do
-  if (NWtot>1 .and. ish==1) then
-     open (newunit=ueav,file='e_vpi.out')
-     open (newunit=utav,file='et_vpi.out')
-  end if
+    ! ---- centre-of-mass and bead moves of every (non-worm) particle
+    if (mod(istep,CMFreq)==0) then
+       do ip=1,Np
+          ipv = ip
+          act = .not. (s%isopen .and. s%iworm==ip)
+          where (act) try_cm = try_cm+1
+          call mv_translate(s,delta_cm,ipv,act,n(:,ACC_CM))
+       end do
+    end if
+    do istag=1,Nstag
+       do ip=1,Np
+          ipv = ip
+          act = .not. (s%isopen .and. s%iworm==ip)
+          where (act) try_stag = try_stag+1
+          if (sampling=="sta") then
+             call mv_end_staging(s,HEAD,Lstag,ipv,act,n(:,ACC_HEAD))
+             call mv_end_staging(s,TAIL,Lstag,ipv,act,n(:,ACC_TAIL))
+             call mv_staging(s,Lstag,ipv,act,n(:,ACC_BD))
+          else
+             call mv_end_bisection(s,HEAD,Nlev,ipv,act,n(:,ACC_HEAD))
+             call mv_end_bisection(s,TAIL,Nlev,ipv,act,n(:,ACC_TAIL))
+             call mv_bisection(s,Nlev,ipv,act,n(:,ACC_BD))
+          end if
+       end do
+    end do
 
-  do iblock=1,Nblock
+    ! ---- worm moves of the walkers in the off-diagonal sector (reference vpi.f90:370-404)
+    act = s%isopen
+    if (any(act)) then
+       do iobdm=1,Nobdm
+          do j=1,2
+             call mv_translate_half(s,j,delta_cm,act,n(:,ACC_CM_HALF))
+          end do
+          do j=1,2
+             call mv_end_staging_half(s,HEAD,j,Lstag,act,n(:,ACC_HEAD_HALF))
+             call mv_end_staging_half(s,TAIL,j,Lstag,act,n(:,ACC_TAIL_HALF))
+             call mv_staging_half(s,j,Lstag,act,n(:,ACC_BD_HALF))
+          end do
+          if (swapping) then
+             where (act) n(:,TRY_SWAP) = n(:,TRY_SWAP)+1
+             call mv_swap(s,Lstag,act,n(:,ACC_SWAP),partner,swp)
+             do w=1,sh%NW
+                if (act(w)) call perm_sampling(perm(w),s%isopen(w),s%iworm(w),partner(w),swp(w))
+             end do
+          end if
+          if (.not. trap) then
+             do w=1,sh%NW
+                if (act(w)) call obdm_accumulate(sh%ep,s%xend(:,:,w),sh%core%nrho(:,:,w))
+             end do
+             call sh%fams%nk_add(sh%ctx,sh%NW,act,s%xend)
+          end if
+       end do
+    end if
+    if (sh%trace) then                    ! PIGS_VPI_TRACE=1: one checksum per walker and step (debugging aid)
+       print '(a,2i6,*(1x,z16.16))', ' trace',iblock,istep,(transfer(sum(s%Path(:,:,:,w)),1_8),w=1,sh%NW)
+    end if
+    end associate
+  end subroutine step_host
 
-     call system_clock(c0,crate)
-     try_open = 0; acc_open = 0; try_close = 0; acc_close = 0
-     try_cm = 0; acc_cm = 0; try_stag = 0; acc_bd = 0; acc_head = 0; acc_tail = 0
-     try_cm_half = 0; acc_cm_half = 0; try_stag_half = 0
-     acc_bd_half = 0; acc_head_half = 0; acc_tail_half = 0
-     try_swap = 0; acc_swap = 0
-     idiag_block = 0; ngr = 0; gr = 0.d0; Sk = 0.d0
-     BE = 0.d0; BE2 = 0.d0; BT = 0.d0; BT2 = 0.d0
+  ! one MC step of the device-resident sampler: the whole step of every walker in one launch (K6), queued and not waited
+  ! for, so that the previous step's estimators, collected behind it, ran beside it on the context's second stream on a
+  ! snapshot of the worldlines (pigs_diagonal_estimators_begin / _end: at 128 walkers per GPU the sampler leaves half of
+  ! the CUs idle); then the step's events
+  subroutine step_device(sh,istep)
+    type(shard_state), intent(inout) :: sh
+    integer, intent(in) :: istep
+    integer :: w,i
 
-     ! one trip more than steps: the estimators of a step are collected at the top of the NEXT trip -- with the
-     ! device-resident sampler they run on the context's second stream, on a snapshot of the worldlines, while that next step
-     ! is sampled (pigs_diagonal_estimators_begin / _end: at 128 walkers per GPU the sampler leaves half of the CUs idle)
-     do istep=1,Nstep+1
+    call pigs_check(pigs_sampler_step(sh%ctx,int(istep,c_int32_t)),'pigs_sampler_step')
+    call collect_estimators(sh)
+    if (CWorm<=0.d0) return
+    ! sector of every walker after the step and what its worm did during it: the permutation-cycle bookkeeping of the
+    ! reference (sample_mod.f90:530-594) is replayed from the event log
+    associate (s => sh%s, perm => sh%perm, ev => sh%dev%ev)
+    call pigs_check(pigs_sampler_events(sh%ctx,ev),'pigs_sampler_events')
+    do w=1,sh%NW
+       s%isopen(w) = ev(2,w)/=0
+       if (swapping) then
+          do i=1,ev(1,w)
+             select case (ev(1+2*i,w))
+             case (1)
+                s%iworm(w) = ev(2+2*i,w)
+                perm(w)%new_cycle = .true.
+                call perm_sampling(perm(w),.true.,s%iworm(w))
+             case (2)
+                perm(w)%end_cycle = .true.
+                call perm_sampling(perm(w),.false.,s%iworm(w))
+             case (3)
+                call perm_sampling(perm(w),.true.,s%iworm(w),ev(2+2*i,w),.true.)
+             end select
+          end do
+       end if
+    end do
+    end associate
+    ! the end-to-end vectors that the step's worm loops handed to the OBDM histogram (momentum = T)
+    call sh%fams%nk_step(sh%ctx,sh%NW)
+  end subroutine step_device
 
-        if (device_sampler .and. istep<=Nstep) then
-           ! the whole step of every walker in one launch (K6); queued, not waited for
-           call pigs_check(pigs_sampler_step(ctx,int(istep,c_int32_t)),'pigs_sampler_step')
-        end if
-        ! ---- the previous step's estimators (reference vpi.f90:443-473)
-        if (est_pending) then
-           if (pend_struct) then
-              call pigs_check(pigs_diagonal_estimators_end(ctx,en9,c_loc(gr_inc),c_loc(sk_inc)),'pigs_diagonal_estimators_end')
-           else
-              call pigs_check(pigs_diagonal_estimators_end(ctx,en9,c_null_ptr,c_null_ptr),'pigs_diagonal_estimators_end')
-           end if
-           est_pending = .false.
-           est_have = .true.
-        end if
-        if (est_have) then
-           est_have = .false.
-           do i=1,pend_nd
-              E1(i) = en9(1,i); E2(i) = en9(4,i); Et(i) = en9(7,i); Kt(i) = en9(8,i); Pt(i) = en9(9,i)
-           end do
-           !$omp parallel do schedule(dynamic,1) private(w,E,Pot,Kin) num_threads(min(pend_nd,16))
-           do i=1,pend_nd
-              w = pend_list(i)
-              idiag(w) = idiag(w)+1; idiag_aux(w) = idiag_aux(w)+1; idiag_block(w) = idiag_block(w)+1
-              E   = 0.5d0*(E1(i)+E2(i))
-              Pot = Pt(i)
-              Kin = E-Pot
-              BE(:,w)  = BE(:,w)+[E,Kin,Pot]
-              BT(:,w)  = BT(:,w)+[Et(i),Kt(i),Pot]
-              BE2(:,w) = BE2(:,w)+[E**2,Kin**2,Pot**2]
-              BT2(:,w) = BT2(:,w)+[Et(i)**2,Kt(i)**2,Pot**2]
-              ngr(w) = ngr(w)+1
-              if (.not. trap) then
-                 if (device_sampler) then
-                    gr(:,w)   = gr(:,w)+gr_inc(:,i)
-                    Sk(:,:,w) = Sk(:,:,w)+sk_inc(:,:,i)
-                 else
-                    ! (host-driven sampler: the mirror still holds the step's worldline -- the next step's moves come below)
-                    call pair_correlation(ep,s%Path(:,:,Nb,w),gr(:,w))
-                    call structure_factor(ep,s%Path(:,:,Nb,w),Sk(:,:,w))
-                 end if
-              end if
-           end do
-           !$omp end parallel do
-        end if
-        if (istep>Nstep) exit
+  ! the estimators of the walkers in the diagonal sector after a step (reference vpi.f90:406-473): LocalEnergy x2 (K4),
+  ! ThermEnergy (K2/K3) and -- device-resident sampler, PBC -- g(r), S(k) on the device (K7) in one library call; the
+  ! host-driven sampler keeps the structural estimators on its mirror.  Then the same walkers' slices into the accumulators
+  ! of the estimator keys.
+  subroutine queue_estimators(sh)
+    type(shard_state), intent(inout) :: sh
+    integer(c_int32_t) :: wl(sh%NW)
+    integer :: w,nd
 
-        if (device_sampler) then
-           if (CWorm>0.d0) then
-              ! sector of every walker after the step and what its worm did during it: the permutation-cycle
-              ! bookkeeping of the reference (sample_mod.f90:530-594) is replayed from the event log
-              call pigs_check(pigs_sampler_events(ctx,dev_ev),'pigs_sampler_events')
-              do w=1,NW
-                 s%isopen(w) = dev_ev(2,w)/=0
-                 if (swapping) then
-                    do i=1,dev_ev(1,w)
-                       select case (dev_ev(1+2*i,w))
-                       case (1)
-                          s%iworm(w) = dev_ev(2+2*i,w)
-                          perm(w)%new_cycle = .true.
-                          call perm_sampling(perm(w),.true.,s%iworm(w))
-                       case (2)
-                          perm(w)%end_cycle = .true.
-                          call perm_sampling(perm(w),.false.,s%iworm(w))
-                       case (3)
-                          call perm_sampling(perm(w),.true.,s%iworm(w),dev_ev(2+2*i,w),.true.)
-                       end select
-                    end do
-                 end if
-              end do
-              ! the end-to-end vectors that the step's worm loops handed to the OBDM histogram (momentum = T)
-              call fams%nk_step(ctx,NW)
-           end if
-        else
-        ! ---- open / close attempt (reference vpi.f90:302-323)
-        isopen0 = s%isopen
-        do w=1,NW
-           iupd(w) = int(mt_real(s%rng(w))*2)
-        end do
-        act = isopen0 .and. iupd==0
-        if (any(act)) then
-           call mv_close(s,Lstag,act,acc_close)
-           do w=1,NW
-              if (.not. act(w)) cycle
-              perm(w)%end_cycle = .not. s%isopen(w)
-              try_close(w) = try_close(w)+1
-              if (swapping) call perm_sampling(perm(w),s%isopen(w),s%iworm(w))
-           end do
-        end if
-        act = (.not. isopen0) .and. iupd==1
-        if (any(act)) then
-           do w=1,NW
-              if (act(w)) s%iworm(w) = min(int(mt_real(s%rng(w))*Np)+1,Np)
-           end do
-           call mv_open(s,Lstag,s%iworm,act,acc_open)
-           do w=1,NW
-              if (.not. act(w)) cycle
-              perm(w)%new_cycle = s%isopen(w)
-              try_open(w) = try_open(w)+1
-              if (swapping) call perm_sampling(perm(w),s%isopen(w),s%iworm(w))
-           end do
-        end if
+    nd = 0
+    do w=1,sh%NW
+       if (.not. sh%s%isopen(w)) then
+          nd = nd+1
+          sh%pend%list(nd) = w
+          wl(nd) = w-1
+       end if
+    end do
+    if (nd==0) return
+    sh%pend%nd = nd
+    if (device_sampler) then
+       sh%pend%structure = .not. trap
+       call pigs_check(pigs_diagonal_estimators_begin(sh%ctx,int(nd,c_int32_t),wl,int(Nbin,c_int32_t),rbin, &
+            & int(Nk,c_int32_t),merge(1_c_int32_t,0_c_int32_t,sh%pend%structure)),'pigs_diagonal_estimators_begin')
+    else
+       call sampler_flush(sh%s)
+       call pigs_check(pigs_diagonal_estimators(sh%ctx,int(nd,c_int32_t),wl,0_c_int32_t,0.d0,0_c_int32_t, &
+            & sh%pend%en9,c_null_ptr,c_null_ptr),'pigs_diagonal_estimators')
+    end if
+    sh%pend%queued = .true.
+    call sh%fams%queue(sh%ctx,nd,wl)
+  end subroutine queue_estimators
 
-        ! ---- centre-of-mass and bead moves of every (non-worm) particle
-        if (mod(istep,CMFreq)==0) then
-           do ip=1,Np
-              ipv = ip
-              act = .not. (s%isopen .and. s%iworm==ip)
-              where (act) try_cm = try_cm+1
-              call mv_translate(s,delta_cm,ipv,act,acc_cm)
-           end do
-        end if
-        do istag=1,Nstag
-           do ip=1,Np
-              ipv = ip
-              act = .not. (s%isopen .and. s%iworm==ip)
-              where (act) try_stag = try_stag+1
-              if (sampling=="sta") then
-                 call mv_end_staging(s,HEAD,Lstag,ipv,act,acc_head)
-                 call mv_end_staging(s,TAIL,Lstag,ipv,act,acc_tail)
-                 call mv_staging(s,Lstag,ipv,act,acc_bd)
-              else
-                 call mv_end_bisection(s,HEAD,Nlev,ipv,act,acc_head)
-                 call mv_end_bisection(s,TAIL,Nlev,ipv,act,acc_tail)
-                 call mv_bisection(s,Nlev,ipv,act,acc_bd)
-              end if
-           end do
-        end do
+  ! what queue_estimators left of the previous step, into the block's sums (reference vpi.f90:443-473)
+  subroutine collect_estimators(sh)
+    type(shard_state), intent(inout), target :: sh
+    integer :: i,w
+    real(8) :: E,Kin,Pot,Et,Kt
 
-        ! ---- worm moves of the walkers in the off-diagonal sector (reference vpi.f90:370-404)
-        act = s%isopen
-        if (any(act)) then
-           do iobdm=1,Nobdm
-              do j=1,2
-                 where (act) try_cm_half = try_cm_half+1
-                 call mv_translate_half(s,j,delta_cm,act,acc_cm_half)
-              end do
-              do j=1,2
-                 where (act) try_stag_half = try_stag_half+1
-                 call mv_end_staging_half(s,HEAD,j,Lstag,act,acc_head_half)
-                 call mv_end_staging_half(s,TAIL,j,Lstag,act,acc_tail_half)
-                 call mv_staging_half(s,j,Lstag,act,acc_bd_half)
-              end do
-              if (swapping) then
-                 where (act) try_swap = try_swap+1
-                 call mv_swap(s,Lstag,act,acc_swap,partner,swp)
-                 do w=1,NW
-                    if (act(w)) call perm_sampling(perm(w),s%isopen(w),s%iworm(w),partner(w),swp(w))
-                 end do
-              end if
-              if (.not. trap) then
-                 do w=1,NW
-                    if (act(w)) call obdm_accumulate(ep,s%xend(:,:,w),nrho(:,:,w))
-                 end do
-                 call fams%nk_add(ctx,NW,act,s%xend)
-              end if
-           end do
-        end if
+    if (.not. sh%pend%queued) return
+    sh%pend%queued = .false.
+    if (device_sampler) then
+       if (sh%pend%structure) then
+          call pigs_check(pigs_diagonal_estimators_end(sh%ctx,sh%pend%en9,c_loc(sh%pend%gr_inc),c_loc(sh%pend%sk_inc)), &
+               & 'pigs_diagonal_estimators_end')
+       else
+          call pigs_check(pigs_diagonal_estimators_end(sh%ctx,sh%pend%en9,c_null_ptr,c_null_ptr),'pigs_diagonal_estimators_end')
+       end if
+    end if
+    !$omp parallel do schedule(dynamic,1) private(w,E,Pot,Kin,Et,Kt) num_threads(min(sh%pend%nd,16))
+    do i=1,sh%pend%nd
+       w = sh%pend%list(i)
+       sh%en%idiag(w) = sh%en%idiag(w)+1; sh%en%idiag_aux(w) = sh%en%idiag_aux(w)+1
+       sh%en%idiag_block(w) = sh%en%idiag_block(w)+1
+       E   = 0.5d0*(sh%pend%en9(1,i)+sh%pend%en9(4,i))
+       Et  = sh%pend%en9(7,i); Kt = sh%pend%en9(8,i)
+       Pot = sh%pend%en9(9,i)
+       Kin = E-Pot
+       sh%en%BE(:,w)  = sh%en%BE(:,w)+[E,Kin,Pot]
+       sh%en%BT(:,w)  = sh%en%BT(:,w)+[Et,Kt,Pot]
+       sh%en%BE2(:,w) = sh%en%BE2(:,w)+[E**2,Kin**2,Pot**2]
+       sh%en%BT2(:,w) = sh%en%BT2(:,w)+[Et**2,Kt**2,Pot**2]
+       sh%en%ngr(w) = sh%en%ngr(w)+1
+       if (.not. trap) then
+          if (device_sampler) then
+             sh%core%gr(:,w)   = sh%core%gr(:,w)+sh%pend%gr_inc(:,i)
+             sh%core%Sk(:,:,w) = sh%core%Sk(:,:,w)+sh%pend%sk_inc(:,:,i)
+          else
+             call pair_correlation(sh%ep,sh%s%Path(:,:,Nb,w),sh%core%gr(:,w))
+             call structure_factor(sh%ep,sh%s%Path(:,:,Nb,w),sh%core%Sk(:,:,w))
+          end if
+       end if
+    end do
+    !$omp end parallel do
+  end subroutine collect_estimators
 
-        end if   ! host-driven / device-resident sampler
-        if (trace .and. .not. device_sampler) then       ! PIGS_VPI_TRACE=1: one checksum per walker and step (debugging aid)
-           print '(a,2i6,*(1x,z16.16))', ' trace',iblock,istep,(transfer(sum(s%Path(:,:,:,w)),1_8),w=1,NW)
-        end if
+  ! end of a block (reference vpi.f90:477-545): what the device counted, the families' sums, every walker's block values
+  ! and lines, the block's one exchange between the shards, the walker averages
+  subroutine block_end(sh,iblock)
+    type(shard_state), intent(inout) :: sh
+    integer, intent(in) :: iblock
+    real(8) :: mE(3),mT(3)
+    integer :: w,nd
 
-        ! ---- estimators of the walkers in the diagonal sector (reference vpi.f90:406-473)
-        nd = 0
-        do w=1,NW
-           if (.not. s%isopen(w)) then
-              nd = nd+1
-              diag_list(nd) = w
-              wl(nd) = w-1
-           end if
-        end do
-        if (nd>0) then
-           ! LocalEnergy x2 (K4), ThermEnergy (K2/K3) and -- device-resident sampler, PBC -- g(r), S(k) on the device (K7) in
-           ! one library call; the host-driven sampler keeps the structural estimators on its mirror.  Accumulated at the top
-           ! of the next trip.
-           pend_nd = nd
-           pend_list(1:nd) = diag_list(1:nd)
-           if (device_sampler) then
-              pend_struct = .not. trap
-              call pigs_check(pigs_diagonal_estimators_begin(ctx,int(nd,c_int32_t),wl,int(Nbin,c_int32_t),rbin, &
-                   & int(Nk,c_int32_t),merge(1_c_int32_t,0_c_int32_t,pend_struct)),'pigs_diagonal_estimators_begin')
-              est_pending = .true.
-           else
-              call sampler_flush(s)
-              call pigs_check(pigs_diagonal_estimators(ctx,int(nd,c_int32_t),wl,0_c_int32_t,0.d0,0_c_int32_t, &
-                   & en9,c_null_ptr,c_null_ptr),'pigs_diagonal_estimators')
-              est_have = .true.
-           end if
-           ! the same walkers' slices into the accumulators of the estimator keys
-           call fams%queue(ctx,nd,wl)
-        end if
+    if (device_sampler) then
+       call pigs_check(pigs_sampler_counters16(sh%ctx,sh%dev%acc),'pigs_sampler_counters16')
+       call sh%moves%from_device(sh%dev%acc,sh%dev%acc0)
+       if (CWorm>0.d0 .and. .not. trap) then
+          ! the device keeps accumulating a walker's OBDM histogram until the block that normalises it
+          sh%dev%reset = merge(1,0,sh%en%idiag_aux/Nstep>=1)
+          call pigs_check(pigs_sampler_nrho(sh%ctx,sh%dev%nrho,sh%dev%reset),'pigs_sampler_nrho')
+          sh%core%nrho = sh%dev%nrho
+       end if
+    end if
+    call sh%fams%read(sh%ctx)
+    if (.not. trap) call sh%fams%nk_read(sh%ctx,sh%en%idiag_aux/Nstep>=1)
+    sh%info%iblock = iblock
+    mE = 0.d0; mT = 0.d0; nd = 0
+    sh%vec = 0.d0
+    associate (en => sh%en)
+    do w=1,sh%NW
+       if (en%idiag_block(w)/=0) then
+          en%BE(:,w)  = en%BE(:,w)/real(en%idiag_block(w));  en%BE2(:,w) = en%BE2(:,w)/real(en%idiag_block(w))
+          en%BT(:,w)  = en%BT(:,w)/real(en%idiag_block(w));  en%BT2(:,w) = en%BT2(:,w)/real(en%idiag_block(w))
+          en%diag_bl(w) = en%diag_bl(w)+1
+          en%AE(:,w)  = en%AE(:,w)+en%BE(:,w);  en%AE2(:,w) = en%AE2(:,w)+en%BE(:,w)**2
+          en%AT(:,w)  = en%AT(:,w)+en%BT(:,w);  en%AT2(:,w) = en%AT2(:,w)+en%BT(:,w)**2
+          call sh%core%block(w,en%ngr(w),sh%vec)
+          sh%info%kin = en%BE(2,w)/Np
+          call sh%fams%block(w,sh%info,sh%vec)
+          write (sh%ue(w),'(5g20.10e3)') real(iblock),en%BE(1,w)/Np,en%BE(2,w)/Np,en%BE(3,w)/Np
+          write (sh%ut(w),'(5g20.10e3)') real(iblock),en%BT(1,w)/Np,en%BT(2,w)/Np,en%BT(3,w)/Np
+          write (sh%uh(w),'(i8,6(1x,z16.16))') iblock,en%BE(1,w)/Np,en%BE(2,w)/Np,en%BE(3,w)/Np, &
+               & en%BT(1,w)/Np,en%BT(2,w)/Np,en%BT(3,w)/Np
+          mE = mE+en%BE(:,w)/Np; mT = mT+en%BT(:,w)/Np; nd = nd+1
+       end if
+       if (en%idiag_aux(w)/Nstep>=1) then
+          en%obdm_bl(w) = en%obdm_bl(w)+1
+          call sh%core%block_nr(w,real(en%idiag_aux(w),8),sh%vec)
+          if (.not. trap) call sh%fams%nk_block(w,real(en%idiag_aux(w),8),sh%info,sh%vec)
+          en%idiag_aux(w) = 0
+       end if
+    end do
+    ! ---- the block's one exchange between the shards: all-reduce of the estimator vector
+    sh%vec(1) = nd; sh%vec(2:4) = mE; sh%vec(5:7) = mT
+    sh%vec(8:7+NSUMS) = sh%moves%block_sums(sum(en%idiag_block))
+    end associate
+    if (G>1) call pigs_check(pigs_estimators_allreduce(sh%ctx,sh%vec,int(sh%nvec,c_int32_t)),'pigs_estimators_allreduce')
+    sh%tot%ndall = nint(sh%vec(1)); sh%tot%mE = sh%vec(2:4); sh%tot%mT = sh%vec(5:7); sh%tot%moves = sh%vec(8:7+NSUMS)
+    ! ---- the walker average of every block value, over the walkers of all shards that counted the block
+    if (sh%ish==1 .and. NWtot>1) then
+       if (sh%tot%ndall>0) then
+          write (sh%ueav,'(5g20.10e3)') real(iblock),sh%tot%mE/sh%tot%ndall
+          write (sh%utav,'(5g20.10e3)') real(iblock),sh%tot%mT/sh%tot%ndall
+       end if
+       call sh%core%average(sh%vec)
+       sh%info%ndall = sh%tot%ndall
+       if (sh%tot%ndall>0) sh%info%kin = sh%tot%mE(2)/sh%tot%ndall
+       call sh%fams%average(sh%info,sh%vec)
+    end if
+  end subroutine block_end
 
-     end do   ! istep
+  ! checkpoint of a block (reference vpi.f90:541-545): the device-resident sampler hands its walkers' state over first
+  subroutine block_checkpoint(sh)
+    type(shard_state), intent(inout) :: sh
+    integer(c_int32_t) :: rpos
+    integer :: w
+    if (device_sampler) then
+       call pigs_check(pigs_path_download_all(sh%ctx,sh%s%Path),'pigs_path_download_all')
+       do w=1,sh%NW
+          call pigs_check(pigs_sampler_get_rng(sh%ctx,int(w-1,c_int32_t),rpos,sh%s%rng(w)%w),'pigs_sampler_get_rng')
+          sh%s%rng(w)%pos = rpos
+       end do
+       call pigs_check(pigs_sampler_get_worm(sh%ctx,sh%dev%isopen,sh%dev%iworm,sh%s%xend),'pigs_sampler_get_worm')
+       sh%s%isopen = sh%dev%isopen/=0; sh%s%iworm = sh%dev%iworm
+    end if
+    call write_checkpoints(sh%s,sh%w0)
+  end subroutine block_checkpoint
 
-     ! ---- end of block (reference vpi.f90:477-545)
-     if (device_sampler) then
-        call pigs_check(pigs_sampler_counters16(ctx,dev_acc),'pigs_sampler_counters16')
-        dev_acc0 = dev_acc-dev_acc0
-        acc_cm   = int(dev_acc0(1,:));  acc_head  = int(dev_acc0(2,:));  acc_tail = int(dev_acc0(3,:))
-        acc_bd   = int(dev_acc0(4,:));  try_open  = int(dev_acc0(5,:));  acc_open = int(dev_acc0(6,:))
-        try_close = int(dev_acc0(7,:)); acc_close = int(dev_acc0(8,:));  acc_cm_half = int(dev_acc0(9,:))
-        acc_head_half = int(dev_acc0(10,:)); acc_tail_half = int(dev_acc0(11,:)); acc_bd_half = int(dev_acc0(12,:))
-        try_swap = int(dev_acc0(13,:)); acc_swap  = int(dev_acc0(14,:)); try_cm   = dble(dev_acc0(15,:))
-        try_stag = dble(dev_acc0(16,:))
-        dev_acc0 = dev_acc
-        if (CWorm>0.d0 .and. .not. trap) then
-           ! the device keeps accumulating a walker's OBDM histogram until the block that normalises it
-           do w=1,NW
-              dev_reset(w) = merge(1,0,idiag_aux(w)/Nstep>=1)
-           end do
-           call pigs_check(pigs_sampler_nrho(ctx,dev_nrho,dev_reset),'pigs_sampler_nrho')
-           nrho = dev_nrho
-        end if
-     end if
-     call fams%read(ctx)
-     if (.not. trap) call fams%nk_read(ctx,idiag_aux/Nstep>=1)
-     info%iblock = iblock
-     mE = 0.d0; mT = 0.d0; nd = 0
-     vec = 0.d0
-     do w=1,NW
-        if (idiag_block(w)/=0) then
-           BE(:,w)  = BE(:,w)/real(idiag_block(w));  BE2(:,w) = BE2(:,w)/real(idiag_block(w))
-           BT(:,w)  = BT(:,w)/real(idiag_block(w));  BT2(:,w) = BT2(:,w)/real(idiag_block(w))
-           diag_bl(w) = diag_bl(w)+1
-           AE(:,w)  = AE(:,w)+BE(:,w);  AE2(:,w) = AE2(:,w)+BE(:,w)**2
-           AT(:,w)  = AT(:,w)+BT(:,w);  AT2(:,w) = AT2(:,w)+BT(:,w)**2
-           if (.not. trap) then
-              call normalize_gr(ep,density,ngr(w),gr(:,w))
-              call normalize_sk(ep,ngr(w),Sk(:,:,w))
-              call series_add(sGr,w,gr(:,w),vec)
-              call series_add(sSk,w,Sk(:,:,w),vec)
-              call count_add(cGr,vec)
-           end if
-           info%kin = BE(2,w)/Np
-           call fams%block(w,info,vec)
-           write (ue(w),'(5g20.10e3)') real(iblock),BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np
-           write (ut(w),'(5g20.10e3)') real(iblock),BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
-           write (uh(w),'(i8,6(1x,z16.16))') iblock,BE(1,w)/Np,BE(2,w)/Np,BE(3,w)/Np,BT(1,w)/Np,BT(2,w)/Np,BT(3,w)/Np
-           mE = mE+BE(:,w)/Np; mT = mT+BT(:,w)/Np; nd = nd+1
-        end if
-        if (idiag_aux(w)/Nstep>=1) then
-           obdm_bl(w) = obdm_bl(w)+1
-           if (.not. trap) then
-              call normalize_nr(ep,density,real(idiag_aux(w),8),Nobdm,nrho(:,:,w))
-              call series_add(sNr,w,nrho(:,:,w),vec)
-              call count_add(cNr,vec)
-              call fams%nk_block(w,real(idiag_aux(w),8),info,vec)
-           end if
-           idiag_aux(w) = 0
-           nrho(:,:,w)  = 0.d0
-        end if
-     end do
-     ! ---- the block's one exchange between the shards: all-reduce of the estimator vector
-     vec(1) = nd; vec(2:4) = mE; vec(5:7) = mT
-     vec(8:20) = [dble(sum(acc_cm)),sum(try_cm),dble(sum(acc_bd)),dble(sum(acc_head)),dble(sum(acc_tail)),sum(try_stag), &
-          & dble(sum(idiag_block)),dble(sum(acc_open)),dble(sum(try_open)),dble(sum(acc_close)),dble(sum(try_close)), &
-          & dble(sum(acc_swap)),dble(sum(try_swap))]
-     if (G>1) call pigs_check(pigs_estimators_allreduce(ctx,vec,int(nvec,c_int32_t)),'pigs_estimators_allreduce')
-     ndall = nint(vec(1)); mE = vec(2:4); mT = vec(5:7); cnt_all = vec(8:20)
-     ! ---- the walker average of every block value, over the walkers of all shards that counted the block
-     if (ish==1 .and. NWtot>1) then
-        if (ndall>0) then
-           write (ueav,'(5g20.10e3)') real(iblock),mE/ndall
-           write (utav,'(5g20.10e3)') real(iblock),mT/ndall
-        end if
-        nall = count_reduced(cGr,vec)
-        if (nall>0) then
-           call series_average(sGr,vec,nall)
-           call series_average(sSk,vec,nall)
-        end if
-        nall = count_reduced(cNr,vec)
-        if (nall>0) call series_average(sNr,vec,nall)
-        info%ndall = ndall
-        if (ndall>0) info%kin = mE(2)/ndall
-        call fams%average(info,vec)
-     end if
-     ! ---- checkpoint (reference vpi.f90:541-545, vpi_mod.f90:263-309): text worldline, particle-major
-     if (checkpointing) then
-        if (device_sampler) then
-           call pigs_check(pigs_path_download_all(ctx,s%Path),'pigs_path_download_all')
-           do w=1,NW
-              call pigs_check(pigs_sampler_get_rng(ctx,int(w-1,c_int32_t),rpos,s%rng(w)%w),'pigs_sampler_get_rng')
-              s%rng(w)%pos = rpos
-           end do
-           call pigs_check(pigs_sampler_get_worm(ctx,dev_open,dev_iworm,s%xend),'pigs_sampler_get_worm')
-           s%isopen = dev_open/=0; s%iworm = dev_iworm
-        end if
-        call write_checkpoints(s,w0)
-     end if
-     call system_clock(c1)
-     t0 = 0.d0; t1 = dble(c1-c0)/dble(crate)
+  ! shard 1 prints the block, which took t seconds, from what the all-reduce left
+  subroutine block_report(sh,iblock,t)
+    type(shard_state), intent(in) :: sh
+    integer, intent(in) :: iblock
+    real(8), intent(in) :: t
+    associate (ndall => sh%tot%ndall, m => sh%tot%moves)
+    print '(a)',            ' -----------------------------------------------------------'
+    print '(a,i8)',         ' BLOCK NUMBER :',iblock
+    if (ndall>0) then
+       print '(a,3g18.9)',  '   > <E>,<Ec>,<Ep>  =',sh%tot%mE/ndall
+       print '(a,3g18.9)',  '   > <Et>,<Kt>,<Vt> =',sh%tot%mT/ndall
+    end if
+    print '(a,f7.2,a)',     '   > CM movements      =',100*m(SUM_ACC_CM)/max(m(SUM_TRY_CM),1.d0),' %'
+    print '(a,f7.2,a)',     '   > Staging movements =',100*m(SUM_ACC_BD)/max(m(SUM_TRY_STAG),1.d0),' %'
+    print '(a,f7.2,a)',     '   > Head movements    =',100*m(SUM_ACC_HEAD)/max(m(SUM_TRY_STAG),1.d0),' %'
+    print '(a,f7.2,a)',     '   > Tail movements    =',100*m(SUM_ACC_TAIL)/max(m(SUM_TRY_STAG),1.d0),' %'
+    print '(a,f7.2,a)',     '   > Diagonal conf.    =',100.d0*m(SUM_DIAG)/real(Nstep*NWtot),' %'
+    print '(a,f7.2,a)',     '   > Open acc          =',100.d0*m(SUM_ACC_OPEN)/max(m(SUM_TRY_OPEN),1.d0),' %'
+    print '(a,f7.2,a)',     '   > Close acc         =',100.d0*m(SUM_ACC_CLOSE)/max(m(SUM_TRY_CLOSE),1.d0),' %'
+    print '(a,f7.2,a)',     '   > Swap acc          =',100.d0*m(SUM_ACC_SWAP)/max(m(SUM_TRY_SWAP),1.d0),' %'
+    print '(a,f9.2,a,i12,a,i10,a,f9.2,a)', '   > Time per block    =',t,' s;  Delta S items so far (shard 1)',sh%s%n_eval_items, &
+         & ' in',sh%s%n_eval_calls,' batches,',sh%s%t_eval,' s inside them'
+    end associate
+  end subroutine block_report
 
-     if (ish==1) then
-     print '(a)',            ' -----------------------------------------------------------'
-     print '(a,i8)',         ' BLOCK NUMBER :',iblock
-     if (ndall>0) then
-        print '(a,3g18.9)',  '   > <E>,<Ec>,<Ep>  =',mE/ndall
-        print '(a,3g18.9)',  '   > <Et>,<Kt>,<Vt> =',mT/ndall
-     end if
-     print '(a,f7.2,a)',     '   > CM movements      =',100*cnt_all(1)/max(cnt_all(2),1.d0),' %'
-     print '(a,f7.2,a)',     '   > Staging movements =',100*cnt_all(3)/max(cnt_all(6),1.d0),' %'
-     print '(a,f7.2,a)',     '   > Head movements    =',100*cnt_all(4)/max(cnt_all(6),1.d0),' %'
-     print '(a,f7.2,a)',     '   > Tail movements    =',100*cnt_all(5)/max(cnt_all(6),1.d0),' %'
-     print '(a,f7.2,a)',     '   > Diagonal conf.    =',100.d0*cnt_all(7)/real(Nstep*NWtot),' %'
-     print '(a,f7.2,a)',     '   > Open acc          =',100.d0*cnt_all(8)/max(cnt_all(9),1.d0),' %'
-     print '(a,f7.2,a)',     '   > Close acc         =',100.d0*cnt_all(10)/max(cnt_all(11),1.d0),' %'
-     print '(a,f7.2,a)',     '   > Swap acc          =',100.d0*cnt_all(12)/max(cnt_all(13),1.d0),' %'
-     print '(a,f9.2,a,i12,a,i10,a,f9.2,a)', '   > Time per block    =',t1-t0,' s;  Delta S items so far (shard 1)',s%n_eval_items, &
-          & ' in',s%n_eval_calls,' batches,',s%t_eval,' s inside them'
-     end if
-
-  end do   ! iblock
-
-  !=====================================================================
-  ! final averages and files (reference vpi.f90:590-642)
-  do w=1,NW
-     suffix = walker_suffix(w0+w-1)
-     close (ue(w)); close (ut(w)); close (uh(w))
-     if (swapping) then
-        open (newunit=k,file='perm_vpi'//trim(suffix)//'.out')
-        do ip=1,Np
-           write (k,*) ip,perm(w)%histogram(ip)
-        end do
-        close (k)
-     end if
-     if (.not. trap) then
-        ! written unconditionally, like the reference (a run without a single diagonal / OBDM block
-        ! yields NaN columns there too)
-        call write_radial('gr_vpi'//trim(suffix)//'.out',ep,diag_bl(w),sGr%sum(:,w),sGr%sq(:,w))
-        call write_sk('sk_vpi'//trim(suffix)//'.out',ep,diag_bl(w),sSk%sum(:,w),sSk%sq(:,w))
-        call write_nr('nr_vpi'//trim(suffix)//'.out',ep,obdm_bl(w),sNr%sum(:,w),sNr%sq(:,w))
-     end if
-     call fams%write_walker(suffix,w,diag_bl(w))
-  end do
-  if (NWtot>1 .and. ish==1) then
-     close (ueav); close (utav)
-     if (.not. trap) then                    ! walker-averaged histograms from the reduced block vectors
-        call write_radial('gr_vpi.out',ep,cGr%nav,sGr%asum,sGr%asq)
-        call write_sk('sk_vpi.out',ep,cGr%nav,sSk%asum,sSk%asq)
-        call write_nr('nr_vpi.out',ep,cNr%nav,sNr%asum,sNr%asq)
-     end if
-     call fams%write_average()
-  end if
-
-  do w=1,NW
-     AE_all(:,w0+w) = AE(:,w); AT_all(:,w0+w) = AT(:,w); diag_bl_all(w0+w) = diag_bl(w)
-  end do
-
-  ! final worldlines back from the device must equal the host mirror: the two were kept in
-  ! step by commits only
-  if (.not. device_sampler) call sampler_flush(s)
-  block
+  ! final averages and files (reference vpi.f90:590-642), the shard's part of what the main program prints and writes,
+  ! and the check of the host mirror
+  subroutine shard_finish(sh)
+    type(shard_state), intent(inout) :: sh
     real(8), allocatable :: chk(:,:,:,:)
-    allocate (chk(dim,Np,0:2*Nb,NW))
-    call pigs_check(pigs_path_download_all(ctx,chk),'pigs_path_download_all')
-    if (device_sampler) s%Path = chk
-    if (any(chk/=s%Path)) then
+    integer(c_int32_t) :: form(4)
+    character(len=32)  :: suffix
+    integer :: w,ip,u
+
+    do w=1,sh%NW
+       suffix = walker_suffix(sh%w0+w-1)
+       close (sh%ue(w)); close (sh%ut(w)); close (sh%uh(w))
+       if (swapping) then
+          open (newunit=u,file='perm_vpi'//trim(suffix)//'.out')
+          do ip=1,Np
+             write (u,*) ip,sh%perm(w)%histogram(ip)
+          end do
+          close (u)
+       end if
+       call sh%core%write_walker(suffix,w,sh%en%diag_bl(w),sh%en%obdm_bl(w))
+       call sh%fams%write_walker(suffix,w,sh%en%diag_bl(w))
+    end do
+    if (NWtot>1 .and. sh%ish==1) then
+       close (sh%ueav); close (sh%utav)
+       call sh%core%write_average()
+       call sh%fams%write_average()
+    end if
+
+    do w=1,sh%NW
+       AE_all(:,sh%w0+w) = sh%en%AE(:,w); AT_all(:,sh%w0+w) = sh%en%AT(:,w); diag_bl_all(sh%w0+w) = sh%en%diag_bl(w)
+    end do
+
+    ! final worldlines back from the device must equal the host mirror: the two were kept in
+    ! step by commits only
+    if (.not. device_sampler) call sampler_flush(sh%s)
+    allocate (chk(dim,Np,0:2*Nb,sh%NW))
+    call pigs_check(pigs_path_download_all(sh%ctx,chk),'pigs_path_download_all')
+    if (device_sampler) sh%s%Path = chk
+    if (any(chk/=sh%s%Path)) then
        write (0,*) 'pigs_vpi: device worldlines differ from the host mirror'
        stop 3
     end if
-    chk_all(:,:,:,w0+1:w0+NW) = chk
-  end block
+    chk_all(:,:,:,sh%w0+1:sh%w0+sh%NW) = chk
 
-  ! the form the device-resident sampler ran its last step in (pigs_sampler_form): tests check they ran the form they meant to
-  if (device_sampler .and. ish==1) then
-     block
-       integer(c_int32_t) :: form(4)
-       if (sampler_form(ctx,form)) print '(a,i5,a,i2,a,l2,a,l2)','  > sampler form: sweep threads',form(1),', TranslateChain workgroups per walker',form(2), &
-            & ', stage machine',form(3)/=0,', shared',form(4)/=0
-     end block
-  end if
+    ! the form the device-resident sampler ran its last step in (pigs_sampler_form): tests check they ran the form they meant to
+    if (device_sampler .and. sh%ish==1) then
+       if (sampler_form(sh%ctx,form)) print '(a,i5,a,i2,a,l2,a,l2)','  > sampler form: sweep threads',form(1), &
+            & ', TranslateChain workgroups per walker',form(2),', stage machine',form(3)/=0,', shared',form(4)/=0
+    end if
 
-  call sampler_free(s)
-  end subroutine run_shard
+    call sampler_free(sh%s)
+  end subroutine shard_finish
 
   ! what the files of walker w (global, 0-based) carry behind their name: .wNNNN, nothing in a run of one walker
   function walker_suffix(w) result(suffix)

@@ -37,7 +37,7 @@ def run_k6(gpu_lib, oracle, names, threads=None, split=0, cm=None, rows=None, ov
     rows: per-walker reference answers (helpers.walker_row of a walkers.npz) in place of the runs' driver.npz -- walker w
     then runs the input of names[0] with seed rows[w]["seed"].  overlap: the diagonal steps' estimators through
     diagonal_estimators_begin / _end, queued behind the next step as the front end queues them (host/pigs_vpi.f90:
-    426-438, 600-610), g(r) and S(k) included and summed over walkers and steps (CWorm = 0 inputs)."""
+    queue_estimators, step_device), g(r) and S(k) included and summed over walkers and steps (CWorm = 0 inputs)."""
     from oracle.pyoracle import System
     cfg = _cfg(names[0])
     if rows is None:
