@@ -2,9 +2,9 @@
 ! pigs_block_stats -- the block statistics behind every estimator file of the front end (pigs_vpi.f90).
 !
 ! A block_series is one output file's worth of numbers, flattened to length n: per walker the sum of the block values
-! and of their squares (the .wNNNN file, or the only file of a one-walker run), the same two moments of the walker
-! average of every block (the unsuffixed file of a run with several walkers), and the place of the series in the vector
-! that the shards all-reduce once per block: there the block values of the walkers that counted the block are summed, so
+! and of their squares (the .wNNNN file, or the only file of a one-walker run), as column 0 the same two moments of the
+! walker average of every block (the unsuffixed file of a run with several walkers), and the place of the series in the
+! vector that the shards all-reduce once per block: there the block values of the walkers that counted the block are summed, so
 ! that slice / count is the block's walker average on every shard.  A block_count is the count slot that goes with the
 ! series of one estimator family, and the number of blocks that at least one walker counted.
 !
@@ -24,8 +24,8 @@ module pigs_block_stats
   type block_series
      integer :: n   = 0
      integer :: off = -1                            ! the slice is vec(off+1:off+n); < 0: the series has none
-     real(8), allocatable :: sum(:,:),sq(:,:)       ! [n,NW] per walker: sum of the block values, of their squares
-     real(8), allocatable :: asum(:),asq(:)         ! [n] the same of the blocks' walker averages
+     real(8), allocatable :: sum(:,:),sq(:,:)       ! [n,0:NW] per walker: sum of the block values, of their squares;
+                                                    ! column 0: the same of the blocks' walker averages
      real(8), allocatable :: mean(:)                ! [n] the walker average of the last block (series_average)
   end type block_series
 
@@ -43,8 +43,8 @@ contains
     integer, intent(in)              :: n,NW
     integer, intent(inout), optional :: nvec
     s%n = n
-    allocate (s%sum(n,NW),s%sq(n,NW),s%asum(n),s%asq(n),s%mean(n))
-    s%sum = 0.d0; s%sq = 0.d0; s%asum = 0.d0; s%asq = 0.d0; s%mean = 0.d0
+    allocate (s%sum(n,0:NW),s%sq(n,0:NW),s%mean(n))
+    s%sum = 0.d0; s%sq = 0.d0; s%mean = 0.d0
     if (present(nvec)) then
        s%off = nvec
        nvec  = nvec+n
@@ -69,16 +69,16 @@ contains
     real(8), intent(in) :: vec(:)
     integer, intent(in) :: cnt
     s%mean = vec(s%off+1:s%off+s%n)/cnt
-    s%asum = s%asum+s%mean
-    s%asq  = s%asq+s%mean*s%mean
+    s%sum(:,0) = s%sum(:,0)+s%mean
+    s%sq(:,0)  = s%sq(:,0)+s%mean*s%mean
   end subroutine series_average
 
   ! the same for a series without a slice: the caller derived the block's walker average a from another series' mean
   subroutine series_add_mean(s,a)
     type(block_series), intent(inout) :: s
     real(8), intent(in) :: a(s%n)
-    s%asum = s%asum+a
-    s%asq  = s%asq+a*a
+    s%sum(:,0) = s%sum(:,0)+a
+    s%sq(:,0)  = s%sq(:,0)+a*a
   end subroutine series_add_mean
 
   ! claims one double of the block vector for a family's count
@@ -154,10 +154,10 @@ contains
        end if
     end do
     do ish=1,2
-       wsum(:,lo(ish):hi(ish)) = s(ish)%sum; wsq(:,lo(ish):hi(ish)) = s(ish)%sq
-       gsum(:,lo(ish):hi(ish)) = g(ish)%sum; gsq(:,lo(ish):hi(ish)) = g(ish)%sq
+       wsum(:,lo(ish):hi(ish)) = s(ish)%sum(:,1:); wsq(:,lo(ish):hi(ish)) = s(ish)%sq(:,1:)
+       gsum(:,lo(ish):hi(ish)) = g(ish)%sum(:,1:); gsq(:,lo(ish):hi(ish)) = g(ish)%sq(:,1:)
     end do
-    asum = s(1)%asum; asq = s(1)%asq; gasum = g(1)%asum; gasq = g(1)%asq
+    asum = s(1)%sum(:,0); asq = s(1)%sq(:,0); gasum = g(1)%sum(:,0); gasq = g(1)%sq(:,0)
     nav = c(1)%nav
   contains
     subroutine group_sums(x,y)

@@ -393,6 +393,15 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_sampler_form_t
 
+     ! pigs_*_accumulate of every estimator family: the slices of the walkers(1:n) (0-based) into the family's sums
+     function pigs_accumulate_t(ctx,n,walkers) bind(C) result(rc)
+       import :: c_int, c_int32_t, c_ptr
+       type(c_ptr), value             :: ctx
+       integer(c_int32_t), value      :: n
+       integer(c_int32_t), intent(in) :: walkers(*)
+       integer(c_int) :: rc
+     end function pigs_accumulate_t
+
      ! density profiles of a trapped system (include/pigs_hip.h, pigs_density_*): looked up at run time, see density_bind
      function pigs_density_init_t(ctx,Nbin,half_width) bind(C) result(rc)
        import :: c_int, c_int32_t, c_double, c_ptr
@@ -401,14 +410,6 @@ module pigs_capi
        real(c_double), value     :: half_width
        integer(c_int) :: rc
      end function pigs_density_init_t
-
-     function pigs_density_accumulate_t(ctx,n,walkers) bind(C) result(rc)
-       import :: c_int, c_int32_t, c_ptr
-       type(c_ptr), value             :: ctx
-       integer(c_int32_t), value      :: n
-       integer(c_int32_t), intent(in) :: walkers(*)
-       integer(c_int) :: rc
-     end function pigs_density_accumulate_t
 
      function pigs_density_read_t(ctx,planar,radial,pair,samples,reset) bind(C) result(rc)
        import :: c_int, c_int32_t, c_int64_t, c_ptr
@@ -426,14 +427,6 @@ module pigs_capi
        integer(c_int32_t), value :: Nk,Ntau,window
        integer(c_int) :: rc
      end function pigs_fqt_init_t
-
-     function pigs_fqt_accumulate_t(ctx,n,walkers) bind(C) result(rc)
-       import :: c_int, c_int32_t, c_ptr
-       type(c_ptr), value             :: ctx
-       integer(c_int32_t), value      :: n
-       integer(c_int32_t), intent(in) :: walkers(*)
-       integer(c_int) :: rc
-     end function pigs_fqt_accumulate_t
 
      function pigs_fqt_read_t(ctx,F,samples,reset) bind(C) result(rc)
        import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
@@ -467,14 +460,6 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_sqv_vectors_t
 
-     function pigs_sqv_accumulate_t(ctx,n,walkers) bind(C) result(rc)
-       import :: c_int, c_int32_t, c_ptr
-       type(c_ptr), value             :: ctx
-       integer(c_int32_t), value      :: n
-       integer(c_int32_t), intent(in) :: walkers(*)
-       integer(c_int) :: rc
-     end function pigs_sqv_accumulate_t
-
      function pigs_sqv_read_t(ctx,S,samples,reset) bind(C) result(rc)
        import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
        type(c_ptr), value             :: ctx
@@ -495,14 +480,6 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_grv_init_t
 
-     function pigs_grv_accumulate_t(ctx,n,walkers) bind(C) result(rc)
-       import :: c_int, c_int32_t, c_ptr
-       type(c_ptr), value             :: ctx
-       integer(c_int32_t), value      :: n
-       integer(c_int32_t), intent(in) :: walkers(*)
-       integer(c_int) :: rc
-     end function pigs_grv_accumulate_t
-
      function pigs_grv_read_t(ctx,vec,radial,samples,reset) bind(C) result(rc)
        import :: c_int, c_int32_t, c_int64_t, c_ptr
        type(c_ptr), value             :: ctx
@@ -513,8 +490,8 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_grv_read_t
 
-     ! F(q,tau) on the full reciprocal grid (include/pigs_hip.h, pigs_fqv_*): looked up at run time, see fqv_bind; _count,
-     ! _vectors and _accumulate have the signatures of the pigs_sqv_* ones
+     ! F(q,tau) on the full reciprocal grid (include/pigs_hip.h, pigs_fqv_*): looked up at run time, see fqv_bind; _count
+     ! and _vectors have the signatures of the pigs_sqv_* ones
      function pigs_fqv_init_t(ctx,nmax,Ntau,window) bind(C) result(rc)
        import :: c_int, c_int32_t, c_ptr
        type(c_ptr), value        :: ctx
@@ -532,7 +509,7 @@ module pigs_capi
      end function pigs_fqv_read_t
 
      ! self part of F(q,tau) and imaginary-time displacement (include/pigs_hip.h, pigs_fqs_*): looked up at run time, see
-     ! fqs_bind; _init has the signature of pigs_fqv_init, _count, _vectors and _accumulate those of the pigs_sqv_* ones
+     ! fqs_bind; _init has the signature of pigs_fqv_init, _count and _vectors those of the pigs_sqv_* ones
      function pigs_fqs_read_t(ctx,F,D,samples,reset) bind(C) result(rc)
        import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
        type(c_ptr), value             :: ctx
@@ -543,8 +520,7 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_fqs_read_t
 
-     ! imaginary-time profiles (include/pigs_hip.h, pigs_tau_*): looked up at run time, see tau_bind; _accumulate has the
-     ! signature of pigs_fqt_accumulate
+     ! imaginary-time profiles (include/pigs_hip.h, pigs_tau_*): looked up at run time, see tau_bind
      function pigs_tau_init_t(ctx) bind(C) result(rc)
        import :: c_int, c_ptr
        type(c_ptr), value :: ctx
@@ -560,8 +536,7 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_tau_read_t
 
-     ! bond-orientational order over a slice window (include/pigs_hip.h, pigs_bop_*): looked up at run time, see bop_bind;
-     ! _accumulate has the signature of pigs_fqt_accumulate
+     ! bond-orientational order over a slice window (include/pigs_hip.h, pigs_bop_*): looked up at run time, see bop_bind
      function pigs_bop_init_t(ctx,rnb,window,Nh,Nr,rbin) bind(C) result(rc)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value        :: ctx
@@ -583,8 +558,7 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_bop_read_t
 
-     ! van Hove functions over a slice window (include/pigs_hip.h, pigs_vh_*): looked up at run time, see vh_bind;
-     ! _accumulate has the signature of pigs_grv_accumulate
+     ! van Hove functions over a slice window (include/pigs_hip.h, pigs_vh_*): looked up at run time, see vh_bind
      function pigs_vh_init_t(ctx,Ntau,window,Nr,rbin,Ns,sbin) bind(C) result(rc)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value        :: ctx
@@ -605,8 +579,7 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_vh_read_t
 
-     ! triplet distribution over a slice window (include/pigs_hip.h, pigs_g3_*): looked up at run time, see g3_bind;
-     ! _accumulate has the signature of pigs_grv_accumulate
+     ! triplet distribution over a slice window (include/pigs_hip.h, pigs_g3_*): looked up at run time, see g3_bind
      function pigs_g3_init_t(ctx,Nr,rbin,Na,window) bind(C) result(rc)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value        :: ctx
@@ -627,7 +600,7 @@ module pigs_capi
      end function pigs_g3_read_t
 
      ! Axilrod-Teller-Muto three-body sum over a slice window (include/pigs_hip.h, pigs_atm_*): looked up at run time, see
-     ! atm_bind; _accumulate has the signature of pigs_grv_accumulate
+     ! atm_bind
      function pigs_atm_init_t(ctx,rc,window) bind(C) result(st)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value        :: ctx
@@ -647,7 +620,7 @@ module pigs_capi
      end function pigs_atm_read_t
 
      ! momentum distribution and one-body density matrix (include/pigs_hip.h, pigs_nk_*): looked up at run time, see
-     ! nk_bind; _init, _count, _vectors and _accumulate have the signatures of the pigs_sqv_* ones
+     ! nk_bind; _init, _count and _vectors have the signatures of the pigs_sqv_* ones
      function pigs_nk_add_t(ctx,n,walkers,nsamp,xend) bind(C) result(rc)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value             :: ctx
@@ -667,8 +640,7 @@ module pigs_capi
        integer(c_int) :: rc
      end function pigs_nk_read_t
 
-     ! a crystal seen from its lattice (include/pigs_hip.h, pigs_lat_*): looked up at run time, see lat_bind; _accumulate has
-     ! the signature of pigs_grv_accumulate
+     ! a crystal seen from its lattice (include/pigs_hip.h, pigs_lat_*): looked up at run time, see lat_bind
      function pigs_lat_init_t(ctx,nsite,sites,nbin,rmax,window,cm) bind(C) result(st)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value         :: ctx
@@ -691,7 +663,7 @@ module pigs_capi
      end function pigs_lat_read_t
 
      ! the superfluid fraction from the centre-of-mass diffusion along tau (include/pigs_hip.h, pigs_sf_*): looked up at
-     ! run time, see sf_bind; _accumulate has the signature of pigs_grv_accumulate
+     ! run time, see sf_bind
      function pigs_sf_init_t(ctx,Ntau,window) bind(C) result(st)
        import :: c_int, c_int32_t, c_ptr
        type(c_ptr), value         :: ctx
@@ -709,7 +681,7 @@ module pigs_capi
      end function pigs_sf_read_t
 
      ! the cluster-size distribution over a slice window (include/pigs_hip.h, pigs_cl_*): looked up at run time, see
-     ! cl_bind; _accumulate has the signature of pigs_grv_accumulate
+     ! cl_bind
      function pigs_cl_init_t(ctx,rc,window) bind(C) result(st)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value         :: ctx
@@ -729,7 +701,7 @@ module pigs_capi
      end function pigs_cl_read_t
 
      ! wrapping clusters and cluster persistence over a slice window (include/pigs_hip.h, pigs_pc_*): looked up at run
-     ! time, see pc_bind; _accumulate has the signature of pigs_grv_accumulate
+     ! time, see pc_bind
      function pigs_pc_init_t(ctx,rc,window,ntau) bind(C) result(st)
        import :: c_int, c_int32_t, c_double, c_ptr
        type(c_ptr), value         :: ctx
@@ -752,91 +724,91 @@ module pigs_capi
 
   ! bound by density_bind (null until then)
   procedure(pigs_density_init_t), pointer       :: dens_init => null()
-  procedure(pigs_density_accumulate_t), pointer :: dens_accumulate => null()
+  procedure(pigs_accumulate_t), pointer         :: dens_accumulate => null()
   procedure(pigs_density_read_t), pointer       :: dens_read => null()
 
   ! bound by fqt_bind (null until then)
   procedure(pigs_fqt_init_t), pointer       :: fqt_init => null()
-  procedure(pigs_fqt_accumulate_t), pointer :: fqt_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: fqt_accumulate => null()
   procedure(pigs_fqt_read_t), pointer       :: fqt_read => null()
 
   ! bound by sqv_bind (null until then)
   procedure(pigs_sqv_init_t), pointer       :: sqv_init => null()
   procedure(pigs_sqv_count_t), pointer      :: sqv_count => null()
   procedure(pigs_sqv_vectors_t), pointer    :: sqv_vectors => null()
-  procedure(pigs_sqv_accumulate_t), pointer :: sqv_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: sqv_accumulate => null()
   procedure(pigs_sqv_read_t), pointer       :: sqv_read => null()
 
   ! bound by grv_bind (null until then)
   procedure(pigs_grv_init_t), pointer       :: grv_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: grv_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: grv_accumulate => null()
   procedure(pigs_grv_read_t), pointer       :: grv_read => null()
 
   ! bound by fqv_bind (null until then)
   procedure(pigs_fqv_init_t), pointer       :: fqv_init => null()
   procedure(pigs_sqv_count_t), pointer      :: fqv_count => null()
   procedure(pigs_sqv_vectors_t), pointer    :: fqv_vectors => null()
-  procedure(pigs_sqv_accumulate_t), pointer :: fqv_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: fqv_accumulate => null()
   procedure(pigs_fqv_read_t), pointer       :: fqv_read => null()
 
   ! bound by fqs_bind (null until then)
   procedure(pigs_fqv_init_t), pointer       :: fqs_init => null()
   procedure(pigs_sqv_count_t), pointer      :: fqs_count => null()
   procedure(pigs_sqv_vectors_t), pointer    :: fqs_vectors => null()
-  procedure(pigs_sqv_accumulate_t), pointer :: fqs_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: fqs_accumulate => null()
   procedure(pigs_fqs_read_t), pointer       :: fqs_read => null()
 
   ! bound by tau_bind (null until then)
   procedure(pigs_tau_init_t), pointer       :: tau_init => null()
-  procedure(pigs_fqt_accumulate_t), pointer :: tau_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: tau_accumulate => null()
   procedure(pigs_tau_read_t), pointer       :: tau_read => null()
 
   ! bound by bop_bind (null until then)
   procedure(pigs_bop_init_t), pointer       :: bop_init => null()
-  procedure(pigs_fqt_accumulate_t), pointer :: bop_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: bop_accumulate => null()
   procedure(pigs_bop_read_t), pointer       :: bop_read => null()
 
   ! bound by vh_bind (null until then)
   procedure(pigs_vh_init_t), pointer        :: vh_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: vh_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: vh_accumulate => null()
   procedure(pigs_vh_read_t), pointer        :: vh_read => null()
 
   ! bound by g3_bind (null until then)
   procedure(pigs_g3_init_t), pointer        :: g3_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: g3_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: g3_accumulate => null()
   procedure(pigs_g3_read_t), pointer        :: g3_read => null()
 
   ! bound by atm_bind (null until then)
   procedure(pigs_atm_init_t), pointer       :: atm_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: atm_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: atm_accumulate => null()
   procedure(pigs_atm_read_t), pointer       :: atm_read => null()
 
   ! bound by nk_bind (null until then)
   procedure(pigs_sqv_init_t), pointer       :: nk_init => null()
   procedure(pigs_sqv_count_t), pointer      :: nk_count => null()
   procedure(pigs_sqv_vectors_t), pointer    :: nk_vectors => null()
-  procedure(pigs_sqv_accumulate_t), pointer :: nk_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: nk_accumulate => null()
   procedure(pigs_nk_add_t), pointer         :: nk_add => null()
   procedure(pigs_nk_read_t), pointer        :: nk_read => null()
 
   ! bound by lat_bind (null until then)
   procedure(pigs_lat_init_t), pointer       :: lat_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: lat_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: lat_accumulate => null()
   procedure(pigs_lat_read_t), pointer       :: lat_read => null()
 
   ! bound by sf_bind (null until then)
   procedure(pigs_sf_init_t), pointer        :: sf_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: sf_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: sf_accumulate => null()
   procedure(pigs_sf_read_t), pointer        :: sf_read => null()
 
   ! bound by cl_bind (null until then)
   procedure(pigs_cl_init_t), pointer        :: cl_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: cl_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: cl_accumulate => null()
   procedure(pigs_cl_read_t), pointer        :: cl_read => null()
 
   ! bound by pc_bind (null until then)
   procedure(pigs_pc_init_t), pointer        :: pc_init => null()
-  procedure(pigs_grv_accumulate_t), pointer :: pc_accumulate => null()
+  procedure(pigs_accumulate_t), pointer     :: pc_accumulate => null()
   procedure(pigs_pc_read_t), pointer        :: pc_read => null()
 
 contains

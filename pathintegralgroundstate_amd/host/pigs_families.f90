@@ -8,18 +8,20 @@
 ! end walks through:
 !     check          the key's values (refused before the backend is asked), the window default, *_bind()
 !     banner         its line of the run's banner
-!     setup          *_init, its grids, allocation, its claims on the block vector, the reset mask, press_vpi*.out
-!     queue          *_accumulate for the diagonal walkers of a step
+!     setup          *_init and the entry that queue calls, its grids, allocation, its claims on the block vector, the reset
+!                    mask, the files with one line per block
+!     queue          the family's *_accumulate for the diagonal walkers of a step: one procedure for all families
 !     read           *_read at the end of a block
 !     block          walker w counted the block: normalize_*, series_add per file, count_add
 !     average        on the shard that writes the walker averages, after the all-reduce: count_reduced, series_average
-!     write_walker   the files of walker w
-!     write_average  the walker-averaged files
+!     write_files    every file of the family once: of walker w, or with w = 0 the walker-averaged ones
 ! A family_set holds one slot per family, in the order of their claims on the block vector and of every device call;
 ! only the slots of the keys that are on are allocated, and the set has one procedure per phase that walks them.
 !
-! A new family is a new extension of `family` here, a slot (and a line of set_create) in family_set, and its keys in
-! family_keys and in the program's namelist.
+! A new family is a new extension of `family` here with these phases but queue, for which its setup names the device
+! entry; a slot (and a line of set_create) in family_set; and its keys in family_keys and in the program's namelist.
+! Whatever a family keeps per walker and for the walker average has the average at index 0 (block_series, the units of
+! the files with one line per block), so that write_files says nothing twice.
 !-----------------------------------------------------------------------
 module pigs_families
 
@@ -107,16 +109,17 @@ module pigs_families
      integer(c_int64_t), allocatable :: smp(:)      ! [NW] the block's samples per walker, from the device
      integer(c_int32_t), allocatable :: reset(:)    ! [NW] 1: the device zeroes the walker's sums after the copy
      type(block_count) :: cnt
+     procedure(pigs_accumulate_t), pointer, nopass :: accumulate => null()     ! what queue calls, and its name in the
+     character(len=24) :: entry = ''                                           ! message of a failure; both set by setup
    contains
-     procedure(check_i),         deferred :: check
-     procedure(banner_i),        deferred :: banner
-     procedure(setup_i),         deferred :: setup
-     procedure(queue_i),         deferred :: queue
-     procedure(read_i),          deferred :: read
-     procedure(block_i),         deferred :: block
-     procedure(average_i),       deferred :: average
-     procedure(write_walker_i),  deferred :: write_walker
-     procedure(write_average_i), deferred :: write_average
+     procedure(check_i),       deferred :: check
+     procedure(banner_i),      deferred :: banner
+     procedure(setup_i),       deferred :: setup
+     procedure :: queue => family_queue
+     procedure(read_i),        deferred :: read
+     procedure(block_i),       deferred :: block
+     procedure(average_i),     deferred :: average
+     procedure(write_files_i), deferred :: write_files
   end type family
 
   abstract interface
@@ -143,13 +146,6 @@ module pigs_families
        integer, intent(in)    :: NW
        integer, intent(inout) :: nvec
      end subroutine setup_i
-     subroutine queue_i(f,ctx,nd,wl)
-       import :: family,c_ptr,c_int32_t
-       class(family), intent(inout) :: f
-       type(c_ptr), intent(in)      :: ctx
-       integer, intent(in)          :: nd
-       integer(c_int32_t), intent(in) :: wl(:)
-     end subroutine queue_i
      subroutine read_i(f,ctx)
        import :: family,c_ptr
        class(family), intent(inout) :: f
@@ -168,16 +164,14 @@ module pigs_families
        type(family_info), intent(in) :: info
        real(8), intent(in)           :: vec(:)
      end subroutine average_i
-     subroutine write_walker_i(f,suffix,w,nblocks)
+     ! w > 0: walker w (local index), whose files carry suffix, over the n blocks it counted; w = 0: the walker averages,
+     ! suffix = '', over the n blocks that one of the walkers counted
+     subroutine write_files_i(f,suffix,w,n)
        import :: family
        class(family), intent(inout) :: f
        character(len=*), intent(in) :: suffix
-       integer, intent(in)          :: w,nblocks
-     end subroutine write_walker_i
-     subroutine write_average_i(f)
-       import :: family
-       class(family), intent(inout) :: f
-     end subroutine write_average_i
+       integer, intent(in)          :: w,n
+     end subroutine write_files_i
   end interface
 
   ! the stored vectors of a reciprocal grid and their |q| shells (sq_vector, fq_vector, fq_self)
@@ -198,12 +192,10 @@ module pigs_families
      procedure :: check => density_check
      procedure :: banner => density_banner
      procedure :: setup => density_setup
-     procedure :: queue => density_queue
      procedure :: read => density_read
      procedure :: block => density_block
      procedure :: average => density_average
-     procedure :: write_walker => density_write_walker
-     procedure :: write_average => density_write_average
+     procedure :: write_files => density_write_files
   end type density_family
 
   ! F(q,tau) on the S(k) grid: the block's raw sums from the device and the normalised block values
@@ -215,12 +207,10 @@ module pigs_families
      procedure :: check => fqt_check
      procedure :: banner => fqt_banner
      procedure :: setup => fqt_setup
-     procedure :: queue => fqt_queue
      procedure :: read => fqt_read_block
      procedure :: block => fqt_block
      procedure :: average => fqt_average
-     procedure :: write_walker => fqt_write_walker
-     procedure :: write_average => fqt_write_average
+     procedure :: write_files => fqt_write_files
   end type fqt_family
 
   ! vector S(q): the block's raw sums from the device, the normalised block values per vector and per shell
@@ -233,12 +223,10 @@ module pigs_families
      procedure :: check => sqv_check
      procedure :: banner => sqv_banner
      procedure :: setup => sqv_setup
-     procedure :: queue => sqv_queue
      procedure :: read => sqv_read_block
      procedure :: block => sqv_block
      procedure :: average => sqv_average
-     procedure :: write_walker => sqv_write_walker
-     procedure :: write_average => sqv_write_average
+     procedure :: write_files => sqv_write_files
   end type sqv_family
 
   ! vector g(r): the block's counts from the device, the normalised block values on the vector grid and radially
@@ -251,12 +239,10 @@ module pigs_families
      procedure :: check => grv_check
      procedure :: banner => grv_banner
      procedure :: setup => grv_setup
-     procedure :: queue => grv_queue
      procedure :: read => grv_read_block
      procedure :: block => grv_block
      procedure :: average => grv_average
-     procedure :: write_walker => grv_write_walker
-     procedure :: write_average => grv_write_average
+     procedure :: write_files => grv_write_files
   end type grv_family
 
   ! a function of (vector, lag) on the full reciprocal grid: fq_vector, and with self = T fq_self, which has the two
@@ -270,7 +256,6 @@ module pigs_families
      character(len=25) :: label = ''                ! of the banner line
      character(len=48) :: files = ''                ! at its end
      character(len=6)  :: fvec = '', fsh = ''       ! file names before _vpi
-     procedure(pigs_sqv_accumulate_t), pointer, nopass :: accumulate => null()
      integer :: ntau = 0, window = 0
      type(qgrid) :: g
      real(8), allocatable :: raw(:,:,:),draw(:,:,:),b(:,:),sh(:,:),bm(:,:)     ! (second index: lag l + 1)
@@ -279,12 +264,10 @@ module pigs_families
      procedure :: check => lagged_check
      procedure :: banner => lagged_banner
      procedure :: setup => lagged_setup
-     procedure :: queue => lagged_queue
      procedure :: read => lagged_read_block
      procedure :: block => lagged_block
      procedure :: average => lagged_average
-     procedure :: write_walker => lagged_write_walker
-     procedure :: write_average => lagged_write_average
+     procedure :: write_files => lagged_write_files
   end type lagged_family
 
   ! imaginary-time profiles: the block's raw sums from the device (Vpair, Vext, W, D2 per slice), the normalised block
@@ -293,18 +276,15 @@ module pigs_families
      integer :: window = 0
      real(8), allocatable :: raw(:,:,:),b(:,:)      ! (second index: slice b + 1)
      type(block_series) :: s
-     integer, allocatable :: up(:)
-     integer :: upav = -1
+     integer, allocatable :: up(:)                  ! [0:NW] the units of the file with one line per block
    contains
      procedure :: check => tau_check
      procedure :: banner => tau_banner
      procedure :: setup => tau_setup
-     procedure :: queue => tau_queue
      procedure :: read => tau_read_block
      procedure :: block => tau_block
      procedure :: average => tau_average
-     procedure :: write_walker => tau_write_walker
-     procedure :: write_average => tau_write_average
+     procedure :: write_files => tau_write_files
   end type tau_family
 
   ! bond-orientational order: the block's raw sums and counts from the device, the normalised block values (the five
@@ -320,12 +300,10 @@ module pigs_families
      procedure :: check => bop_check
      procedure :: banner => bop_banner
      procedure :: setup => bop_setup
-     procedure :: queue => bop_queue
      procedure :: read => bop_read_block
      procedure :: block => bop_block
      procedure :: average => bop_average
-     procedure :: write_walker => bop_write_walker
-     procedure :: write_average => bop_write_average
+     procedure :: write_files => bop_write_files
   end type bop_family
 
   ! van Hove functions: the block's counts from the device and the normalised block values G_s (self grid eps) and G_d
@@ -340,12 +318,10 @@ module pigs_families
      procedure :: check => vh_check
      procedure :: banner => vh_banner
      procedure :: setup => vh_setup
-     procedure :: queue => vh_queue
      procedure :: read => vh_read_block
      procedure :: block => vh_block
      procedure :: average => vh_average
-     procedure :: write_walker => vh_write_walker
-     procedure :: write_average => vh_write_average
+     procedure :: write_files => vh_write_files
   end type vh_family
 
   ! triplet distribution: the block's counts from the device and the normalised block values g3 (packed triangle of leg
@@ -360,12 +336,10 @@ module pigs_families
      procedure :: check => g3_check
      procedure :: banner => g3_banner
      procedure :: setup => g3_setup
-     procedure :: queue => g3_queue
      procedure :: read => g3_read_block
      procedure :: block => g3_block
      procedure :: average => g3_average
-     procedure :: write_walker => g3_write_walker
-     procedure :: write_average => g3_write_average
+     procedure :: write_files => g3_write_files
   end type g3_family
 
   ! Axilrod-Teller-Muto three-body energy: the block's raw sums and triplet counts from the device per window slice, the
@@ -376,18 +350,15 @@ module pigs_families
      real(8), allocatable :: raw(:,:),b(:,:)        ! (first index of raw, second of b: slice a - (Nb-window) + 1)
      integer(c_int64_t), allocatable :: ntrip(:,:)
      type(block_series) :: s
-     integer, allocatable :: up(:)
-     integer :: upav = -1
+     integer, allocatable :: up(:)                  ! [0:NW] the units of the file with one line per block
    contains
      procedure :: check => atm_check
      procedure :: banner => atm_banner
      procedure :: setup => atm_setup
-     procedure :: queue => atm_queue
      procedure :: read => atm_read_block
      procedure :: block => atm_block
      procedure :: average => atm_average
-     procedure :: write_walker => atm_write_walker
-     procedure :: write_average => atm_write_average
+     procedure :: write_files => atm_write_files
   end type atm_family
 
   ! momentum: the off-diagonal family.  Its samples are the end-to-end vectors of the open walkers, so it is queued for all
@@ -399,8 +370,7 @@ module pigs_families
      type(qgrid) :: g
      real(8), allocatable :: raw(:,:),b(:),sh(:),br(:)      ! (b: index 1 is n = 0, index i + 1 the stored vector i)
      integer(c_int64_t), allocatable :: h(:,:),nopen(:),nin(:)
-     integer, allocatable :: nbl(:),un(:)
-     integer :: unav = -1
+     integer, allocatable :: nbl(:),un(:)           ! [NW] blocks normalised, [0:NW] the units of n0_vpi*.out
      type(block_series) :: sVec,sSh,sR
    contains
      procedure :: check => nk_check
@@ -410,8 +380,7 @@ module pigs_families
      procedure :: read => nk_read_nothing
      procedure :: block => nk_block_nothing
      procedure :: average => nk_average
-     procedure :: write_walker => nk_write_walker
-     procedure :: write_average => nk_write_average
+     procedure :: write_files => nk_write_files
   end type nk_family
 
   ! a crystal seen from its lattice: the block's raw sums from the device, the normalised block values of the three files
@@ -423,18 +392,15 @@ module pigs_families
      real(8) :: bl(7)
      integer(c_int64_t), allocatable :: nass(:,:),occ(:,:,:),hr(:,:),hx(:,:,:),nlost(:),hop1(:),hopw(:)
      type(block_series) :: sL,sT,sU
-     integer, allocatable :: up(:)
-     integer :: upav = -1
+     integer, allocatable :: up(:)                  ! [0:NW] the units of the file with one line per block
    contains
      procedure :: check => lat_check
      procedure :: banner => lat_banner
      procedure :: setup => lat_setup
-     procedure :: queue => lat_queue
      procedure :: read => lat_read_block
      procedure :: block => lat_block
      procedure :: average => lat_average
-     procedure :: write_walker => lat_write_walker
-     procedure :: write_average => lat_write_average
+     procedure :: write_files => lat_write_files
   end type lat_family
 
   ! the superfluid fraction from the centre-of-mass diffusion along tau: the block's raw sums from the device and the
@@ -449,12 +415,10 @@ module pigs_families
      procedure :: check => sf_check
      procedure :: banner => sf_banner
      procedure :: setup => sf_setup
-     procedure :: queue => sf_queue
      procedure :: read => sf_read_block
      procedure :: block => sf_block
      procedure :: average => sf_average
-     procedure :: write_walker => sf_write_walker
-     procedure :: write_average => sf_write_average
+     procedure :: write_files => sf_write_files
   end type sf_family
 
   ! clusters: the block's raw sums from the device and the normalised block values per size and per block
@@ -466,18 +430,15 @@ module pigs_families
      real(8), allocatable :: rg2(:,:),bs(:,:)
      real(8) :: bb(4) = 0.d0
      type(block_series) :: s,sb
-     integer, allocatable :: up(:)
-     integer :: upav = -1
+     integer, allocatable :: up(:)                  ! [0:NW] the units of the file with one line per block
    contains
      procedure :: check => cl_check
      procedure :: banner => cl_banner
      procedure :: setup => cl_setup
-     procedure :: queue => cl_queue
      procedure :: read => cl_read_block
      procedure :: block => cl_block
      procedure :: average => cl_average
-     procedure :: write_walker => cl_write_walker
-     procedure :: write_average => cl_write_average
+     procedure :: write_files => cl_write_files
   end type cl_family
 
   ! percolation: the block's raw sums from the device and the normalised block values per block, per size and per lag
@@ -489,18 +450,15 @@ module pigs_families
      real(8), allocatable :: rg2u(:,:),bs(:,:),bp(:,:)
      real(8) :: bb(7) = 0.d0
      type(block_series) :: ss,sp,sb
-     integer, allocatable :: up(:)
-     integer :: upav = -1
+     integer, allocatable :: up(:)                  ! [0:NW] the units of the file with one line per block
    contains
      procedure :: check => pc_check
      procedure :: banner => pc_banner
      procedure :: setup => pc_setup
-     procedure :: queue => pc_queue
      procedure :: read => pc_read_block
      procedure :: block => pc_block
      procedure :: average => pc_average
-     procedure :: write_walker => pc_write_walker
-     procedure :: write_average => pc_write_average
+     procedure :: write_files => pc_write_files
   end type pc_family
 
   integer, parameter :: NFAM = 16
@@ -715,7 +673,7 @@ contains
     integer, intent(in)          :: w,nblocks
     integer :: i
     do i=1,NFAM
-       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%write_walker(suffix,w,nblocks)
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%write_files(suffix,w,nblocks)
     end do
   end subroutine set_write_walker
 
@@ -724,7 +682,7 @@ contains
     class(family_set), intent(inout) :: fs
     integer :: i
     do i=1,NFAM
-       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%write_average()
+       if (allocated(fs%slot(i)%f)) call fs%slot(i)%f%write_files('',0,fs%slot(i)%f%cnt%nav)
     end do
   end subroutine set_write_average
 
@@ -742,6 +700,15 @@ contains
     allocate (f%smp(NW),f%reset(NW))
     f%reset = 1
   end subroutine family_begin
+
+  ! what every family but momentum queues for the diagonal walkers of a step
+  subroutine family_queue(f,ctx,nd,wl)
+    class(family), intent(inout) :: f
+    type(c_ptr), intent(in) :: ctx
+    integer, intent(in)     :: nd
+    integer(c_int32_t), intent(in) :: wl(:)
+    call pigs_check(f%accumulate(ctx,int(nd,c_int32_t),wl),trim(f%entry))
+  end subroutine family_queue
 
   subroutine needs_periodic(key,why)
     character(len=*), intent(in) :: key,why
@@ -888,15 +855,8 @@ contains
     call series_create(f%sPair,ep%Nbin,NW,nvec)
     call count_create(f%cnt,nvec)
     call pigs_check(dens_init(ctx,int(ep%Nbin,c_int32_t),run%rcut/2.d0),'pigs_density_init')
+    f%accumulate => dens_accumulate; f%entry = 'pigs_density_accumulate'
   end subroutine density_setup
-
-  subroutine density_queue(f,ctx,nd,wl)
-    class(density_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(dens_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_density_accumulate')
-  end subroutine density_queue
 
   subroutine density_read(f,ctx)
     class(density_family), intent(inout) :: f
@@ -930,21 +890,14 @@ contains
     end if
   end subroutine density_average
 
-  subroutine density_write_walker(f,suffix,w,nblocks)
+  subroutine density_write_files(f,suffix,w,n)
     class(density_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_density('dens_vpi'//trim(suffix)//'.out',f%ep%dim,f%ep%Nbin,f%run%rcut/2.d0,nblocks,f%sPl%sum(:,w),f%sPl%sq(:,w))
-    call write_profile('rho_vpi'//trim(suffix)//'.out',f%ep%Nbin,f%run%rcut/2.d0,nblocks,f%sRad%sum(:,w),f%sRad%sq(:,w))
-    call write_profile('pr_vpi'//trim(suffix)//'.out',f%ep%Nbin,f%run%rcut/2.d0,nblocks,f%sPair%sum(:,w),f%sPair%sq(:,w))
-  end subroutine density_write_walker
-
-  subroutine density_write_average(f)
-    class(density_family), intent(inout) :: f
-    call write_density('dens_vpi.out',f%ep%dim,f%ep%Nbin,f%run%rcut/2.d0,f%cnt%nav,f%sPl%asum,f%sPl%asq)
-    call write_profile('rho_vpi.out',f%ep%Nbin,f%run%rcut/2.d0,f%cnt%nav,f%sRad%asum,f%sRad%asq)
-    call write_profile('pr_vpi.out',f%ep%Nbin,f%run%rcut/2.d0,f%cnt%nav,f%sPair%asum,f%sPair%asq)
-  end subroutine density_write_average
+    integer, intent(in)          :: w,n
+    call write_density('dens_vpi'//trim(suffix)//'.out',f%ep%dim,f%ep%Nbin,f%run%rcut/2.d0,n,f%sPl%sum(:,w),f%sPl%sq(:,w))
+    call write_profile('rho_vpi'//trim(suffix)//'.out',f%ep%Nbin,f%run%rcut/2.d0,n,f%sRad%sum(:,w),f%sRad%sq(:,w))
+    call write_profile('pr_vpi'//trim(suffix)//'.out',f%ep%Nbin,f%run%rcut/2.d0,n,f%sPair%sum(:,w),f%sPair%sq(:,w))
+  end subroutine density_write_files
 
   !---------------------------------------------------------------------
   ! fq_tau: imaginary-time density correlations of a periodic system on the S(k) grid, lags 0..fq_ntau between the slices
@@ -982,15 +935,8 @@ contains
     call series_create(f%s,ep%dim*ep%Nk*(f%ntau+1),NW,nvec)
     call count_create(f%cnt,nvec)
     call pigs_check(fqt_init(ctx,int(ep%Nk,c_int32_t),int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_fqt_init')
+    f%accumulate => fqt_accumulate; f%entry = 'pigs_fqt_accumulate'
   end subroutine fqt_setup
-
-  subroutine fqt_queue(f,ctx,nd,wl)
-    class(fqt_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(fqt_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_fqt_accumulate')
-  end subroutine fqt_queue
 
   subroutine fqt_read_block(f,ctx)
     class(fqt_family), intent(inout) :: f
@@ -1017,17 +963,12 @@ contains
     if (nall>0) call series_average(f%s,vec,nall)
   end subroutine fqt_average
 
-  subroutine fqt_write_walker(f,suffix,w,nblocks)
+  subroutine fqt_write_files(f,suffix,w,n)
     class(fqt_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_fqt('fqt_vpi'//trim(suffix)//'.out',f%ep,f%ntau,f%window,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
-  end subroutine fqt_write_walker
-
-  subroutine fqt_write_average(f)
-    class(fqt_family), intent(inout) :: f
-    call write_fqt('fqt_vpi.out',f%ep,f%ntau,f%window,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
-  end subroutine fqt_write_average
+    integer, intent(in)          :: w,n
+    call write_fqt('fqt_vpi'//trim(suffix)//'.out',f%ep,f%ntau,f%window,f%run%dt,n,f%s%sum(:,w),f%s%sq(:,w))
+  end subroutine fqt_write_files
 
   !---------------------------------------------------------------------
   ! sq_vector: the structure factor on the full reciprocal grid of a periodic system, averaged over the slices
@@ -1064,20 +1005,13 @@ contains
     call family_begin(f,run,ep,NW)
     f%window = keys%sq_window
     call pigs_check(sqv_init(ctx,int(keys%sq_nmax,c_int32_t),int(f%window,c_int32_t)),'pigs_sqv_init')
+    f%accumulate => sqv_accumulate; f%entry = 'pigs_sqv_accumulate'
     call qgrid_fill(f%g,ctx,ep,sqv_count,sqv_vectors,'pigs_sqv')
     allocate (f%raw(f%g%nq,NW),f%b(f%g%nq),f%sh(f%g%nsh))
     call series_create(f%sVec,f%g%nq,NW,nvec)
     call series_create(f%sSh,f%g%nsh,NW)
     call count_create(f%cnt,nvec)
   end subroutine sqv_setup
-
-  subroutine sqv_queue(f,ctx,nd,wl)
-    class(sqv_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(sqv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sqv_accumulate')
-  end subroutine sqv_queue
 
   subroutine sqv_read_block(f,ctx)
     class(sqv_family), intent(inout) :: f
@@ -1111,19 +1045,13 @@ contains
     end if
   end subroutine sqv_average
 
-  subroutine sqv_write_walker(f,suffix,w,nblocks)
+  subroutine sqv_write_files(f,suffix,w,n)
     class(sqv_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',f%ep,f%g%nq,f%g%n,nblocks,f%sVec%sum(:,w),f%sVec%sq(:,w))
-    call write_sqshell('sq_vpi'//trim(suffix)//'.out',f%g%nsh,f%g%q,f%g%mult,nblocks,f%sSh%sum(:,w),f%sSh%sq(:,w))
-  end subroutine sqv_write_walker
-
-  subroutine sqv_write_average(f)
-    class(sqv_family), intent(inout) :: f
-    call write_sqvec('sqvec_vpi.out',f%ep,f%g%nq,f%g%n,f%cnt%nav,f%sVec%asum,f%sVec%asq)
-    call write_sqshell('sq_vpi.out',f%g%nsh,f%g%q,f%g%mult,f%cnt%nav,f%sSh%asum,f%sSh%asq)
-  end subroutine sqv_write_average
+    integer, intent(in)          :: w,n
+    call write_sqvec('sqvec_vpi'//trim(suffix)//'.out',f%ep,f%g%nq,f%g%n,n,f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_sqshell('sq_vpi'//trim(suffix)//'.out',f%g%nsh,f%g%q,f%g%mult,n,f%sSh%sum(:,w),f%sSh%sq(:,w))
+  end subroutine sqv_write_files
 
   !---------------------------------------------------------------------
   ! gr_vector: the pair distribution on the Cartesian grid of the minimum-image cell of a periodic system, gr_nbin bins
@@ -1165,20 +1093,13 @@ contains
     f%nbin = keys%gr_nbin; f%window = keys%gr_window
     call pigs_check(grv_init(ctx,int(f%nbin,c_int32_t),int(ep%Nbin,c_int32_t),real(ep%rbin,c_double),int(f%window,c_int32_t)), &
          & 'pigs_grv_init')
+    f%accumulate => grv_accumulate; f%entry = 'pigs_grv_accumulate'
     f%ngb = f%nbin**ep%dim
     allocate (f%vec(f%ngb,NW),f%rad(ep%Nbin,NW),f%bvec(f%ngb),f%brad(ep%Nbin))
     call series_create(f%sVec,f%ngb,NW,nvec)
     call series_create(f%sRad,ep%Nbin,NW,nvec)
     call count_create(f%cnt,nvec)
   end subroutine grv_setup
-
-  subroutine grv_queue(f,ctx,nd,wl)
-    class(grv_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(grv_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_grv_accumulate')
-  end subroutine grv_queue
 
   subroutine grv_read_block(f,ctx)
     class(grv_family), intent(inout) :: f
@@ -1209,19 +1130,13 @@ contains
     end if
   end subroutine grv_average
 
-  subroutine grv_write_walker(f,suffix,w,nblocks)
+  subroutine grv_write_files(f,suffix,w,n)
     class(grv_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_grvec('grvec_vpi'//trim(suffix)//'.out',f%ep,f%nbin,f%ngb,nblocks,f%sVec%sum(:,w),f%sVec%sq(:,w))
-    call write_radial('grw_vpi'//trim(suffix)//'.out',f%ep,nblocks,f%sRad%sum(:,w),f%sRad%sq(:,w))
-  end subroutine grv_write_walker
-
-  subroutine grv_write_average(f)
-    class(grv_family), intent(inout) :: f
-    call write_grvec('grvec_vpi.out',f%ep,f%nbin,f%ngb,f%cnt%nav,f%sVec%asum,f%sVec%asq)
-    call write_radial('grw_vpi.out',f%ep,f%cnt%nav,f%sRad%asum,f%sRad%asq)
-  end subroutine grv_write_average
+    integer, intent(in)          :: w,n
+    call write_grvec('grvec_vpi'//trim(suffix)//'.out',f%ep,f%nbin,f%ngb,n,f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_radial('grw_vpi'//trim(suffix)//'.out',f%ep,n,f%sRad%sum(:,w),f%sRad%sq(:,w))
+  end subroutine grv_write_files
 
   !---------------------------------------------------------------------
   ! fq_vector: F(q,tau_l) on the full reciprocal grid of a periodic system, the vectors of sq_vector with |n_k| <=
@@ -1295,13 +1210,13 @@ contains
     call lagged_keys(f,keys,nmax,f%ntau,f%window)
     if (f%self) then
        call pigs_check(fqs_init(ctx,int(nmax,c_int32_t),int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_fqs_init')
+       f%accumulate => fqs_accumulate; f%entry = 'pigs_fqs_accumulate'
        call qgrid_fill(f%g,ctx,ep,fqs_count,fqs_vectors,'pigs_fqs')
-       f%accumulate => fqs_accumulate
        allocate (f%draw(2,f%ntau+1,NW),f%bm(2,f%ntau+1))
     else
        call pigs_check(fqv_init(ctx,int(nmax,c_int32_t),int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_fqv_init')
+       f%accumulate => fqv_accumulate; f%entry = 'pigs_fqv_accumulate'
        call qgrid_fill(f%g,ctx,ep,fqv_count,fqv_vectors,'pigs_fqv')
-       f%accumulate => fqv_accumulate
     end if
     allocate (f%raw(f%g%nq,f%ntau+1,NW),f%b(f%g%nq,f%ntau+1),f%sh(f%g%nsh,f%ntau+1))
     call series_create(f%sVec,f%g%nq*(f%ntau+1),NW,nvec)
@@ -1309,14 +1224,6 @@ contains
     call series_create(f%sSh,f%g%nsh*(f%ntau+1),NW)
     call count_create(f%cnt,nvec)
   end subroutine lagged_setup
-
-  subroutine lagged_queue(f,ctx,nd,wl)
-    class(lagged_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(f%accumulate(ctx,int(nd,c_int32_t),wl),'pigs_'//f%pre//'_accumulate')
-  end subroutine lagged_queue
 
   subroutine lagged_read_block(f,ctx)
     class(lagged_family), intent(inout) :: f
@@ -1357,21 +1264,14 @@ contains
     end if
   end subroutine lagged_average
 
-  subroutine lagged_write_walker(f,suffix,w,nblocks)
+  subroutine lagged_write_files(f,suffix,w,n)
     class(lagged_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_fqvec(trim(f%fvec)//'_vpi'//trim(suffix)//'.out',f%ep,f%ntau,f%run%dt,f%g%nq,f%g%n,nblocks,f%sVec%sum(:,w),f%sVec%sq(:,w))
-    call write_fqshell(trim(f%fsh)//'_vpi'//trim(suffix)//'.out',f%ntau,f%run%dt,f%g%nsh,f%g%q,f%g%mult,nblocks,f%sSh%sum(:,w),f%sSh%sq(:,w))
-    if (f%self) call write_msd('msd_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,nblocks,f%sMsd%sum(:,w),f%sMsd%sq(:,w))
-  end subroutine lagged_write_walker
-
-  subroutine lagged_write_average(f)
-    class(lagged_family), intent(inout) :: f
-    call write_fqvec(trim(f%fvec)//'_vpi.out',f%ep,f%ntau,f%run%dt,f%g%nq,f%g%n,f%cnt%nav,f%sVec%asum,f%sVec%asq)
-    call write_fqshell(trim(f%fsh)//'_vpi.out',f%ntau,f%run%dt,f%g%nsh,f%g%q,f%g%mult,f%cnt%nav,f%sSh%asum,f%sSh%asq)
-    if (f%self) call write_msd('msd_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%sMsd%asum,f%sMsd%asq)
-  end subroutine lagged_write_average
+    integer, intent(in)          :: w,n
+    call write_fqvec(trim(f%fvec)//'_vpi'//trim(suffix)//'.out',f%ep,f%ntau,f%run%dt,f%g%nq,f%g%n,n,f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_fqshell(trim(f%fsh)//'_vpi'//trim(suffix)//'.out',f%ntau,f%run%dt,f%g%nsh,f%g%q,f%g%mult,n,f%sSh%sum(:,w),f%sSh%sq(:,w))
+    if (f%self) call write_msd('msd_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,n,f%sMsd%sum(:,w),f%sMsd%sq(:,w))
+  end subroutine lagged_write_files
 
   !---------------------------------------------------------------------
   ! tau_profile: the imaginary-time profiles of every slice b = 0..2Nb of a periodic or trapped system -- tau_vpi.out.
@@ -1414,26 +1314,19 @@ contains
     call series_create(f%s,4*(2*run%Nb+1),NW,nvec)
     call count_create(f%cnt,nvec)
     call pigs_check(tau_init(ctx),'pigs_tau_init')
+    f%accumulate => tau_accumulate; f%entry = 'pigs_tau_accumulate'
     if (.not. ep%trap) then
-       allocate (f%up(NW))
+       allocate (f%up(0:NW))
        do w=1,NW
           open (newunit=f%up(w),file='press_vpi'//trim(run%suffix(w))//'.out')
           call press_header(f%up(w),f%window)
        end do
        if (run%averages) then
-          open (newunit=f%upav,file='press_vpi.out')
-          call press_header(f%upav,f%window)
+          open (newunit=f%up(0),file='press_vpi.out')
+          call press_header(f%up(0),f%window)
        end if
     end if
   end subroutine tau_setup
-
-  subroutine tau_queue(f,ctx,nd,wl)
-    class(tau_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(tau_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_tau_accumulate')
-  end subroutine tau_queue
 
   subroutine tau_read_block(f,ctx)
     class(tau_family), intent(inout) :: f
@@ -1468,24 +1361,18 @@ contains
        call series_average(f%s,vec,nall)
        if (.not. f%ep%trap .and. info%ndall>0) then
           wwin = virial_window(f%run%Nb,f%window,f%s%mean)
-          write (f%upav,'(20g20.10e3)') real(info%iblock),wwin,info%kin,f%run%density/real(f%ep%dim,8)*(2.d0*(info%kin)-wwin)
+          write (f%up(0),'(20g20.10e3)') real(info%iblock),wwin,info%kin,f%run%density/real(f%ep%dim,8)*(2.d0*(info%kin)-wwin)
        end if
     end if
   end subroutine tau_average
 
-  subroutine tau_write_walker(f,suffix,w,nblocks)
+  subroutine tau_write_files(f,suffix,w,n)
     class(tau_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_tau('tau_vpi'//trim(suffix)//'.out',f%run%Nb,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+    integer, intent(in)          :: w,n
+    call write_tau('tau_vpi'//trim(suffix)//'.out',f%run%Nb,f%run%dt,n,f%s%sum(:,w),f%s%sq(:,w))
     if (.not. f%ep%trap) close (f%up(w))
-  end subroutine tau_write_walker
-
-  subroutine tau_write_average(f)
-    class(tau_family), intent(inout) :: f
-    call write_tau('tau_vpi.out',f%run%Nb,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
-    if (.not. f%ep%trap) close (f%upav)
-  end subroutine tau_write_average
+  end subroutine tau_write_files
 
   !---------------------------------------------------------------------
   ! bond_order: the bond-orientational order of a periodic system in 2D or 3D over the slices Nb-bo_window..Nb+bo_window,
@@ -1550,15 +1437,8 @@ contains
     call count_create(f%cnt,nvec)
     call pigs_check(bop_init(ctx,real(f%rnb,c_double),int(f%window,c_int32_t),int(f%nh,c_int32_t),int(f%nr,c_int32_t), &
          & real(f%epr%rbin,c_double)),'pigs_bop_init')
+    f%accumulate => bop_accumulate; f%entry = 'pigs_bop_accumulate'
   end subroutine bop_setup
-
-  subroutine bop_queue(f,ctx,nd,wl)
-    class(bop_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(bop_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_bop_accumulate')
-  end subroutine bop_queue
 
   subroutine bop_read_block(f,ctx)
     class(bop_family), intent(inout) :: f
@@ -1592,21 +1472,14 @@ contains
     end if
   end subroutine bop_average
 
-  subroutine bop_write_walker(f,suffix,w,nblocks)
+  subroutine bop_write_files(f,suffix,w,n)
     class(bop_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_bo('bo_vpi'//trim(suffix)//'.out',nblocks,f%sB%sum(:,w),f%sB%sq(:,w))
-    call write_boh('boh_vpi'//trim(suffix)//'.out',f%nh,nblocks,f%sH%sum(:,w),f%sH%sq(:,w))
-    call write_radial('g6_vpi'//trim(suffix)//'.out',f%epr,nblocks,f%sG%sum(:,w),f%sG%sq(:,w))
-  end subroutine bop_write_walker
-
-  subroutine bop_write_average(f)
-    class(bop_family), intent(inout) :: f
-    call write_bo('bo_vpi.out',f%cnt%nav,f%sB%asum,f%sB%asq)
-    call write_boh('boh_vpi.out',f%nh,f%cnt%nav,f%sH%asum,f%sH%asq)
-    call write_radial('g6_vpi.out',f%epr,f%cnt%nav,f%sG%asum,f%sG%asq)
-  end subroutine bop_write_average
+    integer, intent(in)          :: w,n
+    call write_bo('bo_vpi'//trim(suffix)//'.out',n,f%sB%sum(:,w),f%sB%sq(:,w))
+    call write_boh('boh_vpi'//trim(suffix)//'.out',f%nh,n,f%sH%sum(:,w),f%sH%sq(:,w))
+    call write_radial('g6_vpi'//trim(suffix)//'.out',f%epr,n,f%sG%sum(:,w),f%sG%sq(:,w))
+  end subroutine bop_write_files
 
   !---------------------------------------------------------------------
   ! van_hove: the van Hove functions of a periodic system for the lags 0..vh_ntau between the slices
@@ -1654,19 +1527,12 @@ contains
     f%eps%rbin = merge(keys%vh_rself,run%rcut,keys%vh_rself>0.d0)/real(f%ns,8)
     call pigs_check(vh_init(ctx,int(f%ntau,c_int32_t),int(f%window,c_int32_t),int(ep%Nbin,c_int32_t),real(ep%rbin,c_double), &
          & int(f%ns,c_int32_t),real(f%eps%rbin,c_double)),'pigs_vh_init')
+    f%accumulate => vh_accumulate; f%entry = 'pigs_vh_accumulate'
     allocate (f%cself(f%ns,0:f%ntau,NW),f%cdist(ep%Nbin,0:f%ntau,NW),f%bs(f%ns,0:f%ntau),f%bd(ep%Nbin,0:f%ntau))
     call series_create(f%sS,f%ns*(f%ntau+1),NW,nvec)
     call series_create(f%sD,ep%Nbin*(f%ntau+1),NW,nvec)
     call count_create(f%cnt,nvec)
   end subroutine vh_setup
-
-  subroutine vh_queue(f,ctx,nd,wl)
-    class(vh_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(vh_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_vh_accumulate')
-  end subroutine vh_queue
 
   subroutine vh_read_block(f,ctx)
     class(vh_family), intent(inout) :: f
@@ -1697,19 +1563,13 @@ contains
     end if
   end subroutine vh_average
 
-  subroutine vh_write_walker(f,suffix,w,nblocks)
+  subroutine vh_write_files(f,suffix,w,n)
     class(vh_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_vh('gd_vpi'//trim(suffix)//'.out',f%ep,f%run%dt,f%ntau,nblocks,f%sD%sum(:,w),f%sD%sq(:,w))
-    call write_vh('gs_vpi'//trim(suffix)//'.out',f%eps,f%run%dt,f%ntau,nblocks,f%sS%sum(:,w),f%sS%sq(:,w))
-  end subroutine vh_write_walker
-
-  subroutine vh_write_average(f)
-    class(vh_family), intent(inout) :: f
-    call write_vh('gd_vpi.out',f%ep,f%run%dt,f%ntau,f%cnt%nav,f%sD%asum,f%sD%asq)
-    call write_vh('gs_vpi.out',f%eps,f%run%dt,f%ntau,f%cnt%nav,f%sS%asum,f%sS%asq)
-  end subroutine vh_write_average
+    integer, intent(in)          :: w,n
+    call write_vh('gd_vpi'//trim(suffix)//'.out',f%ep,f%run%dt,f%ntau,n,f%sD%sum(:,w),f%sD%sq(:,w))
+    call write_vh('gs_vpi'//trim(suffix)//'.out',f%eps,f%run%dt,f%ntau,n,f%sS%sum(:,w),f%sS%sq(:,w))
+  end subroutine vh_write_files
 
   !---------------------------------------------------------------------
   ! triplet: the triplet distribution of a periodic system in 2D or 3D over the slices Nb-g3_window..Nb+g3_window, legs
@@ -1769,19 +1629,12 @@ contains
     f%npk = keys%g3_nr*(keys%g3_nr+1)/2
     call pigs_check(g3_init(ctx,int(f%epr%Nbin,c_int32_t),real(f%epr%rbin,c_double),int(f%na,c_int32_t),int(f%window,c_int32_t)), &
          & 'pigs_g3_init')
+    f%accumulate => g3_accumulate; f%entry = 'pigs_g3_accumulate'
     allocate (f%ctrip(f%na,f%npk,NW),f%cpair(f%epr%Nbin,NW),f%b2(f%epr%Nbin),f%b3(f%na,f%npk),f%ba(f%na))
     call series_create(f%s3,f%na*f%npk,NW,nvec)
     call series_create(f%sA,f%na,NW,nvec)
     call count_create(f%cnt,nvec)
   end subroutine g3_setup
-
-  subroutine g3_queue(f,ctx,nd,wl)
-    class(g3_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(g3_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_g3_accumulate')
-  end subroutine g3_queue
 
   subroutine g3_read_block(f,ctx)
     class(g3_family), intent(inout) :: f
@@ -1812,19 +1665,13 @@ contains
     end if
   end subroutine g3_average
 
-  subroutine g3_write_walker(f,suffix,w,nblocks)
+  subroutine g3_write_files(f,suffix,w,n)
     class(g3_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_g3('g3_vpi'//trim(suffix)//'.out',f%epr,f%na,nblocks,f%s3%sum(:,w),f%s3%sq(:,w))
-    call write_g3ang('g3ang_vpi'//trim(suffix)//'.out',f%na,nblocks,f%sA%sum(:,w),f%sA%sq(:,w))
-  end subroutine g3_write_walker
-
-  subroutine g3_write_average(f)
-    class(g3_family), intent(inout) :: f
-    call write_g3('g3_vpi.out',f%epr,f%na,f%cnt%nav,f%s3%asum,f%s3%asq)
-    call write_g3ang('g3ang_vpi.out',f%na,f%cnt%nav,f%sA%asum,f%sA%asq)
-  end subroutine g3_write_average
+    integer, intent(in)          :: w,n
+    call write_g3('g3_vpi'//trim(suffix)//'.out',f%epr,f%na,n,f%s3%sum(:,w),f%s3%sq(:,w))
+    call write_g3ang('g3ang_vpi'//trim(suffix)//'.out',f%na,n,f%sA%sum(:,w),f%sA%sq(:,w))
+  end subroutine g3_write_files
 
   !---------------------------------------------------------------------
   ! three_body: the Axilrod-Teller-Muto (triple-dipole) energy of a periodic system in 2D or 3D, evaluated on the sampled
@@ -1884,24 +1731,17 @@ contains
     call series_create(f%s,2*ns,NW,nvec)
     call count_create(f%cnt,nvec)
     call pigs_check(atm_init(ctx,real(f%rc,c_double),int(f%window,c_int32_t)),'pigs_atm_init')
-    allocate (f%up(NW))
+    f%accumulate => atm_accumulate; f%entry = 'pigs_atm_accumulate'
+    allocate (f%up(0:NW))
     do w=1,NW
        open (newunit=f%up(w),file='v3_vpi'//trim(run%suffix(w))//'.out')
        call v3_header(f%up(w),f%window)
     end do
     if (run%averages) then
-       open (newunit=f%upav,file='v3_vpi.out')
-       call v3_header(f%upav,f%window)
+       open (newunit=f%up(0),file='v3_vpi.out')
+       call v3_header(f%up(0),f%window)
     end if
   end subroutine atm_setup
-
-  subroutine atm_queue(f,ctx,nd,wl)
-    class(atm_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(atm_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_atm_accumulate')
-  end subroutine atm_queue
 
   subroutine atm_read_block(f,ctx)
     class(atm_family), intent(inout) :: f
@@ -1928,23 +1768,17 @@ contains
     nall = count_reduced(f%cnt,vec)
     if (nall>0) then
        call series_average(f%s,vec,nall)
-       if (info%ndall>0) call write_v3_block(f%upav,info%iblock,f%ep%dim,f%run%density,atm_window_mean(f%window,f%s%mean))
+       if (info%ndall>0) call write_v3_block(f%up(0),info%iblock,f%ep%dim,f%run%density,atm_window_mean(f%window,f%s%mean))
     end if
   end subroutine atm_average
 
-  subroutine atm_write_walker(f,suffix,w,nblocks)
+  subroutine atm_write_files(f,suffix,w,n)
     class(atm_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_v3tau('v3tau_vpi'//trim(suffix)//'.out',f%run%Nb,f%window,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+    integer, intent(in)          :: w,n
+    call write_v3tau('v3tau_vpi'//trim(suffix)//'.out',f%run%Nb,f%window,f%run%dt,n,f%s%sum(:,w),f%s%sq(:,w))
     close (f%up(w))
-  end subroutine atm_write_walker
-
-  subroutine atm_write_average(f)
-    class(atm_family), intent(inout) :: f
-    call write_v3tau('v3tau_vpi.out',f%run%Nb,f%window,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
-    close (f%upav)
-  end subroutine atm_write_average
+  end subroutine atm_write_files
 
   !---------------------------------------------------------------------
   ! momentum: the momentum distribution n(k) of a periodic system with the worm sector on, on the box-commensurate vectors
@@ -1996,7 +1830,7 @@ contains
     f%nv = f%nbin**ep%dim
     call pigs_check(nk_init(ctx,int(keys%nk_nmax,c_int32_t),int(f%nbin,c_int32_t)),'pigs_nk_init')
     call qgrid_fill(f%g,ctx,ep,nk_count,nk_vectors,'pigs_nk')
-    allocate (f%raw(f%g%nq,NW),f%h(f%nv,NW),f%nopen(NW),f%nin(NW),f%b(f%g%nq+1),f%sh(f%g%nsh),f%br(f%nv),f%nbl(NW),f%un(NW))
+    allocate (f%raw(f%g%nq,NW),f%h(f%nv,NW),f%nopen(NW),f%nin(NW),f%b(f%g%nq+1),f%sh(f%g%nsh),f%br(f%nv),f%nbl(NW),f%un(0:NW))
     f%nbl = 0
     call series_create(f%sVec,f%g%nq+1,NW,nvec)
     call series_create(f%sSh,f%g%nsh,NW)
@@ -2007,8 +1841,8 @@ contains
        call n0_header(f%un(w))
     end do
     if (run%averages) then
-       open (newunit=f%unav,file='n0_vpi.out')
-       call n0_header(f%unav)
+       open (newunit=f%un(0),file='n0_vpi.out')
+       call n0_header(f%un(0))
     end if
   end subroutine nk_setup
 
@@ -2046,27 +1880,23 @@ contains
        call series_average(f%sR,vec,nall)
        call sqv_shell_means(f%g%nq,f%g%shell,f%g%nsh,f%g%mult,f%sVec%mean(2:),f%sh)
        call series_add_mean(f%sSh,f%sh)
-       call write_n0_block(f%unav,info%iblock,f%ep%Np,f%sVec%mean(1))
+       call write_n0_block(f%un(0),info%iblock,f%ep%Np,f%sVec%mean(1))
     end if
   end subroutine nk_average
 
-  subroutine nk_write_walker(f,suffix,w,nblocks)
+  subroutine nk_write_files(f,suffix,w,n)
     class(nk_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_nkvec('nkvec_vpi'//trim(suffix)//'.out',f%ep,f%g%nq,f%g%n,f%nbl(w),f%sVec%sum(:,w),f%sVec%sq(:,w))
-    call write_sqshell('nk_vpi'//trim(suffix)//'.out',f%g%nsh,f%g%q,f%g%mult,f%nbl(w),f%sSh%sum(:,w),f%sSh%sq(:,w))
-    call write_grvec('nrvec_vpi'//trim(suffix)//'.out',f%ep,f%nbin,f%nv,f%nbl(w),f%sR%sum(:,w),f%sR%sq(:,w))
+    integer, intent(in)          :: w,n
+    integer :: nb
+    ! a walker's n are the blocks it counted as diagonal: its files here average over those it normalised (set_nk_block)
+    nb = n
+    if (w>0) nb = f%nbl(w)
+    call write_nkvec('nkvec_vpi'//trim(suffix)//'.out',f%ep,f%g%nq,f%g%n,nb,f%sVec%sum(:,w),f%sVec%sq(:,w))
+    call write_sqshell('nk_vpi'//trim(suffix)//'.out',f%g%nsh,f%g%q,f%g%mult,nb,f%sSh%sum(:,w),f%sSh%sq(:,w))
+    call write_grvec('nrvec_vpi'//trim(suffix)//'.out',f%ep,f%nbin,f%nv,nb,f%sR%sum(:,w),f%sR%sq(:,w))
     close (f%un(w))
-  end subroutine nk_write_walker
-
-  subroutine nk_write_average(f)
-    class(nk_family), intent(inout) :: f
-    call write_nkvec('nkvec_vpi.out',f%ep,f%g%nq,f%g%n,f%cnt%nav,f%sVec%asum,f%sVec%asq)
-    call write_sqshell('nk_vpi.out',f%g%nsh,f%g%q,f%g%mult,f%cnt%nav,f%sSh%asum,f%sSh%asq)
-    call write_grvec('nrvec_vpi.out',f%ep,f%nbin,f%nv,f%cnt%nav,f%sR%asum,f%sR%asq)
-    close (f%unav)
-  end subroutine nk_write_average
+  end subroutine nk_write_files
 
   !---------------------------------------------------------------------
   ! lattice: a crystal seen from the lattice of config_ini.in, over the slices Nb-lat_window..Nb+lat_window of a periodic
@@ -2152,24 +1982,17 @@ contains
     call count_create(f%cnt,nvec)
     call pigs_check(lat_init(ctx,int(f%nsite,c_int32_t),keys%lat_sites,int(f%nbin,c_int32_t),real(f%rmax,c_double), &
          & int(f%window,c_int32_t),int(merge(1,0,keys%lat_cm),c_int32_t)),'pigs_lat_init')
-    allocate (f%up(NW))
+    f%accumulate => lat_accumulate; f%entry = 'pigs_lat_accumulate'
+    allocate (f%up(0:NW))
     do w=1,NW
        open (newunit=f%up(w),file='lind_vpi'//trim(run%suffix(w))//'.out')
        call lind_header(f%up(w),f%window)
     end do
     if (run%averages) then
-       open (newunit=f%upav,file='lind_vpi.out')
-       call lind_header(f%upav,f%window)
+       open (newunit=f%up(0),file='lind_vpi.out')
+       call lind_header(f%up(0),f%window)
     end if
   end subroutine lat_setup
-
-  subroutine lat_queue(f,ctx,nd,wl)
-    class(lat_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(lat_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_lat_accumulate')
-  end subroutine lat_queue
 
   subroutine lat_read_block(f,ctx)
     class(lat_family), intent(inout) :: f
@@ -2202,25 +2025,18 @@ contains
        call series_average(f%sL,vec,nall)
        call series_average(f%sT,vec,nall)
        call series_average(f%sU,vec,nall)
-       if (info%ndall>0) call write_lind_block(f%upav,info%iblock,f%sL%mean)
+       if (info%ndall>0) call write_lind_block(f%up(0),info%iblock,f%sL%mean)
     end if
   end subroutine lat_average
 
-  subroutine lat_write_walker(f,suffix,w,nblocks)
+  subroutine lat_write_files(f,suffix,w,n)
     class(lat_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_lindtau('lindtau_vpi'//trim(suffix)//'.out',f%ep%dim,f%window,f%run%dt,nblocks,f%sT%sum(:,w))
-    call write_usite('usite_vpi'//trim(suffix)//'.out',f%ep%dim,f%nbin,f%rmax,nblocks,f%sU%sum(:,w))
+    integer, intent(in)          :: w,n
+    call write_lindtau('lindtau_vpi'//trim(suffix)//'.out',f%ep%dim,f%window,f%run%dt,n,f%sT%sum(:,w))
+    call write_usite('usite_vpi'//trim(suffix)//'.out',f%ep%dim,f%nbin,f%rmax,n,f%sU%sum(:,w))
     close (f%up(w))
-  end subroutine lat_write_walker
-
-  subroutine lat_write_average(f)
-    class(lat_family), intent(inout) :: f
-    call write_lindtau('lindtau_vpi.out',f%ep%dim,f%window,f%run%dt,f%cnt%nav,f%sT%asum)
-    call write_usite('usite_vpi.out',f%ep%dim,f%nbin,f%rmax,f%cnt%nav,f%sU%asum)
-    close (f%upav)
-  end subroutine lat_write_average
+  end subroutine lat_write_files
 
   !---------------------------------------------------------------------
   ! superfluid: the diffusion of the centre of mass along imaginary time over the slices Nb-sf_window..Nb+sf_window of a
@@ -2264,15 +2080,8 @@ contains
     call series_create(f%s,sf_columns(ep%dim)*(f%ntau+1),NW,nvec)
     call count_create(f%cnt,nvec)
     call pigs_check(sf_init(ctx,int(f%ntau,c_int32_t),int(f%window,c_int32_t)),'pigs_sf_init')
+    f%accumulate => sf_accumulate; f%entry = 'pigs_sf_accumulate'
   end subroutine sf_setup
-
-  subroutine sf_queue(f,ctx,nd,wl)
-    class(sf_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(sf_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_sf_accumulate')
-  end subroutine sf_queue
 
   subroutine sf_read_block(f,ctx)
     class(sf_family), intent(inout) :: f
@@ -2299,19 +2108,13 @@ contains
     if (nall>0) call series_average(f%s,vec,nall)
   end subroutine sf_average
 
-  subroutine sf_write_walker(f,suffix,w,nblocks)
+  subroutine sf_write_files(f,suffix,w,n)
     class(sf_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_rhos('rhos_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
-    call write_msdu('msdu_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,nblocks,f%s%sum(:,w),f%s%sq(:,w))
-  end subroutine sf_write_walker
-
-  subroutine sf_write_average(f)
-    class(sf_family), intent(inout) :: f
-    call write_rhos('rhos_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
-    call write_msdu('msdu_vpi.out',f%ep%dim,f%ntau,f%run%dt,f%cnt%nav,f%s%asum,f%s%asq)
-  end subroutine sf_write_average
+    integer, intent(in)          :: w,n
+    call write_rhos('rhos_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,n,f%s%sum(:,w),f%s%sq(:,w))
+    call write_msdu('msdu_vpi'//trim(suffix)//'.out',f%ep%dim,f%ntau,f%run%dt,n,f%s%sum(:,w),f%s%sq(:,w))
+  end subroutine sf_write_files
 
   !---------------------------------------------------------------------
   ! clusters: the connected components of the bond graph r < cl_rc over the slices Nb-cl_window..Nb+cl_window of a periodic
@@ -2364,24 +2167,17 @@ contains
     call series_create(f%sb,4,NW,nvec)
     call count_create(f%cnt,nvec)
     call pigs_check(cl_init(ctx,real(f%rc,c_double),int(f%window,c_int32_t)),'pigs_cl_init')
-    allocate (f%up(NW))
+    f%accumulate => cl_accumulate; f%entry = 'pigs_cl_accumulate'
+    allocate (f%up(0:NW))
     do w=1,NW
        open (newunit=f%up(w),file='clusblk_vpi'//trim(run%suffix(w))//'.out')
        call clus_header(f%up(w),f%rc,f%window)
     end do
     if (run%averages) then
-       open (newunit=f%upav,file='clusblk_vpi.out')
-       call clus_header(f%upav,f%rc,f%window)
+       open (newunit=f%up(0),file='clusblk_vpi.out')
+       call clus_header(f%up(0),f%rc,f%window)
     end if
   end subroutine cl_setup
-
-  subroutine cl_queue(f,ctx,nd,wl)
-    class(cl_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(cl_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_cl_accumulate')
-  end subroutine cl_queue
 
   subroutine cl_read_block(f,ctx)
     class(cl_family), intent(inout) :: f
@@ -2410,23 +2206,17 @@ contains
     if (nall>0) then
        call series_average(f%s,vec,nall)
        call series_average(f%sb,vec,nall)
-       if (info%ndall>0) call write_clus_block(f%upav,info%iblock,f%sb%mean)
+       if (info%ndall>0) call write_clus_block(f%up(0),info%iblock,f%sb%mean)
     end if
   end subroutine cl_average
 
-  subroutine cl_write_walker(f,suffix,w,nblocks)
+  subroutine cl_write_files(f,suffix,w,n)
     class(cl_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_clus('clus_vpi'//trim(suffix)//'.out',f%ep%Np,nblocks,f%s%sum(:,w),f%s%sq(:,w))
+    integer, intent(in)          :: w,n
+    call write_clus('clus_vpi'//trim(suffix)//'.out',f%ep%Np,n,f%s%sum(:,w),f%s%sq(:,w))
     close (f%up(w))
-  end subroutine cl_write_walker
-
-  subroutine cl_write_average(f)
-    class(cl_family), intent(inout) :: f
-    call write_clus('clus_vpi.out',f%ep%Np,f%cnt%nav,f%s%asum,f%s%asq)
-    close (f%upav)
-  end subroutine cl_write_average
+  end subroutine cl_write_files
 
   !---------------------------------------------------------------------
   ! percolation: which clusters of the bond graph r < pc_rc wrap the periodic box, the finite ones with their unfolded
@@ -2481,24 +2271,17 @@ contains
     call series_create(f%sb,7,NW,nvec)
     call count_create(f%cnt,nvec)
     call pigs_check(pc_init(ctx,real(f%rc,c_double),int(f%window,c_int32_t),int(f%ntau,c_int32_t)),'pigs_pc_init')
-    allocate (f%up(NW))
+    f%accumulate => pc_accumulate; f%entry = 'pigs_pc_accumulate'
+    allocate (f%up(0:NW))
     do w=1,NW
        open (newunit=f%up(w),file='perc_vpi'//trim(run%suffix(w))//'.out')
        call perc_header(f%up(w),f%rc,f%window)
     end do
     if (run%averages) then
-       open (newunit=f%upav,file='perc_vpi.out')
-       call perc_header(f%upav,f%rc,f%window)
+       open (newunit=f%up(0),file='perc_vpi.out')
+       call perc_header(f%up(0),f%rc,f%window)
     end if
   end subroutine pc_setup
-
-  subroutine pc_queue(f,ctx,nd,wl)
-    class(pc_family), intent(inout) :: f
-    type(c_ptr), intent(in) :: ctx
-    integer, intent(in)     :: nd
-    integer(c_int32_t), intent(in) :: wl(:)
-    call pigs_check(pc_accumulate(ctx,int(nd,c_int32_t),wl),'pigs_pc_accumulate')
-  end subroutine pc_queue
 
   subroutine pc_read_block(f,ctx)
     class(pc_family), intent(inout) :: f
@@ -2532,24 +2315,17 @@ contains
        call series_average(f%ss,vec,nall)
        call series_average(f%sp,vec,nall)
        call series_average(f%sb,vec,nall)
-       if (info%ndall>0) call write_perc_block(f%upav,info%iblock,f%sb%mean)
+       if (info%ndall>0) call write_perc_block(f%up(0),info%iblock,f%sb%mean)
     end if
   end subroutine pc_average
 
-  subroutine pc_write_walker(f,suffix,w,nblocks)
+  subroutine pc_write_files(f,suffix,w,n)
     class(pc_family), intent(inout) :: f
     character(len=*), intent(in) :: suffix
-    integer, intent(in)          :: w,nblocks
-    call write_percsz('percsz_vpi'//trim(suffix)//'.out',f%ep%Np,nblocks,f%ss%sum(:,w),f%ss%sq(:,w))
-    call write_clpers('clpers_vpi'//trim(suffix)//'.out',f%ntau,f%run%dt,nblocks,f%sp%sum(:,w),f%sp%sq(:,w))
+    integer, intent(in)          :: w,n
+    call write_percsz('percsz_vpi'//trim(suffix)//'.out',f%ep%Np,n,f%ss%sum(:,w),f%ss%sq(:,w))
+    call write_clpers('clpers_vpi'//trim(suffix)//'.out',f%ntau,f%run%dt,n,f%sp%sum(:,w),f%sp%sq(:,w))
     close (f%up(w))
-  end subroutine pc_write_walker
-
-  subroutine pc_write_average(f)
-    class(pc_family), intent(inout) :: f
-    call write_percsz('percsz_vpi.out',f%ep%Np,f%cnt%nav,f%ss%asum,f%ss%asq)
-    call write_clpers('clpers_vpi.out',f%ntau,f%run%dt,f%cnt%nav,f%sp%asum,f%sp%asq)
-    close (f%upav)
-  end subroutine pc_write_average
+  end subroutine pc_write_files
 
 end module pigs_families

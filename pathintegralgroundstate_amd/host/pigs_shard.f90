@@ -269,7 +269,8 @@ contains
   end subroutine core_average
 
   ! the files of walker w (local index), which counted diag_bl diagonal and obdm_bl OBDM blocks: written unconditionally,
-  ! like the reference (a run without a single diagonal / OBDM block yields NaN columns there too)
+  ! like the reference (a run without a single diagonal / OBDM block yields NaN columns there too).  w = 0, suffix = '':
+  ! the walker-averaged ones
   subroutine core_write_walker(c,suffix,w,diag_bl,obdm_bl)
     class(core_stats), intent(inout) :: c
     character(len=*), intent(in) :: suffix
@@ -283,10 +284,7 @@ contains
   ! the walker-averaged histograms, from the reduced block vectors
   subroutine core_write_average(c)
     class(core_stats), intent(inout) :: c
-    if (.not. c%on) return
-    call write_radial('gr_vpi.out',c%ep,c%cGr%nav,c%sGr%asum,c%sGr%asq)
-    call write_sk('sk_vpi.out',c%ep,c%cGr%nav,c%sSk%asum,c%sSk%asq)
-    call write_nr('nr_vpi.out',c%ep,c%cNr%nav,c%sNr%asum,c%sNr%asq)
+    call c%write_walker('',0,c%cGr%nav,c%cNr%nav)
   end subroutine core_write_average
 
 end module pigs_shard
